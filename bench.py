@@ -15,8 +15,13 @@ BASELINE.json configs[1]: TransE_l2, n_ent 14951, n_rel 1345, batch 1000, neg 20
 Extra objects on the JSON line:
   roofline     - algorithmic HBM bytes of one step (12*(R_e*D_e+R_r*D_r)+16*(R_e+R_r))
                  divided by the average step duration measured with HIP events on the launch stream
-  cpu_baseline - the CPU oracle port (oracle/torch_port.py, the reference's torch ops on the host
+  cpu_baseline - (--full) the CPU oracle port (oracle/torch_port.py, the reference's torch ops on the host
                  cores) timed on a bounded sample of the same workload (rank 0, N=1 only)
+
+A plain N=1 run sets up, warms up, times the K steps and prints the line.  --full adds every other
+measurement of the line (CPU baseline, Hogwild / --async_update / heavy-tailed / 3-launch legs, the other
+BASELINE configs, time-to-MRR, the ranking evaluation).  --dump-outputs DIR writes what the timed steps
+computed (dump_outputs) for output-for-output comparisons of two builds: the inputs are seeded.
 """
 import argparse
 import json
@@ -171,6 +176,46 @@ def step_kernels(model, force_pairwise=False):
             "written by the GA tiles' epilogue, update); dominant: neg_bwd_gemm_kernel")
 
 
+def hogwild_procs():
+    """trainer processes of the CPU baseline's --num_proc leg: the host cores this run may use (its affinity mask, narrowed by
+    OMP_NUM_THREADS when that is set - os.cpu_count() counts every core of a shared host), at most 12: every trainer opens the GPU
+    (torch's HIP runtime), and with this process that keeps the processes holding it well below 16."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 2)
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS") or n))
+    except ValueError:
+        pass
+    return max(2, min(12, n))
+
+
+DUMP_BUDGET = 64 << 20          # bytes --dump-outputs may write in all
+
+
+def dump_outputs(out_dir, eng, loss_sums):
+    """--dump-outputs DIR: what the timed steps hand their caller - the embedding tables and their Adagrad state as the last
+    timed step left them (TransR: its projection table too) and the four loss terms [pos, neg, loss, reg] summed over the
+    timed steps - as DIR/<name>.npy (tables float32, sums float64).  When the tables exceed the budget, every table is
+    written as the same fixed share of its rows (seed 0), with the sampled row ids beside it (<prefix>_rows.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    groups = [("entity", eng.ent, eng.ent_state), ("relation", eng.rel, eng.rel_state)]
+    if eng.proj is not None:
+        groups.append(("projection", eng.proj, eng.proj_state))
+    slack = 1 << 20                                             # the loss sums and the .npy headers
+    full = sum(emb.shape[0] * (emb.shape[1] + 1) * 4 for _, emb, _ in groups)
+    frac = 1.0 if full <= DUMP_BUDGET - slack else \
+        (DUMP_BUDGET - slack) / float(full + sum(8 * emb.shape[0] for _, emb, _ in groups))
+    for prefix, emb, state in groups:
+        n = emb.shape[0]
+        if frac < 1.0:
+            rows = np.sort(np.random.RandomState(0).choice(n, max(1, int(n * frac)), replace=False))
+            idx = torch.from_numpy(rows).to(emb.device)
+            emb, state = emb.index_select(0, idx), state.index_select(0, idx)
+            np.save(os.path.join(out_dir, prefix + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, prefix + "_emb.npy"), emb.float().cpu().numpy())
+        np.save(os.path.join(out_dir, prefix + "_state.npy"), state.float().cpu().numpy())
+    np.save(os.path.join(out_dir, "loss_sums.npy"), np.asarray(loss_sums[:4], dtype=np.float64))
+
+
 def cpu_baseline(w, plans, budget_s=12.0, max_steps=200):
     """the CPU baseline on this host's cores: the REFERENCE ITSELF when oracle/make_ref.py staged its hot-path files into
     oracle/_ref at build() time (`kind: "reference"`: dglke.train_pytorch.train() on the unmodified files, DGL stubbed), else the
@@ -207,7 +252,7 @@ def cpu_baseline_reference(w, plans, budget_s=12.0):
            "ms_per_step": round(1e3 * w["B"] / one["value"], 3), "edges_per_s_by_threads": one["edges_per_s_by_threads"],
            "single_process": {"value": one["value"], "threads": one["threads"]}}
     try:
-        procs = max(2, min(64, (os.cpu_count() or 2)))
+        procs = hogwild_procs()
         hv, hsteps, hwall = RB.hogwild(w, procs, seconds=5.0, rate_1=one["edges_per_s_by_threads"].get(1))
         out["num_proc"] = {"value": round(hv, 1), "procs": procs, "steps": hsteps, "seconds": round(hwall, 2),
                            "semantics": "P single-thread trainer processes on one shared-memory KEModel (reference --num_proc P)"}
@@ -269,7 +314,7 @@ def cpu_baseline_port(w, plans, budget_s=12.0, max_steps=200):
     # the reference's own way to use a many-core host: --num_proc P single-thread trainer processes, lock-free on
     # one shared-memory table (train.py:298-317).  `value` is the better of the two configurations.
     try:
-        procs = max(2, min(64, (os.cpu_count() or 2)))
+        procs = hogwild_procs()
         hv, hsteps = torch_port.hogwild_cpu(w, procs, seconds=5.0)
         out["num_proc"] = {"value": round(hv, 1), "procs": procs, "steps": hsteps, "seconds": 5.0,
                            "semantics": "P single-thread processes, Hogwild on shared-memory tables (reference --num_proc P)"}
@@ -600,7 +645,7 @@ def main():
                          "concurrent modes make the steps 3.5 us slower each on ROCm 7.0 (profiles/r03_merged_fwd.txt)")
     ap.add_argument("--hogwild", type=int, default=4, help="also measure K concurrent Hogwild trainers (0 = skip)")
     ap.add_argument("--no-configs", dest="configs", action="store_false",
-                    help="skip the bounded legs of BASELINE configs[2..4] (the `configs` object of the default line)")
+                    help="skip the bounded legs of BASELINE configs[2..4] (the `configs` object of the --full line)")
     ap.add_argument("--no-time-to-mrr", dest="time_to_mrr", action="store_false",
                     help="skip the bounded time-to-MRR@0.65 leg (dglke_train on real FB15k when supplied, else on the planted graph)")
     ap.add_argument("--min-untimed", type=int, default=120,
@@ -609,7 +654,15 @@ def main():
                          "profiles/r03_v2_driver_shape.txt); 0 = exactly --warmup steps")
     ap.add_argument("--no-async-update", dest="async_update", action="store_false",
                     help="skip the --async_update pipeline measurement (reported as its own object)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (the CPU baseline, the Hogwild / --async_update / heavy-tailed / "
+                         "3-launch legs, the other BASELINE configs, time-to-MRR, the ranking evaluation; the --no-* flags above "
+                         "narrow it).  Without it an N = 1 run times the K steps and prints the line, nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed as DIR/<name>.npy (dump_outputs; N = 1 only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # (bench_dist.dist_workload_name: `transe_l2_fb15k` on the sharded engines only when it was asked for; without the flag the
     #  N > 1 headline is BASELINE configs[4])
     args.workload_explicit = any(a == "--workload" or a.startswith("--workload=") for a in sys.argv[1:])
@@ -618,10 +671,14 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world > 1 or os.environ.get("KGE_FORCE_DIST") or args.workload in ("transe_l2_freebase", "rotate_freebase"):
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the single-table N = 1 path only (the sharded engines keep their tables per rank)")
         import bench_dist
         return bench_dist.main(args, world, rank, local_rank)
     if args.gpus != 1:
         raise SystemExit("--gpus %d needs torch.distributed.run (WORLD_SIZE=%d)" % (args.gpus, world))
+    if not args.full:                    # a plain run: the headline only
+        args.no_cpu_baseline, args.hogwild, args.async_update, args.configs, args.time_to_mrr = True, 0, False, False, False
 
     import __graft_entry__
     __graft_entry__.build()
@@ -805,6 +862,8 @@ def main():
     K = args.steps
     accum = eng.read_loss_sums()
     assert all(np.isfinite(accum[:3])), "non-finite loss: %r" % (accum,)
+    if args.dump_outputs:                # (before the --full legs: the Hogwild leg trains on these tables)
+        dump_outputs(args.dump_outputs, eng, accum)
 
     bytes_step = algorithmic_bytes(plans, eng.d_e, eng.d_r)
     step_s = (ev_ms * 1e-3) / K

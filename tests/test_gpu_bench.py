@@ -81,7 +81,7 @@ def test_bench_line_has_the_contract_fields():
 
 @pytest.mark.gpu
 def test_bench_time_to_mrr_leg_reports_the_second_half_of_the_metric():
-    """round 6: the bounded time-to-MRR@0.65 leg of the default line - dglke_train with the reference's FB15k
+    """round 6: the bounded time-to-MRR@0.65 leg of the --full line - dglke_train with the reference's FB15k
     TransE_l2 recipe on real FB15k when supplied, else on the labelled PLANTED graph."""
     import bench
     d = bench.time_to_mrr(timeout_s=280.0)
@@ -94,7 +94,7 @@ def test_bench_time_to_mrr_leg_reports_the_second_half_of_the_metric():
 
 @pytest.mark.gpu
 def test_bench_rank_eval_leg():
-    """the default line's `rank_eval` object: one filtered evaluation at FB15k's shape as the trainers run it, with its rate against the
+    """the --full line's `rank_eval` object: one filtered evaluation at FB15k's shape as the trainers run it, with its rate against the
     fp32-MFMA peak (checked here on a smaller test set)."""
     import bench
     d = bench.rank_eval_leg(n_test=6000)
@@ -125,7 +125,7 @@ def test_forced_exchange_line_carries_per_rank_diagnostics():
 @pytest.mark.gpu
 def test_fb15k_shaped_graph_through_the_sharded_path():
     """north_star: FB15k-shaped triples at 1/2/4/8 GPUs.  (a) `--workload transe_l2_fb15k` through the all-to-all engine with its RCCL
-    exchanges kept at world 1 (the `transe_l2_fb15k_a2a_forced_exchange_relpart` leg of the default line); (b) the `fb15k_shaped` leg
+    exchanges kept at world 1 (the `transe_l2_fb15k_a2a_forced_exchange_relpart` leg of the --full line); (b) the `fb15k_shaped` leg
     of a Freebase-scale line, with the N = 1 point of its own curve beside it."""
     env = dict(os.environ)
     env.update({"KGE_FORCE_DIST": "1", "KGE_DIST_MODE": "a2a", "KGE_DIST_FORCE_COLL": "1", "KGE_DIST_PIPELINE": "0",
@@ -159,10 +159,94 @@ def test_fb15k_shaped_graph_through_the_sharded_path():
 
 @pytest.mark.gpu
 def test_bench_line_carries_the_other_baseline_configs():
-    """the default line's `configs` object (BASELINE.json configs[2..4] as bounded legs in their own processes): checked here on the
+    """the --full line's `configs` object (BASELINE.json configs[2..4] as bounded legs in their own processes): checked here on the
     two FB15k / wikikg2 legs' machinery with a short leg (the Freebase-shard legs need 40 GB and run in the real bench only)."""
     import bench
     legs = bench.other_configs(steps=40, timeout_s=280.0, only=("distmult_fb15k",))
     d = legs["distmult_fb15k"]
     assert "error" not in d, d
     assert d["steps"] == 40 and 10.0 < d["us_per_step"] < 500.0 and d["algorithmic_bytes_per_step"] > 1e7 and 0 < d["frac"] < 1
+
+
+def test_dump_outputs_writes_the_tables_or_a_fixed_sample_within_the_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs DIR): float32 tables + Adagrad state and float64 loss sums; tables beyond the budget are
+    written as the same seeded share of their rows, with the row ids beside them, identically from call to call."""
+    import types
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    eng = types.SimpleNamespace(ent=torch.rand(3000, 40, generator=g), ent_state=torch.rand(3000, generator=g),
+                                rel=torch.rand(50, 40, generator=g), rel_state=torch.rand(50, generator=g), proj=None)
+    sums = [1.5, 2.5, 2.0, 0.25]
+    bench.dump_outputs(str(tmp_path / "a"), eng, sums)
+    z = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert set(z) == {"entity_emb", "entity_state", "relation_emb", "relation_state", "loss_sums"}
+    assert np.array_equal(z["entity_emb"], eng.ent.numpy()) and np.array_equal(z["relation_state"], eng.rel_state.numpy())
+    assert z["entity_emb"].dtype == np.float32 and z["loss_sums"].dtype == np.float64 and z["loss_sums"].tolist() == sums
+    monkeypatch.setattr(bench, "DUMP_BUDGET", (1 << 20) + 200000)          # 1 MiB slack + 200 kB for rows: ~40 % of 492 kB
+    eng.proj, eng.proj_state = torch.rand(50, 1600, generator=g), torch.rand(50, generator=g)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), eng, sums)
+    files = sorted(os.listdir(str(tmp_path / "b")))
+    assert files == sorted(os.listdir(str(tmp_path / "c"))) and "projection_rows.npy" in files and "entity_rows.npy" in files
+    assert sum(os.path.getsize(str(tmp_path / "b" / f)) for f in files) <= bench.DUMP_BUDGET
+    for f in files:
+        a, b = np.load(str(tmp_path / "b" / f)), np.load(str(tmp_path / "c" / f))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    rows = np.load(str(tmp_path / "b" / "entity_rows.npy")).astype(np.int64)
+    assert 0 < len(rows) < 3000 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "entity_emb.npy")), eng.ent.numpy()[rows])
+    prow = np.load(str(tmp_path / "b" / "projection_rows.npy")).astype(np.int64)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "projection_state.npy")), eng.proj_state.numpy()[prow])
+
+
+def test_cpu_baseline_trainer_processes_stay_within_the_run_budget(monkeypatch):
+    """the CPU baseline's --num_proc leg starts at most OMP_NUM_THREADS trainers, and never more than 12 (each one opens the GPU
+    through torch's HIP runtime: with the benchmark's own process, well below 16 processes hold it)."""
+    import bench
+    monkeypatch.setenv("OMP_NUM_THREADS", "4")
+    assert bench.hogwild_procs() == max(2, min(4, len(os.sched_getaffinity(0))))
+    monkeypatch.setenv("OMP_NUM_THREADS", "256")
+    assert 2 <= bench.hogwild_procs() <= 12
+    monkeypatch.delenv("OMP_NUM_THREADS")
+    assert 2 <= bench.hogwild_procs() <= 12
+
+
+def _bench_line(args, timeout=300):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + args,
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, "exactly one JSON line"
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_the_headline_only_and_dumps_what_it_computed(tmp_path):
+    """a plain run measures the headline and nothing else; --dump-outputs writes the trained tables and loss sums of the timed
+    steps, and two runs with the same arguments start from the same inputs (same tables up to the order of float additions)."""
+    d = _bench_line(["--steps", "20", "--warmup", "5", "--dump-outputs", str(tmp_path / "a")])
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["unit"] == "edges/s" and d["dtype"] == "f32" and d["ms_per_step"] > 0
+    for k in ("cpu_baseline", "hogwild", "async_update", "async_update_rel", "heavy_tailed_ids", "strict_step_3_launches",
+              "configs", "time_to_mrr", "rank_eval"):
+        assert k not in d, k
+    z = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert set(z) == {"entity_emb", "entity_state", "relation_emb", "relation_state", "loss_sums"}
+    assert z["entity_emb"].shape == (14951, 400) and z["relation_emb"].shape == (1345, 400) and z["entity_emb"].dtype == np.float32
+    assert np.all(np.isfinite(z["entity_emb"])) and z["entity_state"].max() > 0 and z["relation_state"].max() > 0
+    assert abs(z["loss_sums"][2] / 20 - d["mean_loss"]) < 1e-5
+    d2 = _bench_line(["--steps", "20", "--warmup", "5", "--dump-outputs", str(tmp_path / "b")])
+    for k in z:
+        np.testing.assert_allclose(np.load(str(tmp_path / "b" / (k + ".npy"))), z[k], rtol=1e-4, atol=1e-6, err_msg=k)
+    assert abs(d2["mean_loss"] - d["mean_loss"]) < 1e-5
+
+
+@pytest.mark.gpu
+def test_full_bench_run_carries_the_secondary_legs():
+    """--full adds the legs beside the headline (narrowed here by the --no-* flags to the quick on-device ones)."""
+    d = _bench_line(["--steps", "20", "--warmup", "5", "--full", "--hogwild", "2", "--no-cpu-baseline", "--no-configs",
+                     "--no-time-to-mrr"])
+    assert d["steps"] == 20 and "configs" not in d and "cpu_baseline" not in d
+    for k in ("hogwild", "async_update", "async_update_rel", "heavy_tailed_ids", "strict_step_3_launches"):
+        assert k in d and "error" not in d[k], (k, d.get(k))
+    assert d["hogwild"]["trainers"] == 2 and d["hogwild"]["finite_loss"]

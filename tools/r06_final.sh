@@ -3,8 +3,8 @@
 # FETCH_SIZE / WRITE_SIZE passes of five workloads / legs, the forced-exchange proxy legs
 export GRAFT_REPO_ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06final; mkdir -p $O; cd $R
-timeout 500 python bench.py --steps 20 --warmup 5 > $O/bench_driver_shape.json 2> $O/bench_driver_shape.err
-timeout 400 python bench.py --no-configs > $O/bench_long.json 2> $O/bench_long.err
+timeout 500 python bench.py --steps 20 --warmup 5 --full > $O/bench_driver_shape.json 2> $O/bench_driver_shape.err
+timeout 400 python bench.py --full --no-configs > $O/bench_long.json 2> $O/bench_long.err
 for f in bench_driver_shape bench_long; do python -c "
 import json;d=json.loads(open('$O/$f.json').read().strip().splitlines()[-1]);print('$f', d['value'], d['ms_per_step'], d['roofline']['frac'], d['cpu_baseline']['kind'], d['cpu_baseline']['value'])"; done
 cd /tmp && export TMPDIR=/tmp
