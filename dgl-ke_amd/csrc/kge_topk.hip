@@ -1,0 +1,636 @@
+// kge_topk.hip - inference: top-K triples of a trained model and top-K similar embedding pairs (the reference's ScoreInfer /
+// EmbSimInfer, models/infer.py:52-344) without a score block in memory.
+//
+//   * topk_select_kernel: workgroup = 128 query rows x one SEGMENT of the candidate list, walked in 128-candidate tiles in
+//     increasing index order.  A tile's scores come from the rank_gemm_kernel main loop (k stages of 32 through LDS, 16x16x4
+//     fp32 MFMA, kge_rank_gemm.hip) for the matrix forms, or from a VALU loop over the same staging for the pairwise forms
+//     (TransE_l1, RotatE, l1 and any D that is not a multiple of 4).  The tile goes to LDS; each wavefront then walks its 32
+//     rows: one compare against the row's running K-th best and one ballot per score.  Survivors are merged into the row's
+//     list (in the workspace, sorted) by rank counting in a per-wavefront LDS queue.  Entries are 64-bit composites
+//     (order-preserving score key << 32 | ~candidate index): "composite <= threshold -> reject" is the score test AND tie
+//     rule 2 (equal scores: the lower position first), and NaN (key 0) ranks below every number.
+//   * topk_merge_kernel: bitonic sort of up to 2048 (score, ordinal) entries in LDS, fan-in 2048 / K - 1 lists per pass; a
+//     tree of passes reduces the segments of a row, then the rows of a group, together with the group's running result
+//     (carried across row batches by the caller).
+//   * the K selected scores of the l2 forms are recomputed in the direct difference form (topk_l2_fix_kernel): the
+//     |a|^2 + |b|^2 - 2 a.b form loses ~1e-3 to cancellation at the top of an l2 list.
+// Workspace: O(rows x (D + segments x K)) + O(N) candidate norms, whatever |H| |R| |T| is.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include "kge_common.hpp"
+
+using namespace kge;
+
+#define TK_BM 128
+#define TK_BN 128
+#define TK_BK 32
+#define TK_LD (TK_BK + 4)
+#define TK_MCAP 2048                              // entries of one merge workgroup
+#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+
+// accumulator kinds (template) and epilogues (runtime)
+enum { ACC_MFMA = 0, ACC_DOT = 1, ACC_SQ = 2, ACC_L1 = 3, ACC_ROT = 4 };
+enum { EPI_RAW = 0, EPI_L2G = 1, EPI_COS = 2, EPI_JAC = 3, EPI_GMINUS = 4, EPI_GSQRT = 5 };
+
+struct TopkSelArgs {
+    const float *abase; const int64_t *aidx; int rows;   // query row i: abase + (aidx ? aidx[i] : i) * D
+    const float *nbase; const int64_t *nidx;             // candidate j: nbase + (nidx ? nidx[j] : j) * D
+    int64_t N; int D, epi, S, K;
+    float gamma;
+    const float *an, *bn;                                // [rows], [N]: |a|^2, |b|^2 (L2G, JAC) or |a|, |b| (COS)
+    unsigned long long *part;                            // out [rows, S, K] composites, sorted, 0 = empty
+};
+
+__device__ __forceinline__ uint32_t fkey(float f) {
+    if (f != f) return 0u;                               // NaN: below every number
+    const uint32_t u = f == 0.f ? 0u : __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float keyf(uint32_t k) {
+    if (k == 0u) return __uint_as_float(0x7fc00000u);
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ unsigned long long comp_of(float s, int64_t j) {
+    return ((unsigned long long)fkey(s) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)j);
+}
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+static inline int check_launch_t() { return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH; }
+
+__device__ __forceinline__ float epilogue(const TopkSelArgs &a, float x, int64_t row, int64_t col) {
+    switch (a.epi) {
+    case EPI_L2G: return a.gamma - sqrtf(fmaxf(fmaf(-2.f, x, a.an[row] + a.bn[col]), 1e-30f));
+    case EPI_COS: return x / (a.an[row] * a.bn[col]);
+    case EPI_JAC: return x / (a.an[row] + a.bn[col] - x);
+    case EPI_GMINUS: return a.gamma - x;
+    case EPI_GSQRT: return a.gamma - sqrtf(x);
+    default: return x;
+    }
+}
+
+template <int ACC>
+__global__ __launch_bounds__(256) void topk_select_kernel(TopkSelArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[2][(TK_BM + TK_BN) * TK_LD];
+    __shared__ unsigned long long rthr[TK_BM];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int rb = (int)blockIdx.x / a.S, seg = (int)blockIdx.x % a.S;
+    const int64_t nbn = (a.N + TK_BN - 1) / TK_BN, tps = (nbn + a.S - 1) / a.S;
+    const int64_t tile0 = (int64_t)seg * tps, tile1 = min(nbn, tile0 + tps);
+    const int r0 = rb * TK_BM, D = a.D, K = a.K;
+    float *sc = &lds[0][0];                                                    // [128][128] score tile (after the main loop)
+    unsigned long long *un = reinterpret_cast<unsigned long long *>(&lds[0][0] + TK_BM * TK_BN) + wave * 256;
+    for (int e = tid; e < TK_BM * K; e += 256) {
+        const int lr = e / K;
+        if (r0 + lr < a.rows) a.part[((int64_t)(r0 + lr) * a.S + seg) * K + e % K] = 0ull;
+    }
+    if (tid < TK_BM) rthr[tid] = 0ull;
+    __syncthreads();
+    for (int64_t bn = tile0; bn < tile1; ++bn) {
+        if constexpr (ACC == ACC_MFMA) {
+            // ---- a copy of the rank_gemm_kernel main loop (kge_rank_gemm.hip; a fix to one belongs in both), D % 4 == 0 ------
+            const int nst = (D + TK_BK - 1) / TK_BK;
+            const int c4t = (tid & 7) * 4;
+            const float *gp[8];
+            int lo[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int f = tid + 256 * i, row = f >> 3, c4 = (f & 7) * 4;
+                if (row < TK_BM) gp[i] = row_ptr(a.abase, a.aidx, min(r0 + row, a.rows - 1), D) + c4;
+                else gp[i] = row_ptr(a.nbase, a.nidx, min(bn * TK_BN + row - TK_BM, a.N - 1), D) + c4;
+                lo[i] = row * TK_LD + c4;
+            }
+            f32x4 g[8];
+            const bool tail = (D % TK_BK) != 0 && (nst - 1) * TK_BK + c4t >= D;
+            auto gload = [&](int s) {
+                const int off = min(s * TK_BK, D - 4 - c4t);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) g[i] = *reinterpret_cast<const f32x4 *>(gp[i] + off);
+            };
+            auto lstore = [&](int bf, bool last) {
+                if (last && (D % TK_BK) != 0) {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) g[i] = tail ? (f32x4){0.f, 0.f, 0.f, 0.f} : g[i];
+                }
+#pragma unroll
+                for (int i = 0; i < 8; ++i) *reinterpret_cast<f32x4 *>(&lds[bf][lo[i]]) = g[i];
+            };
+            const int wr = wave >> 1, wc = wave & 1;
+            const int m = lane & 15, q = lane >> 4;
+            const int aoff = (wr * 64 + m) * TK_LD + 4 * q, boff = (TK_BM + wc * 64 + m) * TK_LD + 4 * q;
+            f32x4 acc[4][4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            gload(0);
+            lstore(0, nst == 1);
+            __syncthreads();
+            for (int s = 0; s < nst; ++s) {
+                const int bf = s & 1;
+                if (s + 1 < nst) gload(s + 1);
+                f32x4 af[2][4], bfr[2][4];
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        af[kb][i] = *reinterpret_cast<const f32x4 *>(&lds[bf][aoff + i * 16 * TK_LD + kb * 16]);
+                        bfr[kb][i] = *reinterpret_cast<const f32x4 *>(&lds[bf][boff + i * 16 * TK_LD + kb * 16]);
+                    }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) acc[i][j] = MFMA16(af[0][i][e], bfr[0][j][e], acc[i][j]);
+                __builtin_amdgcn_sched_barrier(0);
+                if (s + 1 < nst) lstore(bf ^ 1, s + 2 == nst);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) acc[i][j] = MFMA16(af[1][i][e], bfr[1][j][e], acc[i][j]);
+                __syncthreads();
+            }
+            // tile -> LDS: acc[i][j][r] = (row 64 wr + 16 i + 4 q + r, column 64 wc + 16 j + m)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = wr * 64 + 16 * i + 4 * q + r;
+                    const int64_t grow = min(r0 + row, a.rows - 1);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int col = wc * 64 + 16 * j + m;
+                        const int64_t gcol = min(bn * TK_BN + col, a.N - 1);
+                        sc[row * TK_BN + col] = epilogue(a, acc[i][j][r], grow, gcol);
+                    }
+                }
+        } else {
+            // ---- VALU tile: thread (tx, ty) owns rows ty + 16 i, columns tx + 16 j; scalar staging (any D) ------------------
+            const int tx = tid & 15, ty = tid >> 4;
+            const int hd = D / 2;
+            const int nst = ACC == ACC_ROT ? (hd + 15) / 16 : (D + TK_BK - 1) / TK_BK;
+            float acc[8][8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[i][j] = 0.f;
+            for (int s = 0; s < nst; ++s) {
+                float g[32];
+#pragma unroll
+                for (int i = 0; i < 32; ++i) {
+                    const int f = tid + 256 * i, row = f >> 5, c = f & 31;
+                    const float *p = row < TK_BM ? row_ptr(a.abase, a.aidx, min(r0 + row, a.rows - 1), D)
+                                                 : row_ptr(a.nbase, a.nidx, min(bn * TK_BN + row - TK_BM, a.N - 1), D);
+                    int col; bool ok;
+                    if constexpr (ACC == ACC_ROT) { const int k = s * 16 + (c & 15); ok = k < hd; col = (c < 16 ? 0 : hd) + min(k, hd - 1); }
+                    else { const int k = s * TK_BK + c; ok = k < D; col = min(k, D - 1); }
+                    const float v = p[col];
+                    g[i] = ok ? v : 0.f;
+                }
+                __syncthreads();
+#pragma unroll
+                for (int i = 0; i < 32; ++i) {
+                    const int f = tid + 256 * i;
+                    lds[0][(f >> 5) * TK_LD + (f & 31)] = g[i];
+                }
+                __syncthreads();
+                if constexpr (ACC == ACC_ROT) {
+                    for (int k = 0; k < 16; ++k) {
+                        float are[8], aim[8], bre[8], bim[8];
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) { are[i] = lds[0][(ty + 16 * i) * TK_LD + k]; aim[i] = lds[0][(ty + 16 * i) * TK_LD + 16 + k]; }
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) { bre[j] = lds[0][(TK_BM + tx + 16 * j) * TK_LD + k]; bim[j] = lds[0][(TK_BM + tx + 16 * j) * TK_LD + 16 + k]; }
+#pragma unroll
+                        for (int i = 0; i < 8; ++i)
+#pragma unroll
+                            for (int j = 0; j < 8; ++j) {
+                                const float dr = are[i] - bre[j], di = aim[i] - bim[j];
+                                acc[i][j] += sqrtf(fmaf(dr, dr, di * di));
+                            }
+                    }
+                } else {
+                    for (int k = 0; k < TK_BK; ++k) {
+                        float av[8], bv[8];
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) av[i] = lds[0][(ty + 16 * i) * TK_LD + k];
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) bv[j] = lds[0][(TK_BM + tx + 16 * j) * TK_LD + k];
+#pragma unroll
+                        for (int i = 0; i < 8; ++i)
+#pragma unroll
+                            for (int j = 0; j < 8; ++j) {
+                                if constexpr (ACC == ACC_DOT) acc[i][j] = fmaf(av[i], bv[j], acc[i][j]);
+                                else if constexpr (ACC == ACC_SQ) { const float d = av[i] - bv[j]; acc[i][j] = fmaf(d, d, acc[i][j]); }
+                                else acc[i][j] += fabsf(av[i] - bv[j]);
+                            }
+                    }
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int row = ty + 16 * i;
+                const int64_t grow = min(r0 + row, a.rows - 1);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int col = tx + 16 * j;
+                    sc[row * TK_BN + col] = epilogue(a, acc[i][j], grow, min(bn * TK_BN + col, a.N - 1));
+                }
+            }
+        }
+        __syncthreads();
+        // ---- selection: wavefront w walks rows 32 w .. 32 w + 31 of the tile ------------------------------------------------
+        for (int lr = wave * 32; lr < wave * 32 + 32; ++lr) {
+            if (r0 + lr >= a.rows) break;
+            const unsigned long long thr = rthr[lr];
+            const int64_t j0 = bn * TK_BN + lane, j1 = j0 + 64;
+            const unsigned long long c0 = j0 < a.N ? comp_of(sc[lr * TK_BN + lane], j0) : 0ull;
+            const unsigned long long c1 = j1 < a.N ? comp_of(sc[lr * TK_BN + lane + 64], j1) : 0ull;
+            const bool s0 = c0 > thr, s1 = c1 > thr;
+            const unsigned long long b0 = __ballot(s0), b1 = __ballot(s1);
+            if ((b0 | b1) == 0ull) continue;                                   // the common case
+            unsigned long long *list = a.part + ((int64_t)(r0 + lr) * a.S + seg) * K;
+            for (int p = lane; p < K; p += 64) un[p] = list[p];
+            const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+            const int n0 = __popcll(b0), n = K + n0 + __popcll(b1);
+            if (s0) un[K + __popcll(b0 & below)] = c0;
+            if (s1) un[K + n0 + __popcll(b1 & below)] = c1;
+            wave_sync();
+            unsigned long long v[4];
+            int rk[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { v[i] = lane + 64 * i < n ? un[lane + 64 * i] : 0ull; rk[i] = 0; }
+            for (int x = 0; x < n; ++x) {
+                const unsigned long long u = un[x];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) rk[i] += u > v[i] ? 1 : 0;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (v[i] != 0ull && rk[i] < K) {
+                    list[rk[i]] = v[i];
+                    if (rk[i] == K - 1) rthr[lr] = v[i];
+                }
+            wave_sync();
+        }
+        __syncthreads();
+    }
+}
+
+// [rows, S, K] composites -> (score, ordinal = row_base[row] + j * stride; -1 = empty)
+__global__ void topk_unpack_kernel(const unsigned long long *part, int64_t n, int SK, const int64_t *row_base, int64_t stride,
+                                   float *os, int64_t *oo) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const unsigned long long c = part[e];
+    if (c == 0ull) { os[e] = 0.f; oo[e] = -1; return; }
+    const int64_t j = (int64_t)(0xffffffffu - (uint32_t)(c & 0xffffffffull));
+    os[e] = keyf((uint32_t)(c >> 32));
+    oo[e] = row_base[e / SK] + j * stride;
+}
+
+// the K selected entries of each row in the direct difference form: gamma - |a - b|_2
+__global__ __launch_bounds__(KGE_BLOCK) void topk_l2_fix_kernel(const float *abase, const int64_t *aidx, const float *nbase,
+                                                                const int64_t *nidx, int D, int rows, int K, const int64_t *row_base,
+                                                                int64_t stride, float gamma, float *os, const int64_t *oo) {
+    const int64_t e = (int64_t)blockIdx.x * KGE_WAVES_PER_BLOCK + (threadIdx.x >> 6);
+    if (e >= (int64_t)rows * K) return;
+    const int64_t o = oo[e];
+    if (o < 0) return;
+    const int64_t row = e / K, j = (o - row_base[row]) / stride;
+    const float *x = row_ptr(abase, aidx, row, D), *y = row_ptr(nbase, nidx, j, D);
+    float s = 0.f;
+    for (int k = threadIdx.x & 63; k < D; k += 64) { const float d = x[k] - y[k]; s = fmaf(d, d, s); }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) os[e] = gamma - sqrtf(s);
+}
+
+__device__ __forceinline__ bool beats(uint32_t ka, int64_t oa, uint32_t kb, int64_t ob) { return ka > kb || (ka == kb && oa < ob); }
+
+// workgroup (g, c): top K of lists [c fan, min(L, (c+1) fan)) of group g (+ the group's running result when c == 0)
+__global__ __launch_bounds__(256) void topk_merge_kernel(const float *is, const int64_t *io, int L, int fan, int K, int nout,
+                                                         const float *xs, const int64_t *xo, float *os, int64_t *oo) {
+    __shared__ uint32_t key[TK_MCAP];
+    __shared__ int64_t ord[TK_MCAP];
+    const int64_t g = (int64_t)blockIdx.x / nout;
+    const int c = (int)blockIdx.x % nout, tid = threadIdx.x;
+    const int l0 = c * fan, nl = min(L, l0 + fan) - l0;
+    const int nin = nl * K, ntot = nin + ((xs && c == 0) ? K : 0);
+    int P = 1;
+    while (P < ntot) P <<= 1;
+    const float *src_s = is + ((int64_t)g * L + l0) * K;
+    const int64_t *src_o = io + ((int64_t)g * L + l0) * K;
+    for (int e = tid; e < P; e += 256) {
+        float s = 0.f; int64_t o = -1;
+        if (e < nin) { s = src_s[e]; o = src_o[e]; }
+        else if (e < ntot) { s = xs[g * K + e - nin]; o = xo[g * K + e - nin]; }
+        key[e] = o < 0 ? 0u : fkey(s);
+        ord[e] = o < 0 ? INT64_MAX : o;
+    }
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P; i += 256) {
+                const int ij = i ^ j;
+                if (ij > i) {
+                    const bool best_first = (i & k) == 0;
+                    const bool sw = best_first ? beats(key[ij], ord[ij], key[i], ord[i]) : beats(key[i], ord[i], key[ij], ord[ij]);
+                    if (sw) {
+                        const uint32_t tk = key[i]; key[i] = key[ij]; key[ij] = tk;
+                        const int64_t to = ord[i]; ord[i] = ord[ij]; ord[ij] = to;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    for (int e = tid; e < K; e += 256) {
+        const bool ok = e < P && ord[e] != INT64_MAX;
+        os[((int64_t)g * nout + c) * K + e] = ok ? keyf(key[e]) : 0.f;
+        oo[((int64_t)g * nout + c) * K + e] = ok ? ord[e] : -1;
+    }
+}
+
+// a score vector as lists of K (ordinal = position)
+__global__ void topk_vec_lists_kernel(const float *score, int64_t n, int64_t total, float *os, int64_t *oo) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    os[e] = e < n ? score[e] : 0.f;
+    oo[e] = e < n ? e : -1;
+}
+
+// |x|^2 (sq) or |x| of rows base + (idx ? idx[i] : i) * D, one wavefront per row
+__global__ __launch_bounds__(KGE_BLOCK) void topk_norm_kernel(const float *base, const int64_t *idx, int64_t n, int D, int sq,
+                                                              float *out) {
+    const int64_t i = (int64_t)blockIdx.x * KGE_WAVES_PER_BLOCK + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const float *x = row_ptr(base, idx, i, D);
+    float s = 0.f;
+    for (int k = threadIdx.x & 63; k < D; k += 64) s = fmaf(x[k], x[k], s);
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) out[i] = sq ? s : sqrtf(s);
+}
+
+// pairwise similarity of (left[i], right[i]), one wavefront per pair (tensor_models.py:59-100, pw=True)
+__global__ __launch_bounds__(KGE_BLOCK) void topk_sim_pair_kernel(int sim, const float *emb, int D, const int64_t *left,
+                                                                  const int64_t *right, int64_t n, float *out) {
+    const int64_t i = (int64_t)blockIdx.x * KGE_WAVES_PER_BLOCK + (threadIdx.x >> 6);
+    if (i >= n) return;
+    const float *x = row_ptr(emb, left, i, D), *y = row_ptr(emb, right, i, D);
+    float dot = 0.f, xx = 0.f, yy = 0.f, d1 = 0.f, d2 = 0.f;
+    for (int k = threadIdx.x & 63; k < D; k += 64) {
+        const float u = x[k], v = y[k], d = u - v;
+        dot = fmaf(u, v, dot); xx = fmaf(u, u, xx); yy = fmaf(v, v, yy); d1 += fabsf(d); d2 = fmaf(d, d, d2);
+    }
+    dot = wave_sum(dot); xx = wave_sum(xx); yy = wave_sum(yy); d1 = wave_sum(d1); d2 = wave_sum(d2);
+    if ((threadIdx.x & 63) != 0) return;
+    float s;
+    switch (sim) {
+    case KGE_SIM_COSINE: s = dot / (sqrtf(xx) * sqrtf(yy)); break;
+    case KGE_SIM_L2: s = -sqrtf(d2); break;
+    case KGE_SIM_L1: s = -d1; break;
+    case KGE_SIM_DOT: s = dot; break;
+    default: s = dot / (xx + yy - dot); break;
+    }
+    out[i] = s;
+}
+
+namespace {
+
+inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
+
+int topk_fan(int K) { return std::max(1, TK_MCAP / K - 1); }
+
+// segments per row block: about one workgroup per CU, few enough that a row's S lists merge in one pass, and at least
+// TK_MIN_TILES tiles per segment - the first tile of a segment fills the row lists (a full merge per row); only the
+// later tiles take the one-compare-one-ballot path
+#define TK_MIN_TILES 4
+int64_t topk_seg_cap(int rows, int K) {
+    const int rb = std::max(1, (rows + TK_BM - 1) / TK_BM);
+    return std::max<int64_t>(1, std::min<int64_t>(topk_fan(K), (256 + rb - 1) / rb));
+}
+int topk_segments(int rows, int64_t N, int K) {
+    const int64_t nbn = (N + TK_BN - 1) / TK_BN;
+    const int64_t s = std::max<int64_t>(1, std::min(nbn / TK_MIN_TILES, topk_seg_cap(rows, K))), tps = (nbn + s - 1) / s;
+    return (int)((nbn + tps - 1) / tps);
+}
+
+struct TkWs {
+    float *A, *an, *bn, *s0, *s1;
+    int64_t *o0, *o1;
+    unsigned long long *part;
+    size_t need;
+};
+TkWs carve(void *ws, int rows, int64_t N, int D, int K) {
+    TkWs w{};
+    char *b = (char *)ws;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char *p = b ? b + off : nullptr; off += al(bytes); return p; };
+    if (rows > 0) {
+        const size_t ent = (size_t)rows * (size_t)topk_seg_cap(rows, K) * K;
+        w.A = (float *)take((size_t)rows * D * 4);
+        w.an = (float *)take((size_t)rows * 4); w.bn = (float *)take((size_t)N * 4);
+        w.part = (unsigned long long *)take(ent * 8);
+        w.s0 = (float *)take(ent * 4); w.o0 = (int64_t *)take(ent * 8);
+        w.s1 = (float *)take(ent * 4); w.o1 = (int64_t *)take(ent * 8);
+    } else {                                           // a score vector of N entries
+        const size_t ent = (size_t)((N + K - 1) / K) * K;
+        w.s0 = (float *)take(ent * 4); w.o0 = (int64_t *)take(ent * 8);
+        w.s1 = (float *)take(ent * 4); w.o1 = (int64_t *)take(ent * 8);
+    }
+    w.need = off;
+    return w;
+}
+
+// tree of merge passes over G groups of L lists each (+ a running result per group in the first pass).  Output: out (when
+// given) or whichever of the two buffers the last pass wrote.
+int merge_tree(int64_t G, int64_t L, int K, const float *is, const int64_t *io, const float *xs, const int64_t *xo, float *out_s,
+               int64_t *out_o, float *ta_s, int64_t *ta_o, float *tb_s, int64_t *tb_o, const float **res_s, const int64_t **res_o,
+               hipStream_t st) {
+    if (L == 1 && !xs && !out_s) { *res_s = is; *res_o = io; return KGE_OK; }
+    float *ts[2] = {ta_s, tb_s};
+    int64_t *to[2] = {ta_o, tb_o};
+    int pp = 0;
+    const int fan = topk_fan(K);
+    while (true) {
+        const int64_t nout = (L + fan - 1) / fan;
+        const bool fin = nout == 1;
+        float *ds = (fin && out_s) ? out_s : ts[pp];
+        int64_t *dq = (fin && out_s) ? out_o : to[pp];
+        hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)(G * nout)), dim3(256), 0, st, is, io, (int)L, fan, K, (int)nout,
+                           xs, xo, ds, dq);
+        if (int rc = check_launch_t()) return rc;
+        xs = nullptr; xo = nullptr;
+        is = ds; io = dq; L = nout; pp ^= 1;
+        if (fin) break;
+    }
+    *res_s = is; *res_o = io;
+    return KGE_OK;
+}
+
+}  // namespace
+
+int kge_fail(int code, const char *msg);
+static int tk_fail(const char *msg) { return kge_fail(KGE_ERR_ARG, msg); }
+
+static int tk_check_model(int model, int d_e, int d_r) {
+    bool ok;
+    if (model == KGE_RESCAL) ok = d_e <= 1024 && (int64_t)d_r == (int64_t)d_e * d_e;
+    else if (model == KGE_COMPLEX || model == KGE_SIMPLE) ok = d_e % 2 == 0 && d_r == d_e;
+    else if (model == KGE_ROTATE) ok = d_e % 2 == 0 && d_r == d_e / 2;
+    else ok = d_r == d_e;
+    if (ok) return KGE_OK;
+    char msg[160];
+    snprintf(msg, sizeof(msg), "kge_topk_select: dims d_e=%d d_r=%d do not fit model %d", d_e, d_r, model);
+    return tk_fail(msg);
+}
+
+extern "C" {
+
+size_t kge_topk_workspace_bytes(int rows, int64_t n_cand, int d, int K) {
+    if (rows < 0 || n_cand < 0 || d < 0 || K < 1 || K > KGE_TOPK_MAX) return 0;
+    return carve(nullptr, rows, n_cand, d, K).need;
+}
+
+int kge_topk_select(int func, int side, const float *ent, int64_t n_ent, const float *rel, int64_t n_rel, const int64_t *h,
+                    const int64_t *r, const int64_t *t, int rows, int d_e, int d_r, float gamma, float emb_init, const int64_t *cand,
+                    int64_t n_cand, const int64_t *row_base, int64_t stride, int group_rows, int K, float *res_score,
+                    int64_t *res_ord, void *ws, size_t ws_bytes, void *stream) {
+    char msg[256];
+    const bool sim = func >= KGE_SIM_COSINE && func <= KGE_SIM_EXT_JACCARD;
+    if (!sim && (func < KGE_TRANSE_L1 || func > KGE_RESCAL)) {
+        snprintf(msg, sizeof(msg), "kge_topk_select: unknown score function %d (TransR has no inference path)", func);
+        return tk_fail(msg);
+    }
+    if (K < 1 || K > KGE_TOPK_MAX) {
+        snprintf(msg, sizeof(msg), "kge_topk_select: K = %d outside 1 .. %d", K, KGE_TOPK_MAX);
+        return tk_fail(msg);
+    }
+    if (rows < 0 || !ent || n_ent <= 0 || d_e <= 0 || n_cand < 0 || n_cand > 0x7fffffff || stride <= 0 || group_rows <= 0 ||
+        (rows && (rows % group_rows || !h || !row_base || !res_score || !res_ord || !ws)) ||
+        (!sim && (!rel || n_rel <= 0 || d_r <= 0 || !r || !t)))
+        return tk_fail("kge_topk_select: bad argument");
+    if (rows == 0 || n_cand == 0) return KGE_OK;
+    const int64_t N = n_cand;
+    const int D = d_e;
+    TkWs w = carve(ws, rows, N, D, K);
+    if (w.need > ws_bytes) {
+        snprintf(msg, sizeof(msg), "kge_topk_select: workspace too small (%zu < %zu)", ws_bytes, w.need);
+        return kge_fail(KGE_ERR_WORKSPACE, msg);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    // ---- query rows ----------------------------------------------------------------------------------------------------------
+    const float *abase = w.A;
+    const int64_t *aidx = nullptr;
+    int acc, epi;
+    const int mf = D % 4 == 0 && D >= TK_BK;               // (the staging's clamped float4 re-reads need D >= 32)
+    if (sim) {
+        abase = ent; aidx = h;
+        if (func == KGE_SIM_L1) { acc = ACC_L1; epi = EPI_GMINUS; }
+        else if (func == KGE_SIM_L2) { acc = mf ? ACC_MFMA : ACC_SQ; epi = mf ? EPI_L2G : EPI_GSQRT; }
+        else { acc = mf ? ACC_MFMA : ACC_DOT; epi = func == KGE_SIM_COSINE ? EPI_COS : func == KGE_SIM_EXT_JACCARD ? EPI_JAC : EPI_RAW; }
+        gamma = 0.f;
+    } else {
+        if (int rc = tk_check_model(func, d_e, d_r)) return rc;
+        if (func == KGE_RESCAL) {
+            RescalMatvecArgs m{};
+            m.B = rows; m.D = d_e; m.rel = rel; m.ridx = r;
+            // score = h . (M t) (score_fun.py:397-402): heads are scored by A = M t, tails by A = M^T h
+            if (side) { m.y1 = ent; m.y1idx = t; m.r1 = w.A; }
+            else { m.z1 = ent; m.z1idx = h; m.c1 = w.A; }
+            if (int rc = launch_rescal_matvec(m, st)) return rc;
+        } else {
+            EdgeFwdArgs ef{};
+            ef.src = EdgeSrc{ent, h, ent, t, rel, r};
+            ef.B = rows; ef.d_e = d_e; ef.d_r = d_r; ef.neg_head = side; ef.model = func;
+            ef.gamma = gamma; ef.rot_div = (float)((double)emb_init / M_PI);
+            ef.A = w.A;
+            if (int rc = launch_edge_fwd(ef, st)) return rc;
+        }
+        if (func == KGE_TRANSE_L1) { acc = ACC_L1; epi = EPI_GMINUS; }
+        else if (func == KGE_ROTATE) { acc = ACC_ROT; epi = EPI_GMINUS; }
+        else if (func == KGE_TRANSE_L2) { acc = mf ? ACC_MFMA : ACC_SQ; epi = mf ? EPI_L2G : EPI_GSQRT; }
+        else { acc = mf ? ACC_MFMA : ACC_DOT; epi = EPI_RAW; }
+    }
+    // ---- norms -----------------------------------------------------------------------------------------------------------------
+    if (epi == EPI_L2G || epi == EPI_COS || epi == EPI_JAC) {
+        const int sq = epi != EPI_COS;
+        hipLaunchKernelGGL(topk_norm_kernel, dim3((unsigned)((rows + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK)), dim3(KGE_BLOCK), 0,
+                           st, abase, aidx, (int64_t)rows, D, sq, w.an);
+        hipLaunchKernelGGL(topk_norm_kernel, dim3((unsigned)((N + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK)), dim3(KGE_BLOCK), 0,
+                           st, ent, cand, N, D, sq, w.bn);
+        if (int rc = check_launch_t()) return rc;
+    }
+    // ---- score + select ----------------------------------------------------------------------------------------------------------
+    TopkSelArgs a{};
+    a.abase = abase; a.aidx = aidx; a.rows = rows; a.nbase = ent; a.nidx = cand; a.N = N; a.D = D; a.epi = epi;
+    a.S = topk_segments(rows, N, K); a.K = K; a.gamma = gamma; a.an = w.an; a.bn = w.bn; a.part = w.part;
+    const dim3 grid((unsigned)((int64_t)((rows + TK_BM - 1) / TK_BM) * a.S));
+    switch (acc) {
+    case ACC_MFMA: hipLaunchKernelGGL(topk_select_kernel<ACC_MFMA>, grid, dim3(256), 0, st, a); break;
+    case ACC_DOT: hipLaunchKernelGGL(topk_select_kernel<ACC_DOT>, grid, dim3(256), 0, st, a); break;
+    case ACC_SQ: hipLaunchKernelGGL(topk_select_kernel<ACC_SQ>, grid, dim3(256), 0, st, a); break;
+    case ACC_L1: hipLaunchKernelGGL(topk_select_kernel<ACC_L1>, grid, dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL(topk_select_kernel<ACC_ROT>, grid, dim3(256), 0, st, a); break;
+    }
+    if (int rc = check_launch_t()) return rc;
+    const int64_t ne = (int64_t)rows * a.S * K;
+    hipLaunchKernelGGL(topk_unpack_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, w.part, ne, a.S * K, row_base, stride,
+                       w.s0, w.o0);
+    if (int rc = check_launch_t()) return rc;
+    // ---- segments of a row -> one list per row; l2 scores in the difference form; rows of a group + running result -> result
+    const float *rs; const int64_t *ro;
+    if (int rc = merge_tree(rows, a.S, K, w.s0, w.o0, nullptr, nullptr, nullptr, nullptr, w.s1, w.o1, w.s0, w.o0, &rs, &ro, st)) return rc;
+    if (epi == EPI_L2G) {
+        const int64_t nk = (int64_t)rows * K;
+        hipLaunchKernelGGL(topk_l2_fix_kernel, dim3((unsigned)((nk + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK)), dim3(KGE_BLOCK), 0, st,
+                           abase, aidx, ent, cand, D, rows, K, row_base, stride, gamma, const_cast<float *>(rs), ro);
+        if (int rc = check_launch_t()) return rc;
+    }
+    float *ta_s = rs == w.s0 ? w.s1 : w.s0, *tb_s = rs == w.s0 ? w.s0 : w.s1;
+    int64_t *ta_o = rs == w.s0 ? w.o1 : w.o0, *tb_o = rs == w.s0 ? w.o0 : w.o1;
+    const float *fs; const int64_t *fo;
+    return merge_tree(rows / group_rows, group_rows, K, rs, ro, res_score, res_ord, res_score, res_ord, ta_s, ta_o, tb_s, tb_o, &fs, &fo, st);
+}
+
+int kge_topk_vector(const float *score, int64_t n, int K, float *res_score, int64_t *res_ord, void *ws, size_t ws_bytes, void *stream) {
+    char msg[256];
+    if (K < 1 || K > KGE_TOPK_MAX) {
+        snprintf(msg, sizeof(msg), "kge_topk_vector: K = %d outside 1 .. %d", K, KGE_TOPK_MAX);
+        return tk_fail(msg);
+    }
+    if (n < 0 || (n && (!score || !ws)) || !res_score || !res_ord) return tk_fail("kge_topk_vector: bad argument");
+    if (n == 0) return KGE_OK;
+    TkWs w = carve(ws, 0, n, 0, K);
+    if (w.need > ws_bytes) {
+        snprintf(msg, sizeof(msg), "kge_topk_vector: workspace too small (%zu < %zu)", ws_bytes, w.need);
+        return kge_fail(KGE_ERR_WORKSPACE, msg);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t L = (n + K - 1) / K, total = L * K;
+    hipLaunchKernelGGL(topk_vec_lists_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, score, n, total, w.s0, w.o0);
+    if (int rc = check_launch_t()) return rc;
+    const float *fs; const int64_t *fo;
+    return merge_tree(1, L, K, w.s0, w.o0, res_score, res_ord, res_score, res_ord, w.s1, w.o1, w.s0, w.o0, &fs, &fo, st);
+}
+
+int kge_sim_pairwise(int sim, const float *emb, int64_t n_emb, int d, const int64_t *left, const int64_t *right, int64_t n, float *out,
+                     void *stream) {
+    if (sim < KGE_SIM_COSINE || sim > KGE_SIM_EXT_JACCARD || !emb || n_emb <= 0 || d <= 0 || n < 0 || (n && (!left || !right || !out)))
+        return tk_fail("kge_sim_pairwise: bad argument");
+    if (n == 0) return KGE_OK;
+    hipLaunchKernelGGL(topk_sim_pair_kernel, dim3((unsigned)((n + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK)), dim3(KGE_BLOCK), 0,
+                       (hipStream_t)stream, sim, emb, d, left, right, n, out);
+    return check_launch_t();
+}
+
+}  // extern "C"

@@ -1,8 +1,8 @@
 """`dglke_train`-compatible entry point (reference: python/dglke/train.py:40-330 + the common flags of
 python/dglke/utils.py:199-297): same flag names, same dataset formats, same log-line formats, same
 output files (`<save_path>/<model>_<dataset>_<n>/<dataset>_<model>_{entity,relation}.npy` +
-config.json, utils.py:35-49) so that the reference's `dglke_eval` / `dglke_predict` can consume the
-embeddings.
+config.json, utils.py:35-49) so that `dglke_eval`, `dglke_predict` and `dglke_emb_sim` (ours in dgl-ke_amd/, or the
+reference's) can consume the embeddings.
 
 What is different underneath: the per-step loop `sample -> forward -> backward -> update`
 (train_pytorch.py:132-152) is ONE fused HIP step (`kge_step_fused`) fed by the on-device sampler,

@@ -583,6 +583,32 @@ typedef struct kge_merge_job {
 } kge_merge_job;
 int kge_adagrad_apply_merged_pair(const kge_merge_job *a, const kge_merge_job *b, float lr, float eps, void *stream);
 
+
+/* ---- inference: top-K triples (the reference's ScoreInfer, models/infer.py:52-214) and top-K similar embedding pairs
+ * (EmbSimInfer, :216-344) with no score block in memory (csrc/kge_topk.hip) ----
+ * kge_topk_select scores `rows` query rows against a candidate list and keeps, per group of `group_rows` consecutive rows,
+ * the K best (score, ordinal) pairs merged with the group's running result res_score / res_ord [rows / group_rows][K]
+ * (ordinal -1 = empty slot; fill with -1 before a group's first call).  Candidate j of row i has the ordinal
+ * row_base[i] + j * stride; equal scores rank by ordinal (lower first), NaN below every number.
+ *   func = a model id (TransE_l1 .. RESCAL; TransR has no inference path): row i is T(h_i, r_i) scored against tails
+ *          (side 0) or T(t_i, r_i) against heads (side 1), formed as in kge_rank_eval; the score forms are the reference's
+ *          `infer` methods (score_fun.py), gamma as given, RotatE's phase from emb_init.
+ *   func = KGE_SIM_*: row i is ent[h_i] (r, t, rel unused); tensor_models.py:59-100.
+ * cand == NULL: every row of `ent` (n_cand of them).  Workspace: kge_topk_workspace_bytes(rows, n_cand, d_e, K), which is
+ * O(rows x (d_e + segments x K)) + 4 n_cand bytes.  rows == 0: the workspace of kge_topk_vector over n_cand scores.
+ * kge_topk_vector: the K best of n scores (ordinal = position), merged with the running result like kge_topk_select.
+ * kge_sim_pairwise: out[i] = sim(emb[left[i]], emb[right[i]]). */
+#define KGE_TOPK_MAX 128
+enum { KGE_SIM_COSINE = 16, KGE_SIM_L2 = 17, KGE_SIM_L1 = 18, KGE_SIM_DOT = 19, KGE_SIM_EXT_JACCARD = 20 };
+size_t kge_topk_workspace_bytes(int rows, int64_t n_cand, int d_e, int K);
+int kge_topk_select(int func, int side, const float *ent, int64_t n_ent, const float *rel, int64_t n_rel, const int64_t *h,
+                    const int64_t *r, const int64_t *t, int rows, int d_e, int d_r, float gamma, float emb_init, const int64_t *cand,
+                    int64_t n_cand, const int64_t *row_base, int64_t stride, int group_rows, int K, float *res_score,
+                    int64_t *res_ord, void *ws, size_t ws_bytes, void *stream);
+int kge_topk_vector(const float *score, int64_t n, int K, float *res_score, int64_t *res_ord, void *ws, size_t ws_bytes, void *stream);
+int kge_sim_pairwise(int sim, const float *emb, int64_t n_emb, int d, const int64_t *left, const int64_t *right, int64_t n, float *out,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif
