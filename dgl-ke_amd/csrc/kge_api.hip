@@ -1171,6 +1171,81 @@ int kge_rank_eval(int model, int neg_head, const float *ent, int64_t n_ent, cons
                             n_cand, filt_ptr, filt_ids, Eb, ranks, pos_score_out, ws, ws_bytes, flags, stream);
 }
 
+// the ranking loop of kge_rank_eval_ex / kge_rank_eval_split: h / t index the query table qent (positive rows, pos-side vectors),
+// candidate j is row cent + (cand ? cand[j] : j) * d_e.  Arguments checked by the callers; N = the candidate count, > 0.
+static int rank_eval_impl(int model, int neg_head, const float *qent, const float *cent, const float *rel, const float *proj,
+                          const int64_t *h, const int64_t *r, const int64_t *t, int64_t E, int d_e, int d_r, float gamma,
+                          float emb_init, const int64_t *cand, int64_t N, const int64_t *filt_ptr, const int64_t *filt_ids,
+                          int Eb, int32_t *ranks, float *pos_score_out, void *ws, size_t ws_bytes, unsigned flags,
+                          hipStream_t s) {
+    Carver cv(ws, ws_bytes);
+    float *A = cv.f((size_t)Eb * d_e), *asq = cv.f(Eb), *P = cv.f(Eb), *bsq = cv.f((size_t)N);
+    float *S = cv.f(std::max((size_t)Eb * (size_t)N, rank_gemm_mask_bytes(Eb, N) / sizeof(float)));
+    float *RV = cv.f((size_t)Eb * d_e);
+    float *THP = cv.f((size_t)Eb * 1024), *TTP = cv.f((size_t)Eb * 1024), *TQ = cv.f((size_t)Eb * 1024), *TSG = cv.f((size_t)Eb * 1024);
+    if (!cv.ok()) return fail(KGE_ERR_WORKSPACE, "kge_rank_eval: workspace too small (%zu < %zu)", ws_bytes,
+                              kge_rank_workspace_bytes(Eb, N, d_e));
+    const bool gemm = use_mfma(model, d_e, (int)N, flags);
+    const bool l2g = gemm && model == KGE_TRANSE_L2;
+    const float rot_div = rot_div_of(emb_init);
+    if (l2g) {       // |b|^2 of every candidate row, once
+        EdgeFwdArgs nb{};
+        nb.B = 0; nb.d_e = d_e; nb.d_r = d_r; nb.model = model; nb.nbase = cent; nb.nidx = cand; nb.n_neg = (int)N;
+        nb.bsq = bsq;
+        KGE_TRY(launch_edge_fwd(nb, s));
+    }
+    for (int64_t e0 = 0; e0 < E; e0 += Eb) {
+        const int rows = (int)((E - e0) < Eb ? (E - e0) : Eb);
+        EdgeFwdArgs ef{};
+        ef.src = EdgeSrc{qent, h + e0, qent, t + e0, rel, r + e0};
+        ef.B = rows; ef.d_e = d_e; ef.d_r = d_r; ef.neg_head = neg_head; ef.model = model;
+        ef.gamma = gamma; ef.rot_div = rot_div;
+        ef.pos_score = pos_score_out ? pos_score_out + e0 : P; ef.A = A; ef.asq = l2g ? asq : nullptr;
+        if (model == KGE_TRANSR) {
+            // the training kernels with one chunk = this batch of test triples and the candidates as negatives
+            RescalMatvecArgs m{};
+            m.B = rows; m.D = d_e; m.Dc = d_r; m.rel = proj; m.ridx = r + e0;
+            m.z1 = qent; m.z1idx = h + e0; m.c1 = THP; m.z2 = qent; m.z2idx = t + e0; m.c2 = TTP;
+            KGE_TRY(launch_rescal_matvec(m, s));
+            TransRArgs tr{};
+            tr.B = rows; tr.C = 1; tr.chunk = rows; tr.N = (int)N; tr.De = d_e; tr.Dr = d_r; tr.neg_head = neg_head;
+            tr.gamma = gamma; tr.ent = qent; tr.cent = cent; tr.h_gid = h + e0; tr.t_gid = t + e0; tr.neg_ids = cand; tr.rel_ids = r + e0;
+            tr.rel = rel; tr.proj = const_cast<float *>(proj);
+            tr.HP = THP; tr.TP = TTP; tr.Q = TQ; tr.SG = TSG; tr.P = ef.pos_score; tr.S = S; tr.Z = nullptr;
+            KGE_TRY(launch_transr_pos(tr, s));
+            KGE_TRY(launch_transr_fwd(tr, s));
+        } else if (model == KGE_RESCAL) {
+            RescalMatvecArgs m{};
+            m.B = rows; m.D = d_e; m.rel = rel; m.ridx = r + e0;
+            m.y1 = qent; m.y1idx = t + e0; m.r1 = neg_head ? A : RV;
+            if (!neg_head) { m.y2 = qent; m.y2idx = h + e0; m.r2 = A; }
+            m.pd = qent; m.pdidx = h + e0; m.p = ef.pos_score;
+            KGE_TRY(launch_rescal_matvec(m, s));
+        } else {
+            KGE_TRY(launch_edge_fwd(ef, s));
+        }
+        if (model == KGE_TRANSR) {
+            // scores already in S
+        } else if (gemm && rank_gemm_supported(model, d_e)) {
+            // one tiled GEMM per batch whose epilogue keeps the comparison bits; ranks from the mask (kge_rank_gemm.hip)
+            KGE_TRY(launch_rank_gemm(model, A, rows, cent, cand, N, d_e, gamma, clamp_of(model), asq, bsq,
+                                     pos_score_out ? pos_score_out + e0 : P, S, filt_ptr, filt_ids, e0, ranks, s));
+            continue;
+        } else if (gemm) {
+            GemmArgs g; fill_gemm(g, model, 1, rows, (int)N, d_e, gamma, A, cent, cand);
+            g.S = S; g.asq = asq; g.bsq = bsq;
+            KGE_TRY(launch_neg_fwd_gemm(g, s));
+        } else {
+            NegArgs na; fill_pair(na, model, 1, rows, (int)N, d_e, gamma, A, cent, cand);
+            na.S = S;
+            KGE_TRY(launch_neg_fwd_pair(na, s));
+        }
+        KGE_TRY(launch_rank_count(S, pos_score_out ? pos_score_out + e0 : P, rows, N, filt_ptr, filt_ids, e0, ranks, s));
+    }
+    return KGE_OK;
+}
+
+
 int kge_rank_eval_ex(int model, int neg_head, const float *ent, int64_t n_ent, const float *rel,
                      int64_t n_rel, const float *proj, const int64_t *h, const int64_t *r, const int64_t *t,
                      int64_t E, int d_e, int d_r, float gamma, float emb_init, const int64_t *cand,
@@ -1186,72 +1261,34 @@ int kge_rank_eval_ex(int model, int neg_head, const float *ent, int64_t n_ent, c
     const int64_t N = cand ? n_cand : n_ent;
     if (N <= 0 || N > 0x7fffffff) return fail(KGE_ERR_ARG, "kge_rank_eval: bad candidate count %lld", (long long)N);
     if (E == 0) return KGE_OK;
+    return rank_eval_impl(model, neg_head, ent, ent, rel, proj, h, r, t, E, d_e, d_r, gamma, emb_init, cand, N, filt_ptr, filt_ids,
+                          Eb, ranks, pos_score_out, ws, ws_bytes, flags, (hipStream_t)stream);
+}
+
+int kge_rank_eval_split(int model, int neg_head, const float *qent, int64_t n_qent, const float *cent, int64_t n_cent,
+                        const float *rel, int64_t n_rel, const float *proj, const int64_t *h, const int64_t *r,
+                        const int64_t *t, int64_t E, int d_e, int d_r, float gamma, float emb_init, const int64_t *cand,
+                        int64_t n_cand, const int64_t *filt_ptr, const int64_t *filt_ids, int Eb, int32_t *ranks,
+                        float *pos_score_out, void *ws, size_t ws_bytes, unsigned flags, void *stream) {
+    if (int rc = check_model(model, d_e, d_r)) return rc;
+    if (model == KGE_TRANSR && !proj)
+        return fail(KGE_ERR_ARG, "kge_rank_eval_split: TransR needs the projection table");
+    if (!qent || !rel || n_qent <= 0 || n_cent < 0 || n_rel <= 0 || E < 0 || (E && (!h || !r || !t || !ranks)) || !ws || Eb <= 0)
+        return fail(KGE_ERR_ARG, "kge_rank_eval_split: bad argument");
+    if ((filt_ptr == nullptr) != (filt_ids == nullptr))
+        return fail(KGE_ERR_ARG, "kge_rank_eval_split: filt_ptr and filt_ids must be given together");
+    const int64_t N = cand ? n_cand : n_cent;
+    if (N < 0 || N > 0x7fffffff) return fail(KGE_ERR_ARG, "kge_rank_eval_split: bad candidate count %lld", (long long)N);
+    if (N > 0 && !cent) return fail(KGE_ERR_ARG, "kge_rank_eval_split: candidates without a candidate table");
+    if (E == 0) return KGE_OK;
     hipStream_t s = (hipStream_t)stream;
-    Carver cv(ws, ws_bytes);
-    float *A = cv.f((size_t)Eb * d_e), *asq = cv.f(Eb), *P = cv.f(Eb), *bsq = cv.f((size_t)N);
-    float *S = cv.f(std::max((size_t)Eb * (size_t)N, rank_gemm_mask_bytes(Eb, N) / sizeof(float)));
-    float *RV = cv.f((size_t)Eb * d_e);
-    float *THP = cv.f((size_t)Eb * 1024), *TTP = cv.f((size_t)Eb * 1024), *TQ = cv.f((size_t)Eb * 1024), *TSG = cv.f((size_t)Eb * 1024);
-    if (!cv.ok()) return fail(KGE_ERR_WORKSPACE, "kge_rank_eval: workspace too small (%zu < %zu)", ws_bytes,
-                              kge_rank_workspace_bytes(Eb, N, d_e));
-    const bool gemm = use_mfma(model, d_e, (int)N, flags);
-    const bool l2g = gemm && model == KGE_TRANSE_L2;
-    const float rot_div = rot_div_of(emb_init);
-    if (l2g) {       // |b|^2 of every candidate row, once
-        EdgeFwdArgs nb{};
-        nb.B = 0; nb.d_e = d_e; nb.d_r = d_r; nb.model = model; nb.nbase = ent; nb.nidx = cand; nb.n_neg = (int)N;
-        nb.bsq = bsq;
-        KGE_TRY(launch_edge_fwd(nb, s));
+    if (N == 0) {                     // a rank that owns no candidate: every count is 0 (pos_score_out is not written)
+        return hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ranks), 1, (size_t)E, s) == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
     }
-    for (int64_t e0 = 0; e0 < E; e0 += Eb) {
-        const int rows = (int)((E - e0) < Eb ? (E - e0) : Eb);
-        EdgeFwdArgs ef{};
-        ef.src = EdgeSrc{ent, h + e0, ent, t + e0, rel, r + e0};
-        ef.B = rows; ef.d_e = d_e; ef.d_r = d_r; ef.neg_head = neg_head; ef.model = model;
-        ef.gamma = gamma; ef.rot_div = rot_div;
-        ef.pos_score = pos_score_out ? pos_score_out + e0 : P; ef.A = A; ef.asq = l2g ? asq : nullptr;
-        if (model == KGE_TRANSR) {
-            // the training kernels with one chunk = this batch of test triples and the candidates as negatives
-            RescalMatvecArgs m{};
-            m.B = rows; m.D = d_e; m.Dc = d_r; m.rel = proj; m.ridx = r + e0;
-            m.z1 = ent; m.z1idx = h + e0; m.c1 = THP; m.z2 = ent; m.z2idx = t + e0; m.c2 = TTP;
-            KGE_TRY(launch_rescal_matvec(m, s));
-            TransRArgs tr{};
-            tr.B = rows; tr.C = 1; tr.chunk = rows; tr.N = (int)N; tr.De = d_e; tr.Dr = d_r; tr.neg_head = neg_head;
-            tr.gamma = gamma; tr.ent = ent; tr.h_gid = h + e0; tr.t_gid = t + e0; tr.neg_ids = cand; tr.rel_ids = r + e0;
-            tr.rel = rel; tr.proj = const_cast<float *>(proj);
-            tr.HP = THP; tr.TP = TTP; tr.Q = TQ; tr.SG = TSG; tr.P = ef.pos_score; tr.S = S; tr.Z = nullptr;
-            KGE_TRY(launch_transr_pos(tr, s));
-            KGE_TRY(launch_transr_fwd(tr, s));
-        } else if (model == KGE_RESCAL) {
-            RescalMatvecArgs m{};
-            m.B = rows; m.D = d_e; m.rel = rel; m.ridx = r + e0;
-            m.y1 = ent; m.y1idx = t + e0; m.r1 = neg_head ? A : RV;
-            if (!neg_head) { m.y2 = ent; m.y2idx = h + e0; m.r2 = A; }
-            m.pd = ent; m.pdidx = h + e0; m.p = ef.pos_score;
-            KGE_TRY(launch_rescal_matvec(m, s));
-        } else {
-            KGE_TRY(launch_edge_fwd(ef, s));
-        }
-        if (model == KGE_TRANSR) {
-            // scores already in S
-        } else if (gemm && rank_gemm_supported(model, d_e)) {
-            // one tiled GEMM per batch whose epilogue keeps the comparison bits; ranks from the mask (kge_rank_gemm.hip)
-            KGE_TRY(launch_rank_gemm(model, A, rows, ent, cand, N, d_e, gamma, clamp_of(model), asq, bsq,
-                                     pos_score_out ? pos_score_out + e0 : P, S, filt_ptr, filt_ids, e0, ranks, s));
-            continue;
-        } else if (gemm) {
-            GemmArgs g; fill_gemm(g, model, 1, rows, (int)N, d_e, gamma, A, ent, cand);
-            g.S = S; g.asq = asq; g.bsq = bsq;
-            KGE_TRY(launch_neg_fwd_gemm(g, s));
-        } else {
-            NegArgs na; fill_pair(na, model, 1, rows, (int)N, d_e, gamma, A, ent, cand);
-            na.S = S;
-            KGE_TRY(launch_neg_fwd_pair(na, s));
-        }
-        KGE_TRY(launch_rank_count(S, pos_score_out ? pos_score_out + e0 : P, rows, N, filt_ptr, filt_ids, e0, ranks, s));
-    }
-    return KGE_OK;
+    if (model == KGE_TRANSR && !cand)
+        return fail(KGE_ERR_ARG, "kge_rank_eval_split: TransR needs an explicit candidate list");
+    return rank_eval_impl(model, neg_head, qent, cent, rel, proj, h, r, t, E, d_e, d_r, gamma, emb_init, cand, N, filt_ptr, filt_ids,
+                          Eb, ranks, pos_score_out, ws, ws_bytes, flags, s);
 }
 
 int kge_step_sharded(const kge_hparams *hp, const kge_shards *sh, const kge_batch *b,

@@ -638,6 +638,7 @@ struct TransRArgs {
     int B, C, chunk, N, De, Dr, neg_head, UR, reg_norm;
     float gamma, lr, eps, reg_coef;
     const float *ent; const int64_t *h_gid, *t_gid, *neg_ids, *rel_ids;
+    const float *cent;               // candidate (negative) rows: neg_ids index this table; null = ent (training)
     const float *rel; float *proj, *proj_state;
     float *HP, *TP, *Q, *SG;         // [B, Dr] projected head / tail, q = x P - r, sign(hp + r - tp)
     float *P;                        // [B] positive scores

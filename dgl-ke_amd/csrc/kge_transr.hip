@@ -188,6 +188,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void transr_fwd_kernel(TransRArgs a, int
     __syncthreads();
     const float *Pi = a.proj + a.rel_ids[i] * (int64_t)De * Dr;
     const float *Qi = a.Q + (int64_t)i * Dr;
+    const float *cb = a.cent ? a.cent : a.ent;      // candidate rows
     float d[4] = {0.f, 0.f, 0.f, 0.f};
     for (int dr0 = 0; dr0 < Dr; dr0 += TR_T) {
         f32x4 acc[4];
@@ -198,12 +199,12 @@ __global__ __launch_bounds__(KGE_BLOCK) void transr_fwd_kernel(TransRArgs a, int
         if constexpr (VEC)
             tile_sweep4<false, true>(acc, De,
                 [&](int row, int k0_, int kk_) { const int k = k0_ + kk_; const int64_t o = rowoff[row];
-                                      return (o >= 0 && k < De) ? *reinterpret_cast<const float4 *>(a.ent + o + k) : f4zero(); },
+                                      return (o >= 0 && k < De) ? *reinterpret_cast<const float4 *>(cb + o + k) : f4zero(); },
                 [&](int k0_, int kk_, int col) { const int k = k0_ + kk_; return (k < De && dr0 + col < Dr) ? *reinterpret_cast<const float4 *>(Pi + (int64_t)k * Dr + dr0 + col)
                                                                         : f4zero(); }, As, Bs, won ? nct : 0);
         else
         tile_sweep<true, false>(acc, De,
-            [&](int row, int k0_, int kk_) { const int k = k0_ + kk_; const int64_t o = rowoff[row]; return (o >= 0 && k < De) ? a.ent[o + k] : 0.f; },
+            [&](int row, int k0_, int kk_) { const int k = k0_ + kk_; const int64_t o = rowoff[row]; return (o >= 0 && k < De) ? cb[o + k] : 0.f; },
             [&](int k0_, int kk_, int col) { const int k = k0_ + kk_; return (k < De && dr0 + col < Dr) ? Pi[(int64_t)k * Dr + dr0 + col] : 0.f; }, As, Bs, won ? nct : 0);
 #pragma unroll
         for (int ct = 0; ct < 4; ++ct) {
@@ -348,7 +349,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void transr_gn_reduce_kernel(TransRArgs 
     if (row >= rows) return;
     const int lane = threadIdx.x & 63, De = a.De;
     const bool reg = a.reg_coef > 0.f && a.reg_norm > 0 && !a.nd_chunk;      // (neg_deg_sample: added by the update kernel, sampled rows only)
-    const float *x = a.ent + a.neg_ids[row] * (int64_t)De;
+    const float *x = (a.cent ? a.cent : a.ent) + a.neg_ids[row] * (int64_t)De;
     for (int d = lane; d < De; d += 64) {
         float v = 0.f;
         int g = 0;
@@ -378,6 +379,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void transr_gp_kernel(TransRArgs a, int 
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63, m = lane & 15, q = lane >> 4;
     int64_t *s_off = reinterpret_cast<int64_t *>(gp_dyn);
     float *s_w = reinterpret_cast<float *>(s_off + N);
+    const float *cb = a.cent ? a.cent : a.ent;      // negative rows
     for (int k = t; k < N; k += KGE_BLOCK) {
         s_off[k] = a.neg_ids[(int64_t)c * N + k] * (int64_t)De;
         s_w[k] = -a.S[(int64_t)i * N + k];
@@ -392,7 +394,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void transr_gp_kernel(TransRArgs a, int 
         tile_sweep4<true, true>(acc, N,
             [&](int row, int k0_, int kk_) {          // Neg_k[de0 + row .. +3]
                 const int k = k0_ + kk_;
-                return (k < N && de0 + row < De) ? *reinterpret_cast<const float4 *>(a.ent + s_off[k] + de0 + row) : f4zero();
+                return (k < N && de0 + row < De) ? *reinterpret_cast<const float4 *>(cb + s_off[k] + de0 + row) : f4zero();
             },
             [&](int k0_, int kk_, int col) {          // dY_ik[dr0 + col .. +3]: one word of sign bytes
                 const int k = k0_ + kk_;
@@ -403,7 +405,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void transr_gp_kernel(TransRArgs a, int 
     tile_sweep<false, false>(acc, N,
         [&](int row, int k0_, int kk_) {
             const int k = k0_ + kk_;
-            return (k < N && de0 + row < De) ? a.ent[s_off[k] + de0 + row] : 0.f;
+            return (k < N && de0 + row < De) ? cb[s_off[k] + de0 + row] : 0.f;
         },
         [&](int k0_, int kk_, int col) {
             const int k = k0_ + kk_;

@@ -138,6 +138,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void transr_fwd_wide_kernel(TransRArgs a
     __syncthreads();
     const float *Pi = a.proj + a.rel_ids[i] * (int64_t)De * Dr;
     const float *Qi = a.Q + (int64_t)i * Dr;
+    const float *cb = a.cent ? a.cent : a.ent;      // candidate rows
     f32x4 acc[TW_NRB][TW_NCB];
 #pragma unroll
     for (int rbk = 0; rbk < TW_NRB; ++rbk)
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void transr_fwd_wide_kernel(TransRArgs a
     float4 nosum;
     wide_sweep<false, true, false>(acc, De,
         [&](int row, int k0_, int kk_) { const int k = k0_ + kk_; const int64_t o = rowoff[row];
-                                         return (o >= 0 && k < De) ? *reinterpret_cast<const float4 *>(a.ent + o + k) : f4zero(); },
+                                         return (o >= 0 && k < De) ? *reinterpret_cast<const float4 *>(cb + o + k) : f4zero(); },
         [&](int k0_, int kk_, int col) { const int k = k0_ + kk_;
                                          return (k < De && col < Dr) ? *reinterpret_cast<const float4 *>(Pi + (int64_t)k * Dr + col) : f4zero(); },
         As, Bs, nrb, (Dr + 15) / 16, nosum);
@@ -271,6 +272,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void transr_gp_wide_kernel(TransRArgs a,
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63, m = lane & 15, q = lane >> 4;
     int64_t *s_off = reinterpret_cast<int64_t *>(gpw_dyn);
     float *s_w = reinterpret_cast<float *>(s_off + N), *s_dq = s_w + N;
+    const float *cb = a.cent ? a.cent : a.ent;      // negative rows
     for (int k = t; k < N; k += KGE_BLOCK) {
         s_off[k] = a.neg_ids[(int64_t)c * N + k] * (int64_t)De;
         s_w[k] = -a.S[(int64_t)i * N + k];
@@ -281,7 +283,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void transr_gp_wide_kernel(TransRArgs a,
     auto loadA = [&](int de0) {
         return [&, de0](int row, int k0_, int kk_) {  // Neg_k[de0 + row .. + 3]
             const int k = k0_ + kk_;
-            return (k < N && de0 + row < De) ? *reinterpret_cast<const float4 *>(a.ent + s_off[k] + de0 + row) : f4zero();
+            return (k < N && de0 + row < De) ? *reinterpret_cast<const float4 *>(cb + s_off[k] + de0 + row) : f4zero();
         };
     };
     auto loadB = [&](int k0_, int kk_, int col) {     // dY_ik[col .. + 3]: one word of sign bytes

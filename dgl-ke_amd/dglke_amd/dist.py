@@ -1211,15 +1211,20 @@ def choose_relation_partition(rels, world, policy="auto", tolerance=1.1):
     return "soft", part, owner, cross
 
 
-def relation_rows_from_owners(rel, rel_state, owner, group=None):
+def relation_rows_from_owners(rel, rel_state, owner, group=None, everywhere=False):
     """after training with rel_local: every rank's replica holds the current rows of ITS relations only - collect the owners' rows
-    into rank 0's replica (gather through the process group; relations nobody owns keep their initial rows)."""
+    into rank 0's replica, or with `everywhere` into every rank's (gather / all-gather through the process group; relations
+    nobody owns keep their initial rows)."""
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     own = torch.as_tensor(np.nonzero(np.asarray(owner) == rank)[0], dtype=torch.int64)
     mine = (own, rel[own.to(rel.device)].cpu(), rel_state[own.to(rel.device)].cpu())
-    parts = [None] * world if rank == 0 else None
-    dist.gather_object(mine, parts, dst=0, group=group)
-    if rank == 0:
+    if everywhere:
+        parts = [None] * world
+        dist.all_gather_object(parts, mine, group=group)
+    else:
+        parts = [None] * world if rank == 0 else None
+        dist.gather_object(mine, parts, dst=0, group=group)
+    if rank == 0 or everywhere:
         for ids, rows, st in parts:
             if len(ids):
                 rel[ids.to(rel.device)] = rows.to(rel.device)
@@ -1237,3 +1242,31 @@ def localize_plan(h, t, r, neg, chunk, N, neg_head, edge_w=None):
                          np.searchsorted(ue, neg), chunk, N, neg_head, edge_w)
     assert p["UE"] == ue.shape[0]
     return ue, p
+
+
+def write_npy_sharded(path, local, lo, n_rows, group=None, max_copy_bytes=256 << 20):
+    """write a range-sharded float32 table into ONE .npy file, byte for byte what np.save writes for the assembled table:
+    rank 0 creates the file at the full shape (np.lib.format.open_memmap), then every rank writes its rows [lo, lo + len(local))
+    through a host staging buffer of at most max_copy_bytes, reused copy after copy.  Collective over `group`.  Returns the
+    staging buffer's size in bytes."""
+    n_rows, d = int(n_rows), int(local.shape[1])
+    if dist.get_rank(group) == 0:
+        mm = np.lib.format.open_memmap(path, mode="w+", dtype=np.float32, shape=(n_rows, d))
+        mm.flush()
+        del mm
+    dist.barrier(group=group)
+    n_local = int(local.shape[0])
+    staged = 0
+    if n_local and d:
+        per = max(1, min(n_local, int(max_copy_bytes) // (4 * d)))
+        buf = torch.empty(per, d, dtype=torch.float32)
+        staged = buf.numel() * 4
+        mm = np.load(path, mmap_mode="r+")
+        for a in range(0, n_local, per):
+            b = min(n_local, a + per)
+            buf[:b - a].copy_(local[a:b])
+            mm[lo + a:lo + b] = buf[:b - a].numpy()
+        mm.flush()
+        del mm
+    dist.barrier(group=group)
+    return staged

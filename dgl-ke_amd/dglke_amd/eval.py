@@ -154,25 +154,27 @@ def sampled_ranks(rk, h, r, t, neg_head, filt, n_entities, n_cand, chunk, rng, c
         e1 = min(E, e0 + chunk)
         cand = cand_of_chunk(k) if cand_of_chunk is not None else rng.randint(0, n_entities, size=n_cand)
         cand = np.asarray(cand, np.int64)
-        f = None
-        if filt is not None:
-            # columns of this chunk's candidate list that hold a filtered entity, per triple (duplicates in the draw
-            # are separate columns): sorted candidates + two binary searches per filtered id
-            order = np.argsort(cand, kind="stable")
-            sc = cand[order]
-            frng, fids = filt
-            ptr, cols = [0], []
-            for i in range(e0, e1):
-                ids = fids[frng[i, 0]:frng[i, 1]]
-                lo, hi = np.searchsorted(sc, ids, "left"), np.searchsorted(sc, ids, "right")
-                hit = [order[a:b] for a, b in zip(lo, hi) if b > a]
-                c = np.concatenate(hit) if hit else np.zeros(0, np.int64)
-                cols.append(c)
-                ptr.append(ptr[-1] + c.shape[0])
-            ptr = np.asarray(ptr, np.int64)
-            f = (np.stack([ptr[:-1], ptr[1:]], 1), np.concatenate(cols) if cols else np.zeros(0, np.int64))
+        f = filter_columns(cand, filt, e0, e1) if filt is not None else None
         out.append(rk.ranks(h[e0:e1], r[e0:e1], t[e0:e1], neg_head, f, cand=cand))
     return torch.cat(out)
+
+
+def filter_columns(cand, filt, e0, e1):
+    """columns of the candidate list `cand` that hold a filtered entity, per test triple e0 .. e1 - 1 (duplicates in the draw
+    are separate columns): sorted candidates + two binary searches per filtered id.  Returns (rng [e1 - e0, 2], cols)."""
+    order = np.argsort(cand, kind="stable")
+    sc = cand[order]
+    frng, fids = filt
+    ptr, cols = [0], []
+    for i in range(e0, e1):
+        ids = fids[frng[i, 0]:frng[i, 1]]
+        lo, hi = np.searchsorted(sc, ids, "left"), np.searchsorted(sc, ids, "right")
+        hit = [order[a:b] for a, b in zip(lo, hi) if b > a]
+        c = np.concatenate(hit) if hit else np.zeros(0, np.int64)
+        cols.append(c)
+        ptr.append(ptr[-1] + c.shape[0])
+    ptr = np.asarray(ptr, np.int64)
+    return np.stack([ptr[:-1], ptr[1:]], 1), np.concatenate(cols) if cols else np.zeros(0, np.int64)
 
 
 def evaluate(model_name, ent, rel, gamma, emb_init, test, known=None, batch=1024, modes=("head", "tail"), proj=None,
@@ -215,3 +217,193 @@ def evaluate(model_name, ent, rel, gamma, emb_init, test, known=None, batch=1024
         else:
             allr.append(rk.ranks(th_, tr_, tt_, neg_head, filt))
     return metrics_from_ranks(torch.cat(allr))
+
+
+# ---- range-sharded tables ---------------------------------------------------------------------------------------------------
+# The multi-GPU trainers keep the entity table range-sharded: rank k owns rows [lo_k, hi_k).  The evaluation below never assembles
+# it: every rank scores ALL test triples against the candidates IT owns (kge_rank_eval_split) and the counts are summed over the
+# ranks.  (The reference splits the test triples over its processes instead, each scoring against one shared host table:
+# train.py:230-257, 330-350; train_pytorch.py:199-253.)
+
+def shard_known(known, neg_head, lo, hi):
+    """the known triples whose corrupted entity (the head when neg_head, else the tail) lies in [lo, hi), that entity shifted
+    by -lo: their filter lists (build_filter / build_filter_device) are this rank's share of the full lists, as columns of its
+    shard."""
+    kh, kr, kt = (np.asarray(x, np.int64) for x in known)
+    side = kh if neg_head else kt
+    m = (side >= lo) & (side < hi)
+    kh, kr, kt = kh[m], kr[m], kt[m]
+    if neg_head:
+        kh = kh - lo
+    else:
+        kt = kt - lo
+    return kh, kr, kt
+
+
+def owned_candidates(cand, lo, hi):
+    """the positions of a candidate list that a rank owning [lo, hi) scores, and their rows in its shard (duplicates stay
+    separate columns)."""
+    cand = np.asarray(cand, np.int64)
+    pos = np.nonzero((cand >= lo) & (cand < hi))[0]
+    return pos, cand[pos] - lo
+
+
+def allgather_rows(local, lo, bounds, ids, comm):
+    """rows `ids` (sorted, unique, global; a device tensor every rank passes alike) of a range-sharded table: every owner
+    contributes the rows it holds through ONE equal-split all-gather (`comm`: dist.RcclComm / HostStagedComm / TorchComm) and
+    every rank receives all of them - copies, bit for bit (a summing all-reduce would turn -0.0 into +0.0)."""
+    world = len(bounds) - 1
+    cut = torch.searchsorted(ids, torch.as_tensor(np.asarray(bounds, np.int64), device=ids.device)).cpu().numpy()
+    cnt = cut[1:] - cut[:-1]
+    cap = int(cnt.max())
+    rank = comm.rank
+    d = local.shape[1]
+    send = torch.zeros(cap, d, dtype=local.dtype, device=local.device)
+    if cnt[rank]:
+        send[:cnt[rank]] = local[ids[cut[rank]:cut[rank + 1]] - lo]
+    recv = torch.empty(world * cap, d, dtype=local.dtype, device=local.device)
+    comm.all_gather(recv, send)
+    return torch.cat([recv[k * cap:k * cap + cnt[k]] for k in range(world)])
+
+
+class SplitRanker(object):
+    """kge_rank_eval_split on one rank's shard: query rows given per call, candidates = (a subset of) the shard."""
+
+    def __init__(self, model_name, shard, rel, gamma, emb_init, batch=1024, flags=0, proj=None):
+        if not rel.is_cuda:
+            raise _lib.KgeError("SplitRanker needs CUDA (HIP) tensors; there is no CPU path")
+        if model_name == 'TransR' and proj is None:
+            raise _lib.KgeError("TransR ranking needs the projection table (proj=...)")
+        self.model = _lib.model_id(model_name)
+        self.shard, self.rel, self.proj = shard, rel, proj
+        self.gamma, self.emb_init = float(gamma), float(emb_init)
+        self.batch, self.flags = int(batch), int(flags)
+        self._ws = None
+        self._all = None
+
+    def ranks(self, qent, h, r, t, neg_head, filt=None, cand=None):
+        """int32 [E]: 1 + #{unfiltered candidates of this shard scoring >= the true triple}; h / t index qent."""
+        dev = self.rel.device
+
+        def put(x, dt=torch.int64):
+            if x is None:
+                return None
+            if isinstance(x, torch.Tensor):
+                return x.to(dev, dt).contiguous()
+            return torch.as_tensor(np.ascontiguousarray(x)).to(dev, dt)
+        h, r, t, cand = put(h), put(r), put(t), put(cand)
+        E = int(h.shape[0])
+        n_cent = int(self.shard.shape[0])
+        if cand is None and self.proj is not None:         # TransR kernels walk an explicit candidate list
+            if self._all is None:
+                self._all = torch.arange(n_cent, dtype=torch.int64, device=dev)
+            cand = self._all
+        n_cand = int(cand.shape[0]) if cand is not None else n_cent
+        if cand is not None and n_cand == 0:               # none of a sampled list is ours (an empty list has no pointer)
+            cand, n_cent = None, 0
+        frng = fids = None
+        if filt is not None:
+            frng, fids = put(filt[0].reshape(-1)), put(filt[1])
+            if fids.shape[0] == 0:
+                fids = torch.zeros(1, dtype=torch.int64, device=dev)
+        Eb = max(1, min(self.batch, E))
+        need = _lib.lib().kge_rank_workspace_bytes(Eb, n_cand, qent.shape[1])
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need + 4096, dtype=torch.uint8, device=dev)
+        ranks = torch.zeros(E, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().kge_rank_eval_split(
+            self.model, int(bool(neg_head)), _lib.ptr(qent), qent.shape[0], _lib.ptr(self.shard), n_cent, _lib.ptr(self.rel),
+            self.rel.shape[0], _lib.ptr(self.proj), _lib.ptr(h), _lib.ptr(r), _lib.ptr(t), E, qent.shape[1], self.rel.shape[1],
+            self.gamma, self.emb_init, _lib.ptr(cand), n_cand, _lib.ptr(frng), _lib.ptr(fids), Eb, _lib.ptr(ranks), None,
+            _lib.ptr(self._ws), self._ws.numel(), self.flags, _lib.stream_ptr()))
+        return ranks
+
+
+def evaluate_sharded(model_name, shard, lo, n_entities, rel, gamma, emb_init, test, rows_of, known=None, batch=1024,
+                     modes=("head", "tail"), proj=None, n_cand=None, chunk=None, seed=0, cache=None, group=None,
+                     block_bytes=64 << 20):
+    """`evaluate` on a range-sharded entity table, collective over `group` (every rank calls it with the same arguments but its
+    own shard = rows [lo, lo + len(shard)) of the table).  rows_of(ids): the rows of the sorted unique global ids `ids` on this
+    rank (collective: ShardedTables.gather, or allgather_rows).  rel / proj: the WHOLE relation-side tables on every rank.
+
+    Every rank ranks every test triple against the candidates it owns - the whole shard, or with n_cand the owned positions of
+    each chunk's draw, drawn exactly as `sampled_ranks` draws them (same seed, same order) - with the filter lists restricted to
+    its entities; 1 + the sum of the ranks' counts is `evaluate`'s rank, and the metrics are computed from the same tensor.
+    The query rows (heads and tails of the test triples) are assembled in blocks of at most ~block_bytes."""
+    import torch.distributed as dist
+    th_, tr_, tt_ = (np.asarray(x, np.int64) for x in test)
+    E = th_.shape[0]
+    n_ent = int(n_entities)
+    hi = lo + int(shard.shape[0])
+    sampled = n_cand is not None and 0 < n_cand < n_ent
+    chunk = int(chunk or batch)
+    rng = np.random.RandomState(seed)
+    dev = rel.device
+    rk = SplitRanker(model_name, shard, rel, gamma, emb_init, batch, proj=proj)
+    if cache is not None and "test" in cache:
+        tdev = cache["test"]
+    else:
+        tdev = tuple(torch.as_tensor(np.ascontiguousarray(x)).to(dev) for x in (th_, tr_, tt_))
+        if cache is not None:
+            cache["test"] = tdev
+    filt = {}
+    for mode in modes:
+        if known is None:
+            filt[mode] = None
+            continue
+        key = ("filt", mode, sampled, lo, hi)
+        if cache is not None and key in cache:
+            filt[mode] = cache[key]
+            continue
+        neg_head = mode == "head"
+        kn = shard_known(known, neg_head, lo, hi)
+        f = build_filter_device(kn, tdev, neg_head, rel.shape[0], n_ent, dev)
+        if sampled and f is not None:
+            f = (f[0].cpu().numpy(), f[1].cpu().numpy())
+        if f is None:
+            f = build_filter(kn[0], kn[1], kn[2], th_, tr_, tt_, neg_head, rel.shape[0])
+            if not sampled:
+                f = (torch.as_tensor(f[0]).to(dev), torch.as_tensor(f[1]).to(dev))
+        if cache is not None:
+            cache[key] = f
+        filt[mode] = f
+    # blocks of test triples: whole evaluation batches (all entities) / whole chunks (sampled), so that every kernel call ranks
+    # the same rows as `evaluate` does
+    unit = chunk if sampled else max(1, min(int(batch), E))
+    per = max(1, int(block_bytes) // max(1, 8 * int(shard.shape[1]) * unit)) * unit
+    counts = torch.zeros(len(modes) * E, dtype=torch.int64, device=dev)
+    # the sampled protocol draws every chunk of the first mode, then of the second: modes outside the blocks
+    for group_modes in ([[m] for m in modes] if sampled else [list(modes)]):
+        for b0 in range(0, E, per):
+            b1 = min(E, b0 + per)
+            ids, inv = torch.unique(torch.cat([tdev[0][b0:b1], tdev[2][b0:b1]]), return_inverse=True)
+            qent = rows_of(ids).contiguous()
+            qh, qt = inv[:b1 - b0].contiguous(), inv[b1 - b0:].contiguous()
+            qr = tdev[1][b0:b1]
+            for mode in group_modes:
+                neg_head = mode == "head"
+                mi = modes.index(mode)
+                f = filt[mode]
+                if not sampled:
+                    fb = (f[0][b0:b1], f[1]) if f is not None else None
+                    counts[mi * E + b0:mi * E + b1] = rk.ranks(qent, qh, qr, qt, neg_head, fb).to(torch.int64) - 1
+                    continue
+                for e0 in range(b0, b1, chunk):
+                    e1 = min(b1, e0 + chunk)
+                    cand = rng.randint(0, n_ent, size=int(n_cand))
+                    pos, local = owned_candidates(cand, lo, hi)
+                    fc = None
+                    if f is not None:
+                        fc = filter_columns(local, f, e0, e1)
+                    got = rk.ranks(qent, qh[e0 - b0:e1 - b0], qr[e0 - b0:e1 - b0], qt[e0 - b0:e1 - b0], neg_head, fc,
+                                   cand=local)
+                    counts[mi * E + e0:mi * E + e1] = got.to(torch.int64) - 1
+    if dist.is_initialized() and dist.get_world_size(group) > 1:
+        if dist.get_backend(group) == "gloo":
+            host = counts.cpu()
+            dist.all_reduce(host, group=group)
+            counts = host.to(dev)
+        else:
+            dist.all_reduce(counts, group=group)
+    ranks = (counts + 1).to(torch.int32)
+    return metrics_from_ranks(ranks)

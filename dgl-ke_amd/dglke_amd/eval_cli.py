@@ -34,7 +34,7 @@ class ArgParser(argparse.ArgumentParser):
         a('-g', '--gamma', type=float, default=12.0)
         a('--eval_percent', type=float, default=1)
         a('--no_eval_filter', action='store_true')
-        a('--gpu', type=int, default=[-1], nargs='+')
+        a('--gpu', type=int, default=[-1], nargs='+')    # several entries: one process per entry, each ranking against its rows
         a('--mix_cpu_gpu', action='store_true')           # accepted, no effect: the tables live in HBM
         a('-de', '--double_ent', action='store_true')
         a('-dr', '--double_rel', action='store_true')
@@ -53,6 +53,8 @@ def main(argv=None):
         raise KgeError("dglke_eval ranks on the GPU only: pass --gpu <id> (there is no CPU fallback)")
     if not os.path.isdir(args.model_path):
         raise KgeError("No existing model_path: {}".format(args.model_path))
+    if len(args.gpu) > 1:
+        return launch_sharded(args)
     dev = th.device("cuda", args.gpu[0])
     th.cuda.set_device(dev)
     ds = get_dataset(args.data_path, args.dataset, args.format, args.delimiter, args.data_files)
@@ -91,6 +93,87 @@ def main(argv=None):
         print('[{}]{} average {}: {}'.format(0, 'Test', k, v))          # train_pytorch.py:236-247 format
     print('Test takes {:.3f} seconds'.format(time.time() - start))
     return metrics
+
+
+def _sharded_worker(rank, args, port):
+    """one of the `--gpu g0 g1 ...` processes: maps only its row range of the entity file, loads the relation-side tables whole
+    and ranks the test triples against its rows (eval.evaluate_sharded); the row exchange goes through RCCL when every process
+    has its own GPU, through the gloo group when they share one (like dglke_train's trainers)."""
+    import torch.distributed as dist
+    from . import dist as kd
+    from . import eval as kev
+    world = len(args.gpu)
+    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
+    comm = None
+    try:
+        dev = th.device("cuda", args.gpu[rank])
+        th.cuda.set_device(dev)
+        if rank != 0:                            # one copy of the loader messages is enough
+            sys.stdout = open(os.devnull, "w")
+        ds = get_dataset(args.data_path, args.dataset, args.format, args.delimiter, args.data_files)
+        sys.stdout = sys.__stdout__
+        if ds.test is None:
+            raise KgeError("the dataset has no test split")
+        model = 'TransE_l2' if args.model_name == 'TransE' else args.model_name
+        stem = os.path.join(args.model_path, '{}_{}_'.format(args.dataset, args.model_name))
+
+        def path(name):
+            f = stem + name + '.npy' if name != 'projection' else stem[:-1] + 'projection.npy'
+            if not os.path.exists(f):
+                raise KgeError("missing embedding file {}".format(f))
+            return f
+        full = np.load(path('entity'), mmap_mode='r')
+        d_e = args.hidden_dim * (2 if args.double_ent else 1)
+        if full.shape != (ds.n_entities, d_e):
+            raise KgeError("entity embeddings are {} but the dataset / flags say {}".format(tuple(full.shape), (ds.n_entities, d_e)))
+        spec = kd.ShardSpec(ds.n_entities, world, rank)
+        shard = th.from_numpy(np.ascontiguousarray(full[spec.lo:spec.hi])).to(dev, th.float32).contiguous()
+        del full
+        rel = th.from_numpy(np.load(path('relation'))).to(dev, th.float32).contiguous()
+        proj = th.from_numpy(np.load(path('projection'))).to(dev, th.float32).contiguous() if model == 'TransR' else None
+        comm = kd.make_comm() if len(set(args.gpu)) == world else kd.HostStagedComm()
+        emb_init = (args.gamma + 2.0) / args.hidden_dim
+        h, r, t = (np.asarray(x) for x in ds.test[:3])
+        if args.eval_percent < 1:
+            keep = np.random.RandomState(args.seed + 17).permutation(len(h))[:max(1, int(len(h) * args.eval_percent))]
+            h, r, t = h[keep], r[keep], t[keep]
+        known = None
+        if args.eval_filter:
+            parts = [p for p in (ds.train, ds.valid, ds.test) if p is not None]
+            known = tuple(np.concatenate([np.asarray(p[k]) for p in parts]) for k in range(3))
+        Eb = int(max(1, min(max(args.batch_size_eval, 4096), (1 << 31) // (4 * ds.n_entities), len(h))))
+        if proj is not None:
+            Eb = min(Eb, 64)
+        start = time.time()
+        metrics = kev.evaluate_sharded(model, shard, spec.lo, ds.n_entities, rel, args.gamma, emb_init, (h, r, t),
+                                       lambda ids: kev.allgather_rows(shard, spec.lo, spec.bounds(), ids, comm), known, batch=Eb,
+                                       proj=proj, n_cand=args.neg_sample_size_eval if args.neg_sample_size_eval > 0 else None,
+                                       chunk=args.batch_size_eval, seed=args.seed + 29)
+        if rank == 0:
+            for k, v in metrics.items():
+                print('[{}]{} average {}: {}'.format(0, 'Test', k, v))          # train_pytorch.py:236-247 format
+            print('Test takes {:.3f} seconds'.format(time.time() - start))
+            print('sharded evaluation: world size {}, entity rows per rank {}'.format(
+                world, [int(b - a) for a, b in zip(spec.bounds()[:-1], spec.bounds()[1:])]))
+            sys.stdout.flush()
+    finally:
+        if comm is not None and hasattr(comm, "close"):
+            comm.close()
+        dist.destroy_process_group()
+
+
+def launch_sharded(args):
+    """`--gpu g0 g1 ...`: one process per entry (the same GPU may be listed twice: the processes then share it), the gloo
+    bootstrap of dglke_train's trainers (train._mp_worker)."""
+    import socket
+    import torch.multiprocessing as mp
+    if min(args.gpu) < 0:
+        raise KgeError("dglke_eval ranks on the GPU only: pass --gpu <ids> (there is no CPU fallback)")
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    mp.spawn(_sharded_worker, args=(args, port), nprocs=len(args.gpu), join=True)
+    return None
 
 
 if __name__ == '__main__':

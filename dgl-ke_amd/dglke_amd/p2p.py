@@ -209,10 +209,10 @@ class ShardedTables(object):
             idx.shape[0], _lib.ptr(out), _lib.stream_ptr()))
         return out if dim > 1 else out.view(-1)
 
-    def collect_relations(self, owner, group=None):
+    def collect_relations(self, owner, group=None, everywhere=False):
         """rel_local: every rank's relation-side tables hold the current rows of ITS relations only (owner[r] = rank of relation r,
-        dist.relation_partition) - bring the owners' rows (relation rows + state, projection rows + state) into rank 0's tables.
-        Collective over the process group."""
+        dist.relation_partition) - bring the owners' rows (relation rows + state, projection rows + state) into rank 0's tables,
+        or with `everywhere` into every rank's (the sharded evaluation ranks on every rank).  Collective over the process group."""
         import numpy as np
         import torch.distributed as dist
         if not self.rel_local:
@@ -221,11 +221,15 @@ class ShardedTables(object):
         own = torch.as_tensor(np.nonzero(np.asarray(owner) == rank)[0], dtype=torch.int64)
         tabs = [t for t in (self.rel_tab, self.rel_state_tab, self.proj_tab, self.proj_state_tab) if t is not None]
         mine = (own, [t[own.to(self.dev)].cpu() for t in tabs])
-        parts = [None] * world if rank == 0 else None
-        dist.gather_object(mine, parts, dst=0, group=group)
-        if rank == 0:
-            for ids, rows in parts[1:]:
-                if len(ids):
+        if everywhere:
+            parts = [None] * world
+            dist.all_gather_object(parts, mine, group=group)
+        else:
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(mine, parts, dst=0, group=group)
+        if rank == 0 or everywhere:
+            for k, (ids, rows) in enumerate(parts):
+                if k != rank and len(ids):
                     for t, r in zip(tabs, rows):
                         t[ids.to(self.dev)] = r.to(self.dev)
 

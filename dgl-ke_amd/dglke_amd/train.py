@@ -499,27 +499,60 @@ class ShardedTrainer(object):
         self.lane.enqueue(n)
 
     def sync_tables(self):
-        """collective point in front of rank 0's validation / test / save: the peer-mapped tables need nothing; relation-side tables
-        that are local to the trainers (TransR / RESCAL) are collected from the relations' owners into rank 0's."""
+        """collective point in front of a validation / test / save: the peer-mapped tables need nothing; relation-side tables
+        that are local to the trainers (TransR / RESCAL) are collected from the relations' owners into every rank's (every rank
+        ranks against its own shard)."""
         if self.rel_side_local:
             th.cuda.synchronize()
-            self.tabs.collect_relations(self.rel_owner)
+            self.tabs.collect_relations(self.rel_owner, everywhere=True)
 
     def close(self):
         self.tabs.close()
 
     def projection(self):
-        """TransR: the projection table as rank 0 holds it after sync_tables()"""
+        """TransR: the projection table as every rank holds it after sync_tables()"""
         return self.tabs.proj_tab
 
-    def full_tables(self):
-        """the whole entity / relation tables read through the shard map (rank-local copies)."""
-        ds = self.dataset
-        ent = self.tabs.gather("ent", th.arange(ds.n_entities, device=self.dev))
-        rel = self.tabs.rel_tab if self.tabs.rel_local else self.tabs.gather("rel", th.arange(ds.n_relations, device=self.dev))
-        return ent, rel
+    def entity_shard(self):
+        """(lo, rows [lo, hi) of the entity table that this rank holds)"""
+        per, n = self.tabs.ent_per, self.dataset.n_entities
+        lo = min(self.rank * per, n)
+        return lo, self.tabs.ent()[:min(lo + per, n) - lo]
+
+    def entity_rows(self, ids):
+        """rows of the sorted unique global ids `ids` on this rank (collective in the all-to-all trainer)"""
+        return self.tabs.gather("ent", ids)
+
+    def relation_table(self):
+        """the whole relation table on this rank"""
+        if self.tabs.rel_local:
+            return self.tabs.rel_tab
+        return self.tabs.gather("rel", th.arange(self.dataset.n_relations, device=self.dev))
+
+    def save(self, emap_file, rmap_file):
+        """<dataset>_<model>_entity.npy written shard by shard into one file (dist.write_npy_sharded), the relation-side tables
+        and config.json from rank 0.  Collective: every rank calls it after sync_tables()."""
+        import torch.distributed as dist
+        from . import dist as kd
+        args = self.args
+        rel = self.relation_table()
+        lo, shard = self.entity_shard()
+        kd.write_npy_sharded(os.path.join(args.save_path, '%s_%s_entity.npy' % (args.dataset, args.model_name)), shard, lo,
+                             self.dataset.n_entities)
+        if self.rank == 0:
+            np.save(os.path.join(args.save_path, '%s_%s_relation.npy' % (args.dataset, args.model_name)), rel.cpu().numpy())
+            if args.model_name == 'TransR':      # TransRScore.save (score_fun.py:190-191): <dataset>_<model>projection.npy
+                np.save(os.path.join(args.save_path, '%s_%sprojection.npy' % (args.dataset, args.model_name)),
+                        self.projection().cpu().numpy())
+            conf = dict(vars(args))
+            conf.update({'emp_file': emap_file, 'rmap_file': rmap_file})
+            with open(os.path.join(args.save_path, 'config.json'), 'w') as f:
+                json.dump(conf, f, indent=4)
+        dist.barrier()
 
     def evaluate(self, which, mode):
+        """`--valid` / `--test` on the sharded table, collective: every rank ranks the split against the entities it holds
+        (eval.evaluate_sharded); rank 0 prints the metrics."""
         from . import eval as kev
         args, ds = self.args, self.dataset
         trip = getattr(ds, which)
@@ -533,16 +566,19 @@ class ShardedTrainer(object):
         if args.eval_filter:
             parts = [p for p in (ds.train, ds.valid, ds.test) if p is not None]
             known = tuple(np.concatenate([np.asarray(p[k]) for p in parts]) for k in range(3))
-        ent, rel = self.full_tables()
+        rel = self.relation_table()
+        lo, shard = self.entity_shard()
         Eb = int(max(1, min(max(args.batch_size_eval, 4096), (1 << 31) // (4 * ds.n_entities), len(h))))
         proj = self.projection() if args.model_name == 'TransR' else None
         if proj is not None:
             Eb = min(Eb, 64)                  # TransR projects every candidate with every test triple's matrix
         cache = self.__dict__.setdefault('_eval_cache', {}).setdefault(which, {})
-        metrics = kev.evaluate(args.model_name, ent, rel, args.gamma, self.emb_init, (h, r, t), known, batch=Eb, proj=proj,
-                               n_cand=args.neg_sample_size_eval, chunk=args.batch_size_eval, seed=args.seed + 29, cache=cache)
-        for k, v in metrics.items():
-            print('[{}]{} average {}: {}'.format(self.rank, mode, k, v))
+        metrics = kev.evaluate_sharded(args.model_name, shard, lo, ds.n_entities, rel, args.gamma, self.emb_init, (h, r, t),
+                                       self.entity_rows, known, batch=Eb, proj=proj, n_cand=args.neg_sample_size_eval,
+                                       chunk=args.batch_size_eval, seed=args.seed + 29, cache=cache)
+        if self.rank == 0:
+            for k, v in metrics.items():
+                print('[{}]{} average {}: {}'.format(self.rank, mode, k, v))
         return metrics
 
     def train(self):
@@ -584,9 +620,9 @@ class ShardedTrainer(object):
             if args.valid and step % args.eval_interval == 0 and step > 1 and self.dataset.valid is not None:
                 dist.barrier()                   # like the reference: all trainers stop for the validation
                 self.sync_tables()
+                valid_start = time.time()
+                self.evaluate('valid', 'Valid')          # every rank ranks against its own shard
                 if rank == 0:
-                    valid_start = time.time()
-                    self.evaluate('valid', 'Valid')
                     print('[proc {}]validation take {:.3f} seconds:'.format(rank, time.time() - valid_start))
                 dist.barrier()           # (`start` is not reset: the interval includes the validation, train_pytorch.py:168-176)
         th.cuda.synchronize()
@@ -600,8 +636,8 @@ class A2ATrainer(ShardedTrainer):
     partitioning is after, general_models.py:590-637), parameter-server semantics as collectives (dglke_amd/dist.py
     DistEngine: pull -> compute -> push, the owner applies the sparse Adagrad in rank order; reference:
     general_models.py:650-680, kvserver.py:41-51).  Collectives: librccl called directly when every rank has its own GPU;
-    ranks that share a GPU (`--gpu 0 0`) exchange through the gloo group (dist.HostStagedComm).  Rank 0 gathers the shards
-    for validation / test / saving."""
+    ranks that share a GPU (`--gpu 0 0`) exchange through the gloo group (dist.HostStagedComm).  Validation, test and saving
+    run on the shards in place (eval.evaluate_sharded, dist.write_npy_sharded)."""
 
     def __init__(self, args, dataset, rank, world):
         from . import dist as kd
@@ -697,7 +733,6 @@ class A2ATrainer(ShardedTrainer):
             w = np.asarray(tr[3])[part] if args.has_edge_importance else None
             self.sampler = UniformChunkedSampler(h, r, t, dataset.n_entities, B, N, self.dev, neg_chunk_size=self.chunk,
                                                  seed=args.seed + 1000 * rank, edge_importance=w)
-        self._full = None
         if rank == 0:
             print("multi-GPU mode a2a: entity rows %d per GPU, relations replicated, collectives: %s"
                   % (self.spec.shard, type(self.comm).__name__))
@@ -730,20 +765,25 @@ class A2ATrainer(ShardedTrainer):
             raise KgeError('[proc {}] {} entities did not fit their owner bucket although the capacity was checked'.format(self.rank, lost))
 
     def sync_tables(self):
-        import torch.distributed as dist
+        """collective point in front of a validation / test / save: every step's update has landed in the shards once the device
+        is idle (the pipelined and overlapped schedules included); relation rows that live with their owner are collected into
+        every rank's replica."""
         th.cuda.synchronize()
-        parts = [None] * self.world if self.rank == 0 else None
-        dist.gather_object(self.ent.cpu(), parts, dst=0)
-        if self.rel_local:                   # every replica holds the current rows of ITS relations only: collect them on rank 0
+        if self.rel_local:                   # every replica holds the current rows of ITS relations only: collect them everywhere
             from . import dist as kd
-            kd.relation_rows_from_owners(self.engine.rel, self.engine.rel_state, self.rel_owner)
+            kd.relation_rows_from_owners(self.engine.rel, self.engine.rel_state, self.rel_owner, everywhere=True)
             if self.engine.proj is not None:     # TransR: the projection rows live with their relation
-                kd.relation_rows_from_owners(self.engine.proj, self.engine.proj_state, self.rel_owner)
-        if self.rank == 0:
-            self._full = (th.cat(parts).to(self.dev), self.engine.rel)
+                kd.relation_rows_from_owners(self.engine.proj, self.engine.proj_state, self.rel_owner, everywhere=True)
 
-    def full_tables(self):
-        return self._full
+    def entity_shard(self):
+        return self.spec.lo, self.ent
+
+    def entity_rows(self, ids):
+        from . import eval as kev
+        return kev.allgather_rows(self.ent, self.spec.lo, self.spec.bounds(), ids, self.comm)
+
+    def relation_table(self):
+        return self.engine.rel
 
     def projection(self):
         return self.engine.proj
@@ -771,29 +811,21 @@ def _mp_worker(rank, args, port):
         trainer.train()
         failure = None
         trainer.sync_tables()
-        if rank == 0:
-            # whatever happens in rank 0's save / test section, every rank must still reach the barrier below
-            # (a rank-0-only exception used to leave the others waiting for the gloo timeout)
-            try:
+        # saving and testing are collective: every rank writes its rows of the entity file and ranks against its own shard
+        try:
+            if rank == 0:
                 print('training takes {} seconds'.format(time.time() - start))
-                ent, rel = trainer.full_tables()
-                if not args.no_save_emb:
+            if not args.no_save_emb:
+                if rank == 0:
                     print('Save model to {}'.format(args.save_path))
-                    np.save(os.path.join(args.save_path, '%s_%s_entity.npy' % (args.dataset, args.model_name)), ent.cpu().numpy())
-                    np.save(os.path.join(args.save_path, '%s_%s_relation.npy' % (args.dataset, args.model_name)), rel.cpu().numpy())
-                    if args.model_name == 'TransR':      # TransRScore.save (score_fun.py:190-191): <dataset>_<model>projection.npy
-                        np.save(os.path.join(args.save_path, '%s_%sprojection.npy' % (args.dataset, args.model_name)),
-                                trainer.projection().cpu().numpy())
-                    conf = dict(vars(args))
-                    conf.update({'emp_file': dataset.emap_fname, 'rmap_file': dataset.rmap_fname})
-                    with open(os.path.join(args.save_path, 'config.json'), 'w') as f:
-                        json.dump(conf, f, indent=4)
-                if args.test:
-                    start = time.time()
-                    trainer.evaluate('test', 'Test')
+                trainer.save(dataset.emap_fname, dataset.rmap_fname)
+            if args.test:
+                start = time.time()
+                trainer.evaluate('test', 'Test')
+                if rank == 0:
                     print('testing takes {:.3f} seconds'.format(time.time() - start))
-            except Exception as e:      # noqa: BLE001 - re-raised after the barrier
-                failure = e
+        except Exception as e:      # noqa: BLE001 - re-raised after the barrier
+            failure = e
         dist.barrier()
         trainer.close()
         if failure is not None:

@@ -398,6 +398,23 @@ int kge_rank_eval_ex(int model, int neg_head, const float *ent, int64_t n_ent, c
                      int64_t n_cand, const int64_t *filt_ptr, const int64_t *filt_ids, int Eb, int32_t *ranks,
                      float *pos_score_out, void *ws, size_t ws_bytes, unsigned flags, void *stream);
 
+/* the same ranking with the candidates in a table other than the query rows: the evaluation of a range-sharded entity table
+ * without assembling it.  The reference splits the TEST TRIPLES over its processes, each scoring against one table in shared
+ * host memory (train.py:230-257, 330-350; train_pytorch.py:199-253); here every rank scores ALL test triples against the
+ * candidates it OWNS and the counts are summed over the ranks: rank = 1 + sum_k (ranks_k - 1).
+ *   h / t index the query table qent [n_qent, d_e] (a compact block of the test triples' rows), r indexes rel / proj;
+ *   candidate j is cent[cand[j]] (cent = the rank's shard, [n_cent, d_e]), or cent[j] for j < n_cent when cand == NULL;
+ *   filter lists hold columns of that candidate set, as in kge_rank_eval.  TransR needs proj and an explicit `cand`.
+ * Output as kge_rank_eval: ranks[i] = 1 + #{unfiltered candidates scoring >= the true triple}.  Every candidate's score is
+ * formed exactly as kge_rank_eval_ex forms it over the whole table, so the shards' counts add up to its ranks.  An empty
+ * candidate set (n_cent == 0 or n_cand == 0: a rank that owns no rows) sets every rank to 1 without a kernel launch and
+ * leaves pos_score_out unwritten.  Workspace: kge_rank_workspace_bytes(Eb, candidate count, d_e). */
+int kge_rank_eval_split(int model, int neg_head, const float *qent, int64_t n_qent, const float *cent, int64_t n_cent,
+                        const float *rel, int64_t n_rel, const float *proj, const int64_t *h, const int64_t *r,
+                        const int64_t *t, int64_t E, int d_e, int d_r, float gamma, float emb_init, const int64_t *cand,
+                        int64_t n_cand, const int64_t *filt_ptr, const int64_t *filt_ids, int Eb, int32_t *ranks,
+                        float *pos_score_out, void *ws, size_t ws_bytes, unsigned flags, void *stream);
+
 /* ---- peer-to-peer sharded step (xGMI direct; the Hogwild multi-GPU mode) ----
  * The reference's multi-GPU trainer keeps ONE entity table in shared host memory and lets every
  * trainer process gather from it and update it without locks (train.py:298-317 --num_proc,
