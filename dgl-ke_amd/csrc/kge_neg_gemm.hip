@@ -638,11 +638,18 @@ __device__ __forceinline__ void neg_fwd_gemm_ldsa_body(const GemmArgs &a, int ti
 #endif                             // wider is SLOWER - 9.3 / 11.7 / 14 us wave life, the time follows the loads per wavefront)
 // (round 5) ... + the phase-1 workgroups of the sampler tail building a batch of the NEXT group (kge_sampler_tail.hpp): the last
 // workgroups of the grid, behind the nbM workgroups of the step itself
+// Leading plain parameters (kernel-argument preload): what a tile wavefront needs for its id round - the
+// block-id split, the tile geometry and the three id arrays - arrives in SGPRs with the wavefront; GemmArgs (which keeps its own
+// copies, unused here) and the edge half's arguments follow under that round.
 template <bool L2, int AM, int MODEL, bool LEAN, bool LDSA>
-__global__ __launch_bounds__(KGE_BLOCK) void neg_fwd_edge_kernel(GemmArgs a, int ti, int tj, int nbG, EdgeFwdArgs e, int nbM, SmpTail st) {
+__global__ __launch_bounds__(KGE_BLOCK) void neg_fwd_edge_kernel(const int64_t *xidx, const int64_t *ridx, const int64_t *nidx, int nbG, int nbM,
+                                                                 int ti, int tj, int C, int chunk, int N, int D, GemmArgs a_in,
+                                                                 EdgeFwdArgs e, SmpTail st) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     if ((int)blockIdx.x < nbG) {
         KGE_TL(1);
+        GemmArgs a = a_in;
+        a.xidx = xidx; a.ridx = ridx; a.nidx = nidx; a.C = C; a.chunk = chunk; a.N = N; a.D = D;
         if constexpr (LDSA) neg_fwd_gemm_ldsa_body<AM>(a, ti, tj, (int)blockIdx.x, nbG, smem);
         else if constexpr (KGE_FWD_NB == 1) neg_fwd_gemm_body<L2, false, AM>(a, ti, tj, (int)blockIdx.x, nbG);
         else neg_fwd_gemm_wide_body<AM, KGE_FWD_NB>(a, ti, (tj + KGE_FWD_NB - 1) / KGE_FWD_NB, (int)blockIdx.x, nbG);
@@ -693,17 +700,19 @@ int launch_neg_fwd_gemm_with_edge(const GemmArgs &a, const EdgeFwdArgs &e, hipSt
     const bool lean = e.lp.genre == KGE_LOSS_LOGSIGMOID && !e.row_pos && !e.Hc;
     const int nbM = nbG + nbP;
     const dim3 g(nbM + (st.phase ? ST_P1_WGS + (st.slot3 ? ST_P3_WGS : 0) : 0)), b(KGE_BLOCK);
-#define KGE_FE2(L2_, AM_, M_, LE_) do { if (ldsa) hipLaunchKernelGGL((neg_fwd_edge_kernel<L2_, AM_, M_, LE_, true>), g, b, lds, s, a, ti, tj, nbG, ee, nbM, st); \
-                                        else hipLaunchKernelGGL((neg_fwd_edge_kernel<L2_, AM_, M_, LE_, false>), g, b, 0, s, a, ti, tj, nbG, ee, nbM, st); } while (0)
+#define KGE_FE_H a.xidx, a.ridx, a.nidx, nbG, nbM, ti, tj, a.C, a.chunk, a.N, a.D, a, ee, st      /* hot values twice: preloaded + in the struct */
+#define KGE_FE2(L2_, AM_, M_, LE_) do { if (ldsa) hipLaunchKernelGGL((neg_fwd_edge_kernel<L2_, AM_, M_, LE_, true>), g, b, lds, s, KGE_FE_H); \
+                                        else hipLaunchKernelGGL((neg_fwd_edge_kernel<L2_, AM_, M_, LE_, false>), g, b, 0, s, KGE_FE_H); } while (0)
 #define KGE_FE(L2_, AM_, M_) do { if (lean) KGE_FE2(L2_, AM_, M_, true); else KGE_FE2(L2_, AM_, M_, false); } while (0)
     if (a.model == KGE_COMPLEX) {
         if (!ldsa) return KGE_ERR_ARG;
-        if (lean) hipLaunchKernelGGL((neg_fwd_edge_kernel<false, 3, KGE_COMPLEX, true, true>), g, b, lds, s, a, ti, tj, nbG, ee, nbM, st);
-        else hipLaunchKernelGGL((neg_fwd_edge_kernel<false, 3, KGE_COMPLEX, false, true>), g, b, lds, s, a, ti, tj, nbG, ee, nbM, st);
+        if (lean) hipLaunchKernelGGL((neg_fwd_edge_kernel<false, 3, KGE_COMPLEX, true, true>), g, b, lds, s, KGE_FE_H);
+        else hipLaunchKernelGGL((neg_fwd_edge_kernel<false, 3, KGE_COMPLEX, false, true>), g, b, lds, s, KGE_FE_H);
     } else if (a.model == KGE_TRANSE_L2) KGE_FE(true, 1, KGE_TRANSE_L2);
     else KGE_FE(false, 2, KGE_DISTMULT);
 #undef KGE_FE
 #undef KGE_FE2
+#undef KGE_FE_H
     return check_launch_g();
 }
 
@@ -896,7 +905,7 @@ __device__ __forceinline__ void neg_bwd_gemm_tile(const GemmArgs &a, int ti, int
 #pragma unroll
             for (int r = 0; r < 4; ++r) selfv[r] = ldg4(a.A + srow[r] * D + dc);
         }
-        const float *qp = (wantQ ? a.QP : a.A) + dc;
+        const float *qp = a.QP + dc;            // (the launchers resolve it: QP, or A - a valid dummy address - when no Q is wanted)
 #pragma unroll
         for (int r = 0; r < 4; ++r) pq[r] = ldg4(qp + srow[r] * D);
     } else if (!DENSE && need_self && a.nidx) {
@@ -1264,19 +1273,26 @@ __device__ __forceinline__ void neg_bwd_gemm_body(const GemmArgs &a, int ti, int
 #ifndef GB_KS
 #define GB_KS 1                       // wavefronts per backward tile along the reduction (stand-alone launch)
 #endif
+// Leading plain parameters (kernel-argument preload): what a tile wavefront needs for its first requests -
+// the block-id split (toff = workgroups of the sampler tail in front, nbM, bpA, bpN), the shapes the tile counts follow from
+// (ti, tj, td are recomputed from them: three scalar instructions instead of three more argument dwords), the negative ids and
+// the two arrays the GA tiles request their own rows from (qp = QP when Q is wanted, else A: the choice needs no struct field).
 template <bool L2, bool FACT, bool DENSE = false, int EW = 0>
-__global__ __launch_bounds__(GB_KS * KGE_BLOCK) void neg_bwd_gemm_kernel(GemmArgs a, int ti, int tj, int td,
-                                                                         int bpA, int bpN, int maxK, int nbM, SmpTail st) {
+__global__ __launch_bounds__(GB_KS * KGE_BLOCK) void neg_bwd_gemm_kernel(const int64_t *nidx, const float *A, const float *qp, int toff, int nbM,
+                                                                         int bpA, int bpN, int chunk, int N, int D, int maxK,
+                                                                         GemmArgs a_in, SmpTail st) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     // (round 5) phase 2 of the sampler tail: the grid's FIRST 8 workgroups when the launch carries one (its chain - counts, keys, a
     // two-pass radix sort, totals - is as long as the tiles': it must not also wait for 230 workgroups to be dispatched; 8 keeps the
     // tiles' block id -> XCD mapping)
-    const int toff = st.phase ? 8 : 0;
     if ((int)blockIdx.x < toff) {
         if constexpr (GB_KS == 1) sampler_tail_p2(st, (int)blockIdx.x);
         return;
     }
     KGE_TL(3);
+    GemmArgs a = a_in;
+    a.nidx = nidx; a.A = A; a.QP = qp; a.chunk = chunk; a.N = N; a.D = D;
+    const int ti = (chunk + 15) / 16, tj = (N + 15) / 16, td = (D + 63) / 64;      // as launch_neg_bwd_gemm sizes the grid
     neg_bwd_gemm_body<L2, FACT, DENSE, GB_KS, EW>(a, ti, tj, td, bpA, bpN, maxK, (int)blockIdx.x - toff, nbM, smem);
 }
 
@@ -1321,6 +1337,8 @@ int launch_neg_bwd_gemm(const GemmArgs &a, hipStream_t s, const SmpTail *tail) {
     const size_t sm = (size_t)mk * 8 + (fact ? (size_t)mk * GB_TJP * 4 : 0);
     const bool l2 = a.model == KGE_TRANSE_L2;
     const dim3 g(nb + nbT), b(GB_KS * KGE_BLOCK);
+    // (hot values twice: preloaded + in the struct; the tiles read their Q-epilogue rows through the leading pointer alone)
+#define KGE_BG_H(BPA_, NB_) a.nidx, a.A, (a.Q ? a.QP : a.A), nbT, NB_, BPA_, bpN, a.chunk, a.N, a.D, mk, a, st
     if (a.ew_GR) {                                               // DistMult / ComplEx: per-edge gradient rows from the GA tiles' epilogue
         const bool simple = a.model == KGE_SIMPLE, cplx = a.model == KGE_COMPLEX || simple;
         if (fact || l2 || (a.model != KGE_DISTMULT && !cplx) || !a.ew_ent || !a.ew_rel || !a.ew_h || !a.ew_t || !a.ew_r ||
@@ -1332,27 +1350,28 @@ int launch_neg_bwd_gemm(const GemmArgs &a, hipStream_t s, const SmpTail *tail) {
             const int nbc = a.C * (bpAc + bpN);
             const dim3 gc(nbc + nbT);
             if (simple) {
-                if (!a.nidx) hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, true, 3>), gc, b, 0, s, a, ti, tj, td, bpAc, bpN, mk, nbc, st);
-                else hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, false, 3>), gc, b, sm, s, a, ti, tj, td, bpAc, bpN, mk, nbc, st);
-            } else if (!a.nidx) hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, true, 2>), gc, b, 0, s, a, ti, tj, td, bpAc, bpN, mk, nbc, st);
-            else hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, false, 2>), gc, b, sm, s, a, ti, tj, td, bpAc, bpN, mk, nbc, st);
+                if (!a.nidx) hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, true, 3>), gc, b, 0, s, KGE_BG_H(bpAc, nbc));
+                else hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, false, 3>), gc, b, sm, s, KGE_BG_H(bpAc, nbc));
+            } else if (!a.nidx) hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, true, 2>), gc, b, 0, s, KGE_BG_H(bpAc, nbc));
+            else hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, false, 2>), gc, b, sm, s, KGE_BG_H(bpAc, nbc));
             return check_launch_g();
         }
-        if (!a.nidx) hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, true, 1>), g, b, 0, s, a, ti, tj, td, bpA, bpN, mk, nb, st);
-        else hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, false, 1>), g, b, sm, s, a, ti, tj, td, bpA, bpN, mk, nb, st);
+        if (!a.nidx) hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, true, 1>), g, b, 0, s, KGE_BG_H(bpA, nb));
+        else hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, false, 1>), g, b, sm, s, KGE_BG_H(bpA, nb));
         return check_launch_g();
     }
     if (!fact && !a.nidx) {                                      // dense operands: the instance without index table / LDS / barrier
-        if (l2) hipLaunchKernelGGL((neg_bwd_gemm_kernel<true, false, true>), g, b, 0, s, a, ti, tj, td, bpA, bpN, mk, nb, st);
-        else hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, true>), g, b, 0, s, a, ti, tj, td, bpA, bpN, mk, nb, st);
+        if (l2) hipLaunchKernelGGL((neg_bwd_gemm_kernel<true, false, true>), g, b, 0, s, KGE_BG_H(bpA, nb));
+        else hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, true>), g, b, 0, s, KGE_BG_H(bpA, nb));
         return check_launch_g();
     }
-    if (l2 && fact) hipLaunchKernelGGL((neg_bwd_gemm_kernel<true, true>), g, b, sm, s, a, ti, tj, td, bpA, bpN, mk, nb, st);
-    else if (l2) hipLaunchKernelGGL((neg_bwd_gemm_kernel<true, false>), g, b, sm, s, a, ti, tj, td, bpA, bpN, mk, nb, st);
-    else if (fact) hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, true>), g, b, sm, s, a, ti, tj, td, bpA, bpN, mk, nb, st);
-    else hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false>), g, b, sm, s, a, ti, tj, td, bpA, bpN, mk, nb, st);
+    if (l2 && fact) hipLaunchKernelGGL((neg_bwd_gemm_kernel<true, true>), g, b, sm, s, KGE_BG_H(bpA, nb));
+    else if (l2) hipLaunchKernelGGL((neg_bwd_gemm_kernel<true, false>), g, b, sm, s, KGE_BG_H(bpA, nb));
+    else if (fact) hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, true>), g, b, sm, s, KGE_BG_H(bpA, nb));
+    else hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false>), g, b, sm, s, KGE_BG_H(bpA, nb));
     return check_launch_g();
 }
+#undef KGE_BG_H
 
 // forward GEMM of one step + Adagrad update of ANOTHER step in one launch (neg_fwd_update_kernel).
 // Returns KGE_ERR_ARG when the combination has no fused instantiation (the caller then launches the two kernels apart).
@@ -1404,7 +1423,9 @@ int launch_neg_bwd_gemm_with_prep(const GemmArgs &a, const EdgeFwdArgs &e, hipSt
     const int mk = (maxK + 3) & ~3;
     const size_t sm = 0;
     const dim3 g(nbG + nbP), b(KGE_BLOCK);
-#define KGE_BP(L2_, M_) hipLaunchKernelGGL((neg_bwd_prep_kernel<L2_, M_>), g, b, sm, s, a, ti, tj, td, bpA, bpN, mk, nbG, ee)
+    GemmArgs ar = a;
+    if (!ar.Q) ar.QP = ar.A;                     // the tiles request their Q-epilogue rows unconditionally (see neg_bwd_gemm_tile)
+#define KGE_BP(L2_, M_) hipLaunchKernelGGL((neg_bwd_prep_kernel<L2_, M_>), g, b, sm, s, ar, ti, tj, td, bpA, bpN, mk, nbG, ee)
     if (a.model == KGE_TRANSE_L2 && e.model == KGE_TRANSE_L2) KGE_BP(true, KGE_TRANSE_L2);
     else if (a.model == KGE_DISTMULT && e.model == KGE_DISTMULT) KGE_BP(false, KGE_DISTMULT);
     else if (a.model == KGE_COMPLEX && e.model == KGE_COMPLEX) KGE_BP(false, KGE_COMPLEX);

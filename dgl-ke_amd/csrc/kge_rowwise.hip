@@ -585,10 +585,14 @@ __global__ __launch_bounds__(KGE_BLOCK) void loss_kernel(LossArgs a) {
 // RAW: the row holds the raw products a_i . b_j of the merged forward launch (LossArgs::l2_raw): the TransE_l2 score
 // gamma - sqrt(|a_i|^2 + |b_j|^2 - 2 a_i.b_j) is rebuilt here, from one more coalesced row of |b|^2 requested with the scores
 // (the arithmetic on the register-resident row lives in kge_loss_body.hpp: the forward tiles' last arriver runs the same code)
+// Leading plain parameters (kernel-argument preload): what a wavefront needs to request its
+// score row, |b|^2 row, |a|^2, positive score and weight arrives in SGPRs with the wavefront; the struct follows under that round.
 template <int NPER, bool LEAN, bool RAW>
-__global__ __launch_bounds__(KGE_BLOCK) void loss_kernel_reg(LossArgs a_in) {
+__global__ __launch_bounds__(KGE_BLOCK) void loss_kernel_reg(const float *neg, const float *bsq, const float *asq, const float *pos,
+                                                             const float *w_, int B_, int N_, int l2_chunk, LossArgs a_in) {
     KGE_TL(2);
     LossArgs a = a_in;
+    a.neg = neg; a.bsq = bsq; a.asq = asq; a.pos = pos; a.w = w_; a.B = B_; a.N = N_; a.l2_chunk = l2_chunk;
     if constexpr (LEAN) loss_args_lean(a);
     const int64_t i = WAVE_ID();
     if (i >= a.B) return;
@@ -633,16 +637,18 @@ int launch_loss(const LossArgs &a, hipStream_t s) {
     const bool lean = a.genre == KGE_LOSS_LOGSIGMOID && !a.pairwise && a.skip_pos && a.clampv == 0.f && !a.neg_copy &&
                       !a.row_pos && !a.row_neg && a.diag_chunk <= 0;
     if (a.l2_raw && (!a.asq || !a.bsq || a.l2_chunk <= 0)) return KGE_ERR_ARG;
-#define KGE_LOSS(N) do { if (a.l2_raw) { if (lean) hipLaunchKernelGGL((loss_kernel_reg<N, true, true>), g, b, 0, s, a); \
-                                         else hipLaunchKernelGGL((loss_kernel_reg<N, false, true>), g, b, 0, s, a); } \
-                         else if (lean) hipLaunchKernelGGL((loss_kernel_reg<N, true, false>), g, b, 0, s, a); \
-                         else hipLaunchKernelGGL((loss_kernel_reg<N, false, false>), g, b, 0, s, a); } while (0)
+#define KGE_LOSS_H a.neg, a.bsq, a.asq, a.pos, a.w, a.B, a.N, a.l2_chunk, a        /* hot values twice: preloaded + in the struct */
+#define KGE_LOSS(N) do { if (a.l2_raw) { if (lean) hipLaunchKernelGGL((loss_kernel_reg<N, true, true>), g, b, 0, s, KGE_LOSS_H); \
+                                         else hipLaunchKernelGGL((loss_kernel_reg<N, false, true>), g, b, 0, s, KGE_LOSS_H); } \
+                         else if (lean) hipLaunchKernelGGL((loss_kernel_reg<N, true, false>), g, b, 0, s, KGE_LOSS_H); \
+                         else hipLaunchKernelGGL((loss_kernel_reg<N, false, false>), g, b, 0, s, KGE_LOSS_H); } while (0)
     if (a.N <= 64) KGE_LOSS(1);
     else if (a.N <= 128) KGE_LOSS(2);
     else if (a.N <= 256) KGE_LOSS(4);
     else if (a.N <= 512) KGE_LOSS(8);
     else hipLaunchKernelGGL(loss_kernel, g, b, 0, s, a);
 #undef KGE_LOSS
+#undef KGE_LOSS_H
     return check_launch();
 }
 
@@ -870,10 +876,15 @@ __global__ __launch_bounds__(KGE_BLOCK) void update_kernel(UpdateArgs a, int nb_
 }
 
 // single-pass register-resident variant: body in kge_update_body.hpp
+// Leading plain parameters (kernel-argument preload): the block-id split, the plan records and the device-side
+// counts - a wavefront's record request leaves without a scalar round for its arguments in front; the struct arrives under it.
 template <int NIT, bool SHARDED, int LEAN>
-__global__ __launch_bounds__(KGE_BLOCK) void update_kernel_reg(UpdateArgs a, int nb_ent, int nbM, SmpTail st) {
+__global__ __launch_bounds__(KGE_BLOCK) void update_kernel_reg(const int32_t *ue_rec, const int32_t *ur_rec, const int32_t *counts_dev,
+                                                               int UE, int UR, int nb_ent, int nbM, UpdateArgs a_in, SmpTail st) {
     if ((int)blockIdx.x >= nbM) { sampler_tail_p3(st, (int)blockIdx.x - nbM); return; }   // (round 5) phase 3 of the sampler tail
     KGE_TL(((int)blockIdx.x < nbM - nb_ent) ? 7 : 4);      // timeline: relation workgroups come first (id 7)
+    UpdateArgs a = a_in;
+    a.ue_rec = ue_rec; a.ur_rec = ur_rec; a.counts_dev = counts_dev; a.UE = UE; a.UR = UR;
     update_reg_body<NIT, SHARDED, LEAN>(a, nb_ent, (int)blockIdx.x, nbM);
 }
 
@@ -909,7 +920,7 @@ int launch_update(const UpdateArgs &a, hipStream_t s, const SmpTail *tail) {
             return KGE_ERR_ARG;
         lean = 5;
     }
-#define KGE_UPD(N, SH, LE) hipLaunchKernelGGL((update_kernel_reg<N, SH, LE>), g, b, 0, s, a, nbE, nbM, st)
+#define KGE_UPD(N, SH, LE) hipLaunchKernelGGL((update_kernel_reg<N, SH, LE>), g, b, 0, s, a.ue_rec, a.ur_rec, a.counts_dev, a.UE, a.UR, nbE, nbM, a, st)
 #define KGE_UPD_L(N, SH)                                                         \
     do { if (lean == 1) KGE_UPD(N, SH, 1); else if (lean == 2) KGE_UPD(N, SH, 2); else if (lean == 3) KGE_UPD(N, SH, 3); \
          else if (lean == 4) KGE_UPD(N, SH, 4); else if (lean == 6) KGE_UPD(N, SH, 6); else if (lean == 7) KGE_UPD(N, SH, 7); \
