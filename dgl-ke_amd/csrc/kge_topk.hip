@@ -9,6 +9,9 @@
 //     list (in the workspace, sorted) by rank counting in a per-wavefront LDS queue.  Entries are 64-bit composites
 //     (order-preserving score key << 32 | ~candidate index): "composite <= threshold -> reject" is the score test AND tie
 //     rule 2 (equal scores: the lower position first), and NaN (key 0) ranks below every number.
+//     The filtered form (template argument TopkSelArgsF; link prediction with known-edge exclusion) looks the survivors of that
+//     compare up in the row's sorted list of entity ids and drops the listed ones before the merge: a listed candidate
+//     never enters a row's list or becomes its threshold.  The unfiltered instances are the code they were without it.
 //   * topk_merge_kernel: bitonic sort of up to 2048 (score, ordinal) entries in LDS, fan-in 2048 / K - 1 lists per pass; a
 //     tree of passes reduces the segments of a row, then the rows of a group, together with the group's running result
 //     (carried across row batches by the caller).
@@ -18,6 +21,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <type_traits>
 #include "kge_common.hpp"
 
 using namespace kge;
@@ -41,6 +45,10 @@ struct TopkSelArgs {
     const float *an, *bn;                                // [rows], [N]: |a|^2, |b|^2 (L2G, JAC) or |a|, |b| (COS)
     unsigned long long *part;                            // out [rows, S, K] composites, sorted, 0 = empty
 };
+// the filtered form: candidates whose ENTITY id is in filt_ids[filt_ptr[2i] .. filt_ptr[2i+1]) (ascending, unique) never enter row i's list
+struct TopkSelArgsF : TopkSelArgs {
+    const int64_t *filt_ptr, *filt_ids;
+};
 
 __device__ __forceinline__ uint32_t fkey(float f) {
     if (f != f) return 0u;                               // NaN: below every number
@@ -59,6 +67,20 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
+__device__ __forceinline__ int64_t lane_bcast(int64_t v, int x) {                 // lane x's v (x wave-uniform)
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, x);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((unsigned long long)v >> 32), x);
+    return (int64_t)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ bool in_sorted(const int64_t *p, int64_t lo, const int64_t end, int64_t id) {   // id in p[lo .. end) ?
+    int64_t hi = end;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (p[mid] < id) lo = mid + 1; else hi = mid;
+    }
+    return lo < end && p[lo] == id;
+}
+
 static inline int check_launch_t() { return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH; }
 
 __device__ __forceinline__ float epilogue(const TopkSelArgs &a, float x, int64_t row, int64_t col) {
@@ -72,8 +94,9 @@ __device__ __forceinline__ float epilogue(const TopkSelArgs &a, float x, int64_t
     }
 }
 
-template <int ACC>
-__global__ __launch_bounds__(256) void topk_select_kernel(TopkSelArgs a) {
+template <int ACC, class Args = TopkSelArgs>
+__global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
+    constexpr bool FILT = !std::is_same<Args, TopkSelArgs>::value;
     __shared__ __attribute__((aligned(16))) float lds[2][(TK_BM + TK_BN) * TK_LD];
     __shared__ unsigned long long rthr[TK_BM];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -89,6 +112,12 @@ __global__ __launch_bounds__(256) void topk_select_kernel(TopkSelArgs a) {
         if (r0 + lr < a.rows) a.part[((int64_t)(r0 + lr) * a.S + seg) * K + e % K] = 0ull;
     }
     if (tid < TK_BM) rthr[tid] = 0ull;
+    const int64_t *frng = nullptr;                                             // [128][2]: the rows' list ranges (filtered form)
+    if constexpr (FILT) {
+        __shared__ int64_t frng_lds[TK_BM * 2];
+        if (tid < TK_BM * 2) frng_lds[tid] = a.filt_ptr[2 * (int64_t)min(r0 + (tid >> 1), a.rows - 1) + (tid & 1)];
+        frng = frng_lds;
+    }
     __syncthreads();
     for (int64_t bn = tile0; bn < tile1; ++bn) {
         if constexpr (ACC == ACC_MFMA) {
@@ -250,15 +279,43 @@ __global__ __launch_bounds__(256) void topk_select_kernel(TopkSelArgs a) {
         }
         __syncthreads();
         // ---- selection: wavefront w walks rows 32 w .. 32 w + 31 of the tile ------------------------------------------------
+        [[maybe_unused]] int64_t id0 = 0, id1 = 0;                              // (filtered form) the entity ids of this lane's two candidates
+        if constexpr (FILT) {
+            const int64_t c0 = min(bn * TK_BN + lane, a.N - 1), c1 = min(bn * TK_BN + lane + 64, a.N - 1);
+            id0 = a.nidx ? a.nidx[c0] : c0; id1 = a.nidx ? a.nidx[c1] : c1;
+        }
         for (int lr = wave * 32; lr < wave * 32 + 32; ++lr) {
             if (r0 + lr >= a.rows) break;
             const unsigned long long thr = rthr[lr];
             const int64_t j0 = bn * TK_BN + lane, j1 = j0 + 64;
             const unsigned long long c0 = j0 < a.N ? comp_of(sc[lr * TK_BN + lane], j0) : 0ull;
             const unsigned long long c1 = j1 < a.N ? comp_of(sc[lr * TK_BN + lane + 64], j1) : 0ull;
-            const bool s0 = c0 > thr, s1 = c1 > thr;
-            const unsigned long long b0 = __ballot(s0), b1 = __ballot(s1);
+            bool s0 = c0 > thr, s1 = c1 > thr;
+            unsigned long long b0 = __ballot(s0), b1 = __ballot(s1);
             if ((b0 | b1) == 0ull) continue;                                   // the common case
+            if constexpr (FILT) {
+                // only the survivors of the compare are looked up in the row's list (the range, read once per workgroup
+                // into LDS, is wave-uniform: rows with an empty list skip this).  Up to 64 entries: one coalesced read,
+                // then every entry broadcast to all lanes; longer lists: a binary search per surviving lane.
+                const int64_t f0 = frng[2 * lr], f1 = frng[2 * lr + 1];
+                if (f1 > f0) {
+                    if (f1 - f0 <= 64) {
+                        const int nf = (int)(f1 - f0);
+                        const int64_t e = lane < nf ? a.filt_ids[f0 + lane] : -1;
+                        bool k0 = false, k1 = false;
+                        for (int x = 0; x < nf; ++x) {
+                            const int64_t v = lane_bcast(e, x);
+                            k0 |= v == id0; k1 |= v == id1;
+                        }
+                        s0 = s0 && !k0; s1 = s1 && !k1;
+                    } else {
+                        if (s0) s0 = !in_sorted(a.filt_ids, f0, f1, id0);
+                        if (s1) s1 = !in_sorted(a.filt_ids, f0, f1, id1);
+                    }
+                    b0 = __ballot(s0); b1 = __ballot(s1);
+                    if ((b0 | b1) == 0ull) continue;
+                }
+            }
             unsigned long long *list = a.part + ((int64_t)(r0 + lr) * a.S + seg) * K;
             for (int p = lane; p < K; p += 64) un[p] = list[p];
             const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
@@ -404,6 +461,25 @@ __global__ __launch_bounds__(KGE_BLOCK) void topk_sim_pair_kernel(int sim, const
     out[i] = s;
 }
 
+// out[i] = 1 when (a_i, r_i, b_i) is in the known index: keys [M] ascending (a * n_rel + r), vals ascending within a key
+__global__ void triples_known_kernel(const int64_t *keys, const int64_t *vals, int64_t M, int64_t n_rel, const int64_t *a,
+                                     const int64_t *r, const int64_t *b, int64_t n, uint8_t *out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t key = a[i] * n_rel + r[i];
+    int64_t lo = 0, hi = M;
+    while (lo < hi) {                                    // first position with keys[p] >= key
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    int64_t end = lo, top = M;
+    while (end < top) {                                  // first position with keys[p] > key
+        const int64_t mid = end + ((top - end) >> 1);
+        if (keys[mid] <= key) end = mid + 1; else top = mid;
+    }
+    out[i] = in_sorted(vals, lo, end, b[i]) ? 1 : 0;
+}
+
 namespace {
 
 inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
@@ -501,11 +577,13 @@ size_t kge_topk_workspace_bytes(int rows, int64_t n_cand, int d, int K) {
     return carve(nullptr, rows, n_cand, d, K).need;
 }
 
-int kge_topk_select(int func, int side, const float *ent, int64_t n_ent, const float *rel, int64_t n_rel, const int64_t *h,
-                    const int64_t *r, const int64_t *t, int rows, int d_e, int d_r, float gamma, float emb_init, const int64_t *cand,
-                    int64_t n_cand, const int64_t *row_base, int64_t stride, int group_rows, int K, float *res_score,
-                    int64_t *res_ord, void *ws, size_t ws_bytes, void *stream) {
+static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent, const float *rel, int64_t n_rel, const int64_t *h,
+                            const int64_t *r, const int64_t *t, int rows, int d_e, int d_r, float gamma, float emb_init,
+                            const int64_t *cand, int64_t n_cand, const int64_t *row_base, int64_t stride, int group_rows, int K,
+                            float *res_score, int64_t *res_ord, void *ws, size_t ws_bytes, const int64_t *filt_ptr,
+                            const int64_t *filt_ids, void *stream) {
     char msg[256];
+    if (filt_ptr && !filt_ids) return tk_fail("kge_topk_select_filtered: filt_ptr given without filt_ids");
     const bool sim = func >= KGE_SIM_COSINE && func <= KGE_SIM_EXT_JACCARD;
     if (!sim && (func < KGE_TRANSE_L1 || func > KGE_RESCAL)) {
         snprintf(msg, sizeof(msg), "kge_topk_select: unknown score function %d (TransR has no inference path)", func);
@@ -575,6 +653,18 @@ int kge_topk_select(int func, int side, const float *ent, int64_t n_ent, const f
     a.abase = abase; a.aidx = aidx; a.rows = rows; a.nbase = ent; a.nidx = cand; a.N = N; a.D = D; a.epi = epi;
     a.S = topk_segments(rows, N, K); a.K = K; a.gamma = gamma; a.an = w.an; a.bn = w.bn; a.part = w.part;
     const dim3 grid((unsigned)((int64_t)((rows + TK_BM - 1) / TK_BM) * a.S));
+    if (filt_ptr) {
+        TopkSelArgsF f{};
+        static_cast<TopkSelArgs &>(f) = a;
+        f.filt_ptr = filt_ptr; f.filt_ids = filt_ids;
+        switch (acc) {
+        case ACC_MFMA: hipLaunchKernelGGL((topk_select_kernel<ACC_MFMA, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
+        case ACC_DOT: hipLaunchKernelGGL((topk_select_kernel<ACC_DOT, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
+        case ACC_SQ: hipLaunchKernelGGL((topk_select_kernel<ACC_SQ, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
+        case ACC_L1: hipLaunchKernelGGL((topk_select_kernel<ACC_L1, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
+        default: hipLaunchKernelGGL((topk_select_kernel<ACC_ROT, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
+        }
+    } else
     switch (acc) {
     case ACC_MFMA: hipLaunchKernelGGL(topk_select_kernel<ACC_MFMA>, grid, dim3(256), 0, st, a); break;
     case ACC_DOT: hipLaunchKernelGGL(topk_select_kernel<ACC_DOT>, grid, dim3(256), 0, st, a); break;
@@ -600,6 +690,33 @@ int kge_topk_select(int func, int side, const float *ent, int64_t n_ent, const f
     int64_t *ta_o = rs == w.s0 ? w.o1 : w.o0, *tb_o = rs == w.s0 ? w.o0 : w.o1;
     const float *fs; const int64_t *fo;
     return merge_tree(rows / group_rows, group_rows, K, rs, ro, res_score, res_ord, res_score, res_ord, ta_s, ta_o, tb_s, tb_o, &fs, &fo, st);
+}
+
+int kge_topk_select(int func, int side, const float *ent, int64_t n_ent, const float *rel, int64_t n_rel, const int64_t *h,
+                    const int64_t *r, const int64_t *t, int rows, int d_e, int d_r, float gamma, float emb_init, const int64_t *cand,
+                    int64_t n_cand, const int64_t *row_base, int64_t stride, int group_rows, int K, float *res_score,
+                    int64_t *res_ord, void *ws, size_t ws_bytes, void *stream) {
+    return topk_select_impl(func, side, ent, n_ent, rel, n_rel, h, r, t, rows, d_e, d_r, gamma, emb_init, cand, n_cand, row_base,
+                            stride, group_rows, K, res_score, res_ord, ws, ws_bytes, nullptr, nullptr, stream);
+}
+
+int kge_topk_select_filtered(int func, int side, const float *ent, int64_t n_ent, const float *rel, int64_t n_rel, const int64_t *h,
+                             const int64_t *r, const int64_t *t, int rows, int d_e, int d_r, float gamma, float emb_init,
+                             const int64_t *cand, int64_t n_cand, const int64_t *row_base, int64_t stride, int group_rows, int K,
+                             float *res_score, int64_t *res_ord, void *ws, size_t ws_bytes, const int64_t *filt_ptr,
+                             const int64_t *filt_ids, void *stream) {
+    return topk_select_impl(func, side, ent, n_ent, rel, n_rel, h, r, t, rows, d_e, d_r, gamma, emb_init, cand, n_cand, row_base,
+                            stride, group_rows, K, res_score, res_ord, ws, ws_bytes, filt_ptr, filt_ids, stream);
+}
+
+int kge_triples_known(const int64_t *keys, const int64_t *vals, int64_t M, int64_t n_rel, const int64_t *a, const int64_t *r,
+                      const int64_t *b, int64_t n, uint8_t *out, void *stream) {
+    if (M < 0 || n < 0 || n_rel <= 0 || (M && (!keys || !vals)) || (n && (!a || !r || !b || !out)))
+        return tk_fail("kge_triples_known: bad argument");
+    if (n == 0) return KGE_OK;
+    hipLaunchKernelGGL(triples_known_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, keys, vals, M, n_rel,
+                       a, r, b, n, out);
+    return check_launch_t();
 }
 
 int kge_topk_vector(const float *score, int64_t n, int K, float *res_score, int64_t *res_ord, void *ws, size_t ws_bytes, void *stream) {

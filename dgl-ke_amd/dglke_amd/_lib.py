@@ -165,6 +165,9 @@ _SIGNATURES = {
     "kge_topk_workspace_bytes": (c_sz, [c_i, c_i64, c_i, c_i]),
     "kge_topk_select": (c_i, [c_i, c_i, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_i64, c_p, c_i64,
                               c_i, c_i, c_p, c_p, c_p, c_sz, c_p]),
+    "kge_topk_select_filtered": (c_i, [c_i, c_i, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_i64, c_p,
+                                       c_i64, c_i, c_i, c_p, c_p, c_p, c_sz, c_p, c_p, c_p]),
+    "kge_triples_known": (c_i, [c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p, c_p]),
     "kge_topk_vector": (c_i, [c_p, c_i64, c_i, c_p, c_p, c_p, c_sz, c_p]),
     "kge_sim_pairwise": (c_i, [c_i, c_p, c_i64, c_i, c_p, c_p, c_i64, c_p, c_p]),
     "kge_ipc_export": (c_i, [c_p, c_p, C.POINTER(c_i64)]),

@@ -41,42 +41,69 @@ def build_filter(known_h, known_r, known_t, test_h, test_r, test_t, neg_head, n_
 _FORCE_TWO_KEY_SORT = False      # tests: take the large-graph path of build_filter_device on a small graph
 
 
+def _put_ids(x, dev):
+    if isinstance(x, torch.Tensor):
+        return x.to(dev, torch.int64)
+    return torch.as_tensor(np.ascontiguousarray(np.asarray(x, np.int64))).to(dev)
+
+
+def sort_known_device(known, neg_head, n_relations, n_entities, dev):
+    """the sort half of `build_filter_device`: (key, val) int64 tensors on `dev`, the unique (key, entity) pairs of the known
+    triples (h, r, t) sorted by key, then entity - key = t * R + r with heads as values (neg_head) or h * R + r with tails.
+    Intermediates are dropped as soon as they are used: for M known triples the peak is 2 x 16 M bytes above what was allocated
+    before (measured at M = 597 213 on the device, tools/link_predict_timing.py: the composite key and torch.unique's
+    buffers), against the 16 M bytes that remain.  Returns None when `key` itself would overflow int64."""
+    R, NE = int(n_relations), int(n_entities)
+    if NE * R >= (1 << 62):
+        return None
+    two_key = NE * R * NE >= (1 << 62) or _FORCE_TWO_KEY_SORT
+    kh, kr, kt = known
+    if neg_head:
+        key, val = _put_ids(kt, dev) * R, _put_ids(kh, dev)
+    else:
+        key, val = _put_ids(kh, dev) * R, _put_ids(kt, dev)
+    key += _put_ids(kr, dev)
+    if two_key:
+        o = torch.argsort(val, stable=True)
+        o = o[torch.argsort(key[o], stable=True)]            # lexicographic (key, entity) order
+        key, val = key[o], val[o]
+        del o
+        if key.shape[0]:
+            keep = torch.ones(key.shape[0], dtype=torch.bool, device=key.device)
+            keep[1:] = (key[1:] != key[:-1]) | (val[1:] != val[:-1])
+            key, val = key[keep], val[keep]
+    else:
+        key *= NE
+        key += val
+        del val
+        comp = torch.unique(key)                             # sorted unique (key, entity) pairs
+        del key
+        key = torch.div(comp, NE, rounding_mode='floor')
+        val = comp - key * NE
+    return key, val
+
+
+def key_ranges(key, qkey):
+    """the lookup half: [n, 2] int64, the [left, right) range of every query key in the sorted `key`"""
+    return torch.stack([torch.searchsorted(key, qkey, right=False), torch.searchsorted(key, qkey, right=True)], 1).contiguous()
+
+
 def build_filter_device(known, test, neg_head, n_relations, n_entities, dev):
     """`build_filter` with the sort on the device: the same lists in the same order (unique (key, entity) pairs sorted by key, then
     entity; per test triple the [left, right) range of its key), as int64 DEVICE tensors ready for `Ranker.ranks`.  One composite
     key `(key * n_entities + entity)` through `torch.unique` instead of a host `np.lexsort` over every known triple - 0.09 s per
     corruption side at FB15k's 592 k known triples, which was 87 % of a validation (tools/eval_timing.py).  When the composite key
     does not fit int64 (Freebase: 86 M entities x 14 824 relations x 86 M) the same order comes from two stable device sorts
-    (entity, then key).  Returns None only when even `key` would overflow."""
-    R, NE = int(n_relations), int(n_entities)
-    if NE * R >= (1 << 62):
+    (entity, then key).  Returns None only when even `key` would overflow.  (The sort is `sort_known_device`, which the
+    link-prediction index - known.py - keeps; the lookup is `key_ranges`.)"""
+    kv = sort_known_device(known, neg_head, n_relations, n_entities, dev)
+    if kv is None:
         return None
-    two_key = NE * R * NE >= (1 << 62) or _FORCE_TWO_KEY_SORT
-
-    def put(x):
-        if isinstance(x, torch.Tensor):
-            return x.to(dev, torch.int64)
-        return torch.as_tensor(np.ascontiguousarray(np.asarray(x, np.int64))).to(dev)
-    kh, kr, kt = (put(x) for x in known)
-    th_, tr_, tt_ = (put(x) for x in test)
-    if neg_head:
-        key, val, tkey = kt * R + kr, kh, tt_ * R + tr_
-    else:
-        key, val, tkey = kh * R + kr, kt, th_ * R + tr_
-    if two_key:
-        o = torch.argsort(val, stable=True)
-        o = o[torch.argsort(key[o], stable=True)]            # lexicographic (key, entity) order
-        key, val = key[o], val[o]
-        if key.shape[0]:
-            keep = torch.ones(key.shape[0], dtype=torch.bool, device=key.device)
-            keep[1:] = (key[1:] != key[:-1]) | (val[1:] != val[:-1])
-            key, val = key[keep], val[keep]
-    else:
-        comp = torch.unique(key * NE + val)                  # sorted unique (key, entity) pairs
-        key = torch.div(comp, NE, rounding_mode='floor')
-        val = comp - key * NE
-    rng = torch.stack([torch.searchsorted(key, tkey, right=False), torch.searchsorted(key, tkey, right=True)], 1)
-    return rng.contiguous(), val.contiguous()
+    key, val = kv
+    R = int(n_relations)
+    th_, tr_, tt_ = (_put_ids(x, dev) for x in test)
+    tkey = (tt_ if neg_head else th_) * R + tr_
+    return key_ranges(key, tkey), val.contiguous()
 
 
 class Ranker(object):

@@ -12,7 +12,11 @@ Deliberate differences from the reference:
     (the reference rebuilds the model with gamma 0 there and so rotates by a phase it never trained);
   * equal scores are ordered by position - (head, relation, tail) or (left, right) - where the reference leaves them unordered;
   * a NaN score ranks below every number;
-  * the device is a GPU (no CPU path), TransR is refused (as in the reference) and K is limited to 1 .. TOPK_MAX.
+  * the device is a GPU (no CPU path), TransR is refused (as in the reference) and K is limited to 1 .. TOPK_MAX;
+  * ke_model: attach_graph takes the known triples (head, rel, tail) themselves (there is no DGLGraph here);
+  * ke_model: exclude_mode 'exclude' is exact - known combinations are left out inside the selection kernel, where the
+    reference takes the 4K best and falls back to a full sort when too few of them survive; results agree wherever
+    scores are not tied.
 """
 import os
 
@@ -96,9 +100,13 @@ def vector_topk(score, k):
     return res_s[0, :m], res_o[0, :m]
 
 
-def select_groups(func, side, ent, rel, d_e, d_r, gamma, emb_init, cand, n_rows, group_rows, row_fn, stride, k, max_rows=None):
+def select_groups(func, side, ent, rel, d_e, d_r, gamma, emb_init, cand, n_rows, group_rows, row_fn, stride, k, max_rows=None,
+                  filt_ids=None):
     """top-k per group of `group_rows` consecutive query rows (n_rows of them, rows batched to the workspace budget).
-    row_fn(r0, r1) -> (h, r, t, row_base) int64 device tensors of rows [r0, r1).  Returns res_s, res_o [groups, k]."""
+    row_fn(r0, r1) -> (h, r, t, row_base) int64 device tensors of rows [r0, r1).  Returns res_s, res_o [groups, k].
+    With filt_ids (the sorted entity lists of known.KnownIndex) row_fn returns a fifth tensor, the rows' [r1 - r0, 2] list
+    ranges, and candidates in a row's list are left out (kge_topk_select_filtered); a group may then return fewer than k
+    results (ordinal -1 in the rest)."""
     h = _lib.lib()
     dev = cand.device
     G = n_rows // group_rows
@@ -121,7 +129,16 @@ def select_groups(func, side, ent, rel, d_e, d_r, gamma, emb_init, cand, n_rows,
         else:                                                  # a group over several calls: the result carries over
             r1 = min((g0 + 1) * group_rows, r0 + per)
             grc = r1 - r0
-        hh, rr, tt, base = row_fn(r0, r1)
+        if filt_ids is not None:
+            hh, rr, tt, base, fptr = row_fn(r0, r1)
+            _lib.check(h.kge_topk_select_filtered(func, side, _lib.ptr(ent), ent.shape[0], relp, n_rel, _lib.ptr(hh),
+                                                  _lib.ptr(rr), _lib.ptr(tt), r1 - r0, d_e, d_r, float(gamma),
+                                                  float(emb_init), _lib.ptr(cand), N, _lib.ptr(base), int(stride), grc, k,
+                                                  _lib.ptr(res_s[g0:]), _lib.ptr(res_o[g0:]), _lib.ptr(ws), ws.numel(),
+                                                  _lib.ptr(fptr), _lib.ptr(filt_ids), _lib.stream_ptr()))
+            r0 = r1
+            continue
+        hh, rr, tt, base = row_fn(r0, r1)[:4]
         _lib.check(h.kge_topk_select(func, side, _lib.ptr(ent), ent.shape[0], relp, n_rel, _lib.ptr(hh), _lib.ptr(rr),
                                      _lib.ptr(tt), r1 - r0, d_e, d_r, float(gamma), float(emb_init), _lib.ptr(cand), N,
                                      _lib.ptr(base), int(stride), grc, k, _lib.ptr(res_s[g0:]), _lib.ptr(res_o[g0:]),
@@ -132,6 +149,90 @@ def select_groups(func, side, ent, rel, d_e, d_r, gamma, emb_init, cand, n_rows,
 
 def _np(x):
     return x.cpu().numpy()
+
+
+def predict_topk(func, ent, rel_tab, gamma, emb_init, score_out, head, rel, tail, exec_mode, k, max_rows=None, known=None,
+                 exclude_mode=None):
+    """the top-k triples of one execution mode (ScoreInfer.topK and ke_model link_predict share this): a list of
+    (head, rel, tail, score, mask) numpy tuples, one per group.  head / rel / tail: checked host id lists (None = all).
+    known (a known.KnownIndex) with exclude_mode 'exclude': combinations that are known triples never enter the selection
+    (kge_topk_select_filtered with the lists of the side the kernel scores; triplet_wise: kge_triples_known on the
+    inputs), a group returns the unknown ones it has, up to k; 'mask': the unfiltered result plus a bool array per group,
+    from one kge_triples_known call over the results of all groups; None: mask is None."""
+    dev = ent.device
+    num_entity, num_rel = ent.shape[0], rel_tab.shape[0]
+    head, rel, tail = _ids(head, num_entity, dev), _ids(rel, num_rel, dev), _ids(tail, num_entity, dev)
+    H, R, T = head.numel(), rel.numel(), tail.numel()
+    d_e, d_r = ent.shape[1], rel_tab.shape[1]
+    exclude = exclude_mode == 'exclude'
+    if exec_mode == 'triplet_wise':
+        if not H == R == T:
+            raise KgeError("For triplet wise execution mode, head, relation and tail lists should have same length")
+        if exclude:
+            keep = th.nonzero(known.known(head, rel, tail) == 0).reshape(-1)       # the unknown inputs, in input order
+            head, rel, tail = head[keep], rel[keep], tail[keep]
+            H = head.numel()
+        hs, rs, ts = ent[head].contiguous(), rel_tab[rel].contiguous(), ent[tail].contiguous()
+        raw = th.empty(H, dtype=th.float32, device=dev)
+        if H:
+            _lib.check(_lib.lib().kge_score_pos(func, _lib.ptr(hs), _lib.ptr(rs), _lib.ptr(ts), H, d_e, d_r,
+                                                gamma, emb_init, _lib.ptr(raw), _lib.stream_ptr()))
+        s, o = vector_topk(raw, k)
+        mask = _np(known.known(head[o], rel[o], tail[o])).astype(bool) if exclude_mode == 'mask' else None
+        return [(_np(head[o]), _np(rel[o]), _np(tail[o]), _np(score_out(s)), mask)]
+
+    def run(side, n_rows, group_rows, split):
+        """split(k) -> (a_pos, rpos) of row k; side 0: a = head, candidates = tails; side 1: a = tail, candidates = heads"""
+        def row_fn(r0, r1):
+            kk = th.arange(r0, r1, dtype=th.int64, device=dev)
+            apos, rpos = split(kk)
+            if side == 0:
+                aid, rid, base = head[apos], rel[rpos], (apos * R + rpos) * T
+            else:
+                aid, rid, base = tail[apos], rel[rpos], rpos * T + apos
+            if exclude:
+                return aid, rid, aid, base, known.ranges(side, aid, rid)
+            return aid, rid, aid, base
+        cand = tail if side == 0 else head
+        return select_groups(func, side, ent, rel_tab, d_e, d_r, gamma, emb_init, cand, n_rows, group_rows, row_fn,
+                             1 if side == 0 else R * T, k, max_rows, known.filt_ids(side) if exclude else None)
+
+    a_major = lambda kk: (kk // R, kk % R)             # rows (a, r), a-major
+    if exec_mode == 'all':
+        side = 0 if T >= H else 1
+        res_s, res_o = run(side, (H if side == 0 else T) * R, max(1, (H if side == 0 else T) * R), a_major)
+    elif exec_mode == 'batch_head':
+        res_s, res_o = run(0, H * R, max(R, 1), a_major)
+    elif exec_mode == 'batch_tail':
+        res_s, res_o = run(1, T * R, max(R, 1), a_major)
+    else:                                                # batch_rel: rows (r, a), relation-major
+        side = 0 if T >= H else 1
+        na = H if side == 0 else T
+        res_s, res_o = run(side, R * na, max(na, 1), lambda kk: (kk % na, kk // na))
+    groups = {'all': 1, 'batch_head': H, 'batch_rel': R, 'batch_tail': T}[exec_mode]
+    combos = {'all': H * R * T, 'batch_head': R * T, 'batch_rel': H * T, 'batch_tail': H * R}[exec_mode]
+    m = min(k, combos)
+    M = None
+    if exclude_mode == 'mask' and m and res_o.shape[0] and H and R and T:
+        o = res_o[:, :m].reshape(-1)                     # (unfiltered: the first m slots of every group are results)
+        tp, rest = o % T, o // T
+        M = _np(known.known(head[rest // R], rel[rest % R], tail[tp])).astype(bool).reshape(-1, m)
+    S, O = _np(score_out(res_s[:, :m])), _np(res_o[:, :m])          # one read-back for all groups
+    hn, rn, tn = _np(head), _np(rel), _np(tail)
+    short = (O < 0).sum(1) if exclude else None                   # fewer unknown combinations than k: empty slots are last
+    out = []
+    for g in range(groups):
+        o = O[g] if g < O.shape[0] else np.zeros(0, np.int64)     # (an empty list on the other axes: no combinations)
+        s = S[g] if g < S.shape[0] else np.zeros(0, np.float32)
+        if exclude and g < O.shape[0] and short[g]:
+            o, s = o[:m - short[g]], s[:m - short[g]]
+        tp, rest = (o % T, o // T) if T else (o, o)
+        rp, hp = (rest % R, rest // R) if R else (rest, rest)
+        mask = None
+        if exclude_mode == 'mask':
+            mask = M[g] if M is not None and g < M.shape[0] else np.zeros(len(o), bool)
+        out.append((hn[hp], rn[rp], tn[tp], s, mask))
+    return out
 
 
 class ScoreInfer(object):
@@ -174,60 +275,8 @@ class ScoreInfer(object):
 
     @on_device
     def _topk(self, head, rel, tail, exec_mode, k):
-        dev = self.dev
-        head, rel, tail = _ids(head, self.num_entity, dev), _ids(rel, self.num_rel, dev), _ids(tail, self.num_entity, dev)
-        H, R, T = head.numel(), rel.numel(), tail.numel()
-        d_e, d_r = self.ent.shape[1], self.rel.shape[1]
-        if exec_mode == 'triplet_wise':
-            if not H == R == T:
-                raise KgeError("For triplet wise execution mode, head, relation and tail lists should have same length")
-            hs, rs, ts = self.ent[head].contiguous(), self.rel[rel].contiguous(), self.ent[tail].contiguous()
-            raw = th.empty(H, dtype=th.float32, device=dev)
-            if H:
-                _lib.check(_lib.lib().kge_score_pos(self.func, _lib.ptr(hs), _lib.ptr(rs), _lib.ptr(ts), H, d_e, d_r,
-                                                    self.gamma, self.emb_init, _lib.ptr(raw), _lib.stream_ptr()))
-            s, o = vector_topk(raw, k)
-            return [(_np(head[o]), _np(rel[o]), _np(tail[o]), _np(self._score_out(s)))]
-
-        def run(side, n_rows, group_rows, split):
-            """split(k) -> (a_pos, rpos) of row k; side 0: a = head, candidates = tails; side 1: a = tail, candidates = heads"""
-            def row_fn(r0, r1):
-                kk = th.arange(r0, r1, dtype=th.int64, device=dev)
-                apos, rpos = split(kk)
-                if side == 0:
-                    hid = head[apos]
-                    return hid, rel[rpos], hid, (apos * R + rpos) * T
-                tid = tail[apos]
-                return tid, rel[rpos], tid, rpos * T + apos
-            cand = tail if side == 0 else head
-            return select_groups(self.func, side, self.ent, self.rel, d_e, d_r, self.gamma, self.emb_init, cand, n_rows,
-                                 group_rows, row_fn, 1 if side == 0 else R * T, k, self.max_rows)
-
-        a_major = lambda kk: (kk // R, kk % R)             # rows (a, r), a-major
-        if exec_mode == 'all':
-            side = 0 if T >= H else 1
-            res_s, res_o = run(side, (H if side == 0 else T) * R, max(1, (H if side == 0 else T) * R), a_major)
-        elif exec_mode == 'batch_head':
-            res_s, res_o = run(0, H * R, max(R, 1), a_major)
-        elif exec_mode == 'batch_tail':
-            res_s, res_o = run(1, T * R, max(R, 1), a_major)
-        else:                                                # batch_rel: rows (r, a), relation-major
-            side = 0 if T >= H else 1
-            na = H if side == 0 else T
-            res_s, res_o = run(side, R * na, max(na, 1), lambda kk: (kk % na, kk // na))
-        groups = {'all': 1, 'batch_head': H, 'batch_rel': R, 'batch_tail': T}[exec_mode]
-        combos = {'all': H * R * T, 'batch_head': R * T, 'batch_rel': H * T, 'batch_tail': H * R}[exec_mode]
-        m = min(k, combos)
-        S, O = _np(self._score_out(res_s[:, :m])), _np(res_o[:, :m])          # one read-back for all groups
-        hn, rn, tn = _np(head), _np(rel), _np(tail)
-        out = []
-        for g in range(groups):
-            o = O[g] if g < O.shape[0] else np.zeros(0, np.int64)     # (an empty list on the other axes: no combinations)
-            s = S[g] if g < S.shape[0] else np.zeros(0, np.float32)
-            tp, rest = (o % T, o // T) if T else (o, o)
-            rp, hp = (rest % R, rest // R) if R else (rest, rest)
-            out.append((hn[hp], rn[rp], tn[tp], s))
-        return out
+        return [g[:4] for g in predict_topk(self.func, self.ent, self.rel, self.gamma, self.emb_init, self._score_out, head, rel,
+                                            tail, exec_mode, k, self.max_rows)]
 
 
 class EmbSimInfer(object):
@@ -242,6 +291,13 @@ class EmbSimInfer(object):
         self.sfunc = sfunc
         self.batch_size = batch_size
         self.max_rows = None
+
+    @classmethod
+    def from_tensor(cls, device, emb, sfunc='cosine'):
+        """the same machinery on a table that is already loaded (ke_model.embed_sim)"""
+        m = cls(device, None, sfunc)
+        m.emb = emb.reshape(emb.shape[0], -1).to(m.dev, th.float32).contiguous()
+        return m
 
     @on_device
     def load_emb(self):

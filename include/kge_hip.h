@@ -623,6 +623,24 @@ int kge_topk_select(int func, int side, const float *ent, int64_t n_ent, const f
                     int64_t n_cand, const int64_t *row_base, int64_t stride, int group_rows, int K, float *res_score,
                     int64_t *res_ord, void *ws, size_t ws_bytes, void *stream);
 int kge_topk_vector(const float *score, int64_t n, int K, float *res_score, int64_t *res_ord, void *ws, size_t ws_bytes, void *stream);
+/* link prediction with known-edge exclusion (the reference's link_predict with exclude_mode, models/ke_model.py:205-455, which
+ * filters after the fact: the 4K best, a loop over g.edge_ids, a full argsort when that was not enough).  The filtered
+ * form of the selection: a candidate j whose ENTITY id (cand[j], or j when cand == NULL) is in row i's list
+ * filt_ids[filt_ptr[2i] .. filt_ptr[2i+1]) - ascending and unique within the list, rows may share lists, an empty range
+ * filters nothing (the layout of the rank evaluation's lists) - never enters the selection: a group with fewer than K
+ * unlisted candidates leaves ordinal -1 in the remaining slots.  Any candidate list (unsorted, repeated ids: every position
+ * of a listed id is left out).  filt_ptr == NULL: exactly the unfiltered entry point; same workspace, same errors, and
+ * filt_ids == NULL with a filt_ptr is an argument error. */
+int kge_topk_select_filtered(int func, int side, const float *ent, int64_t n_ent, const float *rel, int64_t n_rel, const int64_t *h,
+                             const int64_t *r, const int64_t *t, int rows, int d_e, int d_r, float gamma, float emb_init,
+                             const int64_t *cand, int64_t n_cand, const int64_t *row_base, int64_t stride, int group_rows, int K,
+                             float *res_score, int64_t *res_ord, void *ws, size_t ws_bytes, const int64_t *filt_ptr,
+                             const int64_t *filt_ids, void *stream);
+/* out[i] = 1 when the triple (a_i, r_i, b_i) is in the known index, else 0 (ke_model.py:349-377, 'mask', and the per-triple
+ * g.edge_ids of triplet_wise): keys [M] ascending with keys = a * n_rel + r, vals [M] ascending within a key; a two-level
+ * binary search (the key, then the value inside the key's range), since key * n_entities + value need not fit int64. */
+int kge_triples_known(const int64_t *keys, const int64_t *vals, int64_t M, int64_t n_rel, const int64_t *a, const int64_t *r,
+                      const int64_t *b, int64_t n, uint8_t *out, void *stream);
 int kge_sim_pairwise(int sim, const float *emb, int64_t n_emb, int d, const int64_t *left, const int64_t *right, int64_t n, float *out,
                      void *stream);
 
