@@ -1381,6 +1381,9 @@ int launch_neg_fwd_gemm_with_update(const GemmArgs &a, const UpdateArgs &u, hipS
     const bool inplace = !u.emit_ent && !u.emit_rel && !u.g0 && !u.g1 && !u.gs0 && !u.gs1 && !u.gr && !u.gsr && !u.rid &&
                          !u.dry && !u.nd_chunk && u.em.n == 0 && u.rm.n == 0;
     if (!inplace || u.model_d_e % 4 || u.d_r % 4 || dmax > 1024) return KGE_ERR_ARG;
+    // (the update variants below fix the regulariser's norm at 3, like launch_update's LEAN instances: any other norm has no fused
+    //  instantiation and goes to launch_update's generic one - without this the async pipeline applied norm 3 whatever -rn said)
+    if (u.reg_coef > 0.f && u.reg_norm > 0 && u.reg_norm != 3) return KGE_ERR_ARG;
     const int nbE = (u.UE + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK, nbR = (u.UR + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK;
     if (nbE + nbR == 0) return KGE_ERR_ARG;
     const int ti = (a.chunk + 15) / 16, tj = (a.N + 15) / 16;

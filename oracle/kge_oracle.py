@@ -321,9 +321,13 @@ def _criterion(genre, score, label, margin):
         return np.where(v < 0, 0, v), np.where(v < 0, 0, -label).astype(score.dtype)
     if genre == "BCE":
         # -(l*log(sig(s)) + (1-l)*log(1-sig(s)))  (loss.py:30-31); labels 1 / 0 (loss.py:54-56)
+        # written as softplus: -log(sig(s)) = softplus(-s), -log(1 - sig(s)) = softplus(s).  The literal form loses every digit of
+        # log(1 - sig(s)) once sig(s) rounds to 1 (s > 17 in float32, s > 37 in float64); torch's BCELoss clamps its logs at -100
+        # there and reports 100 where the exact value is softplus(s) ~ s - a divergence of the reference's float32 sigmoid, not
+        # followed ('BCE on saturated scores')
         sg = _sigmoid(score)
-        val = -(label * np.log(sg) + (1 - label) * np.log(1 - sg))
-        return val, (sg - label).astype(score.dtype)
+        val = label * np.logaddexp(0, -score) + (1 - label) * np.logaddexp(0, score)
+        return val.astype(score.dtype), (sg - label).astype(score.dtype)
     raise ValueError(genre)
 
 

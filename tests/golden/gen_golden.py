@@ -115,6 +115,11 @@ def run_case(name, case, fp64=False):
     args = make_args(case)
     model = KEModel(args, case["model"], case["n_ent"], case["n_rel"], case["hidden"],
                     case["gamma"], double_entity_emb=case["de"], double_relation_emb=case["dr"])
+    if case.get("init_scale", 1.0) != 1.0:
+        # the loss-option cases: entity and relation tables at a multiple of the default init, so that the scores straddle the
+        # criterion's kink / both tails of the sigmoid (tests/test_loss_option_inputs.py asserts it on the recorded scores)
+        model.entity_emb.emb.mul_(case["init_scale"])
+        model.relation_emb.emb.mul_(case["init_scale"])
     if fp64:
         embs = [model.entity_emb, model.relation_emb] + ([model.score_func.projection_emb] if case["model"] == "TransR" else [])
         for e in embs:
@@ -267,6 +272,27 @@ CASES = {
                                      pairwise=True, seed=31),
     "distmult_logistic_pairwise": base("DistMult", loss_genre="Logistic", adv=False,
                                        pairwise=True, seed=32),
+    # loss genres with -adv / an adversarial temperature != 1 / other score functions, at table scales (init_scale) where the
+    # criterion is exercised on both sides: Hinge with 20 - 80 % of the positives AND of the negatives (pairwise: of the pairs)
+    # active in at least one step, BCE / Logistic with scores spanning [-3, 3] (asserted by tests/test_loss_option_inputs.py)
+    "distmult_hinge_adv": base("DistMult", loss_genre="Hinge", margin=1.0, adv_temp=0.5, init_scale=1.5, seed=101),
+    "transe_l2_bce_adv": base("TransE_l2", loss_genre="BCE", init_scale=3.5, seed=102),
+    "complex_logistic_adv": base("ComplEx", gamma=6.0, de=True, dr=True, loss_genre="Logistic", init_scale=2.2, seed=103),
+    "rotate_hinge": base("RotatE", de=True, loss_genre="Hinge", margin=1.0, adv=False, init_scale=0.82, seed=104),
+    "transe_l1_hinge_adv": base("TransE_l1", loss_genre="Hinge", margin=1.0, init_scale=1.05, seed=105),
+    "transe_l2_hinge_pairwise_impts": base("TransE_l2", loss_genre="Hinge", margin=1.0, adv=False, pairwise=True, impts=True,
+                                           init_scale=3.4, seed=106),
+    "rescal_hinge_adv": base("RESCAL", gamma=6.0, hidden=8, loss_genre="Hinge", margin=1.0, seed=107),
+    "transr_bce_adv": base("TransR", gamma=8.0, hidden=8, loss_genre="BCE", init_scale=0.75, seed=108),
+    "simple_logistic": base("SimplE", gamma=6.0, de=True, dr=True, loss_genre="Logistic", adv=False, init_scale=3.0, seed=109),
+    "nd_distmult_hinge_adv": base("DistMult", loss_genre="Hinge", margin=1.0, neg_deg=True, init_scale=1.7, seed=110),
+    # adversarial temperature != 1 with the default criterion
+    "transe_l2_advtemp2": base("TransE_l2", adv_temp=2.0, init_scale=3.0, seed=111),
+    # regularisation norms other than 3, with a coefficient at which the regulariser is a visible share of every gradient
+    "transe_l2_reg2": base("TransE_l2", reg_norm=2, reg_coef=1e-2, seed=112),
+    "rotate_reg2": base("RotatE", de=True, reg_norm=2, reg_coef=1e-2, seed=113),
+    "distmult_reg1": base("DistMult", gamma=6.0, lr=0.08, reg_norm=1, reg_coef=1e-2, seed=114),
+    "complex_reg4": base("ComplEx", gamma=6.0, de=True, dr=True, reg_norm=4, reg_coef=0.2, seed=115),
     # --neg_deg_sample (general_models.py:396-402, 424-432): the chunk's own positives join the negatives, the
     # diagonal is masked to score 0; their gradients land in the POSITIVE trace
     "nd_transe_l2_small": base("TransE_l2", neg_deg=True, seed=71),
