@@ -265,11 +265,17 @@ int kge_score_neg_bwd(int model, int neg_head, const float *pos_side, const floa
                            neg_score, KGE_SIMPLE_CLAMP, W, n);
         Wuse = W;
     }
-    if (use_mfma(model, d_e, N, flags)) {
+    bool gemm = use_mfma(model, d_e, N, flags);
+    if (gemm) {
         GemmArgs g; fill_gemm(g, model, C, chunk, N, d_e, gamma, A, neg, nullptr);
         g.W = Wuse; g.GA = GA; g.GN = g_neg;
-        KGE_TRY(launch_neg_bwd_gemm(g, s));
-    } else {
+        // KGE_ERR_ARG: chunk or N above the rows a backward tile's workgroup indexes (GB_MAXK, kge_neg_gemm.hip) - nothing was
+        // launched, the pair kernels take any size (the reference accepts any chunk_size / neg_sample_size)
+        const int rc = launch_neg_bwd_gemm(g, s);
+        if (rc == KGE_ERR_ARG) gemm = false;
+        else if (rc != KGE_OK) return fail(rc, "launch_neg_bwd_gemm failed (%d)", rc);
+    }
+    if (!gemm) {
         NegArgs na; fill_pair(na, model, C, chunk, N, d_e, gamma, A, neg, nullptr);
         na.W = Wuse; na.GA = GA; na.GN = g_neg; na.GNp = GNp;
         KGE_TRY(launch_neg_bwd_pair(na, s));

@@ -1089,12 +1089,37 @@ int launch_scatter_add_rows(float *out, int dim, const int64_t *idx, const float
 
 // x.norm(p) ** p over a [n, dim] block (tensor_models.py:54 `norm`; general_models.py:572-576): per-row partials, then a
 // fixed-order single-block sum (deterministic); and its gradient gout * p * |x|^(p-1) * sign(x)
+// |x|^q for the norms the reference's recipes use (q <= 4) by multiplication.  reg_val / reg_grad with a run-time q go through
+// v_log_f32 / v_exp_f32, whose error grows with q * |log2 |x||: measured 1.3e-6 relative on gradient elements and 1.9 roundings
+// on a one-element value, where tests/test_gpu_modular_ops.py holds these two ops to 1e-6 and to ONE rounding per term of the sum
+// (the value's terms are multiplied in double and rounded once; these kernels run once per trace, off the fused path)
+__device__ __forceinline__ float ipow_abs(float ax, int q) {
+    const float a2 = ax * ax;
+    switch (q) {
+        case 0: return 1.f;
+        case 1: return ax;
+        case 2: return a2;
+        case 3: return a2 * ax;
+        case 4: return a2 * a2;
+    }
+    return ax > 0.f ? __builtin_amdgcn_exp2f((float)q * __builtin_amdgcn_logf(ax)) : 0.f;
+}
+__device__ __forceinline__ float pnorm_term(float x, int q) {
+    const double a = fabs((double)x), a2 = a * a;
+    switch (q) {
+        case 1: return fabsf(x);
+        case 2: return (float)a2;
+        case 3: return (float)(a2 * a);
+        case 4: return (float)(a2 * a2);
+    }
+    return reg_val(x, q);
+}
 __global__ __launch_bounds__(KGE_BLOCK) void pnorm_rows_kernel(const float *x, int64_t n, int dim, int p, float *part) {
     const int64_t k = WAVE_ID();
     if (k >= n) return;
     const float *r = x + k * (int64_t)dim;
     float v = 0.f;
-    for (int d = LANE(); d < dim; d += 64) v += reg_val(r[d], p);
+    for (int d = LANE(); d < dim; d += 64) v += pnorm_term(r[d], p);
     v = wave_sum(v);
     if (LANE() == 0) part[k] = v;
 }
@@ -1109,7 +1134,9 @@ __global__ __launch_bounds__(KGE_BLOCK) void pnorm_final_kernel(const float *par
 }
 __global__ void pnorm_bwd_kernel(const float *x, int64_t total, int p, const float *gout, float *gx) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < total) gx[k] = reg_grad(x[k], *gout, p);
+    if (k >= total) return;
+    const float v = x[k], g = *gout * (float)p * ipow_abs(fabsf(v), p - 1);
+    gx[k] = v > 0.f ? g : (v < 0.f ? -g : 0.f);
 }
 int launch_pnorm(const float *x, int64_t n, int dim, int p, float *part, float *out, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(pnorm_rows_kernel, dim3(blocks_for_waves(n)), dim3(KGE_BLOCK), 0, s, x, n, dim, p, part);
