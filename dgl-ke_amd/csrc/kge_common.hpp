@@ -47,15 +47,19 @@ struct KgeTlScope {
     }
 };
 #define KGE_TL(kid) KgeTlScope kge_tl_scope_((kid), (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)))
-#define KGE_TL_MARK(n) kge_tl_scope_.mark(n)
-#define KGE_TL_MARK_K(kid, n) kge_tl_mark((kid), (n))
 #define KGE_TL_DEFINE(name) extern "C" int kge_tl_set_##name(void *p) { \
         return hipMemcpyToSymbol(HIP_SYMBOL(kge_tl_buf), &p, sizeof(p)) == hipSuccess ? 0 : -1; }
 #else
 #define KGE_TL(kid)
+#define KGE_TL_DEFINE(name)
+#endif
+// phase marks inside the wavefronts: only in a timeline build that also has -DKGE_TL_MARKS (a mark changes the overlap, see kge_tl_mark)
+#if defined(KGE_TIMELINE) && defined(KGE_TL_MARKS)
+#define KGE_TL_MARK(n) kge_tl_scope_.mark(n)
+#define KGE_TL_MARK_K(kid, n) kge_tl_mark((kid), (n))
+#else
 #define KGE_TL_MARK(n)
 #define KGE_TL_MARK_K(kid, n)
-#define KGE_TL_DEFINE(name)
 #endif
 
 namespace kge {
@@ -174,12 +178,7 @@ template <> __device__ __forceinline__ void st_wt<1>(float *p, const Pack<1> &x)
 // back at the end of the kernel, in front of the next launch (RotatE: 3.1 us instead of 1.2 between the shared-pair backward and
 // edge_bwd).  Measured on one box (profiles/r04_store_policy.txt): RotatE FB15k shape 60.7 -> 58.3 us/step, cfg-R per GPU 99.5 ->
 // 97.5 (p2p) / 116.4 -> 114.9 (a2a); the a2a engine's gradient messages and gathered cache rows stay plain (write-through: +1.2 us).
-// -DKGE_PLAIN_INTERMEDIATES: plain stores everywhere, -DKGE_PLAIN_NEXT: all but the partials (A/B aids)
-#if defined(KGE_PLAIN_INTERMEDIATES) || defined(KGE_PLAIN_NEXT)
-#define KGE_ST_NEXT kge::st
-#else
 #define KGE_ST_NEXT kge::st_wt
-#endif
 template <int V> __device__ __forceinline__ Pack<V> zero_pack() {
     Pack<V> r;
 #pragma unroll
@@ -589,9 +588,7 @@ struct RescalOuterArgs {             // G_i = c_i * u_i v_i^T (+ G_i) (+ regular
     float *G;                                // [B, D*D]
 };
 #define RESCAL_RB 8                  // row blocks per relation matrix in the update kernels
-#ifndef RESCAL_RBN
 #define RESCAL_RBN 16                // row blocks per relation matrix in the per-unique-relation passes of the fused step
-#endif
 struct RescalUpdateArgs {            // fused Adagrad of the relation matrices (kge_rescal.hip)
     int B, D, UE, UR, neg_head, reg_norm;
     float lr, eps, reg_coef;
@@ -653,12 +650,8 @@ struct TransRArgs {
                                      // the negative rows' regulariser is left to the update kernel (sampled rows only)
     int nG; float *GNp;              // split-K groups of the negative-row gradient and their partial tiles [nG, C*N, De]
 };
-#ifndef TRANSR_GN_GROUPS
 #define TRANSR_GN_GROUPS 16
-#endif
-#ifndef TRANSR_GN_GROUPS_WIDE
 #define TRANSR_GN_GROUPS_WIDE 64     // split-K groups of the 128 x 208-tile kernel (kge_transr_wide.hpp): 4 chunks x 2 row tiles need them
-#endif
 int transr_gn_groups(int De, int Dr, int chunk, int N);      // how many groups launch_transr_bwd will use for this shape
 int launch_transr_pos(const TransRArgs &a, hipStream_t s);
 int launch_transr_fwd(const TransRArgs &a, hipStream_t s);

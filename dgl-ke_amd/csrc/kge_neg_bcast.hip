@@ -25,15 +25,9 @@ KGE_TL_DEFINE(bcast)
 
 #define SB_KB 16                                 // real models: reduction elements per forward sub-slab
 #define SB_KC 8                                  // RotatE: complex columns per sub-slab
-#ifndef SB_KWR
 #define SB_KWR 8                                 // backward, real models: output columns per wavefront
-#endif
-#ifndef SB_RWR
 #define SB_RWR 4                                 // forward, real models: uniform rows per wavefront
-#endif
-#ifndef SB_RWC
 #define SB_RWC 4                                 // forward, RotatE: uniform rows per wavefront (2: 19.4 us, 4: 16.4 us)
-#endif
 
 static inline int check_launch_b() { return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH; }
 
@@ -82,25 +76,15 @@ __device__ __forceinline__ void fwd_step(const float (&xc)[16], const float *ly,
 #pragma unroll
         for (int r = 0; r < RW; ++r) {
             const float *yp = ly + r * 64 + (LB >= 0 ? LB : lbr) + e;
-#ifdef PROBE_FWD_NOY            // tuning probes (wrong results): timing without one ingredient of the loop
-            (void)yp;
-            const v2f y0 = {xc[(e + 2 * r) & 7], xc[(e + 2 * r + 1) & 7]};
-            v2f y1 = {xc[8 + ((e + 2 * r) & 7)], xc[8 + ((e + 2 * r + 1) & 7)]};
-#else
             const v2f y0 = *reinterpret_cast<const v2f *>(yp);
             v2f y1 = {0.f, 0.f};
             if constexpr (CPLX) y1 = *reinterpret_cast<const v2f *>(yp + RW * 64);
-#endif
             const v2f x0 = {xc[e], xc[e + 1]};
             if constexpr (CPLX) {
                 const v2f x1 = {xc[8 + e], xc[9 + e]};
                 const v2f dr = y0 - x0, di = y1 - x1;
                 const v2f m2 = __builtin_elementwise_fma(di, di, dr * dr);
-#ifdef PROBE_FWD_NOSQRT
-                acc[r] += m2;
-#else
                 acc[r] += (v2f){fast_sqrt(m2.x), fast_sqrt(m2.y)};
-#endif
             } else if constexpr (MODEL == KGE_TRANSE_L1) {
                 // one packed subtraction, then |.| as the free source modifier of two scalar additions (written
                 // as asm: the vectoriser otherwise re-packs the additions and pays two v_and for the |.|)
@@ -146,18 +130,10 @@ __device__ __forceinline__ void fwd_step(const float (&xc)[16], const float *ly,
 // LDS in fixed order (run 0 + run 1 + ...): deterministic, one barrier per workgroup.
 // RotatE (arithmetic-heavy: a square root per complex element) gains from it; the real-valued models do not (TransE_l1: the
 // per-lane row loads bound the kernel whatever the occupancy) and keep one wavefront per task.
-#ifndef SB_KS_C
 #define SB_KS_C 4                                // RotatE: wavefronts per task (runs of the reduction)
-#endif
-#ifndef SB_TPB_C
 #define SB_TPB_C 4                               // RotatE: tasks per workgroup (consecutive: same strip, the x rows hit in L1)
-#endif
-#ifndef SB_KS_R
 #define SB_KS_R 1                                // real-valued models
-#endif
-#ifndef SB_TPB_R
 #define SB_TPB_R 4
-#endif
 template <int MODEL> struct FwdShape {
     static constexpr bool CPLX = MODEL == KGE_ROTATE;
     static constexpr int RW = CPLX ? SB_RWC : SB_RWR, KS = CPLX ? SB_KS_C : SB_KS_R, TPB = CPLX ? SB_TPB_C : SB_TPB_R;
@@ -245,9 +221,7 @@ __device__ __forceinline__ void neg_fwd_bcast_body(const NegArgs &a, int ns, int
     float yr[RW], yi[RW], ynr[RW], yni[RW], xa[16], xb[16];
     loady(yr, yi, k_lo);
     loadx(xa, k_lo);
-#ifdef KGE_TL_MARKS
     KGE_TL_MARK_K(1, 0);           // ids, row pointers and the first operands have arrived
-#endif
     if constexpr (SB_KS == 1) {
         // one wavefront per task (real-valued models): full blocks unrolled with compile-time lane bases, branch-free (round 2's
         // loop: at one wavefront per SIMD the rolled form below costs TransE_l1 6 us per launch)
@@ -305,15 +279,11 @@ __device__ __forceinline__ void neg_fwd_bcast_body(const NegArgs &a, int ns, int
         }
         return;
     }
-#ifdef KGE_TL_MARKS
     KGE_TL_MARK_K(1, 1);           // this wavefront's run is done
-#endif
 #pragma unroll
     for (int r = 0; r < RW; ++r) part[wave][r][lane] = acc[r].x + acc[r].y;
     __syncthreads();
-#ifdef KGE_TL_MARKS
     KGE_TL_MARK_K(1, 2);           // every run of the workgroup is done
-#endif
     // one output per thread and pass: (task tw2, row r, negative l); the runs are added in run order
     for (int o = threadIdx.x; o < SB_TPB * RW * 64; o += SB_FWD_BLOCK) {
         const int l = o & 63, r = (o >> 6) % RW, tw2 = (o >> 6) / RW;
@@ -345,9 +315,7 @@ __device__ __forceinline__ void neg_fwd_bcast_body(const NegArgs &a, int ns, int
 // stage's arithmetic and written after it, one workgroup barrier per stage.  Same sums in the same order as the body above
 // (sub-slab by sub-slab, even / odd accumulators, runs added in run order): bit-identical scores.
 // ---------------------------------------------------------------------------------------------
-#ifndef SB_XLDS
-#define SB_XLDS 1
-#endif
+#define SB_XLDS 1                                // RotatE takes this instance where its staging map fits (fwd_launch)
 #define SB_XST 16                                // complex columns per stage
 #define SB_XRS 36                                // dwords per staged row: 16 re | 16 im | 4 pad
 __device__ __forceinline__ void neg_fwd_rot_xlds_body(const NegArgs &a, int ns, int ng, int bid) {
@@ -427,11 +395,6 @@ __device__ __forceinline__ void neg_fwd_rot_xlds_body(const NegArgs &a, int ns, 
 #pragma unroll 1
         for (int s = 0; s < send; ++s) {
             const int k0 = kb + s * SB_XST;
-#ifdef PROBE_FWD_NOX            // tuning probe (wrong results): no staging, no barrier, x read once
-            if (s0 == 0 && s == 0) { xread(xa, bf, 0); xread(xb, bf, 1); }
-            if (k0 < k_hi) fwd_step<KGE_ROTATE, RW, NE, -1>(xa, ly, acc, k0 - kb);
-            if (k0 + NE < k_hi) fwd_step<KGE_ROTATE, RW, NE, -1>(xb, ly, acc, k0 + NE - kb);
-#else
             gx(k0 + SB_XST);                                     // next stage (past the run: a harmless clamped re-read)
             xread(xa, bf, 0);
             xread(xb, bf, 1);
@@ -440,7 +403,6 @@ __device__ __forceinline__ void neg_fwd_rot_xlds_body(const NegArgs &a, int ns, 
             sxw(bf ^ 1);
             __syncthreads();
             bf ^= 1;
-#endif
         }
 #pragma unroll
         for (int r = 0; r < RW; ++r) { yr[r] = ynr[r]; yi[r] = yni[r]; }
@@ -467,14 +429,8 @@ __device__ __forceinline__ void neg_fwd_rot_xlds_body(const NegArgs &a, int ns, 
 // share operands - the forward's 16 workgroups of a (chunk, strip) read the same 64 negative rows (205 KB at cfg-R), the backward's
 // workgroups of a (chunk, column slab) the same slab of A and of the negatives - and in hardware order they sat on eight different
 // XCDs: every L2 fetched every strip (PMC FETCH_SIZE of the forward 29 MB for 6.6 MB of distinct operands at cfg-R,
-// profiles/r05_rotate_wide_pmc_FETCH_SIZE.txt).  xcd_remap hands an XCD a contiguous range of logical ids.  -DSB_NO_XCD: hardware order.
-__device__ __forceinline__ int sb_block(int b, int nb) {
-#ifdef SB_NO_XCD
-    (void)nb; return b;
-#else
-    return kge::xcd_remap(b, nb);
-#endif
-}
+// profiles/r05_rotate_wide_pmc_FETCH_SIZE.txt).  xcd_remap hands an XCD a contiguous range of logical ids.
+__device__ __forceinline__ int sb_block(int b, int nb) { return kge::xcd_remap(b, nb); }
 template <int MODEL>
 __global__ __launch_bounds__(FwdShape<MODEL>::BLOCK) void neg_fwd_bcast_kernel(NegArgs a, int ns, int ng) {
     KGE_TL(1);
@@ -712,9 +668,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void neg_bwd_bcast_kernel(NegArgs a, int
 // RotatE (B 1024, N 256, 200 complex columns) 58.8 -> 27.9 + 5.4 us; arithmetic alone (no loads, no LDS) 13 / 10 us.
 // ---------------------------------------------------------------------------------------------
 #define LC_CW 32                                 // (complex) columns per wavefront: 16 lanes x 2
-#ifndef LC_GQ_CPLX
 #define LC_GQ_CPLX 4                             // quads of negatives per group (staging + LDS reduction round), RotatE
-#endif
 #define LC_GQ_REAL 8                             // ... TransE_l1; both sized so that TWO workgroups fit the LDS of a CU
 #define LC_RTMAX 20                              // most positive rows a wavefront keeps in registers (RotatE: 16)
 
@@ -722,11 +676,7 @@ __device__ __forceinline__ float4 zero4b() { return make_float4(0.f, 0.f, 0.f, 0
 // the GN partials / GA parts leave write-through (kge_common.hpp KGE_ST_NEXT): 13 MB (FB15k shape) - 26 MB (cfg-R) of lines left dirty in the XCDs' L2s
 // were written back at the end of the kernel, in front of the next launch (gap 3.1 us instead of 1.2-1.3, tools/timeline.py)
 __device__ __forceinline__ void st_v2(float *p, v2f x) {
-#ifdef KGE_PLAIN_INTERMEDIATES
-    *reinterpret_cast<v2f *>(p) = x;
-#else
     asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" : : "v"(p), "v"(x) : "memory");
-#endif
 }
 template <int L> __device__ __forceinline__ float rowb(float v) {    // lane L of every row of 16 lanes
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x150 + L, 0xF, 0xF, true));
@@ -739,31 +689,16 @@ template <int L> __device__ __forceinline__ float rowb(float v) {    // lane L o
 // per quad) rather than by VALU issue - more rows per wavefront amortise it, split negatives restore the workgroup count:
 // 8 rows x 455 workgroups 58.3; 8 rows, 2 splits 58.6; 10-12 rows x 325 workgroups x 3 splits 55.9 (taken); 13-16 rows x 260 x 3
 // 59.6; 9 rows x 390 x 2 64.7; 10-12 rows unsplit 64.0
-#ifndef LC_RPW_MIN_REAL
 #define LC_RPW_MIN_REAL 10                       // TransE_l1: fewest rows a wavefront keeps when the launch can afford more workgroups
-#endif
-#ifndef LC_RPW_MIN_CPLX
 #define LC_RPW_MIN_CPLX 8
-#endif
-#ifndef LC_NO_SPLIT_REAL
-#define LC_SPLIT_REAL 1
-#endif
 // Wavefronts per workgroup (round 6).  The GN partials are one per WORKGROUP row group: a workgroup of 4 wavefronts x 8 rows sums 32
 // positives in LDS and cfg-R (chunk 256, D_e 800) left 8 partials per negative row - 26 MB written write-through and read back by the
 // reduction, the largest single item of that step's fabric traffic (profiles/r05_rotate_wide_pmc_*).  8 wavefronts per workgroup (64
 // positives meet in LDS) halve them at the same rows per wavefront, the same occupancy (two workgroups of 8 instead of four of 4 per
 // CU) and the same order of additions inside a wavefront; round 4 measured the launch times a wash (backward +0.5 us, reduction -0.4)
 // and dropped it, round 6 takes it for the bytes.  Wide RotatE rows only: at the FB15k shapes the partials are small.
-#ifndef LC_WPB8_MIN_DE
 #define LC_WPB8_MIN_DE 512
-#endif
-static inline int lc_wpb(int model, int d_e) {
-#ifdef LC_NO_WPB8
-    (void)model; (void)d_e; return 4;
-#else
-    return (model == KGE_ROTATE && d_e >= LC_WPB8_MIN_DE) ? 8 : 4;
-#endif
-}
+static inline int lc_wpb(int model, int d_e) { return (model == KGE_ROTATE && d_e >= LC_WPB8_MIN_DE) ? 8 : 4; }
 static inline void lc_shape(int model, int C, int chunk, int d_e, int &nslab, int &nrw, int &rpw) {
     const int K = model == KGE_ROTATE ? d_e / 2 : d_e;
     const int wpb = lc_wpb(model, d_e);
@@ -790,20 +725,11 @@ size_t neg_bwd_lc_partial_floats(int model, int C, int chunk, int N, int d_e) {
 }
 
 // LC_WPE: wavefronts per SIMD the register allocation aims at where the instantiation fits without spilling (RotatE: 8 rows per
-// wavefront, TransE_l1: up to 16); LC_RED_SINGLE: one buffer of GN partials and a second barrier per group (32 instead of 48 KB
-// of LDS).  Together: four workgroups per CU - every workgroup of the split RotatE launch resident at once (60.9 vs 61.7 us/step)
-#ifndef LC_NO_OCC4
+// wavefront, TransE_l1: up to 16); with ONE buffer of GN partials and a second barrier per group (32 instead of 48 KB of LDS for two
+// alternating buffers): four workgroups per CU - every workgroup of the split RotatE launch resident at once (60.9 vs 61.7 us/step)
 #define LC_WPE 4
-#define LC_RED_SINGLE 1
-#endif
-#ifdef LC_WPE
 #define LC_OCC __attribute__((amdgpu_waves_per_eu((RT <= (MODEL == KGE_ROTATE ? 8 : 16)) ? LC_WPE : 1, (RT <= (MODEL == KGE_ROTATE ? 8 : 16)) ? LC_WPE : 8)))
-#else
-#define LC_OCC
-#endif
-#ifndef LC_WG_CAP
 #define LC_WG_CAP 1024                           // negatives are split while the launch stays within this many workgroups
-#endif
 template <int MODEL, int RT, int WPB = KGE_WAVES_PER_BLOCK>
 __global__ __launch_bounds__(64 * WPB) LC_OCC void neg_bwd_lc_kernel(NegArgs a, int nslab, int nrw, int rpw) {
     KGE_TL(3);
@@ -811,12 +737,7 @@ __global__ __launch_bounds__(64 * WPB) LC_OCC void neg_bwd_lc_kernel(NegArgs a, 
     constexpr bool CPLX = MODEL == KGE_ROTATE;
     constexpr int NV = CPLX ? 4 : 2;                             // floats per lane in a GN partial
     constexpr int LC_GQ = CPLX ? LC_GQ_CPLX : LC_GQ_REAL, LC_SG = 4 * LC_GQ;   // quads / negatives per group
-#ifdef LC_RED_SINGLE
-    constexpr int NRED = 1;                                      // one buffer of GN partials + a second barrier per group: 32 KB of LDS, 4 workgroups per CU
-#else
-    constexpr int NRED = 2;                                      // two alternating buffers
-#endif
-    __shared__ __attribute__((aligned(16))) float red[NRED * LC_GQ * WPB * 64 * NV];   // GN partials
+    __shared__ __attribute__((aligned(16))) float red[LC_GQ * WPB * 64 * NV];   // GN partials: one buffer + a second barrier per group (32 KB of LDS, 4 workgroups per CU)
     __shared__ __attribute__((aligned(16))) float stage[2 * LC_SG * LC_CW * (CPLX ? 2 : 1) + 2 * WPB * LC_SG * (RT > 16 ? 32 : 16)];
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63, sg = lane >> 4, kk = lane & 15;
@@ -835,11 +756,7 @@ __global__ __launch_bounds__(64 * WPB) LC_OCC void neg_bwd_lc_kernel(NegArgs a, 
         //  [32 (k % 8), 32 (k % 8) + 32): parts of the same (chunk, slab) columns share an L2; the heaviest-first dealing over the
         //  rounds is unchanged per CU slot)
         const int b = (int)blockIdx.x, rnd = b >> 8;
-#ifdef SB_NO_XCD
-        const int k = b & 255;
-#else
         const int k = ((b & 7) << 5) | ((b & 255) >> 3);
-#endif
         int t = (rnd << 8) + ((rnd & 1) ? 255 - k : k);
         const int P = a.lc_P, nB = a.lc_nB, ncol = a.C * nslab * nrw, nA = ncol - nB;
         const int remB = ngr % P, remA = ngr % (P + 1);
@@ -928,10 +845,6 @@ __global__ __launch_bounds__(64 * WPB) LC_OCC void neg_bwd_lc_kernel(NegArgs a, 
     };
     // operands of one quad out of LDS buffer bf: y = b_s[cols] (s = quad g, lane row sg), raw W values
     auto lread = [&](int bf, int g, v2f &yr_, v2f &yi_, float &w0_, float &w1_) {
-#ifdef PROBE_BWD_NOLREAD        // tuning probe (wrong results): operands of a quad without the LDS round
-        yr_ = xr[g & 3] * 0.5f; yi_ = xi[g & 3] * 0.5f; w0_ = xr[0].x; w1_ = 0.f; (void)bf;
-        return;
-#endif
         const float *yb = ybuf + (bf * LC_SG + 4 * g + sg) * YF + 2 * kk;
         yr_ = *reinterpret_cast<const v2f *>(yb);
         yi_ = CPLX ? *reinterpret_cast<const v2f *>(yb + LC_CW) : (v2f){0.f, 0.f};
@@ -940,7 +853,7 @@ __global__ __launch_bounds__(64 * WPB) LC_OCC void neg_bwd_lc_kernel(NegArgs a, 
         w1_ = RT > 16 ? wb[16] : 0.f;
     };
     // one quad: RT rows of this wavefront against the 4 negatives of the quad; GN partial -> LDS
-    auto quad = [&](int g, float *redb, const v2f &yr_, const v2f &yi_, float wa, float wb) {
+    auto quad = [&](int g, const v2f &yr_, const v2f &yi_, float wa, float wb) {
         v2f nr = {0.f, 0.f}, ni = {0.f, 0.f};
         static_for<RT>([&](auto nc) {
             constexpr int n = decltype(nc)::value;
@@ -948,11 +861,7 @@ __global__ __launch_bounds__(64 * WPB) LC_OCC void neg_bwd_lc_kernel(NegArgs a, 
             if constexpr (CPLX) {
                 const v2f dr = xr[n] - yr_, di = xi[n] - yi_;
                 const v2f m2 = __builtin_elementwise_fma(di, di, __builtin_elementwise_fma(dr, dr, (v2f){1e-30f, 1e-30f}));
-#ifdef PROBE_BWD_NORSQ
-                const v2f iv = m2 * w;
-#else
                 const v2f iv = (v2f){fast_rsq(m2.x), fast_rsq(m2.y)} * w;   // + tiny: zero difference -> zero gradient
-#endif
                 gr[n] = __builtin_elementwise_fma(dr, -iv, gr[n]);
                 gi[n] = __builtin_elementwise_fma(di, -iv, gi[n]);
                 nr = __builtin_elementwise_fma(dr, iv, nr);
@@ -967,14 +876,9 @@ __global__ __launch_bounds__(64 * WPB) LC_OCC void neg_bwd_lc_kernel(NegArgs a, 
                 nr = __builtin_elementwise_fma(sgn, wv, nr);
             }
         });
-        float *slot = redb + ((g * WPB + wave) * 64 + lane) * NV;
-#ifdef PROBE_BWD_NORED          // tuning probe (wrong results): the GN partials stay in registers (folded into GA so that they are not dead)
-        gr[0] += nr; if constexpr (CPLX) gi[0] += ni;
-        (void)slot;
-#else
+        float *slot = red + ((g * WPB + wave) * 64 + lane) * NV;
         if constexpr (CPLX) *reinterpret_cast<float4 *>(slot) = make_float4(nr.x, nr.y, ni.x, ni.y);
         else *reinterpret_cast<v2f *>(slot) = nr;
-#endif
     };
     gload(min(q_lo, nq - 1));
     lstore(0, q_lo);
@@ -983,12 +887,9 @@ __global__ __launch_bounds__(64 * WPB) LC_OCC void neg_bwd_lc_kernel(NegArgs a, 
     // previous group's partial-sum stores
     __builtin_amdgcn_s_waitcnt(0x0F70);                          // vmcnt(0)
     __syncthreads();
-#ifdef KGE_TL_MARKS
     KGE_TL_MARK_K(3, 0);           // own rows and the first group of operands are staged
-#endif
     int buf = 0;
     for (int qb = q_lo; qb < q_hi; qb += LC_GQ) {
-        float *redb = red + (NRED == 2 ? buf : 0) * (LC_GQ * WPB * 64 * NV);
         gload(min(qb + LC_GQ, nq - 1));                          // next group (past the end: a harmless re-read)
         v2f ya, yia, yb_, yib;
         float wa0, wa1, wb0, wb1;
@@ -998,32 +899,21 @@ __global__ __launch_bounds__(64 * WPB) LC_OCC void neg_bwd_lc_kernel(NegArgs a, 
 #pragma unroll 1
         for (int g = 0; g < LC_GQ; g += 2) {
             lread(buf, g + 1, yb_, yib, wb0, wb1);
-            quad(g, redb, ya, yia, wa0, wa1);
+            quad(g, ya, yia, wa0, wa1);
             lread(buf, g + 2 < LC_GQ ? g + 2 : LC_GQ - 1, ya, yia, wa0, wa1);
-            quad(g + 1, redb, yb_, yib, wb0, wb1);
+            quad(g + 1, yb_, yib, wb0, wb1);
         }
         lstore(buf ^ 1, qb + LC_GQ);
         __syncthreads();
-#ifdef PROBE_BWD_NORED
-        buf ^= 1;
-        continue;
-#endif
-        // fixed-order sum over the 4 wavefronts: one partial per (workgroup row group, negative, column).  The
-        // LDS buffers alternate, so the next group needs no second barrier.
-#if !defined(KGE_PLAIN_INTERMEDIATES) && !defined(LC_ST8)
-        constexpr bool ST16 = !CPLX;
-#else
-        constexpr bool ST16 = false;
-#endif
-        if constexpr (ST16) {
+        // fixed-order sum over the 4 wavefronts: one partial per (workgroup row group, negative, column)
+        if constexpr (!CPLX) {
         // (real-valued models, write-through stores: 16 bytes each - an 8-byte sc1 store costs 2.7 x a 16-byte one per byte,
         //  MI355X_MICROARCH.md - so a thread sums the partials of TWO adjacent lanes = four consecutive columns; per element the
         //  same additions in the same wavefront order as the per-lane form.  Measured: TransE_l1 53.7 -> 53.0 us/step; RotatE
         //  (two halves per lane) is 0.5-0.9 us FASTER with the per-lane 8-byte stores and keeps them; profiles/r04_store_policy.txt)
-        for (int e = tid; e < LC_GQ * (CPLX ? 64 : 32); e += LC_BLOCK) {
-            const int g = CPLX ? e >> 6 : e >> 5, r = CPLX ? e & 63 : (e & 31) * 2;
-            const int l0 = r & ~1, part = CPLX ? r & 1 : 0;
-            const float *p = redb + (g * WPB * 64 + l0) * NV + 2 * part;
+        for (int e = tid; e < LC_GQ * 32; e += LC_BLOCK) {
+            const int g = e >> 5, l0 = (e & 31) * 2;
+            const float *p = red + (g * WPB * 64 + l0) * NV;
             const int sN = 4 * (qb + g) + (l0 >> 4);
             const int cl = slab * LC_CW + 2 * (l0 & 15);
             v2f s0 = *reinterpret_cast<const v2f *>(p), s1 = *reinterpret_cast<const v2f *>(p + NV);
@@ -1034,42 +924,33 @@ __global__ __launch_bounds__(64 * WPB) LC_OCC void neg_bwd_lc_kernel(NegArgs a, 
             }
             if (sN < N && cl < K) {                              // K % 4 == 0: four columns or none
                 Pack<4> o4; o4.v[0] = s0.x; o4.v[1] = s0.y; o4.v[2] = s1.x; o4.v[3] = s1.y;
-                st_wt<4>(a.GNp + (((int64_t)rw * a.C + c) * N + sN) * D + cl + part * K, o4);
+                st_wt<4>(a.GNp + (((int64_t)rw * a.C + c) * N + sN) * D + cl, o4);
             }
         }
         } else {
         for (int e = tid; e < LC_GQ * 64; e += LC_BLOCK) {
             const int g = e >> 6, l = e & 63;
-            const float *p = redb + (g * WPB * 64 + l) * NV;
+            const float *p = red + (g * WPB * 64 + l) * NV;
             const int sN = 4 * (qb + g) + (l >> 4);
             const int cl = slab * LC_CW + 2 * (l & 15);
             float *o = a.GNp + (((int64_t)rw * a.C + c) * N + sN) * D + cl;
-            if constexpr (CPLX) {
-                // (the wavefronts' partials in wavefront order: ((v0 + v1) + v2) + v3 [+ v4 ... + v7])
-                float4 pv[WPB];
+            // (the wavefronts' partials in wavefront order: ((v0 + v1) + v2) + v3 [+ v4 ... + v7])
+            float4 pv[WPB];
 #pragma unroll
-                for (int w = 0; w < WPB; ++w) pv[w] = *reinterpret_cast<const float4 *>(p + w * 64 * NV);
-                float4 acc = pv[0];
+            for (int w = 0; w < WPB; ++w) pv[w] = *reinterpret_cast<const float4 *>(p + w * 64 * NV);
+            float4 acc = pv[0];
 #pragma unroll
-                for (int w = 1; w < WPB; ++w) { acc.x += pv[w].x; acc.y += pv[w].y; acc.z += pv[w].z; acc.w += pv[w].w; }
-                if (sN < N && cl < K) {
-                    st_v2(o, (v2f){acc.x, acc.y});
-                    st_v2(o + K, (v2f){acc.z, acc.w});
-                }
-            } else {
-                v2f acc = *reinterpret_cast<const v2f *>(p);
-#pragma unroll
-                for (int w = 1; w < WPB; ++w) acc += *reinterpret_cast<const v2f *>(p + w * 64 * NV);
-                if (sN < N && cl < K) st_v2(o, acc);
+            for (int w = 1; w < WPB; ++w) { acc.x += pv[w].x; acc.y += pv[w].y; acc.z += pv[w].z; acc.w += pv[w].w; }
+            if (sN < N && cl < K) {
+                st_v2(o, (v2f){acc.x, acc.y});
+                st_v2(o + K, (v2f){acc.z, acc.w});
             }
         }
         }
         buf ^= 1;
-        if constexpr (NRED == 1) __syncthreads();                // the partials are read before the next group overwrites them
+        __syncthreads();                                         // the partials are read before the next group overwrites them
     }
-#ifdef KGE_TL_MARKS
     KGE_TL_MARK_K(3, 1);           // groups done
-#endif
     // GA: sum over the 4 lane rows (different negatives), then lane row 0 stores
 #pragma unroll
     for (int n = 0; n < RT; ++n) {
@@ -1109,45 +990,29 @@ __global__ __launch_bounds__(KGE_BLOCK) void gn_reduce_kernel(NegArgs a, int nrw
     }
 }
 
-// balanced split (NegArgs::lc_P): the instances that hold four workgroups per CU (RotatE at <= 8 rows per wavefront, TransE_l1 at
-// <= 16), every part >= 2 (RotatE) / 1 (TransE_l1) groups of quads, at most 8 / 4 parts.  Measured (tools/timeline.py --per-cu, rotate_fb15k): 896 equal workgroups = 3.5 per CU -
+// balanced split (NegArgs::lc_P): the instances that hold four workgroups per CU (RotatE at <= 8 rows per wavefront), every part
+// >= 2 groups of quads, at most 8 parts.  Measured (tools/timeline.py --per-cu, rotate_fb15k): 896 equal workgroups = 3.5 per CU -
 // the CUs holding four end 3.5 us after those holding three (wavefront life p50 17.6 vs 15.4 us); cfg-R: 832 = 3.25 per CU.
-#ifndef LC_NO_BALANCE
-#define LC_BALANCE 1
-#endif
+// RotatE only: for TransE_l1 it measured 52.95 -> 52.3 us/step (975 -> 1024 workgroups) but the oracle comparison at the recipe's full
+// shape failed with it (tests/test_gpu_parity.py SHAPES)
 static bool lc_balance(int model, int C, int chunk, int N, int d_e, int &P, int &nB) {
     P = 0; nB = 0;
-#ifdef LC_BALANCE
-#ifdef LC_BALANCE_REAL       // TransE_l1: measured 52.95 -> 52.3 us/step (975 -> 1024 workgroups) and NOT validated - the oracle comparison at the
-    const bool real_ok = model == KGE_TRANSE_L1;     // recipe's full shape fails with it (tests/test_gpu_parity.py SHAPES); off
-#else
-    const bool real_ok = false;
-#endif
-    if ((model != KGE_ROTATE && !real_ok) || !neg_bwd_lc_supported(model, d_e) || N % 4 || d_e % 4) return false;
+    if (model != KGE_ROTATE || !neg_bwd_lc_supported(model, d_e) || N % 4 || d_e % 4) return false;
     int nslab, nrw, rpw;
     lc_shape(model, C, chunk, d_e, nslab, nrw, rpw);
-    if (rpw > (model == KGE_ROTATE ? 8 : 16)) return false;
-    const int gq = model == KGE_ROTATE ? LC_GQ_CPLX : LC_GQ_REAL;
-    const int ncol = C * nslab * nrw, ngr = ((N + 3) / 4 + gq - 1) / gq;
+    if (rpw > 8) return false;
+    const int ncol = C * nslab * nrw, ngr = ((N + 3) / 4 + LC_GQ_CPLX - 1) / LC_GQ_CPLX;
     const int total = 4096 / lc_wpb(model, d_e);                 // workgroups of the balanced launch: 16 wavefronts per CU
     if (ncol < 1 || ncol > total) return false;
     const int p = total / ncol, nA = total - ncol * p;
-    const int minpart = model == KGE_ROTATE ? 2 : 1;
-    if (nA == 0 || p + 1 > (model == KGE_ROTATE ? 8 : 4) || ngr / (p + 1) < minpart) return false;      // (nA == 0: the uniform split already fills the chip evenly)
+    if (nA == 0 || p + 1 > 8 || ngr / (p + 1) < 2) return false;      // (nA == 0: the uniform split already fills the chip evenly)
     P = p; nB = ncol - nA;
     return true;
-#else
-    (void)model; (void)C; (void)chunk; (void)N; (void)d_e;
-    return false;
-#endif
 }
 
 // split the negatives while the launch stays within ~4 workgroups per CU and a workgroup keeps >= 2 groups of quads
 int neg_bwd_lc_splits(int model, int C, int chunk, int N, int d_e) {
     { int P, nB; if (lc_balance(model, C, chunk, N, d_e, P, nB)) return P + 1; }
-#ifndef LC_SPLIT_REAL
-    if (model != KGE_ROTATE) return 1;
-#endif
     if (!neg_bwd_lc_supported(model, d_e) || N % 4 || d_e % 4) return 1;
     int nslab, nrw, rpw;
     lc_shape(model, C, chunk, d_e, nslab, nrw, rpw);

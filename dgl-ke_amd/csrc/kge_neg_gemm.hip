@@ -70,9 +70,7 @@ __device__ __forceinline__ float sq4(const float4 &v) { return v.x * v.x + v.y *
 // =============================================================================================
 // forward: one wavefront per 16x16 tile of S
 // =============================================================================================
-#ifndef FU
 #define FU 2    // k-steps (of 16) per register buffer (small on purpose: code size)
-#endif
 
 // `bid` / `nblk`: this workgroup's index and the number of workgroups doing forward-GEMM work (the body is also one half of
 // the horizontally fused "forward GEMM of step s + update of step s-1" launch of the --async_update pipeline)
@@ -117,11 +115,7 @@ __device__ __forceinline__ void neg_fwd_gemm_body(const GemmArgs &a, int ti, int
     // a load under a branch - even a wave-uniform scalar one - makes the compiler's s_waitcnt pass assume at the join that it
     // was NOT issued, so the wait before the MFMAs of the older buffer became vmcnt(0) and also waited for the buffer just
     // requested: the double buffering was there in the source and absent in the ISA (profiles/r02_waitcnt_fix.txt).
-#ifdef FWD_PROBE_NOLOOP            // tuning probe (wrong results): wavefront time without the main loop
-    const int kfull = 0;
-#else
     const int kfull = D >> 4;
-#endif
     // (the k-step index goes through an empty volatile asm: these loads have no other tie to program order - read-only
     //  kernel-argument pointers - and were otherwise hoisted above the MFMAs that still read the buffer they refill)
 #define FWD_LOAD(AV, RV, BV, KS0)                                                \
@@ -406,13 +400,9 @@ __device__ __forceinline__ void neg_fwd_gemm_ldsa_body(const GemmArgs &a, int ti
     // CUs set the end of the launch: tile wavefronts p90 7.0 us, max 8.2 us, profiles/r04_loss_fold.txt).  Same tiles, same
     // arithmetic; only where they run changes.
     int jg, sidx;
-#ifndef KGE_FWD_PLAIN_ORDER
     const int nfull = (tj & 3) ? tjg - 1 : tjg, nheavy = a.C * ti * nfull;
     if (bid < nheavy) { const int L = xcd_remap(bid, nheavy); jg = L % nfull; sidx = L / nfull; }
     else { sidx = xcd_remap(bid - nheavy, nblk - nheavy); jg = tjg - 1; }
-#else
-    { const int L = xcd_remap(bid, nblk); jg = L % tjg; sidx = L / tjg; }
-#endif
     const int it = sidx % ti, c = sidx / ti;
     const int jt = min(jg * 4 + wv, tj - 1);             // (a wavefront beyond the last column tile helps building A, then leaves)
     const bool tile_ok = jg * 4 + wv < tj;
@@ -633,9 +623,8 @@ __device__ __forceinline__ void neg_fwd_gemm_ldsa_body(const GemmArgs &a, int ti
 // (positive scores, |a|^2, |b|^2, dL/dp, P rows, the dense A the backward reads) are consumed one launch later, by the loss
 // kernel (distance transform) and the backward GEMM.  One launch boundary and the whole edge-forward kernel (4.2 + 1.7 us at
 // cfg-T, profiles/r02_v7_timeline.txt) leave the step's critical path.
-#ifndef KGE_FWD_NB
 #define KGE_FWD_NB 1               // direct-load instance: negative fragments per forward wavefront (tuning: 1, 2, 3; measured:
-#endif                             // wider is SLOWER - 9.3 / 11.7 / 14 us wave life, the time follows the loads per wavefront)
+                                   // wider is SLOWER - 9.3 / 11.7 / 14 us wave life, the time follows the loads per wavefront)
 // (round 5) ... + the phase-1 workgroups of the sampler tail building a batch of the NEXT group (kge_sampler_tail.hpp): the last
 // workgroups of the grid, behind the nbM workgroups of the step itself
 // Leading plain parameters (kernel-argument preload): what a tile wavefront needs for its id round - the
@@ -773,9 +762,7 @@ int launch_neg_fwd_gemm(const GemmArgs &a, hipStream_t s) {
 // feeding accumulator s (accumulator s = output columns d0 + 4*n + s -> float4 stores).
 // One "macro step" = 16 values of the reduction index = 4 MFMA k-steps = 16 MFMAs.
 // =============================================================================================
-#ifndef BU
 #define BU 1    // macro steps per register buffer (small on purpose: code size)
-#endif
 #define GB_MAXK 2048                   // rows of a chunk operand whose indices / statistics fit in LDS (32 KB)
 
 struct BwdStage { float w[4]; float4 r[4]; float pm; };
@@ -967,11 +954,7 @@ __device__ __forceinline__ void neg_bwd_gemm_tile(const GemmArgs &a, int ti, int
     // load is in bounds; garbage in clamped rows only reaches outputs that are never stored), row
     // addresses = kernel-argument base + LDS index (global loads, vmcnt only).  One predicated tail
     // step handles K % 16.
-#ifdef BWD_PROBE_NOLOOP            // tuning probe (wrong results): wavefront time without the main loop
-    const int msall = 0;
-#else
     const int msall = K >> 4;
-#endif
     // this wavefront's full macro steps [mlo, msfull): all of them (KS = 1), or the first / second half
     const int mlo = KS == 1 ? 0 : kh * (msall / KS);
     const int msfull = (KS == 1 || kh == KS - 1) ? msall : (kh + 1) * (msall / KS);
@@ -1076,15 +1059,11 @@ __device__ __forceinline__ void neg_bwd_gemm_tile(const GemmArgs &a, int ti, int
             erv[r] = ldg4(a.ew_rel + ewr[r] * D + dc);
         }
     }
-#ifdef KGE_TL_MARKS
     KGE_TL_MARK_K(3, 0);           // prologue done: ids, own rows, first operands and the tail operands have arrived
-#endif
     if (msfull > mlo) {
         if (isGA && vecW) BWD_PIPE(true) else BWD_PIPE(false)
     }
-#ifdef KGE_TL_MARKS
     KGE_TL_MARK_K(3, 1);           // main loop done
-#endif
 #undef BWD_LOAD
 #undef BWD_XFORM
 #undef BWD_MMA1
@@ -1108,9 +1087,7 @@ __device__ __forceinline__ void neg_bwd_gemm_tile(const GemmArgs &a, int ti, int
         }
     }
 
-#ifdef KGE_TL_MARKS
     KGE_TL_MARK_K(3, 2);           // tail macro step issued
-#endif
     if constexpr (KS > 1) {
         // hand-over: the later parts park accumulators + weight sum in LDS ([tile][value][lane]: conflict-free), the first adds
         __shared__ float kred[(KS - 1) * KGE_WAVES_PER_BLOCK * 17 * 64];
@@ -1269,10 +1246,8 @@ __device__ __forceinline__ void neg_bwd_gemm_body(const GemmArgs &a, int ti, int
 
 // measured (MI355X, us/step, GB_KS 1 -> 2): cfg-T 30.65 -> 31.49, DistMult 35.7 -> 35.7, ComplEx wikikg2 38.4 -> 38.4, SimplE 57.7 ->
 // 58.2 - the second wavefront per SIMD repeats the prologue (ids, own rows, first operands) and adds a barrier + LDS hand-over;
-// what bounds the launch is not the overlap inside the k-loop.  Kept as a compile-time option, off.
-#ifndef GB_KS
+// what bounds the launch is not the overlap inside the k-loop.  Kept as a compile-time constant, off.
 #define GB_KS 1                       // wavefronts per backward tile along the reduction (stand-alone launch)
-#endif
 // Leading plain parameters (kernel-argument preload): what a tile wavefront needs for its first requests -
 // the block-id split (toff = workgroups of the sampler tail in front, nbM, bpA, bpN), the shapes the tile counts follow from
 // (ti, tj, td are recomputed from them: three scalar instructions instead of three more argument dwords), the negative ids and

@@ -501,12 +501,8 @@ __global__ __launch_bounds__(KGE_BLOCK) void rescal_apply_vec_kernel(RescalUpdat
 // the row block from L2).
 // ---------------------------------------------------------------------------------------------
 #define RESCAL_RMAX ((1024 + RESCAL_RBN - 1) / RESCAL_RBN)     // rows of one block at the widest supported matrix
-#ifndef RESCAL_UNR
 #define RESCAL_UNR 2                 // rows in flight per wavefront in the backward + update pass
-#endif
-#ifndef RESCAL_EG
 #define RESCAL_EG 1                  // edges of a relation whose vectors are held in registers per pass (D <= 512)
-#endif
 
 __device__ __forceinline__ float4 ld4z(const float *p, bool ok) {
     return ok ? *reinterpret_cast<const float4 *>(p) : make_float4(0.f, 0.f, 0.f, 0.f);

@@ -18,7 +18,6 @@ using namespace kge;
 KGE_TL_DEFINE(rowwise)
 
 #define WAVE_ID() ((int64_t)blockIdx.x * KGE_WAVES_PER_BLOCK + (threadIdx.x >> 6))
-#define LANE() (threadIdx.x & 63)
 
 static inline int blocks_for_waves(int64_t waves) {
     return (int)((waves + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK);
@@ -620,15 +619,11 @@ __global__ __launch_bounds__(KGE_BLOCK) void loss_kernel_reg(const float *neg, c
             nv[u] = (j < N && j != jd) ? a.gamma - sqrtf(fmaxf(fmaf(-2.f, nv[u], asq_i + bq[u]), 1e-30f)) : 0.f;
         }
     }
-#ifdef KGE_TL_MARKS
     KGE_TL_MARK(0);              // score row, positive score, weight have arrived
-#endif
     // (the row's share of the running total: when the positive share comes from edge_fwd, B slots further on than edge_fwd's add -
     //  the same two adds as the strict step's in-launch loss rows, whose other half runs in the SAME launch)
     loss_row_regs<NPER>(a, i, nv, w, p, lane, (int)((a.skip_pos ? i + a.B : i) & (KGE_ACC_SLOTS - 1)));
-#ifdef KGE_TL_MARKS
     KGE_TL_MARK(1);              // softmax, criterion, reductions done; gradient stores acknowledged
-#endif
 }
 
 int launch_loss(const LossArgs &a, hipStream_t s) {
@@ -907,13 +902,11 @@ int launch_update(const UpdateArgs &a, hipStream_t s, const SmpTail *tail) {
     // (4: the generic instance - gradient-emitting step, neg_deg_sample - with the norm fixed at 3 as well)
     int lean = !reg3 ? 0 : ((!inplace || a.nd_chunk) ? 4 : (a.transe_fast ? (a.Q ? 3 : 1) : 2));
     const int nit = dmax <= 256 ? 1 : (dmax <= 512 ? 2 : 4);
-#ifndef UPD_NO_EMIT6
     if (lean == 4 && a.emit_ent && a.emit_rel && a.g0 && (a.g1 || a.msg_rows) && a.gr && !a.transe_fast && !a.nd_chunk && !a.Hs && !a.Ts && !a.Rs && !a.Ns && !a.dry)
         lean = 6;                    // the all-to-all engine's step for the models with per-edge gradient rows
     else if (lean == 4 && a.emit_ent && !a.emit_rel && a.g0 && (a.g1 || a.msg_rows) && !a.gr && !a.gsr && !a.rid && !a.transe_fast && !a.nd_chunk && !a.Hs &&
              !a.Ts && !a.Rs && !a.Ns && !a.dry)
         lean = 7;                    // ... under relation partitioning: entity messages out, the relation trace applied in place
-#endif
     if (a.gn_parts > 0) {            // unsummed GN partials / GA parts (see UpdateArgs): the folded instance or nothing
         if (lean != 1 || sharded || !(vec && dmax <= 512) || !a.GNp || a.gn_parts > KGE_GN_MAXP || a.ga_parts < 1 || a.ga_parts > KGE_GA_MAXP ||
             a.Hs || a.Rs || a.Ns)

@@ -265,22 +265,9 @@ __global__ __launch_bounds__(SP_THREADS) void sample_plan_kernel(SamplerArgs a) 
         neg_ids[j] = id;
         ek[2 * B + j] = ((K)id << CBITS) | (K)(2 * B + j);
     }
-#ifdef SP_BITONIC
-    int n2 = 1;
-    while (n2 < NE) n2 <<= 1;
-    for (int i = NE + t; i < n2; i += SP_THREADS) ek[i] = ~(K)0;
-    __syncthreads();
-#ifdef KGE_TL_MARKS
-    KGE_TL_MARK(0);              // ids sampled, keys in LDS
-#endif
-    // ---- 2. sort by (entity, code) ----
-    bitonic_sort<K>(ek, n2);
-#else
     for (int i = NE + t; i < MAXE; i += SP_THREADS) ek[i] = ~(K)0;
     __syncthreads();
-#ifdef KGE_TL_MARKS
     KGE_TL_MARK(0);              // ids sampled, keys in LDS
-#endif
     // ---- 2. sort by (entity, code): the codes ARE the positions, so a STABLE sort by the id bits alone gives that order -
     // a block radix sort (rocPRIM: 8 bits per pass, ranks by wavefront matching) over the bits of n_ent - 1: 2 passes for
     // FB15k's 14 951 entities, 4 for Freebase's 86 M, instead of the 78 compare-exchange stages of the bitonic network
@@ -296,10 +283,7 @@ __global__ __launch_bounds__(SP_THREADS) void sample_plan_kernel(SamplerArgs a) 
         for (int e = 0; e < EPT; ++e) ek[(EPT) * t + e] = item[e];
         __syncthreads();
     }
-#endif
-#ifdef KGE_TL_MARKS
     KGE_TL_MARK(1);              // sorted
-#endif
     // ---- 3. packed flags: bit fields {unique: 0..15, positive: 16..31}; negative rank = k - positive rank ----
     for (int k = t; k < NE; k += SP_THREADS) {
         const uint64_t id = ek[k] >> CBITS, code = ek[k] & ((1u << CBITS) - 1);
@@ -321,9 +305,7 @@ __global__ __launch_bounds__(SP_THREADS) void sample_plan_kernel(SamplerArgs a) 
     if (t == 0) { ue_pos_ptr[UE] = 2 * B; ue_neg_ptr[UE] = CN; counts[0] = UE; }
     __syncthreads();
     __threadfence_block();
-#ifdef KGE_TL_MARKS
     KGE_TL_MARK(2);              // lists written
-#endif
     for (int u = t; u < UE; u += SP_THREADS) {
         const int64_t id = ue_id[u];
         const int p0 = ue_pos_ptr[u], p1 = ue_pos_ptr[u + 1], n0 = ue_neg_ptr[u], n1 = ue_neg_ptr[u + 1];

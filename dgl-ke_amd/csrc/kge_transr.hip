@@ -595,12 +595,7 @@ int launch_transr_bwd(const TransRArgs &a, hipStream_t s) {
         const int nJW = (a.N + TW_R - 1) / TW_R, nEW = (a.De + TW_R - 1) / TW_R, ipgw = (a.chunk + a.nG - 1) / a.nG;
         hipLaunchKernelGGL(transr_gn_wide_kernel, dim3(a.C * nJW * a.nG), b, (size_t)ipgw * (sizeof(int64_t) + TW_R * sizeof(float)), s, a, nJW);
         hipLaunchKernelGGL(transr_gn_reduce_kernel, dim3(((int64_t)a.C * a.N + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK), b, 0, s, a);
-        #ifndef TW_GP_PER_EDGE
-        const int gp_blocks = a.B * nEW;
-#else
-        const int gp_blocks = a.B;
-#endif
-        hipLaunchKernelGGL(transr_gp_wide_kernel, dim3(gp_blocks), b, (size_t)a.N * (sizeof(int64_t) + sizeof(float)) + TW_C * sizeof(float), s, a, nEW);
+        hipLaunchKernelGGL(transr_gp_wide_kernel, dim3(a.B * nEW), b, (size_t)a.N * (sizeof(int64_t) + sizeof(float)) + TW_C * sizeof(float), s, a, nEW);
         return check_launch_t();
     }
     hipLaunchKernelGGL(transr_dq_kernel, dim3(a.B), b, 0, s, a);

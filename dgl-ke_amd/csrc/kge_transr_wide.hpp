@@ -9,9 +9,7 @@
 // of a wavefront's ds_read_b32 (rows q, q + 1, ..) alternate bank halves.
 #pragma once
 
-#ifndef TW_R
 #define TW_R 64                     // rows of a workgroup tile: one 16-row block per wavefront (128: two - measured slower, 2 workgroups per CU)
-#endif
 #define TW_WR (TW_R / 4)             // rows of a wavefront
 #define TW_NRB (TW_WR / 16)
 #define TW_AUNITS (TW_R * TR_K / 4 / KGE_BLOCK)   // float4 units of one A slab per thread
@@ -260,13 +258,9 @@ __global__ __launch_bounds__(KGE_BLOCK) void transr_gp_wide_kernel(TransRArgs a,
     __shared__ float As[2][TR_K][TW_LDA], Bs[2][TR_K][TW_LDB];
     __shared__ float red[KGE_WAVES_PER_BLOCK];
     extern __shared__ char gpw_dyn[];            // per negative of the chunk: its row's offset in the entity table, -W_ij; then dq_i [208]
-#ifndef TW_GP_PER_EDGE
+    // one workgroup per (positive, row tile).  (Measured: one workgroup per positive walking its row tiles - ids / weights staged once,
+    //  dq from the first sweep only - needs 180 VGPRs, 2 wavefronts per SIMD: 334 us against 303 with a workgroup per tile)
     const int eb_first = blockIdx.x % nEB, eb_last = eb_first + 1, i = blockIdx.x / nEB;
-#else
-    // (measured: one workgroup per positive walking its row tiles - ids / weights staged once, dq from the first sweep only - needs
-    //  180 VGPRs, 2 wavefronts per SIMD: 334 us against 303 with a workgroup per tile)
-    const int eb_first = 0, eb_last = nEB, i = blockIdx.x;
-#endif
     const int De = a.De, Dr = a.Dr, N = a.N;
     const int c = i / a.chunk;
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63, m = lane & 15, q = lane >> 4;

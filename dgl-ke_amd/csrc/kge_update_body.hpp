@@ -6,9 +6,7 @@
 #include "kge_common.hpp"
 
 #define KGE_ST_ROW kge::st_wt      // updated table rows: read next by another kernel on any XCD - write-through store
-#ifndef LANE
 #define LANE() (threadIdx.x & 63)
-#endif
 // running-sum slot update: a fire-and-forget hardware float atomic (global_atomic_add_f32, no return value).
 // A plain read-modify-write costs a dependent global load - one more ~1.5 us round trip at the end of every
 // wavefront's chain (update kernel 15.7 -> see profiles/r01_microbench_mi355x.txt).  The result is still
@@ -370,9 +368,6 @@ __device__ __forceinline__ void update_reg_body(const UpdateArgs &a_in, int nb_e
     const int nb_rel = nblk - nb_ent;
     const int bx = bid < nb_rel ? bid + nb_ent : bid - nb_rel;
     if (bx < nb_ent) {
-#ifdef UPD_PROBE_NOENT
-        return;
-#endif
         // (the wavefront number through readfirstlane: the compiler then knows that the record / count addresses are wave-uniform
         //  and fetches them with scalar loads)
         const int64_t u = (int64_t)bx * KGE_WAVES_PER_BLOCK + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -386,13 +381,7 @@ __device__ __forceinline__ void update_reg_body(const UpdateArgs &a_in, int nb_e
         asm volatile("" : "+v"(r0.x));         // (keeps the record loads above the early exit)
         if (u >= cnt_e) return;
         const int64_t id = (int64_t)(uint32_t)r0.x | ((int64_t)r0.y << 32);
-#if defined(UPD_PROBE_NOGRAD)      // tuning probe: table read-modify-write only (no gradient rows)
-        const int p0 = 0, p1 = 0, n0 = 0, n1 = 0, adj0 = 0, slot0 = 0; (void)r1;
-#elif defined(UPD_PROBE_NONEG)     // tuning probe: no negative-gradient rows
-        const int p0 = r0.z, p1 = r0.w, n0 = 0, n1 = 0, adj0 = r1.z, slot0 = 0;
-#else
         const int p0 = r0.z, p1 = r0.w, n0 = r1.x, n1 = r1.y, adj0 = r1.z, slot0 = r1.w;
-#endif
         float *row = shard_row(a.em, a.ent, id, d);
         float *srow = shard_state(a.em, a.ent_state, id);
         const bool has_pos = p1 > p0, has_neg = n1 > n0;
@@ -668,11 +657,7 @@ __device__ __forceinline__ void update_reg_body(const UpdateArgs &a_in, int nb_e
             if (a.gs1) a.gs1[mu * (int64_t)a.ld_gs_e] = has_neg ? s1 : 0.f;
             }
         }
-#ifdef UPD_PROBE_NOACC
-        if (false) {
-#else
         if (reg && (a.reg_ent || a.acc)) {
-#endif
             rv = wave_sum(rv);
             const float val = a.reg_coef * rv * (float)((has_pos ? 1 : 0) + (n1 - n0));
             if (lane == 0) {
@@ -681,9 +666,6 @@ __device__ __forceinline__ void update_reg_body(const UpdateArgs &a_in, int nb_e
             }
         } else if (a.reg_ent && lane == 0) a.reg_ent[u] = 0.f;
     } else {
-#ifdef UPD_PROBE_NOREL
-        return;
-#endif
         // two instances of the relation part: long relation lists are shared by the four wavefronts of a workgroup (barriers, LDS);
         // device-built plans carry the length of the batch's longest relation list in counts[3], and a batch without a long one
         // (kernel-uniform) runs the plain instance - the shared-list code costs 0.25 us per step on uniform ids just by being

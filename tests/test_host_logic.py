@@ -192,6 +192,37 @@ def test_inline_assembly_wide_stores_carry_their_wait_states():
     assert n >= 1
 
 
+def test_kernel_sources_have_one_build_configuration():
+    """the kernel sources compile one way: the only macros a preprocessor conditional may test are the developer timeline's
+    (kge_common.hpp).  A tuning probe or an A/B alternative lives in a working copy and a variant library (tools/build_variant.sh),
+    not behind a -D in the shipped kernels."""
+    src_dir = os.path.join(ROOT, "dgl-ke_amd", "csrc")
+    tested, files = set(), [f for f in sorted(os.listdir(src_dir)) if f.endswith((".hip", ".hpp"))]
+    assert files
+    for f in files:
+        text = open(os.path.join(src_dir, f)).read().replace("\\\n", " ")
+        for m in re.finditer(r"^[ \t]*#[ \t]*(if|ifdef|ifndef|elif)\b(.*)$", text, re.M):
+            cond = re.sub(r"//.*|/\*.*?\*/", "", m.group(2))
+            names = set(re.findall(r"[A-Za-z_]\w*", cond)) - {"defined"}
+            assert names or m.group(1) in ("if", "elif"), "%s: %s" % (f, m.group(0))
+            tested |= {(n, f) for n in names}
+    extra = sorted((n, f) for n, f in tested if n not in ("KGE_TIMELINE", "KGE_TL_MARKS"))
+    assert not extra, "conditional compilation on %s" % extra
+    assert {n for n, _ in tested} == {"KGE_TIMELINE", "KGE_TL_MARKS"}      # (the scan does see conditionals)
+
+
+def test_makefile_and_build_compile_the_same_sources():
+    """csrc/Makefile's SRCS (which tools/build_variant*.sh follow) and __graft_entry__.SOURCES (which build() follows) name the
+    same files, and every one of them exists: a variant library exports what dglke_amd/_lib.py binds"""
+    import __graft_entry__
+    src_dir = os.path.join(ROOT, "dgl-ke_amd", "csrc")
+    lines = [m.group(1) for m in re.finditer(r"^SRCS[ \t]*=[ \t]*(.*)$", open(os.path.join(src_dir, "Makefile")).read(), re.M)]
+    assert len(lines) == 1, lines
+    srcs = lines[0].split()
+    assert len(set(srcs)) == len(srcs) and set(srcs) == set(__graft_entry__.SOURCES)
+    assert all(os.path.isfile(os.path.join(src_dir, s)) for s in srcs)
+
+
 def _lc_balanced_map(ncol, ngr, P, nB):
     """Python statement of the block -> (column, part, groups) map of the shared-pair backward's balanced split
     (dgl-ke_amd/csrc/kge_neg_bcast.hip, neg_bwd_lc_kernel, NegArgs::lc_P): 1024 block ids, rounds of 256, odd rounds reversed,
