@@ -174,6 +174,56 @@ def test_workspace_accounts_for_the_gradient_parts_of_the_shared_pair_backward()
                ws(model, d_e, d_e if model != "ComplEx" else d_e, 1000, 5, 200, 200, _lib.FLAG_TWO_PASS_PAIR)
 
 
+# (B, C, chunk, N, n_cand) -> model -> (d_e, d_r, kge_step_workspace_bytes at flags 0 / 1 / 16 / 32, kge_step_async_workspace_bytes at
+# the same flags, kge_score_neg_workspace_bytes, kge_rank_workspace_bytes(B, n_cand, d_e)), with UE = 2 B + C N and UR = B.  The
+# values are those of the library before each workspace got its single carve function (kge_api.hip carve_step / carve_neg /
+# carve_rank): what callers allocate must not move.  Second shape: the FB15k recipes (bench.py WORKLOADS widths for RESCAL / TransR).
+_WORKSPACE_BYTES = {
+    (64, 4, 16, 16, 500): {
+        "TransE_l1": (64, 64, (138496, 138496, 138496, 192768), (375296, 375296, 375296, 483840), 53760, 1211904),
+        "TransE_l2": (64, 64, (122112, 122112, 122112, 160000), (342528, 342528, 342528, 418304), 37376, 1211904),
+        "DistMult": (64, 64, (122112, 122112, 122112, 160000), (342528, 342528, 342528, 418304), 37376, 1211904),
+        "ComplEx": (64, 64, (122112, 122112, 122112, 160000), (342528, 342528, 342528, 418304), 37376, 1211904),
+        "RotatE": (64, 32, (130304, 130304, 130304, 184576), (342528, 342528, 342528, 451072), 53760, 1211904),
+        "SimplE": (64, 64, (122112, 122112, 122112, 160000), (342528, 342528, 342528, 418304), 37376, 1211904),
+        "RESCAL": (16, 256, (191488, 191488, 191488, 209408), (530432, 530432, 530432, 566272), 12800, 1187328),
+        "TransR": (16, 24, (477184, 477184, 477184, 782848), (983040, 983040, 983040, 1594368), 12800, 1187328),
+    },
+    (1000, 5, 200, 200, 14951): {
+        "TransE_l1": (400, 400, (23397376, 23397376, 20197376, 35545088), (56394752, 56394752, 49994752, 80690176), 12008192, 79456256),
+        "TransE_l2": (400, 400, (12197376, 12197376, 12197376, 16345088), (33994752, 33994752, 33994752, 42290176), 4008192, 79456256),
+        "DistMult": (400, 400, (12197376, 12197376, 12197376, 16345088), (33994752, 33994752, 33994752, 42290176), 4008192, 79456256),
+        "ComplEx": (400, 400, (12197376, 12197376, 12197376, 16345088), (33994752, 33994752, 33994752, 42290176), 4008192, 79456256),
+        "RotatE": (400, 200, (28997376, 28997376, 22597376, 44345088), (65994752, 65994752, 53194752, 96690176), 15208192, 79456256),
+        "SimplE": (400, 400, (12197376, 12197376, 12197376, 16345088), (33994752, 33994752, 33994752, 42290176), 4008192, 79456256),
+        "RESCAL": (500, 250000, (85186560, 85186560, 85186560, 92141824), (2178373632, 2178373632, 2178373632, 2192284160), 4808448, 80256512),
+        "TransR": (200, 200, (265901824, 265901824, 265901824, 360473600), (536603648, 536603648, 536603648, 725747200), 2408192, 77856256),
+    },
+}
+
+
+def test_workspace_sizes_are_the_recorded_ones():
+    """the four *_workspace_bytes functions (host arithmetic only, no step call) over the eight models, flags {0, FORCE_PAIRWISE,
+    TWO_PASS_PAIR, NEG_DEG_SAMPLE} and two shapes return the recorded byte counts exactly"""
+    import ctypes as C
+    from dglke_amd import _lib
+    L = _lib.lib()
+    flags = (0, _lib.FLAG_FORCE_PAIRWISE, _lib.FLAG_TWO_PASS_PAIR, _lib.FLAG_NEG_DEG_SAMPLE)
+    assert flags == (0, 1, 16, 32)
+    for (B, Cn, chunk, N, n_cand), models in _WORKSPACE_BYTES.items():
+        assert len(models) == 8
+        for model, (d_e, d_r, step, asy, score_neg, rank) in models.items():
+            for k, fl in enumerate(flags):
+                hp = _lib.KgeHParams()
+                hp.model, hp.d_e, hp.d_r, hp.flags = _lib.model_id(model), d_e, d_r, fl
+                hp.gamma, hp.lr, hp.adv_temp, hp.reg_norm = 12.0, 0.1, 1.0, 3
+                args = (C.byref(hp), B, Cn, chunk, N, 2 * B + Cn * N, B)
+                assert L.kge_step_workspace_bytes(*args) == step[k], (model, B, fl)
+                assert L.kge_step_async_workspace_bytes(*args) == asy[k], (model, B, fl)
+            assert L.kge_score_neg_workspace_bytes(_lib.model_id(model), Cn, chunk, N, d_e) == score_neg, (model, B)
+            assert L.kge_rank_workspace_bytes(B, n_cand, d_e) == rank, (model, B)
+
+
 def test_inline_assembly_wide_stores_carry_their_wait_states():
     """a 128-bit global store written as inline assembly must be followed by two wait states before its data registers may be
     overwritten (gfx940+ VMEM store-data hazard) - the compiler does not see inside the asm statement, so the statement itself
