@@ -1296,6 +1296,140 @@ int kge_rank_eval_split(int model, int neg_head, const float *qent, int64_t n_qe
                           Eb, ranks, pos_score_out, ws, ws_bytes, flags, s);
 }
 
+// ---- chunked-candidate ranking (kge_rank_chunk.hip) ----
+// one block of whole chunks: pos-side vectors / norms / positive scores of its rows, the candidates' norms (TransE_l2), and - for the
+// score-block route only, but the layout does not depend on the flags - the id list and the score block
+struct ChunkBufs { float *A, *asq, *P, *RV, *THP, *TTP, *TQ, *TSG, *bsq_own, *bsq_c, *S; int64_t *ids; };
+static size_t carve_chunked(Carver &cv, ChunkBufs &w, int model, int64_t rows, int chunk, int64_t n_cand, int self_cand, int d_e, int d_r) {
+    const size_t nch = (size_t)((rows + chunk - 1) / chunk), R = nch * (size_t)chunk;
+    const size_t ncols = (size_t)n_cand + (self_cand ? (size_t)chunk : 0);
+    w.A = cv.f(R * d_e); w.asq = cv.f(R); w.P = cv.f(R);
+    w.RV = cv.f(model == KGE_RESCAL ? R * d_e : 0);                    // V = M t (RESCAL)
+    const size_t tr = model == KGE_TRANSR ? R * (size_t)d_r : 0;       // TransR: hp, tp, q, sign rows
+    w.THP = cv.f(tr); w.TTP = cv.f(tr); w.TQ = cv.f(tr); w.TSG = cv.f(tr);
+    w.bsq_own = cv.f(R); w.bsq_c = cv.f(nch * (size_t)n_cand);
+    w.ids = cv.i64(nch * ncols);
+    w.S = cv.f(R * ncols);
+    return cv.off;
+}
+
+size_t kge_rank_chunked_workspace_bytes(int model, int rows, int chunk, int64_t n_cand, int self_cand, int d_e, int d_r) {
+    if (rows <= 0 || chunk <= 0 || n_cand < 0 || d_e <= 0 || d_r <= 0) return 0;
+    Carver cv; ChunkBufs w; return carve_chunked(cv, w, model, rows, chunk, n_cand, self_cand, d_e, d_r);
+}
+
+int kge_rank_eval_chunked(int model, int neg_head, const float *ent, int64_t n_ent, const float *rel, int64_t n_rel,
+                          const float *proj, const int64_t *h, const int64_t *r, const int64_t *t, int64_t E,
+                          int d_e, int d_r, float gamma, float emb_init, int chunk,
+                          const int64_t *cand, int64_t n_cand, int64_t cand_stride, int self_cand,
+                          const int64_t *filt_ptr, const int64_t *filt_ids, int32_t *ranks, float *pos_score_out,
+                          void *ws, size_t ws_bytes, unsigned flags, void *stream) {
+    if (int rc = check_model(model, d_e, d_r)) return rc;
+    if (chunk <= 0) return fail(KGE_ERR_ARG, "kge_rank_eval_chunked: chunk must be positive (got %d)", chunk);
+    if (self_cand && filt_ptr)
+        return fail(KGE_ERR_ARG, "kge_rank_eval_chunked: self_cand and a filter exclude each other "
+                                 "(if negative sampling based on degree, we can't filter positive edges)");
+    if ((filt_ptr == nullptr) != (filt_ids == nullptr))
+        return fail(KGE_ERR_ARG, "kge_rank_eval_chunked: filt_ptr and filt_ids must be given together");
+    if (model == KGE_TRANSR && !proj) return fail(KGE_ERR_ARG, "kge_rank_eval_chunked: TransR needs the projection table");
+    if (!ent || !rel || n_ent <= 0 || n_rel <= 0 || E < 0 || (E && (!h || !r || !t || !ranks)) || !ws)
+        return fail(KGE_ERR_ARG, "kge_rank_eval_chunked: bad argument");
+    const int64_t NC = cand ? n_cand : n_ent;
+    if (NC <= 0 || cand_stride < 0 || (int64_t)chunk * (NC + (self_cand ? chunk : 0)) > 0x7fffffff)
+        return fail(KGE_ERR_ARG, "kge_rank_eval_chunked: bad candidate count %lld / stride %lld", (long long)NC, (long long)cand_stride);
+    if (E == 0) return KGE_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nch_all = (E + chunk - 1) / chunk;
+    const int64_t ncols_full = NC + (self_cand ? chunk : 0);
+    // the largest block of whole chunks that fits the workspace (and the 32-bit element counts of the training kernels)
+    auto need_of = [&](int64_t nch) { Carver cv; ChunkBufs w; return carve_chunked(cv, w, model, nch * chunk, chunk, NC, self_cand, d_e, d_r); };
+    if (need_of(1) > ws_bytes)
+        return fail(KGE_ERR_WORKSPACE, "kge_rank_eval_chunked: workspace too small for one chunk (%zu < %zu)", ws_bytes, need_of(1));
+    int64_t lo = 1, hi = std::min(nch_all, std::max<int64_t>(1, (int64_t)(1 << 30) / ((int64_t)chunk * ncols_full)));
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) / 2;
+        if (need_of(mid) <= ws_bytes) lo = mid; else hi = mid - 1;
+    }
+    const int64_t nchb = lo;
+    Carver cv(ws, ws_bytes); ChunkBufs w;
+    carve_chunked(cv, w, model, nchb * chunk, chunk, NC, self_cand, d_e, d_r);
+    const bool gemm = model != KGE_TRANSR && use_mfma(model, d_e, (int)NC, flags) && rank_gemm_supported(model, d_e);
+    const bool l2g = gemm && model == KGE_TRANSE_L2;
+    const bool shared = !cand || cand_stride == 0;
+    const float rot_div = rot_div_of(emb_init);
+    ChunkCands cc{};
+    cc.cand = cand; cc.n_cand = NC; cc.stride = cand_stride; cc.own = self_cand ? (neg_head ? h : t) : nullptr;
+    cc.n_ent = n_ent; cc.E = E; cc.chunk = chunk;
+    if (l2g && shared) {             // |b|^2 of the one list, once
+        ChunkCands c1 = cc; c1.own = nullptr;
+        KGE_TRY(launch_chunk_bsq(c1, 0, 0, NC, ent, d_e, w.bsq_own, w.bsq_c, s));
+    }
+    for (int64_t c0 = 0; c0 < nch_all; c0 += nchb) {
+        const int nch = (int)std::min(nchb, nch_all - c0);
+        const int64_t e0 = c0 * chunk;
+        const int rows = (int)std::min<int64_t>((int64_t)nch * chunk, E - e0);
+        float *P = pos_score_out ? pos_score_out + e0 : w.P;
+        // positive scores and pos-side vectors of every row of the block
+        EdgeFwdArgs ef;
+        fill_edge(ef, EdgeSrc{ent, h + e0, ent, t + e0, rel, r + e0}, model, rows, d_e, d_r, neg_head, gamma, rot_div);
+        ef.pos_score = P; ef.A = w.A; ef.asq = l2g ? w.asq : nullptr;
+        if (model == KGE_TRANSR) {
+            RescalMatvecArgs m{};
+            m.B = rows; m.D = d_e; m.Dc = d_r; m.rel = proj; m.ridx = r + e0;
+            m.z1 = ent; m.z1idx = h + e0; m.c1 = w.THP; m.z2 = ent; m.z2idx = t + e0; m.c2 = w.TTP;
+            KGE_TRY(launch_rescal_matvec(m, s));
+        } else if (model == KGE_RESCAL) {
+            RescalMatvecArgs m{};
+            m.B = rows; m.D = d_e; m.rel = rel; m.ridx = r + e0;
+            m.y1 = ent; m.y1idx = t + e0; m.r1 = neg_head ? w.A : w.RV;
+            if (!neg_head) { m.y2 = ent; m.y2idx = h + e0; m.r2 = w.A; }
+            m.pd = ent; m.pdidx = h + e0; m.p = P;
+            KGE_TRY(launch_rescal_matvec(m, s));
+        } else {
+            KGE_TRY(launch_edge_fwd(ef, s));
+        }
+        if (gemm) {
+            if (l2g && (!shared || self_cand)) {
+                ChunkCands c1 = cc; if (shared) c1.cand = nullptr;
+                KGE_TRY(launch_chunk_bsq(c1, c0, rows, shared ? 0 : (int64_t)nch * NC, ent, d_e, w.bsq_own, w.bsq_c, s));
+            }
+            if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ranks + e0), 1, (size_t)rows, s) != hipSuccess)
+                return fail(KGE_ERR_LAUNCH, "kge_rank_eval_chunked: memset failed");
+            KGE_TRY(launch_rank_chunk_gemm(model, cc, c0, nch, w.A, w.asq, P, ent, d_e, gamma, clamp_of(model), w.bsq_own, w.bsq_c,
+                                           shared ? 1 : 0, filt_ptr, filt_ids, ranks, s));
+            continue;
+        }
+        // score-block route: the whole chunks of the block in one call of the training kernels, a short last chunk in its own
+        const int nfull = rows / chunk, rem = rows % chunk;
+        for (int gidx = 0; gidx < 2; ++gidx) {
+            const int C = gidx == 0 ? nfull : (rem ? 1 : 0), m = gidx == 0 ? chunk : rem;
+            if (C == 0) continue;
+            const int64_t row_off = gidx == 0 ? 0 : (int64_t)nfull * chunk;
+            const int64_t cfirst = c0 + (gidx == 0 ? 0 : nfull);
+            const int64_t ncols = NC + (self_cand ? m : 0);
+            int64_t *ids = w.ids + (gidx == 0 ? 0 : (int64_t)nfull * ncols_full);
+            float *S = w.S + row_off * ncols_full;
+            KGE_TRY(launch_chunk_ids(cc, cfirst, C, m, ncols, ids, s));
+            if (model == KGE_TRANSR) {
+                TransRArgs tr{};
+                tr.B = C * m; tr.C = C; tr.chunk = m; tr.N = (int)ncols; tr.De = d_e; tr.Dr = d_r; tr.neg_head = neg_head;
+                tr.gamma = gamma; tr.ent = ent; tr.cent = ent; tr.h_gid = h + e0 + row_off; tr.t_gid = t + e0 + row_off;
+                tr.neg_ids = ids; tr.rel_ids = r + e0 + row_off; tr.rel = rel; tr.proj = const_cast<float *>(proj);
+                tr.HP = w.THP + row_off * d_r; tr.TP = w.TTP + row_off * d_r; tr.Q = w.TQ + row_off * d_r; tr.SG = w.TSG + row_off * d_r;
+                tr.P = P + row_off; tr.S = S; tr.Z = nullptr;
+                KGE_TRY(launch_transr_pos(tr, s));
+                KGE_TRY(launch_transr_fwd(tr, s));
+            } else {
+                NegArgs na; fill_pair(na, model, C, m, (int)ncols, d_e, gamma, w.A + row_off * d_e, ent, ids);
+                na.S = S;
+                KGE_TRY(launch_neg_fwd_pair(na, s));
+            }
+            KGE_TRY(launch_chunk_count(cc, cfirst, C, m, ncols, S, P + row_off, filt_ptr, filt_ids, ranks, s));
+        }
+    }
+    return KGE_OK;
+}
+
 int kge_step_sharded(const kge_hparams *hp, const kge_shards *sh, const kge_batch *b,
                      const kge_step_out *out, void *ws, size_t ws_bytes, void *stream) {
     if (!sh) return fail(KGE_ERR_ARG, "kge_step_sharded: null shard map");

@@ -508,6 +508,20 @@ size_t rank_gemm_mask_bytes(int rows, int64_t N);
 int launch_rank_gemm(int model, const float *A, int rows, const float *nbase, const int64_t *nidx, int64_t N, int D, float gamma,
                      float clampv, const float *asq, const float *bsq, const float *P, void *mask, const int64_t *filt_ptr,
                      const int64_t *filt_ids, int64_t e0, int32_t *ranks, hipStream_t s);
+// ---- chunked-candidate ranking (kge_rank_chunk.hip) ----
+struct ChunkCands {                 // the candidate columns of chunk c = triples [c * chunk, min(E, (c + 1) * chunk))
+    const int64_t *cand; int64_t n_cand, stride;   // list of chunk c: cand + c * stride (stride 0: one shared list); null: entity j, n_cand = n_ent
+    const int64_t *own;              // self_cand: the triples' corrupted-side ids (h or t), prepended per chunk; else null
+    int64_t n_ent, E; int chunk;
+};
+int launch_chunk_bsq(const ChunkCands &cc, int64_t c0, int rows, int64_t n_list, const float *ent, int D, float *bsq_own, float *bsq_c,
+                     hipStream_t s);
+int launch_rank_chunk_gemm(int model, const ChunkCands &cc, int64_t c0, int nch, const float *A, const float *asq, const float *P,
+                           const float *ent, int D, float gamma, float clampv, const float *bsq_own, const float *bsq_c, int shared,
+                           const int64_t *filt_ptr, const int64_t *filt_ids, int32_t *ranks, hipStream_t s);
+int launch_chunk_ids(const ChunkCands &cc, int64_t cfirst, int nch, int m, int64_t ncols, int64_t *ids, hipStream_t s);
+int launch_chunk_count(const ChunkCands &cc, int64_t cfirst, int nch, int m, int64_t ncols, const float *S, const float *P,
+                       const int64_t *filt_ptr, const int64_t *filt_ids, int32_t *ranks, hipStream_t s);
 struct GemmArgs {                   // LDS-staged fp32-MFMA negative scoring (kge_neg_gemm.hip)
     int model, C, chunk, N, D;
     float gamma;

@@ -122,6 +122,69 @@ class Ranker(object):
             raise _lib.KgeError("TransR ranking needs the projection table (proj=...)")
         self._ws = None
         self._all = None
+        self._cws = None                   # workspace of chunked_ranks
+        self.chunk_ws_budget = 512 << 20   # bytes: chunked_ranks asks for at most this (never less than one chunk needs)
+
+    def chunked_ranks(self, h, r, t, neg_head, chunk, cand=None, filt=None, self_cand=False, want_pos_score=False):
+        """int32 [E] ranks, the triples taken in chunks of `chunk` and every chunk ranked against its own candidates
+        (kge_rank_eval_chunked, one call).  cand: None (all entities), [n] (one list for all chunks) or [n_chunks, n] entity ids,
+        -1 = empty slot; filt: the (ranges, entity ids) pair of build_filter_device / build_filter - ids, not columns;
+        self_cand: prepend every chunk's own corrupted-side entities, the triple's own column scoring 0 (--neg_deg_sample_eval)."""
+        dev = self.ent.device
+
+        def put(x, dt=torch.int64):
+            if x is None:
+                return None
+            if isinstance(x, torch.Tensor):
+                return x.to(dev, dt).contiguous()
+            return torch.as_tensor(np.ascontiguousarray(x)).to(dev, dt)
+        h, r, t, cand = put(h), put(r), put(t), put(cand)
+        E, chunk = int(h.shape[0]), int(chunk)
+        n_ent = int(self.ent.shape[0])
+        if chunk <= 0:
+            raise _lib.KgeError("chunked_ranks: chunk must be positive")
+        if self_cand and filt is not None:
+            raise _lib.KgeError("if negative sampling based on degree, we can't filter positive edges.")
+        n_chunks = (E + chunk - 1) // chunk
+        stride = 0
+        if cand is not None:
+            if cand.dim() == 2:
+                if cand.shape[0] != n_chunks:
+                    raise _lib.KgeError("chunked_ranks: %d candidate lists for %d chunks" % (cand.shape[0], n_chunks))
+                stride = int(cand.shape[1])
+            elif cand.dim() != 1:
+                raise _lib.KgeError("chunked_ranks: cand must be [n] or [n_chunks, n]")
+            if cand.numel() == 0:
+                raise _lib.KgeError("chunked_ranks: empty candidate list")
+            if int(cand.max()) >= n_ent:
+                raise _lib.KgeError("chunked_ranks: candidate id %d outside the %d entities" % (int(cand.max()), n_ent))
+        n_cand = int(cand.shape[-1]) if cand is not None else n_ent
+        frng = fids = None
+        if filt is not None:
+            frng, fids = put(filt[0].reshape(-1)), put(filt[1])
+            if fids.shape[0] == 0:
+                fids = torch.zeros(1, dtype=torch.int64, device=dev)
+        ranks = torch.zeros(E, dtype=torch.int32, device=dev)
+        pos = torch.empty(E, dtype=torch.float32, device=dev) if want_pos_score else None
+        if E == 0:
+            return (ranks, pos) if want_pos_score else ranks
+        d_e, d_r = int(self.ent.shape[1]), int(self.rel.shape[1])
+
+        def need_of(nch):
+            return _lib.lib().kge_rank_chunked_workspace_bytes(self.model, nch * chunk, chunk, n_cand, int(bool(self_cand)), d_e, d_r)
+        nch = n_chunks                      # whole chunks per block: as many as the budget holds, at least one
+        while nch > 1 and need_of(nch) > self.chunk_ws_budget:
+            nch = (nch + 1) // 2
+        need = need_of(nch)
+        if self._cws is None or self._cws.numel() < need:
+            self._cws = None
+            self._cws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _lib.check(_lib.lib().kge_rank_eval_chunked(
+            self.model, int(bool(neg_head)), _lib.ptr(self.ent), n_ent, _lib.ptr(self.rel), self.rel.shape[0], _lib.ptr(self.proj),
+            _lib.ptr(h), _lib.ptr(r), _lib.ptr(t), E, d_e, d_r, self.gamma, self.emb_init, chunk, _lib.ptr(cand), n_cand, stride,
+            int(bool(self_cand)), _lib.ptr(frng), _lib.ptr(fids), _lib.ptr(ranks), _lib.ptr(pos), _lib.ptr(self._cws), need,
+            self.flags, _lib.stream_ptr()))
+        return (ranks, pos) if want_pos_score else ranks
 
     def ranks(self, h, r, t, neg_head, filt=None, cand=None, want_pos_score=False):
         """int32 [E] ranks of the true triples among the corruptions of the chosen side."""
@@ -205,19 +268,35 @@ def filter_columns(cand, filt, e0, e1):
 
 
 def evaluate(model_name, ent, rel, gamma, emb_init, test, known=None, batch=1024, modes=("head", "tail"), proj=None,
-             n_cand=None, chunk=None, seed=0, cache=None):
+             n_cand=None, chunk=None, seed=0, cache=None, neg_deg_sample=False):
     """filtered (known given) or raw ranking metrics over both corruption modes, averaged over all
     2E rankings like the reference (logs of the head and the tail sampler are concatenated,
     train_pytorch.py:221-231).  test / known: (h, r, t) triples of int64 arrays.  n_cand (< number of entities):
     rank against n_cand sampled candidates per chunk of `chunk` triples instead of all entities.
     cache: a dict the caller keeps per (split, known set) - the filter lists and the test triples stay on the device between
-    calls (a training run validates the SAME split against the SAME known triples every --eval_interval steps)."""
+    calls (a training run validates the SAME split against the SAME known triples every --eval_interval steps).
+    neg_deg_sample: --neg_deg_sample_eval (general_models.py:396-432) - every chunk's own corrupted-side entities are prepended
+    to its candidates (n_cand sampled ones, or all entities) and the triple's own column scores 0; raw ranking only."""
+    if neg_deg_sample and known is not None:
+        raise _lib.KgeError("if negative sampling based on degree, we can't filter positive edges.")
     rk = Ranker(model_name, ent, rel, gamma, emb_init, batch, proj=proj)
     th_, tr_, tt_ = test
     n_ent = int(ent.shape[0])
     sampled = n_cand is not None and 0 < n_cand < n_ent
     rng = np.random.RandomState(seed)
     dev = ent.device
+    if neg_deg_sample:
+        ck = int(chunk or batch)
+        n_chunks = (len(th_) + ck - 1) // ck
+        tdev = tuple(_put_ids(x, dev) for x in test)
+        cands = None
+        if sampled:       # sampled_ranks' order: one draw per chunk, every chunk of the first mode before the second
+            cands = np.stack([rng.randint(0, n_ent, size=int(n_cand)) for _ in range(len(modes) * n_chunks)]) \
+                if n_chunks else np.zeros((0, int(n_cand)), np.int64)
+            cands = _put_ids(cands, dev).reshape(len(modes), n_chunks, int(n_cand))
+        allr = [rk.chunked_ranks(tdev[0], tdev[1], tdev[2], mode == "head", ck, cand=cands[k] if sampled else None, self_cand=True)
+                for k, mode in enumerate(modes)]
+        return metrics_from_ranks(torch.cat(allr))
     if cache is not None and not sampled:
         if "test" not in cache:
             cache["test"] = tuple(torch.as_tensor(np.ascontiguousarray(np.asarray(x, np.int64))).to(dev) for x in test)
@@ -243,6 +322,36 @@ def evaluate(model_name, ent, rel, gamma, emb_init, test, known=None, batch=1024
             allr.append(sampled_ranks(rk, th_, tr_, tt_, neg_head, filt, n_ent, int(n_cand), int(chunk or batch), rng))
         else:
             allr.append(rk.ranks(th_, tr_, tt_, neg_head, filt))
+    return metrics_from_ranks(torch.cat(allr))
+
+
+def evaluate_candidates(model_name, ent, rel, gamma, emb_init, test, cand_head=None, cand_tail=None, known=None, batch=1024,
+                        proj=None):
+    """ranking against GIVEN candidates, one list per test triple and side - the official ogbl-wikikg2 / ogbl-biokg protocol and
+    what the reference's forward_test_wikikg does (general_models.py:487-527).  cand_head / cand_tail: [E, n] integer matrices of
+    entity ids (row i: the corrupted heads / tails triple i is ranked against; -1 pads a short row), either may be None; known:
+    (h, r, t) triples whose corruptions do not count (filtered on the device by entity id).  The metrics cover the sides given."""
+    if cand_head is None and cand_tail is None:
+        raise _lib.KgeError("evaluate_candidates needs candidates for at least one side")
+    rk = Ranker(model_name, ent, rel, gamma, emb_init, batch, proj=proj)
+    dev = ent.device
+    tdev = tuple(_put_ids(x, dev) for x in test)
+    E = int(tdev[0].shape[0])
+    n_ent = int(ent.shape[0])
+    allr = []
+    for neg_head, cand in ((True, cand_head), (False, cand_tail)):
+        if cand is None:
+            continue
+        cand = _put_ids(cand, dev)
+        if cand.dim() != 2 or cand.shape[0] != E:
+            raise _lib.KgeError("evaluate_candidates: the %s candidates are %s for %d test triples"
+                                % ("head" if neg_head else "tail", tuple(cand.shape), E))
+        filt = None
+        if known is not None:
+            filt = build_filter_device(known, tdev, neg_head, rel.shape[0], n_ent, dev)
+            if filt is None:
+                filt = build_filter(known[0], known[1], known[2], *(x.cpu().numpy() for x in tdev), neg_head, rel.shape[0])
+        allr.append(rk.chunked_ranks(tdev[0], tdev[1], tdev[2], neg_head, 1, cand=cand, filt=filt))
     return metrics_from_ranks(torch.cat(allr))
 
 

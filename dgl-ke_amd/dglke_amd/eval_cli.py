@@ -41,14 +41,23 @@ class ArgParser(argparse.ArgumentParser):
         a('--num_proc', type=int, default=1)              # accepted, no effect: one process ranks on the GPU
         a('--num_thread', type=int, default=1)
         a('--seed', type=int, default=0)
+        # this build: rank every test triple against ITS OWN candidates - two .npy id matrices [test triples, n] (corrupted
+        # heads, corrupted tails; -1 pads a row; `none` leaves a side out), the ogbl-wikikg2 / ogbl-biokg protocol
+        a('--eval_candidates', type=str, default=None, nargs=2, metavar=('HEAD.npy', 'TAIL.npy'))
 
 
 def main(argv=None):
     from . import eval as kev
     args = ArgParser().parse_args(argv)
     args.eval_filter = not args.no_eval_filter
-    if args.neg_deg_sample_eval:
-        raise KgeError("--neg_deg_sample_eval is not available (uniform --neg_sample_size_eval or all entities)")
+    if args.neg_deg_sample_eval and args.eval_filter:
+        raise KgeError("if negative sampling based on degree, we can't filter positive edges.")
+    if args.eval_candidates and (args.neg_sample_size_eval > 0 or args.neg_deg_sample_eval):
+        raise KgeError("--eval_candidates ranks against the given lists: --neg_sample_size_eval / --neg_deg_sample_eval do not apply")
+    if len(args.gpu) > 1 and args.neg_deg_sample_eval:
+        raise KgeError("--neg_deg_sample_eval is not available on sharded tables")
+    if len(args.gpu) > 1 and args.eval_candidates:
+        raise KgeError("--eval_candidates is not available on sharded tables")
     if args.gpu[0] < 0:
         raise KgeError("dglke_eval ranks on the GPU only: pass --gpu <id> (there is no CPU fallback)")
     if not os.path.isdir(args.model_path):
@@ -75,9 +84,24 @@ def main(argv=None):
         raise KgeError("entity embeddings are {} but the dataset / flags say {}".format(tuple(ent.shape), (ds.n_entities, d_e)))
     emb_init = (args.gamma + 2.0) / args.hidden_dim
     h, r, t = (np.asarray(x) for x in ds.test[:3])
+    cands = [None, None]
+    if args.eval_candidates:
+        for k, f in enumerate(args.eval_candidates):
+            if f.lower() == 'none':
+                continue
+            if not os.path.exists(f):
+                raise KgeError("missing candidate file {}".format(f))
+            c = np.load(f)
+            if c.ndim != 2 or c.shape[0] != len(h) or not np.issubdtype(c.dtype, np.integer):
+                raise KgeError("candidate file {} holds {} {}: expected an integer matrix with one row for each of the {} test "
+                               "triples".format(f, c.dtype, tuple(c.shape), len(h)))
+            cands[k] = c
+        if cands[0] is None and cands[1] is None:
+            raise KgeError("--eval_candidates: at least one of the two files must be given")
     if args.eval_percent < 1:
         keep = np.random.RandomState(args.seed + 17).permutation(len(h))[:max(1, int(len(h) * args.eval_percent))]
         h, r, t = h[keep], r[keep], t[keep]
+        cands = [c[keep] if c is not None else None for c in cands]
     known = None
     if args.eval_filter:
         parts = [p for p in (ds.train, ds.valid, ds.test) if p is not None]
@@ -86,9 +110,13 @@ def main(argv=None):
     if proj is not None:
         Eb = min(Eb, 64)
     start = time.time()
-    metrics = kev.evaluate(model, ent, rel, args.gamma, emb_init, (h, r, t), known, batch=Eb, proj=proj,
-                           n_cand=args.neg_sample_size_eval if args.neg_sample_size_eval > 0 else None,
-                           chunk=args.batch_size_eval, seed=args.seed + 29)
+    if args.eval_candidates:
+        metrics = kev.evaluate_candidates(model, ent, rel, args.gamma, emb_init, (h, r, t), cands[0], cands[1], known, batch=Eb,
+                                          proj=proj)
+    else:
+        metrics = kev.evaluate(model, ent, rel, args.gamma, emb_init, (h, r, t), known, batch=Eb, proj=proj,
+                               n_cand=args.neg_sample_size_eval if args.neg_sample_size_eval > 0 else None,
+                               chunk=args.batch_size_eval, seed=args.seed + 29, neg_deg_sample=args.neg_deg_sample_eval)
     for k, v in metrics.items():
         print('[{}]{} average {}: {}'.format(0, 'Test', k, v))          # train_pytorch.py:236-247 format
     print('Test takes {:.3f} seconds'.format(time.time() - start))

@@ -350,7 +350,8 @@ class Trainer(object):
         cache = self.__dict__.setdefault('_eval_cache', {}).setdefault(which, {})
         metrics = kev.evaluate(args.model_name, m.entity_emb.emb, m.relation_emb.emb, args.gamma, m.emb_init,
                                (h, r, t), known, batch=Eb, proj=proj, n_cand=args.neg_sample_size_eval,
-                               chunk=args.batch_size_eval, seed=args.seed + 29, cache=cache)   # sampled candidates if < n_entities
+                               chunk=args.batch_size_eval, seed=args.seed + 29, cache=cache,   # sampled candidates if < n_entities
+                               neg_deg_sample=args.neg_deg_sample_eval)
         for k, v in metrics.items():
             print('[{}]{} average {}: {}'.format(0, mode, k, v))
         return metrics
@@ -848,6 +849,10 @@ def launch_multi_gpu(args):
 
 def main(argv=None):
     args = ArgParser().parse_args(argv)
+    if args.neg_deg_sample_eval:                 # before anything is loaded or created
+        if len(args.gpu) > 1:
+            raise KgeError("--neg_deg_sample_eval is not available on sharded tables")
+        assert args.no_eval_filter, "if negative sampling based on degree, we can't filter positive edges."   # train.py:878
     prepare_save_path(args)
     init_time_start = time.time()
     if len(args.gpu) > 1:                        # multi-GPU: one process per GPU on peer-to-peer shared tables

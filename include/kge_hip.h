@@ -415,6 +415,34 @@ int kge_rank_eval_split(int model, int neg_head, const float *qent, int64_t n_qe
                         int64_t n_cand, const int64_t *filt_ptr, const int64_t *filt_ids, int Eb, int32_t *ranks,
                         float *pos_score_out, void *ws, size_t ws_bytes, unsigned flags, void *stream);
 
+/* ---- chunked-candidate ranking (csrc/kge_rank_chunk.hip): KEModel.forward_test over the batches of an EvalSampler with
+ * --neg_sample_size_eval / --neg_deg_sample_eval (models/general_models.py:396-432, 436-485; dataloader/sampler.py:459-597) and
+ * the per-triple candidate lists of forward_test_wikikg (models/general_models.py:487-527), for E test triples in one call ----
+ * Chunk c holds the triples [c * chunk, min(E, (c + 1) * chunk)) (the last chunk may be short) and is ranked against ITS OWN
+ * candidates cand[c * cand_stride .. + n_cand): cand_stride == 0 = one list shared by all chunks, cand == NULL = all n_ent
+ * entities (n_cand ignored).  An entry < 0 is an empty slot and never counts (ragged lists); repeats are separate candidates.
+ * An entry >= n_ent is the caller's error: the library never reads through it (it is left out like an empty slot) and does
+ * not report it - no call here synchronises; dglke_amd.eval checks its lists before the call and raises.
+ *   ranks[i] = 1 + #{candidate j of i's chunk : score(i, j) >= score(i), cand_j not in filt_i}
+ * filt_i = filt_ids[filt_ptr[2i] .. filt_ptr[2i+1]) holds ENTITY ids, ascending and unique within a list, rows may share lists -
+ * the layout of kge_topk_select_filtered, what eval.build_filter_device returns; filt_ptr == NULL: raw ranking.
+ * self_cand != 0 (--neg_deg_sample_eval): the corrupted-side entities (heads when neg_head, else tails) of a chunk's own m
+ * triples are prepended, m + n_cand candidates; column i' of triple i' takes the score exactly 0.0f, as the reference's zero
+ * mask leaves it (general_models.py:396-402, 417-432: mask[:, 0::(N+1)] = 0), so it counts iff 0 >= score(i').  Together with a
+ * filter: KGE_ERR_ARG (the reference asserts that the two exclude each other).
+ * Matrix-form models: an fp32-MFMA tile kernel over (chunk, row tile, candidate tile) whose epilogue compares, filters and
+ * counts - no score block.  TransE_l1, RotatE, TransR and KGE_FLAG_FORCE_PAIRWISE: the training kernels' chunked negative scores
+ * into a block of the workspace + a counting kernel.  TransR needs proj.  E == 0: KGE_OK without a launch.
+ * Workspace: any size from kge_rank_chunked_workspace_bytes(model, chunk, chunk, ...) (one chunk) up; the entry walks E in blocks
+ * of as many whole chunks as fit.  n_cand of the size function = the candidates per list (n_ent for cand == NULL). */
+size_t kge_rank_chunked_workspace_bytes(int model, int rows, int chunk, int64_t n_cand, int self_cand, int d_e, int d_r);
+int kge_rank_eval_chunked(int model, int neg_head, const float *ent, int64_t n_ent, const float *rel, int64_t n_rel,
+                          const float *proj, const int64_t *h, const int64_t *r, const int64_t *t, int64_t E,
+                          int d_e, int d_r, float gamma, float emb_init, int chunk,
+                          const int64_t *cand, int64_t n_cand, int64_t cand_stride, int self_cand,
+                          const int64_t *filt_ptr, const int64_t *filt_ids, int32_t *ranks, float *pos_score_out,
+                          void *ws, size_t ws_bytes, unsigned flags, void *stream);
+
 /* ---- peer-to-peer sharded step (xGMI direct; the Hogwild multi-GPU mode) ----
  * The reference's multi-GPU trainer keeps ONE entity table in shared host memory and lets every
  * trainer process gather from it and update it without locks (train.py:298-317 --num_proc,
