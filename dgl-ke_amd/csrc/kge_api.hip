@@ -639,6 +639,18 @@ int Step::setup(void *ws, size_t ws_bytes) {
         if (sh && !sh->rel_local) return fail(KGE_ERR_ARG, "TransR on sharded tables needs kge_shards.rel_local / proj_local (ABI 8)");
         if (!tbx->proj || !tbx->proj_state) return fail(KGE_ERR_ARG, "TransR needs kge_tables.proj / proj_state");
     }
+    if (c.emit && c.emit->msg_rows) {
+        // packed single-trace messages are written by the register-resident update kernel alone (launch_update sends every other
+        // width to the generic update_kernel, which knows the two-trace layouts only) - refused here, before the first launch
+        const int dr_u = p.rescal ? hp->d_e : hp->d_r;
+        if (hp->d_e % 4 != 0 || dr_u % 4 != 0 || (hp->d_e > dr_u ? hp->d_e : dr_u) > 1024)
+            return fail(KGE_ERR_ARG, "kge_step_grads: packed messages (emit.msg_rows) need row widths that are multiples of 4 and at most "
+                                     "1024 floats (d_e=%d d_r=%d); use the two-trace messages", hp->d_e, hp->d_r);
+        if (!c.emit->g0 || c.emit->ld_e < hp->d_e + 4 || c.emit->msg_cap < 1 || c.emit->msg_cap_extra < 1)
+            return fail(KGE_ERR_ARG, "kge_step_grads: packed messages need g0, ld_e >= d_e + 4 and the bucket geometry");
+    }
+    if (c.emit && out && out->g_pos_ent && (c.emit->ld_e > 0 || c.emit->ent_by_id))
+        return fail(KGE_ERR_ARG, "g_pos_ent output cannot be combined with a strided emit or with messages addressed by row id");
     if (need > ws_bytes) return fail(KGE_ERR_WORKSPACE, "kge_step: workspace too small (%zu < %zu)", ws_bytes, need);
     if (p.pipelined && (sh || c.emit || p.transr || p.rescal))
         return fail(KGE_ERR_ARG, "kge_step_async: not available for RESCAL / TransR and the sharded / gradient-emitting steps");
@@ -967,21 +979,21 @@ int Step::phase_update() {
         ua.g0 = emit->g0; ua.gs0 = emit->gs0; ua.g1 = emit->g1; ua.gs1 = emit->gs1;
         ua.gr = emit->gr; ua.gsr = emit->gsr; ua.rid = emit->rid;
         ua.emit_ent = 1; ua.emit_rel = emit->gr ? 1 : 0; ua.emit_by_id = emit->ent_by_id ? 1 : 0;
-        if (emit->msg_rows) {                     // packed single-trace entity messages (ABI 8)
-            if (!emit->g0 || emit->ld_e < d_e + 4 || emit->msg_cap < 1 || emit->msg_cap_extra < 1)
-                return fail(KGE_ERR_ARG, "kge_step_grads: packed messages need g0, ld_e >= d_e + 4 and the bucket geometry");
+        if (emit->msg_rows) {                     // packed single-trace entity messages (ABI 8; checked in Step::setup)
             ua.msg_rows = emit->msg_rows; ua.msg_cap = emit->msg_cap; ua.msg_capT = emit->msg_cap + emit->msg_cap_extra;
             ua.g1 = nullptr; ua.gs0 = nullptr; ua.gs1 = nullptr;
         }
         if (emit->ld_e > 0) { ua.ld_e = emit->ld_e; ua.ld_gs_e = emit->ld_e; }
         if (emit->ld_r > 0) { ua.ld_r = emit->ld_r; ua.ld_gs_r = emit->ld_r; }
     }
-    if (out && out->g_pos_ent) {
-        if (emit && emit->ld_e > 0) return fail(KGE_ERR_ARG, "g_pos_ent output cannot be combined with a strided emit");
-        ua.g0 = out->g_pos_ent;
-    }
+    // g_pos_ent next to a dense emit by union entry (the only emit it combines with, Step::setup): the kernel has one trace-0
+    // pointer - it writes the message array g0, which is the same [UE, d_e] block, and the output is a copy of it
+    const bool copy_g0 = emit && out && out->g_pos_ent && (phases & PH_UPD_ENT);
+    if (out && out->g_pos_ent && !emit) ua.g0 = out->g_pos_ent;
     if (c.build_update) { *c.build_update = ua; return KGE_OK; }
     KGE_TRY(launch_update(ua, s, c.tail));
+    if (copy_g0 && hipMemcpyAsync(out->g_pos_ent, emit->g0, (size_t)b->UE * d_e * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return fail(KGE_ERR_LAUNCH, "hipMemcpyAsync failed");
     // deterministic reduction of this step's loss terms (only when the caller wants the per-step values; running sums are
     // accumulated by the kernels above without it)
     if (p.want4 && (phases & PH_UPD_ENT)) {

@@ -472,6 +472,14 @@ class DistEngine(object):
         # without it and KGE_DIST_LOCAL_SHORTCUT=0 keep the route -> gather -> step -> messages -> apply path)
         self.local_only = (spec.world == 1 and not self.coll and hasattr(self.ops, "step_local") and
                            os.environ.get("KGE_DIST_LOCAL_SHORTCUT", "1") != "0")
+        # the message path's width rule, said up front: kge_step_grads writes packed messages, and kge_adagrad_apply_merged applies
+        # packed and two-trace ones, only for rows of a multiple of 4 and at most 1024 floats (the in-place step of local_only and
+        # the relation trace applied in place have no such rule; test doubles bring their own arithmetic)
+        if isinstance(self.ops, HipOps) and not self.local_only:
+            bad = [w for w in [self.d_e] + ([] if self._rel_inplace else [self.d_r]) if w % 4 or w > 1024]
+            if bad:
+                raise _lib.KgeError("DistEngine: gradient messages need row widths that are multiples of 4 and at most 1024 floats "
+                                    "(d_e=%d, d_r=%d): kge_adagrad_apply_merged has no instance for %r" % (self.d_e, self.d_r, bad))
         self._pair_ok = os.environ.get("KGE_DIST_PAIR_APPLY", "1") != "0"      # (A/B aid: the two owner-side applies as two launches)
         # (compute graphs - precapture() - are OPT-IN: measured slower than six eager launches, 180 vs 172 us per forced-collective
         #  step at cfg-R: a graph launch costs more host time than the launches it replaces at this size)

@@ -333,7 +333,9 @@ int kge_step_phase(const kge_hparams *hp, const kge_tables *tb, const kge_batch 
  * kge_step_grads: same as kge_step_fused but instead of updating the entity table it EMITS, per
  * union entry u, the two trace gradients and their Adagrad increments so that the owner rank can
  * apply them: g0[u,:] (trace 0), gs0[u] = mean(g0^2); g1[u,:] = sum over duplicates (trace 1),
- * gs1[u] = sum_k mean(g_k^2).  The relation table is still updated locally unless rel_emit. */
+ * gs1[u] = sum_k mean(g_k^2).  The relation table is still updated locally unless rel_emit.
+ * kge_step_out.g_pos_ent may be asked for next to a DENSE emit by union entry (ld_e == 0, ent_by_id == 0, no msg_rows): it then
+ * holds a copy of g0; with any other emit layout the call returns KGE_ERR_ARG. */
 typedef struct kge_emit {
     float *g0;  float *gs0;  /* [UE,d_e], [UE] */
     float *g1;  float *gs1;  /* [UE,d_e], [UE] */
@@ -355,6 +357,9 @@ typedef struct kge_emit {
     /* row msg_rows[2u] of g0 - its positive trace if it has one, else its negative trace - and, only when the row is in BOTH      */
     /* traces (msg_rows[2u+1] = p >= 0), the negative trace as a second message at position p of the same owner bucket's extra     */
     /* region (`link` = p in the first one's header, else -1).  msg_rows comes from kge_route_build (ue_msg); g1 / gs* are unused.  */
+    /* Only the register-resident update kernel writes this layout: d_e and d_r (RESCAL: d_e) multiples of 4 and at most 1024      */
+    /* floats.  Any other width returns KGE_ERR_ARG before anything is launched (the two-trace layouts serve every width), and so    */
+    /* does msg_rows without g0, with ld_e < d_e + 4 or with msg_cap / msg_cap_extra < 1.                                            */
     const int32_t *msg_rows;
     int32_t msg_cap, msg_cap_extra;   /* bucket geometry of the packed messages: cap + cap_extra rows per owner, extra region from cap */
 } kge_emit;
