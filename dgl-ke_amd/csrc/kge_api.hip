@@ -1442,6 +1442,112 @@ int kge_rank_eval_chunked(int model, int neg_head, const float *ent, int64_t n_e
     return KGE_OK;
 }
 
+// ---- relation ranking (kge_rank_rel.hip) ----
+// one batch of Eb test triples: query rows / their norms / positive scores, the relation rows' norms (TransE_l2), the score block or
+// comparison mask, and TransR's projected rows, negated relation rows and identity ids.  The layout does not depend on the flags.
+struct RelBufs { float *Q, *qsq, *P, *csq, *S, *THP, *TTP, *TQ, *TSG, *RQ; int64_t *ids; };
+static size_t carve_rank_rel(Carver &cv, RelBufs &w, int model, int Eb, int64_t n_rel, int d_e, int d_r) {
+    const size_t qw = model == KGE_ROTATE ? 0 : model == KGE_RESCAL ? (size_t)d_e * d_e : (size_t)d_e;
+    w.Q = cv.f((size_t)Eb * qw); w.qsq = cv.f(Eb); w.P = cv.f(Eb); w.csq = cv.f((size_t)n_rel);
+    w.S = (float *)cv.bytes(std::max((size_t)Eb * (size_t)n_rel * sizeof(float), rank_gemm_mask_bytes(Eb, n_rel)));
+    const size_t tr = model == KGE_TRANSR ? (size_t)Eb * d_r : 0;
+    w.THP = cv.f(tr); w.TTP = cv.f(tr); w.TQ = cv.f(tr); w.TSG = cv.f(tr);
+    w.RQ = cv.f(model == KGE_TRANSR ? (size_t)n_rel * d_r : 0);
+    w.ids = cv.i64(model == KGE_TRANSR ? std::max((size_t)n_rel, (size_t)Eb) : 0);
+    return cv.off;
+}
+
+size_t kge_rank_rel_workspace_bytes(int model, int Eb, int64_t n_rel, int d_e, int d_r) {
+    if (Eb <= 0 || n_rel <= 0 || n_rel > 0x7fffffff || check_model(model, d_e, d_r) != KGE_OK) return 0;
+    Carver cv; RelBufs w; return carve_rank_rel(cv, w, model, Eb, n_rel, d_e, d_r);
+}
+
+int kge_rank_rel_eval(int model, const float *ent, int64_t n_ent, const float *rel, int64_t n_rel, const float *proj,
+                      const int64_t *h, const int64_t *r, const int64_t *t, int64_t E, int d_e, int d_r,
+                      float gamma, float emb_init, const int64_t *filt_ptr, const int64_t *filt_ids, int Eb,
+                      int32_t *ranks, float *pos_score_out, void *ws, size_t ws_bytes, unsigned flags, void *stream) {
+    if (int rc = check_model(model, d_e, d_r)) return rc;
+    if (model == KGE_TRANSR && !proj) return fail(KGE_ERR_ARG, "kge_rank_rel_eval: TransR needs the projection table");
+    if (!ent || !rel || n_ent <= 0 || n_rel <= 0 || E < 0 || (E && (!h || !r || !t || !ranks)) || !ws)
+        return fail(KGE_ERR_ARG, "kge_rank_rel_eval: bad argument (a null pointer or a count that is not positive)");
+    if (n_rel > 0x7fffffff) return fail(KGE_ERR_ARG, "kge_rank_rel_eval: bad relation count %lld", (long long)n_rel);
+    if (Eb <= 0) return fail(KGE_ERR_ARG, "kge_rank_rel_eval: Eb must be positive (got %d)", Eb);
+    if (!filt_ptr || !filt_ids)
+        return fail(KGE_ERR_ARG, "kge_rank_rel_eval: filt_ptr and filt_ids are required (every list holds the triple's own relation)");
+    if (E == 0) return KGE_OK;
+    if (Eb > E) Eb = (int)E;
+    hipStream_t s = (hipStream_t)stream;
+    Carver cv(ws, ws_bytes); RelBufs w;
+    const size_t need = carve_rank_rel(cv, w, model, Eb, n_rel, d_e, d_r);
+    if (need > ws_bytes) return fail(KGE_ERR_WORKSPACE, "kge_rank_rel_eval: workspace too small (%zu < %zu)", ws_bytes, need);
+    const float rot_div = rot_div_of(emb_init);
+    // the width and the form of the (query row, relation row) product
+    const int D = model == KGE_RESCAL ? d_e * d_e : d_e;
+    const int form = model == KGE_TRANSE_L1 ? KGE_TRANSE_L1 : model == KGE_TRANSE_L2 ? KGE_TRANSE_L2 : KGE_DISTMULT;
+    const bool matrix = model != KGE_TRANSE_L1 && model != KGE_ROTATE && model != KGE_TRANSR;
+    const bool gemm = matrix && !(flags & KGE_FLAG_FORCE_PAIRWISE) && rank_gemm_supported(form, D);
+    const bool l2g = gemm && model == KGE_TRANSE_L2;
+    if (l2g) {       // |c|^2 of every relation row, once
+        EdgeFwdArgs nb{};
+        nb.B = 0; nb.d_e = d_e; nb.d_r = d_r; nb.model = model; nb.nbase = rel; nb.nidx = nullptr; nb.n_neg = (int)n_rel;
+        nb.bsq = w.csq;
+        KGE_TRY(launch_edge_fwd(nb, s));
+    }
+    if (model == KGE_TRANSR) KGE_TRY(launch_rel_neg_rows(rel, n_rel, d_r, w.RQ, w.ids, std::max<int64_t>(n_rel, Eb), s));
+    for (int64_t e0 = 0; e0 < E; e0 += Eb) {
+        const int rows = (int)((E - e0) < Eb ? (E - e0) : Eb);
+        float *P = pos_score_out ? pos_score_out + e0 : w.P;
+        // positive scores: the forward of the true triples, as kge_rank_eval forms them
+        if (model == KGE_TRANSR) {
+            RescalMatvecArgs m{};
+            m.B = rows; m.D = d_e; m.Dc = d_r; m.rel = proj; m.ridx = r + e0;
+            m.z1 = ent; m.z1idx = h + e0; m.c1 = w.THP; m.z2 = ent; m.z2idx = t + e0; m.c2 = w.TTP;
+            KGE_TRY(launch_rescal_matvec(m, s));
+            TransRArgs tp{};
+            tp.B = rows; tp.C = 1; tp.chunk = rows; tp.De = d_e; tp.Dr = d_r; tp.gamma = gamma; tp.ent = ent;
+            tp.h_gid = h + e0; tp.t_gid = t + e0; tp.rel_ids = r + e0; tp.rel = rel; tp.proj = const_cast<float *>(proj);
+            tp.HP = w.THP; tp.TP = w.TTP; tp.Q = w.TQ; tp.SG = w.TSG; tp.P = P;
+            KGE_TRY(launch_transr_pos(tp, s));
+        } else if (model == KGE_RESCAL) {
+            RescalMatvecArgs m{};
+            m.B = rows; m.D = d_e; m.rel = rel; m.ridx = r + e0;
+            m.y1 = ent; m.y1idx = t + e0; m.pd = ent; m.pdidx = h + e0; m.p = P;
+            KGE_TRY(launch_rescal_matvec(m, s));
+        } else {
+            EdgeFwdArgs ef;
+            fill_edge(ef, EdgeSrc{ent, h + e0, ent, t + e0, rel, r + e0}, model, rows, d_e, d_r, 0, gamma, rot_div);
+            ef.pos_score = P;
+            KGE_TRY(launch_edge_fwd(ef, s));
+        }
+        if (model == KGE_ROTATE) {
+            KGE_TRY(launch_rel_rotate_score(ent, rel, h + e0, t + e0, rows, n_rel, d_e, gamma, rot_div, w.S, s));
+            KGE_TRY(launch_rank_count(w.S, P, rows, n_rel, filt_ptr, filt_ids, e0, ranks, s));
+            continue;
+        }
+        KGE_TRY(launch_rel_query(model, ent, h + e0, t + e0, rows, d_e, w.Q, l2g ? w.qsq : nullptr, s));
+        if (model == KGE_TRANSR) {
+            // the training forward with the roles exchanged: "positive" j = relation j (matrix P_j, q row -c_j), the batch's u rows
+            // are the one chunk's shared "negatives": S[j, i] = gamma - |u_i P_j + c_j|_1
+            TransRArgs tr{};
+            tr.B = (int)n_rel; tr.C = 1; tr.chunk = (int)n_rel; tr.N = rows; tr.De = d_e; tr.Dr = d_r; tr.gamma = gamma;
+            tr.ent = w.Q; tr.cent = w.Q; tr.neg_ids = w.ids; tr.rel_ids = w.ids; tr.rel = rel; tr.proj = const_cast<float *>(proj);
+            tr.Q = w.RQ; tr.S = w.S; tr.Z = nullptr;
+            KGE_TRY(launch_transr_fwd(tr, s));
+            KGE_TRY(launch_rel_count_t(w.S, P, rows, n_rel, filt_ptr, filt_ids, e0, ranks, s));
+        } else if (gemm) {
+            KGE_TRY(launch_rank_gemm(form, w.Q, rows, rel, nullptr, n_rel, D, gamma, clamp_of(model), w.qsq, w.csq, P, w.S, filt_ptr,
+                                     filt_ids, e0, ranks, s));
+        } else {
+            NegArgs na; fill_pair(na, form, 1, rows, (int)n_rel, D, gamma, w.Q, rel, nullptr);
+            na.clampv = clamp_of(model);
+            na.S = w.S;
+            KGE_TRY(launch_neg_fwd_pair(na, s));
+            KGE_TRY(launch_rank_count(w.S, P, rows, n_rel, filt_ptr, filt_ids, e0, ranks, s));
+        }
+    }
+    return KGE_OK;
+}
+
 int kge_step_sharded(const kge_hparams *hp, const kge_shards *sh, const kge_batch *b,
                      const kge_step_out *out, void *ws, size_t ws_bytes, void *stream) {
     if (!sh) return fail(KGE_ERR_ARG, "kge_step_sharded: null shard map");

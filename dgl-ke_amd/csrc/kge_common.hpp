@@ -522,6 +522,15 @@ int launch_rank_chunk_gemm(int model, const ChunkCands &cc, int64_t c0, int nch,
 int launch_chunk_ids(const ChunkCands &cc, int64_t cfirst, int nch, int m, int64_t ncols, int64_t *ids, hipStream_t s);
 int launch_chunk_count(const ChunkCands &cc, int64_t cfirst, int nch, int m, int64_t ncols, const float *S, const float *P,
                        const int64_t *filt_ptr, const int64_t *filt_ids, int32_t *ranks, hipStream_t s);
+// ---- relation ranking (kge_rank_rel.hip) ----
+// query rows of a batch of (h, t) pairs: Q [rows, d_e] (RESCAL: [rows, d_e * d_e]), qsq [rows] = |q|^2 or null
+int launch_rel_query(int model, const float *ent, const int64_t *h, const int64_t *t, int rows, int d_e, float *Q, float *qsq,
+                     hipStream_t s);
+int launch_rel_rotate_score(const float *ent, const float *rel, const int64_t *h, const int64_t *t, int rows, int64_t n_rel, int d_e,
+                            float gamma, float rot_div, float *S, hipStream_t s);      // S [rows, n_rel]
+int launch_rel_neg_rows(const float *rel, int64_t n_rel, int d_r, float *out, int64_t *ids, int64_t n_ids, hipStream_t s);   // -rel, iota
+int launch_rel_count_t(const float *St, const float *P, int rows, int64_t N, const int64_t *filt_ptr, const int64_t *filt_ids,
+                       int64_t e0, int32_t *ranks, hipStream_t s);                     // launch_rank_count over St [N, rows]
 struct GemmArgs {                   // LDS-staged fp32-MFMA negative scoring (kge_neg_gemm.hip)
     int model, C, chunk, N, D;
     float gamma;

@@ -165,6 +165,9 @@ _SIGNATURES = {
     "kge_rank_chunked_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i64, c_i, c_i, c_i]),
     "kge_rank_eval_chunked": (c_i, [c_i, c_i, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_f, c_f, c_i, c_p, c_i64,
                                     c_i64, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_u, c_p]),
+    "kge_rank_rel_workspace_bytes": (c_sz, [c_i, c_i, c_i64, c_i, c_i]),
+    "kge_rank_rel_eval": (c_i, [c_i, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_f, c_f, c_p, c_p, c_i, c_p, c_p,
+                                c_p, c_sz, c_u, c_p]),
     "kge_topk_workspace_bytes": (c_sz, [c_i, c_i64, c_i, c_i]),
     "kge_topk_select": (c_i, [c_i, c_i, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_i64, c_p, c_i64,
                               c_i, c_i, c_p, c_p, c_p, c_sz, c_p]),

@@ -106,6 +106,46 @@ def build_filter_device(known, test, neg_head, n_relations, n_entities, dev):
     return key_ranges(key, tkey), val.contiguous()
 
 
+def build_relation_filter(known, test, n_entities, n_relations, dev=None):
+    """relation lists for `Ranker.relation_ranks` (kge_rank_rel_eval): for test triple i = (h, r, t) the ascending unique relation
+    ids that do NOT count among its candidates - its own relation r, and with `known` ((h, r, t) id arrays, or None for raw
+    ranking) every relation j for which (h, j, t) is a known triple.  The test triples are appended to the known ones, so every
+    list holds its own relation.  Sorted on `dev` (default: the GPU when there is one) like `build_filter_device`: one composite
+    key ((h * n_entities + t) * n_relations + relation) through torch.unique, or two stable sorts when that would not fit int64;
+    the ranges come from `key_ranges`.  Returns (ranges [E, 2], ids) int64 tensors on `dev`; triples with the same (h, t) share a
+    list.  known=None: ranges[i] = (i, i + 1), ids = r."""
+    if dev is None:
+        dev = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
+    th_, tr_, tt_ = (_put_ids(x, dev) for x in test)
+    E = int(th_.shape[0])
+    if known is None:
+        lo = torch.arange(E, dtype=torch.int64, device=dev)
+        return torch.stack([lo, lo + 1], 1).contiguous(), tr_.contiguous()
+    NE, R = int(n_entities), int(n_relations)
+    if NE * NE >= (1 << 62):
+        raise _lib.KgeError("build_relation_filter: %d entities are too many for the (head, tail) key" % NE)
+    kh, kr, kt = (torch.cat([_put_ids(x, dev), y]) for x, y in zip(known, (th_, tr_, tt_)))
+    key = kh * NE
+    key += kt
+    del kh, kt
+    if NE * NE * R >= (1 << 62) or _FORCE_TWO_KEY_SORT:
+        o = torch.argsort(kr, stable=True)
+        o = o[torch.argsort(key[o], stable=True)]            # lexicographic (key, relation) order
+        key, val = key[o], kr[o]
+        del o
+        keep = torch.ones(key.shape[0], dtype=torch.bool, device=key.device)
+        keep[1:] = (key[1:] != key[:-1]) | (val[1:] != val[:-1])
+        key, val = key[keep], val[keep]
+    else:
+        key *= R
+        key += kr
+        comp = torch.unique(key)                             # sorted unique (key, relation) pairs
+        del key
+        key = torch.div(comp, R, rounding_mode='floor')
+        val = comp - key * R
+    return key_ranges(key, th_ * NE + tt_), val.contiguous()
+
+
 class Ranker(object):
     """device-resident evaluation of one (ent, rel) table pair."""
 
@@ -124,6 +164,48 @@ class Ranker(object):
         self._all = None
         self._cws = None                   # workspace of chunked_ranks
         self.chunk_ws_budget = 512 << 20   # bytes: chunked_ranks asks for at most this (never less than one chunk needs)
+        self._rws = None                   # workspace of relation_ranks
+        self.rel_ws_budget = 512 << 20     # bytes: relation_ranks asks for at most this (never less than one row needs)
+
+    def relation_ranks(self, h, r, t, filt, want_pos_score=False):
+        """int32 [E] ranks of the true RELATIONS among all relations (kge_rank_rel_eval): 1 + the relations outside the triple's
+        list that score at least as high as the true one.  filt: the (ranges, relation ids) pair of `build_relation_filter` -
+        required, every list holds at least the triple's own relation.  The triples go in batches of `self.batch`, halved until
+        the workspace fits `rel_ws_budget` (RESCAL's query rows are d_e^2 wide, TransR keeps a [relations, batch] block)."""
+        dev = self.ent.device
+
+        def put(x, dt=torch.int64):
+            if isinstance(x, torch.Tensor):
+                return x.to(dev, dt).contiguous()
+            return torch.as_tensor(np.ascontiguousarray(x)).to(dev, dt)
+        if filt is None:
+            raise _lib.KgeError("relation_ranks needs the lists of build_relation_filter (raw ranking: known=None)")
+        h, r, t = put(h), put(r), put(t)
+        frng, fids = put(filt[0].reshape(-1)), put(filt[1])
+        E = int(h.shape[0])
+        ranks = torch.zeros(E, dtype=torch.int32, device=dev)
+        pos = torch.empty(E, dtype=torch.float32, device=dev) if want_pos_score else None
+        if E == 0:
+            return (ranks, pos) if want_pos_score else ranks
+        n_rel, d_e, d_r = int(self.rel.shape[0]), int(self.ent.shape[1]), int(self.rel.shape[1])
+
+        def need_of(eb):
+            return _lib.lib().kge_rank_rel_workspace_bytes(self.model, eb, n_rel, d_e, d_r)
+        Eb = max(1, min(self.batch, E))
+        while Eb > 1 and need_of(Eb) > self.rel_ws_budget:
+            Eb = (Eb + 1) // 2
+        need = need_of(Eb)
+        if need == 0:
+            raise _lib.KgeError("relation_ranks: the tables are %s / %s, which this model does not take"
+                                % (tuple(self.ent.shape), tuple(self.rel.shape)))
+        if self._rws is None or self._rws.numel() < need:
+            self._rws = None
+            self._rws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _lib.check(_lib.lib().kge_rank_rel_eval(
+            self.model, _lib.ptr(self.ent), self.ent.shape[0], _lib.ptr(self.rel), n_rel, _lib.ptr(self.proj), _lib.ptr(h),
+            _lib.ptr(r), _lib.ptr(t), E, d_e, d_r, self.gamma, self.emb_init, _lib.ptr(frng), _lib.ptr(fids), Eb, _lib.ptr(ranks),
+            _lib.ptr(pos), _lib.ptr(self._rws), need, self.flags, _lib.stream_ptr()))
+        return (ranks, pos) if want_pos_score else ranks
 
     def chunked_ranks(self, h, r, t, neg_head, chunk, cand=None, filt=None, self_cand=False, want_pos_score=False):
         """int32 [E] ranks, the triples taken in chunks of `chunk` and every chunk ranked against its own candidates
@@ -353,6 +435,24 @@ def evaluate_candidates(model_name, ent, rel, gamma, emb_init, test, cand_head=N
                 filt = build_filter(known[0], known[1], known[2], *(x.cpu().numpy() for x in tdev), neg_head, rel.shape[0])
         allr.append(rk.chunked_ranks(tdev[0], tdev[1], tdev[2], neg_head, 1, cand=cand, filt=filt))
     return metrics_from_ranks(torch.cat(allr))
+
+
+def evaluate_relations(model_name, ent, rel, gamma, emb_init, test, known=None, batch=1024, proj=None, cache=None):
+    """relation ranking: every test triple (h, r, t) against ALL relations as (h, ?, t) - the metrics of `metrics_from_ranks` over
+    the E rankings.  rank = 1 + the relations, other than r itself, that score at least as high as r; with `known` ((h, r, t)
+    triples) the relations j for which (h, j, t) is a known triple do not count either (filtered), known=None ranks raw.  The
+    reference has no such evaluation; the protocol is stated in include/kge_hip.h (kge_rank_rel_eval).  cache: as in `evaluate` -
+    the lists and the test ids stay on the device between the validations of a run."""
+    rk = Ranker(model_name, ent, rel, gamma, emb_init, batch, proj=proj)
+    dev = ent.device
+    if cache is not None and "rel_test" in cache:
+        tdev, filt = cache["rel_test"], cache["rel_filt"]
+    else:
+        tdev = tuple(_put_ids(x, dev) for x in test)
+        filt = build_relation_filter(known, tdev, ent.shape[0], rel.shape[0], dev)
+        if cache is not None:
+            cache["rel_test"], cache["rel_filt"] = tdev, filt
+    return metrics_from_ranks(rk.relation_ranks(tdev[0], tdev[1], tdev[2], filt))
 
 
 # ---- range-sharded tables ---------------------------------------------------------------------------------------------------

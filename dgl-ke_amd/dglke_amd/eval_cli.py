@@ -44,6 +44,9 @@ class ArgParser(argparse.ArgumentParser):
         # this build: rank every test triple against ITS OWN candidates - two .npy id matrices [test triples, n] (corrupted
         # heads, corrupted tails; -1 pads a row; `none` leaves a side out), the ogbl-wikikg2 / ogbl-biokg protocol
         a('--eval_candidates', type=str, default=None, nargs=2, metavar=('HEAD.npy', 'TAIL.npy'))
+        # this build: after the entity metrics, rank the true RELATION of every test triple among all relations (h, ?, t) and
+        # print REL_MRR / REL_MR / REL_HITS@k; filtered unless --no_eval_filter
+        a('--eval_relation', action='store_true')
 
 
 def main(argv=None):
@@ -58,6 +61,10 @@ def main(argv=None):
         raise KgeError("--neg_deg_sample_eval is not available on sharded tables")
     if len(args.gpu) > 1 and args.eval_candidates:
         raise KgeError("--eval_candidates is not available on sharded tables")
+    if len(args.gpu) > 1 and args.eval_relation:
+        raise KgeError("--eval_relation is not available on sharded tables")
+    if args.eval_relation and args.eval_candidates:
+        raise KgeError("--eval_relation ranks against all relations: the lists of --eval_candidates are entity lists")
     if args.gpu[0] < 0:
         raise KgeError("dglke_eval ranks on the GPU only: pass --gpu <id> (there is no CPU fallback)")
     if not os.path.isdir(args.model_path):
@@ -119,6 +126,11 @@ def main(argv=None):
                                chunk=args.batch_size_eval, seed=args.seed + 29, neg_deg_sample=args.neg_deg_sample_eval)
     for k, v in metrics.items():
         print('[{}]{} average {}: {}'.format(0, 'Test', k, v))          # train_pytorch.py:236-247 format
+    if args.eval_relation:
+        rel_metrics = kev.evaluate_relations(model, ent, rel, args.gamma, emb_init, (h, r, t), known, batch=Eb, proj=proj)
+        for k, v in rel_metrics.items():
+            print('[{}]{} average REL_{}: {}'.format(0, 'Test', k, v))
+            metrics['REL_' + k] = v
     print('Test takes {:.3f} seconds'.format(time.time() - start))
     return metrics
 

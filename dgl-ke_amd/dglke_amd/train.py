@@ -50,6 +50,7 @@ class ArgParser(argparse.ArgumentParser):
         a('--neg_deg_sample', action='store_true')
         a('--neg_deg_sample_eval', action='store_true')
         a('--neg_sample_size_eval', type=int, default=-1)
+        a('--eval_relation', action='store_true')    # this build: REL_MRR / REL_MR / REL_HITS@k of (h, ?, t) after the entity metrics
         a('--eval_percent', type=float, default=1)
         a('--no_eval_filter', action='store_true')
         a('-log', '--log_interval', type=int, default=1000)
@@ -354,6 +355,12 @@ class Trainer(object):
                                neg_deg_sample=args.neg_deg_sample_eval)
         for k, v in metrics.items():
             print('[{}]{} average {}: {}'.format(0, mode, k, v))
+        if args.eval_relation:
+            rel_metrics = kev.evaluate_relations(args.model_name, m.entity_emb.emb, m.relation_emb.emb, args.gamma, m.emb_init,
+                                                 (h, r, t), known, batch=Eb, proj=proj, cache=cache)
+            for k, v in rel_metrics.items():
+                print('[{}]{} average REL_{}: {}'.format(0, mode, k, v))
+                metrics['REL_' + k] = v
         return metrics
 
     def train(self):
@@ -853,6 +860,8 @@ def main(argv=None):
         if len(args.gpu) > 1:
             raise KgeError("--neg_deg_sample_eval is not available on sharded tables")
         assert args.no_eval_filter, "if negative sampling based on degree, we can't filter positive edges."   # train.py:878
+    if args.eval_relation and len(args.gpu) > 1:
+        raise KgeError("--eval_relation is not available on sharded tables")
     prepare_save_path(args)
     init_time_start = time.time()
     if len(args.gpu) > 1:                        # multi-GPU: one process per GPU on peer-to-peer shared tables

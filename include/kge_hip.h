@@ -448,6 +448,34 @@ int kge_rank_eval_chunked(int model, int neg_head, const float *ent, int64_t n_e
                           const int64_t *filt_ptr, const int64_t *filt_ids, int32_t *ranks, float *pos_score_out,
                           void *ws, size_t ws_bytes, unsigned flags, void *stream);
 
+/* ---- relation ranking (csrc/kge_rank_rel.hip): every test triple (h, r, t) against ALL n_rel relations ----
+ * The reference has no counterpart - its evaluation corrupts entities only - so no reference line can be cited; the protocol is
+ * fixed here.  For test triple i = (h, r, t)
+ *   ranks[i] = 1 + #{j in [0, n_rel) : j not in list_i, s(h, j, t) >= s(h, r, t)}
+ * list_i = filt_ids[filt_ptr[2i] .. filt_ptr[2i+1]) holds RELATION ids (column j = relation j), ascending and unique; rows may
+ * share a list.  It is REQUIRED and always holds the triple's own relation r: the own column never counts, raw or filtered - its
+ * score and the positive score are formed in two different ways, so their >= would be decided by rounding.  Raw ranking:
+ * list_i = {r}; filtered ranking: {r} united with every j for which (h, j, t) is a known triple (dglke_amd.eval.build_relation_filter
+ * builds both).  s is the score kge_rank_eval ranks with (SimplE clamped at +-20, RotatE's phase = row / (emb_init / pi));
+ * pos_score_out (optional) receives the E true-triple scores.
+ * For a fixed (h, t) the score is a function of the relation row c_j alone: TransE q = t - h, gamma - |q - c_j|; DistMult /
+ * ComplEx / SimplE / RESCAL q . c_j with q = h o t, [h_re t_re + h_im t_im | h_re t_im - h_im t_re], 1/2 [h_i o t_j | h_j o t_i],
+ * vec(h t^T) - the forms of kge_rank_eval's kernels with the relation table as the candidate table (TransE_l2 and the dot forms:
+ * the fp32-MFMA tile kernel + bit mask; TransE_l1, widths that are no multiple of 4 and KGE_FLAG_FORCE_PAIRWISE: the pairwise
+ * score block + counting kernel); RotatE: gamma - sum_k |h_k e^{i theta_jk} - t_k| by a kernel that keeps a relation tile's
+ * cos / sin in LDS; TransR: gamma - |(h - t) P_j + c_j|_1 by the training forward with the relations as its positives (needs
+ * proj).  RESCAL and TransR cost d_e * d_r multiply-adds per (triple, relation) - inherent to the models - and RESCAL's query
+ * rows are d_e^2 wide: size Eb from the workspace you can afford.
+ * One pass per Eb triples (Eb > E is taken as E); the ranks do not depend on Eb.  Workspace: kge_rank_rel_workspace_bytes(model, Eb,
+ * n_rel, d_e, d_r) (0: bad arguments).  Errors before any launch: KGE_ERR_ARG for a null pointer, a bad model / width combination,
+ * TransR without proj, n_rel > 0x7fffffff, Eb <= 0, a missing filter pointer; KGE_ERR_WORKSPACE for a workspace that is too small.
+ * E == 0: KGE_OK without a launch. */
+size_t kge_rank_rel_workspace_bytes(int model, int Eb, int64_t n_rel, int d_e, int d_r);
+int kge_rank_rel_eval(int model, const float *ent, int64_t n_ent, const float *rel, int64_t n_rel, const float *proj,
+                      const int64_t *h, const int64_t *r, const int64_t *t, int64_t E, int d_e, int d_r,
+                      float gamma, float emb_init, const int64_t *filt_ptr, const int64_t *filt_ids, int Eb,
+                      int32_t *ranks, float *pos_score_out, void *ws, size_t ws_bytes, unsigned flags, void *stream);
+
 /* ---- peer-to-peer sharded step (xGMI direct; the Hogwild multi-GPU mode) ----
  * The reference's multi-GPU trainer keeps ONE entity table in shared host memory and lets every
  * trainer process gather from it and update it without locks (train.py:298-317 --num_proc,
