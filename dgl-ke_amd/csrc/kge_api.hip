@@ -1168,13 +1168,47 @@ int kge_step_grads(const kge_hparams *hp, const kge_tables *tb, const kge_batch 
     return run_step(hp, tb, b, out, ws, ws_bytes, stream, c);
 }
 
-struct RankBufs { float *A, *asq, *P, *bsq, *S, *RV, *THP, *TTP, *TQ, *TSG; };
+// TransR's rows of a batch of test triples: projected head / tail, q = x P - r, sign(hp + r - tp); n floats each
+struct TransRRows { float *THP, *TTP, *TQ, *TSG; };
+static void carve_transr_rows(Carver &cv, TransRRows &w, size_t n) {
+    w.THP = cv.f(n); w.TTP = cv.f(n); w.TQ = cv.f(n); w.TSG = cv.f(n);
+}
+
+// what every ranking entry needs of a batch of `rows` test triples (h, r, t: the batch's ids) before it scores candidates: the positive
+// scores P and the pos-side vectors A (+ their squared norms asq when given).  A == null: positive scores only (relation ranking).
+// TransR: only the projections hp, tp - launch_transr_pos, which the caller runs with its own candidates, makes P and q from them.
+static int rank_pos_side(int model, int neg_head, const float *ent, const float *rel, const float *proj, const int64_t *h,
+                         const int64_t *r, const int64_t *t, int rows, int d_e, int d_r, float gamma, float rot_div, float *P,
+                         float *A, float *asq, float *RV, const TransRRows &w, hipStream_t s) {
+    if (model == KGE_TRANSR) {
+        RescalMatvecArgs m{};
+        m.B = rows; m.D = d_e; m.Dc = d_r; m.rel = proj; m.ridx = r;
+        m.z1 = ent; m.z1idx = h; m.c1 = w.THP; m.z2 = ent; m.z2idx = t; m.c2 = w.TTP;
+        KGE_TRY(launch_rescal_matvec(m, s));
+    } else if (model == KGE_RESCAL) {
+        RescalMatvecArgs m{};
+        m.B = rows; m.D = d_e; m.rel = rel; m.ridx = r;
+        m.y1 = ent; m.y1idx = t; m.pd = ent; m.pdidx = h; m.p = P;
+        if (A) {
+            m.r1 = neg_head ? A : RV;                   // V = M t
+            if (!neg_head) { m.y2 = ent; m.y2idx = h; m.r2 = A; }
+        }
+        KGE_TRY(launch_rescal_matvec(m, s));
+    } else {
+        EdgeFwdArgs ef;
+        fill_edge(ef, EdgeSrc{ent, h, ent, t, rel, r}, model, rows, d_e, d_r, neg_head, gamma, rot_div);
+        ef.pos_score = P; ef.A = A; ef.asq = asq;
+        KGE_TRY(launch_edge_fwd(ef, s));
+    }
+    return KGE_OK;
+}
+
+struct RankBufs : TransRRows { float *A, *asq, *P, *bsq, *S, *RV; };
 static size_t carve_rank(Carver &cv, RankBufs &w, int Eb, int64_t N, int d_e) {
     w.A = cv.f((size_t)Eb * d_e); w.asq = cv.f(Eb); w.P = cv.f(Eb); w.bsq = cv.f((size_t)N);
     w.S = (float *)cv.bytes(std::max((size_t)Eb * (size_t)N * sizeof(float), rank_gemm_mask_bytes(Eb, N)));   // scores / the comparison mask
     w.RV = cv.f((size_t)Eb * d_e);                      // V = M t (RESCAL)
-    w.THP = cv.f((size_t)Eb * 1024); w.TTP = cv.f((size_t)Eb * 1024);       // TransR: hp, tp, q, sign rows (d_r <= 1024)
-    w.TQ = cv.f((size_t)Eb * 1024); w.TSG = cv.f((size_t)Eb * 1024);
+    carve_transr_rows(cv, w, (size_t)Eb * 1024);        // (d_r <= 1024)
     return cv.off;
 }
 
@@ -1200,7 +1234,7 @@ static int rank_eval_impl(int model, int neg_head, const float *qent, const floa
     Carver cv(ws, ws_bytes); RankBufs w;
     const size_t need = carve_rank(cv, w, Eb, N, d_e);
     if (need > ws_bytes) return fail(KGE_ERR_WORKSPACE, "kge_rank_eval: workspace too small (%zu < %zu)", ws_bytes, need);
-    float *A = w.A, *asq = w.asq, *P = w.P, *bsq = w.bsq, *S = w.S, *RV = w.RV, *THP = w.THP, *TTP = w.TTP, *TQ = w.TQ, *TSG = w.TSG;
+    float *A = w.A, *asq = w.asq, *bsq = w.bsq, *S = w.S;
     const bool gemm = use_mfma(model, d_e, (int)N, flags);
     const bool l2g = gemm && model == KGE_TRANSE_L2;
     const float rot_div = rot_div_of(emb_init);
@@ -1212,38 +1246,22 @@ static int rank_eval_impl(int model, int neg_head, const float *qent, const floa
     }
     for (int64_t e0 = 0; e0 < E; e0 += Eb) {
         const int rows = (int)((E - e0) < Eb ? (E - e0) : Eb);
-        EdgeFwdArgs ef;
-        fill_edge(ef, EdgeSrc{qent, h + e0, qent, t + e0, rel, r + e0}, model, rows, d_e, d_r, neg_head, gamma, rot_div);
-        ef.pos_score = pos_score_out ? pos_score_out + e0 : P; ef.A = A; ef.asq = l2g ? asq : nullptr;
+        float *P = pos_score_out ? pos_score_out + e0 : w.P;
+        KGE_TRY(rank_pos_side(model, neg_head, qent, rel, proj, h + e0, r + e0, t + e0, rows, d_e, d_r, gamma, rot_div, P, A,
+                              l2g ? asq : nullptr, w.RV, w, s));
         if (model == KGE_TRANSR) {
             // the training kernels with one chunk = this batch of test triples and the candidates as negatives
-            RescalMatvecArgs m{};
-            m.B = rows; m.D = d_e; m.Dc = d_r; m.rel = proj; m.ridx = r + e0;
-            m.z1 = qent; m.z1idx = h + e0; m.c1 = THP; m.z2 = qent; m.z2idx = t + e0; m.c2 = TTP;
-            KGE_TRY(launch_rescal_matvec(m, s));
             TransRArgs tr{};
             tr.B = rows; tr.C = 1; tr.chunk = rows; tr.N = (int)N; tr.De = d_e; tr.Dr = d_r; tr.neg_head = neg_head;
             tr.gamma = gamma; tr.ent = qent; tr.cent = cent; tr.h_gid = h + e0; tr.t_gid = t + e0; tr.neg_ids = cand; tr.rel_ids = r + e0;
             tr.rel = rel; tr.proj = const_cast<float *>(proj);
-            tr.HP = THP; tr.TP = TTP; tr.Q = TQ; tr.SG = TSG; tr.P = ef.pos_score; tr.S = S; tr.Z = nullptr;
+            tr.HP = w.THP; tr.TP = w.TTP; tr.Q = w.TQ; tr.SG = w.TSG; tr.P = P; tr.S = S; tr.Z = nullptr;
             KGE_TRY(launch_transr_pos(tr, s));
             KGE_TRY(launch_transr_fwd(tr, s));
-        } else if (model == KGE_RESCAL) {
-            RescalMatvecArgs m{};
-            m.B = rows; m.D = d_e; m.rel = rel; m.ridx = r + e0;
-            m.y1 = qent; m.y1idx = t + e0; m.r1 = neg_head ? A : RV;
-            if (!neg_head) { m.y2 = qent; m.y2idx = h + e0; m.r2 = A; }
-            m.pd = qent; m.pdidx = h + e0; m.p = ef.pos_score;
-            KGE_TRY(launch_rescal_matvec(m, s));
-        } else {
-            KGE_TRY(launch_edge_fwd(ef, s));
-        }
-        if (model == KGE_TRANSR) {
-            // scores already in S
         } else if (gemm && rank_gemm_supported(model, d_e)) {
             // one tiled GEMM per batch whose epilogue keeps the comparison bits; ranks from the mask (kge_rank_gemm.hip)
-            KGE_TRY(launch_rank_gemm(model, A, rows, cent, cand, N, d_e, gamma, clamp_of(model), asq, bsq,
-                                     pos_score_out ? pos_score_out + e0 : P, S, filt_ptr, filt_ids, e0, ranks, s));
+            KGE_TRY(launch_rank_gemm(model, A, rows, cent, cand, N, d_e, gamma, clamp_of(model), asq, bsq, P, S, filt_ptr, filt_ids, e0,
+                                     ranks, s));
             continue;
         } else if (gemm) {
             GemmArgs g; fill_gemm(g, model, 1, rows, (int)N, d_e, gamma, A, cent, cand);
@@ -1254,7 +1272,7 @@ static int rank_eval_impl(int model, int neg_head, const float *qent, const floa
             na.S = S;
             KGE_TRY(launch_neg_fwd_pair(na, s));
         }
-        KGE_TRY(launch_rank_count(S, pos_score_out ? pos_score_out + e0 : P, rows, N, filt_ptr, filt_ids, e0, ranks, s));
+        KGE_TRY(launch_rank_count(S, P, rows, N, filt_ptr, filt_ids, e0, ranks, s));
     }
     return KGE_OK;
 }
@@ -1311,14 +1329,13 @@ int kge_rank_eval_split(int model, int neg_head, const float *qent, int64_t n_qe
 // ---- chunked-candidate ranking (kge_rank_chunk.hip) ----
 // one block of whole chunks: pos-side vectors / norms / positive scores of its rows, the candidates' norms (TransE_l2), and - for the
 // score-block route only, but the layout does not depend on the flags - the id list and the score block
-struct ChunkBufs { float *A, *asq, *P, *RV, *THP, *TTP, *TQ, *TSG, *bsq_own, *bsq_c, *S; int64_t *ids; };
+struct ChunkBufs : TransRRows { float *A, *asq, *P, *RV, *bsq_own, *bsq_c, *S; int64_t *ids; };
 static size_t carve_chunked(Carver &cv, ChunkBufs &w, int model, int64_t rows, int chunk, int64_t n_cand, int self_cand, int d_e, int d_r) {
     const size_t nch = (size_t)((rows + chunk - 1) / chunk), R = nch * (size_t)chunk;
     const size_t ncols = (size_t)n_cand + (self_cand ? (size_t)chunk : 0);
     w.A = cv.f(R * d_e); w.asq = cv.f(R); w.P = cv.f(R);
     w.RV = cv.f(model == KGE_RESCAL ? R * d_e : 0);                    // V = M t (RESCAL)
-    const size_t tr = model == KGE_TRANSR ? R * (size_t)d_r : 0;       // TransR: hp, tp, q, sign rows
-    w.THP = cv.f(tr); w.TTP = cv.f(tr); w.TQ = cv.f(tr); w.TSG = cv.f(tr);
+    carve_transr_rows(cv, w, model == KGE_TRANSR ? R * (size_t)d_r : 0);
     w.bsq_own = cv.f(R); w.bsq_c = cv.f(nch * (size_t)n_cand);
     w.ids = cv.i64(nch * ncols);
     w.S = cv.f(R * ncols);
@@ -1381,25 +1398,8 @@ int kge_rank_eval_chunked(int model, int neg_head, const float *ent, int64_t n_e
         const int64_t e0 = c0 * chunk;
         const int rows = (int)std::min<int64_t>((int64_t)nch * chunk, E - e0);
         float *P = pos_score_out ? pos_score_out + e0 : w.P;
-        // positive scores and pos-side vectors of every row of the block
-        EdgeFwdArgs ef;
-        fill_edge(ef, EdgeSrc{ent, h + e0, ent, t + e0, rel, r + e0}, model, rows, d_e, d_r, neg_head, gamma, rot_div);
-        ef.pos_score = P; ef.A = w.A; ef.asq = l2g ? w.asq : nullptr;
-        if (model == KGE_TRANSR) {
-            RescalMatvecArgs m{};
-            m.B = rows; m.D = d_e; m.Dc = d_r; m.rel = proj; m.ridx = r + e0;
-            m.z1 = ent; m.z1idx = h + e0; m.c1 = w.THP; m.z2 = ent; m.z2idx = t + e0; m.c2 = w.TTP;
-            KGE_TRY(launch_rescal_matvec(m, s));
-        } else if (model == KGE_RESCAL) {
-            RescalMatvecArgs m{};
-            m.B = rows; m.D = d_e; m.rel = rel; m.ridx = r + e0;
-            m.y1 = ent; m.y1idx = t + e0; m.r1 = neg_head ? w.A : w.RV;
-            if (!neg_head) { m.y2 = ent; m.y2idx = h + e0; m.r2 = w.A; }
-            m.pd = ent; m.pdidx = h + e0; m.p = P;
-            KGE_TRY(launch_rescal_matvec(m, s));
-        } else {
-            KGE_TRY(launch_edge_fwd(ef, s));
-        }
+        KGE_TRY(rank_pos_side(model, neg_head, ent, rel, proj, h + e0, r + e0, t + e0, rows, d_e, d_r, gamma, rot_div, P, w.A,
+                              l2g ? w.asq : nullptr, w.RV, w, s));
         if (gemm) {
             if (l2g && (!shared || self_cand)) {
                 ChunkCands c1 = cc; if (shared) c1.cand = nullptr;
@@ -1445,13 +1445,12 @@ int kge_rank_eval_chunked(int model, int neg_head, const float *ent, int64_t n_e
 // ---- relation ranking (kge_rank_rel.hip) ----
 // one batch of Eb test triples: query rows / their norms / positive scores, the relation rows' norms (TransE_l2), the score block or
 // comparison mask, and TransR's projected rows, negated relation rows and identity ids.  The layout does not depend on the flags.
-struct RelBufs { float *Q, *qsq, *P, *csq, *S, *THP, *TTP, *TQ, *TSG, *RQ; int64_t *ids; };
+struct RelBufs : TransRRows { float *Q, *qsq, *P, *csq, *S, *RQ; int64_t *ids; };
 static size_t carve_rank_rel(Carver &cv, RelBufs &w, int model, int Eb, int64_t n_rel, int d_e, int d_r) {
     const size_t qw = model == KGE_ROTATE ? 0 : model == KGE_RESCAL ? (size_t)d_e * d_e : (size_t)d_e;
     w.Q = cv.f((size_t)Eb * qw); w.qsq = cv.f(Eb); w.P = cv.f(Eb); w.csq = cv.f((size_t)n_rel);
     w.S = (float *)cv.bytes(std::max((size_t)Eb * (size_t)n_rel * sizeof(float), rank_gemm_mask_bytes(Eb, n_rel)));
-    const size_t tr = model == KGE_TRANSR ? (size_t)Eb * d_r : 0;
-    w.THP = cv.f(tr); w.TTP = cv.f(tr); w.TQ = cv.f(tr); w.TSG = cv.f(tr);
+    carve_transr_rows(cv, w, model == KGE_TRANSR ? (size_t)Eb * d_r : 0);
     w.RQ = cv.f(model == KGE_TRANSR ? (size_t)n_rel * d_r : 0);
     w.ids = cv.i64(model == KGE_TRANSR ? std::max((size_t)n_rel, (size_t)Eb) : 0);
     return cv.off;
@@ -1497,27 +1496,15 @@ int kge_rank_rel_eval(int model, const float *ent, int64_t n_ent, const float *r
     for (int64_t e0 = 0; e0 < E; e0 += Eb) {
         const int rows = (int)((E - e0) < Eb ? (E - e0) : Eb);
         float *P = pos_score_out ? pos_score_out + e0 : w.P;
-        // positive scores: the forward of the true triples, as kge_rank_eval forms them
+        // positive scores: the forward of the true triples, as kge_rank_eval forms them (no pos-side vectors: the query rows follow)
+        KGE_TRY(rank_pos_side(model, 0, ent, rel, proj, h + e0, r + e0, t + e0, rows, d_e, d_r, gamma, rot_div, P, nullptr, nullptr,
+                              nullptr, w, s));
         if (model == KGE_TRANSR) {
-            RescalMatvecArgs m{};
-            m.B = rows; m.D = d_e; m.Dc = d_r; m.rel = proj; m.ridx = r + e0;
-            m.z1 = ent; m.z1idx = h + e0; m.c1 = w.THP; m.z2 = ent; m.z2idx = t + e0; m.c2 = w.TTP;
-            KGE_TRY(launch_rescal_matvec(m, s));
             TransRArgs tp{};
             tp.B = rows; tp.C = 1; tp.chunk = rows; tp.De = d_e; tp.Dr = d_r; tp.gamma = gamma; tp.ent = ent;
             tp.h_gid = h + e0; tp.t_gid = t + e0; tp.rel_ids = r + e0; tp.rel = rel; tp.proj = const_cast<float *>(proj);
             tp.HP = w.THP; tp.TP = w.TTP; tp.Q = w.TQ; tp.SG = w.TSG; tp.P = P;
             KGE_TRY(launch_transr_pos(tp, s));
-        } else if (model == KGE_RESCAL) {
-            RescalMatvecArgs m{};
-            m.B = rows; m.D = d_e; m.rel = rel; m.ridx = r + e0;
-            m.y1 = ent; m.y1idx = t + e0; m.pd = ent; m.pdidx = h + e0; m.p = P;
-            KGE_TRY(launch_rescal_matvec(m, s));
-        } else {
-            EdgeFwdArgs ef;
-            fill_edge(ef, EdgeSrc{ent, h + e0, ent, t + e0, rel, r + e0}, model, rows, d_e, d_r, 0, gamma, rot_div);
-            ef.pos_score = P;
-            KGE_TRY(launch_edge_fwd(ef, s));
         }
         if (model == KGE_ROTATE) {
             KGE_TRY(launch_rel_rotate_score(ent, rel, h + e0, t + e0, rows, n_rel, d_e, gamma, rot_div, w.S, s));
@@ -1533,7 +1520,7 @@ int kge_rank_rel_eval(int model, const float *ent, int64_t n_ent, const float *r
             tr.ent = w.Q; tr.cent = w.Q; tr.neg_ids = w.ids; tr.rel_ids = w.ids; tr.rel = rel; tr.proj = const_cast<float *>(proj);
             tr.Q = w.RQ; tr.S = w.S; tr.Z = nullptr;
             KGE_TRY(launch_transr_fwd(tr, s));
-            KGE_TRY(launch_rel_count_t(w.S, P, rows, n_rel, filt_ptr, filt_ids, e0, ranks, s));
+            KGE_TRY(launch_rank_count(w.S, P, rows, n_rel, filt_ptr, filt_ids, e0, ranks, s, true));
         } else if (gemm) {
             KGE_TRY(launch_rank_gemm(form, w.Q, rows, rel, nullptr, n_rel, D, gamma, clamp_of(model), w.qsq, w.csq, P, w.S, filt_ptr,
                                      filt_ids, e0, ranks, s));

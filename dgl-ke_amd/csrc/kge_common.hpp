@@ -11,7 +11,8 @@
 #define KGE_WAVES_PER_BLOCK (KGE_BLOCK / KGE_WAVE)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
+// c += a b over one 16 x 16 x 4 fp32 matrix-core tile
+#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 // ---- developer timeline (build with -DKGE_TIMELINE; tools/timeline.py): every wavefront of the step's kernels
 // records {kernel id | hardware id, start, end} (100 MHz wall clock) into a per-translation-unit device buffer
@@ -64,6 +65,9 @@ struct KgeTlScope {
 
 namespace kge {
 
+// after a kernel launch: did the launch itself fail (bad configuration, no code object)?
+static inline int check_launch() { return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH; }
+
 // Wavefront reductions on DPP (data-parallel primitives: the cross-lane operand is part of the VALU
 // instruction) + v_readlane, instead of __shfl_xor butterflies: a shuffle compiles to ds_bpermute_b32 - an
 // LDS-crossbar round trip of >100 cycles - and a 64-lane butterfly is a dependent chain of six of them; with
@@ -100,6 +104,33 @@ __device__ __forceinline__ float wave_sum(float v) {
 __device__ __forceinline__ float wave_max(float v) {
     v = row_max16(v);
     return fmaxf(fmaxf(readlane_f(v, 0), readlane_f(v, 16)), fmaxf(readlane_f(v, 32), readlane_f(v, 48)));
+}
+
+// thread 0 of the workgroup runs done(sum of cnt over the workgroup's KGE_BLOCK threads).  One use per kernel: the partials' LDS words
+// are not fenced for a second round.
+template <class F>
+__device__ __forceinline__ void block_count_sum(int cnt, const F &done) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    __shared__ int part[KGE_WAVES_PER_BLOCK];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+#pragma unroll
+        for (int w = 0; w < KGE_WAVES_PER_BLOCK; ++w) tot += part[w];
+        done(tot);
+    }
+}
+
+// id in p[lo .. end) (ascending, unique) ?
+__device__ __forceinline__ bool in_sorted(const int64_t *__restrict__ p, int64_t lo, const int64_t end, int64_t id) {
+    int64_t hi = end;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (p[mid] < id) lo = mid + 1; else hi = mid;
+    }
+    return lo < end && p[lo] == id;
 }
 
 // row pointer with optional one-level indirection: base + (idx ? idx[i] : i) * ld
@@ -502,7 +533,8 @@ int launch_pnorm_bwd(const float *x, int64_t total, int p, const float *gout, fl
 int launch_mask_diag(float *x, int C, int chunk, int Np, hipStream_t s);
 int launch_rank_mask(const float *neg, const float *pos, const float *bias, int64_t E, int64_t N, int64_t *ranks, hipStream_t s);
 int launch_rank_count(const float *S, const float *P, int rows, int64_t N, const int64_t *filt_ptr,
-                      const int64_t *filt_ids, int64_t e0, int32_t *ranks, hipStream_t s);
+                      const int64_t *filt_ids, int64_t e0, int32_t *ranks, hipStream_t s,
+                      bool transposed = false);          // transposed: S is [N, rows]
 bool rank_gemm_supported(int model, int d_e);          // kge_rank_gemm.hip: LDS-tiled fp32-MFMA ranking of the matrix-form models
 size_t rank_gemm_mask_bytes(int rows, int64_t N);
 int launch_rank_gemm(int model, const float *A, int rows, const float *nbase, const int64_t *nidx, int64_t N, int D, float gamma,
@@ -529,8 +561,6 @@ int launch_rel_query(int model, const float *ent, const int64_t *h, const int64_
 int launch_rel_rotate_score(const float *ent, const float *rel, const int64_t *h, const int64_t *t, int rows, int64_t n_rel, int d_e,
                             float gamma, float rot_div, float *S, hipStream_t s);      // S [rows, n_rel]
 int launch_rel_neg_rows(const float *rel, int64_t n_rel, int d_r, float *out, int64_t *ids, int64_t n_ids, hipStream_t s);   // -rel, iota
-int launch_rel_count_t(const float *St, const float *P, int rows, int64_t N, const int64_t *filt_ptr, const int64_t *filt_ids,
-                       int64_t e0, int32_t *ranks, hipStream_t s);                     // launch_rank_count over St [N, rows]
 struct GemmArgs {                   // LDS-staged fp32-MFMA negative scoring (kge_neg_gemm.hip)
     int model, C, chunk, N, D;
     float gamma;

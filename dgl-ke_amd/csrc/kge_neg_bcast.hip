@@ -29,7 +29,6 @@ KGE_TL_DEFINE(bcast)
 #define SB_RWR 4                                 // forward, real models: uniform rows per wavefront
 #define SB_RWC 4                                 // forward, RotatE: uniform rows per wavefront (2: 19.4 us, 4: 16.4 us)
 
-static inline int check_launch_b() { return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH; }
 
 __device__ __forceinline__ float fast_sqrt(float x) { return __builtin_amdgcn_sqrtf(x); }   // v_sqrt_f32 (1 ulp)
 __device__ __forceinline__ float fast_rsq(float x) { return __builtin_amdgcn_rsqf(x); }     // v_rsq_f32
@@ -471,7 +470,7 @@ int launch_neg_fwd_bcast_with_edge(const NegArgs &a, const EdgeFwdArgs &e, hipSt
     const bool lean = e.lp.genre == KGE_LOSS_LOGSIGMOID && !e.row_pos && !e.Hc;
     if (lean) hipLaunchKernelGGL(neg_fwd_bcast_edge_kernel<true>, dim3(nbF + nbP), dim3(SB_FWD_BLOCK), 0, s, a, ns, ng, nbF, ee);
     else hipLaunchKernelGGL(neg_fwd_bcast_edge_kernel<false>, dim3(nbF + nbP), dim3(SB_FWD_BLOCK), 0, s, a, ns, ng, nbF, ee);
-    return check_launch_b();
+    return check_launch();
 }
 
 template <int MODEL> static int fwd_launch(const NegArgs &a, hipStream_t s) {
@@ -483,11 +482,11 @@ template <int MODEL> static int fwd_launch(const NegArgs &a, hipStream_t s) {
         // staged-row instance: the tasks of a workgroup share their strip (ng % SB_TPB == 0) and a stage of 16 columns exists
         if (ng % SB_TPB == 0 && a.d_e / 2 >= SB_XST && (a.d_e / 2) % 4 == 0) {
             hipLaunchKernelGGL(neg_fwd_rot_xlds_kernel, dim3((unsigned)nb), dim3(SB_FWD_BLOCK), 0, s, a, ns, ng);
-            return check_launch_b();
+            return check_launch();
         }
     }
     hipLaunchKernelGGL(neg_fwd_bcast_kernel<MODEL>, dim3((unsigned)nb), dim3(SB_FWD_BLOCK), 0, s, a, ns, ng);
-    return check_launch_b();
+    return check_launch();
 }
 
 int launch_neg_fwd_bcast(const NegArgs &a, hipStream_t s) {
@@ -1049,22 +1048,22 @@ template <int MODEL> static int lc_launch(const NegArgs &a, hipStream_t s) {
             if (rpw <= 8) hipLaunchKernelGGL((neg_bwd_lc_kernel<MODEL, 8, 8>), g, b8, 0, s, a_, nslab, nrw, rpw);
             else if (rpw <= 12) hipLaunchKernelGGL((neg_bwd_lc_kernel<MODEL, 12, 8>), g, b8, 0, s, a_, nslab, nrw, rpw);
             else hipLaunchKernelGGL((neg_bwd_lc_kernel<MODEL, 16, 8>), g, b8, 0, s, a_, nslab, nrw, rpw);
-            if (int rc = check_launch_b()) return rc;
+            if (int rc = check_launch()) return rc;
             if (a.defer_reduce) return KGE_OK;
             const int64_t n4w = (int64_t)a.C * a.N * a.d_e / 4 + (a.ga_parts > 1 ? (int64_t)a.C * a.chunk * a.d_e / 4 : 0);
             hipLaunchKernelGGL(gn_reduce_kernel, dim3((unsigned)((n4w + KGE_BLOCK - 1) / KGE_BLOCK)), dim3(KGE_BLOCK), 0, s, a, nrw);
-            return check_launch_b();
+            return check_launch();
         }
     }
     if (rpw <= 8) hipLaunchKernelGGL((neg_bwd_lc_kernel<MODEL, 8>), g, b, 0, s, a_, nslab, nrw, rpw);
     else if (rpw <= 12) hipLaunchKernelGGL((neg_bwd_lc_kernel<MODEL, 12>), g, b, 0, s, a_, nslab, nrw, rpw);
     else if (rpw <= 16) hipLaunchKernelGGL((neg_bwd_lc_kernel<MODEL, 16>), g, b, 0, s, a_, nslab, nrw, rpw);
     else if constexpr (MODEL != KGE_ROTATE) hipLaunchKernelGGL((neg_bwd_lc_kernel<MODEL, LC_RTMAX>), g, b, 0, s, a_, nslab, nrw, rpw);
-    if (int rc = check_launch_b()) return rc;
+    if (int rc = check_launch()) return rc;
     if (a.defer_reduce) return KGE_OK;           // the caller sums the partials in its next launch (launch_edge_bwd_with_gn_reduce)
     const int64_t n4 = (int64_t)a.C * a.N * a.d_e / 4 + (a.ga_parts > 1 ? (int64_t)a.C * a.chunk * a.d_e / 4 : 0);
     hipLaunchKernelGGL(gn_reduce_kernel, dim3((unsigned)((n4 + KGE_BLOCK - 1) / KGE_BLOCK)), dim3(KGE_BLOCK), 0, s, a, nrw);
-    return check_launch_b();
+    return check_launch();
 }
 
 template <int MODEL> static int bwd_launch(const NegArgs &a, hipStream_t s) {
@@ -1077,7 +1076,7 @@ template <int MODEL> static int bwd_launch(const NegArgs &a, hipStream_t s) {
     const bool vecw = a.N % 4 == 0 && a.N % GS == 0 && a.N >= GS;
     if (vecw) hipLaunchKernelGGL((neg_bwd_bcast_kernel<MODEL, true>), dim3((unsigned)nb), dim3(KGE_BLOCK), 0, s, a, nsA, nsN);
     else hipLaunchKernelGGL((neg_bwd_bcast_kernel<MODEL, false>), dim3((unsigned)nb), dim3(KGE_BLOCK), 0, s, a, nsA, nsN);
-    return check_launch_b();
+    return check_launch();
 }
 
 int launch_neg_bwd_bcast(const NegArgs &a, hipStream_t s) {

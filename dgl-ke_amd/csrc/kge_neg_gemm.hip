@@ -45,7 +45,6 @@
 using namespace kge;
 KGE_TL_DEFINE(gemm)
 
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 // program order is kept across this point: loads by the compiler-level memory barrier, everything else by the scheduling barrier
 // MFMAs are pure values without a place in program order: the accumulators go through an empty volatile asm (AGPR operands, no
 // instruction) so that the MFMAs producing them stay BEFORE this point
@@ -62,7 +61,6 @@ bool neg_mfma_supported(int model, int d_e, int N) {
 // the fused loss keeps a [chunk][tiles] factor table in LDS and combines <= 16 partials per row in registers
 bool neg_gemm_fused_loss_supported(int chunk, int N) { return N <= 256 && chunk <= 768; }
 
-static inline int check_launch_g() { return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH; }
 __device__ __forceinline__ float4 ldg4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ float sq4(const float4 &v) { return v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w; }
@@ -702,7 +700,7 @@ int launch_neg_fwd_gemm_with_edge(const GemmArgs &a, const EdgeFwdArgs &e, hipSt
 #undef KGE_FE
 #undef KGE_FE2
 #undef KGE_FE_H
-    return check_launch_g();
+    return check_launch();
 }
 
 // loss rows inside the first launch: LDS-tile instance only, one register-resident score row per wavefront (N <= 256), every
@@ -737,7 +735,7 @@ int launch_neg_fwd_gemm_with_edge_loss(const GemmArgs &a, const EdgeFwdArgs &e, 
     else if (a.model == KGE_TRANSE_L2) KGE_FL(1, KGE_TRANSE_L2);
     else KGE_FL(2, KGE_DISTMULT);
 #undef KGE_FL
-    return check_launch_g();
+    return check_launch();
 }
 
 int launch_neg_fwd_gemm(const GemmArgs &a, hipStream_t s) {
@@ -751,7 +749,7 @@ int launch_neg_fwd_gemm(const GemmArgs &a, hipStream_t s) {
     else if (l2) hipLaunchKernelGGL((neg_fwd_gemm_kernel<true, false>), g, b, 0, s, a, ti, tj);
     else if (st) hipLaunchKernelGGL((neg_fwd_gemm_kernel<false, true>), g, b, 0, s, a, ti, tj);
     else hipLaunchKernelGGL((neg_fwd_gemm_kernel<false, false>), g, b, 0, s, a, ti, tj);
-    return check_launch_g();
+    return check_launch();
 }
 
 // =============================================================================================
@@ -1329,22 +1327,22 @@ int launch_neg_bwd_gemm(const GemmArgs &a, hipStream_t s, const SmpTail *tail) {
                 else hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, false, 3>), gc, b, sm, s, KGE_BG_H(bpAc, nbc));
             } else if (!a.nidx) hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, true, 2>), gc, b, 0, s, KGE_BG_H(bpAc, nbc));
             else hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, false, 2>), gc, b, sm, s, KGE_BG_H(bpAc, nbc));
-            return check_launch_g();
+            return check_launch();
         }
         if (!a.nidx) hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, true, 1>), g, b, 0, s, KGE_BG_H(bpA, nb));
         else hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, false, 1>), g, b, sm, s, KGE_BG_H(bpA, nb));
-        return check_launch_g();
+        return check_launch();
     }
     if (!fact && !a.nidx) {                                      // dense operands: the instance without index table / LDS / barrier
         if (l2) hipLaunchKernelGGL((neg_bwd_gemm_kernel<true, false, true>), g, b, 0, s, KGE_BG_H(bpA, nb));
         else hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false, true>), g, b, 0, s, KGE_BG_H(bpA, nb));
-        return check_launch_g();
+        return check_launch();
     }
     if (l2 && fact) hipLaunchKernelGGL((neg_bwd_gemm_kernel<true, true>), g, b, sm, s, KGE_BG_H(bpA, nb));
     else if (l2) hipLaunchKernelGGL((neg_bwd_gemm_kernel<true, false>), g, b, sm, s, KGE_BG_H(bpA, nb));
     else if (fact) hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, true>), g, b, sm, s, KGE_BG_H(bpA, nb));
     else hipLaunchKernelGGL((neg_bwd_gemm_kernel<false, false>), g, b, sm, s, KGE_BG_H(bpA, nb));
-    return check_launch_g();
+    return check_launch();
 }
 #undef KGE_BG_H
 
@@ -1376,7 +1374,7 @@ int launch_neg_fwd_gemm_with_update(const GemmArgs &a, const UpdateArgs &u, hipS
     if (nit == 1) KGE_FU_N(1); else if (nit == 2) KGE_FU_N(2); else KGE_FU_N(4);
 #undef KGE_FU_N
 #undef KGE_FU
-    return check_launch_g();
+    return check_launch();
 }
 
 // backward GEMM of one step + PREP (edge forward) of the NEXT step in one launch (neg_bwd_prep_kernel).
@@ -1410,5 +1408,5 @@ int launch_neg_bwd_gemm_with_prep(const GemmArgs &a, const EdgeFwdArgs &e, hipSt
     else if (a.model == KGE_SIMPLE && e.model == KGE_SIMPLE) KGE_BP(false, KGE_SIMPLE);
     else return KGE_ERR_ARG;
 #undef KGE_BP
-    return check_launch_g();
+    return check_launch();
 }

@@ -13,9 +13,6 @@
 
 using namespace kge;
 
-static inline int check_launch_p() {
-    return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
-}
 
 #define PT 32          // tile edge (rows and cols of the output tile)
 #define PK 32          // k-slab
@@ -143,7 +140,7 @@ int launch_neg_fwd_pair(const NegArgs &a, hipStream_t s) {
             hipLaunchKernelGGL(neg_fwd_pair_kernel<KGE_ROTATE>, dim3(nb), dim3(KGE_BLOCK), 0, s, a, ti, tj); break;
         default: return KGE_ERR_ARG;
     }
-    return check_launch_p();
+    return check_launch();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -308,5 +305,5 @@ int launch_neg_bwd_pair(const NegArgs &a, hipStream_t s) {
             hipLaunchKernelGGL(neg_bwd_pair_kernel<KGE_ROTATE>, dim3(nb), dim3(KGE_BLOCK), 0, s, a, ti, tj, tk); break;
         default: return KGE_ERR_ARG;
     }
-    return check_launch_p();
+    return check_launch();
 }

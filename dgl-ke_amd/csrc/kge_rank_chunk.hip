@@ -10,21 +10,20 @@
 // is the smallest the 16 x 16 x 4 MFMA has, and at the default chunk of 8 a 128-row tile would spend 15/16 of the matrix pipe on
 // padding.  Every wavefront owns 64 candidates of all the tile's rows (4 or 16 independent accumulators); k runs in table order in
 // stages of 32 through LDS with the same MFMA sequence per (row, candidate) as rank_gemm_kernel: a score does not depend on how
-// the rows are grouped into chunks, tiles or blocks.  The epilogue forms the score as rank_gemm_kernel does, compares it with the
-// row's positive score, looks a candidate that counts up in the row's filter list (entity ids, binary search) and adds the
-// tile's counts to the ranks with integer atomics: no [rows, candidates] block, no mask.
+// the rows are grouped into chunks, tiles or blocks.  The main loop is its own and not kge_tile_gemm.hpp's: a single LDS buffer and
+// an MI x 256 tile with all wavefronts across the candidates, for chunks far smaller than that loop's 128 rows.  The epilogue forms
+// the score with the same tile_score as rank_gemm_kernel, compares it with the row's positive score, looks a candidate that counts
+// up in the row's filter list (entity ids, binary search) and adds the tile's counts to the ranks with integer atomics: no
+// [rows, candidates] block, no mask.
 // The other models and KGE_FLAG_FORCE_PAIRWISE: the training kernels' chunked negative scores into a block (kge_api.hip) over
 // the id list chunk_ids_kernel lays out, then chunk_count_kernel.
-#include "kge_common.hpp"
+#include "kge_tile_gemm.hpp"
 
 using namespace kge;
 
 #define RC_BN 256
 #define RC_BK 32                                  // (the stage loop below is written for two 16-k halves)
 #define RC_LD (RC_BK + 4)                         // dwords per staged row: 4 x odd, conflict-free fragment reads
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-
-static inline int check_launch_c() { return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH; }
 
 // rows of chunk c (the last chunk may be short)
 __device__ __forceinline__ int chunk_rows(const ChunkCands &cc, int64_t c) {
@@ -41,15 +40,6 @@ __device__ __forceinline__ int64_t chunk_cand_id(const ChunkCands &cc, int64_t c
         id = cc.cand ? cc.cand[c * cc.stride + j] : j;
     }
     return (id >= 0 && id < cc.n_ent) ? id : -1;
-}
-// x in ids[lo, hi) (ascending, unique)
-__device__ __forceinline__ bool in_list(const int64_t *__restrict__ ids, int64_t lo, int64_t hi, int64_t x) {
-    const int64_t end = hi;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (ids[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo < end && ids[lo] == x;
 }
 
 // |b|^2 of the candidate rows, one wavefront per slot: slots [0, rows) = the own entities of the block's rows (cc.own),
@@ -208,12 +198,10 @@ __global__ __launch_bounds__(256) void rank_chunk_gemm_kernel(RankChunkArgs a) {
             int cnt = 0;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                float x = acc[i][j][r];
-                if (a.l2) x = a.gamma - sqrtf(fmaxf(fmaf(-2.f, x, as + bs[j]), 1e-30f));
-                else if (a.clampv > 0.f) x = fminf(fmaxf(x, -a.clampv), a.clampv);
+                float x = tile_score(acc[i][j][r], a.l2, a.gamma, as, bs[j], a.clampv);
                 if (cc.own && colj[j] == lrow) x = 0.f;                 // the triple's own column: mask[:, 0::(N+1)] = 0
                 bool hit = rok && cid[j] >= 0 && x >= p;
-                if (hit && f1 > f0) hit = !in_list(a.filt_ids, f0, f1, cid[j]);
+                if (hit && f1 > f0) hit = !in_sorted(a.filt_ids, f0, f1, cid[j]);
                 cnt += hit ? 1 : 0;
             }
             if (cnt) atomicAdd(&rcnt[16 * i + 4 * q + r], cnt);
@@ -232,7 +220,7 @@ int launch_chunk_bsq(const ChunkCands &cc, int64_t c0, int rows, int64_t n_list,
     if (n <= 0) return KGE_OK;
     hipLaunchKernelGGL(chunk_bsq_kernel, dim3((unsigned)((n + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK)), dim3(KGE_BLOCK), 0, s, cc, c0,
                        rows, n_list, ent, D, bsq_own, bsq_c);
-    return check_launch_c();
+    return check_launch();
 }
 
 // chunks [c0, c0 + nch): ranks[e] += #{counting candidates}; A / asq / P: the block's rows (edge_fwd / rescal_matvec)
@@ -253,7 +241,7 @@ int launch_rank_chunk_gemm(int model, const ChunkCands &cc, int64_t c0, int nch,
     if (nb > 0x7fffffff) return KGE_ERR_ARG;
     if (wide) hipLaunchKernelGGL(rank_chunk_gemm_kernel<4>, dim3((unsigned)nb), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(rank_chunk_gemm_kernel<1>, dim3((unsigned)nb), dim3(256), 0, s, a);
-    return check_launch_c();
+    return check_launch();
 }
 
 // ---- the score-block route ---------------------------------------------------------------------------------------------------------
@@ -287,27 +275,17 @@ __global__ __launch_bounds__(KGE_BLOCK) void chunk_count_kernel(ChunkCands cc, i
         const int64_t id = chunk_cand_id(cc, c, m, j);
         const float x = (cc.own && j == li) ? 0.f : row[j];
         bool hit = id >= 0 && x >= p;
-        if (hit && f1 > f0) hit = !in_list(filt_ids, f0, f1, id);
+        if (hit && f1 > f0) hit = !in_sorted(filt_ids, f0, f1, id);
         cnt += hit ? 1 : 0;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-    __shared__ int part[KGE_WAVES_PER_BLOCK];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int tot = 0;
-#pragma unroll
-        for (int w = 0; w < KGE_WAVES_PER_BLOCK; ++w) tot += part[w];
-        ranks[e] = 1 + tot;
-    }
+    block_count_sum(cnt, [&](int tot) { ranks[e] = 1 + tot; });
 }
 
 int launch_chunk_ids(const ChunkCands &cc, int64_t cfirst, int nch, int m, int64_t ncols, int64_t *ids, hipStream_t s) {
     const int64_t n = (int64_t)nch * ncols;
     if (n <= 0) return KGE_OK;
     hipLaunchKernelGGL(chunk_ids_kernel, dim3((unsigned)((n + KGE_BLOCK - 1) / KGE_BLOCK)), dim3(KGE_BLOCK), 0, s, cc, cfirst, nch, m, ncols, ids);
-    return check_launch_c();
+    return check_launch();
 }
 
 int launch_chunk_count(const ChunkCands &cc, int64_t cfirst, int nch, int m, int64_t ncols, const float *S, const float *P,
@@ -315,5 +293,5 @@ int launch_chunk_count(const ChunkCands &cc, int64_t cfirst, int nch, int m, int
     const int64_t rows = (int64_t)nch * m;
     if (rows <= 0) return KGE_OK;
     hipLaunchKernelGGL(chunk_count_kernel, dim3((unsigned)rows), dim3(KGE_BLOCK), 0, s, cc, cfirst, m, ncols, S, P, filt_ptr, filt_ids, ranks);
-    return check_launch_c();
+    return check_launch();
 }

@@ -11,14 +11,13 @@
 //     RotatE           -                                           s_j = gamma - sum_k |h_k e^{i theta_jk} - t_k|
 // i.e. for six models the form the entity-ranking kernels already evaluate with the relation table in the place of the entity
 // table (kge_rank_gemm.hip, kge_neg_pair.hip / kge_neg_bcast.hip + kge_eval.hip; sequence in kge_api.hip).  This file holds what
-// they lack: rel_query_kernel (the per-pair query rows), rel_rotate_score_kernel (RotatE over relation phases), rel_neg_rows_kernel
-// and rel_count_t_kernel (TransR: the training forward kge_transr.hip with the roles exchanged - the relations are its "positives",
-// Q_j = -c_j, the batch's u rows its shared "negatives" - leaves a [n_rel, rows] block that is counted transposed).
+// they lack: rel_query_kernel (the per-pair query rows), rel_rotate_score_kernel (RotatE over relation phases) and rel_neg_rows_kernel
+// (TransR: the training forward kge_transr.hip with the roles exchanged - the relations are its "positives", Q_j = -c_j, the batch's
+// u rows its shared "negatives" - leaves a [n_rel, rows] block that rank_count_kernel<true> counts transposed).
 #include "kge_common.hpp"
 
 using namespace kge;
 
-static inline int check_launch_r() { return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH; }
 
 // ---- query rows: one wavefront per test triple ----------------------------------------------------------------------------------------
 struct RelQueryArgs {
@@ -95,7 +94,7 @@ static int launch_rel_query_m(const RelQueryArgs &a, hipStream_t s) {
     const bool vec = halves ? (a.d_e / 2) % 4 == 0 : a.d_e % 4 == 0;
     if (vec) hipLaunchKernelGGL((rel_query_kernel<MODEL, 4>), g, b, 0, s, a);
     else hipLaunchKernelGGL((rel_query_kernel<MODEL, 1>), g, b, 0, s, a);
-    return check_launch_r();
+    return check_launch();
 }
 
 int launch_rel_query(int model, const float *ent, const int64_t *h, const int64_t *t, int rows, int d_e, float *Q, float *qsq,
@@ -209,7 +208,7 @@ int launch_rel_rotate_score(const float *ent, const float *rel, const int64_t *h
     const int64_t nb = (int64_t)((rows + RR_BM - 1) / RR_BM) * a.nbn;
     if (nb > 0x7fffffff) return KGE_ERR_ARG;
     hipLaunchKernelGGL(rel_rotate_score_kernel, dim3((unsigned)nb), dim3(KGE_BLOCK), 0, s, a);
-    return check_launch_r();
+    return check_launch();
 }
 
 // ---- TransR ---------------------------------------------------------------------------------------------------------------------------
@@ -226,44 +225,5 @@ int launch_rel_neg_rows(const float *rel, int64_t n_rel, int d_r, float *out, in
     const int64_t n = n_rel * d_r, m = n > n_ids ? n : n_ids;
     if (m <= 0) return KGE_OK;
     hipLaunchKernelGGL(rel_neg_rows_kernel, dim3((unsigned)((m + KGE_BLOCK - 1) / KGE_BLOCK)), dim3(KGE_BLOCK), 0, s, rel, n, out, ids, n_ids);
-    return check_launch_r();
-}
-
-// rank_count_kernel (kge_eval.hip) over a TRANSPOSED block St [N, rows]: one workgroup per test triple i of the batch,
-//   rank = 1 + #{j : St[j, i] >= p_i} - #{j in filt_i : St[j, i] >= p_i},   filt_i = filt_ids[filt_ptr[2 (e0 + i)] .. [2 (e0 + i) + 1])
-// (the column reads are strided; N = n_rel is small and the block is L2-resident right after the forward that wrote it)
-__global__ __launch_bounds__(KGE_BLOCK) void rel_count_t_kernel(const float *__restrict__ St, const float *__restrict__ P, int rows,
-                                                                int64_t N, const int64_t *__restrict__ filt_ptr,
-                                                                const int64_t *__restrict__ filt_ids, int64_t e0,
-                                                                int32_t *__restrict__ ranks) {
-    const int i = blockIdx.x;
-    const float p = P[i];
-    const float *col = St + i;
-    int cnt = 0;
-    for (int64_t j = threadIdx.x; j < N; j += KGE_BLOCK) cnt += col[j * rows] >= p ? 1 : 0;
-    if (filt_ptr) {
-        const int64_t f0 = filt_ptr[2 * (e0 + i)], f1 = filt_ptr[2 * (e0 + i) + 1];
-        for (int64_t k = f0 + threadIdx.x; k < f1; k += KGE_BLOCK) {
-            const int64_t j = filt_ids[k];
-            if (j >= 0 && j < N) cnt -= col[j * rows] >= p ? 1 : 0;
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-    __shared__ int part[KGE_WAVES_PER_BLOCK];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int tot = 0;
-#pragma unroll
-        for (int w = 0; w < KGE_WAVES_PER_BLOCK; ++w) tot += part[w];
-        ranks[e0 + i] = 1 + tot;
-    }
-}
-
-int launch_rel_count_t(const float *St, const float *P, int rows, int64_t N, const int64_t *filt_ptr, const int64_t *filt_ids,
-                       int64_t e0, int32_t *ranks, hipStream_t s) {
-    if (rows <= 0) return KGE_OK;
-    hipLaunchKernelGGL(rel_count_t_kernel, dim3(rows), dim3(KGE_BLOCK), 0, s, St, P, rows, N, filt_ptr, filt_ids, e0, ranks);
-    return check_launch_r();
+    return check_launch();
 }

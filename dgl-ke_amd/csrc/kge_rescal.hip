@@ -13,7 +13,6 @@
 
 using namespace kge;
 
-static inline int check_launch_r() { return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH; }
 
 // ---------------------------------------------------------------------------------------------
 // one pass over M_i (i = edge): out_r1 = M y1, out_r2 = M y2 (row dots), out_c1 = M^T z1, out_c2 = M^T z2
@@ -196,13 +195,13 @@ int launch_rescal_matvec(const RescalMatvecArgs &a, hipStream_t s) {
         if (cols <= 256) hipLaunchKernelGGL(rescal_matvec4_kernel<1>, g, b, 0, s, a);
         else if (cols <= 512) hipLaunchKernelGGL(rescal_matvec4_kernel<2>, g, b, 0, s, a);
         else hipLaunchKernelGGL(rescal_matvec4_kernel<4>, g, b, 0, s, a);
-        return check_launch_r();
+        return check_launch();
     }
     if (cols <= 256) hipLaunchKernelGGL(rescal_matvec_kernel<4>, g, b, 0, s, a);
     else if (cols <= 512) hipLaunchKernelGGL(rescal_matvec_kernel<8>, g, b, 0, s, a);
     else if (cols <= 1024) hipLaunchKernelGGL(rescal_matvec_kernel<16>, g, b, 0, s, a);
     else return KGE_ERR_ARG;
-    return check_launch_r();
+    return check_launch();
 }
 
 // out_i = s1_i * u1_i (+ u2_i)   (vector combine: GH = dp * (M t) + M^T GA ...), one wavefront per edge
@@ -221,7 +220,7 @@ int launch_rescal_axpy(const float *s1, const float *u1, const float *u2, int B,
     if (B == 0) return KGE_OK;
     hipLaunchKernelGGL(rescal_axpy_kernel, dim3((B + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK), dim3(KGE_BLOCK), 0, s,
                        s1, u1, u2, B, D, out, alpha);
-    return check_launch_r();
+    return check_launch();
 }
 
 // materialised per-edge relation gradient (drop-in / debugging path only):
@@ -247,7 +246,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void rescal_outer_kernel(RescalOuterArgs
 int launch_rescal_outer(const RescalOuterArgs &a, hipStream_t s) {
     if (a.B == 0) return KGE_OK;
     hipLaunchKernelGGL(rescal_outer_kernel, dim3(a.B), dim3(KGE_BLOCK), 0, s, a);
-    return check_launch_r();
+    return check_launch();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -658,7 +657,7 @@ int launch_rescal_rel_fwd(const RescalRelFwdArgs &a, hipStream_t s) {
     else RF(4, 1);
 #undef RF
     hipLaunchKernelGGL(rescal_psum_kernel, dim3((a.B + 255) / 256), dim3(256), 0, s, a);
-    return check_launch_r();
+    return check_launch();
 }
 
 // backward + Adagrad in ONE pass over the row block: the column products M^T h_e and M^T GA_e of every edge of the relation
@@ -826,7 +825,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void rescal_combine_kernel(RescalCombine
 int launch_rescal_combine(const RescalCombineArgs &a, hipStream_t s) {
     if (a.B == 0) return KGE_OK;
     hipLaunchKernelGGL(rescal_combine_kernel, dim3((a.B + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK), dim3(KGE_BLOCK), 0, s, a);
-    return check_launch_r();
+    return check_launch();
 }
 
 __global__ void rescal_reg_finalize_kernel(RescalUpdateArgs a) {
@@ -866,5 +865,5 @@ int launch_rescal_update_rel(const RescalUpdateArgs &a, hipStream_t s) {
     else hipLaunchKernelGGL(rescal_apply_kernel<4>, ga, ba, 0, s, a);
     if (a.reg_part && (a.reg_rel || a.acc))
         hipLaunchKernelGGL(rescal_reg_finalize_kernel, dim3((a.UR + 255) / 256), dim3(256), 0, s, a);
-    return check_launch_r();
+    return check_launch();
 }

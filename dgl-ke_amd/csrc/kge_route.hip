@@ -12,7 +12,6 @@
 
 using namespace kge;
 
-static inline int check_launch_r() { return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH; }
 int kge_fail(int code, const char *msg);          // kge_api.hip: records the message kge_last_error() returns
 
 #define RT_THREADS 256
@@ -320,7 +319,7 @@ int kge_route_build(const kge_batch *b, int world, int64_t rows_per_shard, int c
     const int items = a.UEmax > world * cap ? a.UEmax : world * cap;
     hipLaunchKernelGGL(route_build_kernel, dim3((items + RT_THREADS - 1) / RT_THREADS), dim3(RT_THREADS), 0, (hipStream_t)stream, a,
                        (int64_t)0, (int64_t)0);
-    return check_launch_r();
+    return check_launch();
 }
 
 int kge_route_build_group(const kge_batch *b0, int n_batches, size_t in_stride_bytes, int world, int64_t rows_per_shard, int cap,
@@ -340,7 +339,7 @@ int kge_route_build_group(const kge_batch *b0, int n_batches, size_t in_stride_b
     const int items = a.UEmax > world * cap ? a.UEmax : world * cap;
     hipLaunchKernelGGL(route_build_kernel, dim3((items + RT_THREADS - 1) / RT_THREADS, n_batches), dim3(RT_THREADS), 0, (hipStream_t)stream,
                        a, (int64_t)in_stride_bytes, (int64_t)out_stride_bytes);
-    return check_launch_r();
+    return check_launch();
 }
 
 int kge_route_fill(const kge_batch *b0, int n_batches, size_t stride_bytes, int world, int64_t rows_per_shard, int32_t *max_fill,
@@ -351,7 +350,7 @@ int kge_route_fill(const kge_batch *b0, int n_batches, size_t stride_bytes, int 
     hipLaunchKernelGGL(route_fill_kernel, dim3(n_batches), dim3(RT_THREADS), 0, (hipStream_t)stream,
                        reinterpret_cast<const char *>(b0->ue_id), reinterpret_cast<const char *>(b0->counts_dev),
                        reinterpret_cast<const char *>(b0->ue_rec), (int64_t)stride_bytes, b0->UE, world, rows_per_shard, max_fill);
-    return check_launch_r();
+    return check_launch();
 }
 
 int kge_batch_localized(const kge_batch *b, const int64_t *h_loc, const int64_t *t_loc, const int64_t *neg_loc,
@@ -371,7 +370,7 @@ int kge_gather_rows_req(const float *table, int64_t n_rows, int dim, const int64
         hipLaunchKernelGGL(gather_req_kernel<4>, dim3(nb), dim3(KGE_BLOCK), 0, (hipStream_t)stream, table, dim, ids, id_offset, n_rows, n_ids, out);
     else
         hipLaunchKernelGGL(gather_req_kernel<1>, dim3(nb), dim3(KGE_BLOCK), 0, (hipStream_t)stream, table, dim, ids, id_offset, n_rows, n_ids, out);
-    return check_launch_r();
+    return check_launch();
 }
 
 static int merge_args(MergeArgs &a, const kge_merge_job *j, float lr, float eps) {
@@ -399,7 +398,7 @@ int kge_adagrad_apply_merged_pair(const kge_merge_job *ja, const kge_merge_job *
     if (dmax <= 256) hipLaunchKernelGGL(apply_merged_pair_kernel<1>, g, bl, 0, (hipStream_t)stream, a, b, nbA);
     else if (dmax <= 512) hipLaunchKernelGGL(apply_merged_pair_kernel<2>, g, bl, 0, (hipStream_t)stream, a, b, nbA);
     else hipLaunchKernelGGL(apply_merged_pair_kernel<4>, g, bl, 0, (hipStream_t)stream, a, b, nbA);
-    return check_launch_r();
+    return check_launch();
 }
 
 int kge_adagrad_apply_merged(float *table, float *state_sum, int64_t n_rows, int dim, int nsrc, int cap, const int32_t *id_words,
@@ -417,7 +416,7 @@ int kge_adagrad_apply_merged(float *table, float *state_sum, int64_t n_rows, int
     if (dim <= 256) hipLaunchKernelGGL(apply_merged_kernel<1>, g, bl, 0, (hipStream_t)stream, a);
     else if (dim <= 512) hipLaunchKernelGGL(apply_merged_kernel<2>, g, bl, 0, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(apply_merged_kernel<4>, g, bl, 0, (hipStream_t)stream, a);
-    return check_launch_r();
+    return check_launch();
 }
 
 }  // extern "C"

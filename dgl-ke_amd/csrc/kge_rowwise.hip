@@ -22,9 +22,6 @@ KGE_TL_DEFINE(rowwise)
 static inline int blocks_for_waves(int64_t waves) {
     return (int)((waves + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK);
 }
-static inline int check_launch() {
-    return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH;
-}
 
 // ------------------------------------------------------------------------------------------
 // gather

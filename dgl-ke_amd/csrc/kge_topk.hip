@@ -2,8 +2,8 @@
 // EmbSimInfer, models/infer.py:52-344) without a score block in memory.
 //
 //   * topk_select_kernel: workgroup = 128 query rows x one SEGMENT of the candidate list, walked in 128-candidate tiles in
-//     increasing index order.  A tile's scores come from the rank_gemm_kernel main loop (k stages of 32 through LDS, 16x16x4
-//     fp32 MFMA, kge_rank_gemm.hip) for the matrix forms, or from a VALU loop over the same staging for the pairwise forms
+//     increasing index order.  A tile's scores come from the main loop rank_gemm_kernel runs (k stages of 32 through LDS, 16x16x4
+//     fp32 MFMA, kge_tile_gemm.hpp) for the matrix forms, or from a VALU loop over the same staging for the pairwise forms
 //     (TransE_l1, RotatE, l1 and any D that is not a multiple of 4).  The tile goes to LDS; each wavefront then walks its 32
 //     rows: one compare against the row's running K-th best and one ballot per score.  Survivors are merged into the row's
 //     list (in the workspace, sorted) by rank counting in a per-wavefront LDS queue.  Entries are 64-bit composites
@@ -22,16 +22,11 @@
 #include <cmath>
 #include <cstdio>
 #include <type_traits>
-#include "kge_common.hpp"
+#include "kge_tile_gemm.hpp"
 
 using namespace kge;
 
-#define TK_BM 128
-#define TK_BN 128
-#define TK_BK 32
-#define TK_LD (TK_BK + 4)
 #define TK_MCAP 2048                              // entries of one merge workgroup
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 // accumulator kinds (template) and epilogues (runtime)
 enum { ACC_MFMA = 0, ACC_DOT = 1, ACC_SQ = 2, ACC_L1 = 3, ACC_ROT = 4 };
@@ -72,20 +67,9 @@ __device__ __forceinline__ int64_t lane_bcast(int64_t v, int x) {               
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((unsigned long long)v >> 32), x);
     return (int64_t)(((unsigned long long)hi << 32) | lo);
 }
-__device__ __forceinline__ bool in_sorted(const int64_t *p, int64_t lo, const int64_t end, int64_t id) {   // id in p[lo .. end) ?
-    int64_t hi = end;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (p[mid] < id) lo = mid + 1; else hi = mid;
-    }
-    return lo < end && p[lo] == id;
-}
-
-static inline int check_launch_t() { return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH; }
-
 __device__ __forceinline__ float epilogue(const TopkSelArgs &a, float x, int64_t row, int64_t col) {
     switch (a.epi) {
-    case EPI_L2G: return a.gamma - sqrtf(fmaxf(fmaf(-2.f, x, a.an[row] + a.bn[col]), 1e-30f));
+    case EPI_L2G: return l2_score(x, a.gamma, a.an[row], a.bn[col]);
     case EPI_COS: return x / (a.an[row] * a.bn[col]);
     case EPI_JAC: return x / (a.an[row] + a.bn[col] - x);
     case EPI_GMINUS: return a.gamma - x;
@@ -97,97 +81,37 @@ __device__ __forceinline__ float epilogue(const TopkSelArgs &a, float x, int64_t
 template <int ACC, class Args = TopkSelArgs>
 __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
     constexpr bool FILT = !std::is_same<Args, TopkSelArgs>::value;
-    __shared__ __attribute__((aligned(16))) float lds[2][(TK_BM + TK_BN) * TK_LD];
-    __shared__ unsigned long long rthr[TK_BM];
+    __shared__ __attribute__((aligned(16))) float lds[2][(TILE_BM + TILE_BN) * TILE_LD];
+    __shared__ unsigned long long rthr[TILE_BM];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int rb = (int)blockIdx.x / a.S, seg = (int)blockIdx.x % a.S;
-    const int64_t nbn = (a.N + TK_BN - 1) / TK_BN, tps = (nbn + a.S - 1) / a.S;
+    const int64_t nbn = (a.N + TILE_BN - 1) / TILE_BN, tps = (nbn + a.S - 1) / a.S;
     const int64_t tile0 = (int64_t)seg * tps, tile1 = min(nbn, tile0 + tps);
-    const int r0 = rb * TK_BM, D = a.D, K = a.K;
+    const int r0 = rb * TILE_BM, D = a.D, K = a.K;
     float *sc = &lds[0][0];                                                    // [128][128] score tile (after the main loop)
-    unsigned long long *un = reinterpret_cast<unsigned long long *>(&lds[0][0] + TK_BM * TK_BN) + wave * 256;
-    for (int e = tid; e < TK_BM * K; e += 256) {
+    unsigned long long *un = reinterpret_cast<unsigned long long *>(&lds[0][0] + TILE_BM * TILE_BN) + wave * 256;
+    for (int e = tid; e < TILE_BM * K; e += 256) {
         const int lr = e / K;
         if (r0 + lr < a.rows) a.part[((int64_t)(r0 + lr) * a.S + seg) * K + e % K] = 0ull;
     }
-    if (tid < TK_BM) rthr[tid] = 0ull;
+    if (tid < TILE_BM) rthr[tid] = 0ull;
     const int64_t *frng = nullptr;                                             // [128][2]: the rows' list ranges (filtered form)
     if constexpr (FILT) {
-        __shared__ int64_t frng_lds[TK_BM * 2];
-        if (tid < TK_BM * 2) frng_lds[tid] = a.filt_ptr[2 * (int64_t)min(r0 + (tid >> 1), a.rows - 1) + (tid & 1)];
+        __shared__ int64_t frng_lds[TILE_BM * 2];
+        if (tid < TILE_BM * 2) frng_lds[tid] = a.filt_ptr[2 * (int64_t)min(r0 + (tid >> 1), a.rows - 1) + (tid & 1)];
         frng = frng_lds;
     }
     __syncthreads();
     for (int64_t bn = tile0; bn < tile1; ++bn) {
         if constexpr (ACC == ACC_MFMA) {
-            // ---- a copy of the rank_gemm_kernel main loop (kge_rank_gemm.hip; a fix to one belongs in both), D % 4 == 0 ------
-            const int nst = (D + TK_BK - 1) / TK_BK;
-            const int c4t = (tid & 7) * 4;
-            const float *gp[8];
-            int lo[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int f = tid + 256 * i, row = f >> 3, c4 = (f & 7) * 4;
-                if (row < TK_BM) gp[i] = row_ptr(a.abase, a.aidx, min(r0 + row, a.rows - 1), D) + c4;
-                else gp[i] = row_ptr(a.nbase, a.nidx, min(bn * TK_BN + row - TK_BM, a.N - 1), D) + c4;
-                lo[i] = row * TK_LD + c4;
-            }
-            f32x4 g[8];
-            const bool tail = (D % TK_BK) != 0 && (nst - 1) * TK_BK + c4t >= D;
-            auto gload = [&](int s) {
-                const int off = min(s * TK_BK, D - 4 - c4t);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) g[i] = *reinterpret_cast<const f32x4 *>(gp[i] + off);
-            };
-            auto lstore = [&](int bf, bool last) {
-                if (last && (D % TK_BK) != 0) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) g[i] = tail ? (f32x4){0.f, 0.f, 0.f, 0.f} : g[i];
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i) *reinterpret_cast<f32x4 *>(&lds[bf][lo[i]]) = g[i];
-            };
+            // ---- the shared 128 x 128 MFMA tile (kge_tile_gemm.hpp), D % 4 == 0 ------------------------------------------------
+            f32x4 acc[4][4];
+            tile_gemm_128x128(
+                lds, D, wave, [=](int i) { return row_ptr(a.abase, a.aidx, min(r0 + i, a.rows - 1), D); },
+                [=](int j) { return row_ptr(a.nbase, a.nidx, min(bn * TILE_BN + j, a.N - 1), D); }, acc);
             const int wr = wave >> 1, wc = wave & 1;
             const int m = lane & 15, q = lane >> 4;
-            const int aoff = (wr * 64 + m) * TK_LD + 4 * q, boff = (TK_BM + wc * 64 + m) * TK_LD + 4 * q;
-            f32x4 acc[4][4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            gload(0);
-            lstore(0, nst == 1);
-            __syncthreads();
-            for (int s = 0; s < nst; ++s) {
-                const int bf = s & 1;
-                if (s + 1 < nst) gload(s + 1);
-                f32x4 af[2][4], bfr[2][4];
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        af[kb][i] = *reinterpret_cast<const f32x4 *>(&lds[bf][aoff + i * 16 * TK_LD + kb * 16]);
-                        bfr[kb][i] = *reinterpret_cast<const f32x4 *>(&lds[bf][boff + i * 16 * TK_LD + kb * 16]);
-                    }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[i][j] = MFMA16(af[0][i][e], bfr[0][j][e], acc[i][j]);
-                __builtin_amdgcn_sched_barrier(0);
-                if (s + 1 < nst) lstore(bf ^ 1, s + 2 == nst);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) acc[i][j] = MFMA16(af[1][i][e], bfr[1][j][e], acc[i][j]);
-                __syncthreads();
-            }
             // tile -> LDS: acc[i][j][r] = (row 64 wr + 16 i + 4 q + r, column 64 wc + 16 j + m)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -198,15 +122,15 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int col = wc * 64 + 16 * j + m;
-                        const int64_t gcol = min(bn * TK_BN + col, a.N - 1);
-                        sc[row * TK_BN + col] = epilogue(a, acc[i][j][r], grow, gcol);
+                        const int64_t gcol = min(bn * TILE_BN + col, a.N - 1);
+                        sc[row * TILE_BN + col] = epilogue(a, acc[i][j][r], grow, gcol);
                     }
                 }
         } else {
             // ---- VALU tile: thread (tx, ty) owns rows ty + 16 i, columns tx + 16 j; scalar staging (any D) ------------------
             const int tx = tid & 15, ty = tid >> 4;
             const int hd = D / 2;
-            const int nst = ACC == ACC_ROT ? (hd + 15) / 16 : (D + TK_BK - 1) / TK_BK;
+            const int nst = ACC == ACC_ROT ? (hd + 15) / 16 : (D + TILE_BK - 1) / TILE_BK;
             float acc[8][8];
 #pragma unroll
             for (int i = 0; i < 8; ++i)
@@ -217,11 +141,11 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
 #pragma unroll
                 for (int i = 0; i < 32; ++i) {
                     const int f = tid + 256 * i, row = f >> 5, c = f & 31;
-                    const float *p = row < TK_BM ? row_ptr(a.abase, a.aidx, min(r0 + row, a.rows - 1), D)
-                                                 : row_ptr(a.nbase, a.nidx, min(bn * TK_BN + row - TK_BM, a.N - 1), D);
+                    const float *p = row < TILE_BM ? row_ptr(a.abase, a.aidx, min(r0 + row, a.rows - 1), D)
+                                                 : row_ptr(a.nbase, a.nidx, min(bn * TILE_BN + row - TILE_BM, a.N - 1), D);
                     int col; bool ok;
                     if constexpr (ACC == ACC_ROT) { const int k = s * 16 + (c & 15); ok = k < hd; col = (c < 16 ? 0 : hd) + min(k, hd - 1); }
-                    else { const int k = s * TK_BK + c; ok = k < D; col = min(k, D - 1); }
+                    else { const int k = s * TILE_BK + c; ok = k < D; col = min(k, D - 1); }
                     const float v = p[col];
                     g[i] = ok ? v : 0.f;
                 }
@@ -229,16 +153,16 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
 #pragma unroll
                 for (int i = 0; i < 32; ++i) {
                     const int f = tid + 256 * i;
-                    lds[0][(f >> 5) * TK_LD + (f & 31)] = g[i];
+                    lds[0][(f >> 5) * TILE_LD + (f & 31)] = g[i];
                 }
                 __syncthreads();
                 if constexpr (ACC == ACC_ROT) {
                     for (int k = 0; k < 16; ++k) {
                         float are[8], aim[8], bre[8], bim[8];
 #pragma unroll
-                        for (int i = 0; i < 8; ++i) { are[i] = lds[0][(ty + 16 * i) * TK_LD + k]; aim[i] = lds[0][(ty + 16 * i) * TK_LD + 16 + k]; }
+                        for (int i = 0; i < 8; ++i) { are[i] = lds[0][(ty + 16 * i) * TILE_LD + k]; aim[i] = lds[0][(ty + 16 * i) * TILE_LD + 16 + k]; }
 #pragma unroll
-                        for (int j = 0; j < 8; ++j) { bre[j] = lds[0][(TK_BM + tx + 16 * j) * TK_LD + k]; bim[j] = lds[0][(TK_BM + tx + 16 * j) * TK_LD + 16 + k]; }
+                        for (int j = 0; j < 8; ++j) { bre[j] = lds[0][(TILE_BM + tx + 16 * j) * TILE_LD + k]; bim[j] = lds[0][(TILE_BM + tx + 16 * j) * TILE_LD + 16 + k]; }
 #pragma unroll
                         for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -248,12 +172,12 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
                             }
                     }
                 } else {
-                    for (int k = 0; k < TK_BK; ++k) {
+                    for (int k = 0; k < TILE_BK; ++k) {
                         float av[8], bv[8];
 #pragma unroll
-                        for (int i = 0; i < 8; ++i) av[i] = lds[0][(ty + 16 * i) * TK_LD + k];
+                        for (int i = 0; i < 8; ++i) av[i] = lds[0][(ty + 16 * i) * TILE_LD + k];
 #pragma unroll
-                        for (int j = 0; j < 8; ++j) bv[j] = lds[0][(TK_BM + tx + 16 * j) * TK_LD + k];
+                        for (int j = 0; j < 8; ++j) bv[j] = lds[0][(TILE_BM + tx + 16 * j) * TILE_LD + k];
 #pragma unroll
                         for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -273,7 +197,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const int col = tx + 16 * j;
-                    sc[row * TK_BN + col] = epilogue(a, acc[i][j], grow, min(bn * TK_BN + col, a.N - 1));
+                    sc[row * TILE_BN + col] = epilogue(a, acc[i][j], grow, min(bn * TILE_BN + col, a.N - 1));
                 }
             }
         }
@@ -281,15 +205,15 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
         // ---- selection: wavefront w walks rows 32 w .. 32 w + 31 of the tile ------------------------------------------------
         [[maybe_unused]] int64_t id0 = 0, id1 = 0;                              // (filtered form) the entity ids of this lane's two candidates
         if constexpr (FILT) {
-            const int64_t c0 = min(bn * TK_BN + lane, a.N - 1), c1 = min(bn * TK_BN + lane + 64, a.N - 1);
+            const int64_t c0 = min(bn * TILE_BN + lane, a.N - 1), c1 = min(bn * TILE_BN + lane + 64, a.N - 1);
             id0 = a.nidx ? a.nidx[c0] : c0; id1 = a.nidx ? a.nidx[c1] : c1;
         }
         for (int lr = wave * 32; lr < wave * 32 + 32; ++lr) {
             if (r0 + lr >= a.rows) break;
             const unsigned long long thr = rthr[lr];
-            const int64_t j0 = bn * TK_BN + lane, j1 = j0 + 64;
-            const unsigned long long c0 = j0 < a.N ? comp_of(sc[lr * TK_BN + lane], j0) : 0ull;
-            const unsigned long long c1 = j1 < a.N ? comp_of(sc[lr * TK_BN + lane + 64], j1) : 0ull;
+            const int64_t j0 = bn * TILE_BN + lane, j1 = j0 + 64;
+            const unsigned long long c0 = j0 < a.N ? comp_of(sc[lr * TILE_BN + lane], j0) : 0ull;
+            const unsigned long long c1 = j1 < a.N ? comp_of(sc[lr * TILE_BN + lane + 64], j1) : 0ull;
             bool s0 = c0 > thr, s1 = c1 > thr;
             unsigned long long b0 = __ballot(s0), b1 = __ballot(s1);
             if ((b0 | b1) == 0ull) continue;                                   // the common case
@@ -491,11 +415,11 @@ int topk_fan(int K) { return std::max(1, TK_MCAP / K - 1); }
 // later tiles take the one-compare-one-ballot path
 #define TK_MIN_TILES 4
 int64_t topk_seg_cap(int rows, int K) {
-    const int rb = std::max(1, (rows + TK_BM - 1) / TK_BM);
+    const int rb = std::max(1, (rows + TILE_BM - 1) / TILE_BM);
     return std::max<int64_t>(1, std::min<int64_t>(topk_fan(K), (256 + rb - 1) / rb));
 }
 int topk_segments(int rows, int64_t N, int K) {
-    const int64_t nbn = (N + TK_BN - 1) / TK_BN;
+    const int64_t nbn = (N + TILE_BN - 1) / TILE_BN;
     const int64_t s = std::max<int64_t>(1, std::min(nbn / TK_MIN_TILES, topk_seg_cap(rows, K))), tps = (nbn + s - 1) / s;
     return (int)((nbn + tps - 1) / tps);
 }
@@ -544,7 +468,7 @@ int merge_tree(int64_t G, int64_t L, int K, const float *is, const int64_t *io, 
         int64_t *dq = (fin && out_s) ? out_o : to[pp];
         hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)(G * nout)), dim3(256), 0, st, is, io, (int)L, fan, K, (int)nout,
                            xs, xo, ds, dq);
-        if (int rc = check_launch_t()) return rc;
+        if (int rc = check_launch()) return rc;
         xs = nullptr; xo = nullptr;
         is = ds; io = dq; L = nout; pp ^= 1;
         if (fin) break;
@@ -610,7 +534,7 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
     const float *abase = w.A;
     const int64_t *aidx = nullptr;
     int acc, epi;
-    const int mf = D % 4 == 0 && D >= TK_BK;               // (the staging's clamped float4 re-reads need D >= 32)
+    const int mf = D % 4 == 0 && D >= TILE_BK;               // (the staging's clamped float4 re-reads need D >= 32)
     if (sim) {
         abase = ent; aidx = h;
         if (func == KGE_SIM_L1) { acc = ACC_L1; epi = EPI_GMINUS; }
@@ -646,13 +570,13 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
                            st, abase, aidx, (int64_t)rows, D, sq, w.an);
         hipLaunchKernelGGL(topk_norm_kernel, dim3((unsigned)((N + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK)), dim3(KGE_BLOCK), 0,
                            st, ent, cand, N, D, sq, w.bn);
-        if (int rc = check_launch_t()) return rc;
+        if (int rc = check_launch()) return rc;
     }
     // ---- score + select ----------------------------------------------------------------------------------------------------------
     TopkSelArgs a{};
     a.abase = abase; a.aidx = aidx; a.rows = rows; a.nbase = ent; a.nidx = cand; a.N = N; a.D = D; a.epi = epi;
     a.S = topk_segments(rows, N, K); a.K = K; a.gamma = gamma; a.an = w.an; a.bn = w.bn; a.part = w.part;
-    const dim3 grid((unsigned)((int64_t)((rows + TK_BM - 1) / TK_BM) * a.S));
+    const dim3 grid((unsigned)((int64_t)((rows + TILE_BM - 1) / TILE_BM) * a.S));
     if (filt_ptr) {
         TopkSelArgsF f{};
         static_cast<TopkSelArgs &>(f) = a;
@@ -672,11 +596,11 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
     case ACC_L1: hipLaunchKernelGGL(topk_select_kernel<ACC_L1>, grid, dim3(256), 0, st, a); break;
     default: hipLaunchKernelGGL(topk_select_kernel<ACC_ROT>, grid, dim3(256), 0, st, a); break;
     }
-    if (int rc = check_launch_t()) return rc;
+    if (int rc = check_launch()) return rc;
     const int64_t ne = (int64_t)rows * a.S * K;
     hipLaunchKernelGGL(topk_unpack_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, w.part, ne, a.S * K, row_base, stride,
                        w.s0, w.o0);
-    if (int rc = check_launch_t()) return rc;
+    if (int rc = check_launch()) return rc;
     // ---- segments of a row -> one list per row; l2 scores in the difference form; rows of a group + running result -> result
     const float *rs; const int64_t *ro;
     if (int rc = merge_tree(rows, a.S, K, w.s0, w.o0, nullptr, nullptr, nullptr, nullptr, w.s1, w.o1, w.s0, w.o0, &rs, &ro, st)) return rc;
@@ -684,7 +608,7 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
         const int64_t nk = (int64_t)rows * K;
         hipLaunchKernelGGL(topk_l2_fix_kernel, dim3((unsigned)((nk + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK)), dim3(KGE_BLOCK), 0, st,
                            abase, aidx, ent, cand, D, rows, K, row_base, stride, gamma, const_cast<float *>(rs), ro);
-        if (int rc = check_launch_t()) return rc;
+        if (int rc = check_launch()) return rc;
     }
     float *ta_s = rs == w.s0 ? w.s1 : w.s0, *tb_s = rs == w.s0 ? w.s0 : w.s1;
     int64_t *ta_o = rs == w.s0 ? w.o1 : w.o0, *tb_o = rs == w.s0 ? w.o0 : w.o1;
@@ -716,7 +640,7 @@ int kge_triples_known(const int64_t *keys, const int64_t *vals, int64_t M, int64
     if (n == 0) return KGE_OK;
     hipLaunchKernelGGL(triples_known_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, keys, vals, M, n_rel,
                        a, r, b, n, out);
-    return check_launch_t();
+    return check_launch();
 }
 
 int kge_topk_vector(const float *score, int64_t n, int K, float *res_score, int64_t *res_ord, void *ws, size_t ws_bytes, void *stream) {
@@ -735,7 +659,7 @@ int kge_topk_vector(const float *score, int64_t n, int K, float *res_score, int6
     hipStream_t st = (hipStream_t)stream;
     const int64_t L = (n + K - 1) / K, total = L * K;
     hipLaunchKernelGGL(topk_vec_lists_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, score, n, total, w.s0, w.o0);
-    if (int rc = check_launch_t()) return rc;
+    if (int rc = check_launch()) return rc;
     const float *fs; const int64_t *fo;
     return merge_tree(1, L, K, w.s0, w.o0, res_score, res_ord, res_score, res_ord, w.s1, w.o1, w.s0, w.o0, &fs, &fo, st);
 }
@@ -747,7 +671,7 @@ int kge_sim_pairwise(int sim, const float *emb, int64_t n_emb, int d, const int6
     if (n == 0) return KGE_OK;
     hipLaunchKernelGGL(topk_sim_pair_kernel, dim3((unsigned)((n + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK)), dim3(KGE_BLOCK), 0,
                        (hipStream_t)stream, sim, emb, d, left, right, n, out);
-    return check_launch_t();
+    return check_launch();
 }
 
 }  // extern "C"

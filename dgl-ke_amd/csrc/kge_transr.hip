@@ -17,12 +17,10 @@
 using namespace kge;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 #define TR_T 64          // output tile edge
 #define TR_K 16          // reduction slab
 #define TR_LD (TR_T + 4)
 
-static inline int check_launch_t() { return hipGetLastError() == hipSuccess ? KGE_OK : KGE_ERR_LAUNCH; }
 
 // Operand loads may return RAW data (sign bytes + a scale) that is converted to fp32 only when it is written to LDS, one slab
 // later: a conversion inside the load would make the wavefront wait for the load before the slab's MFMAs instead of under them
@@ -564,7 +562,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void transr_proj_apply_vec_kernel(TransR
 int launch_transr_pos(const TransRArgs &a, hipStream_t s) {
     if (a.B == 0) return KGE_OK;
     hipLaunchKernelGGL(transr_pos_kernel, dim3((a.B + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK), dim3(KGE_BLOCK), 0, s, a);
-    return check_launch_t();
+    return check_launch();
 }
 // the 128 x 208-tile kernels: operand widths, and their per-workgroup id / weight tables beside 45 KB of tiles
 static bool transr_use_wide(int De, int Dr, int chunk, int N) {
@@ -580,12 +578,12 @@ int launch_transr_fwd(const TransRArgs &a, hipStream_t s) {
     if (transr_use_wide(a.De, a.Dr, a.chunk, a.N)) {
         const int nJW = (a.N + TW_R - 1) / TW_R;
         hipLaunchKernelGGL(transr_fwd_wide_kernel, dim3(a.B * nJW), dim3(KGE_BLOCK), 0, s, a, nJW);
-        return check_launch_t();
+        return check_launch();
     }
     const int nJB = (a.N + TR_T - 1) / TR_T;
     if (a.De % 4 == 0 && a.Dr % 4 == 0) hipLaunchKernelGGL(transr_fwd_kernel<true>, dim3(a.B * nJB), dim3(KGE_BLOCK), 0, s, a, nJB);
     else hipLaunchKernelGGL(transr_fwd_kernel<false>, dim3(a.B * nJB), dim3(KGE_BLOCK), 0, s, a, nJB);
-    return check_launch_t();
+    return check_launch();
 }
 int launch_transr_bwd(const TransRArgs &a, hipStream_t s) {
     if (a.B == 0) return KGE_OK;
@@ -596,7 +594,7 @@ int launch_transr_bwd(const TransRArgs &a, hipStream_t s) {
         hipLaunchKernelGGL(transr_gn_wide_kernel, dim3(a.C * nJW * a.nG), b, (size_t)ipgw * (sizeof(int64_t) + TW_R * sizeof(float)), s, a, nJW);
         hipLaunchKernelGGL(transr_gn_reduce_kernel, dim3(((int64_t)a.C * a.N + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK), b, 0, s, a);
         hipLaunchKernelGGL(transr_gp_wide_kernel, dim3(a.B * nEW), b, (size_t)a.N * (sizeof(int64_t) + sizeof(float)) + TW_C * sizeof(float), s, a, nEW);
-        return check_launch_t();
+        return check_launch();
     }
     hipLaunchKernelGGL(transr_dq_kernel, dim3(a.B), b, 0, s, a);
     const bool vec = a.De % 4 == 0 && a.Dr % 4 == 0;      // 16-byte operand loads (4 sign bytes per word)
@@ -609,7 +607,7 @@ int launch_transr_bwd(const TransRArgs &a, hipStream_t s) {
     if (vec) hipLaunchKernelGGL(transr_gp_kernel<true>, dim3(a.B * nEB * nRB), b, gp_lds, s, a, nEB, nRB);
     else hipLaunchKernelGGL(transr_gp_kernel<false>, dim3(a.B * nEB * nRB), b, gp_lds, s, a, nEB, nRB);
     hipLaunchKernelGGL(transr_gr_kernel, gw, b, 0, s, a);
-    return check_launch_t();
+    return check_launch();
 }
 int launch_transr_proj_update(const TransRArgs &a, hipStream_t s) {
     if (a.B == 0 || a.UR == 0) return KGE_OK;
@@ -623,7 +621,7 @@ int launch_transr_proj_update(const TransRArgs &a, hipStream_t s) {
         hipLaunchKernelGGL(transr_proj_apply_vec_kernel, dim3(a.UR * TR_RB), dim3(KGE_BLOCK), 0, s, a, tpr);
     } else
         hipLaunchKernelGGL(transr_proj_apply_kernel, dim3(a.UR * TR_RB), dim3(KGE_BLOCK), 0, s, a);
-    return check_launch_t();
+    return check_launch();
 }
 
 // =============================================================================================
@@ -791,7 +789,7 @@ int kge_transr_project(const float *proj, const float *x, int64_t B, int d_e, in
     if (B == 0) return KGE_OK;
     PnArgs a{}; a.B = (int)B; a.De = d_e; a.Dr = d_r; a.proj = proj; a.x = x; a.Y = out;
     hipLaunchKernelGGL(transr_pv_fwd_kernel, dim3((unsigned)B), dim3(KGE_BLOCK), 0, (hipStream_t)stream, a);
-    return check_launch_t();
+    return check_launch();
 }
 
 int kge_transr_project_bwd(const float *proj, const float *x, const float *gy, int64_t B, int d_e, int d_r, float *gx,
@@ -801,7 +799,7 @@ int kge_transr_project_bwd(const float *proj, const float *x, const float *gy, i
     PnArgs a{}; a.B = (int)B; a.De = d_e; a.Dr = d_r; a.proj = proj; a.x = x; a.gy = gy; a.gx = gx; a.gproj = gproj;
     a.accumulate = accumulate;
     hipLaunchKernelGGL(transr_pv_bwd_kernel, dim3((unsigned)B), dim3(KGE_BLOCK), 0, (hipStream_t)stream, a);
-    return check_launch_t();
+    return check_launch();
 }
 
 int kge_transr_project_neg(const float *proj, const float *neg, int C, int chunk, int N, int d_e, int d_r, float *Y, void *stream) {
@@ -812,7 +810,7 @@ int kge_transr_project_neg(const float *proj, const float *neg, int C, int chunk
     const dim3 g((unsigned)(a.B * nJB * nRB)), b(KGE_BLOCK);
     if (d_e % 4 == 0 && d_r % 4 == 0) hipLaunchKernelGGL(transr_pn_fwd_kernel<true>, g, b, 0, (hipStream_t)stream, a, nJB, nRB);
     else hipLaunchKernelGGL(transr_pn_fwd_kernel<false>, g, b, 0, (hipStream_t)stream, a, nJB, nRB);
-    return check_launch_t();
+    return check_launch();
 }
 
 int kge_transr_project_neg_bwd(const float *proj, const float *neg, const float *gY, int C, int chunk, int N, int d_e, int d_r,
@@ -833,7 +831,7 @@ int kge_transr_project_neg_bwd(const float *proj, const float *neg, const float 
         if (vec) hipLaunchKernelGGL(transr_pn_bwd_proj_kernel<true>, dim3((unsigned)(a.B * nEB * nRB)), b, 0, s, a, nEB, nRB);
         else hipLaunchKernelGGL(transr_pn_bwd_proj_kernel<false>, dim3((unsigned)(a.B * nEB * nRB)), b, 0, s, a, nEB, nRB);
     }
-    return check_launch_t();
+    return check_launch();
 }
 
 }  // extern "C"
