@@ -848,16 +848,20 @@ __device__ __forceinline__ void neg_bwd_gemm_tile(const GemmArgs &a, int ti, int
     const int d = PAIRED ? (m < 8 ? dre : Kc + dre) : dt * 64 + m * 4;       // this lane's 4 output columns
     const bool dok = PAIRED ? dre < Kc : d < D;          // D % 4 == 0 (PAIRED: Kc % 4 == 0): all-or-nothing
     const int dc = dok ? d : 0;
-    // workgroup-shared table in LDS: rix[k] = row index of reduction element k in the streamed operand (GA: negative row,
-    // gathered through neg_ids or dense; GN: positive row of the chunk).  INDICES, not pointers: a pointer read back from
-    // LDS turns the row loads into flat loads, which count on lgkmcnt and serialise behind every LDS wait (measured: 48 %
-    // of the wavefront time parked in s_waitcnt).
+    // workgroup-shared table in LDS: rix[k] = ELEMENT OFFSET (row * D) of reduction element k's row in the streamed operand (GA:
+    // negative row, gathered through neg_ids or dense; GN: positive row of the chunk).  OFFSETS, not pointers: a pointer read
+    // back from LDS turns the row loads into flat loads, which count on lgkmcnt and serialise behind every LDS wait (measured:
+    // 48 % of the wavefront time parked in s_waitcnt).  And not row indices either (round 8): `index * D` in the loop was a full
+    // 64 x 64-bit multiply per row - 3 integer multiplies + 2 more VALU instructions between the LDS read and the request it
+    // feeds, in front of MFMAs whose time ADDS to VALU time on this chip (profiles/r08_gemm_loop_issue.txt).  The thread that
+    // fills entry k multiplies once, in front of the barrier that is there anyway; the loop adds offset to base (one
+    // v_lshl_add_u64 per row).
     // FACT, GN: ftab[k][t] = factor f(k, t) of every positive row k of the chunk and every column tile t, computed by
     // thread k in the same pass as the row's statistics (one dependent round; the wavefront whose output rows are
     // column tile rt reads column rt).
     int64_t *rix = reinterpret_cast<int64_t *>(smem);                     // [maxK]
     float *ftab = smem + 2 * maxK;                                        // [maxK][GB_TJP]
-    // (1) the index this thread contributes to rix (GA, gathered negatives: a global load - the OLDEST request, the LDS
+    // (1) the row this thread contributes to rix (GA, gathered negatives: a global load - the OLDEST request, the LDS
     //     write below waits for it alone)
     const int k0 = threadIdx.x;
     const int64_t rbase = isGA ? (int64_t)c * N : (int64_t)c * chunk;     // DENSE: reduction element k is row rbase + k
@@ -899,9 +903,9 @@ __device__ __forceinline__ void neg_bwd_gemm_tile(const GemmArgs &a, int ti, int
     }
     // (3) the index table
     if (!DENSE) {
-        if (k0 < K) rix[k0] = rix0;
+        if (k0 < K) rix[k0] = rix0 * D;
         for (int k = k0 + KS * KGE_BLOCK; k < K; k += KS * KGE_BLOCK)         // K > the workgroup's threads
-            rix[k] = isGA ? (a.nidx ? a.nidx[(int64_t)c * N + k] : (int64_t)c * N + k) : (int64_t)c * chunk + k;
+            rix[k] = (isGA ? (a.nidx ? a.nidx[(int64_t)c * N + k] : (int64_t)c * N + k) : (int64_t)c * chunk + k) * D;
     }
     if (FACT && !isGA) {
         for (int k = threadIdx.x; k < K; k += KS * KGE_BLOCK) {
@@ -950,7 +954,7 @@ __device__ __forceinline__ void neg_bwd_gemm_tile(const GemmArgs &a, int ti, int
 
     // Main loop over FULL macro steps: no per-lane predicates (rows / columns are clamped so every
     // load is in bounds; garbage in clamped rows only reaches outputs that are never stored), row
-    // addresses = kernel-argument base + LDS index (global loads, vmcnt only).  One predicated tail
+    // addresses = kernel-argument base + LDS offset (global loads, vmcnt only).  One predicated tail
     // step handles K % 16.
     const int msall = K >> 4;
     // this wavefront's full macro steps [mlo, msfull): all of them (KS = 1), or the first / second half
@@ -958,24 +962,37 @@ __device__ __forceinline__ void neg_bwd_gemm_tile(const GemmArgs &a, int ti, int
     const int msfull = (KS == 1 || kh == KS - 1) ? msall : (kh + 1) * (msall / KS);
     const float *Xb = (isGA ? a.nbase : a.A) + dc;                 // operand base (global address space)
     const float *Wq = Wrow + (int64_t)(q * 4) * wstride;
+    // (round 8) no multiply in the loop: what a macro step adds to an address is wave-uniform - xstep elements of the dense
+    // operand, wstep of W - so the loop carries the two offsets of macro step g (xg, wg: scalar adds next to `g += 2 * BU`) and
+    // a load takes `step < last ? running offset : offset of the last full step` - the clamp as a scalar select instead of
+    // `min(ms) * stride`, which the compiler could not strength-reduce (GN: 8 scalar 64-bit multiplies per loop iteration).
+    // The lane's part is constant: its 4 dense rows (xd[e], DENSE only) and its W pointer.
+    const int64_t xstep = (int64_t)16 * D, wstep = 16 * wstride;
+    const int64_t xlast = (int64_t)(msfull - 1) * xstep, wlast = (int64_t)(msfull - 1) * wstep;
+    int64_t xd[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) xd[e] = DENSE ? (rbase + q * 4 + e) * D : 0;
+    const int64_t we[4] = {0, wstride, 2 * wstride, 3 * wstride};
 
     // loads are UNCONDITIONAL (macro step clamped; see the forward kernel: a load under a branch defeats the double buffering),
     // the W-layout choice is a compile-time constant of the loop instance (VECW), not a branch per load
-#define BWD_LOAD(ST, MS0, VECW)                                                                \
+    // (XG / WG: the offsets of macro step MS0, see xstep / wstep above)
+#define BWD_LOAD(ST, MS0, XG, WG, VECW)                                                        \
     _Pragma("unroll") for (int u = 0; u < BU; ++u) {                                           \
-        const int ms = min((MS0) + u, msfull - 1);                                             \
-        int64_t ri[4];                                                                         \
+        const bool in_ = (MS0) + u < msfull - 1;                                               \
+        const int ms = in_ ? (MS0) + u : msfull - 1;                                           \
+        int64_t ro[4];                     /* element offsets of the 4 operand rows */         \
         _Pragma("unroll") for (int e = 0; e < 4; ++e)                                          \
-            ri[e] = DENSE ? rbase + (ms * 16 + q * 4 + e) : rix[ms * 16 + q * 4 + e];          \
+            ro[e] = DENSE ? xd[e] + (in_ ? (XG) + u * xstep : xlast) : rix[ms * 16 + q * 4 + e]; \
         if (VECW) {                                                                            \
             const float4 t4 = ldg4(Wq + ms * 16);                                              \
             ST[u].w[0] = t4.x; ST[u].w[1] = t4.y; ST[u].w[2] = t4.z; ST[u].w[3] = t4.w;        \
         } else {                                                                               \
-            _Pragma("unroll") for (int e = 0; e < 4; ++e)                                      \
-                ST[u].w[e] = Wq[(int64_t)(ms * 16 + e) * wstride];                             \
+            const int64_t wo = in_ ? (WG) + u * wstep : wlast;                                 \
+            _Pragma("unroll") for (int e = 0; e < 4; ++e) ST[u].w[e] = Wq[wo + we[e]];         \
         }                                                                                      \
         if (FACT) ST[u].pm = PMrow[isGA ? ms : 0];    /* macro step ms = column tile ms */     \
-        _Pragma("unroll") for (int e = 0; e < 4; ++e) ST[u].r[e] = ldg4(Xb + ri[e] * D);       \
+        _Pragma("unroll") for (int e = 0; e < 4; ++e) ST[u].r[e] = ldg4(Xb + ro[e]);           \
     }
     // u_ij -> dL/dn_ij: one factor per (row, macro step) for GA, one LDS read of four per-row factors for GN
 #define BWD_XFORM(ST, MS0)                                                                     \
@@ -1004,22 +1021,23 @@ __device__ __forceinline__ void neg_bwd_gemm_tile(const GemmArgs &a, int ti, int
 #define BWD_MMA_G(ST, MS0) _Pragma("unroll") for (int u = 0; u < BU; ++u) { if ((MS0) + u < msfull) { BWD_MMA1(ST, u) } }
 #define BWD_PIPE(VECW)                                                                         \
     {                                                                                          \
-        BWD_LOAD(s0, mlo, VECW);                                                               \
         int g = mlo;                                                                           \
-        for (; g + 2 * BU <= msfull; g += 2 * BU) {                                            \
-            BWD_LOAD(s1, g + BU, VECW);                                                        \
+        int64_t xg = mlo * xstep, wg = mlo * wstep;                                            \
+        BWD_LOAD(s0, mlo, xg, wg, VECW);                                                       \
+        for (; g + 2 * BU <= msfull; g += 2 * BU, xg += 2 * BU * xstep, wg += 2 * BU * wstep) { \
+            BWD_LOAD(s1, g + BU, xg + BU * xstep, wg + BU * wstep, VECW);                      \
             KGE_ORDER();                           /* requests first, then the MFMAs on the other buffer */ \
             BWD_XFORM(s0, g);                                                                  \
             BWD_MMA(s0);                                                                       \
             KGE_ORDER();                                                                       \
-            BWD_LOAD(s0, g + 2 * BU, VECW);                                                    \
+            BWD_LOAD(s0, g + 2 * BU, xg + 2 * BU * xstep, wg + 2 * BU * wstep, VECW);          \
             KGE_ORDER();                                                                       \
             BWD_XFORM(s1, g + BU);                                                             \
             BWD_MMA(s1);                                                                       \
             KGE_ORDER();                                                                       \
         }                                                                                      \
         if (g < msfull) {                    /* fewer than 2 * BU macro steps left */          \
-            BWD_LOAD(s1, g + BU, VECW);                                                        \
+            BWD_LOAD(s1, g + BU, xg + BU * xstep, wg + BU * wstep, VECW);                      \
             BWD_XFORM(s0, g);                                                                  \
             BWD_MMA_G(s0, g);                                                                  \
             BWD_XFORM(s1, g + BU);                                                             \
@@ -1040,7 +1058,7 @@ __device__ __forceinline__ void neg_bwd_gemm_tile(const GemmArgs &a, int ti, int
         for (int e = 0; e < 4; ++e) {
             const int kc = min(kk + e, K - 1);
             tw[e] = Wrow[(int64_t)kc * wstride];
-            tx[e] = ldg4(Xb + (DENSE ? rbase + kc : rix[kc]) * D);
+            tx[e] = ldg4(Xb + (DENSE ? (rbase + kc) * D : rix[kc]));
         }
         if (FACT && isGA) tpm = PMrow[min(msall, tj - 1)];
     }

@@ -1,6 +1,7 @@
 // valu_rate_probe.hip - issue cost of the VALU instruction kinds the pairwise kernels (kge_neg_bcast.hip: TransE_l1, RotatE) are
 // made of, on MI355X: plain fp32, packed fp32 (v_pk_*), the quarter-rate unit (v_sqrt / v_rsq / v_exp) and the instruction MIX of
-// the RotatE forward / backward inner loops.  Every wavefront runs REPS x 64 independent instructions of one kind (8 dependency
+// the RotatE forward / backward inner loops, and (round 8) the two integer multiplies a 64-bit `index * D` address is made of
+// (v_mul_lo_u32, v_mad_u64_u32: they stood in the backward GEMM's main loop, profiles/r08_gemm_loop_issue.txt).  Every wavefront runs REPS x 64 independent instructions of one kind (8 dependency
 // chains) between two s_memtime reads; 1 / 2 / 4 wavefronts per SIMD (one workgroup per CU, 256 CUs).
 // Output: shader cycles per wavefront-instruction as seen by ONE wavefront, and per SIMD (= the former / wavefronts per SIMD):
 // the second is the issue cost that bounds a VALU-bound kernel.
@@ -13,16 +14,16 @@
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-enum { K_FMA, K_ADDABS, K_PKFMA, K_PKADD, K_PKMUL, K_SQRT, K_RSQ, K_EXP, K_ROT_FWD, K_ROT_FWD_SCALAR, K_ROT_BWD, K_ROT_FWD_LDS, K_L1_FWD, K_N };
+enum { K_FMA, K_ADDABS, K_PKFMA, K_PKADD, K_PKMUL, K_SQRT, K_RSQ, K_EXP, K_ROT_FWD, K_ROT_FWD_SCALAR, K_ROT_BWD, K_ROT_FWD_LDS, K_L1_FWD, K_MULLO, K_MAD64, K_N };
 static const char *KNAME[K_N] = {"v_fma_f32", "v_add_f32 |abs|", "v_pk_fma_f32", "v_pk_add_f32", "v_pk_mul_f32", "v_sqrt_f32", "v_rsq_f32",
                                  "v_exp_f32", "RotatE fwd mix (per 2 complex: 3 pk_add 1 pk_mul 1 pk_fma 2 sqrt)",
                                  "RotatE fwd, unpacked (per complex: 2 sub 1 mul 1 fma 1 sqrt 1 add)",
                                  "RotatE bwd mix (per 2 complex: 2 pk_add 1 pk_mul 6 pk_fma 1 mov_dpp 2 rsq)",
                                  "RotatE fwd mix + 1 ds_read_b128 (broadcast) per 2 complex",
-                                 "TransE_l1 fwd (per 2 elements: 1 pk_add 2 add|abs|)"};
+                                 "TransE_l1 fwd (per 2 elements: 1 pk_add 2 add|abs|)", "v_mul_lo_u32", "v_mad_u64_u32"};
 // instructions per unrolled block (for the per-instruction figures) and "units" per block (complex elements / elements)
-static const int KINSTR[K_N] = {64, 64, 64, 64, 64, 64, 64, 64, 8 * 7, 8 * 6, 8 * 12, 8 * 8, 16 * 3};
-static const int KUNITS[K_N] = {64, 64, 128, 128, 128, 64, 64, 64, 16, 8, 16, 16, 32};
+static const int KINSTR[K_N] = {64, 64, 64, 64, 64, 64, 64, 64, 8 * 7, 8 * 6, 8 * 12, 8 * 8, 16 * 3, 64, 64};
+static const int KUNITS[K_N] = {64, 64, 128, 128, 128, 64, 64, 64, 16, 8, 16, 16, 32, 64, 64};
 
 #define REP8(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
 
@@ -32,6 +33,10 @@ __global__ __launch_bounds__(1024) void k_rate(float *o, unsigned long long *tl,
     const float s = threadIdx.x * 0.001f + 1.f;
     float x[8];
     v2f p[8], q[8], acc[8];
+    unsigned ux[8];
+    unsigned long long wx[8];
+    for (int i = 0; i < 8; ++i) { ux[i] = threadIdx.x * 2654435761u + i; wx[i] = ux[i]; }
+    const unsigned uy = 400u + (threadIdx.x & 1);
     for (int i = 0; i < 8; ++i) { x[i] = s + i; p[i] = v2f{s + i, s - i}; q[i] = v2f{0.5f * s + i, 0.25f * s}; acc[i] = v2f{0.f, 0.f}; }
     if (threadIdx.x < 256) lds[threadIdx.x] = v4f{s, s + 1, s + 2, s + 3};
     __syncthreads();
@@ -189,6 +194,20 @@ __global__ __launch_bounds__(1024) void k_rate(float *o, unsigned long long *tl,
 #define X(i) asm volatile("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(q[i]) : "v"(n1[i]), "v"(y2));
             REP8(X)
 #undef X
+        } else if (KIND == K_MULLO) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+#define X(i) asm volatile("v_mul_lo_u32 %0, %0, %1" : "+v"(ux[i]) : "v"(uy));
+                REP8(X)
+#undef X
+            }
+        } else if (KIND == K_MAD64) {
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+#define X(i) asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(wx[i]) : "v"(ux[i]), "v"(uy) : "vcc");
+                REP8(X)
+#undef X
+            }
         } else if (KIND == K_L1_FWD) {
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
@@ -207,7 +226,7 @@ __global__ __launch_bounds__(1024) void k_rate(float *o, unsigned long long *tl,
     }
     unsigned long long t1 = __builtin_readcyclecounter();
     float r_ = 0.f;
-    for (int i = 0; i < 8; ++i) r_ += x[i] + p[i].x + p[i].y + q[i].x + q[i].y + acc[i].x + acc[i].y;
+    for (int i = 0; i < 8; ++i) r_ += x[i] + p[i].x + p[i].y + q[i].x + q[i].y + acc[i].x + acc[i].y + (float)ux[i] + (float)wx[i];
     o[blockIdx.x * blockDim.x + threadIdx.x] = r_;
     if ((threadIdx.x & 63) == 0) tl[blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)] = t1 - t0;
 }
@@ -222,7 +241,7 @@ int main() {
     hipStream_t s; CK(hipStreamCreate(&s));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     kfn K[K_N] = {k_rate<K_FMA>, k_rate<K_ADDABS>, k_rate<K_PKFMA>, k_rate<K_PKADD>, k_rate<K_PKMUL>, k_rate<K_SQRT>, k_rate<K_RSQ>, k_rate<K_EXP>,
-                  k_rate<K_ROT_FWD>, k_rate<K_ROT_FWD_SCALAR>, k_rate<K_ROT_BWD>, k_rate<K_ROT_FWD_LDS>, k_rate<K_L1_FWD>};
+                  k_rate<K_ROT_FWD>, k_rate<K_ROT_FWD_SCALAR>, k_rate<K_ROT_BWD>, k_rate<K_ROT_FWD_LDS>, k_rate<K_L1_FWD>, k_rate<K_MULLO>, k_rate<K_MAD64>};
     const int reps = 400;
     printf("valu_rate_probe: %d workgroups (one per CU), %d repetitions of the unrolled block per wavefront; cycles = s_memtime shader cycles\n", blocks, reps);
     printf("%-96s %5s %12s %12s %12s %10s\n", "instruction kind", "w/SIMD", "cyc/instr/wave", "cyc/instr/SIMD", "cyc/unit/SIMD", "kernel us");
