@@ -382,7 +382,13 @@ int kge_adagrad_apply_rows(float *table, float *state_sum, int64_t n_rows, int d
  * filt_i = filt_ids[filt_ptr[2i] .. filt_ptr[2i+1]) are candidate COLUMNS whose corrupted triple
  * exists in the graph (the reference's bias == -1 mask, :463-475; unique within a list; filt_ptr
  * is [E][2] begin/end so that triples with the same (h,r) or (r,t) share one list; NULL =
- * --no_eval_filter, where the true triple itself counts exactly as in the reference).  One pass per
+ * --no_eval_filter, where the true triple's own column is a candidate like any other: it counts as in the
+ * reference on every table whose scores are exact in fp32, otherwise its tile-form score and the directly formed
+ * positive score may differ in the last bit and rounding decides).
+ * Ties: a candidate that scores EXACTLY the positive score counts, as in the reference (`>=`, pessimistic: a
+ * collapsed model ranks last, not first); -0.0 and +0.0 compare equal; SimplE compares after the clamp, so
+ * candidates saturated at the positive score's +-20 tie with it (tests/test_gpu_rank_ties.py pins all three on
+ * every ranking entry point below).  One pass per
  * Eb triples.  Matrix-form models (TransE_l2, DistMult, ComplEx, SimplE, RESCAL): a tiled fp32-MFMA
  * GEMM whose epilogue keeps the comparison bit of every (triple, candidate) pair, ranks from the
  * bit mask (csrc/kge_rank_gemm.hip); KGE_FLAG_FORCE_PAIRWISE, the pairwise models and TransR: the
