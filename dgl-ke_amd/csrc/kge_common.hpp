@@ -264,9 +264,18 @@ constexpr bool is_complex_model(int m) { return m == KGE_COMPLEX || m == KGE_ROT
 #define KGE_SIMPLE_CLAMP 20.f        // th.clamp(score, -20, 20), score_fun.py:568
 
 // fast-math variants (hardware exp/log, |rel err| ~1e-6) for the hot kernels
-__device__ __forceinline__ float fast_sigmoid(float x) { return __frcp_rn(1.f + __expf(-x)); }
-__device__ __forceinline__ float fast_neg_logsigmoid(float z) {
-    return fmaxf(-z, 0.f) + __logf(1.f + __expf(-fabsf(z)));
+// softplus and the logistic of the same argument from ONE exponential e = exp(-|z|) (1 + e in (1, 2]: v_rcp_f32, 1 ulp, no
+// IEEE division sequence):  lg = log(1 + e);  -logsigmoid(z) = max(-z, 0) + lg,  -logsigmoid(-z) = max(z, 0) + lg;
+// sig = sigmoid(z) = r (z >= 0), e r (z < 0);  sigmoid(-z) = 1 - sig = e r (z >= 0), r (z < 0) taken by the same select
+struct SoftSig { float lg, sig, nsig; };
+__device__ __forceinline__ SoftSig fast_soft_sig(float z) {
+    const float e = __expf(-fabsf(z)), t = 1.f + e;
+    const float r = __builtin_amdgcn_rcpf(t), er = e * r;
+    SoftSig o;
+    o.lg = __builtin_amdgcn_logf(t) * 0.6931471805599453f;      // t in (1, 2]: v_log_f32 needs no denormal scaling here
+    o.sig = z >= 0.f ? r : er;
+    o.nsig = z >= 0.f ? er : r;
+    return o;
 }
 __device__ __forceinline__ void criterion_fast(int genre, float s, float label, float margin,
                                                float &val, float &dval) {
@@ -275,12 +284,14 @@ __device__ __forceinline__ void criterion_fast(int genre, float s, float label, 
         val = v < 0.f ? 0.f : v;
         dval = v < 0.f ? 0.f : -label;
     } else if (genre == KGE_LOSS_BCE) {
-        val = label * fast_neg_logsigmoid(s) + (1.f - label) * fast_neg_logsigmoid(-s);
-        dval = fast_sigmoid(s) - label;
+        const SoftSig q = fast_soft_sig(s);
+        val = label * (fmaxf(-s, 0.f) + q.lg) + (1.f - label) * (fmaxf(s, 0.f) + q.lg);
+        dval = q.sig - label;
     } else {
         const float z = label * s;
-        val = fast_neg_logsigmoid(z);
-        dval = -label * fast_sigmoid(-z);
+        const SoftSig q = fast_soft_sig(z);
+        val = fmaxf(-z, 0.f) + q.lg;
+        dval = -label * q.nsig;
     }
 }
 
@@ -447,7 +458,16 @@ struct LossArgs {
     float *neg_copy;                 // optional copy of the scores before overwrite
     int skip_pos;                    // the positive-loss part was already done by edge_fwd
     int diag_chunk;                  // > 0 (neg_deg_sample): column i % diag_chunk of row i is masked - score 0, no gradient
+    // filled by the launchers (loss_fill_host), never by the callers:
+    float inv_B, inv_N;              // 1 / B, 1 / N: one IEEE division each on the host, none per wavefront
+    int pk;                          // packed column layout (kge_loss_body.hpp): N % 4 == 0 and every row-wise array 16-byte aligned
 };
+// ONE predicate for the loss launch and the in-launch loss rows: both take the same layout for the same arguments
+inline void loss_fill_host(LossArgs &a) {
+    a.inv_B = 1.f / (float)a.B; a.inv_N = 1.f / (float)a.N;
+    auto al = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    a.pk = a.N > 0 && a.N % 4 == 0 && al(a.neg) && al(a.dneg) && al(a.neg_copy) && (!a.l2_raw || al(a.bsq));
+}
 
 struct UpdateArgs {
     int model_d_e, d_r, UE, UR, reg_norm;

@@ -14,40 +14,91 @@ __device__ __forceinline__ void loss_args_lean(LossArgs &a) {
     a.row_pos = nullptr; a.row_neg = nullptr; a.diag_chunk = 0;
 }
 
-// nv[u] = score of column lane + 64 u of row i (0 beyond N and in the masked diagonal column); w = edge weight, p = positive
-// score (read only by the pairwise / !skip_pos variants).  Writes dL/dn over the row (a.dneg, TransE_l2: pre-divided by the
-// distance), the optional score copy, the row's loss terms and the running sums.  slot2: where this row's share of the total
-// goes in the running sums (the stand-alone kernel: the row's own slot; the in-launch variant: a slot the edge half of the
-// same launch does not touch)
-template <int NPER>
+// Column layout of a register-resident row.  PK (N % 4 == 0, rows 16-byte aligned): a lane holds PACKS of four consecutive
+// columns - pack p of lane l = columns 4 (l + 64 p) .. + 3, slot u = 4 p + k - so that a row moves as one 16-byte access per
+// lane and pack and N = 200 fills ONE pack of 50 lanes (strided: four slots, the last with 8 live lanes at a full slot's price).
+// Otherwise slot u = column lane + 64 u.  A pack is live or dead as a whole.
+typedef float f32x2 __attribute__((ext_vector_type(2)));     // two fp32 in an even-aligned VGPR pair
+template <bool PK> __device__ __forceinline__ int loss_col(int lane, int u) {
+    return PK ? 4 * (lane + 64 * (u >> 2)) + (u & 3) : lane + 64 * u;
+}
+template <bool PK> __device__ __forceinline__ bool loss_live(int lane, int u, int N) {
+    return (PK ? 4 * (lane + 64 * (u >> 2)) : lane + 64 * u) < N;
+}
+// first column of the request that brings slot u (PK: the pack's), clamped into the row instead of predicated: no branch
+// joins in front of the waits
+template <bool PK> __device__ __forceinline__ int loss_ld_col(int lane, int u, int N) {
+    return PK ? 4 * min(lane + 64 * (u >> 2), (N >> 2) - 1) : min(lane + 64 * u, N - 1);
+}
+// x[] = the row at p (columns beyond N: unspecified - the callers select on loss_live)
+template <int NPER, bool PK>
+__device__ __forceinline__ void loss_row_load(const float *p, int lane, int N, float (&x)[NPER]) {
+    if constexpr (PK) {
+        static_assert(NPER % 4 == 0, "packs of four columns");
+#pragma unroll
+        for (int q = 0; q < NPER / 4; ++q) {
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(p + loss_ld_col<true>(lane, 4 * q, N));
+            x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < NPER; ++u) x[u] = p[loss_ld_col<false>(lane, u, N)];
+    }
+}
+template <int NPER, bool PK>
+__device__ __forceinline__ void loss_row_store(float *p, int lane, int N, const float (&x)[NPER]) {
+    if constexpr (PK) {
+#pragma unroll
+        for (int q = 0; q < NPER / 4; ++q)
+            if (loss_live<true>(lane, 4 * q, N)) {
+                f32x4 v; v.x = x[4 * q]; v.y = x[4 * q + 1]; v.z = x[4 * q + 2]; v.w = x[4 * q + 3];
+                *reinterpret_cast<f32x4 *>(p + loss_col<true>(lane, 4 * q)) = v;
+            }
+    } else {
+#pragma unroll
+        for (int u = 0; u < NPER; ++u) if (loss_live<false>(lane, u, N)) p[loss_col<false>(lane, u)] = x[u];
+    }
+}
+
+// nv[u] = score of column loss_col<PK>(lane, u) of row i (0 beyond N and in the masked diagonal column); w = edge weight,
+// p = positive score (read only by the pairwise / !skip_pos variants).  Writes dL/dn over the row (a.dneg, TransE_l2:
+// pre-divided by the distance), the optional score copy, the row's loss terms and the running sums.  slot2: where this row's
+// share of the total goes in the running sums (the stand-alone kernel: the row's own slot; the in-launch variant: a slot the
+// edge half of the same launch does not touch).
+// The arithmetic runs unpredicated on every slot, in passes over the slots (independent chains next to each other: a
+// transcendental's result is not the next instruction's operand); dead slots are taken out by selects where they would
+// enter a sum and by the stores' predicate.  Per-row factors (weight, 1/B, 1/Z or 1/N) are folded into ONE multiplier.
+template <int NPER, bool PK>
 __device__ __forceinline__ void loss_row_regs(const LossArgs &a, int64_t i, float (&nv)[NPER], float w, float p, int lane,
                                               int slot2) {
     using namespace kge;
     const int N = a.N;
     float *dn = a.dneg + i * (int64_t)N;
-    float *cp = a.neg_copy ? a.neg_copy + i * (int64_t)N : nullptr;
     const int jd = a.diag_chunk > 0 ? (int)(i % a.diag_chunk) : -1;
-    const float invB = 1.f / (float)a.B;
+    const float invB = a.inv_B;
     const int slot = (int)(i & (KGE_ACC_SLOTS - 1));
+    float g[NPER];
+    if (a.neg_copy) loss_row_store<NPER, PK>(a.neg_copy + i * (int64_t)N, lane, N, nv);
     if (a.pairwise) {   // loss.py:76-80
         const float sc = w / ((float)a.B * (float)N);
         float lsum = 0.f, dsum = 0.f;
 #pragma unroll
         for (int u = 0; u < NPER; ++u) {
-            const int j = lane + 64 * u;
-            if (j < N) {
-                float val, dv;
-                criterion_fast(a.genre, p - nv[u], 1.f, a.margin, val, dv);
-                lsum += val * sc;
-                const float dd = dv * sc;
-                dsum += dd;
-                if (cp) cp[j] = nv[u];
-                float g = -dd;
-                if (a.l2_scale) { const float d = a.gamma - nv[u]; g = d > 1e-15f ? g / d : 0.f; }
-                if (a.clampv > 0.f && fabsf(nv[u]) >= a.clampv) g = 0.f;
-                dn[j] = j == jd ? 0.f : g;
-            }
+            float val, dv;
+            criterion_fast(a.genre, p - nv[u], 1.f, a.margin, val, dv);
+            const bool live = loss_live<PK>(lane, u, N);
+            lsum += live ? val * sc : 0.f;
+            const float dd = dv * sc;
+            dsum += live ? dd : 0.f;
+            g[u] = -dd;
         }
+#pragma unroll
+        for (int u = 0; u < NPER; ++u) {
+            if (a.l2_scale) { const float d = a.gamma - nv[u]; g[u] = d > 1e-15f ? g[u] * __builtin_amdgcn_rcpf(d) : 0.f; }
+            if (a.clampv > 0.f && fabsf(nv[u]) >= a.clampv) g[u] = 0.f;
+            if (loss_col<PK>(lane, u) == jd) g[u] = 0.f;
+        }
+        loss_row_store<NPER, PK>(dn, lane, N, g);
         lsum = wave_sum(lsum);
         dsum = wave_sum(dsum);
         if (lane == 0) {
@@ -69,38 +120,94 @@ __device__ __forceinline__ void loss_row_regs(const LossArgs &a, int64_t i, floa
         }
     }
     const float neg_label = a.genre == KGE_LOSS_BCE ? 0.f : -1.f;
-    float mx = -INFINITY, Z = 1.f;
-    float ex[NPER];
-    if (a.adv) {   // softmax(neg * T) over the row, detached (loss.py:87-88)
+    // the criterion does not wait for the softmax: its transcendentals fill the max reduction's shadow
+    float nl[NPER];
 #pragma unroll
-        for (int u = 0; u < NPER; ++u) if (lane + 64 * u < N) mx = fmaxf(mx, nv[u] * a.adv_temp);
+    for (int u = 0; u < NPER; ++u) criterion_fast(a.genre, nv[u], neg_label, a.margin, nl[u], g[u]);
+    // sums: one partial per group of slots that are live or dead together (PK: a pack; strided: a slot), ONE select each
+    constexpr int GS = PK ? 4 : 1;
+    // element-wise multiplies / adds on the two PAIRS of a pack, spelled as packed fp32 (v_pk_mul / v_pk_add / v_pk_fma_f32: one
+    // issue slot for two columns) instead of left to the vectoriser; the same operations in the same order as the scalar form
+    constexpr int PW = PK ? 2 : 1;
+    float acc = 0.f, rs;         // rs: the row's multiplier of the attention weights - 1/Z (-adv) or 1/N
+    if (a.adv) {   // softmax(neg * T) over the row, detached (loss.py:87-88)
+        float mx = -INFINITY;
+#pragma unroll
+        for (int q = 0; q < NPER; q += GS) {
+            float m = nv[q] * a.adv_temp;
+#pragma unroll
+            for (int u = q + 1; u < q + GS; ++u) m = fmaxf(m, nv[u] * a.adv_temp);
+            mx = fmaxf(mx, loss_live<PK>(lane, q, N) ? m : -INFINITY);
+        }
         mx = wave_max(mx);
         float z = 0.f;
 #pragma unroll
-        for (int u = 0; u < NPER; ++u) {
-            ex[u] = (lane + 64 * u < N) ? __expf(nv[u] * a.adv_temp - mx) : 0.f;
-            z += ex[u];
+        for (int q = 0; q < NPER; q += GS) {
+            float zq = 0.f, aq = 0.f;
+#pragma unroll
+            for (int u = q; u < q + GS; u += PW) {
+                if constexpr (PW == 2) {
+                    const f32x2 sv = {nv[u], nv[u + 1]};
+                    const f32x2 t = sv * a.adv_temp - mx;
+                    const f32x2 ex = {__expf(t.x), __expf(t.y)};
+                    f32x2 gg = {g[u], g[u + 1]};
+                    gg *= ex;
+                    g[u] = gg.x; g[u + 1] = gg.y;
+                    zq += ex.x; zq += ex.y;
+                    aq = fmaf(ex.x, nl[u], aq); aq = fmaf(ex.y, nl[u + 1], aq);
+                } else {
+                    const float ex = __expf(nv[u] * a.adv_temp - mx);
+                    zq += ex;
+                    aq = fmaf(ex, nl[u], aq);
+                    g[u] *= ex;
+                }
+            }
+            const bool live = loss_live<PK>(lane, q, N);
+            z += live ? zq : 0.f;
+            acc += live ? aq : 0.f;
         }
-        Z = wave_sum(z);
+        // Z and the loss sum reduced side by side (two independent DPP chains); 1/Z: ONE v_rcp_f32 per row (1 ulp)
+        z = wave_sum(z);
+        acc = wave_sum(acc);
+        rs = __builtin_amdgcn_rcpf(z);
+    } else {
+#pragma unroll
+        for (int q = 0; q < NPER; q += GS) {
+            float aq = 0.f;
+#pragma unroll
+            for (int u = q; u < q + GS; ++u) aq += nl[u];
+            acc += loss_live<PK>(lane, q, N) ? aq : 0.f;
+        }
+        acc = wave_sum(acc);
+        rs = a.inv_N;
     }
-    const float invZ = 1.f / Z, invN = 1.f / (float)N;
-    float acc = 0.f;
+    const float ws = w * rs;
+    acc = acc * ws * invB;
+    const float gs = ws * 0.5f * invB;
+#pragma unroll
+    for (int u = 0; u < NPER; u += PW) {
+        if constexpr (PW == 2) {
+            f32x2 gg = {g[u], g[u + 1]};
+            gg *= gs;
+            if (a.l2_scale) {
+                const f32x2 sv = {nv[u], nv[u + 1]};
+                const f32x2 d = a.gamma - sv;
+                const f32x2 r = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+                gg *= r;
+                gg.x = d.x > 1e-15f ? gg.x : 0.f; gg.y = d.y > 1e-15f ? gg.y : 0.f;
+            }
+            g[u] = gg.x; g[u + 1] = gg.y;
+        } else {
+            g[u] *= gs;
+            if (a.l2_scale) { const float d = a.gamma - nv[u]; g[u] = d > 1e-15f ? g[u] * __builtin_amdgcn_rcpf(d) : 0.f; }
+        }
+    }
 #pragma unroll
     for (int u = 0; u < NPER; ++u) {
-        const int j = lane + 64 * u;
-        if (j < N) {
-            float nl, dnl;
-            criterion_fast(a.genre, nv[u], neg_label, a.margin, nl, dnl);
-            const float A = a.adv ? ex[u] * invZ : invN;
-            acc += A * nl * w;
-            float g = dnl * w * A * 0.5f * invB;
-            if (cp) cp[j] = nv[u];
-            if (a.l2_scale) { const float d = a.gamma - nv[u]; g = d > 1e-15f ? g / d : 0.f; }
-            if (a.clampv > 0.f && fabsf(nv[u]) >= a.clampv) g = 0.f;
-            dn[j] = j == jd ? 0.f : g;
-        }
+        if (a.clampv > 0.f && fabsf(nv[u]) >= a.clampv) g[u] = 0.f;
+        if (loss_col<PK>(lane, u) == jd) g[u] = 0.f;
     }
-    acc = wave_sum(acc) * invB;
+    loss_row_store<NPER, PK>(dn, lane, N, g);
     if (lane == 0) {
         if (a.row_neg) a.row_neg[i] = acc;
         if (a.acc) {

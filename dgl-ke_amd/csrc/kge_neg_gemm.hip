@@ -381,6 +381,56 @@ static inline size_t fwd_lds_bytes(int D) { return (size_t)16 * fwd_lds_stride(D
 // loss-fold instance (round 4): + |a_i|^2 of the 16 rows + the "this workgroup arrived last" word, in the SAME shared array
 static inline size_t fwd_lds_bytes_lf(int D) { return fwd_lds_bytes(D) + 32 * sizeof(float); }
 
+// the loss rows of one strip's last arriver: this wavefront's four rows (row0 ..) of chunk c, in the column layout of
+// kge_loss_body.hpp.  All four rows requested together, L1-bypassing (the lines were written by other CUs - possibly other XCDs -
+// during this launch); indices clamped instead of predicated (no branch joins in front of the waits).  PK: one 16-byte sc1
+// load per row - the compiler does not count a load it cannot see, so the loads and their wait are one asm statement.
+template <bool PK>
+__device__ __forceinline__ void lf_loss_rows(const GemmArgs &a, const LossArgs &la, int c, int row0, int lane) {
+    constexpr int NPER = 4;                   // N <= 256 (checked by the launcher)
+    const int N = la.N;
+    float nv[4][NPER], wr[4];
+    // (the weights are requested first: the score round's wait below covers them)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wr[r] = la.w ? la.w[(int64_t)c * a.chunk + min(row0 + r, a.chunk - 1)] : 1.f;
+    if constexpr (PK) {
+        const float *q[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            q[r] = a.S + ((int64_t)c * a.chunk + min(row0 + r, a.chunk - 1)) * N + loss_ld_col<true>(lane, 0, N);
+        f32x4 v0, v1, v2, v3;
+        // four loads and their wait in ONE statement: the compiler sees the results only behind the wait
+        asm volatile("global_load_dwordx4 %0, %4, off sc1\n\t"
+                     "global_load_dwordx4 %1, %5, off sc1\n\t"
+                     "global_load_dwordx4 %2, %6, off sc1\n\t"
+                     "global_load_dwordx4 %3, %7, off sc1\n\t"
+                     "s_waitcnt vmcnt(0)"
+                     : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3) : "v"(q[0]), "v"(q[1]), "v"(q[2]), "v"(q[3]) : "memory");
+        const f32x4 v[4] = {v0, v1, v2, v3};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { nv[r][0] = v[r].x; nv[r][1] = v[r].y; nv[r][2] = v[r].z; nv[r][3] = v[r].w; }
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int64_t gi = (int64_t)c * a.chunk + min(row0 + r, a.chunk - 1);
+#pragma unroll
+            for (int u = 0; u < NPER; ++u)
+                nv[r][u] = __hip_atomic_load(a.S + gi * N + loss_ld_col<false>(lane, u, N), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (row0 + r < a.chunk) {             // (wave-uniform)
+            const int64_t gi = (int64_t)c * a.chunk + row0 + r;
+#pragma unroll
+            for (int u = 0; u < NPER; ++u) if (!loss_live<PK>(lane, u, N)) nv[r][u] = 0.f;
+            // the edge half of this launch adds the row's positive share to slot gi of the running total: this half takes
+            // the slot B further on (one add per slot and launch keeps the sums order-independent while 2 B <= KGE_ACC_SLOTS)
+            loss_row_regs<NPER, PK>(la, gi, nv[r], wr[r], 0.f, lane, (int)((gi + la.B) & (KGE_ACC_SLOTS - 1)));
+        }
+    }
+}
+
 // LF (round 4, the strict step's 3-launch form): the loss rows of a 16-row strip run INSIDE this launch.  The tiles store final
 // scores (TransE_l2: |a_i|^2 from the LDS tile, |b_j|^2 accumulated from the B fragments under the MFMAs) write-through, every
 // workgroup of the strip draws an arrival ticket, and the workgroup that arrives last runs LossGenerator on the strip's rows
@@ -585,33 +635,9 @@ __device__ __forceinline__ void neg_fwd_gemm_ldsa_body(const GemmArgs &a, int ti
         if (!*lastw) return;
         LossArgs la = *lap;
         if constexpr (LLEAN) loss_args_lean(la);
-        constexpr int NPER = 4;                   // N <= 256 (checked by the launcher)
-        const int N = la.N;
-        const int row0 = it * 16 + wv * 4;        // this wavefront's four rows of the strip
-        // all four rows requested together, L1-bypassing (the lines were written by other CUs - possibly other XCDs - during this
-        // launch); indices clamped instead of predicated (no branch joins in front of the waits)
-        float nv[4][NPER];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int64_t gi = (int64_t)c * a.chunk + min(row0 + r, a.chunk - 1);
-#pragma unroll
-            for (int u = 0; u < NPER; ++u)
-                nv[r][u] = __hip_atomic_load(a.S + gi * N + min(lane + 64 * u, N - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        float wr[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) wr[r] = la.w ? la.w[(int64_t)c * a.chunk + min(row0 + r, a.chunk - 1)] : 1.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            if (row0 + r < a.chunk) {             // (wave-uniform)
-                const int64_t gi = (int64_t)c * a.chunk + row0 + r;
-#pragma unroll
-                for (int u = 0; u < NPER; ++u) if (lane + 64 * u >= N) nv[r][u] = 0.f;
-                // the edge half of this launch adds the row's positive share to slot gi of the running total: this half takes
-                // the slot B further on (one add per slot and launch keeps the sums order-independent while 2 B <= KGE_ACC_SLOTS)
-                loss_row_regs<NPER>(la, gi, nv[r], wr[r], 0.f, lane, (int)((gi + la.B) & (KGE_ACC_SLOTS - 1)));
-            }
-        }
+        // same column layout as the loss launch would take for this N (bit-identical rows)
+        if (la.pk) lf_loss_rows<true>(a, la, c, it * 16 + wv * 4, lane);
+        else lf_loss_rows<false>(a, la, c, it * 16 + wv * 4, lane);
     }
 }
 
@@ -712,7 +738,9 @@ bool neg_fwd_loss_fold_supported(int model, int C, int chunk, int N, int d_e, in
     return (int64_t)C * ((chunk + 15) / 16) <= KGE_TICKET_INTS;
 }
 
-int launch_neg_fwd_gemm_with_edge_loss(const GemmArgs &a, const EdgeFwdArgs &e, const LossArgs &la, int *tickets, hipStream_t s) {
+int launch_neg_fwd_gemm_with_edge_loss(const GemmArgs &a, const EdgeFwdArgs &e, const LossArgs &la_, int *tickets, hipStream_t s) {
+    LossArgs la = la_;
+    loss_fill_host(la);
     if (a.C == 0 || a.PM || !a.xbase || !a.rbase || !a.xidx || !a.ridx || !tickets || a.lds_off) return KGE_ERR_ARG;
     if (!neg_fwd_loss_fold_supported(a.model, a.C, a.chunk, a.N, a.D, e.d_r) || e.model != a.model || e.d_e != a.D) return KGE_ERR_ARG;
     if (e.src.em.n || e.src.rm.n || e.nd_own || la.pairwise || !la.skip_pos || la.l2_raw || la.diag_chunk > 0 || la.neg != a.S ||

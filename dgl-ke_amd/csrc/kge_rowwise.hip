@@ -583,61 +583,66 @@ __global__ __launch_bounds__(KGE_BLOCK) void loss_kernel(LossArgs a) {
 // (the arithmetic on the register-resident row lives in kge_loss_body.hpp: the forward tiles' last arriver runs the same code)
 // Leading plain parameters (kernel-argument preload): what a wavefront needs to request its
 // score row, |b|^2 row, |a|^2, positive score and weight arrives in SGPRs with the wavefront; the struct follows under that round.
-template <int NPER, bool LEAN, bool RAW>
+// PK: the packed column layout of kge_loss_body.hpp (N % 4 == 0, 16-byte aligned rows): the score row, the |b|^2 row and the
+// dL/dn row move as ONE 16-byte access per lane and pack
+template <int NPER, bool LEAN, bool RAW, bool PK>
 __global__ __launch_bounds__(KGE_BLOCK) void loss_kernel_reg(const float *neg, const float *bsq, const float *asq, const float *pos,
                                                              const float *w_, int B_, int N_, int l2_chunk, LossArgs a_in) {
     KGE_TL(2);
     LossArgs a = a_in;
     a.neg = neg; a.bsq = bsq; a.asq = asq; a.pos = pos; a.w = w_; a.B = B_; a.N = N_; a.l2_chunk = l2_chunk;
     if constexpr (LEAN) loss_args_lean(a);
-    const int64_t i = WAVE_ID();
-    if (i >= a.B) return;
+    if constexpr (RAW) a.l2_scale = 1;          // (checked by the launcher)
+    // the row index in an SGPR: row addresses and the chunk division are scalar work
+    const int i32 = (int)blockIdx.x * KGE_WAVES_PER_BLOCK + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (i32 >= a.B) return;
+    const int64_t i = i32;
     const int lane = LANE();
     const int N = a.N;
-    const float *n = a.neg + i * (int64_t)N;
     float nv[NPER];
     // neg_deg_sample: the positive edge itself sits in column i % chunk - score 0, no gradient
     const int jd = a.diag_chunk > 0 ? (int)(i % a.diag_chunk) : -1;
-#pragma unroll
-    for (int u = 0; u < NPER; ++u) { const int j = lane + 64 * u; nv[u] = (j < N && j != jd) ? n[j] : 0.f; }
+    loss_row_load<NPER, PK>(a.neg + i * (int64_t)N, lane, N, nv);
     float bq[RAW ? NPER : 1], asq_i = 0.f;
     if constexpr (RAW) {
-        const float *bqp = a.bsq + (i / a.l2_chunk) * (int64_t)N;
-#pragma unroll
-        for (int u = 0; u < NPER; ++u) { const int j = lane + 64 * u; bq[u] = j < N ? bqp[j] : 0.f; }
+        loss_row_load<NPER, PK>(a.bsq + (int64_t)((unsigned)i32 / (unsigned)a.l2_chunk) * N, lane, N, bq);
         asq_i = a.asq[i];
     }
     const float w = a.w ? a.w[i] : 1.f;
     const float p = a.pos[i];
-    if constexpr (RAW) {
 #pragma unroll
-        for (int u = 0; u < NPER; ++u) {
-            const int j = lane + 64 * u;
-            nv[u] = (j < N && j != jd) ? a.gamma - sqrtf(fmaxf(fmaf(-2.f, nv[u], asq_i + bq[u]), 1e-30f)) : 0.f;
-        }
+    for (int u = 0; u < NPER; ++u) {
+        if constexpr (RAW) nv[u] = a.gamma - sqrtf(fmaxf(fmaf(-2.f, nv[u], asq_i + bq[u]), 1e-30f));
+        if (!loss_live<PK>(lane, u, N) || loss_col<PK>(lane, u) == jd) nv[u] = 0.f;
     }
     KGE_TL_MARK(0);              // score row, positive score, weight have arrived
     // (the row's share of the running total: when the positive share comes from edge_fwd, B slots further on than edge_fwd's add -
     //  the same two adds as the strict step's in-launch loss rows, whose other half runs in the SAME launch)
-    loss_row_regs<NPER>(a, i, nv, w, p, lane, (int)((a.skip_pos ? i + a.B : i) & (KGE_ACC_SLOTS - 1)));
+    loss_row_regs<NPER, PK>(a, i, nv, w, p, lane, (int)((a.skip_pos ? i + a.B : i) & (KGE_ACC_SLOTS - 1)));
     KGE_TL_MARK(1);              // softmax, criterion, reductions done; gradient stores acknowledged
 }
 
-int launch_loss(const LossArgs &a, hipStream_t s) {
-    if (a.B == 0) return KGE_OK;
+int launch_loss(const LossArgs &a_, hipStream_t s) {
+    if (a_.B == 0) return KGE_OK;
+    if (a_.N <= 0) return KGE_ERR_ARG;
+    LossArgs a = a_;
+    loss_fill_host(a);
     const dim3 g(blocks_for_waves(a.B)), b(KGE_BLOCK);
     const bool lean = a.genre == KGE_LOSS_LOGSIGMOID && !a.pairwise && a.skip_pos && a.clampv == 0.f && !a.neg_copy &&
                       !a.row_pos && !a.row_neg && a.diag_chunk <= 0;
-    if (a.l2_raw && (!a.asq || !a.bsq || a.l2_chunk <= 0)) return KGE_ERR_ARG;
+    if (a.l2_raw && (!a.asq || !a.bsq || a.l2_chunk <= 0 || !a.l2_scale)) return KGE_ERR_ARG;
+    const bool pk = a.pk != 0;
 #define KGE_LOSS_H a.neg, a.bsq, a.asq, a.pos, a.w, a.B, a.N, a.l2_chunk, a        /* hot values twice: preloaded + in the struct */
-#define KGE_LOSS(N) do { if (a.l2_raw) { if (lean) hipLaunchKernelGGL((loss_kernel_reg<N, true, true>), g, b, 0, s, KGE_LOSS_H); \
-                                         else hipLaunchKernelGGL((loss_kernel_reg<N, false, true>), g, b, 0, s, KGE_LOSS_H); } \
-                         else if (lean) hipLaunchKernelGGL((loss_kernel_reg<N, true, false>), g, b, 0, s, KGE_LOSS_H); \
-                         else hipLaunchKernelGGL((loss_kernel_reg<N, false, false>), g, b, 0, s, KGE_LOSS_H); } while (0)
-    if (a.N <= 64) KGE_LOSS(1);
-    else if (a.N <= 128) KGE_LOSS(2);
-    else if (a.N <= 256) KGE_LOSS(4);
-    else if (a.N <= 512) KGE_LOSS(8);
+#define KGE_LOSS(N, PK) do { if (a.l2_raw) { if (lean) hipLaunchKernelGGL((loss_kernel_reg<N, true, true, PK>), g, b, 0, s, KGE_LOSS_H); \
+                                             else hipLaunchKernelGGL((loss_kernel_reg<N, false, true, PK>), g, b, 0, s, KGE_LOSS_H); } \
+                             else if (lean) hipLaunchKernelGGL((loss_kernel_reg<N, true, false, PK>), g, b, 0, s, KGE_LOSS_H); \
+                             else hipLaunchKernelGGL((loss_kernel_reg<N, false, false, PK>), g, b, 0, s, KGE_LOSS_H); } while (0)
+    if (pk && a.N <= 256) KGE_LOSS(4, true);           // one pack: 4 .. 256 columns on 1 .. 64 lanes
+    else if (pk && a.N <= 512) KGE_LOSS(8, true);
+    else if (a.N <= 64) KGE_LOSS(1, false);
+    else if (a.N <= 128) KGE_LOSS(2, false);
+    else if (a.N <= 256) KGE_LOSS(4, false);
+    else if (a.N <= 512) KGE_LOSS(8, false);
     else hipLaunchKernelGGL(loss_kernel, g, b, 0, s, a);
 #undef KGE_LOSS
 #undef KGE_LOSS_H
