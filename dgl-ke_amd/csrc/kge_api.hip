@@ -419,6 +419,9 @@ struct StepCall {
     EdgeFwdArgs *build_prep = nullptr;       // PH_PREP: fill the launch arguments instead of launching
     const EdgeFwdArgs *co_prep = nullptr;    // PH_BWD: the NEXT step's PREP to run alongside the backward
     const SmpTail *tail = nullptr;           // the sampler job this step's launches carry as tail workgroups
+    const kge_known *known = nullptr;        // known triples left out of the negatives (kge_step_*_known): PH_FWD builds the pair mask
+    uint32_t *known_mask = nullptr;          // ... into this buffer of the caller's, and the stand-alone loss kernel reads it
+    size_t known_mask_bytes = 0;
 };
 
 static StepCall phase_call(int phases) { StepCall c; c.phases = phases; return c; }
@@ -477,6 +480,42 @@ static size_t carve_step(Carver &cv, StepBufs &w, const kge_hparams *hp, int B_,
 
 size_t kge_step_workspace_bytes(const kge_hparams *hp, int B, int C, int chunk, int N, int UE, int UR) {
     Carver cv; StepBufs w; return carve_step(cv, w, hp, B, C, chunk, N, UE, UR, false);
+}
+
+// ---- known triples left out of the negatives (kge_known.hip) ----
+size_t kge_known_mask_bytes(int B, int N) {
+    if (B <= 0 || N <= 0) return 0;
+    return (size_t)B * (size_t)((N + 31) / 32) * sizeof(uint32_t);
+}
+
+static int check_known(const kge_known *k, const uint32_t *mask, size_t mask_bytes, int B, int N) {
+    if (k->n_rel <= 0 || k->m_tail < 0 || k->m_head < 0 || (k->m_tail > 0 && (!k->keys_tail || !k->vals_tail)) ||
+        (k->m_head > 0 && (!k->keys_head || !k->vals_head)))
+        return fail(KGE_ERR_ARG, "kge_known: n_rel > 0 and both sorted sides (keys, vals, m >= 0) are required");
+    if (!mask || mask_bytes < kge_known_mask_bytes(B, N))
+        return fail(KGE_ERR_ARG, "kge_known: the mask buffer is missing or smaller than kge_known_mask_bytes(B, N) (%zu < %zu)", mask_bytes,
+                    kge_known_mask_bytes(B, N));
+    return KGE_OK;
+}
+
+static KnownMaskArgs known_args(const kge_batch *b, const kge_known *k, uint32_t *mask) {
+    KnownMaskArgs a{};
+    a.B = b->B; a.chunk = b->chunk; a.N = b->N; a.neg_head = b->neg_head;
+    a.h = b->h_gid; a.r = b->rel_ids; a.t = b->t_gid; a.neg = b->neg_ids; a.counts_dev = b->counts_dev;
+    a.keys[0] = k->keys_tail; a.vals[0] = k->vals_tail; a.m[0] = k->m_tail;
+    a.keys[1] = k->keys_head; a.vals[1] = k->vals_head; a.m[1] = k->m_head;
+    a.n_rel = k->n_rel; a.mask = mask;
+    return a;
+}
+
+int kge_known_neg_mask(const kge_batch *b, const kge_known *known, uint32_t *mask, size_t mask_bytes, void *stream) {
+    if (!b || !known) return fail(KGE_ERR_ARG, "kge_known_neg_mask: null argument");
+    if (b->B <= 0 || b->C <= 0 || b->chunk <= 0 || b->N <= 0 || (int64_t)b->C * b->chunk != b->B)
+        return fail(KGE_ERR_ARG, "kge_known_neg_mask: need C*chunk == B (B=%d C=%d chunk=%d)", b->B, b->C, b->chunk);
+    if (!b->h_gid || !b->t_gid || !b->rel_ids || !b->neg_ids) return fail(KGE_ERR_ARG, "kge_known_neg_mask: null batch pointer");
+    if (int rc = check_known(known, mask, mask_bytes, b->B, b->N)) return rc;
+    KGE_TRY(launch_known_mask(known_args(b, known, mask), (hipStream_t)stream));
+    return KGE_OK;
 }
 
 // every path decision of one step call, from its inputs alone
@@ -652,6 +691,16 @@ int Step::setup(void *ws, size_t ws_bytes) {
     if (c.emit && out && out->g_pos_ent && (c.emit->ld_e > 0 || c.emit->ent_by_id))
         return fail(KGE_ERR_ARG, "g_pos_ent output cannot be combined with a strided emit or with messages addressed by row id");
     if (need > ws_bytes) return fail(KGE_ERR_WORKSPACE, "kge_step: workspace too small (%zu < %zu)", ws_bytes, need);
+    if (c.known) {
+        // the known pairs are taken out by the STAND-ALONE loss kernel: every step form whose loss runs elsewhere is refused, and so is
+        // neg_deg_sample (its in-batch columns are positives of the chunk by construction: the two do not combine)
+        if (hp->flags & (KGE_FLAG_FUSED_LOSS | KGE_FLAG_LOSS_IN_FWD))
+            return fail(KGE_ERR_ARG, "known-triple exclusion: KGE_FLAG_FUSED_LOSS / KGE_FLAG_LOSS_IN_FWD run the loss outside the stand-alone kernel");
+        if (p.nd) return fail(KGE_ERR_ARG, "known-triple exclusion: not available with KGE_FLAG_NEG_DEG_SAMPLE");
+        if (sh || c.emit || p.pipelined)
+            return fail(KGE_ERR_ARG, "known-triple exclusion: strict single-table step only (no gradient emission, sharding or async pipeline)");
+        if (int rc = check_known(c.known, c.known_mask, c.known_mask_bytes, b->B, b->N)) return rc;
+    }
     if (p.pipelined && (sh || c.emit || p.transr || p.rescal))
         return fail(KGE_ERR_ARG, "kge_step_async: not available for RESCAL / TransR and the sharded / gradient-emitting steps");
     // a batch of the NEXT group is built by tail workgroups of this step's first, backward and update launches
@@ -808,11 +857,12 @@ int Step::phase_fwd() {
         } else KGE_TRY(launch_neg_fwd_pair(na, s));
     }
     if (p.fused_loss || p.fold_loss) return KGE_OK;  // no stand-alone loss kernel: the backward GEMM / the forward tiles run it
+    if (c.known) KGE_TRY(launch_known_mask(known_args(b, c.known, c.known_mask), s));      // one extra launch ahead of the loss
     LossArgs la; fill_step_loss(la);
     la.row_pos = p.want4 ? w.row_pos : nullptr;
     if (p.merged_fwd && p.is_l2) { la.l2_raw = 1; la.l2_chunk = b->chunk; la.asq = w.asq; la.bsq = w.bsq; }
     la.skip_pos = (p.pairwise || p.rescal || p.transr) ? 0 : 1; la.diag_chunk = p.nd ? b->chunk : 0;  // RESCAL / TransR: no edge_fwd -> positive part here
-    KGE_TRY(launch_loss(la, s));
+    KGE_TRY(launch_loss(la, s, c.known ? c.known_mask : nullptr));
     return KGE_OK;
 }
 
@@ -1030,9 +1080,10 @@ size_t kge_sampler_tail_scratch_bytes(int B, int C, int N, int64_t n_ent) {
     return (size_t)tail_scratch(B, C * N, n_ent > ((int64_t)1 << (32 - SP_CODE_BITS))).total;
 }
 
-int kge_step_fused_sampling(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
-                            size_t ws_bytes, const kge_sampler_job *job, void *stream) {
-    if (!job) return run_step(hp, tb, b, out, ws, ws_bytes, stream);
+// the strict step with a known-triple index: kge_step_fused (job NULL) / kge_step_fused_sampling + the pair mask in front of the loss
+static int step_sampling(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
+                         size_t ws_bytes, const kge_sampler_job *job, StepCall c, void *stream) {
+    if (!job) return run_step(hp, tb, b, out, ws, ws_bytes, stream, c);
     if (!job->heads || !job->rels || !job->tails || !job->state || !job->slot || !job->scratch || job->n_train <= 0 || job->n_ent <= 0 ||
         job->B <= 0 || job->C <= 0 || job->chunk <= 0 || job->N <= 0 || job->C * job->chunk != job->B || job->k < 0 || job->advance < 0)
         return fail(KGE_ERR_ARG, "kge_step_fused_sampling: bad sampler job");
@@ -1046,8 +1097,21 @@ int kge_step_fused_sampling(const kge_hparams *hp, const kge_tables *tb, const k
     t.a.B = job->B; t.a.C = job->C; t.a.chunk = job->chunk; t.a.N = job->N; t.a.seed = job->seed; t.a.state = job->state;
     t.a.slots = (char *)job->slot; t.a.slot_bytes = 0; t.a.preperm = job->pre_permuted ? 1 : 0; t.slot3 = (char *)job->prev_slot;
     t.scratch = (char *)job->scratch; t.k = job->k; t.advance = job->advance; t.phase = 1;
-    StepCall c; c.tail = &t;
+    c.tail = &t;
     return run_step(hp, tb, b, out, ws, ws_bytes, stream, c);
+}
+
+int kge_step_fused_sampling(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
+                            size_t ws_bytes, const kge_sampler_job *job, void *stream) {
+    return step_sampling(hp, tb, b, out, ws, ws_bytes, job, StepCall{}, stream);
+}
+
+int kge_step_fused_known(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
+                         size_t ws_bytes, const kge_sampler_job *job, const kge_known *known, uint32_t *mask, size_t mask_bytes,
+                         void *stream) {
+    StepCall c;
+    if (known) { c.known = known; c.known_mask = mask; c.known_mask_bytes = mask_bytes; }
+    return step_sampling(hp, tb, b, out, ws, ws_bytes, job, c, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1156,6 +1220,21 @@ int kge_step_phase(const kge_hparams *hp, const kge_tables *tb, const kge_batch 
     if (phases & KGE_PHASE_BACKWARD) ph |= PH_BWD;
     if (phases & KGE_PHASE_UPDATE) ph |= PH_UPDATE;
     return run_step(hp, tb, b, out, ws, ws_bytes, stream, phase_call(ph | PH_STRICT));
+}
+
+int kge_step_phase_known(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
+                         size_t ws_bytes, int phases, const kge_known *known, uint32_t *mask, size_t mask_bytes, void *stream) {
+    if (!known) return kge_step_phase(hp, tb, b, out, ws, ws_bytes, phases, stream);
+    if (phases <= 0 || phases > (KGE_PHASE_GATHER | KGE_PHASE_FORWARD | KGE_PHASE_BACKWARD | KGE_PHASE_UPDATE))
+        return fail(KGE_ERR_ARG, "kge_step_phase_known: bad phase mask %d", phases);
+    int ph = 0;
+    if (phases & KGE_PHASE_GATHER) ph |= PH_PREP;
+    if (phases & KGE_PHASE_FORWARD) ph |= PH_FWD;
+    if (phases & KGE_PHASE_BACKWARD) ph |= PH_BWD;
+    if (phases & KGE_PHASE_UPDATE) ph |= PH_UPDATE;
+    StepCall c = phase_call(ph | PH_STRICT);
+    c.known = known; c.known_mask = mask; c.known_mask_bytes = mask_bytes;
+    return run_step(hp, tb, b, out, ws, ws_bytes, stream, c);
 }
 
 int kge_step_grads(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, const kge_emit *emit,

@@ -535,7 +535,19 @@ int launch_gather_rows_sharded(float *const *shard_rows, int n_shards, int64_t p
                                const int64_t *idx, int64_t n, float *out, hipStream_t s);
 int launch_edge_fwd(const EdgeFwdArgs &a, hipStream_t s);
 int launch_edge_bwd(const EdgeBwdArgs &a, hipStream_t s);
-int launch_loss(const LossArgs &a, hipStream_t s);
+// known: the known-pair bit mask [B][ceil(N / 32)] of kge_known_neg_mask or null.  It travels NEXT TO LossArgs (a trailing kernel
+// parameter of the stand-alone loss kernels) and not inside it: the struct has no 8-byte hole, and a longer struct would move the
+// arguments that follow it in the in-launch loss of kge_neg_gemm.hip
+int launch_loss(const LossArgs &a, hipStream_t s, const uint32_t *known = nullptr);
+struct KnownMaskArgs {               // kge_known.hip: one bit per (positive row, negative column) whose corrupted triple is known
+    int B, chunk, N, neg_head;
+    const int64_t *h, *r, *t, *neg;  // [B] x 3, [C * N]
+    const int32_t *counts_dev;       // device-built plans: counts_dev[2] is the step's corrupt-head flag; else neg_head above
+    const int64_t *keys[2], *vals[2]; int64_t m[2];   // [0] tail side (key h * R + r -> tails), [1] head side (key t * R + r -> heads)
+    int64_t n_rel;
+    uint32_t *mask;                  // [B][ceil(N / 32)]
+};
+int launch_known_mask(const KnownMaskArgs &a, hipStream_t s);
 int launch_finalize(const FinalizeArgs &a, hipStream_t s);
 struct SmpTail;                  // sampler tail workgroups riding on a step launch (kge_sampler_tail.hpp); null / phase 0: none
 int launch_update(const UpdateArgs &a, hipStream_t s, const SmpTail *tail = nullptr);

@@ -64,13 +64,15 @@ __device__ __forceinline__ void loss_row_store(float *p, int lane, int N, const 
 // p = positive score (read only by the pairwise / !skip_pos variants).  Writes dL/dn over the row (a.dneg, TransE_l2:
 // pre-divided by the distance), the optional score copy, the row's loss terms and the running sums.  slot2: where this row's
 // share of the total goes in the running sums (the stand-alone kernel: the row's own slot; the in-launch variant: a slot the
-// edge half of the same launch does not touch).
+// edge half of the same launch does not touch).  kn: bit u set = slot u is a KNOWN pair (kge_known_neg_mask; the caller has put
+// KGE_KNOWN_SCORE into nv[u]): its gradient is forced to 0.0f where the masked diagonal column's is.  0 (every caller but the
+// stand-alone kernel with a mask): folded away.
 // The arithmetic runs unpredicated on every slot, in passes over the slots (independent chains next to each other: a
 // transcendental's result is not the next instruction's operand); dead slots are taken out by selects where they would
 // enter a sum and by the stores' predicate.  Per-row factors (weight, 1/B, 1/Z or 1/N) are folded into ONE multiplier.
 template <int NPER, bool PK>
 __device__ __forceinline__ void loss_row_regs(const LossArgs &a, int64_t i, float (&nv)[NPER], float w, float p, int lane,
-                                              int slot2) {
+                                              int slot2, unsigned kn = 0u) {
     using namespace kge;
     const int N = a.N;
     float *dn = a.dneg + i * (int64_t)N;
@@ -96,7 +98,7 @@ __device__ __forceinline__ void loss_row_regs(const LossArgs &a, int64_t i, floa
         for (int u = 0; u < NPER; ++u) {
             if (a.l2_scale) { const float d = a.gamma - nv[u]; g[u] = d > 1e-15f ? g[u] * __builtin_amdgcn_rcpf(d) : 0.f; }
             if (a.clampv > 0.f && fabsf(nv[u]) >= a.clampv) g[u] = 0.f;
-            if (loss_col<PK>(lane, u) == jd) g[u] = 0.f;
+            if (loss_col<PK>(lane, u) == jd || ((kn >> u) & 1u)) g[u] = 0.f;
         }
         loss_row_store<NPER, PK>(dn, lane, N, g);
         lsum = wave_sum(lsum);
@@ -205,7 +207,7 @@ __device__ __forceinline__ void loss_row_regs(const LossArgs &a, int64_t i, floa
 #pragma unroll
     for (int u = 0; u < NPER; ++u) {
         if (a.clampv > 0.f && fabsf(nv[u]) >= a.clampv) g[u] = 0.f;
-        if (loss_col<PK>(lane, u) == jd) g[u] = 0.f;
+        if (loss_col<PK>(lane, u) == jd || ((kn >> u) & 1u)) g[u] = 0.f;
     }
     loss_row_store<NPER, PK>(dn, lane, N, g);
     if (lane == 0) {

@@ -482,7 +482,7 @@ int launch_edge_bwd(const EdgeBwdArgs &a, hipStream_t s) {
 // ------------------------------------------------------------------------------------------
 // loss + d loss / d score.  One wavefront per positive edge (row of the [B,N] negative scores).
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(KGE_BLOCK) void loss_kernel(LossArgs a) {
+__global__ __launch_bounds__(KGE_BLOCK) void loss_kernel(LossArgs a, const uint32_t *known) {
     const int64_t i = WAVE_ID();
     if (i >= a.B) return;
     const int lane = LANE();
@@ -495,6 +495,10 @@ __global__ __launch_bounds__(KGE_BLOCK) void loss_kernel(LossArgs a) {
     const float invB = 1.f / (float)a.B;
     // neg_deg_sample: the positive edge itself sits in column i % chunk - score 0, no gradient (general_models.py:401, 429-432)
     const int jd = a.diag_chunk > 0 ? (int)(i % a.diag_chunk) : -1;
+    // known pairs (kge_known_neg_mask): bit j of the row's mask words - the score becomes KGE_KNOWN_SCORE, the gradient 0
+    const uint32_t *km = known ? known + i * (int64_t)((N + 31) >> 5) : nullptr;
+    auto kn = [&](int j) { return km && ((km[j >> 5] >> (j & 31)) & 1u); };
+    auto sc_of = [&](int j) { return j == jd ? 0.f : kn(j) ? KGE_KNOWN_SCORE : n[j]; };
     if (a.l2_raw) {     // merged forward launch: the row holds raw products - rebuild the scores in place first (score_fun.py:26-34)
         const float as = a.asq[i];
         const float *bq = a.bsq + (i / a.l2_chunk) * (int64_t)N;
@@ -506,7 +510,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void loss_kernel(LossArgs a) {
         const float sc = w / ((float)a.B * (float)N);
         float lsum = 0.f, dsum = 0.f;
         for (int j = lane; j < N; j += 64) {
-            const float nv = j == jd ? 0.f : n[j];
+            const float nv = sc_of(j);
             float val, dv;
             criterion(a.genre, p - nv, 1.f, a.margin, val, dv);
             lsum += val * sc;
@@ -516,7 +520,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void loss_kernel(LossArgs a) {
             float g = -dd;
             if (a.l2_scale) { const float d = a.gamma - nv; g = d > 1e-15f ? g / d : 0.f; }
             if (a.clampv > 0.f && fabsf(nv) >= a.clampv) g = 0.f;
-            dn[j] = j == jd ? 0.f : g;
+            dn[j] = (j == jd || kn(j)) ? 0.f : g;
         }
         lsum = wave_sum(lsum);
         dsum = wave_sum(dsum);
@@ -541,16 +545,16 @@ __global__ __launch_bounds__(KGE_BLOCK) void loss_kernel(LossArgs a) {
     const float neg_label = a.genre == KGE_LOSS_BCE ? 0.f : -1.f;
     float mx = -INFINITY, Z = 1.f;
     if (a.adv) {   // softmax(neg * T) over the row, detached (loss.py:87-88)
-        for (int j = lane; j < N; j += 64) mx = fmaxf(mx, (j == jd ? 0.f : n[j]) * a.adv_temp);
+        for (int j = lane; j < N; j += 64) mx = fmaxf(mx, sc_of(j) * a.adv_temp);
         mx = wave_max(mx);
         float z = 0.f;
-        for (int j = lane; j < N; j += 64) z += expf((j == jd ? 0.f : n[j]) * a.adv_temp - mx);
+        for (int j = lane; j < N; j += 64) z += expf(sc_of(j) * a.adv_temp - mx);
         Z = wave_sum(z);
     }
     const float invZ = 1.f / Z, invN = 1.f / (float)N;
     float acc = 0.f;
     for (int j = lane; j < N; j += 64) {
-        const float nv = j == jd ? 0.f : n[j];
+        const float nv = sc_of(j);
         float nl, dnl;
         criterion(a.genre, nv, neg_label, a.margin, nl, dnl);
         const float A = a.adv ? expf(nv * a.adv_temp - mx) * invZ : invN;
@@ -559,7 +563,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void loss_kernel(LossArgs a) {
         if (cp) cp[j] = nv;
         if (a.l2_scale) { const float d = a.gamma - nv; g = d > 1e-15f ? g / d : 0.f; }
         if (a.clampv > 0.f && fabsf(nv) >= a.clampv) g = 0.f;
-        dn[j] = j == jd ? 0.f : g;
+        dn[j] = (j == jd || kn(j)) ? 0.f : g;
     }
     acc = wave_sum(acc) * invB;
     if (lane == 0) {
@@ -587,7 +591,8 @@ __global__ __launch_bounds__(KGE_BLOCK) void loss_kernel(LossArgs a) {
 // dL/dn row move as ONE 16-byte access per lane and pack
 template <int NPER, bool LEAN, bool RAW, bool PK>
 __global__ __launch_bounds__(KGE_BLOCK) void loss_kernel_reg(const float *neg, const float *bsq, const float *asq, const float *pos,
-                                                             const float *w_, int B_, int N_, int l2_chunk, LossArgs a_in) {
+                                                             const float *w_, int B_, int N_, int l2_chunk, LossArgs a_in,
+                                                             const uint32_t *known) {
     KGE_TL(2);
     LossArgs a = a_in;
     a.neg = neg; a.bsq = bsq; a.asq = asq; a.pos = pos; a.w = w_; a.B = B_; a.N = N_; a.l2_chunk = l2_chunk;
@@ -615,24 +620,39 @@ __global__ __launch_bounds__(KGE_BLOCK) void loss_kernel_reg(const float *neg, c
         if constexpr (RAW) nv[u] = a.gamma - sqrtf(fmaxf(fmaf(-2.f, nv[u], asq_i + bq[u]), 1e-30f));
         if (!loss_live<PK>(lane, u, N) || loss_col<PK>(lane, u) == jd) nv[u] = 0.f;
     }
+    // known pairs (kge_known_neg_mask; never on the LEAN instances): the row's mask words are wave-uniform - a slot whose bit is
+    // set takes KGE_KNOWN_SCORE (criterion 0, softmax weight 0) and loss_row_regs zeroes its gradient with the diagonal's
+    unsigned kn = 0u;
+    if constexpr (!LEAN) {
+        if (known) {
+            const uint32_t *km = known + i * (int64_t)((N + 31) >> 5);
+#pragma unroll
+            for (int u = 0; u < NPER; ++u) {
+                const int cl = loss_ld_col<PK>(lane, u, N) + (PK ? (u & 3) : 0);      // (clamped into the row: dead slots are masked below)
+                const bool k1 = loss_live<PK>(lane, u, N) && ((km[cl >> 5] >> (cl & 31)) & 1u);
+                if (k1) nv[u] = KGE_KNOWN_SCORE;
+                kn |= (k1 ? 1u : 0u) << u;
+            }
+        }
+    }
     KGE_TL_MARK(0);              // score row, positive score, weight have arrived
     // (the row's share of the running total: when the positive share comes from edge_fwd, B slots further on than edge_fwd's add -
     //  the same two adds as the strict step's in-launch loss rows, whose other half runs in the SAME launch)
-    loss_row_regs<NPER, PK>(a, i, nv, w, p, lane, (int)((a.skip_pos ? i + a.B : i) & (KGE_ACC_SLOTS - 1)));
+    loss_row_regs<NPER, PK>(a, i, nv, w, p, lane, (int)((a.skip_pos ? i + a.B : i) & (KGE_ACC_SLOTS - 1)), kn);
     KGE_TL_MARK(1);              // softmax, criterion, reductions done; gradient stores acknowledged
 }
 
-int launch_loss(const LossArgs &a_, hipStream_t s) {
+int launch_loss(const LossArgs &a_, hipStream_t s, const uint32_t *known) {
     if (a_.B == 0) return KGE_OK;
     if (a_.N <= 0) return KGE_ERR_ARG;
     LossArgs a = a_;
     loss_fill_host(a);
     const dim3 g(blocks_for_waves(a.B)), b(KGE_BLOCK);
     const bool lean = a.genre == KGE_LOSS_LOGSIGMOID && !a.pairwise && a.skip_pos && a.clampv == 0.f && !a.neg_copy &&
-                      !a.row_pos && !a.row_neg && a.diag_chunk <= 0;
+                      !a.row_pos && !a.row_neg && a.diag_chunk <= 0 && !known;
     if (a.l2_raw && (!a.asq || !a.bsq || a.l2_chunk <= 0 || !a.l2_scale)) return KGE_ERR_ARG;
     const bool pk = a.pk != 0;
-#define KGE_LOSS_H a.neg, a.bsq, a.asq, a.pos, a.w, a.B, a.N, a.l2_chunk, a        /* hot values twice: preloaded + in the struct */
+#define KGE_LOSS_H a.neg, a.bsq, a.asq, a.pos, a.w, a.B, a.N, a.l2_chunk, a, known /* hot values twice: preloaded + in the struct */
 #define KGE_LOSS(N, PK) do { if (a.l2_raw) { if (lean) hipLaunchKernelGGL((loss_kernel_reg<N, true, true, PK>), g, b, 0, s, KGE_LOSS_H); \
                                              else hipLaunchKernelGGL((loss_kernel_reg<N, false, true, PK>), g, b, 0, s, KGE_LOSS_H); } \
                              else if (lean) hipLaunchKernelGGL((loss_kernel_reg<N, true, false, PK>), g, b, 0, s, KGE_LOSS_H); \
@@ -643,7 +663,7 @@ int launch_loss(const LossArgs &a_, hipStream_t s) {
     else if (a.N <= 128) KGE_LOSS(2, false);
     else if (a.N <= 256) KGE_LOSS(4, false);
     else if (a.N <= 512) KGE_LOSS(8, false);
-    else hipLaunchKernelGGL(loss_kernel, g, b, 0, s, a);
+    else hipLaunchKernelGGL(loss_kernel, g, b, 0, s, a, known);
 #undef KGE_LOSS
 #undef KGE_LOSS_H
     return check_launch();

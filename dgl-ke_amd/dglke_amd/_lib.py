@@ -77,6 +77,15 @@ class KgeSamplerJob(C.Structure):
                 ("reserved", c_i32), ("prev_slot", c_p)]
 
 
+class KgeKnown(C.Structure):
+    """kge_known: the two sorted (key, entity) sides of a known-triple index (known.KnownIndex.side)"""
+    _fields_ = [("keys_tail", c_p), ("vals_tail", c_p), ("m_tail", c_i64), ("keys_head", c_p), ("vals_head", c_p),
+                ("m_head", c_i64), ("n_rel", c_i64)]
+
+
+KNOWN_SCORE = -1.0e6        # KGE_KNOWN_SCORE: the score a known pair takes in the loss and in kge_step_out.neg_score
+
+
 class KgeEmit(C.Structure):
     _fields_ = [("g0", c_p), ("gs0", c_p), ("g1", c_p), ("gs1", c_p), ("gr", c_p), ("gsr", c_p),
                 ("ld_e", c_i32), ("ld_r", c_i32), ("rid", c_p), ("ent_by_id", c_i32), ("reserved", c_i32),
@@ -142,6 +151,12 @@ _SIGNATURES = {
     "kge_sampler_tail_scratch_bytes": (c_sz, [c_i, c_i, c_i, c_i64]),
     "kge_step_fused_sampling": (c_i, [C.POINTER(KgeHParams), C.POINTER(KgeTables), C.POINTER(KgeBatch),
                                       C.POINTER(KgeStepOut), c_p, c_sz, C.POINTER(KgeSamplerJob), c_p]),
+    "kge_known_mask_bytes": (c_sz, [c_i, c_i]),
+    "kge_known_neg_mask": (c_i, [C.POINTER(KgeBatch), C.POINTER(KgeKnown), c_p, c_sz, c_p]),
+    "kge_step_fused_known": (c_i, [C.POINTER(KgeHParams), C.POINTER(KgeTables), C.POINTER(KgeBatch), C.POINTER(KgeStepOut), c_p,
+                                   c_sz, C.POINTER(KgeSamplerJob), C.POINTER(KgeKnown), c_p, c_sz, c_p]),
+    "kge_step_phase_known": (c_i, [C.POINTER(KgeHParams), C.POINTER(KgeTables), C.POINTER(KgeBatch), C.POINTER(KgeStepOut), c_p,
+                                   c_sz, c_i, C.POINTER(KgeKnown), c_p, c_sz, c_p]),
     "kge_pipe_create": (c_i, [C.POINTER(c_p)]),
     "kge_pipe_destroy": (c_i, [c_p]),
     "kge_step_async_workspace_bytes": (c_sz, [C.POINTER(KgeHParams), c_i, c_i, c_i, c_i, c_i, c_i]),

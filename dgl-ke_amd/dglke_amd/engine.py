@@ -100,6 +100,41 @@ class StepEngine(object):
         self._pipe = None              # kge_pipe of the --async_update pipeline (side stream + events)
         self._aws = None
         self._aws_bytes = 0
+        self._known = None             # (KgeKnown, KnownIndex) of attach_known: known triples left out of the negatives
+        self._kmask = None
+        self._kmask_bytes = 0
+
+    def attach_known(self, index):
+        """leave the triples of `index` (known.KnownIndex on this engine's device; None detaches) out of every step's negatives:
+        a (positive, negative) pair whose corrupted triple is in the index takes the score KGE_KNOWN_SCORE in the loss - loss term,
+        gradient and self-adversarial weight 0 (include/kge_hip.h, kge_step_fused_known).  The index is only read: engines of
+        several `--num_proc` lanes share one; the pair mask of a step lives in a buffer of this engine's.  Strict single-table
+        step (`step`, `step_timed`, `capture`); not with KGE_FLAG_NEG_DEG_SAMPLE / FUSED_LOSS / LOSS_IN_FWD."""
+        if index is None:
+            self._known = None
+            return
+        if self.shards is not None:
+            raise _lib.KgeError("attach_known: known-triple exclusion runs on the strict single-table step only")
+        if (index.n_ent, index.n_rel) != (self.n_entities, self.n_relations):
+            raise _lib.KgeError("attach_known: the index describes %d entities x %d relations, the engine %d x %d"
+                                % (index.n_ent, index.n_rel, self.n_entities, self.n_relations))
+        if torch.device(index.dev) != self.device:
+            raise _lib.KgeError("attach_known: the index lives on %s, the engine on %s" % (index.dev, self.device))
+        (kt, vt), (kh, vh) = index.side(False), index.side(True)
+        k = _lib.KgeKnown()
+        k.keys_tail, k.vals_tail, k.m_tail = ptr(kt), ptr(vt), kt.numel()
+        k.keys_head, k.vals_head, k.m_head = ptr(kh), ptr(vh), kh.numel()
+        k.n_rel = index.n_rel
+        self._known = (k, index)       # (the index keeps the sorted arrays alive)
+
+    def known_mask_for(self, b):
+        need = int(lib().kge_known_mask_bytes(b.B, b.N))
+        if need > self._kmask_bytes:
+            if self._graphs:
+                raise _lib.KgeError("the known-pair mask would be re-allocated after graph capture")
+            self._kmask = torch.zeros(need, dtype=torch.uint8, device=self.device)
+            self._kmask_bytes = need
+        return self._kmask
 
     def _bind_tables(self):
         tb = _lib.KgeTables()
@@ -154,6 +189,14 @@ class StepEngine(object):
                 setattr(out, k, ptr(t))
         if sample_job is not None and (self.shards is not None or emit is not None):
             raise _lib.KgeError("the sampler tail rides on the strict single-table step only")
+        if self._known is not None:
+            if self.shards is not None or emit is not None:
+                raise _lib.KgeError("known-triple exclusion runs on the strict single-table step only")
+            km = self.known_mask_for(batch)
+            check(lib().kge_step_fused_known(C.byref(self.hp), C.byref(self.tb), C.byref(batch.c), C.byref(out), ptr(ws),
+                                             self._ws_bytes, C.byref(sample_job) if sample_job is not None else None,
+                                             C.byref(self._known[0]), ptr(km), self._kmask_bytes, stream_ptr()))
+            return
         if self.shards is not None:
             if emit is not None:
                 raise _lib.KgeError("gradient emission and peer-to-peer sharding are different multi-GPU modes")
@@ -183,8 +226,14 @@ class StepEngine(object):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
         ev[0].record()
         for k, ph in enumerate((_lib.PHASE_GATHER, _lib.PHASE_FORWARD, _lib.PHASE_BACKWARD, _lib.PHASE_UPDATE)):
-            check(lib().kge_step_phase(C.byref(self.hp), C.byref(self.tb), C.byref(batch.c), C.byref(out), ptr(ws),
-                                       self._ws_bytes, ph, stream_ptr()))
+            if self._known is not None:
+                km = self.known_mask_for(batch)
+                check(lib().kge_step_phase_known(C.byref(self.hp), C.byref(self.tb), C.byref(batch.c), C.byref(out), ptr(ws),
+                                                 self._ws_bytes, ph, C.byref(self._known[0]), ptr(km), self._kmask_bytes,
+                                                 stream_ptr()))
+            else:
+                check(lib().kge_step_phase(C.byref(self.hp), C.byref(self.tb), C.byref(batch.c), C.byref(out), ptr(ws),
+                                           self._ws_bytes, ph, stream_ptr()))
             ev[k + 1].record()
         ev[4].synchronize()
         t = [ev[k].elapsed_time(ev[k + 1]) * 1e-3 for k in range(4)]
@@ -208,6 +257,8 @@ class StepEngine(object):
         stream capture ends)."""
         if self.shards is not None:
             raise _lib.KgeError("--async_update is not available on peer-to-peer sharded tables")
+        if self._known is not None:
+            raise _lib.KgeError("known-triple exclusion is not available in the --async_update pipeline")
         if self._pipe is None:
             h = C.c_void_p()
             check(lib().kge_pipe_create(C.byref(h)))
@@ -253,11 +304,36 @@ class StepEngine(object):
                     g_neg=torch.empty(batch.C * Np, self.d_e, device=dev),
                     g_rel=torch.empty(batch.B, self.d_r, device=dev))
 
-    def capture(self, batches, stream=None, async_update=False):
+    def capture(self, batches, stream=None, async_update=False, sampler=None):
         """record `len(batches)` consecutive steps into one HIP graph (on `stream` if given);
-        returns the graph.  async_update: the --async_update pipeline, flushed at the end of the group."""
+        returns the graph.  async_update: the --async_update pipeline, flushed at the end of the group.
+        sampler (dataloader.DeviceSampler; `batches` is then the NUMBER of steps, at most its slots): the graph is [one sampler
+        launch + that many steps over its slots] - every replay trains on the next batches of the sampler's sequence, whose host
+        step counter the caller advances by the group size per replay (an even size keeps the corruption sides in place)."""
+        if sampler is not None:
+            if async_update:
+                raise _lib.KgeError("capture: the sampler form records strict steps")
+            n = int(batches)
+            probe = sampler._batches.get((0, sampler.host_step % 2 == 0))
+            if probe is None:
+                from .dataloader import DeviceBatch
+                probe = DeviceBatch(sampler, 0, sampler.host_step % 2 == 0)
+            self.workspace_for(probe)
+            if self._known is not None:
+                self.known_mask_for(probe)
+            g = torch.cuda.CUDAGraph()
+            with _lib.graph_capture(g, stream=stream):
+                batches = sampler.sample(n)
+                for b in batches:
+                    self.step(b)
+            sampler.host_step -= n         # the capture itself did not run the steps
+            g._kge_batches = batches
+            self._graphs += 1
+            return g
         for b in batches:
             (self.async_workspace_for if async_update else self.workspace_for)(b)
+            if self._known is not None:
+                self.known_mask_for(b)
         # warm-up on a side stream is not needed: the library allocates nothing
         g = torch.cuda.CUDAGraph()
         with _lib.graph_capture(g, stream=stream):

@@ -97,6 +97,11 @@ class ArgParser(argparse.ArgumentParser):
                'default the flag maps onto the STRICT step, which is faster on this GPU than a pipeline that must still land the '
                'relation trace between two steps (profiles/r03_v3_workloads_kernels.txt: 32.9 vs 30.7 us per cfg-T step) and is '
                'within the licence of the flag (staleness <= 1 step; here 0)')
+        a('--exclude_positive', action='store_true',
+          help='leave known training triples out of the negatives: a sampled entity whose corrupted triple (n, r, t) / (h, r, n) is in '
+               'the training split contributes neither loss nor gradient nor self-adversarial weight (the reference sampler\'s '
+               'exclude_positive parameter, which its CLI never sets; "filtered negatives" elsewhere).  One GPU; not with '
+               '--neg_deg_sample, --async_update_pipeline or --async_update_rel')
         a('--dist_slack', type=float, default=None,
           help='--dist_mode a2a: initial capacity of an owner bucket as a multiple of the mean share of a batch\'s unique entities '
                '(default 1.5, or KGE_DIST_SLACK); buckets grow by themselves when a group of batches needs more')
@@ -320,6 +325,16 @@ class Trainer(object):
             trip = tuple(np.asarray(x)[sel] for x in tr[:3])
             w = np.asarray(tr[3])[sel] if args.has_edge_importance else None
             self.lanes.append(_Lane(self, k, eng, trip, w))
+        self.known = None
+        if getattr(args, 'exclude_positive', False):
+            # ONE index of the whole training split, sorted on the device once; the lanes' engines only read it
+            from .known import KnownIndex
+            check_exclude_positive(args)
+            self.known = KnownIndex(tuple(np.asarray(x) for x in tr[:3]), dataset.n_entities, dataset.n_relations, self.dev)
+            for lane in self.lanes:
+                lane.engine.attach_known(self.known)
+            print('[Train] --exclude_positive: {} training triples are never a negative of their own (h, r) / (r, t)'.format(
+                len(self.known)))
 
     def _run(self, n):
         """n steps on every lane, concurrently (no synchronisation here)."""
@@ -425,8 +440,9 @@ class Trainer(object):
                         0, t_interval, since_log))
                     timed = None
                 t_interval = 0.0
-                print('[proc {}]sample+forward+backward+update (fused HIP step{}{}): {:.3f}'.format(
+                print('[proc {}]sample+forward+backward+update (fused HIP step{}{}{}): {:.3f}'.format(
                     0, ', --async_update pipeline' if self.lanes[0].async_update else '',
+                    ', known training triples excluded' if self.known is not None else '',
                     '' if self.n_lanes == 1 else ', %d concurrent trainers' % self.n_lanes, t_train))
                 since_log, start = 0, time.time()
             if args.valid and step % args.eval_interval == 0 and step > 1 and self.dataset.valid is not None:
@@ -854,8 +870,22 @@ def launch_multi_gpu(args):
     mp.spawn(_mp_worker, args=(args, port), nprocs=len(args.gpu), join=True)
 
 
+def check_exclude_positive(args):
+    """--exclude_positive runs on the strict single-table step (kge_step_fused_known): refuse what has no such step"""
+    if not getattr(args, 'exclude_positive', False):
+        return
+    if len(args.gpu) > 1:
+        raise KgeError("--exclude_positive is not available on more than one GPU (sharded tables)")
+    if args.neg_deg_sample:
+        raise KgeError("--exclude_positive is not available with --neg_deg_sample")
+    if getattr(args, 'async_update_pipeline', False) or getattr(args, 'async_update_rel', False):
+        raise KgeError("--exclude_positive is not available in the one-step-stale pipeline (--async_update_pipeline / "
+                       "--async_update_rel); plain --async_update runs the strict step and is fine")
+
+
 def main(argv=None):
     args = ArgParser().parse_args(argv)
+    check_exclude_positive(args)                 # before anything is loaded or created
     if args.neg_deg_sample_eval:                 # before anything is loaded or created
         if len(args.gpu) > 1:
             raise KgeError("--neg_deg_sample_eval is not available on sharded tables")

@@ -711,6 +711,44 @@ int kge_triples_known(const int64_t *keys, const int64_t *vals, int64_t M, int64
 int kge_sim_pairwise(int sim, const float *emb, int64_t n_emb, int d, const int64_t *left, const int64_t *right, int64_t n, float *out,
                      void *stream);
 
+/* ---- known triples left out of the TRAINING negatives (dglke_train --exclude_positive; the reference sampler's `exclude_positive`,
+ * dataloader/sampler.py:377, 396, 418, which its CLI hard-wires to False, train.py:125-158) ----
+ * kge_known: a set K of known triples as the two sorted (key, entity) indexes the evaluation side already builds
+ * (dglke_amd.eval.sort_known_device): unique pairs, ascending by key, then entity.  Tail side: key = h * n_rel + r, values = tails
+ * (used by the steps that corrupt tails); head side: key = t * n_rel + r, values = heads.  m_* == 0 (pointers may be NULL): an
+ * empty side, nothing is known.  Ids int64, n_entities * n_rel < 2^62.
+ * Row i of a batch is the positive (h_i, r_i, t_i) of chunk c, column j holds n = neg_ids[c * N + j]; the pair (i, j) is KNOWN when
+ * the corrupted triple - (n, r_i, t_i) / (h_i, r_i, n) - is in K (n equal to the row's own corrupted entity is the simplest
+ * case).  A known pair behaves in LossGenerator exactly as a negative whose score is minus infinity: loss term 0 in all four
+ * genres, pointwise and pairwise; gradient exactly 0.0f; self-adversarial weight 0 and no share in the softmax normaliser; the
+ * denominators 1 / N and 1 / B do not change.  It is implemented as the large finite score KGE_KNOWN_SCORE, so a row whose N
+ * columns are all known needs no special case (its softmax is uniform over zeros): loss 0, zero gradients, no NaN / Inf.
+ * kge_step_out.neg_score holds KGE_KNOWN_SCORE exactly at the known pairs.  Positive scores, the positive loss part, the
+ * regulariser, the plan and the sampler are untouched.
+ * kge_known_neg_mask: ONE launch (csrc/kge_known.hip) that writes one bit per pair, mask[B][ceil(N / 32)] (bit j & 31 of word
+ * j >> 5 of row i), kge_known_mask_bytes(B, N) bytes.  The corrupted side is kge_batch.counts_dev[2] on device-built plans,
+ * kge_batch.neg_head otherwise.
+ * kge_step_fused_known / kge_step_phase_known: kge_step_fused_sampling (job may be NULL: kge_step_fused) / kge_step_phase with the
+ * mask launch in front of the loss launch (phase group FORWARD) and the stand-alone loss kernel reading the mask.  The mask buffer
+ * is the caller's (one per stream of steps); kge_step_workspace_bytes does not change.  known == NULL: exactly the old entries
+ * (mask is ignored).  KGE_ERR_ARG before any launch: KGE_FLAG_FUSED_LOSS / KGE_FLAG_LOSS_IN_FWD (their loss does not run in the
+ * stand-alone kernel), KGE_FLAG_NEG_DEG_SAMPLE, a null or too small mask, n_rel <= 0, a side with m > 0 and no arrays.  Gradient
+ * emission, sharded tables and the async pipeline have no entry with a known index.  The sampler job rides on the same three
+ * launches as in kge_step_fused_sampling (the mask and loss launches carry nothing), with the same limits. */
+#define KGE_KNOWN_SCORE (-1.0e6f)
+typedef struct kge_known {
+    const int64_t *keys_tail, *vals_tail; int64_t m_tail;   /* key = h * n_rel + r -> known tails */
+    const int64_t *keys_head, *vals_head; int64_t m_head;   /* key = t * n_rel + r -> known heads */
+    int64_t n_rel;
+} kge_known;
+size_t kge_known_mask_bytes(int B, int N);
+int kge_known_neg_mask(const kge_batch *b, const kge_known *known, uint32_t *mask, size_t mask_bytes, void *stream);
+int kge_step_fused_known(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
+                         size_t ws_bytes, const kge_sampler_job *job, const kge_known *known, uint32_t *mask, size_t mask_bytes,
+                         void *stream);
+int kge_step_phase_known(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
+                         size_t ws_bytes, int phases, const kge_known *known, uint32_t *mask, size_t mask_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
