@@ -1278,3 +1278,40 @@ def write_npy_sharded(path, local, lo, n_rows, group=None, max_copy_bytes=256 <<
         del mm
     dist.barrier(group=group)
     return staged
+
+
+# ---- process bootstrap of `--gpu g0 g1 ...` (dglke_train's trainers, dglke_eval's rankers) -----------------------------------------
+
+def _rank_main(rank, worker, args, port):
+    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=len(args.gpu))
+    try:
+        worker(rank, args)
+    finally:
+        dist.destroy_process_group()
+
+
+def spawn_ranks(worker, args):
+    """one process per entry of args.gpu (the same GPU may be listed twice: the processes then share it, which is how the
+    multi-process paths are tested on a one-GPU box); every process runs worker(rank, args) - a module-level function - inside a
+    gloo group on a free local port.  The group carries the barriers, the hipIpc handles and the exchanges of ranks that share a
+    GPU; ranks with a GPU of their own open RCCL themselves (make_comm)."""
+    import socket
+    import torch.multiprocessing as mp
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    mp.spawn(_rank_main, args=(worker, args, port), nprocs=len(args.gpu), join=True)
+
+
+def load_dataset(rank, args):
+    """kgdataset.get_dataset from the flags; only rank 0 shows the loader's messages (one copy is enough)"""
+    import os
+    import sys
+    from .kgdataset import get_dataset
+    out = sys.stdout
+    if rank != 0:
+        sys.stdout = open(os.devnull, "w")
+    ds = get_dataset(args.data_path, args.dataset, args.format, args.delimiter, args.data_files,
+                     getattr(args, 'has_edge_importance', False))      # (dglke_eval has no such flag)
+    sys.stdout = out
+    return ds

@@ -104,6 +104,26 @@ class StepEngine(object):
         self._kmask = None
         self._kmask_bytes = 0
 
+    @classmethod
+    def from_args(cls, args, model_name, n_entities, n_relations, device, tables=None, shards=None, **given):
+        """the engine of an argument namespace (dglke_train's, or a hand-made one: what is missing or None takes the reference's
+        default).  `given`: constructor arguments the caller holds itself (KEModel: hidden_dim, gamma, the double_* flags).  The
+        step flags are decided here and nowhere else: degree-sampled negatives with --neg_deg_sample for every model, the
+        relation trace deferred too when both --async_update and --async_update_rel are set (only the async step reads it)."""
+        def arg(name, default=None):
+            return getattr(args, name, None) or default
+        flags = _lib.FLAG_NEG_DEG_SAMPLE if arg('neg_deg_sample') else 0
+        if arg('async_update') and arg('async_update_rel'):
+            flags |= _lib.FLAG_ASYNC_REL
+        kw = dict(hidden_dim=getattr(args, 'hidden_dim', None), gamma=getattr(args, 'gamma', None),
+                  double_entity_emb=bool(arg('double_ent')), double_relation_emb=bool(arg('double_rel')))
+        kw.update(given)
+        return cls(model_name, n_entities, n_relations, kw['hidden_dim'], kw['gamma'], args.lr, device,
+                   kw['double_entity_emb'], kw['double_relation_emb'], bool(arg('neg_adversarial_sampling')),
+                   arg('adversarial_temperature', 1.0), arg('regularization_coef', 0.0),
+                   getattr(args, 'regularization_norm', 3) or 0, arg('loss_genre', 'Logsigmoid'), bool(arg('pairwise')),
+                   getattr(args, 'margin', 1.0), flags=flags, tables=tables, shards=shards)
+
     def attach_known(self, index):
         """leave the triples of `index` (known.KnownIndex on this engine's device; None detaches) out of every step's negatives:
         a (positive, negative) pair whose corrupted triple is in the index takes the score KGE_KNOWN_SCORE in the loss - loss term,

@@ -313,6 +313,40 @@ def metrics_from_ranks(ranks):
             "HITS@10": float((rk <= 10).double().mean())}
 
 
+def print_metrics(mode, metrics):
+    """the lines of `test()` (train_pytorch.py:236-247): '[0]Valid average MRR: ...'; mode: 'Valid' or 'Test'"""
+    for k, v in metrics.items():
+        print('[{}]{} average {}: {}'.format(0, mode, k, v))
+
+
+def eval_setup(dataset, which, args, cands=None):
+    """what dglke_train's validation / test and dglke_eval hand to `evaluate*`, from the split `which` ('valid' / 'test') of
+    `dataset` and the flags: (test, known, batch, cands).
+    test: the split's (h, r, t), with --eval_percent p < 1 a random share of it (RandomState(seed + 17): the same rows in every
+    process and at every validation); cands: the optional (head, tail) candidate matrices, either may be None, cut to the same rows;
+    known: train + valid + test concatenated (the splits that exist), or None with --no_eval_filter;
+    batch: test triples per kernel call - 4096 (or --batch_size_eval if larger), less where batch x entities x 4 bytes of scores
+    would pass 2 GiB; 64 for TransR, which projects every candidate with every test triple's matrix."""
+    trip = getattr(dataset, which)
+    if trip is None:
+        raise _lib.KgeError("the dataset has no %s split" % which)
+    test = tuple(np.asarray(x) for x in trip[:3])
+    if args.eval_percent < 1:
+        n = len(test[0])
+        keep = np.random.RandomState(args.seed + 17).permutation(n)[:max(1, int(n * args.eval_percent))]
+        test = tuple(x[keep] for x in test)
+        if cands is not None:
+            cands = [c[keep] if c is not None else None for c in cands]
+    known = None
+    if args.eval_filter:
+        parts = [p for p in (dataset.train, dataset.valid, dataset.test) if p is not None]
+        known = tuple(np.concatenate([np.asarray(p[k]) for p in parts]) for k in range(3))
+    batch = int(max(1, min(max(args.batch_size_eval, 4096), (1 << 31) // (4 * dataset.n_entities), len(test[0]))))
+    if args.model_name == 'TransR':
+        batch = min(batch, 64)
+    return test, known, batch, cands
+
+
 def sampled_ranks(rk, h, r, t, neg_head, filt, n_entities, n_cand, chunk, rng, cand_of_chunk=None):
     """`--neg_sample_size_eval n_cand` (EvalSampler with a negative sample size below the entity count,
     dataloader/sampler.py:514-597): every chunk of `chunk` test triples is ranked against ITS OWN n_cand candidates
@@ -353,8 +387,9 @@ def evaluate(model_name, ent, rel, gamma, emb_init, test, known=None, batch=1024
              n_cand=None, chunk=None, seed=0, cache=None, neg_deg_sample=False):
     """filtered (known given) or raw ranking metrics over both corruption modes, averaged over all
     2E rankings like the reference (logs of the head and the tail sampler are concatenated,
-    train_pytorch.py:221-231).  test / known: (h, r, t) triples of int64 arrays.  n_cand (< number of entities):
-    rank against n_cand sampled candidates per chunk of `chunk` triples instead of all entities.
+    train_pytorch.py:221-231).  test / known: (h, r, t) triples of int64 arrays.  n_cand, 0 < n_cand < number of entities:
+    rank against n_cand sampled candidates per chunk of `chunk` triples instead of all entities (anything else - the flag's -1,
+    None, the entity count - ranks against all of them: --neg_sample_size_eval is passed as it is).
     cache: a dict the caller keeps per (split, known set) - the filter lists and the test triples stay on the device between
     calls (a training run validates the SAME split against the SAME known triples every --eval_interval steps).
     neg_deg_sample: --neg_deg_sample_eval (general_models.py:396-432) - every chunk's own corrupted-side entities are prepended

@@ -11,7 +11,6 @@ libkge_hip.  Two ways to run a training step:
 import torch as th
 
 from . import ops
-from . import _lib
 from .engine import StepEngine
 from .loss import LossGenerator
 from .score_fun import (ComplExScore, DistMultScore, RESCALScore, RotatEScore, SimplEScore, TransEScore,
@@ -85,21 +84,16 @@ class KEModel(object):
         self.head_neg_prepare = self.score_func.create_neg_prepare(True)
         self.tail_neg_prepare = self.score_func.create_neg_prepare(False)
         self.reset_parameters()
-        self.engine = StepEngine(
-            model_name, n_entities, n_relations, hidden_dim, gamma, args.lr, device,
-            double_entity_emb, double_relation_emb,
-            bool(getattr(args, 'neg_adversarial_sampling', False)),
-            getattr(args, 'adversarial_temperature', None) or 1.0,
-            getattr(args, 'regularization_coef', 0.0) or 0.0,
-            getattr(args, 'regularization_norm', 3) or 0,
-            getattr(args, 'loss_genre', None) or 'Logsigmoid',
-            bool(getattr(args, 'pairwise', False)), getattr(args, 'margin', 1.0),
-            tables=(self.entity_emb.emb, self.entity_emb.state_sum, self.relation_emb.emb,
-                    self.relation_emb.state_sum) + ((self.score_func.projection_emb.emb,
-                                                     self.score_func.projection_emb.state_sum)
-                                                    if model_name == 'TransR' else ()),
-            flags=_lib.FLAG_NEG_DEG_SAMPLE if getattr(args, 'neg_deg_sample', False) and
-            model_name not in ('TransR', 'RESCAL') else 0)
+        self.engine = StepEngine.from_args(args, model_name, n_entities, n_relations, device, tables=self.tables(),
+                                           hidden_dim=hidden_dim, gamma=gamma, double_entity_emb=double_entity_emb,
+                                           double_relation_emb=double_relation_emb)
+
+    def tables(self):
+        """the tables and their Adagrad states as StepEngine(tables=...) takes them: engines built on them train this model"""
+        t = (self.entity_emb.emb, self.entity_emb.state_sum, self.relation_emb.emb, self.relation_emb.state_sum)
+        if self.model_name == 'TransR':
+            t += (self.score_func.projection_emb.emb, self.score_func.projection_emb.state_sum)
+        return t
 
     # ---- bookkeeping (general_models.py:278-330) ----------------------------------------
     def share_memory(self):

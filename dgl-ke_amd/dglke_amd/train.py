@@ -9,6 +9,10 @@ What is different underneath: the per-step loop `sample -> forward -> backward -
 replayed from a hipGraph; validation / test are one `kge_rank_eval` call per corruption mode instead
 of the per-triple Python loop.  There is no CPU training path: `--gpu` must name a GPU.
 
+One training loop (`_Trainer.train`) drives the three trainers: `Trainer` (one GPU; `--num_proc` lanes = streams) and, one process
+per entry of `--gpu g0 g1 ...`, `A2ATrainer` (range-sharded entity table, all-to-all exchanges) or `ShardedTrainer` (peer-to-peer
+mapped tables).
+
     python -m dglke_amd.train --model_name TransE_l2 --dataset FB15k --data_path data --gpu 0 \\
         --batch_size 1000 --neg_sample_size 200 --hidden_dim 400 --gamma 19.9 --lr 0.25 \\
         --max_step 24000 --log_interval 1000 --batch_size_eval 16 -adv --regularization_coef 1e-9 --test
@@ -24,8 +28,11 @@ import numpy as np
 import torch as th
 
 from . import _lib
+from . import dist as kd
+from . import eval as kev
 from ._lib import KgeError
-from .kgdataset import get_dataset
+from .dataloader import DeviceSampler, UniformChunkedSampler
+from .engine import StepEngine
 
 
 class ArgParser(argparse.ArgumentParser):
@@ -142,15 +149,30 @@ def prepare_save_path(args):
     os.makedirs(args.save_path, exist_ok=True)
 
 
-def save_model(args, model, emap_file=None, rmap_file=None):
-    """utils.py:35-49 (same keys, including the reference's 'emp_file' spelling)"""
-    os.makedirs(args.save_path, exist_ok=True)
-    print('Save model to {}'.format(args.save_path))
-    model.save_emb(args.save_path, args.dataset)
+def write_config(args, emap_file, rmap_file):
+    """config.json of utils.py:35-49 (same keys, including the reference's 'emp_file' spelling)"""
     conf = dict(vars(args))
     conf.update({'emp_file': emap_file, 'rmap_file': rmap_file})
     with open(os.path.join(args.save_path, 'config.json'), 'w') as f:
         json.dump(conf, f, indent=4)
+
+
+def save_model(args, model, emap_file=None, rmap_file=None):
+    """utils.py:35-49"""
+    os.makedirs(args.save_path, exist_ok=True)
+    print('Save model to {}'.format(args.save_path))
+    model.save_emb(args.save_path, args.dataset)
+    write_config(args, emap_file, rmap_file)
+
+
+def step_marks(max_step, log_interval, eval_interval, valid, force_sync_interval=-1, force_sync=False):
+    """the sorted steps at which the training loop stops enqueueing: every multiple of --log_interval, with --valid of
+    --eval_interval, where the trainers wait for each other (force_sync) of --force_sync_interval, and max_step"""
+    marks = {max_step}
+    for iv in (log_interval, eval_interval if valid else 0, force_sync_interval if force_sync else 0):
+        if iv and iv > 0:
+            marks.update(range(iv, max_step + 1, iv))
+    return sorted(marks)
 
 
 class _Lane(object):
@@ -160,26 +182,16 @@ class _Lane(object):
     Hogwild training (train.py:298-317, RandomPartition of the edges sampler.py:256-290) with the
     processes replaced by streams."""
 
-    def __init__(self, trainer, k, engine, triples, weights):
-        from .dataloader import DeviceSampler, UniformChunkedSampler
-        a = trainer.args
+    def __init__(self, trainer, k, engine, part):
         self.t, self.k, self.engine = trainer, k, engine
         self.stream = th.cuda.current_stream() if trainer.n_lanes == 1 else th.cuda.Stream(device=trainer.dev)
-        B, N, chunk = a.batch_size, a.neg_sample_size, trainer.chunk
-        n_ent = trainer.dataset.n_entities
-        if trainer.device_sampler:
-            self.sampler = DeviceSampler(triples[0], triples[1], triples[2], n_ent, B, N, trainer.dev,
-                                         n_slots=max(2, a.graph_steps or 2), neg_chunk_size=chunk, seed=a.seed + 1000 * k)
-        else:
-            self.sampler = UniformChunkedSampler(triples[0], triples[1], triples[2], n_ent, B, N, trainer.dev,
-                                                 neg_chunk_size=chunk, seed=a.seed + 1000 * k, edge_importance=weights)
+        self.sampler = trainer.make_sampler(k, part)
         self._graph = None
         self._rem_graphs = {}
-        self.dropin_logs = {}
         # --async_update (reference: tensor_models.py:136-175, general_models.py:639-647): the one-step-stale pipeline of
         # kge_step_async - the entity update of step s-1 shares a launch with the backward of step s; every captured /
         # enqueued group of steps ends with a flush
-        self.async_update = bool(getattr(a, 'async_update', False)) and trainer.async_ok and trainer.async_pipeline
+        self.async_update = trainer.async_update
 
     def _steps(self, batches):
         eng = self.engine
@@ -191,9 +203,8 @@ class _Lane(object):
 
     def timed_step(self):
         """one strict step with the reference's four timers (train_pytorch.py:132-152): returns seconds per phase"""
-        import time as _t
         with th.cuda.stream(self.stream):
-            t0 = _t.time()
+            t0 = time.time()
             if self.t.device_sampler:
                 e0, e1 = th.cuda.Event(enable_timing=True), th.cuda.Event(enable_timing=True)
                 e0.record()
@@ -202,10 +213,10 @@ class _Lane(object):
                 d = self.engine.step_timed(b)
                 # one sampler launch builds a whole group of batches in the training loop (its latency does not depend on the
                 # count): this step's share of a launch is 1 / group
-                smp = e0.elapsed_time(e1) * 1e-3 / max(1, int(getattr(self.t.args, 'graph_steps', 1) or 1))
+                smp = e0.elapsed_time(e1) * 1e-3 / max(1, self.t.args.graph_steps)
             else:
                 b = self.sampler.next_batches(1)[0]
-                smp = _t.time() - t0
+                smp = time.time() - t0
                 d = self.engine.step_timed(b)
         if d is not None:
             d['sample'] = smp
@@ -213,17 +224,8 @@ class _Lane(object):
 
     def enqueue(self, n):
         """enqueue n steps on this lane's stream (no synchronisation)."""
-        t, eng = self.t, self.engine
+        t = self.t
         with th.cuda.stream(self.stream):
-            if not t.fused:
-                for _ in range(n):           # drop-in path (autograd Functions over the modular kernels)
-                    pos_g, neg_g = next(self.sampler)
-                    loss, log = t.model.forward(pos_g, neg_g, t.args.gpu[0])
-                    loss.backward()
-                    t.model.update(t.args.gpu[0])
-                    for k_, v_ in log.items():          # reference: logs.append(log), averaged at the log marks
-                        self.dropin_logs[k_] = self.dropin_logs.get(k_, 0.0) + float(v_)
-                return
             if not t.device_sampler:
                 self._steps(self.sampler.next_batches(n))
                 return
@@ -264,154 +266,104 @@ class _Lane(object):
                 done += k
 
 
-class Trainer(object):
-    """the training loop of train_pytorch.py:105-196 over the fused step."""
+class _Trainer(object):
+    """what the three trainers share: the device, the batch geometry, the split of the training triples, the samplers, the
+    engines and the training loop of train_pytorch.py:105-196 over the fused step.  A trainer says how n steps are enqueued
+    (`enqueue`), whose loss sums it prints (`loss_engines`), and - one process per GPU - how the processes meet (`barrier`) and
+    what a validation needs first (`sync_tables`)."""
 
-    def __init__(self, args, dataset):
-        from .engine import StepEngine
-        from .general_models import KEModel
-        self.args = args
-        self.dataset = dataset
-        if args.gpu[0] < 0:
+    def __init__(self, args, dataset, rank=0, world=1):
+        self.args, self.dataset, self.rank, self.world = args, dataset, rank, world
+        if args.gpu[rank] < 0:
             raise KgeError("dglke_amd trains on the GPU only: pass --gpu <id> (there is no CPU fallback)")
-        th.cuda.set_device(args.gpu[0])
-        self.dev = th.device("cuda", args.gpu[0])
-        th.manual_seed(args.seed)
-        self.model = KEModel(args, args.model_name, dataset.n_entities, dataset.n_relations, args.hidden_dim,
-                             args.gamma, double_entity_emb=args.double_ent, double_relation_emb=args.double_rel)
-        tr = dataset.train
+        th.cuda.set_device(args.gpu[rank])
+        self.dev = th.device("cuda", args.gpu[rank])
         B, N = args.batch_size, args.neg_sample_size
         self.chunk = N if N <= B else B
-        C = B // self.chunk
-        # --neg_deg_sample runs on the fused step (KGE_FLAG_NEG_DEG_SAMPLE) for every model - round 6: TransR and RESCAL too (the
-        # reference's concat-and-mask is model-agnostic, general_models.py:396-402, 417-432), also with --num_proc lanes
-        self.fused = True
-        self.step_flags = _lib.FLAG_NEG_DEG_SAMPLE if args.neg_deg_sample else 0
-        if getattr(args, 'async_update', False) and getattr(args, 'async_update_rel', False):
-            self.step_flags |= _lib.FLAG_ASYNC_REL
-            self.model.engine.hp.flags |= _lib.FLAG_ASYNC_REL
-        self.device_sampler = self.fused and not args.has_edge_importance and 2 * B + C * N <= 8192
-        self.n_lanes = max(1, int(args.num_proc))
-        self.async_ok = self.fused and args.model_name not in ('TransR', 'RESCAL')
-        # entity-only deferral (the reference's --async_update) runs as the strict step unless the pipeline is asked for: with the
-        # relation trace landing between two steps the pipeline needs one more launch than it hides (VERDICT r03 weak 5)
-        self.async_pipeline = bool(getattr(args, 'async_update_rel', False) or getattr(args, 'async_update_pipeline', False))
-        if getattr(args, 'async_update', False) and not self.async_ok:
-            print('--async_update: not available for this model / option combination; running the strict step')
-        elif getattr(args, 'async_update', False) and not self.async_pipeline:
-            print('--async_update: running the strict step (no staleness; faster on this GPU than the entity-only one-step-stale '
-                  'pipeline - pass --async_update_rel to defer the relation trace too, or --async_update_pipeline to force it)')
-        if self.n_lanes > 1 and not self.fused:
-            raise KgeError("--num_proc > 1 needs the fused step (not available with --neg_deg_sample)")
-        # the lanes share the tables; every lane trains on its own random share of the triples
-        m = self.model
-        tables = (m.entity_emb.emb, m.entity_emb.state_sum, m.relation_emb.emb, m.relation_emb.state_sum)
-        if args.model_name == 'TransR':       # the lanes share the projection table too (general_models.py:97-100)
-            tables += (m.score_func.projection_emb.emb, m.score_func.projection_emb.state_sum)
-        parts = np.array_split(np.random.RandomState(args.seed).permutation(len(tr[0])), self.n_lanes)
-        if min(len(p) for p in parts) < B:
-            # both samplers work on whole batches (the reference drops partial ones, dataloader/sampler.py:503-504): a trainer
-            # whose share of the triples is smaller than one batch could never step
-            raise KgeError("every trainer needs at least batch_size training triples: %d triples over %d trainer(s) < batch_size %d "
-                           "- lower --batch_size or --num_proc" % (len(tr[0]), self.n_lanes, B))
-        self.lanes = []
-        for k in range(self.n_lanes):
-            eng = m.engine if k == 0 else StepEngine(
-                args.model_name, dataset.n_entities, dataset.n_relations, args.hidden_dim, args.gamma, args.lr,
-                self.dev, args.double_ent, args.double_rel, args.neg_adversarial_sampling,
-                args.adversarial_temperature, args.regularization_coef, args.regularization_norm, args.loss_genre,
-                args.pairwise, args.margin, flags=self.step_flags, tables=tables)
-            sel = parts[k] if self.n_lanes > 1 else slice(None)
-            trip = tuple(np.asarray(x)[sel] for x in tr[:3])
-            w = np.asarray(tr[3])[sel] if args.has_edge_importance else None
-            self.lanes.append(_Lane(self, k, eng, trip, w))
-        self.known = None
-        if getattr(args, 'exclude_positive', False):
-            # ONE index of the whole training split, sorted on the device once; the lanes' engines only read it
-            from .known import KnownIndex
-            check_exclude_positive(args)
-            self.known = KnownIndex(tuple(np.asarray(x) for x in tr[:3]), dataset.n_entities, dataset.n_relations, self.dev)
-            for lane in self.lanes:
-                lane.engine.attach_known(self.known)
-            print('[Train] --exclude_positive: {} training triples are never a negative of their own (h, r) / (r, t)'.format(
-                len(self.known)))
+        self.C = B // self.chunk
+        self.d_e = args.hidden_dim * (2 if args.double_ent else 1)
+        self.d_r = args.hidden_dim * (2 if args.double_rel else 1)
+        self.emb_init = (args.gamma + 2.0) / args.hidden_dim
+        # the on-device sampler builds the batches of a whole group ahead; batches it cannot build - edge importance, or more ids
+        # than its launch handles - come from the host sampler (plans built on the host, step by step)
+        self.device_sampler = not args.has_edge_importance and 2 * B + self.C * N <= DeviceSampler.MAX_ELEMENTS
+        self.n_lanes, self.async_update, self.known = 1, False, None
 
-    def _run(self, n):
-        """n steps on every lane, concurrently (no synchronisation here)."""
-        for lane in self.lanes:
-            lane.enqueue(n)
+    def make_engine(self, n_entities=None, **tables):
+        """a StepEngine of the flags on this trainer's device; tables= / shards=: the tables it trains (default: its own)"""
+        return StepEngine.from_args(self.args, self.args.model_name, n_entities or self.dataset.n_entities,
+                                    self.dataset.n_relations, self.dev, **tables)
 
-    def evaluate(self, which, mode):
-        from . import eval as kev
-        args, ds = self.args, self.dataset
-        trip = getattr(ds, which)
-        if trip is None:
-            raise KgeError("the dataset has no %s split" % which)
-        h, r, t = (np.asarray(x) for x in trip[:3])
-        if args.eval_percent < 1:
-            rng = np.random.RandomState(args.seed + 17)
-            keep = rng.permutation(len(h))[:max(1, int(len(h) * args.eval_percent))]
-            h, r, t = h[keep], r[keep], t[keep]
-        known = None
-        if args.eval_filter:
-            parts = [p for p in (ds.train, ds.valid, ds.test) if p is not None]
-            known = tuple(np.concatenate([np.asarray(p[k]) for p in parts]) for k in range(3))
-        m = self.model
-        n_cand = m.n_entities
-        Eb = int(max(1, min(max(args.batch_size_eval, 4096), (1 << 31) // (4 * n_cand), len(h))))
-        proj = m.score_func.projection_emb.emb if args.model_name == 'TransR' else None
-        if proj is not None:
-            Eb = min(Eb, 64)                  # TransR projects every candidate with every test triple's matrix
-        # (the split and the known set do not change during a run: filter lists and test ids stay on the device between validations)
-        cache = self.__dict__.setdefault('_eval_cache', {}).setdefault(which, {})
-        metrics = kev.evaluate(args.model_name, m.entity_emb.emb, m.relation_emb.emb, args.gamma, m.emb_init,
-                               (h, r, t), known, batch=Eb, proj=proj, n_cand=args.neg_sample_size_eval,
-                               chunk=args.batch_size_eval, seed=args.seed + 29, cache=cache,   # sampled candidates if < n_entities
-                               neg_deg_sample=args.neg_deg_sample_eval)
-        for k, v in metrics.items():
-            print('[{}]{} average {}: {}'.format(0, mode, k, v))
-        if args.eval_relation:
-            rel_metrics = kev.evaluate_relations(args.model_name, m.entity_emb.emb, m.relation_emb.emb, args.gamma, m.emb_init,
-                                                 (h, r, t), known, batch=Eb, proj=proj, cache=cache)
-            for k, v in rel_metrics.items():
-                print('[{}]{} average REL_{}: {}'.format(0, mode, k, v))
-                metrics['REL_' + k] = v
-        return metrics
+    def split(self, n, edge_rank=None, refusal=None):
+        """the rows of the training split of each of n trainers: those a relation partition assigns (edge_rank[i] = the trainer
+        of triple i), else a random partition by --seed (RandomPartition, sampler.py:256-290; one trainer: every row, in order).
+        Both samplers work on whole batches (the reference drops partial ones, dataloader/sampler.py:503-504), so a trainer whose
+        share is smaller than one batch could never step: refused here - the partition is the same on every rank, so every rank
+        raises, before any collective.  refusal: the caller's wording, a template over the names below."""
+        n_trip, B = len(self.dataset.train[0]), self.args.batch_size
+        if edge_rank is not None:
+            parts = [np.nonzero(edge_rank == k)[0] for k in range(n)]
+        elif n > 1:
+            parts = np.array_split(np.random.RandomState(self.args.seed).permutation(n_trip), n)
+        else:
+            parts = [slice(None)]               # (a view: a large split is not copied)
+        share = [len(range(n_trip)[p]) if isinstance(p, slice) else len(p) for p in parts]
+        if min(share) < B:
+            refusal = refusal or ("--batch_size %(batch)d is larger than a trainer's share of the training triples (%(triples)d "
+                                  "over %(n)d trainers)")
+            raise KgeError(refusal % dict(trainer=int(np.argmin(share)), share=min(share), batch=B, triples=n_trip, n=n))
+        return parts
+
+    def make_sampler(self, k, part):
+        """trainer k's sampler over the rows `part` of the training split"""
+        a, tr = self.args, self.dataset.train
+        h, r, t = (np.asarray(x)[part] for x in tr[:3])
+        if self.device_sampler:
+            return DeviceSampler(h, r, t, self.dataset.n_entities, a.batch_size, a.neg_sample_size, self.dev,
+                                 n_slots=max(2, a.graph_steps or 2), neg_chunk_size=self.chunk, seed=a.seed + 1000 * k)
+        w = np.asarray(tr[3])[part] if a.has_edge_importance else None
+        return UniformChunkedSampler(h, r, t, self.dataset.n_entities, a.batch_size, a.neg_sample_size, self.dev,
+                                     neg_chunk_size=self.chunk, seed=a.seed + 1000 * k, edge_importance=w)
+
+    def loss_engines(self):
+        """(proc number, engine) of the loss sums this process prints at a log mark"""
+        return [(self.rank, self.engine)]
+
+    def barrier(self):
+        pass
+
+    def sync_tables(self):
+        pass
 
     def train(self):
         args = self.args
-        eng = self.model.engine
         keys = ['loss'] if args.pairwise else ['pos_loss', 'neg_loss', 'loss']
         if args.regularization_coef > 0 and args.regularization_norm > 0:
             keys.append('regularization')
         idx = {'pos_loss': 0, 'neg_loss': 1, 'loss': 2, 'regularization': 3}
+        # --force_sync_interval (reference train_pytorch.py:181-187: every trainer waits at a barrier every so many steps, so that no
+        # trainer of the lock-free shared-table modes runs far ahead of the others; the all-to-all mode is in step by construction).
+        # --num_proc K lanes on one GPU are streams of this process: the synchronise at a mark IS their barrier
+        fsi = args.force_sync_interval
+        force_sync = fsi > 0 and (self.world > 1 or self.n_lanes > 1)
+        # the reference's four timers (train_pytorch.py:127-177), one GPU, one lane, strict step: the LAST step before a log mark
+        # runs as four phase groups with HIP events in between (same kernels, same result).  That one step is launched eagerly and
+        # synchronised, so its absolute times are not those of the graph-replayed steps: only the SPLIT is taken from it - the
+        # printed totals are the interval's measured training time divided in that step's proportions
+        phase_timers = self.world == 1 and self.n_lanes == 1 and not self.lanes[0].async_update
         th.cuda.synchronize()
+        self.barrier()
         train_start = start = time.time()
-        step, t_train, reached = 0, 0.0, None
-        marks = set()
-        for iv in (args.log_interval, args.eval_interval if args.valid else 0):
-            if iv and iv > 0:
-                marks.update(range(iv, args.max_step + 1, iv))
-        marks.add(args.max_step)
-        # --force_sync_interval with --num_proc K lanes on one GPU: the lanes are streams of this process - the synchronise at a mark
-        # IS the reference's barrier between its trainer processes (train_pytorch.py:181-187)
-        fsi = int(getattr(args, 'force_sync_interval', -1) or -1)
-        if fsi > 0 and self.n_lanes > 1:
-            marks.update(range(fsi, args.max_step + 1, fsi))
-        since_log = 0
-        timed = None
-        t_interval = 0.0
-        for nxt in sorted(marks):
+        step = since_log = 0
+        t_train = t_interval = 0.0
+        timed = reached = None
+        for nxt in step_marks(args.max_step, args.log_interval, args.eval_interval, args.valid, fsi, force_sync):
             n = nxt - step
             at_log = args.log_interval > 0 and nxt % args.log_interval == 0
             if n > 0:
                 t0 = time.time()
-                # the reference's four timers (train_pytorch.py:127-177): the LAST step before a log mark runs as four
-                # phase groups with HIP events in between (same kernels, same result).  That one step is launched eagerly and
-                # synchronised, so its absolute times are not those of the graph-replayed steps: only the SPLIT is taken from
-                # it - the printed totals are the interval's measured training time divided in that step's proportions
-                want_timers = at_log and self.fused and self.n_lanes == 1 and not self.lanes[0].async_update
-                self._run(n - 1 if want_timers else n)
+                want_timers = at_log and phase_timers
+                self.enqueue(n - 1 if want_timers else n)
                 if want_timers:
                     th.cuda.synchronize()
                     timed = self.lanes[0].timed_step()
@@ -419,18 +371,14 @@ class Trainer(object):
                 t_train += time.time() - t0
                 t_interval += time.time() - t0
                 step, since_log = nxt, since_log + n
+            if force_sync and step % fsi == 0:
+                self.barrier()
             if at_log and since_log:
-                for lane in self.lanes:
-                    if self.fused:
-                        sums = lane.engine.read_loss_sums()
-                        for k in keys:
-                            print('[proc {}][Train]({}/{}) average {}: {}'.format(lane.k, step, args.max_step, k,
-                                                                                sums[idx[k]] / since_log))
-                    else:
-                        for k, v in lane.dropin_logs.items():
-                            print('[proc {}][Train]({}/{}) average {}: {}'.format(lane.k, step, args.max_step, k, v / since_log))
-                        lane.dropin_logs = {}
-                    print('[proc {}][Train] {} steps take {:.3f} seconds'.format(lane.k, since_log, time.time() - start))
+                for proc, eng in self.loss_engines():
+                    sums = eng.read_loss_sums()
+                    for k in keys:
+                        print('[proc {}][Train]({}/{}) average {}: {}'.format(proc, step, args.max_step, k, sums[idx[k]] / since_log))
+                    print('[proc {}][Train] {} steps take {:.3f} seconds'.format(proc, since_log, time.time() - start))
                 if timed is not None:
                     tot = sum(timed[k] for k in ('sample', 'forward', 'backward', 'update')) or 1.0
                     sc = t_interval / tot
@@ -440,87 +388,148 @@ class Trainer(object):
                         0, t_interval, since_log))
                     timed = None
                 t_interval = 0.0
-                print('[proc {}]sample+forward+backward+update (fused HIP step{}{}{}): {:.3f}'.format(
-                    0, ', --async_update pipeline' if self.lanes[0].async_update else '',
-                    ', known training triples excluded' if self.known is not None else '',
-                    '' if self.n_lanes == 1 else ', %d concurrent trainers' % self.n_lanes, t_train))
+                if self.world == 1:
+                    print('[proc {}]sample+forward+backward+update (fused HIP step{}{}{}): {:.3f}'.format(
+                        0, ', --async_update pipeline' if self.lanes[0].async_update else '',
+                        ', known training triples excluded' if self.known is not None else '',
+                        '' if self.n_lanes == 1 else ', %d concurrent trainers' % self.n_lanes, t_train))
                 since_log, start = 0, time.time()
             if args.valid and step % args.eval_interval == 0 and step > 1 and self.dataset.valid is not None:
+                self.barrier()                   # like the reference: all trainers stop for the validation
+                self.sync_tables()
                 valid_start = time.time()
-                m = self.evaluate('valid', 'Valid')
-                print('[proc {}]validation take {:.3f} seconds:'.format(0, time.time() - valid_start))
-                if args.target_mrr is not None and reached is None and m['MRR'] >= args.target_mrr:
+                m = self.evaluate('valid', 'Valid')      # (several processes: every rank ranks against its own shard)
+                if self.rank == 0:
+                    print('[proc {}]validation take {:.3f} seconds:'.format(0, time.time() - valid_start))
+                # --target_mrr stops a single-GPU run only: the multi-GPU trainers ignore the flag (their ranks would have to
+                # agree on the stop and leave the loop's collectives together)
+                if self.world == 1 and args.target_mrr is not None and m['MRR'] >= args.target_mrr:
                     reached = (step, t_train)
                     print('[proc 0]validation MRR {:.4f} >= {:.4f} after {} steps, {:.3f} s of training'.format(
                         m['MRR'], args.target_mrr, step, t_train))
                     break
+                self.barrier()
                 # (no reset of `start` here: the reference's '[Train] N steps take' interval includes a validation that falls
                 #  inside it, train_pytorch.py:168-176)
-        print('proc {} takes {:.3f} seconds'.format(0, time.time() - train_start))
+        th.cuda.synchronize()
+        print('proc {} takes {:.3f} seconds'.format(self.rank, time.time() - train_start))
+        self.barrier()
         return reached
 
 
-class ShardedTrainer(object):
+class Trainer(_Trainer):
+    """one GPU: `--num_proc` lanes on the tables of one KEModel."""
+
+    def __init__(self, args, dataset):
+        from .general_models import KEModel
+        super(Trainer, self).__init__(args, dataset)
+        th.manual_seed(args.seed)
+        # (the model's own engine is lane 0's: built from the same flags as the other lanes' - --neg_deg_sample runs on the fused
+        # step for every model, the reference's concat-and-mask is model-agnostic, general_models.py:396-402, 417-432)
+        self.model = m = KEModel(args, args.model_name, dataset.n_entities, dataset.n_relations, args.hidden_dim,
+                                 args.gamma, double_entity_emb=args.double_ent, double_relation_emb=args.double_rel)
+        self.step_flags = int(m.engine.hp.flags)
+        self.n_lanes = max(1, int(args.num_proc))
+        # entity-only deferral (the reference's --async_update) runs as the strict step unless the pipeline is asked for: with the
+        # relation trace landing between two steps the pipeline needs one more launch than it hides
+        async_ok = args.model_name not in ('TransR', 'RESCAL')
+        pipeline = args.async_update_rel or args.async_update_pipeline
+        self.async_update = bool(args.async_update and async_ok and pipeline)
+        if args.async_update and not async_ok:
+            print('--async_update: not available for this model / option combination; running the strict step')
+        elif args.async_update and not pipeline:
+            print('--async_update: running the strict step (no staleness; faster on this GPU than the entity-only one-step-stale '
+                  'pipeline - pass --async_update_rel to defer the relation trace too, or --async_update_pipeline to force it)')
+        # the lanes share the tables (TransR: the projection table too); every lane trains on its own random share of the triples
+        parts = self.split(self.n_lanes, refusal="every trainer needs at least batch_size training triples: %(triples)d triples over "
+                           "%(n)d trainer(s) < batch_size %(batch)d - lower --batch_size or --num_proc")
+        self.lanes = [_Lane(self, k, m.engine if k == 0 else self.make_engine(tables=m.tables()), parts[k])
+                      for k in range(self.n_lanes)]
+        if args.exclude_positive:
+            # ONE index of the whole training split, sorted on the device once; the lanes' engines only read it
+            from .known import KnownIndex
+            check_exclude_positive(args)
+            self.known = KnownIndex(tuple(np.asarray(x) for x in dataset.train[:3]), dataset.n_entities, dataset.n_relations,
+                                    self.dev)
+            for lane in self.lanes:
+                lane.engine.attach_known(self.known)
+            print('[Train] --exclude_positive: {} training triples are never a negative of their own (h, r) / (r, t)'.format(
+                len(self.known)))
+
+    def enqueue(self, n):
+        """n steps on every lane, concurrently (no synchronisation here)."""
+        for lane in self.lanes:
+            lane.enqueue(n)
+
+    def loss_engines(self):
+        return [(lane.k, lane.engine) for lane in self.lanes]
+
+    def evaluate(self, which, mode):
+        args, m = self.args, self.model
+        test, known, Eb, _ = kev.eval_setup(self.dataset, which, args)
+        proj = m.score_func.projection_emb.emb if args.model_name == 'TransR' else None
+        # (the split and the known set do not change during a run: filter lists and test ids stay on the device between validations)
+        cache = self.__dict__.setdefault('_eval_cache', {}).setdefault(which, {})
+        metrics = kev.evaluate(args.model_name, m.entity_emb.emb, m.relation_emb.emb, args.gamma, m.emb_init, test, known,
+                               batch=Eb, proj=proj, n_cand=args.neg_sample_size_eval, chunk=args.batch_size_eval,
+                               seed=args.seed + 29, cache=cache, neg_deg_sample=args.neg_deg_sample_eval)
+        kev.print_metrics(mode, metrics)
+        if args.eval_relation:
+            rel_metrics = kev.evaluate_relations(args.model_name, m.entity_emb.emb, m.relation_emb.emb, args.gamma, m.emb_init,
+                                                 test, known, batch=Eb, proj=proj, cache=cache)
+            rel_metrics = {'REL_' + k: v for k, v in rel_metrics.items()}
+            kev.print_metrics(mode, rel_metrics)
+            metrics.update(rel_metrics)
+        return metrics
+
+
+class ShardedTrainer(_Trainer):
     """one of the `--gpu g0 g1 ...` trainer processes (reference: train.py:298-317, one process per GPU on
     tables in shared host memory).  Here the shared tables are the union of the GPUs' HBM, mapped peer to peer
     (dglke_amd/p2p.py): every process trains on its random share of the triples with the fused step
     (`kge_step_sharded`), lock-free across processes like the reference; the process group (gloo) is only
-    used to exchange the hipIpc handles and for barriers."""
+    used to exchange the hipIpc handles and for barriers.  What every multi-process trainer does the same way - barriers,
+    evaluation and saving on the shards in place - is here too; `build` is this mode's own part."""
 
     def __init__(self, args, dataset, rank, world):
-        from . import p2p
-        from .engine import StepEngine
-        self.args, self.dataset, self.rank, self.world = args, dataset, rank, world
-        th.cuda.set_device(args.gpu[rank])
-        self.dev = th.device("cuda", args.gpu[rank])
-        B, N = args.batch_size, args.neg_sample_size
-        self.chunk = N if N <= B else B
-        self.fused, self.n_lanes, self.async_ok = True, 1, False
-        # (edge importance / more than 8192 ids per batch: host-built batches, like the single-GPU trainer's host sampler path)
-        self.device_sampler = 2 * B + (B // self.chunk) * N <= 8192 and not args.has_edge_importance
-        if args.neg_deg_sample and args.model_name in ('TransR', 'RESCAL'):
-            raise KgeError("--neg_deg_sample is not available for %s on sharded tables" % args.model_name)
-        d_e = args.hidden_dim * (2 if args.double_ent else 1)
-        d_r = args.hidden_dim * (2 if args.double_rel else 1)
-        self.emb_init = (args.gamma + 2.0) / args.hidden_dim
-        # TransR / RESCAL (round 6): the entity table is spread over the GPUs like every model's; the relation-side tables - relation
-        # rows / matrices and TransR's projection table - are whole tables LOCAL to every trainer and the triples are partitioned BY
-        # RELATION (whole relations, dist.relation_partition), so that a relation's rows are trained on exactly one GPU: the
-        # reference's --rel_part layout, which its own multi-GPU TransR recipe passes (examples/freebase/multi_gpu.sh:80-89,
-        # general_models.py:590-637).  The owners' rows are collected when the tables are read (sync_tables).
+        super(ShardedTrainer, self).__init__(args, dataset, rank, world)
+        # TransR / RESCAL: the entity table is spread over the GPUs like every model's; the relation side - relation rows / matrices
+        # and TransR's projection table - is LOCAL to the trainer that holds the relation's edges, so the triples are partitioned
+        # BY RELATION (whole relations): the reference's --rel_part layout, which its own multi-GPU TransR recipe passes
+        # (examples/freebase/multi_gpu.sh:80-89, general_models.py:590-637).  The owners' rows are collected by sync_tables.
         self.rel_side_local = args.model_name in ('TransR', 'RESCAL')
-        self.rel_owner, part = None, None
+        if self.rel_side_local and args.neg_deg_sample:
+            raise KgeError("--neg_deg_sample is not available for %s on more than one GPU" % args.model_name)
+        self.rel_owner = None
+        self.build()
+
+    def build(self):
+        from . import p2p
+        args, dataset, rank, world = self.args, self.dataset, self.rank, self.world
+        edge_rank = refusal = None
         if self.rel_side_local:
-            from . import dist as kd
             self.rel_owner, edge_rank = kd.relation_partition(dataset.train[1], world)
-            part = np.nonzero(edge_rank == rank)[0]
-            cnt = np.bincount(edge_rank, minlength=world)
+            refusal = "relation partition: trainer %(trainer)d gets %(share)d training triples, fewer than --batch_size %(batch)d"
             if rank == 0:
                 print("%s on %d GPUs: entity table sharded peer to peer, relation-side tables local, triples partitioned by relation "
-                      "(whole relations; edges per trainer %s)" % (args.model_name, world, cnt.tolist()))
-            if cnt.min() < B:
-                raise KgeError("relation partition: trainer %d gets %d training triples, fewer than --batch_size %d"
-                               % (int(cnt.argmin()), int(cnt.min()), B))
-        self.tabs = p2p.ShardedTables(dataset.n_entities, dataset.n_relations, d_e,
-                                      d_r * d_e if args.model_name == 'RESCAL' else d_r, self.dev, world, rank,
+                      "(whole relations; edges per trainer %s)" % (args.model_name, world, np.bincount(edge_rank, minlength=world).tolist()))
+        part = self.split(world, edge_rank, refusal)[rank]
+        self.tabs = p2p.ShardedTables(dataset.n_entities, dataset.n_relations, self.d_e,
+                                      self.d_r * self.d_e if args.model_name == 'RESCAL' else self.d_r, self.dev, world, rank,
                                       rel_local=self.rel_side_local,
-                                      proj_dim=d_e * d_r if args.model_name == 'TransR' else 0)
+                                      proj_dim=self.d_e * self.d_r if args.model_name == 'TransR' else 0)
         if not self.tabs.probe():
             raise KgeError("peer mappings do not reach the other GPUs' memory")
         self.tabs.init_uniform(self.emb_init, args.seed)
-        self.engine = StepEngine(args.model_name, dataset.n_entities, dataset.n_relations, args.hidden_dim, args.gamma,
-                                 args.lr, self.dev, args.double_ent, args.double_rel, args.neg_adversarial_sampling,
-                                 args.adversarial_temperature, args.regularization_coef, args.regularization_norm,
-                                 args.loss_genre, args.pairwise, args.margin,
-                                 flags=_lib.FLAG_NEG_DEG_SAMPLE if args.neg_deg_sample else 0, shards=self.tabs)
-        tr = dataset.train
-        if part is None:
-            part = np.array_split(np.random.RandomState(args.seed).permutation(len(tr[0])), world)[rank]
-        self.lane = _Lane(self, rank, self.engine, tuple(np.asarray(x)[part] for x in tr[:3]),
-                          np.asarray(tr[3])[part] if args.has_edge_importance else None)
+        self.engine = self.make_engine(shards=self.tabs)
+        self.lane = _Lane(self, rank, self.engine, part)
 
-    def _enqueue(self, n):
+    def enqueue(self, n):
         self.lane.enqueue(n)
+
+    def barrier(self):
+        import torch.distributed as dist
+        dist.barrier()
 
     def sync_tables(self):
         """collective point in front of a validation / test / save: the peer-mapped tables need nothing; relation-side tables
@@ -556,8 +565,6 @@ class ShardedTrainer(object):
     def save(self, emap_file, rmap_file):
         """<dataset>_<model>_entity.npy written shard by shard into one file (dist.write_npy_sharded), the relation-side tables
         and config.json from rank 0.  Collective: every rank calls it after sync_tables()."""
-        import torch.distributed as dist
-        from . import dist as kd
         args = self.args
         rel = self.relation_table()
         lo, shard = self.entity_shard()
@@ -568,90 +575,23 @@ class ShardedTrainer(object):
             if args.model_name == 'TransR':      # TransRScore.save (score_fun.py:190-191): <dataset>_<model>projection.npy
                 np.save(os.path.join(args.save_path, '%s_%sprojection.npy' % (args.dataset, args.model_name)),
                         self.projection().cpu().numpy())
-            conf = dict(vars(args))
-            conf.update({'emp_file': emap_file, 'rmap_file': rmap_file})
-            with open(os.path.join(args.save_path, 'config.json'), 'w') as f:
-                json.dump(conf, f, indent=4)
-        dist.barrier()
+            write_config(args, emap_file, rmap_file)
+        self.barrier()
 
     def evaluate(self, which, mode):
         """`--valid` / `--test` on the sharded table, collective: every rank ranks the split against the entities it holds
         (eval.evaluate_sharded); rank 0 prints the metrics."""
-        from . import eval as kev
         args, ds = self.args, self.dataset
-        trip = getattr(ds, which)
-        if trip is None:
-            raise KgeError("the dataset has no %s split" % which)
-        h, r, t = (np.asarray(x) for x in trip[:3])
-        if args.eval_percent < 1:
-            keep = np.random.RandomState(args.seed + 17).permutation(len(h))[:max(1, int(len(h) * args.eval_percent))]
-            h, r, t = h[keep], r[keep], t[keep]
-        known = None
-        if args.eval_filter:
-            parts = [p for p in (ds.train, ds.valid, ds.test) if p is not None]
-            known = tuple(np.concatenate([np.asarray(p[k]) for p in parts]) for k in range(3))
-        rel = self.relation_table()
+        test, known, Eb, _ = kev.eval_setup(ds, which, args)
         lo, shard = self.entity_shard()
-        Eb = int(max(1, min(max(args.batch_size_eval, 4096), (1 << 31) // (4 * ds.n_entities), len(h))))
-        proj = self.projection() if args.model_name == 'TransR' else None
-        if proj is not None:
-            Eb = min(Eb, 64)                  # TransR projects every candidate with every test triple's matrix
         cache = self.__dict__.setdefault('_eval_cache', {}).setdefault(which, {})
-        metrics = kev.evaluate_sharded(args.model_name, shard, lo, ds.n_entities, rel, args.gamma, self.emb_init, (h, r, t),
-                                       self.entity_rows, known, batch=Eb, proj=proj, n_cand=args.neg_sample_size_eval,
-                                       chunk=args.batch_size_eval, seed=args.seed + 29, cache=cache)
+        metrics = kev.evaluate_sharded(args.model_name, shard, lo, ds.n_entities, self.relation_table(), args.gamma, self.emb_init,
+                                       test, self.entity_rows, known, batch=Eb,
+                                       proj=self.projection() if args.model_name == 'TransR' else None,
+                                       n_cand=args.neg_sample_size_eval, chunk=args.batch_size_eval, seed=args.seed + 29, cache=cache)
         if self.rank == 0:
-            for k, v in metrics.items():
-                print('[{}]{} average {}: {}'.format(self.rank, mode, k, v))
+            kev.print_metrics(mode, metrics)
         return metrics
-
-    def train(self):
-        import torch.distributed as dist
-        args, rank = self.args, self.rank
-        keys = ['loss'] if args.pairwise else ['pos_loss', 'neg_loss', 'loss']
-        if args.regularization_coef > 0 and args.regularization_norm > 0:
-            keys.append('regularization')
-        idx = {'pos_loss': 0, 'neg_loss': 1, 'loss': 2, 'regularization': 3}
-        marks = set()
-        for iv in (args.log_interval, args.eval_interval if args.valid else 0):
-            if iv and iv > 0:
-                marks.update(range(iv, args.max_step + 1, iv))
-        marks.add(args.max_step)
-        # --force_sync_interval (reference train_pytorch.py:181-187: every trainer waits at a barrier every so many steps, so that no
-        # process of the lock-free shared-table mode runs far ahead of the others); the all-to-all mode is in step by construction
-        fsi = int(getattr(args, 'force_sync_interval', -1) or -1)
-        if fsi > 0:
-            marks.update(range(fsi, args.max_step + 1, fsi))
-        th.cuda.synchronize()
-        dist.barrier()
-        train_start = start = time.time()
-        step = since_log = 0
-        for nxt in sorted(marks):
-            n = nxt - step
-            if n > 0:
-                self._enqueue(n)
-                th.cuda.synchronize()
-                step, since_log = nxt, since_log + n
-            if fsi > 0 and step % fsi == 0:
-                dist.barrier()
-            if args.log_interval > 0 and step % args.log_interval == 0 and since_log:
-                sums = self.engine.read_loss_sums()
-                for k in keys:
-                    print('[proc {}][Train]({}/{}) average {}: {}'.format(rank, step, args.max_step, k,
-                                                                        sums[idx[k]] / since_log))
-                print('[proc {}][Train] {} steps take {:.3f} seconds'.format(rank, since_log, time.time() - start))
-                since_log, start = 0, time.time()
-            if args.valid and step % args.eval_interval == 0 and step > 1 and self.dataset.valid is not None:
-                dist.barrier()                   # like the reference: all trainers stop for the validation
-                self.sync_tables()
-                valid_start = time.time()
-                self.evaluate('valid', 'Valid')          # every rank ranks against its own shard
-                if rank == 0:
-                    print('[proc {}]validation take {:.3f} seconds:'.format(rank, time.time() - valid_start))
-                dist.barrier()           # (`start` is not reset: the interval includes the validation, train_pytorch.py:168-176)
-        th.cuda.synchronize()
-        print('proc {} takes {:.3f} seconds'.format(rank, time.time() - train_start))
-        dist.barrier()
 
 
 class A2ATrainer(ShardedTrainer):
@@ -663,58 +603,27 @@ class A2ATrainer(ShardedTrainer):
     ranks that share a GPU (`--gpu 0 0`) exchange through the gloo group (dist.HostStagedComm).  Validation, test and saving
     run on the shards in place (eval.evaluate_sharded, dist.write_npy_sharded)."""
 
-    def __init__(self, args, dataset, rank, world):
-        from . import dist as kd
-        from .dataloader import DeviceSampler
-        from .engine import StepEngine
-        self.args, self.dataset, self.rank, self.world = args, dataset, rank, world
-        th.cuda.set_device(args.gpu[rank])
-        self.dev = th.device("cuda", args.gpu[rank])
+    def build(self):
+        args, dataset, rank, world = self.args, self.dataset, self.rank, self.world
         B, N = args.batch_size, args.neg_sample_size
-        self.chunk = N if N <= B else B
-        self.fused, self.n_lanes, self.async_ok = True, 1, False
-        # the on-device sampler builds the batches of a whole group ahead (group routing, one id exchange, group graphs); batches it
-        # cannot build - edge importance, or more than 8192 ids per batch - come from the host sampler: plans built on the host,
-        # routed and exchanged step by step, eager launches (the same sharded step; slower: the host builds a plan per step)
-        self.device_sampler = 2 * B + (B // self.chunk) * N <= 8192 and not args.has_edge_importance
-        # TransR / RESCAL (round 6): the relation side - relation rows / matrices, TransR's projection table - is applied IN PLACE on the
-        # trainer that holds the relation's edges, so the triples are always partitioned by whole relations for these two (the
-        # reference's own multi-GPU TransR recipe passes --rel_part, examples/freebase/multi_gpu.sh:80-89); only entity messages travel
-        self.rel_side_local = args.model_name in ('RESCAL', 'TransR')
-        if self.rel_side_local and args.neg_deg_sample:
-            raise KgeError("--neg_deg_sample is not available for %s on more than one GPU" % args.model_name)
-        d_e = args.hidden_dim * (2 if args.double_ent else 1)
-        self.emb_init = (args.gamma + 2.0) / args.hidden_dim
-        self.spec = kd.ShardSpec(dataset.n_entities, world, rank)
-        th.manual_seed(args.seed + 7919 * (rank + 1))
-        self.ent = th.empty(self.spec.n_local, d_e, dtype=th.float32, device=self.dev).uniform_(-self.emb_init, self.emb_init)
-        self.ent_state = th.zeros(self.spec.n_local, dtype=th.float32, device=self.dev)
-        th.manual_seed(args.seed)                       # identical relation replicas on every rank
-        self.engine = StepEngine(args.model_name, 1, dataset.n_relations, args.hidden_dim, args.gamma, args.lr, self.dev,
-                                 args.double_ent, args.double_rel, args.neg_adversarial_sampling,
-                                 args.adversarial_temperature, args.regularization_coef, args.regularization_norm,
-                                 args.loss_genre, args.pairwise, args.margin,
-                                 flags=_lib.FLAG_NEG_DEG_SAMPLE if args.neg_deg_sample else 0)
-        own_gpu = len(set(args.gpu)) == world
-        self.comm = kd.make_comm() if own_gpu else kd.HostStagedComm()
-        slack = args.dist_slack if getattr(args, 'dist_slack', None) else float(os.environ.get("KGE_DIST_SLACK", "1.5"))
-        # --rel_part (the reference's multi-GPU recipes pass it, examples/freebase/multi_gpu.sh): the triples are split BY RELATION
+        tr = dataset.train
+        # --rel_part (the reference's multi-GPU recipes pass it, examples/freebase/multi_gpu.sh; always for TransR / RESCAL, whose
+        # relation side is applied IN PLACE on the trainer that holds the relation's edges): the triples are split BY RELATION
         # (dist.choose_relation_partition: whole relations while that balances, else the reference's SoftRelationPartition with its
         # large relations dealt over all trainers).  While every relation lives on ONE trainer its row is updated there and nowhere
         # else - no relation exchange (dist.DistEngine rel_local); with split relations the relation gradients are all-gathered
         # and applied by every trainer like without --rel_part (exact for any edge split), only the edge shares are the reference's
-        self.rel_part = bool(getattr(args, 'rel_part', False)) or self.rel_side_local
-        tr = dataset.train
-        self.rel_owner, self.rel_local, part = None, False, None
+        self.rel_part = args.rel_part or self.rel_side_local
+        self.rel_local, edge_rank, refusal = False, None, None
         if self.rel_part:
             mode, edge_rank, self.rel_owner, cross = kd.choose_relation_partition(
-                tr[1], world, 'whole' if self.rel_side_local else getattr(args, 'rel_part_policy', 'auto'))
+                tr[1], world, 'whole' if self.rel_side_local else args.rel_part_policy)
             self.rel_local = len(cross) == 0
-            part = np.nonzero(edge_rank == rank)[0]
+            n_rel = int((self.rel_owner != -1).sum())
             cnt = np.bincount(edge_rank, minlength=world)
             if rank == 0:
                 print("relation partition (%s): %d relations over %d trainers, edges per trainer %s%s" % (
-                    mode, int((self.rel_owner != -1).sum()), world, cnt.tolist(),
+                    mode, n_rel, world, cnt.tolist(),
                     "" if self.rel_local else "; %d relations split over the trainers: relation gradients all-gathered" % len(cross)))
                 if cnt.max() > 1.5 * cnt.mean():
                     # (--rel_part_policy whole only: a relation with more than 1 / world of the edges unbalances the trainers; every
@@ -722,41 +631,34 @@ class A2ATrainer(ShardedTrainer):
                     print("WARNING: --rel_part leaves trainer %d with %.2f x the mean edge share (whole relations only; the most "
                           "frequent relation holds %.1f %% of the edges; --rel_part_policy soft splits it)"
                           % (int(cnt.argmax()), cnt.max() / cnt.mean(), 100.0 * np.bincount(np.asarray(tr[1])).max() / len(tr[1])))
-            if cnt.min() < B:            # the partition is the same on every rank: every rank sees the short one and stops HERE, before
-                raise KgeError("--rel_part: trainer %d gets %d training triples, fewer than --batch_size %d (%d relations over %d "
-                               "trainers)" % (int(cnt.argmin()), int(cnt.min()), B, int((self.rel_owner != -1).sum()), world))   # any collective
+            refusal = ("--rel_part: trainer %%(trainer)d gets %%(share)d training triples, fewer than --batch_size %%(batch)d "
+                       "(%d relations over %%(n)d trainers)" % n_rel)
+        part = self.split(world, edge_rank, refusal)[rank]
+        self.spec = kd.ShardSpec(dataset.n_entities, world, rank)
+        th.manual_seed(args.seed + 7919 * (rank + 1))
+        self.ent = th.empty(self.spec.n_local, self.d_e, dtype=th.float32, device=self.dev).uniform_(-self.emb_init, self.emb_init)
+        self.ent_state = th.zeros(self.spec.n_local, dtype=th.float32, device=self.dev)
+        th.manual_seed(args.seed)                       # identical relation replicas on every rank
+        self.engine = self.make_engine(n_entities=1)    # (the entity rows of a step come from the shards: DistEngine's row cache)
+        self.comm = kd.make_comm() if len(set(args.gpu)) == world else kd.HostStagedComm()
+        slack = args.dist_slack or float(os.environ.get("KGE_DIST_SLACK", "1.5"))
         self.de = kd.DistEngine(self.engine, self.spec, self.ent, self.ent_state, comm=self.comm, slack=slack,
-                                rel_local=self.rel_local,
-                                ue_bound=None if self.device_sampler else 2 * B + (B // self.chunk) * N)
+                                rel_local=self.rel_local, ue_bound=None if self.device_sampler else 2 * B + self.C * N)
         # exchanges may overlap the steps only under the staleness --async_update licenses (tensor_models.py:136-175): then push,
         # owner-side apply and the pull of step s+2 run on a side stream next to step s+1 (DistEngine._steps_overlapped: entity rows
         # exactly one step stale, relation rows current; KGE_DIST_PIPELINE=1: the pull only, the same tables bit for bit);
         # without the flag every step gathers after its predecessor's update has landed, like the reference
-        self.pipelined = bool(getattr(args, 'async_update', False))
+        self.pipelined = args.async_update
         if self.pipelined and os.environ.get("KGE_DIST_PIPELINE", "overlap") == "overlap":
             self.pipelined = "overlap"
-        # --dist_schedule (the schedule used to be reachable through an environment variable only): sync = every step pulls
-        # after its predecessor's update (what runs without --async_update), pull = the pull of step s+1 next to step s, overlap = every
-        # exchange on a side stream (the default with --async_update); the two stale schedules need the flag's licence
-        sched = getattr(args, 'dist_schedule', None)
-        if sched:
-            if sched != 'sync' and not getattr(args, 'async_update', False):
-                raise KgeError("--dist_schedule %s computes on one-step-stale entity rows: it needs --async_update" % sched)
-            self.pipelined = {'sync': False, 'pull': True, 'overlap': 'overlap'}[sched]
-        if part is None:
-            part = np.array_split(np.random.RandomState(args.seed).permutation(len(tr[0])), world)[rank]
-        if len(part) < B:
-            raise KgeError("--batch_size %d is larger than a trainer's share of the training triples (%d over %d trainers)"
-                           % (B, len(tr[0]), world))
-        h, r, t = (np.asarray(x)[part] for x in tr[:3])
-        if self.device_sampler:
-            self.sampler = DeviceSampler(h, r, t, dataset.n_entities, B, N, self.dev, n_slots=max(2, args.graph_steps or 2),
-                                         neg_chunk_size=self.chunk, seed=args.seed + 1000 * rank)
-        else:
-            from .dataloader import UniformChunkedSampler
-            w = np.asarray(tr[3])[part] if args.has_edge_importance else None
-            self.sampler = UniformChunkedSampler(h, r, t, dataset.n_entities, B, N, self.dev, neg_chunk_size=self.chunk,
-                                                 seed=args.seed + 1000 * rank, edge_importance=w)
+        # --dist_schedule: sync = every step pulls after its predecessor's update (what runs without --async_update), pull = the pull
+        # of step s+1 next to step s, overlap = every exchange on a side stream (the default with --async_update); the two stale
+        # schedules need the flag's licence
+        if args.dist_schedule:
+            if args.dist_schedule != 'sync' and not args.async_update:
+                raise KgeError("--dist_schedule %s computes on one-step-stale entity rows: it needs --async_update" % args.dist_schedule)
+            self.pipelined = {'sync': False, 'pull': True, 'overlap': 'overlap'}[args.dist_schedule]
+        self.sampler = self.make_sampler(rank, part)
         if rank == 0:
             print("multi-GPU mode a2a: entity rows %d per GPU, relations replicated, collectives: %s"
                   % (self.spec.shard, type(self.comm).__name__))
@@ -765,7 +667,7 @@ class A2ATrainer(ShardedTrainer):
                       "trainer that holds the relation's edges" % (args.model_name, world,
                                                                     ", projection matrices" if args.model_name == 'TransR' else " = matrices"))
 
-    def _enqueue(self, n):
+    def enqueue(self, n):
         """n sharded steps, eagerly (every rank issues the same collectives in the same order); inside a group of sampled
         batches the pull of step s+1 overlaps step s."""
         smp, done = self.sampler, 0
@@ -794,7 +696,6 @@ class A2ATrainer(ShardedTrainer):
         every rank's replica."""
         th.cuda.synchronize()
         if self.rel_local:                   # every replica holds the current rows of ITS relations only: collect them everywhere
-            from . import dist as kd
             kd.relation_rows_from_owners(self.engine.rel, self.engine.rel_state, self.rel_owner, everywhere=True)
             if self.engine.proj is not None:     # TransR: the projection rows live with their relation
                 kd.relation_rows_from_owners(self.engine.proj, self.engine.proj_state, self.rel_owner, everywhere=True)
@@ -803,7 +704,6 @@ class A2ATrainer(ShardedTrainer):
         return self.spec.lo, self.ent
 
     def entity_rows(self, ids):
-        from . import eval as kev
         return kev.allgather_rows(self.ent, self.spec.lo, self.spec.bounds(), ids, self.comm)
 
     def relation_table(self):
@@ -816,69 +716,47 @@ class A2ATrainer(ShardedTrainer):
         self.de.close()              # the group graphs first, then the communicator (dist.RcclComm.close)
 
 
-def _mp_worker(rank, args, port):
+def _mp_worker(rank, args):
     import torch.distributed as dist
-    world = len(args.gpu)
-    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
+    init_time_start = time.time()
+    dataset = kd.load_dataset(rank, args)
+    trainer = (A2ATrainer if args.dist_mode == 'a2a' else ShardedTrainer)(args, dataset, rank, len(args.gpu))
+    if rank == 0:
+        print('Total initialize time {:.3f} seconds'.format(time.time() - init_time_start))
+    start = time.time()
+    trainer.train()
+    failure = None
+    trainer.sync_tables()
+    # saving and testing are collective: every rank writes its rows of the entity file and ranks against its own shard
     try:
-        init_time_start = time.time()
-        if rank != 0:                            # one copy of the loader messages is enough
-            sys.stdout = open(os.devnull, "w")
-        dataset = get_dataset(args.data_path, args.dataset, args.format, args.delimiter, args.data_files,
-                              args.has_edge_importance)
-        sys.stdout = sys.__stdout__
-        a2a = args.dist_mode == 'a2a'
-        trainer = (A2ATrainer if a2a else ShardedTrainer)(args, dataset, rank, world)
         if rank == 0:
-            print('Total initialize time {:.3f} seconds'.format(time.time() - init_time_start))
-        start = time.time()
-        trainer.train()
-        failure = None
-        trainer.sync_tables()
-        # saving and testing are collective: every rank writes its rows of the entity file and ranks against its own shard
-        try:
+            print('training takes {} seconds'.format(time.time() - start))
+        if not args.no_save_emb:
             if rank == 0:
-                print('training takes {} seconds'.format(time.time() - start))
-            if not args.no_save_emb:
-                if rank == 0:
-                    print('Save model to {}'.format(args.save_path))
-                trainer.save(dataset.emap_fname, dataset.rmap_fname)
-            if args.test:
-                start = time.time()
-                trainer.evaluate('test', 'Test')
-                if rank == 0:
-                    print('testing takes {:.3f} seconds'.format(time.time() - start))
-        except Exception as e:      # noqa: BLE001 - re-raised after the barrier
-            failure = e
-        dist.barrier()
-        trainer.close()
-        if failure is not None:
-            raise failure
-    finally:
-        dist.destroy_process_group()
-
-
-def launch_multi_gpu(args):
-    """`--gpu g0 g1 ...`: one trainer process per listed GPU (the same GPU may be listed twice: the processes
-    then share it, which is how the path is tested on a one-GPU box)."""
-    import socket
-    import torch.multiprocessing as mp
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    mp.spawn(_mp_worker, args=(args, port), nprocs=len(args.gpu), join=True)
+                print('Save model to {}'.format(args.save_path))
+            trainer.save(dataset.emap_fname, dataset.rmap_fname)
+        if args.test:
+            start = time.time()
+            trainer.evaluate('test', 'Test')
+            if rank == 0:
+                print('testing takes {:.3f} seconds'.format(time.time() - start))
+    except Exception as e:      # noqa: BLE001 - re-raised after the barrier
+        failure = e
+    dist.barrier()
+    trainer.close()
+    if failure is not None:
+        raise failure
 
 
 def check_exclude_positive(args):
     """--exclude_positive runs on the strict single-table step (kge_step_fused_known): refuse what has no such step"""
-    if not getattr(args, 'exclude_positive', False):
+    if not args.exclude_positive:
         return
     if len(args.gpu) > 1:
         raise KgeError("--exclude_positive is not available on more than one GPU (sharded tables)")
     if args.neg_deg_sample:
         raise KgeError("--exclude_positive is not available with --neg_deg_sample")
-    if getattr(args, 'async_update_pipeline', False) or getattr(args, 'async_update_rel', False):
+    if args.async_update_pipeline or args.async_update_rel:
         raise KgeError("--exclude_positive is not available in the one-step-stale pipeline (--async_update_pipeline / "
                        "--async_update_rel); plain --async_update runs the strict step and is fine")
 
@@ -894,34 +772,30 @@ def main(argv=None):
         raise KgeError("--eval_relation is not available on sharded tables")
     prepare_save_path(args)
     init_time_start = time.time()
-    if len(args.gpu) > 1:                        # multi-GPU: one process per GPU on peer-to-peer shared tables
-        if min(args.gpu) < 0:
-            raise KgeError("dglke_amd trains on the GPU only: pass --gpu <ids> (there is no CPU fallback)")
-        if args.log_interval <= 0:
-            raise KgeError("--log_interval must be positive")
-        if args.num_proc > len(args.gpu):            # reference: several trainer processes per GPU (train.py:94-100, 115-119)
-            if args.num_proc % len(args.gpu):
-                raise KgeError("--num_proc should be a multiple of the number of GPUs")
-            args.gpu = [g for g in args.gpu for _ in range(args.num_proc // len(args.gpu))]
-        args.batch_size = get_compatible_batch_size(args.batch_size, args.neg_sample_size)
-        args.eval_filter = not args.no_eval_filter
-        args.soft_rel_part = args.strict_rel_part = False
-        launch_multi_gpu(args)
-        return None
+    multi = len(args.gpu) > 1                    # one trainer process per listed GPU (the same GPU may be listed twice)
+    if multi and min(args.gpu) < 0:
+        raise KgeError("dglke_amd trains on the GPU only: pass --gpu <ids> (there is no CPU fallback)")
     if args.log_interval <= 0:
         raise KgeError("--log_interval must be positive")
-    dataset = get_dataset(args.data_path, args.dataset, args.format, args.delimiter, args.data_files,
-                          args.has_edge_importance)
-    if args.test and dataset.test is None:
-        raise KgeError("--test: the dataset has no test split")
-    if args.neg_sample_size_eval < 0:
-        args.neg_sample_size_eval = dataset.n_entities
+    if multi and args.num_proc > len(args.gpu):      # reference: several trainer processes per GPU (train.py:94-100, 115-119)
+        if args.num_proc % len(args.gpu):
+            raise KgeError("--num_proc should be a multiple of the number of GPUs")
+        args.gpu = [g for g in args.gpu for _ in range(args.num_proc // len(args.gpu))]
+    if not multi:
+        dataset = kd.load_dataset(0, args)
+        if args.test and dataset.test is None:
+            raise KgeError("--test: the dataset has no test split")
+        if args.neg_sample_size_eval < 0:
+            args.neg_sample_size_eval = dataset.n_entities
     args.batch_size = get_compatible_batch_size(args.batch_size, args.neg_sample_size)
-    args.batch_size_eval = get_compatible_batch_size(args.batch_size_eval, args.neg_sample_size_eval)
+    if not multi:
+        args.batch_size_eval = get_compatible_batch_size(args.batch_size_eval, args.neg_sample_size_eval)
     args.eval_filter = not args.no_eval_filter
-    if args.neg_deg_sample_eval:
-        assert not args.eval_filter, "if negative sampling based on degree, we can't filter positive edges."
     args.soft_rel_part = args.strict_rel_part = False     # one replicated HBM relation table
+    if multi:
+        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+        kd.spawn_ranks(_mp_worker, args)
+        return None
     trainer = Trainer(args, dataset)
     print('Total initialize time {:.3f} seconds'.format(time.time() - init_time_start))
     start = time.time()

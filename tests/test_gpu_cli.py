@@ -44,7 +44,7 @@ def test_train_cli_end_to_end(tmp_path, capsys, model, extra):
     out = capsys.readouterr().out
     if "--neg_deg_sample" in extra:      # it runs on the fused step, not on the per-op drop-in path
         from dglke_amd import _lib
-        assert tr.fused and tr.model.engine.hp.flags & _lib.FLAG_NEG_DEG_SAMPLE
+        assert all(l.engine.hp.flags & _lib.FLAG_NEG_DEG_SAMPLE for l in tr.lanes) and tr.model.engine.hp.flags & _lib.FLAG_NEG_DEG_SAMPLE
     # reference log formats (train_pytorch.py:165-172, :236-247)
     assert "[proc 0][Train](500/1250) average loss:" in out and "[proc 0][Train](1000/1250) average pos_loss:" in out
     assert "[0]Valid average MRR:" in out and "[0]Test average HITS@10:" in out and "training takes" in out
@@ -228,7 +228,8 @@ def test_train_cli_transr_lanes_and_rejected_flags(tmp_path, capsys):
     for model, lanes in (("TransR", "1"), ("TransR", "2"), ("RESCAL", "2")):
         tr2 = T.main(_base(tmp_path, model) + ["--max_step", "300", "--neg_deg_sample", "--num_proc", lanes, "--lr", "0.05"])
         out = capsys.readouterr().out
-        assert tr2.fused and tr2.step_flags & 32 and len(tr2.lanes) == int(lanes)
+        from dglke_amd import _lib
+        assert all(l.engine.hp.flags & _lib.FLAG_NEG_DEG_SAMPLE for l in tr2.lanes) and tr2.step_flags & 32 and len(tr2.lanes) == int(lanes)
         loss = float([l for l in out.split("\n") if "(300/300) average loss:" in l][0].split(":")[1])
         assert np.isfinite(loss) and 0.0 < loss < 5.0, out[-800:]
     with pytest.raises(KgeError):

@@ -358,3 +358,112 @@ def test_device_filter_lists_equal_the_host_lists():
                                 torch.device("cpu"))
     assert big is not None and big[0].shape == (5, 2)
     assert E.build_filter_device(known, test, True, 1 << 40, 1 << 30, torch.device("cpu")) is None
+
+
+# ---- dglke_train / dglke_eval driver: the step marks of the training loop and the evaluation setup ------------------------------
+
+def test_step_marks_against_hand_written_lists():
+    from dglke_amd.train import step_marks
+    assert step_marks(1250, 500, 1000, True) == [500, 1000, 1250]
+    assert step_marks(1250, 500, 1000, False) == [500, 1000, 1250]
+    assert step_marks(1250, 500, 300, True) == [300, 500, 600, 900, 1000, 1200, 1250]
+    assert step_marks(1250, 500, 300, False) == [500, 1000, 1250]           # --eval_interval counts with --valid only
+    assert step_marks(400, 1000, 10000, True) == [400]
+    # --force_sync_interval 150 where it applies (lanes on one GPU, several GPUs) and where it does not
+    assert step_marks(600, 300, 10000, False, 150, True) == [150, 300, 450, 600]
+    assert step_marks(500, 300, 10000, False, 150, True) == [150, 300, 450, 500]
+    assert step_marks(600, 300, 10000, False, 150, False) == [300, 600]
+    assert step_marks(600, 300, 10000, False, -1, True) == [300, 600]         # the flag's default: never
+
+
+class _Splits(object):
+    def __init__(self, n_entities, n_train, n_valid, n_test, seed=0):
+        rng = np.random.RandomState(seed)
+        self.n_entities, self.n_relations = n_entities, 7
+
+        def trip(n):
+            return None if n is None else (rng.randint(0, n_entities, n), rng.randint(0, 7, n), rng.randint(0, n_entities, n))
+        self.train, self.valid, self.test = trip(n_train), trip(n_valid), trip(n_test)
+
+
+def _eval_args(**kw):
+    import argparse
+    a = dict(model_name='TransE_l2', eval_percent=1, seed=5, eval_filter=True, batch_size_eval=16)
+    a.update(kw)
+    return argparse.Namespace(**a)
+
+
+def test_eval_setup_batch():
+    from dglke_amd._lib import KgeError
+    from dglke_amd.eval import eval_setup
+    fb = _Splits(14951, 100, 50, 59071)                     # FB15k's entity and test-triple counts
+    assert eval_setup(fb, 'test', _eval_args())[2] == 4096
+    assert eval_setup(fb, 'test', _eval_args(batch_size_eval=5000))[2] == 5000
+    assert eval_setup(fb, 'test', _eval_args(model_name='TransR'))[2] == 64
+    assert eval_setup(_Splits(14951, 100, 50, 3), 'test', _eval_args())[2] == 3
+    assert eval_setup(_Splits(14951, 100, 50, 3), 'test', _eval_args(model_name='TransR'))[2] == 3
+    # a [batch, entities] float32 score block stays within 2 GiB
+    assert eval_setup(_Splits(1 << 20, 100, 50, 59071), 'test', _eval_args())[2] == 512
+    with pytest.raises(KgeError, match="no valid split"):
+        eval_setup(_Splits(100, 100, None, 10), 'valid', _eval_args())
+
+
+def test_eval_setup_eval_percent_keeps_the_same_rows_of_triples_and_candidates():
+    from dglke_amd.eval import eval_setup
+    ds = _Splits(300, 1000, 200, 137)
+    n = 137
+    cand_h = np.arange(n * 4).reshape(n, 4)
+    test, known, batch, cands = eval_setup(ds, 'test', _eval_args(eval_percent=0.1), [cand_h, None])
+    keep = np.random.RandomState(5 + 17).permutation(n)[:max(1, int(0.1 * n))]
+    assert len(keep) == 13 and batch == 13
+    for got, full in zip(test, ds.test):
+        assert np.array_equal(got, full[keep])
+    assert np.array_equal(cands[0], cand_h[keep]) and cands[1] is None
+    assert all(len(k) == 1000 + 200 + 137 for k in known)            # the known set is never subsampled
+    # a share that rounds to nothing keeps one triple; the whole split comes back untouched, in order
+    assert len(eval_setup(ds, 'test', _eval_args(eval_percent=0.001))[0][0]) == 1
+    test, _, _, cands = eval_setup(ds, 'valid', _eval_args())
+    assert cands is None and all(np.array_equal(a, b) for a, b in zip(test, ds.valid))
+
+
+def test_eval_setup_known_set():
+    from dglke_amd.eval import eval_setup
+    ds = _Splits(300, 1000, 200, 137)
+    known = eval_setup(ds, 'test', _eval_args())[1]
+    for k in range(3):
+        assert np.array_equal(known[k], np.concatenate([ds.train[k], ds.valid[k], ds.test[k]]))
+    ds = _Splits(300, 1000, None, 137)                      # no valid split: the splits that exist
+    known = eval_setup(ds, 'test', _eval_args())[1]
+    for k in range(3):
+        assert np.array_equal(known[k], np.concatenate([ds.train[k], ds.test[k]]))
+    assert eval_setup(ds, 'test', _eval_args(eval_filter=False))[1] is None           # --no_eval_filter
+
+
+def test_split_of_the_training_triples_and_its_refusal():
+    """one trainer: every row in order; several: the random partition by --seed, or the rows a relation partition assigns; a share
+    below one batch is refused whichever trainer it falls to (every rank computes the same partition and raises)"""
+    import argparse
+    import types
+    from dglke_amd import train as T
+    from dglke_amd._lib import KgeError
+    ds = _Splits(300, 1001, 10, 10)
+
+    def split(batch, *a, **k):
+        t = types.SimpleNamespace(args=argparse.Namespace(batch_size=batch, seed=4), dataset=ds)
+        return T._Trainer.split(t, *a, **k)
+    (part,) = split(256, 1)
+    assert np.array_equal(ds.train[0][part], ds.train[0])
+    parts = split(256, 3)
+    want = np.array_split(np.random.RandomState(4).permutation(1001), 3)
+    assert len(parts) == 3 and all(np.array_equal(a, b) for a, b in zip(parts, want))
+    edge_rank = (ds.train[1] >= 2).astype(np.int64)             # relations 0, 1 -> trainer 0
+    parts = split(256, 2, edge_rank)
+    assert np.array_equal(parts[0], np.nonzero(ds.train[1] < 2)[0]) and np.array_equal(parts[1], np.nonzero(ds.train[1] >= 2)[0])
+    with pytest.raises(KgeError, match="--batch_size 400 is larger than a trainer's share of the training triples .1001 over 3 trainers."):
+        split(400, 3)
+    n0 = int((ds.train[1] < 2).sum())
+    with pytest.raises(KgeError, match="trainer 0 gets %d training triples, fewer than --batch_size 400" % n0):
+        split(400, 2, edge_rank, "relation partition: trainer %(trainer)d gets %(share)d training triples, fewer than --batch_size %(batch)d")
+    assert len(split(1001, 1)) == 1
+    with pytest.raises(KgeError):
+        split(1002, 1)
