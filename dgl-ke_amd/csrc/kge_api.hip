@@ -30,6 +30,9 @@ int fail(int code, const char *fmt, ...) {
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
+// kge_debug_carve (test support): where to record the carved buffers of this thread's calls, and the gap behind each
+thread_local struct { int64_t *trace; int cap, count; size_t gap; bool on; } g_carve = {nullptr, 0, 0, 0, false};
+
 // bump allocator over the caller's workspace.  Each workspace has ONE carve function (carve_neg, carve_step, carve_rank): the
 // entry point carves its buffers with it, the *_workspace_bytes function runs it on a measuring Carver and returns the offset
 struct Carver {
@@ -38,7 +41,7 @@ struct Carver {
     Carver() : Carver(nullptr, SIZE_MAX) {}            // measuring: the pointers it hands out are never used
     void *bytes(size_t n) {
         const size_t o = off;
-        off = align_up(off + n);
+        off = align_up(off + n + kge_carve_note(o, n));
         return (void *)(base + o);
     }
     float *f(size_t n_floats) { return (float *)bytes(n_floats * sizeof(float)); }
@@ -136,10 +139,29 @@ __global__ void l2_scale_kernel(const float *dneg, const float *score, float gam
 
 int kge_fail(int code, const char *msg) { return fail(code, "%s", msg); }
 
+size_t kge_carve_note(size_t off, size_t bytes) {
+    if (!g_carve.on) return 0;
+    if (g_carve.trace && g_carve.count < g_carve.cap) {
+        g_carve.trace[2 * g_carve.count] = (int64_t)off;
+        g_carve.trace[2 * g_carve.count + 1] = (int64_t)bytes;
+    }
+    g_carve.count++;
+    return g_carve.gap;
+}
+
 extern "C" {
 
 int kge_abi_version(void) { return KGE_ABI_VERSION; }
 const char *kge_last_error(void) { return g_err; }
+
+// test support: trace + guard gaps of every buffer this thread carves from now on (include/kge_hip.h)
+int kge_debug_carve(int64_t *trace, int cap_pairs, size_t gap) {
+    if (cap_pairs < 0 || (cap_pairs > 0 && !trace)) return fail(KGE_ERR_ARG, "kge_debug_carve: bad argument");
+    g_carve.trace = cap_pairs ? trace : nullptr; g_carve.cap = cap_pairs; g_carve.count = 0; g_carve.gap = gap;
+    g_carve.on = cap_pairs > 0 || gap > 0;
+    return KGE_OK;
+}
+int kge_debug_carve_count(void) { return g_carve.count; }
 
 int kge_gather_rows(const float *table, int64_t n_rows, int dim, const int64_t *idx, int64_t n_idx,
                     float *out, void *stream) {
@@ -317,15 +339,15 @@ int kge_loss_fwd_bwd(int loss_genre, int adv, float adv_temp, int pairwise, floa
         return fail(KGE_ERR_ARG, "kge_loss_fwd_bwd: bad argument");
     Carver cv(ws, ws_bytes);
     float *row_pos = cv.f(B), *row_neg = cv.f(B);
-    if (!cv.ok()) return fail(KGE_ERR_WORKSPACE, "workspace too small");
+    // finalize writes 4 floats {pos, neg, loss, reg}; loss3 has room for 3 -> stage in ws (carved before the first launch: a
+    // workspace too small for it is refused with nothing enqueued)
+    float *l4 = loss3 ? cv.f(4) : nullptr;
+    if (!cv.ok()) return fail(KGE_ERR_WORKSPACE, "workspace too small (%zu < %zu)", ws_bytes, cv.off);
     LossArgs a;
     fill_loss(a, LossParams{loss_genre, adv, pairwise, adv_temp, margin}, (int)B, N, pos, neg, w, dpos, dneg);
     a.row_pos = row_pos; a.row_neg = row_neg;
     KGE_TRY(launch_loss(a, (hipStream_t)stream));
     if (loss3) {
-        // finalize writes 4 floats {pos, neg, loss, reg}; loss3 has room for 3 -> stage in ws
-        float *l4 = cv.f(4);
-        if (!cv.ok()) return fail(KGE_ERR_WORKSPACE, "workspace too small");
         FinalizeArgs f{};
         f.B = (int)B; f.UE = 0; f.UR = 0; f.pairwise = pairwise;
         f.row_pos = row_pos; f.row_neg = row_neg; f.loss4 = l4;
@@ -357,8 +379,9 @@ int kge_scatter_add_rows(float *out, int64_t n_rows, int dim, const int64_t *idx
 }
 
 int kge_pnorm_pow(const float *x, int64_t n, int dim, int p, float *out, void *ws, size_t ws_bytes, void *stream) {
-    if (!out || (n && !x) || n < 0 || dim <= 0 || p <= 0 || !ws || ws_bytes < (size_t)(n > 0 ? n : 1) * sizeof(float))
-        return fail(KGE_ERR_ARG, "kge_pnorm_pow: bad argument (workspace: n floats)");
+    if (!out || (n && !x) || n < 0 || dim <= 0 || p <= 0 || !ws) return fail(KGE_ERR_ARG, "kge_pnorm_pow: bad argument");
+    if (ws_bytes < (size_t)(n > 0 ? n : 1) * sizeof(float))
+        return fail(KGE_ERR_WORKSPACE, "kge_pnorm_pow: workspace too small (%zu < n floats = %zu)", ws_bytes, (size_t)(n > 0 ? n : 1) * sizeof(float));
     KGE_TRY(launch_pnorm(x, n, dim, p, (float *)ws, out, (hipStream_t)stream));
     return KGE_OK;
 }

@@ -525,6 +525,9 @@ struct FinalizeArgs {
 };
 
 int kge_fail(int code, const char *msg);      // records the message kge_last_error() returns (kge_api.hip); returns code
+// both workspace allocators (Carver in kge_api.hip, carve in kge_topk.hip) report every buffer here: records (offset, bytes) while
+// kge_debug_carve has a trace set on this thread and returns the guard gap to leave behind the buffer (0 when the setting is off)
+size_t kge_carve_note(size_t off, size_t bytes);
 int launch_gather_rows(const float *table, int dim, const int64_t *idx, int64_t n, float *out,
                        hipStream_t s);
 int launch_nd_ids(const int64_t *own, const int64_t *neg_ids, int C, int chunk, int Ns, int64_t *out, hipStream_t s);   // [own | sampled] ids per chunk

@@ -434,7 +434,7 @@ TkWs carve(void *ws, int rows, int64_t N, int D, int K) {
     TkWs w{};
     char *b = (char *)ws;
     size_t off = 0;
-    auto take = [&](size_t bytes) { char *p = b ? b + off : nullptr; off += al(bytes); return p; };
+    auto take = [&](size_t bytes) { char *p = b ? b + off : nullptr; off = al(off + bytes + kge_carve_note(off, bytes)); return p; };
     if (rows > 0) {
         const size_t ent = (size_t)rows * (size_t)topk_seg_cap(rows, K) * K;
         w.A = (float *)take((size_t)rows * D * 4);

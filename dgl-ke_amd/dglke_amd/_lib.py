@@ -194,6 +194,8 @@ _SIGNATURES = {
     "kge_ipc_export": (c_i, [c_p, c_p, C.POINTER(c_i64)]),
     "kge_ipc_open": (c_i, [c_p, C.POINTER(c_p)]),
     "kge_ipc_close": (c_i, [c_p]),
+    "kge_debug_carve": (c_i, [c_p, c_i, c_sz]),      # test support (include/kge_hip.h): trace is a HOST int64 array
+    "kge_debug_carve_count": (c_i, []),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

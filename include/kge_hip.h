@@ -154,7 +154,8 @@ int kge_score_neg_bwd(int model, int neg_head, const float *pos_side, const floa
 /* ---- A6: LossGenerator.get_total_loss (models/pytorch/loss.py:69-98) + its gradient ----
  * pos [B], neg [B,N], w = edge importance [B] or NULL.  loss3 = {pos_loss, neg_loss, loss}
  * (pairwise: {nan, nan, loss}); dpos [B], dneg [B,N] = d loss / d score.
- * ws: scratch of >= 2*B floats. */
+ * ws: scratch of 2 * a(4 * B) bytes, + 256 when loss3 is asked, a(x) = x rounded up to a multiple of 256 (two [B] float rows and
+ * the staged loss terms, each 256-byte aligned); KGE_ERR_WORKSPACE before any launch when it is smaller. */
 int kge_loss_fwd_bwd(int loss_genre, int adv, float adv_temp, int pairwise, float margin,
                      const float *pos, const float *neg, const float *w, int64_t B, int N,
                      float *loss3, float *dpos, float *dneg, void *ws, size_t ws_bytes,
@@ -279,6 +280,18 @@ typedef struct kge_step_out {
  * averages the reference prints, train_pytorch.py:165-167); optionally zero the slots. */
 int kge_reduce_loss(float *loss_accum, float *out4, int zero_after, void *stream);
 
+/* ---- the workspace contract: holds for EVERY (ws, ws_bytes) pair of this header, sized by its *_workspace_bytes function ----
+ *  - contents on entry are arbitrary: the library never reads a workspace byte that the same call has not written before
+ *    (calls that share a workspace by design - the phases of one kge_step_phase step, the steps of one kge_step_async group up
+ *    to the flush, the jobs k = 0 .. last (advance > 0) of one sampler group on their tail scratch: job k's third phase reads its
+ *    header and sorted keys under the first launch of job k + 1's step - count as one call);
+ *  - contents on exit are unspecified;
+ *  - nothing is written outside the buffers carved from [ws, ws + need), need = what the size function returns: a caller may
+ *    allocate exactly that many bytes, and each carved buffer is written within its own bounds;
+ *  - ws must be 256-byte aligned;
+ *  - the caller-zeroed words are no workspace and must hold zeros when first handed over: kge_step_out.tickets,
+ *    kge_step_out.loss_accum, the sampler `state` and the route counters.
+ * ws_bytes below the size function's value returns KGE_ERR_WORKSPACE before any launch. */
 size_t kge_step_workspace_bytes(const kge_hparams *hp, int B, int C, int chunk, int N, int UE,
                                 int UR);
 /* forward + backward + update of one batch, enqueued on `stream`. */
@@ -748,6 +761,16 @@ int kge_step_fused_known(const kge_hparams *hp, const kge_tables *tb, const kge_
                          void *stream);
 int kge_step_phase_known(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
                          size_t ws_bytes, int phases, const kge_known *known, uint32_t *mask, size_t mask_bytes, void *stream);
+
+/* ---- test support: not part of the stable boundary ----
+ * kge_debug_carve: while set (per calling thread), every buffer that an entry point or a *_workspace_bytes function carves from a
+ * workspace is recorded as trace[2k] = offset from the base that carve started at, trace[2k + 1] = bytes (HOST memory, room for
+ * cap_pairs pairs; further buffers are counted, not recorded), and `gap` extra bytes are left behind every buffer before the
+ * 256-byte round-up.  The size functions and the entries share the allocators, so they agree with the gap as without it.  The
+ * call resets the count; (NULL, 0, 0) switches the setting off: the layout is then exactly the documented one.
+ * kge_debug_carve_count: buffers carved by this thread since its last kge_debug_carve call. */
+int kge_debug_carve(int64_t *trace, int cap_pairs, size_t gap);
+int kge_debug_carve_count(void);
 
 #ifdef __cplusplus
 }
