@@ -175,6 +175,43 @@ def step_marks(max_step, log_interval, eval_interval, valid, force_sync_interval
     return sorted(marks)
 
 
+def plan_enqueue(n, G, host_step, have_group_graph, n_slots, rem_keys):
+    """what `_Lane.enqueue(n)` does on the device sampler, as a list of (kind, k, parity) and the sampler's host step afterwards:
+    k steps that start at a host step of that parity (1: the first of them corrupts tails), kind one of
+      'eager'         one sampler launch + k steps, launched;
+      'capture_group' the same recorded as THE group graph (k = G) - a capture runs nothing: the host step does not move;
+      'replay_group'  the group graph replayed;
+      'capture_rem'   recorded as the remainder graph of the key (k, parity);
+      'replay_rem'    the remainder graph of the key (k, parity) replayed.
+    The corruption side of slot j is baked into a recorded graph (DeviceBatch.neg_head) while the ids of the slot follow the device's
+    own step counter, so a graph may only be replayed at the parity it was recorded at: the group graph (even G only) at odd host
+    steps, a remainder graph under its key.  G = --graph_steps, have_group_graph: the lane holds the group graph, n_slots: the
+    sampler's slots, rem_keys: the keys of the remainder graphs the lane holds (at most eight are recorded, and none before the
+    group graph exists: a run too short for that one does not pay for captures)."""
+    acts, hs, done, rem_keys = [], host_step, 0, set(rem_keys)
+    if G >= 2 and G % 2 == 0 and n >= G and hs % 2 == 1:
+        if not have_group_graph:
+            acts.append(('eager', G, hs % 2))             # eager warm-up (also allocates the workspace)
+            hs, done = hs + G, done + G
+            if n - done >= G:
+                acts.append(('capture_group', G, hs % 2))
+                have_group_graph = True
+        while have_group_graph and n - done >= G:
+            acts.append(('replay_group', G, hs % 2))
+            hs, done = hs + G, done + G
+    while done < n:                                       # remainder (< G steps, or the parity of a full group is off)
+        k = min(n_slots, n - done)
+        key = (k, hs % 2)
+        if key not in rem_keys and have_group_graph and len(rem_keys) < 8:
+            # the log / eval marks repeat: record [1 sampler launch + k steps] once instead of paying
+            # ~6 eager launches per step every time (56 -> 44 us/step at log_interval 1000, eval 500)
+            acts.append(('capture_rem', k, hs % 2))
+            rem_keys.add(key)
+        acts.append(('replay_rem' if key in rem_keys else 'eager', k, hs % 2))
+        hs, done = hs + k, done + k
+    return acts, hs
+
+
 class _Lane(object):
     """one trainer: a StepEngine (sharing the tables), its sampler over its share of the training triples,
     its HIP stream and - device sampler - a hipGraph of [1 sampler launch + G steps].  `--num_proc K` on
@@ -229,41 +266,24 @@ class _Lane(object):
             if not t.device_sampler:
                 self._steps(self.sampler.next_batches(n))
                 return
-            G, smp, done = t.args.graph_steps, self.sampler, 0
-            if G >= 2 and G % 2 == 0 and n >= G and smp.host_step % 2 == 1:
-                if self._graph is None:
-                    self._steps(smp.sample(G))        # eager warm-up (also allocates the workspace)
-                    done += G
-                    if n - done >= G:
-                        self.stream.synchronize()
-                        g = th.cuda.CUDAGraph()
-                        with _lib.graph_capture(g, stream=self.stream if t.n_lanes > 1 else None):
-                            self._steps(smp.sample(G))
-                        self._graph = g
-                        smp.host_step -= G            # the capture itself did not run the steps
-                while self._graph is not None and n - done >= G:
-                    self._graph.replay()
-                    smp.host_step += G
-                    done += G
-            while done < n:                           # remainder (< G steps, or the parity of a full group is off)
-                k = min(smp.n_slots, n - done)
-                key = (k, smp.host_step % 2)          # neg_head of slot j is baked into the graph: same parity only
-                g = self._rem_graphs.get(key)
-                if g is None and self._graph is not None and len(self._rem_graphs) < 8:
-                    # the log / eval marks repeat: record [1 sampler launch + k steps] once instead of paying
-                    # ~6 eager launches per step every time (56 -> 44 us/step at log_interval 1000, eval 500)
+            smp = self.sampler
+            acts, _ = plan_enqueue(n, t.args.graph_steps, smp.host_step, self._graph is not None, smp.n_slots, self._rem_graphs)
+            for kind, k, parity in acts:
+                if kind == 'eager':
+                    self._steps(smp.sample(k))
+                elif kind in ('capture_group', 'capture_rem'):
                     self.stream.synchronize()
                     g = th.cuda.CUDAGraph()
                     with _lib.graph_capture(g, stream=self.stream if t.n_lanes > 1 else None):
                         self._steps(smp.sample(k))
                     smp.host_step -= k                # the capture itself did not run the steps
-                    self._rem_graphs[key] = g
-                if g is not None:
-                    g.replay()
-                    smp.host_step += k
+                    if kind == 'capture_group':
+                        self._graph = g
+                    else:
+                        self._rem_graphs[(k, parity)] = g
                 else:
-                    self._steps(smp.sample(k))
-                done += k
+                    (self._graph if kind == 'replay_group' else self._rem_graphs[(k, parity)]).replay()
+                    smp.host_step += k
 
 
 class _Trainer(object):
@@ -761,7 +781,8 @@ def check_exclude_positive(args):
                        "--async_update_rel); plain --async_update runs the strict step and is fine")
 
 
-def main(argv=None):
+def main(argv=None, before_train=None):
+    """before_train (one GPU): called with the built Trainer in front of its first step - the tests take the initial tables there"""
     args = ArgParser().parse_args(argv)
     check_exclude_positive(args)                 # before anything is loaded or created
     if args.neg_deg_sample_eval:                 # before anything is loaded or created
@@ -797,6 +818,8 @@ def main(argv=None):
         kd.spawn_ranks(_mp_worker, args)
         return None
     trainer = Trainer(args, dataset)
+    if before_train is not None:
+        before_train(trainer)
     print('Total initialize time {:.3f} seconds'.format(time.time() - init_time_start))
     start = time.time()
     trainer.train()
