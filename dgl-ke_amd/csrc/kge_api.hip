@@ -80,7 +80,9 @@ bool use_mfma(int model, int d_e, int N, unsigned flags) {
 }
 
 int check_loss(int genre, int adv, int pairwise) {
-    if (genre < KGE_LOSS_LOGSIGMOID || genre > KGE_LOSS_BCE) return fail(KGE_ERR_ARG, "unknown loss genre %d", genre);
+    if (genre < KGE_LOSS_LOGSIGMOID || genre > KGE_LOSS_SOFTMAX) return fail(KGE_ERR_ARG, "unknown loss genre %d", genre);
+    if (genre == KGE_LOSS_SOFTMAX && adv) return fail(KGE_ERR_ARG, "Softmax loss cannot be adversarial sampled: the softmax is the weighting");
+    if (genre == KGE_LOSS_SOFTMAX && pairwise) return fail(KGE_ERR_ARG, "Softmax loss cannot be applied to pairwise loss function");
     if (pairwise && adv) return fail(KGE_ERR_ARG, "loss cannot be pairwise and adversarial sampled");
     if (pairwise && genre != KGE_LOSS_LOGISTIC && genre != KGE_LOSS_HINGE)
         return fail(KGE_ERR_ARG, "this loss cannot be applied to pairwise loss function");
@@ -106,7 +108,7 @@ void fill_pair(NegArgs &na, int model, int C, int chunk, int N, int d_e, float g
 // the criterion and its operands; everything else (row terms, running sums, score transforms) is the caller's
 void fill_loss(LossArgs &a, const LossParams &lp, int B, int N, const float *pos, const float *neg, const float *w, float *dpos, float *dneg) {
     a = LossArgs{};
-    a.B = B; a.N = N; a.genre = lp.genre; a.adv = lp.adv; a.pairwise = lp.pairwise; a.adv_temp = lp.adv_temp; a.margin = lp.margin;
+    a.B = B; a.N = N; a.genre = lp.genre; a.adv = lp.adv; a.pos_row = lp.pos_row; a.adv_temp = lp.adv_temp; a.margin = lp.margin;
     a.pos = pos; a.neg = neg; a.w = w; a.dpos = dpos; a.dneg = dneg;
 }
 // the fields EdgeFwdArgs and EdgeBwdArgs share; inputs beyond them, outputs and the regulariser are the caller's
@@ -344,12 +346,12 @@ int kge_loss_fwd_bwd(int loss_genre, int adv, float adv_temp, int pairwise, floa
     float *l4 = loss3 ? cv.f(4) : nullptr;
     if (!cv.ok()) return fail(KGE_ERR_WORKSPACE, "workspace too small (%zu < %zu)", ws_bytes, cv.off);
     LossArgs a;
-    fill_loss(a, LossParams{loss_genre, adv, pairwise, adv_temp, margin}, (int)B, N, pos, neg, w, dpos, dneg);
+    fill_loss(a, LossParams{loss_genre, adv, loss_pos_row(loss_genre, pairwise), adv_temp, margin}, (int)B, N, pos, neg, w, dpos, dneg);
     a.row_pos = row_pos; a.row_neg = row_neg;
     KGE_TRY(launch_loss(a, (hipStream_t)stream));
     if (loss3) {
         FinalizeArgs f{};
-        f.B = (int)B; f.UE = 0; f.UR = 0; f.pairwise = pairwise;
+        f.B = (int)B; f.UE = 0; f.UR = 0; f.pos_row = loss_pos_row(loss_genre, pairwise);
         f.row_pos = row_pos; f.row_neg = row_neg; f.loss4 = l4;
         KGE_TRY(launch_finalize(f, (hipStream_t)stream));
         if (hipMemcpyAsync(loss3, l4, 3 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
@@ -544,7 +546,7 @@ int kge_known_neg_mask(const kge_batch *b, const kge_known *known, uint32_t *mas
 // every path decision of one step call, from its inputs alone
 struct StepPlan {
     int N, CN;                 // negative rows per chunk / per batch as the scoring, loss and gradient kernels see them
-    bool nd, reg, pairwise, is_l2, transr, rescal, rescal_rel, sh_dense, pipelined, want4;
+    bool nd, reg, pos_row, is_l2, transr, rescal, rescal_rel, sh_dense, pipelined, want4;
     bool gemm, fused_loss, transe_fast, qfuse, need_cp, dense_neg, l2g, merged_fwd, merged_pair, fold_loss, dense_bwd;
     bool ew_bwd, lc, fuse_gnred, fold_upd; int ga_parts, fold_nrw;
 };
@@ -557,7 +559,7 @@ static StepPlan plan_step(const kge_hparams *hp, const kge_batch *b, const kge_s
     // plan of the batch keeps indexing the sampled ones (b->N)
     p.nd = (fl & KGE_FLAG_NEG_DEG_SAMPLE) != 0;
     const int N = p.N = p.nd ? chunk + b->N : b->N; p.CN = C * N;
-    p.reg = hp->reg_coef > 0.f && hp->reg_norm > 0; p.pairwise = hp->pairwise != 0; p.want4 = out && out->loss4;
+    p.reg = hp->reg_coef > 0.f && hp->reg_norm > 0; p.pos_row = loss_pos_row(hp->loss_genre, hp->pairwise) != 0; p.want4 = out && out->loss4;
     p.is_l2 = model == KGE_TRANSE_L2; p.transr = model == KGE_TRANSR; p.rescal = model == KGE_RESCAL;
     p.rescal_rel = p.rescal && d_e % 4 == 0;         // RESCAL's passes over M per unique relation (16-byte accesses)
     p.sh_dense = sh && (p.transr || p.rescal);       // the two families run on a dense block of the batch's entity rows (Step::setup)
@@ -566,10 +568,10 @@ static StepPlan plan_step(const kge_hparams *hp, const kge_batch *b, const kge_s
     // KGE_FLAG_FUSED_LOSS (matrix-core path, pointwise criteria): no loss kernel - the forward tiles emit the factorised gradient
     // (kge_neg_gemm.hip).  4 launches per step instead of 5, 1.6 MB less traffic, but measured 41.7 vs 41.1 us per step at cfg-T
     // (profiles/r02_fused_loss_experiment.txt), so it is opt-in.  (RESCAL has no edge_fwd: its positive-loss part lives in the loss kernel)
-    p.fused_loss = p.gemm && !p.pairwise && !p.nd && !p.rescal && (fl & KGE_FLAG_FUSED_LOSS) && neg_gemm_fused_loss_supported(chunk, N);
+    p.fused_loss = p.gemm && !p.pos_row && !p.nd && !p.rescal && (fl & KGE_FLAG_FUSED_LOSS) && neg_gemm_fused_loss_supported(chunk, N);
     const bool transe = model == KGE_TRANSE_L1 || p.is_l2;
     // TransE fast path: edge_fwd leaves P rows, the update rebuilds the per-edge gradients from them (no edge_bwd launch)
-    p.transe_fast = transe && !p.pairwise && !p.nd && d_e % 4 == 0 && d_r % 4 == 0 && (d_e > d_r ? d_e : d_r) <= 1024 && !(fl & KGE_FLAG_NO_TRANSE_FAST);
+    p.transe_fast = transe && !p.pos_row && !p.nd && d_e % 4 == 0 && d_r % 4 == 0 && (d_e > d_r ? d_e : d_r) <= 1024 && !(fl & KGE_FLAG_NO_TRANSE_FAST);
     // ... behind the matrix-core backward: its GA epilogue also writes Q = GA +/- P (into the GT buffer, unused on this path)
     // and the update reads one gradient row per list entry (GemmArgs::Q)
     p.qfuse = p.transe_fast && p.gemm;
@@ -583,7 +585,7 @@ static StepPlan plan_step(const kge_hparams *hp, const kge_batch *b, const kge_s
     p.l2g = p.gemm && p.is_l2;                       // GEMM form of the L2 distance needs |a|^2, |b|^2
     // PREP and the forward of a strict step can share ONE launch: not in the async pipeline (its forward shares a launch with
     // the previous update already), only when this call runs both and launches both itself
-    const bool one_fwd = !p.pipelined && !p.pairwise && (phases & (PH_PREP | PH_FWD)) == (PH_PREP | PH_FWD) && !c.build_prep &&
+    const bool one_fwd = !p.pipelined && !p.pos_row && (phases & (PH_PREP | PH_FWD)) == (PH_PREP | PH_FWD) && !c.build_prep &&
                          !c.co_update && !(fl & KGE_FLAG_SPLIT_FWD);
     // edge-forward and the forward GEMM in one launch (kge_neg_gemm.hip, neg_fwd_edge_kernel): the tiles build their pos-side
     // fragments from the table rows themselves and emit raw products, the loss kernel applies the TransE_l2 distance transform.
@@ -736,7 +738,7 @@ int Step::setup(void *ws, size_t ws_bytes) {
     P = (out && out->pos_score) ? out->pos_score : w.P; GN = (out && out->g_neg) ? out->g_neg : w.GN;
     GR = (out && out->g_rel && !p.transe_fast) ? out->g_rel : w.GR;
     acc = out ? out->loss_accum : nullptr;
-    lp = LossParams{hp->loss_genre, hp->adv, hp->pairwise, hp->adv_temp, hp->margin}; rot_div = rot_div_of(hp->emb_init);
+    lp = LossParams{hp->loss_genre, hp->adv, p.pos_row ? 1 : 0, hp->adv_temp, hp->margin}; rot_div = rot_div_of(hp->emb_init);
     src = EdgeSrc{tb->ent, b->h_gid, tb->ent, b->t_gid, tb->rel, b->rel_ids, em, rm};
     if (p.transr) {
         tr.HP = w.HP; tr.TP = w.TP; tr.Q = w.Q; tr.SG = w.SG; tr.DQ = w.DQ; tr.Z = w.Z; tr.GP = w.GP;
@@ -812,7 +814,7 @@ int Step::phase_prep() {
     ef.Bn = (p.dense_neg || p.dense_bwd) ? w.Bn : nullptr;
     if (p.need_cp) { ef.Hc = w.Hc; ef.Tc = w.Tc; ef.Rc = w.Rc; }
     ef.asq = (p.l2g && !p.fold_loss) ? w.asq : nullptr; ef.bsq = (p.l2g && !p.fold_loss) ? w.bsq : nullptr;
-    ef.do_pos_loss = p.pairwise ? 0 : 1; ef.lp = lp; ef.w = b->edge_w; ef.w_mean = b->edge_w_mean;
+    ef.do_pos_loss = p.pos_row ? 0 : 1; ef.lp = lp; ef.w = b->edge_w; ef.w_mean = b->edge_w_mean;
     ef.dpos = w.dP; ef.row_pos = p.want4 ? w.row_pos : nullptr; ef.acc = acc;
     if (p.transr) return prep_transr();
     if (p.rescal) return prep_rescal();
@@ -884,7 +886,7 @@ int Step::phase_fwd() {
     LossArgs la; fill_step_loss(la);
     la.row_pos = p.want4 ? w.row_pos : nullptr;
     if (p.merged_fwd && p.is_l2) { la.l2_raw = 1; la.l2_chunk = b->chunk; la.asq = w.asq; la.bsq = w.bsq; }
-    la.skip_pos = (p.pairwise || p.rescal || p.transr) ? 0 : 1; la.diag_chunk = p.nd ? b->chunk : 0;  // RESCAL / TransR: no edge_fwd -> positive part here
+    la.skip_pos = (p.pos_row || p.rescal || p.transr) ? 0 : 1; la.diag_chunk = p.nd ? b->chunk : 0;  // RESCAL / TransR: no edge_fwd -> positive part here
     KGE_TRY(launch_loss(la, s, c.known ? c.known_mask : nullptr));
     return KGE_OK;
 }
@@ -1071,7 +1073,7 @@ int Step::phase_update() {
     // accumulated by the kernels above without it)
     if (p.want4 && (phases & PH_UPD_ENT)) {
         FinalizeArgs f{};
-        f.B = b->B; f.UE = b->UE; f.UR = b->UR; f.pairwise = hp->pairwise;
+        f.B = b->B; f.UE = b->UE; f.UR = b->UR; f.pos_row = p.pos_row ? 1 : 0;
         f.row_pos = w.row_pos; f.row_neg = w.row_neg; f.reg_ent = w.reg_ent; f.reg_rel = w.reg_rel;
         f.counts_dev = b->counts_dev; f.loss4 = out->loss4;
         KGE_TRY(launch_finalize(f, s));

@@ -336,8 +336,14 @@ struct EdgeSrc {           // where the rows of one positive edge come from
     kge::ShardMap em, rm;                      // entity / relation table sharding (n = 0: local tables)
 };
 
+// ONE predicate for the lowering: the criterion reads the positive score WITH its row of negatives (-pw: crit(p - n_ij);
+// Softmax: p is a term of the row's partition sum).  Such a step has no positive part that edge_fwd could do ahead of the
+// scores (do_pos_loss 0, skip_pos 0), no factorised / in-launch loss, takes the launch sequence with the stand-alone loss
+// kernel, and reports {NaN, NaN, loss, regularisation}.  The kernels tell the two apart by the genre.
+inline int loss_pos_row(int genre, int pairwise) { return (pairwise || genre == KGE_LOSS_SOFTMAX) ? 1 : 0; }
+
 struct LossParams {                 // LossGenerator configuration (loss.py:41-61)
-    int genre, adv, pairwise;
+    int genre, adv, pos_row;        // pos_row: loss_pos_row(genre, pairwise)
     float adv_temp, margin;
 };
 
@@ -443,7 +449,7 @@ __device__ __forceinline__ void gn_reduce_body(const NegArgs &a, int nrw, int64_
 }
 
 struct LossArgs {
-    int B, N, genre, adv, pairwise;
+    int B, N, genre, adv, pos_row;      // pos_row: loss_pos_row(genre, pairwise) - the criterion reads p with its row
     float adv_temp, margin;
     const float *pos, *neg, *w;
     float w_mean;                    // kge_batch.edge_w_mean (0: the rows' wavefronts sum the weights themselves)
@@ -518,7 +524,7 @@ __device__ __forceinline__ int64_t gn_row(const UpdateArgs &a, int slot) {
 }
 
 struct FinalizeArgs {
-    int B, UE, UR, pairwise;
+    int B, UE, UR, pos_row;          // pos_row (loss_pos_row): no positive / negative halves - {NaN, NaN, loss, reg}
     const float *row_pos, *row_neg, *reg_ent, *reg_rel;
     const int32_t *counts_dev;
     float *loss4;

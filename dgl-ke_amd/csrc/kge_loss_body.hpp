@@ -10,7 +10,7 @@
 // LEAN: the common configuration (Logsigmoid, point-wise, positive part done by edge_fwd, no score clamp, no per-step
 // outputs) - everything else is compiled out of the LEAN instances
 __device__ __forceinline__ void loss_args_lean(LossArgs &a) {
-    a.genre = KGE_LOSS_LOGSIGMOID; a.pairwise = 0; a.skip_pos = 1; a.clampv = 0.f; a.neg_copy = nullptr;
+    a.genre = KGE_LOSS_LOGSIGMOID; a.pos_row = 0; a.skip_pos = 1; a.clampv = 0.f; a.neg_copy = nullptr;
     a.row_pos = nullptr; a.row_neg = nullptr; a.diag_chunk = 0;
 }
 
@@ -60,8 +60,65 @@ __device__ __forceinline__ void loss_row_store(float *p, int lane, int N, const 
     }
 }
 
+// Softmax (KGE_LOSS_SOFTMAX, include/kge_hip.h): cross-entropy of the positive p against the negatives of its own row -
+//   m = max(p, max_j n_j), e_p = exp(p - m), e_j = exp(n_j - m), Z = e_p + sum_j e_j, l = m + log Z - p,
+//   dL/dn_j = (w / B) e_j / Z, dL/dp = -(w / B) (sum_j e_j) / Z.
+// One row of loss_row_regs (below: its arguments, the column layout and the style of the passes); a function of its own with
+// its own gradient registers, so that the instances it is compiled out of (LEAN) keep their instruction streams.
+template <int NPER, bool PK>
+__device__ __forceinline__ void loss_row_softmax(const LossArgs &a, int64_t i, const float (&nv)[NPER], float w, float p, int lane,
+                                                 int slot2, unsigned kn, float *dn, int jd) {
+    using namespace kge;
+    const int N = a.N;
+    const float invB = a.inv_B;
+    float g[NPER];
+    // m = max(p, max_j n_j): one wave_max; the masked diagonal column takes part with its score 0, a known pair with
+    // KGE_KNOWN_SCORE (its exponential is 0.0f).  A DEAD slot holds score 0 too (the callers put it there): where every live
+    // score lies below about -88, its __expf(0 - m) is +inf.  That is harmless only because dead slots leave the maximum and the
+    // sum through SELECTS and the row through the store's predicate - never through a multiply by 0 (inf * 0 = NaN).
+    constexpr int GS = PK ? 4 : 1;
+    float mx = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < NPER; q += GS) {
+        float m = nv[q];
+#pragma unroll
+        for (int u = q + 1; u < q + GS; ++u) m = fmaxf(m, nv[u]);
+        mx = fmaxf(mx, loss_live<PK>(lane, q, N) ? m : -INFINITY);
+    }
+    mx = fmaxf(wave_max(mx), p);
+    float z = 0.f;
+#pragma unroll
+    for (int q = 0; q < NPER; q += GS) {
+        float zq = 0.f;
+#pragma unroll
+        for (int u = q; u < q + GS; ++u) { g[u] = __expf(nv[u] - mx); zq += g[u]; }
+        z += loss_live<PK>(lane, q, N) ? zq : 0.f;
+    }
+    z = wave_sum(z);                                // sum_j e_j: one wave_sum
+    const float ep = __expf(p - mx), Z = ep + z;    // Z >= 1: the largest term is exp(0)
+    const float gs = w * invB * __builtin_amdgcn_rcpf(Z);      // weight, 1/B and 1/Z in ONE multiplier; one v_rcp_f32 per row
+#pragma unroll
+    for (int u = 0; u < NPER; ++u) {
+        g[u] *= gs;
+        if (a.l2_scale) { const float d = a.gamma - nv[u]; g[u] = d > 1e-15f ? g[u] * __builtin_amdgcn_rcpf(d) : 0.f; }
+        if (a.clampv > 0.f && fabsf(nv[u]) >= a.clampv) g[u] = 0.f;
+        if (loss_col<PK>(lane, u) == jd || ((kn >> u) & 1u)) g[u] = 0.f;
+    }
+    loss_row_store<NPER, PK>(dn, lane, N, g);
+    if (lane == 0) {
+        // dL/dp from the UNMASKED sum, as -(sum_j e_j) / Z (not 1 - e_p / Z: no cancellation when the positive dominates)
+        a.dpos[i] = (a.clampv > 0.f && fabsf(p) >= a.clampv) ? 0.f : -gs * z;
+        // log Z once per row.  Where the positive is the row's maximum, e_p = 1 and Z = 1 + z: log1p(z) by its series
+        // below 2^-12 (the rounding of 1 + z would cost the small loss of a dominating positive its digits)
+        const float lz = (ep == 1.f && z < 0x1p-12f) ? z * (1.f - 0.5f * z) : __builtin_amdgcn_logf(Z) * 0.6931471805599453f;
+        const float l = ((mx - p) + lz) * w * invB;
+        if (a.row_pos) { a.row_pos[i] = 0.f; a.row_neg[i] = l; }
+        if (a.acc) acc_add(&a.acc[2 * KGE_ACC_SLOTS + slot2], l, a.B <= KGE_ACC_SLOTS);
+    }
+}
+
 // nv[u] = score of column loss_col<PK>(lane, u) of row i (0 beyond N and in the masked diagonal column); w = edge weight,
-// p = positive score (read only by the pairwise / !skip_pos variants).  Writes dL/dn over the row (a.dneg, TransE_l2:
+// p = positive score (read only by the pairwise, Softmax and !skip_pos variants).  Writes dL/dn over the row (a.dneg, TransE_l2:
 // pre-divided by the distance), the optional score copy, the row's loss terms and the running sums.  slot2: where this row's
 // share of the total goes in the running sums (the stand-alone kernel: the row's own slot; the in-launch variant: a slot the
 // edge half of the same launch does not touch).  kn: bit u set = slot u is a KNOWN pair (kge_known_neg_mask; the caller has put
@@ -69,8 +126,11 @@ __device__ __forceinline__ void loss_row_store(float *p, int lane, int N, const 
 // stand-alone kernel with a mask): folded away.
 // The arithmetic runs unpredicated on every slot, in passes over the slots (independent chains next to each other: a
 // transcendental's result is not the next instruction's operand); dead slots are taken out by selects where they would
-// enter a sum and by the stores' predicate.  Per-row factors (weight, 1/B, 1/Z or 1/N) are folded into ONE multiplier.
-template <int NPER, bool PK>
+// enter a sum and by the stores' predicate (loss_row_softmax relies on the 0 in the dead slots and on the selects, see there).
+// Per-row factors (weight, 1/B, 1/Z or 1/N) are folded into ONE multiplier.
+// SM: the Softmax branch is compiled in - false in the forward tiles' in-launch loss rows, whose launcher refuses the genre: those
+// kernels stay what they were.
+template <int NPER, bool PK, bool SM = true>
 __device__ __forceinline__ void loss_row_regs(const LossArgs &a, int64_t i, float (&nv)[NPER], float w, float p, int lane,
                                               int slot2, unsigned kn = 0u) {
     using namespace kge;
@@ -81,7 +141,8 @@ __device__ __forceinline__ void loss_row_regs(const LossArgs &a, int64_t i, floa
     const int slot = (int)(i & (KGE_ACC_SLOTS - 1));
     float g[NPER];
     if (a.neg_copy) loss_row_store<NPER, PK>(a.neg_copy + i * (int64_t)N, lane, N, nv);
-    if (a.pairwise) {   // loss.py:76-80
+    if (a.pos_row) {   // the criterion reads p with its row: Softmax, or loss.py:76-80
+        if (SM && a.genre == KGE_LOSS_SOFTMAX) { loss_row_softmax<NPER, PK>(a, i, nv, w, p, lane, slot2, kn, dn, jd); return; }
         const float sc = w / ((float)a.B * (float)N);
         float lsum = 0.f, dsum = 0.f;
 #pragma unroll

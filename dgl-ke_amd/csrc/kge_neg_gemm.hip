@@ -426,7 +426,7 @@ __device__ __forceinline__ void lf_loss_rows(const GemmArgs &a, const LossArgs &
             for (int u = 0; u < NPER; ++u) if (!loss_live<PK>(lane, u, N)) nv[r][u] = 0.f;
             // the edge half of this launch adds the row's positive share to slot gi of the running total: this half takes
             // the slot B further on (one add per slot and launch keeps the sums order-independent while 2 B <= KGE_ACC_SLOTS)
-            loss_row_regs<NPER, PK>(la, gi, nv[r], wr[r], 0.f, lane, (int)((gi + la.B) & (KGE_ACC_SLOTS - 1)));
+            loss_row_regs<NPER, PK, false>(la, gi, nv[r], wr[r], 0.f, lane, (int)((gi + la.B) & (KGE_ACC_SLOTS - 1)));
         }
     }
 }
@@ -743,7 +743,7 @@ int launch_neg_fwd_gemm_with_edge_loss(const GemmArgs &a, const EdgeFwdArgs &e, 
     loss_fill_host(la);
     if (a.C == 0 || a.PM || !a.xbase || !a.rbase || !a.xidx || !a.ridx || !tickets || a.lds_off) return KGE_ERR_ARG;
     if (!neg_fwd_loss_fold_supported(a.model, a.C, a.chunk, a.N, a.D, e.d_r) || e.model != a.model || e.d_e != a.D) return KGE_ERR_ARG;
-    if (e.src.em.n || e.src.rm.n || e.nd_own || la.pairwise || !la.skip_pos || la.l2_raw || la.diag_chunk > 0 || la.neg != a.S ||
+    if (e.src.em.n || e.src.rm.n || e.nd_own || la.pos_row || !la.skip_pos || la.l2_raw || la.diag_chunk > 0 || la.neg != a.S ||
         la.dneg != a.S || la.N != a.N || la.B != a.C * a.chunk) return KGE_ERR_ARG;
     const bool negjob = e.bsq || e.Bn;
     const int64_t waves = (int64_t)e.B + (negjob ? e.n_neg : 0);
@@ -1343,7 +1343,7 @@ int launch_neg_bwd_gemm(const GemmArgs &a, hipStream_t s, const SmpTail *tail) {
     const int nbT = st.phase ? 8 : 0;            // (ST_P2_WGS <= 8 tail workgroups in front of the tiles, see the kernel)
     if (!a.W) return KGE_ERR_ARG;
     const bool fact = a.PM != nullptr;                           // W holds u_ij: factorised fused loss
-    if (fact && (a.lp.pairwise || !a.PS || !a.PL)) return KGE_ERR_ARG;
+    if (fact && (a.lp.pos_row || !a.PS || !a.PL)) return KGE_ERR_ARG;
     const int maxK = a.chunk > a.N ? a.chunk : a.N;
     if (maxK > GB_MAXK) return KGE_ERR_ARG;
     const int ti = (a.chunk + 15) / 16, tj = (a.N + 15) / 16, td = (a.D + 63) / 64;

@@ -506,7 +506,33 @@ __global__ __launch_bounds__(KGE_BLOCK) void loss_kernel(LossArgs a, const uint3
         for (int j = lane; j < N; j += 64) nw[j] = a.gamma - sqrtf(fmaxf(fmaf(-2.f, n[j], as + bq[j]), 1e-30f));
         // (a lane re-reads only what it wrote itself: columns j = lane mod 64)
     }
-    if (a.pairwise) {   // loss.py:76-80
+    if (a.pos_row && a.genre == KGE_LOSS_SOFTMAX) {   // softmax cross-entropy of p against its row: loss_row_regs' arithmetic, streamed
+        float mx = -INFINITY;
+        for (int j = lane; j < N; j += 64) mx = fmaxf(mx, sc_of(j));
+        mx = fmaxf(wave_max(mx), p);
+        float z = 0.f;
+        for (int j = lane; j < N; j += 64) z += __expf(sc_of(j) - mx);
+        z = wave_sum(z);
+        const float ep = __expf(p - mx), Z = ep + z;
+        const float gs = w * invB * __builtin_amdgcn_rcpf(Z);
+        for (int j = lane; j < N; j += 64) {
+            const float nv = sc_of(j);
+            float g = __expf(nv - mx) * gs;
+            if (cp) cp[j] = nv;
+            if (a.l2_scale) { const float d = a.gamma - nv; g = d > 1e-15f ? g * __builtin_amdgcn_rcpf(d) : 0.f; }
+            if (a.clampv > 0.f && fabsf(nv) >= a.clampv) g = 0.f;
+            dn[j] = (j == jd || kn(j)) ? 0.f : g;
+        }
+        if (lane == 0) {
+            a.dpos[i] = (a.clampv > 0.f && fabsf(p) >= a.clampv) ? 0.f : -gs * z;
+            const float lz = (ep == 1.f && z < 0x1p-12f) ? z * (1.f - 0.5f * z) : __builtin_amdgcn_logf(Z) * 0.6931471805599453f;
+            const float l = ((mx - p) + lz) * w * invB;
+            if (a.row_pos) { a.row_pos[i] = 0.f; a.row_neg[i] = l; }
+            if (a.acc) acc_add(&a.acc[2 * KGE_ACC_SLOTS + (int)(i & (KGE_ACC_SLOTS - 1))], l, a.B <= KGE_ACC_SLOTS);
+        }
+        return;
+    }
+    if (a.pos_row) {   // loss.py:76-80
         const float sc = w / ((float)a.B * (float)N);
         float lsum = 0.f, dsum = 0.f;
         for (int j = lane; j < N; j += 64) {
@@ -648,7 +674,7 @@ int launch_loss(const LossArgs &a_, hipStream_t s, const uint32_t *known) {
     LossArgs a = a_;
     loss_fill_host(a);
     const dim3 g(blocks_for_waves(a.B)), b(KGE_BLOCK);
-    const bool lean = a.genre == KGE_LOSS_LOGSIGMOID && !a.pairwise && a.skip_pos && a.clampv == 0.f && !a.neg_copy &&
+    const bool lean = a.genre == KGE_LOSS_LOGSIGMOID && !a.pos_row && a.skip_pos && a.clampv == 0.f && !a.neg_copy &&
                       !a.row_pos && !a.row_neg && a.diag_chunk <= 0 && !known;
     if (a.l2_raw && (!a.asq || !a.bsq || a.l2_chunk <= 0 || !a.l2_scale)) return KGE_ERR_ARG;
     const bool pk = a.pk != 0;
@@ -688,7 +714,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void finalize_kernel(FinalizeArgs a) {
     const float rr = block_sum_det(a.reg_rel, a.counts_dev ? a.counts_dev[1] : a.UR, sh);
     if (threadIdx.x == 0) {
         float o[4];
-        if (a.pairwise) { o[0] = NAN; o[1] = NAN; o[2] = ln; }
+        if (a.pos_row) { o[0] = NAN; o[1] = NAN; o[2] = ln; }
         else { o[0] = lp; o[1] = ln; o[2] = 0.5f * (lp + ln); }
         o[3] = re + rr;
         if (a.loss4) for (int k = 0; k < 4; ++k) a.loss4[k] = o[k];

@@ -17,7 +17,7 @@ from .score_fun import (ComplExScore, DistMultScore, RESCALScore, RotatEScore, S
                         TransRScore)
 from .tensor_models import (ExternalEmbedding, cuda, get_dev, get_device, get_scalar, norm,
                             reshape)
-from ._lib import KgeError
+from ._lib import LOSS_IDS, KgeError
 
 EMB_INIT_EPS = 2.0
 
@@ -226,7 +226,7 @@ class KEModel(object):
         if not sync_log:
             return None
         v = self.engine.read_loss()
-        if self.engine.hp.pairwise:
+        if self.engine.hp.pairwise or self.engine.hp.loss_genre == LOSS_IDS['Softmax']:
             log = {'loss': v[2]}
         else:
             log = {'pos_loss': v[0], 'neg_loss': v[1], 'loss': v[2]}

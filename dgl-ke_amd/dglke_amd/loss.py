@@ -10,8 +10,12 @@ from . import ops
 class LossGenerator(object):
     def __init__(self, args, loss_genre='Logsigmoid', neg_adversarial_sampling=False,
                  adversarial_temperature=1.0, pairwise=False):
-        if loss_genre not in ('Hinge', 'Logistic', 'Logsigmoid', 'BCE'):
+        if loss_genre not in ('Hinge', 'Logistic', 'Logsigmoid', 'BCE', 'Softmax'):
             raise ValueError('loss genre %s is not support' % loss_genre)
+        # Softmax (not in the reference): cross-entropy of the positive against the negatives of its own row,
+        # l_i = log(exp(p_i) + sum_j exp(n_ij)) - p_i, loss = mean_i w_i l_i (include/kge_hip.h, enum kge_loss)
+        if loss_genre == 'Softmax' and neg_adversarial_sampling:
+            raise ValueError('Softmax loss cannot be adversarial sampled')
         if pairwise and neg_adversarial_sampling:
             raise ValueError('loss cannot be pairwise and adversarial sampled')
         if pairwise and loss_genre not in ['Logistic', 'Hinge']:
@@ -34,6 +38,6 @@ class LossGenerator(object):
                                        self.neg_adversarial_sampling,
                                        self.adversarial_temperature, self.pairwise, self.margin)
         vals = loss3.tolist()
-        if self.pairwise:
+        if self.pairwise or self.loss_genre == 'Softmax':      # no positive / negative halves
             return loss, {'loss': vals[2]}
         return loss, {'pos_loss': vals[0], 'neg_loss': vals[1], 'loss': vals[2]}

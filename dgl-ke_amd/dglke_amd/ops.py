@@ -195,7 +195,8 @@ class _Loss(torch.autograd.Function):
 
 def loss_fwd_bwd(pos, neg, w, genre, adv, adv_temp, pairwise, margin):
     """LossGenerator.get_total_loss (loss.py:69-98): returns (loss scalar with grad_fn,
-    loss3 = [pos_loss, neg_loss, loss])."""
+    loss3 = [pos_loss, neg_loss, loss]; pairwise and genre 'Softmax' - the cross-entropy of the positive against its row,
+    not in the reference - [nan, nan, loss])."""
     return _Loss.apply(pos, neg, w, _lib.LOSS_IDS[genre], bool(adv), float(adv_temp),
                        bool(pairwise), float(margin))
 

@@ -77,7 +77,7 @@ class ArgParser(argparse.ArgumentParser):
         a('-rc', '--regularization_coef', type=float, default=0.000002)
         a('-rn', '--regularization_norm', type=int, default=3)
         a('-pw', '--pairwise', action='store_true')
-        a('--loss_genre', default='Logsigmoid', choices=['Hinge', 'Logistic', 'Logsigmoid', 'BCE'])
+        a('--loss_genre', default='Logsigmoid', choices=['Hinge', 'Logistic', 'Logsigmoid', 'BCE', 'Softmax'])
         a('-m', '--margin', type=float, default=1.0)
         a('--gpu', type=int, default=[-1], nargs='+')
         a('--mix_cpu_gpu', action='store_true')
@@ -357,7 +357,7 @@ class _Trainer(object):
 
     def train(self):
         args = self.args
-        keys = ['loss'] if args.pairwise else ['pos_loss', 'neg_loss', 'loss']
+        keys = ['loss'] if args.pairwise or args.loss_genre == 'Softmax' else ['pos_loss', 'neg_loss', 'loss']
         if args.regularization_coef > 0 and args.regularization_norm > 0:
             keys.append('regularization')
         idx = {'pos_loss': 0, 'neg_loss': 1, 'loss': 2, 'regularization': 3}
@@ -781,9 +781,20 @@ def check_exclude_positive(args):
                        "--async_update_rel); plain --async_update runs the strict step and is fine")
 
 
+def check_loss_flags(args):
+    """--loss_genre Softmax (cross-entropy of the positive against its row): the softmax is the weighting and the row is the pairing"""
+    if args.loss_genre != 'Softmax':
+        return
+    if args.neg_adversarial_sampling:
+        raise KgeError("--loss_genre Softmax cannot be combined with -adv (the softmax is the weighting)")
+    if args.pairwise:
+        raise KgeError("--loss_genre Softmax cannot be combined with -pw")
+
+
 def main(argv=None, before_train=None):
     """before_train (one GPU): called with the built Trainer in front of its first step - the tests take the initial tables there"""
     args = ArgParser().parse_args(argv)
+    check_loss_flags(args)                       # before anything is loaded or created
     check_exclude_positive(args)                 # before anything is loaded or created
     if args.neg_deg_sample_eval:                 # before anything is loaded or created
         if len(args.gpu) > 1:

@@ -51,7 +51,19 @@ enum kge_loss {
     KGE_LOSS_LOGSIGMOID = 0,
     KGE_LOSS_LOGISTIC   = 1,
     KGE_LOSS_HINGE      = 2,
-    KGE_LOSS_BCE        = 3
+    KGE_LOSS_BCE        = 3,
+    /* softmax cross-entropy of the positive against the negatives of its own row (not in the reference; the "1 vs. sampled"
+     * loss, InfoNCE without a temperature).  Row i with positive score p_i, row scores n_ij (j < N, as the loss kernel sees
+     * them) and weight w_i = edge importance of edge i (per edge) or 1:
+     *   m_i = max(p_i, max_j n_ij);  e_p = exp(p_i - m_i), e_j = exp(n_ij - m_i), Z_i = e_p + sum_j e_j
+     *   l_i = m_i + log Z_i - p_i;   loss = (1/B) sum_i w_i l_i   (no factor 1/2: there are no halves to average)
+     *   dL/dn_ij = (w_i / B) e_j / Z_i;   dL/dp_i = -(w_i / B) (sum_j e_j) / Z_i
+     * The masked diagonal column of KGE_FLAG_NEG_DEG_SAMPLE stays in Z_i with its score 0 and gets gradient 0; a known pair
+     * (kge_step_fused_known) contributes exp(KGE_KNOWN_SCORE - m) = 0 and gets gradient 0; dL/dp_i is formed from the unmasked
+     * sum.  Refused with adv (the softmax is the weighting) and with pairwise; margin and adv_temp are ignored.  Reported like
+     * a pairwise loss: {nan, nan, loss, regularization}.  KGE_FLAG_FUSED_LOSS / KGE_FLAG_LOSS_IN_FWD fall back silently, as
+     * for pairwise: the step takes the pairwise launch sequence (edge rows, scores, stand-alone loss kernel, ...). */
+    KGE_LOSS_SOFTMAX    = 4
 };
 
 enum kge_status {
@@ -153,7 +165,9 @@ int kge_score_neg_bwd(int model, int neg_head, const float *pos_side, const floa
 
 /* ---- A6: LossGenerator.get_total_loss (models/pytorch/loss.py:69-98) + its gradient ----
  * pos [B], neg [B,N], w = edge importance [B] or NULL.  loss3 = {pos_loss, neg_loss, loss}
- * (pairwise: {nan, nan, loss}); dpos [B], dneg [B,N] = d loss / d score.
+ * (pairwise and KGE_LOSS_SOFTMAX: {nan, nan, loss}); dpos [B], dneg [B,N] = d loss / d score.
+ * KGE_LOSS_SOFTMAX (definition at enum kge_loss): l_i = log(exp(p_i) + sum_j exp(n_ij)) - p_i, loss = (1/B) sum_i w_i l_i with
+ * the per-edge weight; KGE_ERR_ARG with adv or pairwise; margin and adv_temp are ignored.
  * ws: scratch of 2 * a(4 * B) bytes, + 256 when loss3 is asked, a(x) = x rounded up to a multiple of 256 (two [B] float rows and
  * the staged loss terms, each 256-byte aligned); KGE_ERR_WORKSPACE before any launch when it is smaller. */
 int kge_loss_fwd_bwd(int loss_genre, int adv, float adv_temp, int pairwise, float margin,
@@ -236,7 +250,8 @@ typedef struct kge_batch {
 typedef struct kge_hparams {
     int32_t model;       /* enum kge_model                                                   */
     int32_t d_e, d_r;    /* entity / relation row widths in floats                           */
-    int32_t loss_genre;  /* enum kge_loss                                                    */
+    int32_t loss_genre;  /* enum kge_loss; KGE_LOSS_SOFTMAX: softmax cross-entropy of the    */
+                         /* positive against its row, adv and pairwise must be 0             */
     int32_t adv;         /* args.neg_adversarial_sampling                                    */
     int32_t pairwise;
     int32_t reg_norm;    /* args.regularization_norm                                         */
