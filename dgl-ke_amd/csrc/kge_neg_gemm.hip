@@ -263,7 +263,7 @@ __global__ __launch_bounds__(KGE_BLOCK) void neg_fwd_update_kernel(GemmArgs a, i
         neg_fwd_gemm_body<L2, false>(a, ti, tj, (int)blockIdx.x, nbG);
     } else {
         KGE_TL(4);
-        update_reg_body<NIT, false, LEAN>(u, nb_ent, (int)blockIdx.x - nbG, (int)gridDim.x - nbG);
+        update_reg_body<NIT, false, LEAN>(u, update_head(u, nb_ent, (int)blockIdx.x - nbG, (int)gridDim.x - nbG));
     }
 }
 

@@ -920,15 +920,19 @@ __global__ __launch_bounds__(KGE_BLOCK) void update_kernel(UpdateArgs a, int nb_
 
 // single-pass register-resident variant: body in kge_update_body.hpp
 // Leading plain parameters (kernel-argument preload): the block-id split, the plan records and the device-side
-// counts - a wavefront's record request leaves without a scalar round for its arguments in front; the struct arrives under it.
+// counts - the record address is formed from preloaded registers alone.  As emitted (tools/chain_heads.py, profiles/
+// r10_update_heads.txt): at kernel entry ten s_loads of UpdateArgs fields, the record (s_load_dwordx8) and the four counts
+// (s_load_dwordx4) leave back to back with no wait in front, one s_waitcnt lgkmcnt(0) follows, then the tail test, the entity /
+// relation branch, the exit tests and the row requests.  The sampler-tail workgroups run the same head and ignore its result.
 template <int NIT, bool SHARDED, int LEAN>
 __global__ __launch_bounds__(KGE_BLOCK) void update_kernel_reg(const int32_t *ue_rec, const int32_t *ur_rec, const int32_t *counts_dev,
                                                                int UE, int UR, int nb_ent, int nbM, UpdateArgs a_in, SmpTail st) {
-    if ((int)blockIdx.x >= nbM) { sampler_tail_p3(st, (int)blockIdx.x - nbM); return; }   // (round 5) phase 3 of the sampler tail
-    KGE_TL(((int)blockIdx.x < nbM - nb_ent) ? 7 : 4);      // timeline: relation workgroups come first (id 7)
     UpdateArgs a = a_in;
     a.ue_rec = ue_rec; a.ur_rec = ur_rec; a.counts_dev = counts_dev; a.UE = UE; a.UR = UR;
-    update_reg_body<NIT, SHARDED, LEAN>(a, nb_ent, (int)blockIdx.x, nbM);
+    const UpdateHead hd = update_head(a, nb_ent, (int)blockIdx.x, nbM);       // (in front of the tail test: see update_head)
+    if ((int)blockIdx.x >= nbM) { sampler_tail_p3(st, (int)blockIdx.x - nbM); return; }   // (round 5) phase 3 of the sampler tail
+    KGE_TL(((int)blockIdx.x < nbM - nb_ent) ? 7 : 4);      // timeline: relation workgroups come first (id 7)
+    update_reg_body<NIT, SHARDED, LEAN>(a, hd);
 }
 
 int launch_update(const UpdateArgs &a, hipStream_t s, const SmpTail *tail) {

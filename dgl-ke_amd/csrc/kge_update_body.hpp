@@ -3,10 +3,16 @@
 // horizontally fused "backward GEMM of step s + entity update of step s-1" launch of the --async_update pipeline
 // (kge_neg_gemm.hip).
 #pragma once
+#include <type_traits>
 #include "kge_common.hpp"
 
 #define KGE_ST_ROW kge::st_wt      // updated table rows: read next by another kernel on any XCD - write-through store
 #define LANE() (threadIdx.x & 63)
+// four wave-uniform words an EARLIER launch wrote (a plan record half, the device-side counts): read through the constant
+// address space they are scalar loads whatever the compiler can prove about this kernel's own stores
+#define KGE_UNIFORM_AS __attribute__((address_space(4)))
+typedef int UniformI4 __attribute__((ext_vector_type(4)));
+template <class T> using GlobalPtr = T __attribute__((address_space(1))) *;
 // running-sum slot update: a fire-and-forget hardware float atomic (global_atomic_add_f32, no return value).
 // A plain read-modify-write costs a dependent global load - one more ~1.5 us round trip at the end of every
 // wavefront's chain (update kernel 15.7 -> see profiles/r01_microbench_mi355x.txt).  The result is still
@@ -40,21 +46,18 @@ __device__ __forceinline__ kge::Pack<4> ld_parts(const float *p, int parts, int6
 // one relation row per wavefront (second half of update_reg_body).  COOP: the instance for batches with a long relation list.
 // (Sums of squares are written as explicit fmaf: left to the compiler, the two instances contracted `ss += g * g` differently and
 //  a row without any shared list came out 1 ulp apart - device-built batches pick the instance per batch, host plans always COOP.)
+// `u`, `r0`, `r1`, `cnt_r`: this wavefront's relation entry, its plan record (of entry UR - 1 when u is beyond the bound) and the
+// batch's relation count, all requested by update_reg_body's head and already in scalar registers.
 template <int NIT, bool SHARDED, int LEAN, bool COOP, bool FOLD = false>
-__device__ __forceinline__ void update_rel_row(const UpdateArgs &a, int bx, int nb_ent, int lane, bool reg, bool qm) {
+__device__ __forceinline__ void update_rel_row(const UpdateArgs &a, int64_t u, UniformI4 r0, UniformI4 r1, int cnt_r, int lane, bool reg, bool qm) {
     using namespace kge;
     constexpr int LB2 = NIT <= 2 ? 2 : 1;
     constexpr int LBR = NIT <= 2 ? 6 : 2;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int64_t u = ((int64_t)bx - nb_ent) * KGE_WAVES_PER_BLOCK + wv;
     // COOP (long lists shared by the workgroup, see below): no early exit - the four wavefronts meet at barriers, a wavefront
     // without a row takes part with an empty record.  Otherwise wavefronts without a row leave at once.
     if (!COOP && u >= a.UR) return;
     const int d = a.d_r;
-    const int64_t uc = u < a.UR ? u : (int64_t)a.UR - 1;                   // a.UR >= 1: this workgroup exists
-    int4 r0 = reinterpret_cast<const int4 *>(a.ur_rec)[2 * uc];           // count and record together (see the entity part)
-    const int4 r1 = reinterpret_cast<const int4 *>(a.ur_rec)[2 * uc + 1];
-    const int cnt_r = a.counts_dev ? a.counts_dev[1] : a.UR;
     const bool valid = u < a.UR && u < cnt_r;
     // gradient-emitting step on a device-built plan: message rows beyond the batch's relation count are pads (id -1)
     if (!valid && a.rid && u < a.UR && lane == 0) { a.rid[u * (int64_t)a.ld_r] = -1; a.rid[u * (int64_t)a.ld_r + 1] = -1; }
@@ -316,6 +319,69 @@ __device__ __forceinline__ void update_rel_row(const UpdateArgs &a, int bx, int 
     } else if (a.reg_rel && lane == 0) a.reg_rel[u] = 0.f;
 }
 
+// ---- the head of every wavefront's chain, entity or relation: ONE scalar round.  The plan record (32 bytes), the four
+// device-side counts {UE, UR, corrupt-head flag, longest relation list} (16 bytes, one load; the update reads words 0, 1 and 3)
+// and every UpdateArgs field either part needs to form its row addresses are requested here, in front of the entity / relation
+// branch and of both exit tests, and arrive under one wait.  Records and counts were written by an earlier launch and are
+// wave-uniform (the wavefront number goes through readfirstlane): read through the constant address space they are scalar
+// loads, and the id, the list bounds and the first entries land in scalar registers - the row addresses are scalar multiplies.
+// Branch-free: the entry is clamped to the bound the record array was sized for (the record of an entry beyond the COUNT is
+// allocated but stale - it is loaded, never used), and a host-built plan (counts_dev null) reads its own record in place of
+// the counts, never the null pointer.
+// Callable for ANY workgroup of the launch, also one with no update work (bid >= nblk, update_kernel_reg's sampler-tail
+// workgroups): such a workgroup reads the last record of a trace that has one.  The stand-alone kernel calls it at kernel
+// entry, in front of its sampler-tail test - behind that test the compiler has to assume the tail's scalar loads still in
+// flight and puts a wait between the first argument loads of this round (profiles/r10_update_heads.txt).
+// PRECONDITIONS (the launchers keep them; nothing here checks them):
+//  1. UE + UR >= 1 and nblk = ceil(UE / 4) + ceil(UR / 4), nb_ent = ceil(UE / 4).  launch_update and
+//     launch_neg_fwd_gemm_with_update return before the launch when both traces are empty.  With both bounds 0 the clamp below
+//     would wrap and the record request leave from a wild address.
+//  2. only a workgroup with bid < nblk may hand the result to update_reg_body.  For bid >= nblk, and for bx >= nb_ent when the
+//     relation trace is empty, the head names an entry of a trace that has one only so that its loads stay in bounds: the body
+//     would take it for that trace's workgroup and update a row a second time.
+//  3. counts_dev, when not null, points at FOUR readable int32 words (16 bytes are read whatever the update uses).
+struct UpdateHead {
+    UniformI4 r0, r1, cn;          // the record's two halves, the four counts (the record's first half again on a host-built plan)
+    int64_t u;                     // entry of this wavefront in its trace (beyond the bound: no row)
+    bool is_ent, dev_counts;
+};
+__device__ __forceinline__ UpdateHead update_head(UpdateArgs &a, int nb_ent, int bid, int nblk) {
+    // the (fewer) relation workgroups are dispatched FIRST: measured 14.9 vs 16.5 us - a relation wavefront has
+    // the same dependent-load chain as an entity wavefront and must not start after all entity workgroups
+    const int nb_rel = nblk - nb_ent;
+    const int bx = bid < nb_rel ? bid + nb_ent : bid - nb_rel;
+    UpdateHead hd;
+    hd.is_ent = bx < nb_ent || a.UR <= 0;
+    const uint32_t u32 = (uint32_t)(bx < nb_ent ? bx : bx - nb_ent) * KGE_WAVES_PER_BLOCK +
+                         (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int bound = hd.is_ent ? a.UE : a.UR;        // the bound the grid and the record array were sized for; >= 1 (the launch has work)
+    const uint32_t uc = u32 < (uint32_t)bound ? u32 : (uint32_t)bound - 1;
+    const UniformI4 KGE_UNIFORM_AS *rp = (const UniformI4 KGE_UNIFORM_AS *)(hd.is_ent ? a.ue_rec : a.ur_rec) + 2 * (int64_t)uc;
+    hd.dev_counts = a.counts_dev != nullptr;
+    const UniformI4 KGE_UNIFORM_AS *cp = hd.dev_counts ? (const UniformI4 KGE_UNIFORM_AS *)a.counts_dev : rp;
+    hd.r0 = rp[0]; hd.r1 = rp[1]; hd.cn = cp[0];
+    hd.u = (int64_t)u32;
+    // (empty asm statements that take and return them all: the requests stay above the branches and share the wait in front of
+    //  the first one; every later use, a register copy included, reads what the asm returned and so stands below the wait.  The
+    //  scheduling barrier keeps the requests together above it.)
+    __builtin_amdgcn_sched_barrier(0);
+    // (pointers pass through the asm as GLOBAL pointers: what an asm returns has no known origin, and a generic pointer of unknown
+    //  origin makes every row access a flat one)
+#define KGE_HEAD_G(f) GlobalPtr<std::remove_pointer_t<decltype(a.f)>> g_##f = (GlobalPtr<std::remove_pointer_t<decltype(a.f)>>)a.f
+#define KGE_HEAD_B(f) a.f = (decltype(a.f))g_##f
+    KGE_HEAD_G(ent); KGE_HEAD_G(ent_state); KGE_HEAD_G(rel); KGE_HEAD_G(rel_state); KGE_HEAD_G(P); KGE_HEAD_G(Q); KGE_HEAD_G(GA); KGE_HEAD_G(GN); KGE_HEAD_G(GR); KGE_HEAD_G(ue_pos_adj);
+    KGE_HEAD_G(ue_neg_slot); KGE_HEAD_G(ur_edge); KGE_HEAD_G(Hs); KGE_HEAD_G(Ts); KGE_HEAD_G(Rs); KGE_HEAD_G(Ns); KGE_HEAD_G(reg_ent); KGE_HEAD_G(reg_rel); KGE_HEAD_G(acc);
+    asm volatile("" : "+s"(hd.r0), "+s"(hd.r1), "+s"(hd.cn), "+s"(g_ent), "+s"(g_ent_state), "+s"(g_rel), "+s"(g_rel_state), "+s"(g_P),
+                 "+s"(g_Q), "+s"(g_GA), "+s"(g_GN), "+s"(g_GR), "+s"(g_ue_pos_adj), "+s"(g_ue_neg_slot), "+s"(g_ur_edge));
+    asm volatile("" : "+s"(a.model_d_e), "+s"(a.d_r), "+s"(a.reg_coef), "+s"(a.lr), "+s"(a.eps), "+s"(a.neg_head), "+s"(g_Hs), "+s"(g_Ts),
+                 "+s"(g_Rs), "+s"(g_Ns), "+s"(g_reg_ent), "+s"(g_reg_rel), "+s"(g_acc));
+    KGE_HEAD_B(ent); KGE_HEAD_B(ent_state); KGE_HEAD_B(rel); KGE_HEAD_B(rel_state); KGE_HEAD_B(P); KGE_HEAD_B(Q); KGE_HEAD_B(GA); KGE_HEAD_B(GN); KGE_HEAD_B(GR); KGE_HEAD_B(ue_pos_adj);
+    KGE_HEAD_B(ue_neg_slot); KGE_HEAD_B(ur_edge); KGE_HEAD_B(Hs); KGE_HEAD_B(Ts); KGE_HEAD_B(Rs); KGE_HEAD_B(Ns); KGE_HEAD_B(reg_ent); KGE_HEAD_B(reg_rel); KGE_HEAD_B(acc);
+#undef KGE_HEAD_G
+#undef KGE_HEAD_B
+    return hd;
+}
+
 // single-pass variant: the row and its gradients stay in registers (row width <= 256*NIT floats),
 // so every table row is read once and written once - the algorithmic minimum.  Memory-level
 // parallelism: one 32-byte plan record per row gives the row id, the list bounds AND the first
@@ -325,10 +391,10 @@ __device__ __forceinline__ void update_rel_row(const UpdateArgs &a, int bx, int 
 // LEAN: the common fused-step case - TransE fast path, tables updated in place, no gradient outputs - with the
 // generic / emitting code removed at compile time.  Code size matters: the five kernels of a step do not fit the
 // instruction cache together, every launch starts cold, and the full-featured kernel was 11 k instructions.
-// `bid` / `nblk`: this workgroup's index and the number of workgroups doing update work (the body also runs as one
-// half of a horizontally fused launch, see neg_bwd_update_kernel in kge_neg_gemm.hip).
+// `hd`: update_head(a_in, nb_ent, bid, nblk) of this workgroup (`bid` / `nblk`: its index and the number of workgroups doing
+// update work - the body also runs as one half of a horizontally fused launch, see neg_fwd_update_kernel in kge_neg_gemm.hip).
 template <int NIT, bool SHARDED, int LEAN_>     // LEAN: 0 = everything at run time, 1 = in-place + TransE fast path,
-__device__ __forceinline__ void update_reg_body(const UpdateArgs &a_in, int nb_ent, int bid, int nblk) {   // 2 = in-place + per-edge gradients
+__device__ __forceinline__ void update_reg_body(const UpdateArgs &a_in, const UpdateHead &hd) {   // 2 = in-place + per-edge gradients
     using namespace kge;                         // 3 = 1 with Q rows; 4 (round 4) = 0 with the regulariser's norm fixed at 3 - the
     constexpr int LEAN = (LEAN_ == 4 || LEAN_ == 6 || LEAN_ == 7) ? 0 : (LEAN_ == 5 ? 1 : LEAN_); // gradient-emitting (sharded all-to-all) step of every BASELINE recipe
     // 6 (round 4) = 4 narrowed to what the all-to-all engine's step asks for when the model has per-edge gradient rows (RotatE /
@@ -363,23 +429,14 @@ __device__ __forceinline__ void update_reg_body(const UpdateArgs &a_in, int nb_e
     constexpr int LB1 = NIT <= 2 ? 4 : 2;       // entity lists: entries with one source row
     constexpr int LB2 = NIT <= 2 ? 2 : 1;       // entries with two (TransE fast path without Q: P and GA)
     constexpr int LBR = NIT <= 2 ? 6 : 2;       // relation lists (one source row; the relation part holds less other state)
-    // the (fewer) relation workgroups are dispatched FIRST: measured 14.9 vs 16.5 us - a relation wavefront has
-    // the same dependent-load chain as an entity wavefront and must not start after all entity workgroups
-    const int nb_rel = nblk - nb_ent;
-    const int bx = bid < nb_rel ? bid + nb_ent : bid - nb_rel;
-    if (bx < nb_ent) {
-        // (the wavefront number through readfirstlane: the compiler then knows that the record / count addresses are wave-uniform
-        //  and fetches them with scalar loads)
-        const int64_t u = (int64_t)bx * KGE_WAVES_PER_BLOCK + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-        if (u >= a.UE) return;                 // UE: the bound the grid and the record array were sized for
+    const bool is_ent = hd.is_ent, dev_counts = hd.dev_counts;
+    const UniformI4 r0 = hd.r0, r1 = hd.r1, cn = hd.cn;
+    const int64_t u = hd.u;
+    if (is_ent) {
+        if (u >= a.UE) return;
         const int d = a.model_d_e;
-        // the device-side row count and this wavefront's plan record are requested TOGETHER (the record of a row beyond the
-        // count is allocated, just unused): count -> record -> rows was one dependent round more in every wavefront
-        int4 r0 = reinterpret_cast<const int4 *>(a.ue_rec)[2 * u];
-        const int4 r1 = reinterpret_cast<const int4 *>(a.ue_rec)[2 * u + 1];
-        const int cnt_e = a.counts_dev ? a.counts_dev[0] : a.UE;
-        asm volatile("" : "+v"(r0.x));         // (keeps the record loads above the early exit)
-        if (u >= cnt_e) return;
+        const int cnt_e = dev_counts ? cn.x : a.UE;
+        if (u >= cnt_e) return;                // rows are requested only behind the count test
         const int64_t id = (int64_t)(uint32_t)r0.x | ((int64_t)r0.y << 32);
         const int p0 = r0.z, p1 = r0.w, n0 = r1.x, n1 = r1.y, adj0 = r1.z, slot0 = r1.w;
         float *row = shard_row(a.em, a.ent, id, d);
@@ -671,10 +728,11 @@ __device__ __forceinline__ void update_reg_body(const UpdateArgs &a_in, int nb_e
         // (kernel-uniform) runs the plain instance - the shared-list code costs 0.25 us per step on uniform ids just by being
         // there (registers, code layout; profiles/r02_heavy_lists.txt)
         constexpr int COOP_MIN_R = 2 * (NIT <= 2 ? 6 : 2) + 1;
-        const bool coop = !(a.transe_fast && !qm) && (!a.counts_dev || a.counts_dev[3] - 1 >= COOP_MIN_R);
-        if constexpr (FOLD) update_rel_row<NIT, SHARDED, LEAN, false, true>(a, bx, nb_ent, lane, reg, qm);   // (fast path without Q: never the shared-list instance)
-        else if (coop) update_rel_row<NIT, SHARDED, LEAN, true>(a, bx, nb_ent, lane, reg, qm);
-        else update_rel_row<NIT, SHARDED, LEAN, false>(a, bx, nb_ent, lane, reg, qm);
+        const bool coop = !(a.transe_fast && !qm) && (!dev_counts || cn.w - 1 >= COOP_MIN_R);
+        const int cnt_r = dev_counts ? cn.y : a.UR;
+        if constexpr (FOLD) update_rel_row<NIT, SHARDED, LEAN, false, true>(a, u, r0, r1, cnt_r, lane, reg, qm);   // (fast path without Q: never the shared-list instance)
+        else if (coop) update_rel_row<NIT, SHARDED, LEAN, true>(a, u, r0, r1, cnt_r, lane, reg, qm);
+        else update_rel_row<NIT, SHARDED, LEAN, false>(a, u, r0, r1, cnt_r, lane, reg, qm);
     }
 }
 
