@@ -19,9 +19,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 
-def test_route_build_matches_numpy():
-    """owner buckets of fixed capacity, cache rows, re-addressed batch - host plan and device-built plan."""
+def run_route_build_case():
+    """the body of test_route_build_matches_numpy; -> the routing arrays of every configuration"""
     import ctypes as C
+    res = {}
     from dglke_amd import _lib, plan
     from dglke_amd import dist as kd
     rng = np.random.RandomState(3)
@@ -58,13 +59,18 @@ def test_route_build_matches_numpy():
         want[:, 0], want[:, 1] = (cr & 0xffffffff).astype(np.uint32).view(np.int32), (cr >> 32).astype(np.int32)
         assert np.array_equal(rec, want)
         assert lb.c.B == B and lb.c.UE == b.UE
+        res.update({"%s w%d" % (k, world): getattr(eng_like, k).clone() for k in ("req_ids", "h_loc", "t_loc", "neg_loc", "ue_loc", "ue_rec_loc",
+                                                                                  "overflow")})
+    return res
 
 
-def test_route_fill_and_capacity_growth():
-    """kge_route_fill (largest owner-bucket fill of a GROUP of batches: host-built plans one by one, consecutive sampler slots in
-    one launch) against numpy, and DistEngine.ensure_capacity on top of it: heavy-tailed ids whose hubs sit in the first shard,
-    a deliberately small capacity - the buckets grow BEFORE the group runs and the overflow counter of the routing kernel stays 0
-    (the exchange itself is covered by the world-2 tests below, the decision across ranks by tests/test_dist_gloo.py at world 8)."""
+def test_route_build_matches_numpy():
+    """owner buckets of fixed capacity, cache rows, re-addressed batch - host plan and device-built plan."""
+    run_route_build_case()
+
+
+def run_route_fill_case():
+    """the body of test_route_fill_and_capacity_growth; -> the fills, the group's route pool and the last batch's single routing"""
     from dglke_amd import plan
     from dglke_amd import dist as kd
     from dglke_amd.dataloader import DeviceSampler
@@ -86,6 +92,7 @@ def test_route_fill_and_capacity_growth():
         return int(np.bincount(np.minimum(ue // per, world - 1)[both], minlength=world).max())
     want2 = max(both_max(b.p["ue_id"], b.p["ue_rec"].reshape(-1, 8)) for b in host)
     assert out.tolist() == [want, want2] and want > 150 and want2 > 0
+    res = dict(fill_host=out.clone())
     # consecutive sampler slots: ONE launch
     h = rng.randint(0, n_ent, 20000); t = rng.randint(0, n_ent, 20000); r = rng.randint(0, 7, 20000)
     h = np.where(rng.rand(20000) < 0.6, h % per, h)
@@ -100,6 +107,7 @@ def test_route_fill_and_capacity_growth():
         ue = a["ue_id"][:a["counts"][0]]
         fills.append(int(np.bincount(np.minimum(ue // per, world - 1), minlength=world).max()))
     assert int(out[0].item()) == max(fills)
+    res["fill_slots"] = out.clone()
     # ensure_capacity at world 1 is a no-op (one owner: the bound); the growth rule itself on a world-8 spec without collectives
     class _NoComm(object):
         world, rank = 8, 0
@@ -137,6 +145,16 @@ def test_route_fill_and_capacity_growth():
             assert np.array_equal(got, ref.cpu().numpy()[:n]), "%s of slot %d differs between group and single routing" % (name, b.slot)
         assert np.array_equal(lb.req_ids.cpu().numpy(), s0.req_ids.cpu().numpy())
     assert de.check_overflow() == 0
+    res.update(pool=de._route_pool.clone(), req_ids=s0.req_ids.clone(), ue_rec_loc=s0.ue_rec_loc.clone())
+    return res
+
+
+def test_route_fill_and_capacity_growth():
+    """kge_route_fill (largest owner-bucket fill of a GROUP of batches: host-built plans one by one, consecutive sampler slots in
+    one launch) against numpy, and DistEngine.ensure_capacity on top of it: heavy-tailed ids whose hubs sit in the first shard,
+    a deliberately small capacity - the buckets grow BEFORE the group runs and the overflow counter of the routing kernel stays 0
+    (the exchange itself is covered by the world-2 tests below, the decision across ranks by tests/test_dist_gloo.py at world 8)."""
+    run_route_fill_case()
 
 
 def test_precaptured_compute_graphs_equal_eager_launches():
@@ -251,7 +269,7 @@ def test_overlapped_schedule_equals_pipelined_pull():
         assert float((res[0][1] > 0).sum()) > 100
 
 
-def test_gather_rows_req_skips_pads_and_foreign_ids():
+def run_gather_rows_req_case():
     from dglke_amd import dist as kd
     t = torch.arange(0, 80, dtype=torch.float32, device=DEV).reshape(10, 8)
     ids = torch.tensor([105, -1, 100, 109, 99, 110], device=DEV)          # shard holds ids 100..109
@@ -261,6 +279,11 @@ def test_gather_rows_req_skips_pads_and_foreign_ids():
     want = torch.full((6, 8), -7.0)
     want[0], want[2], want[3] = t[5].cpu(), t[0].cpu(), t[9].cpu()
     assert torch.equal(out.cpu(), want)
+    return dict(out=out)
+
+
+def test_gather_rows_req_skips_pads_and_foreign_ids():
+    run_gather_rows_req_case()
 
 
 @pytest.mark.parametrize("nsrc,cap,dim,n_rows", [(1, 40, 8, 64), (2, 33, 8, 40), (3, 100, 64, 120), (8, 257, 400, 600),
@@ -268,6 +291,11 @@ def test_gather_rows_req_skips_pads_and_foreign_ids():
 def test_apply_merged_equals_sequential_apply(nsrc, cap, dim, n_rows):
     """rows that arrive from several sources are applied once, in source order, by the first source's wavefront: compare with a
     sequential numpy statement (kvserver.py:41-51 per pushed row, tensor_models.py:316 trace order)."""
+    run_apply_merged_case(nsrc, cap, dim, n_rows)
+
+
+def run_apply_merged_case(nsrc, cap, dim, n_rows):
+    """the body of test_apply_merged_equals_sequential_apply; -> the tables and states of the merged apply and of the pair launch"""
     from dglke_amd import dist as kd
     rng = np.random.RandomState(nsrc * 1000 + cap)
     lo, T, lr = 1000, 2, 0.1
@@ -309,6 +337,7 @@ def test_apply_merged_equals_sequential_apply(nsrc, cap, dim, n_rows):
     kd.HipOps().apply_merged(t2, s2, nsrc, cap, None, lo, torch.from_numpy(m2).to(DEV), T, lr)
     torch.cuda.synchronize()
     assert torch.equal(t2, t_d) and torch.equal(s2, s_d)
+    res = dict(table=t_d, state=s_d, table_ids_inside=t2, state_ids_inside=s2)
     # round 4: the step's two applies as ONE launch (kge_adagrad_apply_merged_pair: this job next to a second, narrower,
     # single-trace job with the ids inside its messages - the relation replica's) - bit-identical to the two separate calls
     if dim % 4 == 0:
@@ -333,6 +362,8 @@ def test_apply_merged_equals_sequential_apply(nsrc, cap, dim, n_rows):
         torch.cuda.synchronize()
         assert torch.equal(ta, t_d) and torch.equal(sa, s_d) and torch.equal(tb2, tb1) and torch.equal(sb2, sb1)
         assert not torch.equal(tb1.cpu(), torch.from_numpy(tab_b))
+        res.update(pair_table_a=ta, pair_state_a=sa, pair_table_b=tb2, pair_state_b=sb2)
+    return res
 
 
 @pytest.mark.parametrize("mode", ["sampled", "sampled_overlap"])

@@ -392,15 +392,9 @@ def _packed_reference(table, state, ids, g, gs, lr, eps=1e-10):
     return t64, s64
 
 
-@pytest.mark.parametrize("inside", [False, True], ids=["idx", "ids_inside"])
-@pytest.mark.parametrize("T", [1, 2, 3])
-@pytest.mark.parametrize("dim", [8, 30, 1028])
-def test_adagrad_apply_packed_matches_float64_and_skips(dim, T, inside):
-    """msg = [g_0 | .. | g_{T-1} | gs_0 .. gs_{T-1} | (id_lo id_hi)]: the T traces in order, ids from idx or from the message, negative
-    ids skipped (row and state bit-unchanged), a trace with increment exactly 0 skipped while the later traces of the row are applied.
-    Twice per case: an ld that is a multiple of 4 (dim 8 / 1028: the 16-byte instance) and one that is not (the scalar instance, as
-    for dim 30).  Bounds of test_adagrad_apply_rows_matches_float64_and_skips.  Ids at or above 2^31 are out of scope: a table with
-    that many rows does not fit this test (the id is read as two int32 words and widened, see apply_packed_kernel)."""
+def run_apply_packed_case(dim, T, inside):
+    """the body of test_adagrad_apply_packed_matches_float64_and_skips; -> table and state, by ld"""
+    res = {}
     rng = np.random.RandomState(M._seed("packed", dim, T, inside))
     n_tab, n, lr = 700, 500, 0.3
     need = T * dim + T + (2 if inside else 0)
@@ -437,6 +431,20 @@ def test_adagrad_apply_packed_matches_float64_and_skips(dim, T, inside):
         _record("apply_packed dim=%d T=%d %s" % (dim, T, "ids inside" if inside else "idx"), "ld=%d" % ld,
                 "%d negative ids, %d zero-increment traces" % (drop.sum(), zero.sum()), **errs)
         _check(errs, "apply_packed dim %d T %d ld %d" % (dim, T, ld))
+        res.update({"table ld%d" % ld: t_d, "state ld%d" % ld: s_d})
+    return res
+
+
+@pytest.mark.parametrize("inside", [False, True], ids=["idx", "ids_inside"])
+@pytest.mark.parametrize("T", [1, 2, 3])
+@pytest.mark.parametrize("dim", [8, 30, 1028])
+def test_adagrad_apply_packed_matches_float64_and_skips(dim, T, inside):
+    """msg = [g_0 | .. | g_{T-1} | gs_0 .. gs_{T-1} | (id_lo id_hi)]: the T traces in order, ids from idx or from the message, negative
+    ids skipped (row and state bit-unchanged), a trace with increment exactly 0 skipped while the later traces of the row are applied.
+    Twice per case: an ld that is a multiple of 4 (dim 8 / 1028: the 16-byte instance) and one that is not (the scalar instance, as
+    for dim 30).  Bounds of test_adagrad_apply_rows_matches_float64_and_skips.  Ids at or above 2^31 are out of scope: a table with
+    that many rows does not fit this test (the id is read as two int32 words and widened, see apply_packed_kernel)."""
+    run_apply_packed_case(dim, T, inside)
 
 
 def test_adagrad_apply_packed_argument_errors():

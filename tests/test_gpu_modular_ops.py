@@ -159,12 +159,11 @@ def test_score_neg_refuses_a_rescal_width_it_cannot_serve():
 # --------------------------------------------------------------------------------------------------------------------------
 # (b) score_pos forward and backward
 # --------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("c", M.POS_CASES, ids=lambda c: c["id"])
-def test_score_pos_matches_float64(c):
-    """kge_score_pos / kge_score_pos_bwd (edge_bwd with clamp_pos = 1; RESCAL: matvec, two axpy, outer product) at
-    B = 1, 37, 1000, 4101: score, gh, gr, gt"""
+def run_pos_case(c, Bs=None):
+    """the body of test_score_pos_matches_float64 at the case's batch sizes (or `Bs`); -> every output, by batch size"""
     from dglke_amd import ops
-    for B in c["Bs"]:
+    res = {}
+    for B in Bs or c["Bs"]:
         tag = "%s B=%d" % (c["id"], B)
         inp = M.pos_inputs(c, B)
         ref = M.oracle_pos(c, inp)
@@ -188,19 +187,26 @@ def test_score_pos_matches_float64(c):
             errs[k] = M.worst(M.masked(got[k], ref[k], edges), ref[k], M.grad_bound(ref[k]))
         _record("score_pos", tag, note, **errs)
         _check(errs, tag)
+        res.update({"%s B%d" % (k, B): v for k, v in got.items()})
+    return res
+
+
+@pytest.mark.parametrize("c", M.POS_CASES, ids=lambda c: c["id"])
+def test_score_pos_matches_float64(c):
+    """kge_score_pos / kge_score_pos_bwd (edge_bwd with clamp_pos = 1; RESCAL: matvec, two axpy, outer product) at
+    B = 1, 37, 1000, 4101: score, gh, gr, gt"""
+    run_pos_case(c)
 
 
 # --------------------------------------------------------------------------------------------------------------------------
 # (c) pnorm_pow
 # --------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("zeros", [False, True], ids=["dense", "zeros"])
-@pytest.mark.parametrize("p", [1, 2, 3, 4])
-def test_pnorm_pow_value_and_gradient(p, zeros):
-    """x.norm(p) ** p and its gradient.  Value: n * dim * 2^-24 * sum |x|^p (one rounding per term of a fixed-order sum, at most
-    n * dim of them deep).  Gradient: 1e-6 relative per element; exactly 0 at x == 0 for every p."""
+def run_pnorm_case(p, zeros, shapes=None):
+    """the body of test_pnorm_pow_value_and_gradient at M.PNORM_SHAPES (or `shapes`); -> value and gradient, by shape"""
     from dglke_amd import ops
     coef = 0.37
-    for n, dim in M.PNORM_SHAPES:
+    res = {}
+    for n, dim in shapes or M.PNORM_SHAPES:
         tag = "p=%d n=%s dim=%d%s" % (p, n, dim, " zeros" if zeros else "")
         x = M.pnorm_input(n, dim, zeros)
         val, grad = M.pnorm_ref(x, p, coef)
@@ -214,14 +220,23 @@ def test_pnorm_pow_value_and_gradient(p, zeros):
         _record("pnorm_pow", tag, **errs)
         assert not g[x == 0].any(), tag + ": gradient at an exact zero"
         _check(errs, tag)
+        res.update({"value " + tag: y.detach().cpu().numpy().reshape(1), "grad " + tag: g})
+    return res
+
+
+@pytest.mark.parametrize("zeros", [False, True], ids=["dense", "zeros"])
+@pytest.mark.parametrize("p", [1, 2, 3, 4])
+def test_pnorm_pow_value_and_gradient(p, zeros):
+    """x.norm(p) ** p and its gradient.  Value: n * dim * 2^-24 * sum |x|^p (one rounding per term of a fixed-order sum, at most
+    n * dim of them deep).  Gradient: 1e-6 relative per element; exactly 0 at x == 0 for every p."""
+    run_pnorm_case(p, zeros)
 
 
 # --------------------------------------------------------------------------------------------------------------------------
 # (d) mask_diag
 # --------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", M.MASK_SHAPES, ids=lambda s: "C%d-chunk%d-Np%d" % s)
-def test_mask_diag_forward_and_backward_bit_exact(shape):
-    """only the [c, i, i] elements change (i < min(chunk, Np)), the gradient is masked at the same places, the input is kept"""
+def run_mask_diag_case(shape):
+    """the body of test_mask_diag_forward_and_backward_bit_exact; -> output and gradient"""
     from dglke_amd import ops
     C, chunk, Np = shape
     rng = np.random.RandomState(5)
@@ -234,15 +249,20 @@ def test_mask_diag_forward_and_backward_bit_exact(shape):
     assert np.array_equal(xt.grad.cpu().numpy(), M.mask_diag_ref(g, C, chunk, Np))
     assert np.array_equal(xt.detach().cpu().numpy(), x)
     _record("mask_diag", "C=%d chunk=%d Np=%d" % shape, "bit-exact")
+    return dict(y=y.detach().cpu().numpy(), grad=xt.grad.cpu().numpy())
+
+
+@pytest.mark.parametrize("shape", M.MASK_SHAPES, ids=lambda s: "C%d-chunk%d-Np%d" % s)
+def test_mask_diag_forward_and_backward_bit_exact(shape):
+    """only the [c, i, i] elements change (i < min(chunk, Np)), the gradient is masked at the same places, the input is kept"""
+    run_mask_diag_case(shape)
 
 
 # --------------------------------------------------------------------------------------------------------------------------
 # (e) gather_local
 # --------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", M.GATHER_CASES, ids=lambda c: "%s-rows%d-idx%d-dim%d" % c)
-def test_gather_local_forward_bit_exact_backward_inside_the_atomic_bound(case):
-    """forward kge_gather_rows: bit-exact.  Backward kge_scatter_add_rows (float atomics, any order): per element within
-    count * 2^-24 * sum |terms| of the float64 np.add.at - the worst case of any summation order, no margin"""
+def run_gather_case(case):
+    """the body of test_gather_local_forward_bit_exact_backward_inside_the_atomic_bound; -> gathered rows and scattered gradient"""
     from dglke_amd import ops
     kind, rows, n_idx, dim = case
     block, idx, g = M.gather_input(*case)
@@ -257,15 +277,21 @@ def test_gather_local_forward_bit_exact_backward_inside_the_atomic_bound(case):
     errs = dict(grad=M.worst(got, ref, bound + 1e-300))
     _record("gather_local", "%s rows=%d idx=%d dim=%d" % case, "forward bit-exact", **errs)
     _check(errs, str(case))
+    return dict(out=out.detach().cpu().numpy(), grad=got)
+
+
+@pytest.mark.parametrize("case", M.GATHER_CASES, ids=lambda c: "%s-rows%d-idx%d-dim%d" % c)
+def test_gather_local_forward_bit_exact_backward_inside_the_atomic_bound(case):
+    """forward kge_gather_rows: bit-exact.  Backward kge_scatter_add_rows (float atomics, any order): per element within
+    count * 2^-24 * sum |terms| of the float64 np.add.at - the worst case of any summation order, no margin"""
+    run_gather_case(case)
 
 
 # --------------------------------------------------------------------------------------------------------------------------
 # (f) adagrad_scatter and adagrad_apply_rows
 # --------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("dup", [False, True], ids=["unique", "duplicates"])
-@pytest.mark.parametrize("dim", M.ADAGRAD_DIMS)
-def test_adagrad_scatter_matches_float64(dim, dup):
-    """3 000 (index, gradient) rows, with duplicates and a hub of five rows: tolerances of test_adagrad_scatter_duplicate_semantics"""
+def run_adagrad_scatter_case(dim, dup):
+    """the body of test_adagrad_scatter_matches_float64; -> table and state"""
     from dglke_amd import ops
     table, state, idx, grad = M.adagrad_input(dim, dup)
     t_d, s_d = _dev(table), _dev(state)
@@ -278,11 +304,18 @@ def test_adagrad_scatter_matches_float64(dim, dup):
     untouched[idx] = False
     assert np.array_equal(t_d.cpu().numpy()[untouched], table[untouched]) and np.array_equal(s_d.cpu().numpy()[untouched], state[untouched])
     _check(errs, "adagrad_scatter dim %d" % dim)
+    return dict(table=t_d, state=s_d)
 
 
+@pytest.mark.parametrize("dup", [False, True], ids=["unique", "duplicates"])
 @pytest.mark.parametrize("dim", M.ADAGRAD_DIMS)
-def test_adagrad_apply_rows_matches_float64_and_skips(dim):
-    """unique ids; rows with idx = -1 and rows with gs = 0 are skipped: their table rows and states stay bit for bit"""
+def test_adagrad_scatter_matches_float64(dim, dup):
+    """3 000 (index, gradient) rows, with duplicates and a hub of five rows: tolerances of test_adagrad_scatter_duplicate_semantics"""
+    run_adagrad_scatter_case(dim, dup)
+
+
+def run_adagrad_apply_rows_case(dim):
+    """the body of test_adagrad_apply_rows_matches_float64_and_skips; -> table and state"""
     from dglke_amd import ops
     table, state, idx, grad = M.adagrad_input(dim, False)
     gs = (grad.astype(np.float64) ** 2).mean(1).astype(np.float32)
@@ -305,20 +338,33 @@ def test_adagrad_apply_rows_matches_float64_and_skips(dim):
     _record("adagrad_rows", "dim=%d" % dim, "%d idx=-1 and %d gs=0 rows untouched bit for bit" % (drop.sum(), zero.sum()), **errs)
     assert (got_t[idx[keep]] != table[idx[keep]]).any(1).all(), "a kept row did not move"
     _check(errs, "adagrad_apply_rows dim %d" % dim)
+    return dict(table=t_d, state=s_d)
+
+
+@pytest.mark.parametrize("dim", M.ADAGRAD_DIMS)
+def test_adagrad_apply_rows_matches_float64_and_skips(dim):
+    """unique ids; rows with idx = -1 and rows with gs = 0 are skipped: their table rows and states stay bit for bit"""
+    run_adagrad_apply_rows_case(dim)
 
 
 # --------------------------------------------------------------------------------------------------------------------------
 # (g) rank_from_scores
 # --------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("with_bias", [False, True], ids=["nobias", "bias"])
-@pytest.mark.parametrize("shape", M.RANK_SHAPES, ids=lambda s: "E%d-N%d" % s)
-def test_rank_from_scores_equals_numpy(shape, with_bias):
-    """1 + #{j: neg[i, j] >= pos[i], bias[i, j] != -1}: exact ties count, masked candidates do not; integer equality"""
+def run_rank_case(shape, with_bias):
+    """the body of test_rank_from_scores_equals_numpy; -> ranks"""
     from dglke_amd import ops
     neg, pos, bias = M.rank_input(shape[0], shape[1], with_bias)
     got = ops.rank_from_scores(_dev(neg), _dev(pos), None if bias is None else _dev(bias))
     assert got.dtype == torch.int64 and np.array_equal(got.cpu().numpy(), M.rank_ref(neg, pos, bias))
     _record("rank", "E=%d N=%d %s" % (shape + ("bias" if with_bias else "nobias",)), "equal")
+    return dict(ranks=got)
+
+
+@pytest.mark.parametrize("with_bias", [False, True], ids=["nobias", "bias"])
+@pytest.mark.parametrize("shape", M.RANK_SHAPES, ids=lambda s: "E%d-N%d" % s)
+def test_rank_from_scores_equals_numpy(shape, with_bias):
+    """1 + #{j: neg[i, j] >= pos[i], bias[i, j] != -1}: exact ties count, masked candidates do not; integer equality"""
+    run_rank_case(shape, with_bias)
 
 
 # --------------------------------------------------------------------------------------------------------------------------

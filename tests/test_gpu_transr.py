@@ -127,10 +127,8 @@ def test_transr_fused_step_matches_oracle_at_tile_shapes(shape):
         es, rs, ps = (x.cpu().numpy().astype(np.float64) for x in (eng.ent_state, eng.rel_state, eng.proj_state))
 
 
-@pytest.mark.parametrize("C,chunk,N,De,Dr", [(2, 8, 12, 16, 16), (1, 5, 7, 10, 6), (3, 33, 70, 64, 40), (2, 64, 64, 128, 72)])
-def test_transr_projection_ops_match_torch_autograd(C, chunk, N, De, Dr):
-    """the per-op route's HIP projections (kge_transr_project / _neg and their analytic backward) against the reference's
-    th.matmul formulation (score_fun.py:131-166) in fp64 with torch autograd."""
+def run_projection_ops_case(C, chunk, N, De, Dr):
+    """the body of test_transr_projection_ops_match_torch_autograd; -> the two projections and the three gradients"""
     from dglke_amd import ops
     g = torch.Generator().manual_seed(C * 100 + N)
     B = C * chunk
@@ -155,6 +153,14 @@ def test_transr_projection_ops_match_torch_autograd(C, chunk, N, De, Dr):
     np.testing.assert_allclose(xd.grad.cpu().numpy(), x64.grad.numpy(), rtol=2e-5, atol=3e-5)
     np.testing.assert_allclose(nd.grad.cpu().numpy(), n64.grad.numpy(), rtol=2e-5, atol=2e-4)
     np.testing.assert_allclose(pd.grad.cpu().numpy(), p64.grad.numpy(), rtol=2e-5, atol=2e-4)
+    return dict(y=y.detach(), Y=Y.detach(), gx=xd.grad, gneg=nd.grad, gproj=pd.grad)
+
+
+@pytest.mark.parametrize("C,chunk,N,De,Dr", [(2, 8, 12, 16, 16), (1, 5, 7, 10, 6), (3, 33, 70, 64, 40), (2, 64, 64, 128, 72)])
+def test_transr_projection_ops_match_torch_autograd(C, chunk, N, De, Dr):
+    """the per-op route's HIP projections (kge_transr_project / _neg and their analytic backward) against the reference's
+    th.matmul formulation (score_fun.py:131-166) in fp64 with torch autograd."""
+    run_projection_ops_case(C, chunk, N, De, Dr)
 
 
 @pytest.mark.parametrize("shape", [TILE_SHAPES[0], TILE_SHAPES[3], TILE_SHAPES[4]],
