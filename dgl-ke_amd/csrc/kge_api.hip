@@ -50,7 +50,12 @@ struct Carver {
 };
 
 int check_model(int model, int d_e, int d_r) {
-    if (model < KGE_TRANSE_L1 || model > KGE_TRANSR) return fail(KGE_ERR_ARG, "unknown model %d", model);
+    if (model < KGE_TRANSE_L1 || (model > KGE_TRANSR && model != KGE_QUATE)) return fail(KGE_ERR_ARG, "unknown model %d", model);
+    if (model == KGE_QUATE) {
+        if (d_e <= 0 || d_e % 4 || d_r != d_e)
+            return fail(KGE_ERR_ARG, "QuatE needs d_e a positive multiple of 4 and d_r == d_e (got %d, %d)", d_e, d_r);
+        return KGE_OK;
+    }
     if (model == KGE_TRANSR) {
         if (d_e <= 0 || d_r <= 0 || d_r > 1024) return fail(KGE_ERR_ARG, "TransR needs 0 < d_r <= 1024 (got d_e=%d d_r=%d)", d_e, d_r);
         return KGE_OK;
@@ -71,6 +76,9 @@ int check_model(int model, int d_e, int d_r) {
     }
     return KGE_OK;
 }
+
+// QuatE runs the strict step on local tables and single-table ranking; the other entries open with their own tests
+int no_quate(const char *who) { return fail(KGE_ERR_ARG, "%s: not available for QuatE (strict step on local tables, single-table ranking)", who); }
 
 inline float rot_div_of(float emb_init) { return (float)((double)emb_init / M_PI); }
 inline float clamp_of(int model) { return model == KGE_SIMPLE ? KGE_SIMPLE_CLAMP : 0.f; }
@@ -568,7 +576,8 @@ static StepPlan plan_step(const kge_hparams *hp, const kge_batch *b, const kge_s
     // KGE_FLAG_FUSED_LOSS (matrix-core path, pointwise criteria): no loss kernel - the forward tiles emit the factorised gradient
     // (kge_neg_gemm.hip).  4 launches per step instead of 5, 1.6 MB less traffic, but measured 41.7 vs 41.1 us per step at cfg-T
     // (profiles/r02_fused_loss_experiment.txt), so it is opt-in.  (RESCAL has no edge_fwd: its positive-loss part lives in the loss kernel)
-    p.fused_loss = p.gemm && !p.pos_row && !p.nd && !p.rescal && (fl & KGE_FLAG_FUSED_LOSS) && neg_gemm_fused_loss_supported(chunk, N);
+    p.fused_loss = p.gemm && !p.pos_row && !p.nd && !p.rescal && model != KGE_QUATE && (fl & KGE_FLAG_FUSED_LOSS) &&
+                   neg_gemm_fused_loss_supported(chunk, N);
     const bool transe = model == KGE_TRANSE_L1 || p.is_l2;
     // TransE fast path: edge_fwd leaves P rows, the update rebuilds the per-edge gradients from them (no edge_bwd launch)
     p.transe_fast = transe && !p.pos_row && !p.nd && d_e % 4 == 0 && d_r % 4 == 0 && (d_e > d_r ? d_e : d_r) <= 1024 && !(fl & KGE_FLAG_NO_TRANSE_FAST);
@@ -1174,6 +1183,7 @@ size_t kge_step_async_workspace_bytes(const kge_hparams *hp, int B, int C, int c
 int kge_step_async(kge_pipe *p, const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_batch *b_next,
                    const kge_step_out *out, void *ws, size_t ws_bytes, void *stream) {
     if (!p || !hp || !tb || !b || !ws) return fail(KGE_ERR_ARG, "kge_step_async: null argument");
+    if (hp->model == KGE_QUATE) return no_quate("kge_step_async");
     const size_t half = (ws_bytes / 2) & ~(size_t)255;
     void *wsp = (char *)ws + (size_t)p->parity * half;
     void *wsn = (char *)ws + (size_t)(p->parity ^ 1) * half;
@@ -1264,6 +1274,7 @@ int kge_step_phase_known(const kge_hparams *hp, const kge_tables *tb, const kge_
 
 int kge_step_grads(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, const kge_emit *emit,
                    void *ws, size_t ws_bytes, void *stream) {
+    if (hp && hp->model == KGE_QUATE) return no_quate("kge_step_grads");
     if (!emit || !emit->g0 || (!emit->msg_rows && (!emit->gs0 || !emit->g1 || !emit->gs1)))
         return fail(KGE_ERR_ARG, "kge_step_grads: emit buffers g0/gs0/g1/gs1 are required (packed messages: g0 + msg_rows)");
     if ((emit->gr == nullptr) != (emit->gsr == nullptr))
@@ -1412,6 +1423,7 @@ int kge_rank_eval_split(int model, int neg_head, const float *qent, int64_t n_qe
                         float gamma, float emb_init, const int64_t *cand, int64_t n_cand, const int64_t *filt_ptr, const int64_t *filt_ids,
                         int Eb, int32_t *ranks, float *pos_score_out, void *ws, size_t ws_bytes, unsigned flags, void *stream) {
     if (int rc = check_model(model, d_e, d_r)) return rc;
+    if (model == KGE_QUATE) return no_quate("kge_rank_eval_split");
     if (model == KGE_TRANSR && !proj)
         return fail(KGE_ERR_ARG, "kge_rank_eval_split: TransR needs the projection table");
     if (n_qent <= 0 || n_cent < 0) return fail(KGE_ERR_ARG, "kge_rank_eval_split: bad argument");
@@ -1549,7 +1561,7 @@ int kge_rank_eval_chunked(int model, int neg_head, const float *ent, int64_t n_e
 // ---- relation ranking (kge_rank_rel.hip) ----
 // one batch of Eb test triples: query rows / their norms / positive scores, the relation rows' norms (TransE_l2), the score block or
 // comparison mask, and TransR's projected rows, negated relation rows and identity ids.  The layout does not depend on the flags.
-struct RelBufs : TransRRows { float *Q, *qsq, *P, *csq, *S, *RQ; int64_t *ids; };
+struct RelBufs : TransRRows { float *Q, *qsq, *P, *csq, *S, *RQ, *RN; int64_t *ids; };
 static size_t carve_rank_rel(Carver &cv, RelBufs &w, int model, int Eb, int64_t n_rel, int d_e, int d_r) {
     const size_t qw = model == KGE_ROTATE ? 0 : model == KGE_RESCAL ? (size_t)d_e * d_e : (size_t)d_e;
     w.Q = cv.f((size_t)Eb * qw); w.qsq = cv.f(Eb); w.P = cv.f(Eb); w.csq = cv.f((size_t)n_rel);
@@ -1557,11 +1569,14 @@ static size_t carve_rank_rel(Carver &cv, RelBufs &w, int model, int Eb, int64_t 
     carve_transr_rows(cv, w, model == KGE_TRANSR ? (size_t)Eb * d_r : 0);
     w.RQ = cv.f(model == KGE_TRANSR ? (size_t)n_rel * d_r : 0);
     w.ids = cv.i64(model == KGE_TRANSR ? std::max((size_t)n_rel, (size_t)Eb) : 0);
+    w.RN = model == KGE_QUATE ? cv.f((size_t)n_rel * d_r) : nullptr;       // QuatE: the relation table normalised per quaternion
     return cv.off;
 }
 
 size_t kge_rank_rel_workspace_bytes(int model, int Eb, int64_t n_rel, int d_e, int d_r) {
     if (Eb <= 0 || n_rel <= 0 || n_rel > 0x7fffffff || check_model(model, d_e, d_r) != KGE_OK) return 0;
+    // ids up to KGE_TRANSR only: a QuatE call takes the DistMult layout followed by the normalised relation table (include/kge_hip.h)
+    if (model == KGE_QUATE) return 0;
     Carver cv; RelBufs w; return carve_rank_rel(cv, w, model, Eb, n_rel, d_e, d_r);
 }
 
@@ -1597,6 +1612,9 @@ int kge_rank_rel_eval(int model, const float *ent, int64_t n_ent, const float *r
         KGE_TRY(launch_edge_fwd(nb, s));
     }
     if (model == KGE_TRANSR) KGE_TRY(launch_rel_neg_rows(rel, n_rel, d_r, w.RQ, w.ids, std::max<int64_t>(n_rel, Eb), s));
+    // QuatE: s_j = <conj(h) (x) t, r^_j> - the product runs against the normalised rows
+    const float *relc = rel;
+    if (model == KGE_QUATE) { KGE_TRY(launch_rel_unit_rows(rel, n_rel, d_r, w.RN, s)); relc = w.RN; }
     for (int64_t e0 = 0; e0 < E; e0 += Eb) {
         const int rows = (int)((E - e0) < Eb ? (E - e0) : Eb);
         float *P = pos_score_out ? pos_score_out + e0 : w.P;
@@ -1626,10 +1644,10 @@ int kge_rank_rel_eval(int model, const float *ent, int64_t n_ent, const float *r
             KGE_TRY(launch_transr_fwd(tr, s));
             KGE_TRY(launch_rank_count(w.S, P, rows, n_rel, filt_ptr, filt_ids, e0, ranks, s, true));
         } else if (gemm) {
-            KGE_TRY(launch_rank_gemm(form, w.Q, rows, rel, nullptr, n_rel, D, gamma, clamp_of(model), w.qsq, w.csq, P, w.S, filt_ptr,
+            KGE_TRY(launch_rank_gemm(form, w.Q, rows, relc, nullptr, n_rel, D, gamma, clamp_of(model), w.qsq, w.csq, P, w.S, filt_ptr,
                                      filt_ids, e0, ranks, s));
         } else {
-            NegArgs na; fill_pair(na, form, 1, rows, (int)n_rel, D, gamma, w.Q, rel, nullptr);
+            NegArgs na; fill_pair(na, form, 1, rows, (int)n_rel, D, gamma, w.Q, relc, nullptr);
             na.clampv = clamp_of(model);
             na.S = w.S;
             KGE_TRY(launch_neg_fwd_pair(na, s));
@@ -1642,6 +1660,7 @@ int kge_rank_rel_eval(int model, const float *ent, int64_t n_ent, const float *r
 int kge_step_sharded(const kge_hparams *hp, const kge_shards *sh, const kge_batch *b,
                      const kge_step_out *out, void *ws, size_t ws_bytes, void *stream) {
     if (!sh) return fail(KGE_ERR_ARG, "kge_step_sharded: null shard map");
+    if (hp && hp->model == KGE_QUATE) return no_quate("kge_step_sharded");
     // (RESCAL's relation "row" is a d_e x d_e matrix streamed by its own kernels: only the entity width is bounded)
     if (hp && (hp->d_e % 4 || hp->d_e > 1024 || (hp->model != KGE_RESCAL && (hp->d_r % 4 || hp->d_r > 1024))))
         return fail(KGE_ERR_ARG, "kge_step_sharded: row widths must be multiples of 4 and <= 1024 floats");

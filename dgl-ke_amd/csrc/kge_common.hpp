@@ -263,6 +263,27 @@ __device__ __forceinline__ float neg_logsigmoid(float z) {
 constexpr bool is_complex_model(int m) { return m == KGE_COMPLEX || m == KGE_ROTATE || m == KGE_SIMPLE; }
 #define KGE_SIMPLE_CLAMP 20.f        // th.clamp(score, -20, 20), score_fun.py:568
 
+// QuatE (include/kge_hip.h, enum kge_model): rows are four quarters [a | b | c | d], one quaternion per column
+struct Quat { float a, b, c, d; };
+__device__ __forceinline__ Quat quat_mul(const Quat &x, const Quat &y) {       // Hamilton product x (x) y
+    Quat o;
+    o.a = x.a * y.a - x.b * y.b - x.c * y.c - x.d * y.d;
+    o.b = x.a * y.b + x.b * y.a + x.c * y.d - x.d * y.c;
+    o.c = x.a * y.c - x.b * y.d + x.c * y.a + x.d * y.b;
+    o.d = x.a * y.d + x.b * y.c - x.c * y.b + x.d * y.a;
+    return o;
+}
+__device__ __forceinline__ Quat quat_conj(const Quat &x) { return Quat{x.a, -x.b, -x.c, -x.d}; }
+__device__ __forceinline__ float quat_dot(const Quat &x, const Quat &y) { return x.a * y.a + x.b * y.b + x.c * y.c + x.d * y.d; }
+// r / |r| with sqrtf and true divisions (a power-of-two norm normalises exactly), 0 where |r| == 0; n: the norm
+__device__ __forceinline__ Quat quat_unit(const Quat &r, float &n) {
+    n = sqrtf(r.a * r.a + r.b * r.b + r.c * r.c + r.d * r.d);
+    if (!(n > 0.f)) return Quat{0.f, 0.f, 0.f, 0.f};
+    return Quat{r.a / n, r.b / n, r.c / n, r.d / n};
+}
+// vector instances of the QuatE row kernels: every quarter a whole number of 16-byte packs
+inline bool quate_vec(int d_e) { return (d_e / 4) % 4 == 0; }
+
 // fast-math variants (hardware exp/log, |rel err| ~1e-6) for the hot kernels
 // softplus and the logistic of the same argument from ONE exponential e = exp(-|z|) (1 + e in (1, 2]: v_rcp_f32, 1 ulp, no
 // IEEE division sequence):  lg = log(1 + e);  -logsigmoid(z) = max(-z, 0) + lg,  -logsigmoid(-z) = max(z, 0) + lg;
@@ -603,6 +624,7 @@ int launch_rel_query(int model, const float *ent, const int64_t *h, const int64_
 int launch_rel_rotate_score(const float *ent, const float *rel, const int64_t *h, const int64_t *t, int rows, int64_t n_rel, int d_e,
                             float gamma, float rot_div, float *S, hipStream_t s);      // S [rows, n_rel]
 int launch_rel_neg_rows(const float *rel, int64_t n_rel, int d_r, float *out, int64_t *ids, int64_t n_ids, hipStream_t s);   // -rel, iota
+int launch_rel_unit_rows(const float *rel, int64_t n_rel, int d_r, float *out, hipStream_t s);      // QuatE: rows normalised per quaternion
 struct GemmArgs {                   // LDS-staged fp32-MFMA negative scoring (kge_neg_gemm.hip)
     int model, C, chunk, N, D;
     float gamma;

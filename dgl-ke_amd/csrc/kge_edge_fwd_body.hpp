@@ -38,8 +38,41 @@ __device__ __forceinline__ void edge_fwd_body(const EdgeFwdArgs &a_in, int bid) 
         constexpr int EK = 2;
         Pack<V> hreg[EK], rreg[EK], treg[EK];
         bool regres = false;
-        if constexpr (!is_complex_model(MODEL)) regres = a.d_e / V <= 64 * EK && a.d_r == a.d_e;
-        if constexpr (!is_complex_model(MODEL)) {
+        if constexpr (!is_complex_model(MODEL) && MODEL != KGE_QUATE) regres = a.d_e / V <= 64 * EK && a.d_r == a.d_e;
+        if constexpr (MODEL == KGE_QUATE) {
+            // QuatE: one quaternion per column of the four quarters [a | b | c | d].  Per round of 64 column packs the twelve
+            // quarter packs of h, r and t are requested before the first use (lane offsets clamped, surplus lanes compute nothing);
+            // the relation is normalised in registers.  x (x) y with (x, y) = (h, r^) or (t, conj(r^)) is the pos-side vector and
+            // the positive score is its dot with the other entity row: <h (x) r^, t> = <h, t (x) conj(r^)>.
+            const int qd = a.d_e / 4;
+            const int nit = qd / V;
+            for (int base = 0; base < nit; base += 64) {
+                const int off = min(base + lane, nit - 1) * V;
+                Pack<V> hq[4], rq[4], tq[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    hq[c] = ld<V>(h + c * qd + off); rq[c] = ld<V>(r + c * qd + off); tq[c] = ld<V>(t + c * qd + off);
+                }
+                if (base + lane < nit) {
+                    Pack<V> aq[4];
+#pragma unroll
+                    for (int e = 0; e < V; ++e) {
+                        const Quat hh{hq[0].v[e], hq[1].v[e], hq[2].v[e], hq[3].v[e]};
+                        const Quat tt{tq[0].v[e], tq[1].v[e], tq[2].v[e], tq[3].v[e]};
+                        float nrm;
+                        const Quat ru = quat_unit(Quat{rq[0].v[e], rq[1].v[e], rq[2].v[e], rq[3].v[e]}, nrm);
+                        const Quat av = a.neg_head ? quat_mul(tt, quat_conj(ru)) : quat_mul(hh, ru);
+                        ps += quat_dot(av, a.neg_head ? hh : tt);
+                        as += quat_dot(av, av);
+                        aq[0].v[e] = av.a; aq[1].v[e] = av.b; aq[2].v[e] = av.c; aq[3].v[e] = av.d;
+                    }
+                    if (A) {
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) KGE_ST_A<V>(A + c * qd + off, aq[c]);
+                    }
+                }
+            }
+        } else if constexpr (!is_complex_model(MODEL)) {
             const int nit = a.d_e / V;
             if (regres) {
 #pragma unroll

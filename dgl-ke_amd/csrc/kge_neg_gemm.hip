@@ -54,7 +54,7 @@ KGE_TL_DEFINE(gemm)
 bool neg_mfma_supported(int model, int d_e, int N) {
     (void)N;
     if (model != KGE_TRANSE_L2 && model != KGE_DISTMULT && model != KGE_COMPLEX && model != KGE_SIMPLE &&
-        model != KGE_RESCAL) return false;
+        model != KGE_RESCAL && model != KGE_QUATE) return false;
     return d_e % 4 == 0;   // 16-byte aligned rows
 }
 

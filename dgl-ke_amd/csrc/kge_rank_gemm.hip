@@ -105,7 +105,8 @@ __global__ __launch_bounds__(KGE_BLOCK) void rank_mask_kernel(const unsigned lon
 }
 
 bool rank_gemm_supported(int model, int d_e) {
-    return (model == KGE_TRANSE_L2 || model == KGE_DISTMULT || model == KGE_COMPLEX || model == KGE_SIMPLE || model == KGE_RESCAL) &&
+    return (model == KGE_TRANSE_L2 || model == KGE_DISTMULT || model == KGE_COMPLEX || model == KGE_SIMPLE || model == KGE_RESCAL ||
+            model == KGE_QUATE) &&
            d_e >= 4 && d_e % 4 == 0;
 }
 size_t rank_gemm_mask_bytes(int rows, int64_t N) { return (size_t)rows * (size_t)((N + 127) / 128 * 2) * 8; }

@@ -9,6 +9,7 @@
 //     RESCAL           q = vec(h t^T), d_e^2 wide                  s_j = q . vec(M_j)
 //     TransR           u = h - t                                   s_j = gamma - |u P_j + c_j|_1
 //     RotatE           -                                           s_j = gamma - sum_k |h_k e^{i theta_jk} - t_k|
+//     QuatE            q = conj(h) (x) t, per column of the quarters  s_j = q . c^_j,  c^_j = the row normalised per quaternion
 // i.e. for six models the form the entity-ranking kernels already evaluate with the relation table in the place of the entity
 // table (kge_rank_gemm.hip, kge_neg_pair.hip / kge_neg_bcast.hip + kge_eval.hip; sequence in kge_api.hip).  This file holds what
 // they lack: rel_query_kernel (the per-pair query rows), rel_rotate_score_kernel (RotatE over relation phases) and rel_neg_rows_kernel
@@ -45,6 +46,23 @@ __global__ __launch_bounds__(KGE_BLOCK) void rel_query_kernel(RelQueryArgs a) {
 #pragma unroll
             for (int e = 0; e < V; ++e) o.v[e] = hv * tv.v[e];
             st<V>(q + (int64_t)r * D + b, o);
+        }
+    } else if constexpr (MODEL == KGE_QUATE) {
+        // q = conj(h) (x) t per column of the four quarters: <h (x) r^, t> = <conj(h) (x) t, r^>
+        float *q = a.Q + (int64_t)i * D;
+        const int qd = D / 4;
+        for (int off = lane * V; off < qd; off += KGE_WAVE * V) {
+            Pack<V> hq[4], tq[4], o[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) { hq[c] = ld<V>(h + c * qd + off); tq[c] = ld<V>(t + c * qd + off); }
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                const Quat g = quat_mul(quat_conj(Quat{hq[0].v[e], hq[1].v[e], hq[2].v[e], hq[3].v[e]}),
+                                        Quat{tq[0].v[e], tq[1].v[e], tq[2].v[e], tq[3].v[e]});
+                o[0].v[e] = g.a; o[1].v[e] = g.b; o[2].v[e] = g.c; o[3].v[e] = g.d;
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) st<V>(q + c * qd + off, o[c]);
         }
     } else if constexpr (MODEL == KGE_COMPLEX || MODEL == KGE_SIMPLE) {
         float *q = a.Q + (int64_t)i * D;
@@ -91,7 +109,7 @@ template <int MODEL>
 static int launch_rel_query_m(const RelQueryArgs &a, hipStream_t s) {
     const dim3 g((unsigned)((a.rows + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK)), b(KGE_BLOCK);
     const bool halves = MODEL == KGE_COMPLEX || MODEL == KGE_SIMPLE;
-    const bool vec = halves ? (a.d_e / 2) % 4 == 0 : a.d_e % 4 == 0;
+    const bool vec = MODEL == KGE_QUATE ? quate_vec(a.d_e) : halves ? (a.d_e / 2) % 4 == 0 : a.d_e % 4 == 0;
     if (vec) hipLaunchKernelGGL((rel_query_kernel<MODEL, 4>), g, b, 0, s, a);
     else hipLaunchKernelGGL((rel_query_kernel<MODEL, 1>), g, b, 0, s, a);
     return check_launch();
@@ -108,6 +126,7 @@ int launch_rel_query(int model, const float *ent, const int64_t *h, const int64_
         case KGE_SIMPLE: return launch_rel_query_m<KGE_SIMPLE>(a, s);
         case KGE_RESCAL: return launch_rel_query_m<KGE_RESCAL>(a, s);
         case KGE_TRANSR: return launch_rel_query_m<KGE_TRANSR>(a, s);
+        case KGE_QUATE: return launch_rel_query_m<KGE_QUATE>(a, s);
     }
     return KGE_ERR_ARG;
 }
@@ -225,5 +244,27 @@ int launch_rel_neg_rows(const float *rel, int64_t n_rel, int d_r, float *out, in
     const int64_t n = n_rel * d_r, m = n > n_ids ? n : n_ids;
     if (m <= 0) return KGE_OK;
     hipLaunchKernelGGL(rel_neg_rows_kernel, dim3((unsigned)((m + KGE_BLOCK - 1) / KGE_BLOCK)), dim3(KGE_BLOCK), 0, s, rel, n, out, ids, n_ids);
+    return check_launch();
+}
+
+// ---- QuatE ----------------------------------------------------------------------------------------------------------------------------
+// out = the relation table normalised per quaternion (quat_unit: the arithmetic of the edge kernels), the candidate table of the
+// (query row, relation row) product.  One thread per quaternion.
+__global__ __launch_bounds__(KGE_BLOCK) void rel_unit_rows_kernel(const float *__restrict__ rel, int64_t n_rel, int qd,
+                                                                  float *__restrict__ out) {
+    const int64_t k = (int64_t)blockIdx.x * KGE_BLOCK + threadIdx.x;
+    if (k >= n_rel * qd) return;
+    const int64_t o = (k / qd) * (4 * (int64_t)qd) + k % qd;
+    float n;
+    const Quat u = quat_unit(Quat{rel[o], rel[o + qd], rel[o + 2 * (int64_t)qd], rel[o + 3 * (int64_t)qd]}, n);
+    out[o] = u.a; out[o + qd] = u.b; out[o + 2 * (int64_t)qd] = u.c; out[o + 3 * (int64_t)qd] = u.d;
+}
+
+int launch_rel_unit_rows(const float *rel, int64_t n_rel, int d_r, float *out, hipStream_t s) {
+    const int qd = d_r / 4;
+    const int64_t n = n_rel * qd;
+    if (n <= 0) return KGE_OK;
+    if ((n + KGE_BLOCK - 1) / KGE_BLOCK > 0x7fffffff) return KGE_ERR_ARG;
+    hipLaunchKernelGGL(rel_unit_rows_kernel, dim3((unsigned)((n + KGE_BLOCK - 1) / KGE_BLOCK)), dim3(KGE_BLOCK), 0, s, rel, n_rel, qd, out);
     return check_launch();
 }

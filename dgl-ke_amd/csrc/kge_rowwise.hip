@@ -148,7 +148,7 @@ static int launch_edge_fwd_m(const EdgeFwdArgs &a, hipStream_t s) {
     if (!negjob) b.n_neg = 0;
     const int nb = blocks_for_waves(waves);
     const bool cx = is_complex_model(MODEL);
-    const bool vec = cx ? ((a.d_e / 2) % 4 == 0 && a.d_r % 4 == 0) : (a.d_e % 4 == 0);
+    const bool vec = MODEL == KGE_QUATE ? quate_vec(a.d_e) : cx ? ((a.d_e / 2) % 4 == 0 && a.d_r % 4 == 0) : (a.d_e % 4 == 0);
     const bool lean = vec && a.src.em.n == 0 && a.src.rm.n == 0 && a.lp.genre == KGE_LOSS_LOGSIGMOID && !a.row_pos && !a.Hc &&
                       !a.nd_own;
     if (lean)
@@ -169,6 +169,7 @@ int launch_edge_fwd(const EdgeFwdArgs &a, hipStream_t s) {
         case KGE_COMPLEX: return launch_edge_fwd_m<KGE_COMPLEX>(a, s);
         case KGE_ROTATE: return launch_edge_fwd_m<KGE_ROTATE>(a, s);
         case KGE_SIMPLE: return launch_edge_fwd_m<KGE_SIMPLE>(a, s);
+        case KGE_QUATE: return launch_edge_fwd_m<KGE_QUATE>(a, s);
     }
     return KGE_ERR_ARG;
 }
@@ -233,7 +234,69 @@ __device__ __forceinline__ void edge_bwd_body(const EdgeBwdArgs &a_in, int64_t w
     // neg_deg_sample: the in-batch negative row of this edge feeds the corrupted side (general_models.py:396-402)
     const float *gnd = a.GNd ? a.GNd + ((i / a.nd_chunk) * a.nd_Np + i % a.nd_chunk) * (int64_t)a.d_e : nullptr;
 
-    if constexpr (!is_complex_model(MODEL)) {
+    if constexpr (MODEL == KGE_QUATE) {
+        // QuatE (include/kge_hip.h): p = sum <h (x) r^, t> and L reaches the pos-side vector A through G = dL/dA.  Both are the same
+        // trilinear form: tail mode (A = h (x) r^) with t' = dp t + G, head mode (A = t (x) conj(r^)) with h' = dp h + G -
+        //   tail:  gh = t' (x) conj(r^),      gt = dp (h (x) r^),   g = dL/dr^ = conj(h) (x) t'
+        //   head:  gh = dp (t (x) conj(r^)),  gt = h' (x) r^,       g = conj(h') (x) t
+        // and dL/dr = (g - r^ <r^, g>) / n per quaternion (0 where n == 0), plus the regulariser of the raw row.
+        const int qd = a.d_e / 4;
+        const int nit = qd / V;
+        const float dp = dp_in;
+        for (int base = 0; base < nit; base += 64) {
+            const int off = min(base + lane, nit - 1) * V;
+            Pack<V> hq[4], rq[4], tq[4], gq[4], nq[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                hq[c] = ld<V>(h + c * qd + off); rq[c] = ld<V>(r + c * qd + off); tq[c] = ld<V>(t + c * qd + off);
+                gq[c] = ga ? ld_ga(ga + c * qd + off) : zero_pack<V>();
+                nq[c] = gnd ? ld<V>(gnd + c * qd + off) : zero_pack<V>();
+            }
+            if (base + lane >= nit) continue;
+            Pack<V> oh[4], ot[4], orr[4];
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                const Quat hh{hq[0].v[e], hq[1].v[e], hq[2].v[e], hq[3].v[e]};
+                const Quat tt{tq[0].v[e], tq[1].v[e], tq[2].v[e], tq[3].v[e]};
+                const Quat rw{rq[0].v[e], rq[1].v[e], rq[2].v[e], rq[3].v[e]};
+                const Quat gg{gq[0].v[e], gq[1].v[e], gq[2].v[e], gq[3].v[e]};
+                float nrm;
+                const Quat ru = quat_unit(rw, nrm);
+                Quat gh, gt, g;
+                if (a.neg_head) {
+                    const Quat hp{fmaf(dp, hh.a, gg.a), fmaf(dp, hh.b, gg.b), fmaf(dp, hh.c, gg.c), fmaf(dp, hh.d, gg.d)};
+                    const Quat tr = quat_mul(tt, quat_conj(ru));
+                    gh = Quat{dp * tr.a, dp * tr.b, dp * tr.c, dp * tr.d};
+                    gt = quat_mul(hp, ru);
+                    g = quat_mul(quat_conj(hp), tt);
+                } else {
+                    const Quat tp{fmaf(dp, tt.a, gg.a), fmaf(dp, tt.b, gg.b), fmaf(dp, tt.c, gg.c), fmaf(dp, tt.d, gg.d)};
+                    const Quat hr = quat_mul(hh, ru);
+                    gh = quat_mul(tp, quat_conj(ru));
+                    gt = Quat{dp * hr.a, dp * hr.b, dp * hr.c, dp * hr.d};
+                    g = quat_mul(quat_conj(hh), tp);
+                }
+                const float inv = nrm > 0.f ? 1.f / nrm : 0.f, pr = quat_dot(ru, g);
+                Quat gr{(g.a - ru.a * pr) * inv, (g.b - ru.b * pr) * inv, (g.c - ru.c * pr) * inv, (g.d - ru.d * pr) * inv};
+                if (reg) {
+                    gr.a += reg_grad(rw.a, a.reg_coef, a.reg_norm); gr.b += reg_grad(rw.b, a.reg_coef, a.reg_norm);
+                    gr.c += reg_grad(rw.c, a.reg_coef, a.reg_norm); gr.d += reg_grad(rw.d, a.reg_coef, a.reg_norm);
+                }
+                // neg_deg_sample: the in-batch negative row joins the corrupted side
+                if (a.neg_head) { gh.a += nq[0].v[e]; gh.b += nq[1].v[e]; gh.c += nq[2].v[e]; gh.d += nq[3].v[e]; }
+                else            { gt.a += nq[0].v[e]; gt.b += nq[1].v[e]; gt.c += nq[2].v[e]; gt.d += nq[3].v[e]; }
+                oh[0].v[e] = gh.a; oh[1].v[e] = gh.b; oh[2].v[e] = gh.c; oh[3].v[e] = gh.d;
+                ot[0].v[e] = gt.a; ot[1].v[e] = gt.b; ot[2].v[e] = gt.c; ot[3].v[e] = gt.d;
+                orr[0].v[e] = gr.a; orr[1].v[e] = gr.b; orr[2].v[e] = gr.c; orr[3].v[e] = gr.d;
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (GH) st_wt<V>(GH + c * qd + off, oh[c]);
+                if (GT) st_wt<V>(GT + c * qd + off, ot[c]);
+                if (GR) st_wt<V>(GR + c * qd + off, orr[c]);
+            }
+        }
+    } else if constexpr (!is_complex_model(MODEL)) {
         const int nit = a.d_e / V;
         const float dp = dp_in;
         float inv = 0.f;
@@ -434,7 +497,7 @@ static int launch_edge_bwd_gnred_m(const EdgeBwdArgs &a, const NegArgs &n, int n
     const int64_t n4 = (int64_t)n.C * n.N * n.d_e / 4;
     const int nbR = (int)((n4 + KGE_BLOCK - 1) / KGE_BLOCK);
     const bool cx = is_complex_model(MODEL);
-    const bool vec = cx ? ((a.d_e / 2) % 4 == 0 && a.d_r % 4 == 0) : (a.d_e % 4 == 0);
+    const bool vec = MODEL == KGE_QUATE ? quate_vec(a.d_e) : cx ? ((a.d_e / 2) % 4 == 0 && a.d_r % 4 == 0) : (a.d_e % 4 == 0);
     const bool local = a.src.em.n == 0 && a.src.rm.n == 0;
     if (!vec) return KGE_ERR_ARG;
     if (local) hipLaunchKernelGGL((edge_bwd_gnred_kernel<MODEL, 4, true>), dim3(nbE + nbR), dim3(KGE_BLOCK), 0, s, a, n, nrw, nbE);
@@ -454,7 +517,7 @@ int launch_edge_bwd_with_gn_reduce(const EdgeBwdArgs &a, const NegArgs &n, int n
 template <int MODEL>
 static int launch_edge_bwd_m(const EdgeBwdArgs &a, hipStream_t s) {
     const bool cx = is_complex_model(MODEL);
-    const bool vec = cx ? ((a.d_e / 2) % 4 == 0 && a.d_r % 4 == 0) : (a.d_e % 4 == 0);
+    const bool vec = MODEL == KGE_QUATE ? quate_vec(a.d_e) : cx ? ((a.d_e / 2) % 4 == 0 && a.d_r % 4 == 0) : (a.d_e % 4 == 0);
     const int nb = blocks_for_waves((int64_t)a.B * (vec ? edge_bwd_wpe(MODEL, 4, a.d_e) : 1));
     const bool local = a.src.em.n == 0 && a.src.rm.n == 0;
     if (vec && local)
@@ -475,6 +538,7 @@ int launch_edge_bwd(const EdgeBwdArgs &a, hipStream_t s) {
         case KGE_COMPLEX: return launch_edge_bwd_m<KGE_COMPLEX>(a, s);
         case KGE_ROTATE: return launch_edge_bwd_m<KGE_ROTATE>(a, s);
         case KGE_SIMPLE: return launch_edge_bwd_m<KGE_SIMPLE>(a, s);
+        case KGE_QUATE: return launch_edge_bwd_m<KGE_QUATE>(a, s);
     }
     return KGE_ERR_ARG;
 }

@@ -487,6 +487,7 @@ static int tk_check_model(int model, int d_e, int d_r) {
     if (model == KGE_RESCAL) ok = d_e <= 1024 && (int64_t)d_r == (int64_t)d_e * d_e;
     else if (model == KGE_COMPLEX || model == KGE_SIMPLE) ok = d_e % 2 == 0 && d_r == d_e;
     else if (model == KGE_ROTATE) ok = d_e % 2 == 0 && d_r == d_e / 2;
+    else if (model == KGE_QUATE) ok = d_e % 4 == 0 && d_r == d_e;
     else ok = d_r == d_e;
     if (ok) return KGE_OK;
     char msg[160];
@@ -509,7 +510,7 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
     char msg[256];
     if (filt_ptr && !filt_ids) return tk_fail("kge_topk_select_filtered: filt_ptr given without filt_ids");
     const bool sim = func >= KGE_SIM_COSINE && func <= KGE_SIM_EXT_JACCARD;
-    if (!sim && (func < KGE_TRANSE_L1 || func > KGE_RESCAL)) {
+    if (!sim && (func < KGE_TRANSE_L1 || (func > KGE_RESCAL && func != KGE_QUATE))) {
         snprintf(msg, sizeof(msg), "kge_topk_select: unknown score function %d (TransR has no inference path)", func);
         return tk_fail(msg);
     }

@@ -16,7 +16,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KGE_LIB") or os.path.join(_HERE, "libkge_hip.so")   # KGE_LIB: A/B builds
 
 KGE_ABI_VERSION = 8
-MODEL_IDS = {"TransE_l1": 0, "TransE_l2": 1, "TransE": 1, "DistMult": 2, "ComplEx": 3, "RotatE": 4, "SimplE": 5, "RESCAL": 6, "TransR": 7}
+MODEL_IDS = {"TransE_l1": 0, "TransE_l2": 1, "TransE": 1, "DistMult": 2, "ComplEx": 3, "RotatE": 4, "SimplE": 5, "RESCAL": 6, "TransR": 7,
+             "QuatE": 8}
 LOSS_IDS = {"Logsigmoid": 0, "Logistic": 1, "Hinge": 2, "BCE": 3, "Softmax": 4}
 FLAG_FORCE_PAIRWISE = 1
 FLAG_NO_TRANSE_FAST = 2
@@ -331,6 +332,19 @@ def graph_capture(g, stream=None):
     finally:
         if was:
             gc.enable()
+
+
+def rank_rel_workspace_bytes(model, Eb, n_rel, d_e, d_r):
+    """bytes of a kge_rank_rel_eval workspace.  kge_rank_rel_workspace_bytes answers for the ids up to TransR; a QuatE call takes
+    the DistMult layout followed by the normalised relation table [n_rel, d_r], 256-byte aligned (include/kge_hip.h).  0: bad
+    arguments."""
+    h = lib()
+    if model != MODEL_IDS["QuatE"]:
+        return h.kge_rank_rel_workspace_bytes(model, Eb, n_rel, d_e, d_r)
+    if d_e <= 0 or d_e % 4 or d_r != d_e:
+        return 0
+    base = h.kge_rank_rel_workspace_bytes(MODEL_IDS["DistMult"], Eb, n_rel, d_e, d_r)
+    return base + (n_rel * d_r * 4 + 255) // 256 * 256 if base else 0
 
 
 def model_id(name):

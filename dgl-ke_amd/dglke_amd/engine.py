@@ -30,6 +30,12 @@ class StepEngine(object):
         self.d_r = 2 * hidden_dim if double_relation_emb else hidden_dim
         if model_name == 'RESCAL':                          # relation row = [rel_dim x ent_dim] matrix, general_models.py:232-236
             self.d_r = self.d_r * self.d_e
+        if model_name == 'QuatE':                           # rows are four quarters [a | b | c | d] (include/kge_hip.h)
+            if self.d_e % 4 or self.d_r != self.d_e:
+                raise _lib.KgeError("QuatE needs an entity width that is a multiple of 4 and relation width == entity width "
+                                    "(got %d, %d)" % (self.d_e, self.d_r))
+            if shards is not None:
+                raise _lib.KgeError("QuatE runs the strict step on local tables only (no sharded tables)")
         hp = _lib.KgeHParams()
         hp.model = model_id(model_name)
         hp.d_e, hp.d_r = self.d_e, self.d_r

@@ -190,7 +190,7 @@ class Ranker(object):
         n_rel, d_e, d_r = int(self.rel.shape[0]), int(self.ent.shape[1]), int(self.rel.shape[1])
 
         def need_of(eb):
-            return _lib.lib().kge_rank_rel_workspace_bytes(self.model, eb, n_rel, d_e, d_r)
+            return _lib.rank_rel_workspace_bytes(self.model, eb, n_rel, d_e, d_r)
         Eb = max(1, min(self.batch, E))
         while Eb > 1 and need_of(Eb) > self.rel_ws_budget:
             Eb = (Eb + 1) // 2

@@ -21,7 +21,7 @@ class ArgParser(argparse.ArgumentParser):
         super(ArgParser, self).__init__()
         a = self.add_argument
         a('--model_name', default='TransE', choices=['TransE', 'TransE_l1', 'TransE_l2', 'TransR', 'RESCAL', 'DistMult',
-                                                     'ComplEx', 'RotatE', 'SimplE'])
+                                                     'ComplEx', 'RotatE', 'SimplE', 'QuatE'])
         a('--data_path', type=str, default='data')
         a('--dataset', type=str, default='FB15k')
         a('--format', type=str, default='built_in')
@@ -89,6 +89,11 @@ def main(argv=None):
         raise KgeError("--eval_relation is not available on sharded tables")
     if args.eval_relation and args.eval_candidates:
         raise KgeError("--eval_relation ranks against all relations: the lists of --eval_candidates are entity lists")
+    if args.model_name == 'QuatE':               # before anything is loaded
+        from .train import check_quate_widths
+        check_quate_widths(args.model_name, args.hidden_dim, args.double_ent, args.double_rel)
+        if len(args.gpu) > 1:
+            raise KgeError("QuatE is not available on sharded tables (--gpu takes one entry)")
     if args.gpu[0] < 0:
         raise KgeError("dglke_eval ranks on the GPU only: pass --gpu <id> (there is no CPU fallback)")
     if not os.path.isdir(args.model_path):

@@ -13,6 +13,8 @@ Deliberate differences from the reference:
   * equal scores are ordered by position - (head, relation, tail) or (left, right) - where the reference leaves them unordered;
   * a NaN score ranks below every number;
   * the device is a GPU (no CPU path), TransR is refused (as in the reference) and K is limited to 1 .. TOPK_MAX;
+  * the models: TransE_l1 / TransE_l2, DistMult, ComplEx, RotatE, RESCAL as in the reference, and SimplE and QuatE (rows of
+    four quaternion quarters, the relation normalised per quaternion: include/kge_hip.h), which the reference does not have;
   * ke_model: attach_graph takes the known triples (head, rel, tail) themselves (there is no DGLGraph here);
   * ke_model: exclude_mode 'exclude' is exact - known combinations are left out inside the selection kernel, where the
     reference takes the 4K best and falls back to a full sort when too few of them survive; results agree wherever

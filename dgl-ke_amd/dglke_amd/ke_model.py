@@ -13,7 +13,9 @@ The one signature difference: attach_graph takes the known triples - (head, rel,
 object with `.train` of that shape (kgdataset.KGDataset) - where the reference takes a DGLGraph; etid_field / ntid_filed
 are accepted and ignored.  The model classes score with the gamma they were constructed with under both sfunc values
 (ke_model.py:868-893); everything else follows infer.py's stated differences (ties by position, NaN last, K <= 128, GPU
-only, TransR refused, 'exclude' exact).  fit / save / eval are not supported, as in the reference."""
+only, TransR refused, 'exclude' exact).  fit / save / eval are not supported, as in the reference.  The classes: TransE, TransE_l1,
+TransE_l2, TransR (loads, refuses link_predict), DistMult, ComplEx, RotatE, RESCAL as in the reference, and SimplE and QuatE,
+which the reference does not have."""
 import json
 import os
 
@@ -198,6 +200,20 @@ class SimplEModel(KGEModel):
 
     def __init__(self, device):
         super(SimplEModel, self).__init__(device, 'SimplE')
+
+
+class QuatEModel(KGEModel):
+    """(not among the reference's classes) QuatE: rows are four quarters of quaternion components, the relation row as wide as
+    the entity row and normalised per quaternion inside the kernels (include/kge_hip.h, enum kge_model)"""
+
+    def __init__(self, device):
+        super(QuatEModel, self).__init__(device, 'QuatE')
+
+    def _after_load(self):
+        d = self._entity_emb.shape[1]
+        if d % 4 or self._relation_emb.shape[1] != d:
+            raise KgeError("QuatE: rows of %d (entity) and %d (relation) values: the width must be a multiple of 4 and the same "
+                           "for both" % (d, self._relation_emb.shape[1]))
 
 
 class RESCALModel(KGEModel):

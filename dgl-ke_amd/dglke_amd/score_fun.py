@@ -4,7 +4,8 @@
 
 Hand-written kernels, forward and analytic backward: TransE_l1 / TransE_l2 (score_fun.py:40), DistMult (:222),
 ComplEx (:289), RotatE (:451), SimplE (:556), RESCAL (:378); TransR (:110) per-op = library GEMM projections +
-the TransE_l1 kernels in relation space (its fast path is the fused step).
+the TransE_l1 kernels in relation space (its fast path is the fused step).  QuatE (not in the reference; include/kge_hip.h,
+enum kge_model) runs on the same per-op entries as ComplEx.
 """
 import torch as th
 
@@ -89,6 +90,12 @@ class DistMultScore(_HipScore):
 class ComplExScore(_HipScore):
     """score_fun.py:289-376"""
     model_name = 'ComplEx'
+
+
+class QuatEScore(_HipScore):
+    """QuatE (Zhang et al., NeurIPS 2019): rows are four quarters [a | b | c | d], one quaternion per column; the relation is
+    normalised per quaternion and score = sum <h (x) r^, t> (include/kge_hip.h, enum kge_model).  No gamma, no clamp."""
+    model_name = 'QuatE'
 
 
 class SimplEScore(_HipScore):

@@ -42,7 +42,7 @@ class ArgParser(argparse.ArgumentParser):
         super(ArgParser, self).__init__(prog="dglke_train")
         a = self.add_argument
         a('--model_name', default='TransE', choices=['TransE', 'TransE_l1', 'TransE_l2', 'TransR', 'RESCAL',
-                                                     'DistMult', 'ComplEx', 'RotatE', 'SimplE'])
+                                                     'DistMult', 'ComplEx', 'RotatE', 'SimplE', 'QuatE'])
         a('--data_path', type=str, default='data')
         a('--dataset', type=str, default='FB15k')
         a('--format', type=str, default='built_in')
@@ -791,11 +791,36 @@ def check_loss_flags(args):
         raise KgeError("--loss_genre Softmax cannot be combined with -pw")
 
 
+def check_quate_widths(model_name, hidden_dim, double_ent, double_rel):
+    """QuatE rows are four quarters of quaternion components and the relation row is as wide as the entity row"""
+    if model_name != 'QuatE':
+        return
+    width = hidden_dim * (2 if double_ent else 1)
+    if width % 4:
+        raise KgeError("QuatE: the entity width (--hidden_dim%s = %d) must be a multiple of 4 (four quarters [a | b | c | d])"
+                       % (" x 2 with -de" if double_ent else "", width))
+    if bool(double_rel) != bool(double_ent):
+        raise KgeError("QuatE: the relation width must equal the entity width: pass -dr together with -de (and neither alone)")
+
+
+def check_quate(args):
+    """QuatE trains on the strict step of one GPU's tables: refuse what has no such step, before anything is loaded"""
+    if args.model_name != 'QuatE':
+        return
+    check_quate_widths(args.model_name, args.hidden_dim, args.double_ent, args.double_rel)
+    if len(args.gpu) > 1:
+        raise KgeError("QuatE is not available on more than one GPU (--gpu takes one entry)")
+    if args.async_update_pipeline or args.async_update_rel:
+        raise KgeError("QuatE is not available in the one-step-stale pipeline (--async_update_pipeline / --async_update_rel); "
+                       "plain --async_update runs the strict step and is fine")
+
+
 def main(argv=None, before_train=None):
     """before_train (one GPU): called with the built Trainer in front of its first step - the tests take the initial tables there"""
     args = ArgParser().parse_args(argv)
     check_loss_flags(args)                       # before anything is loaded or created
     check_exclude_positive(args)                 # before anything is loaded or created
+    check_quate(args)                            # before anything is loaded or created
     if args.neg_deg_sample_eval:                 # before anything is loaded or created
         if len(args.gpu) > 1:
             raise KgeError("--neg_deg_sample_eval is not available on sharded tables")

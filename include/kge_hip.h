@@ -42,8 +42,21 @@ enum kge_model {
                           [d_e x d_r] (kge_tables.proj); fused step and ranking only (no modular autograd ops) */
     KGE_RESCAL    = 6, /* score_fun.py:378 RESCALScore: relation row = [d_e x d_e] matrix M (d_r = d_e*d_e),
                           p = h.(M t); BOTH corruption modes use the pos-side vector M x (:428-447) */
-    KGE_SIMPLE    = 5  /* score_fun.py:556 SimplEScore: rows = [x_i | x_j] halves, relation = [r | r_inv];
+    KGE_SIMPLE    = 5, /* score_fun.py:556 SimplEScore: rows = [x_i | x_j] halves, relation = [r | r_inv];
                           scores are clamped to [-20, 20] like the reference (:568, :622, :641) */
+    KGE_QUATE     = 8  /* QuatE (Zhang et al., NeurIPS 2019; not in the reference).  Rows are four quarters [a | b | c | d] of
+                          q = d_e / 4 columns each: column k of an entity row is the quaternion a_k + b_k i + c_k j + d_k k.
+                          d_e % 4 == 0, d_r == d_e.  The relation row is normalised per column: n_k = sqrt(ra^2 + rb^2 + rc^2 + rd^2),
+                          r^_k = r_k / n_k (sqrtf and a true division), r^_k = 0 where n_k == 0.  With h = (a, b, c, d) and
+                          r^ = (p, q, u, v) the Hamilton product h (x) r^ is
+                            (ap - bq - cu - dv,  aq + bp + cv - du,  au - bv + cp + dq,  av + bu - cq + dp)
+                          and s(h, r, t) = sum_k <(h (x) r^)_k, t_k> (4-component dot; no gamma, no clamp: gamma is ignored).
+                          Pos-side vectors: A = h (x) r^ (tails corrupted), A = t (x) conj(r^) (heads corrupted), since
+                          <h (x) r, t> = <h, t (x) conj(r)>; the chunked score is A . candidate.  Adjoint: ds/dt = h (x) r^,
+                          ds/dh = t (x) conj(r^), g = ds/dr^ = conj(h) (x) t, ds/dr = (g - r^ <r^, g>) / n per quaternion (0 where
+                          n == 0); gradients arriving through A chain the same way.  The regulariser acts on the raw rows.
+                          Relation ranking of a fixed pair: s_j = <conj(h) (x) t, r^_j>.  Strict step on local tables, ranking and
+                          top-K; kge_step_sharded, kge_step_grads, kge_step_async and kge_rank_eval_split refuse it. */
 };
 
 /* loss criteria (models/pytorch/loss.py:44-59) */
@@ -503,7 +516,13 @@ int kge_rank_eval_chunked(int model, int neg_head, const float *ent, int64_t n_e
  * One pass per Eb triples (Eb > E is taken as E); the ranks do not depend on Eb.  Workspace: kge_rank_rel_workspace_bytes(model, Eb,
  * n_rel, d_e, d_r) (0: bad arguments).  Errors before any launch: KGE_ERR_ARG for a null pointer, a bad model / width combination,
  * TransR without proj, n_rel > 0x7fffffff, Eb <= 0, a missing filter pointer; KGE_ERR_WORKSPACE for a workspace that is too small.
- * E == 0: KGE_OK without a launch. */
+ * E == 0: KGE_OK without a launch.
+ * KGE_QUATE: q = conj(h) (x) t and s_j = q . c^_j, c^_j the relation row normalised per quaternion; the call first writes the
+ * normalised table [n_rel, d_r] into its workspace and the dot-form kernels read that.  kge_rank_rel_workspace_bytes answers for
+ * the ids up to KGE_TRANSR only (0 for every other id, KGE_QUATE included); the workspace of a KGE_QUATE call is the
+ * KGE_DISTMULT layout followed by that table:
+ *   kge_rank_rel_workspace_bytes(KGE_DISTMULT, Eb, n_rel, d_e, d_r) + n_rel * d_r * sizeof(float) rounded up to 256 bytes
+ * (dglke_amd._lib.rank_rel_workspace_bytes). */
 size_t kge_rank_rel_workspace_bytes(int model, int Eb, int64_t n_rel, int d_e, int d_r);
 int kge_rank_rel_eval(int model, const float *ent, int64_t n_ent, const float *rel, int64_t n_rel, const float *proj,
                       const int64_t *h, const int64_t *r, const int64_t *t, int64_t E, int d_e, int d_r,
