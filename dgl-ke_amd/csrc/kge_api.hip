@@ -50,7 +50,13 @@ struct Carver {
 };
 
 int check_model(int model, int d_e, int d_r) {
-    if (model < KGE_TRANSE_L1 || (model > KGE_TRANSR && model != KGE_QUATE)) return fail(KGE_ERR_ARG, "unknown model %d", model);
+    if (model < KGE_TRANSE_L1 || (model > KGE_TRANSR && model != KGE_QUATE && model != KGE_PAIRRE))
+        return fail(KGE_ERR_ARG, "unknown model %d", model);
+    if (model == KGE_PAIRRE) {
+        if (d_e <= 0 || (int64_t)d_r != 2 * (int64_t)d_e)
+            return fail(KGE_ERR_ARG, "PairRE needs d_e > 0 and d_r == 2 * d_e, r = [rH | rT] (got %d, %d)", d_e, d_r);
+        return KGE_OK;
+    }
     if (model == KGE_QUATE) {
         if (d_e <= 0 || d_e % 4 || d_r != d_e)
             return fail(KGE_ERR_ARG, "QuatE needs d_e a positive multiple of 4 and d_r == d_e (got %d, %d)", d_e, d_r);
@@ -79,6 +85,11 @@ int check_model(int model, int d_e, int d_r) {
 
 // QuatE runs the strict step on local tables and single-table ranking; the other entries open with their own tests
 int no_quate(const char *who) { return fail(KGE_ERR_ARG, "%s: not available for QuatE (strict step on local tables, single-table ranking)", who); }
+
+// PairRE likewise, and it has no relation ranking (the score is not a product of a query row and the relation row)
+int no_pairre(const char *who) {
+    return fail(KGE_ERR_ARG, "%s: not available for PairRE (strict step on local tables, single-table entity ranking and top-K)", who);
+}
 
 inline float rot_div_of(float emb_init) { return (float)((double)emb_init / M_PI); }
 inline float clamp_of(int model) { return model == KGE_SIMPLE ? KGE_SIMPLE_CLAMP : 0.f; }
@@ -129,6 +140,23 @@ void fill_edge_bwd(EdgeBwdArgs &e, const EdgeSrc &src, int model, int B, int d_e
                    const float *dpos, const float *GA) {
     fill_edge(e, src, model, B, d_e, d_r, neg_head, gamma, rot_div);
     e.dpos = dpos; e.GA = GA;
+}
+
+// PairRE (kge_pairre.hip): the edge forward of B edges whose rows come from src, and the chunked scoring block
+void fill_pairre_edge(PairreEdgeArgs &e, const EdgeSrc &src, int B, int d_e, int neg_head, float gamma, float *P, float *A, float *W) {
+    e = PairreEdgeArgs{};
+    e.src = src; e.B = B; e.d_e = d_e; e.neg_head = neg_head; e.gamma = gamma; e.pos_score = P; e.A = A; e.W = W;
+}
+void fill_pairre_neg(PairreNegArgs &n, int C, int chunk, int N, int d_e, float gamma, const float *A, const float *W, const float *nbase,
+                     const int64_t *nidx, const float *nrm) {
+    n = PairreNegArgs{};
+    n.C = C; n.chunk = chunk; n.N = N; n.d_e = d_e; n.gamma = gamma; n.A = A; n.W = W; n.nbase = nbase; n.nidx = nidx; n.nrm = nrm;
+}
+// the norms of n candidate rows base + (idx ? idx[j] : j) * d_e
+int pairre_norms(const float *base, const int64_t *idx, int64_t n, int d_e, float *nrm, hipStream_t s) {
+    PairreEdgeArgs e{};
+    e.d_e = d_e; e.nbase = base; e.nidx = idx; e.n_neg = (int)n; e.nrm = nrm;
+    return launch_pairre_edge_fwd(e, s);
 }
 
 // SimplE, modular backward: no gradient through a saturated clamp
@@ -192,6 +220,11 @@ int kge_score_pos(int model, const float *h, const float *r, const float *t, int
         KGE_TRY(launch_rescal_matvec(m, (hipStream_t)stream));
         return KGE_OK;
     }
+    if (model == KGE_PAIRRE) {
+        PairreEdgeArgs e; fill_pairre_edge(e, EdgeSrc{h, nullptr, t, nullptr, r, nullptr}, (int)B, d_e, 0, gamma, out, nullptr, nullptr);
+        KGE_TRY(launch_pairre_edge_fwd(e, (hipStream_t)stream));
+        return KGE_OK;
+    }
     EdgeFwdArgs a;
     fill_edge(a, EdgeSrc{h, nullptr, t, nullptr, r, nullptr}, model, (int)B, d_e, d_r, 0, gamma, rot_div_of(emb_init));
     a.pos_score = out;
@@ -218,6 +251,12 @@ int kge_score_pos_bwd(int model, const float *h, const float *r, const float *t,
         KGE_TRY(launch_rescal_outer(o, s));
         return KGE_OK;
     }
+    if (model == KGE_PAIRRE) {
+        PairreBwdArgs e{};
+        e.src = EdgeSrc{h, nullptr, t, nullptr, r, nullptr}; e.B = (int)B; e.d_e = d_e; e.dpos = dpos; e.GH = gh; e.GT = gt; e.GR = gr;
+        KGE_TRY(launch_pairre_edge_bwd(e, (hipStream_t)stream));
+        return KGE_OK;
+    }
     EdgeBwdArgs a;
     fill_edge_bwd(a, EdgeSrc{h, nullptr, t, nullptr, r, nullptr}, model, (int)B, d_e, d_r, 0, gamma, rot_div_of(emb_init), dpos, nullptr);
     a.clamp_pos = 1; a.GH = gh; a.GT = gt; a.GR = gr;
@@ -226,7 +265,7 @@ int kge_score_pos_bwd(int model, const float *h, const float *r, const float *t,
 }
 
 // the workspace of the modular negative-score entry points (forward and backward share it)
-struct NegBufs { float *A, *asq, *bsq, *W, *GA, *GNp; };
+struct NegBufs { float *A, *asq, *bsq, *W, *GA, *GNp, *PW, *PGW, *Pnrm; };
 static size_t carve_neg(Carver &cv, NegBufs &w, int model, int C, int chunk, int N, int d_e) {
     const size_t B = (size_t)C * chunk;
     w.A = cv.f(B * d_e);                              // pos-side vectors
@@ -234,6 +273,8 @@ static size_t carve_neg(Carver &cv, NegBufs &w, int model, int C, int chunk, int
     w.W = cv.f(B * (size_t)N);                        // L2-scaled / clamp-masked dneg
     w.GA = cv.f(B * d_e);
     w.GNp = neg_bwd_lc_supported(model, d_e) ? cv.f(neg_bwd_lc_partial_floats(model, C, chunk, N, d_e)) : nullptr;
+    w.PW = w.PGW = w.Pnrm = nullptr;
+    if (model == KGE_PAIRRE) { w.PW = cv.f(B * d_e); w.PGW = cv.f(B * d_e); w.Pnrm = cv.f((size_t)C * N); }   // w, Gw, candidate norms
     return cv.off;
 }
 
@@ -249,6 +290,12 @@ static int neg_prepare(int model, int neg_head, const float *pos_side, const flo
         RescalMatvecArgs m{};
         m.B = B; m.D = d_e; m.rel = rel; m.y1 = pos_side; m.r1 = w.A;
         KGE_TRY(launch_rescal_matvec(m, s));
+        return KGE_OK;
+    }
+    if (model == KGE_PAIRRE) {         // (a, w) of every edge and the norm of every candidate row, one launch
+        PairreEdgeArgs e; fill_pairre_edge(e, EdgeSrc{pos_side, nullptr, pos_side, nullptr, rel, nullptr}, B, d_e, neg_head, gamma, nullptr, w.A, w.PW);
+        e.nbase = neg; e.n_neg = C * N; e.nrm = w.Pnrm;
+        KGE_TRY(launch_pairre_edge_fwd(e, s));
         return KGE_OK;
     }
     EdgeFwdArgs a;
@@ -271,7 +318,11 @@ int kge_score_neg_fwd(int model, int neg_head, const float *pos_side, const floa
     if (carve_neg(cv, w, model, C, chunk, N, d_e) > ws_bytes) return fail(KGE_ERR_WORKSPACE, "workspace too small");
     const bool mf = use_mfma(model, d_e, N, flags);
     if (int rc = neg_prepare(model, neg_head, pos_side, rel, neg, C, chunk, N, d_e, d_r, gamma, emb_init, mf && model == KGE_TRANSE_L2, w, s)) return rc;
-    if (mf) {
+    if (model == KGE_PAIRRE) {
+        PairreNegArgs n; fill_pairre_neg(n, C, chunk, N, d_e, gamma, w.A, w.PW, neg, nullptr, w.Pnrm);
+        n.S = out;
+        KGE_TRY(launch_pairre_neg_fwd(n, s));
+    } else if (mf) {
         GemmArgs g; fill_gemm(g, model, C, chunk, N, d_e, gamma, w.A, neg, nullptr);
         g.S = out; g.asq = w.asq; g.bsq = w.bsq;
         KGE_TRY(launch_neg_fwd_gemm(g, s));
@@ -299,6 +350,17 @@ int kge_score_neg_bwd(int model, int neg_head, const float *pos_side, const floa
     const size_t need = carve_neg(cv, w, model, C, chunk, N, d_e);
     if (need > ws_bytes) return fail(KGE_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
     if (int rc = neg_prepare(model, neg_head, pos_side, rel, neg, C, chunk, N, d_e, d_r, gamma, emb_init, false, w, s)) return rc;
+    if (model == KGE_PAIRRE) {
+        PairreNegArgs n; fill_pairre_neg(n, C, chunk, N, d_e, gamma, w.A, w.PW, neg, nullptr, w.Pnrm);
+        n.G = dneg; n.GA = w.GA; n.GW = w.PGW; n.GN = g_neg;
+        KGE_TRY(launch_pairre_neg_bwd(n, s));
+        PairreBwdArgs e{};
+        e.src = EdgeSrc{pos_side, nullptr, pos_side, nullptr, rel, nullptr}; e.B = B; e.d_e = d_e; e.neg_head = neg_head;
+        e.GA = w.GA; e.GW = w.PGW; e.GR = g_rel;
+        if (neg_head) e.GT = g_pos_side; else e.GH = g_pos_side;
+        KGE_TRY(launch_pairre_edge_bwd(e, s));
+        return KGE_OK;
+    }
     const float *Wuse = dneg;
     if (model == KGE_TRANSE_L2 || model == KGE_SIMPLE) {
         const int64_t n = (int64_t)B * N;
@@ -468,6 +530,7 @@ struct StepBufs {
     float *Xd; int64_t *iota, *ndids;                                               // RESCAL / TransR
     float *HP, *TP, *Q, *SG, *DQ, *TR1, *TR2, *GP, *gs0, *gs1, *k0, *k1, *TGNp, *gs1p; signed char *Z;   // TransR
     float *row_pos, *row_neg, *reg_ent, *reg_rel, *GNp, *Hc, *Tc, *Rc;
+    float *PW, *PGW, *Pnrm;                                                         // PairRE: w, Gw [B, d_e], candidate norms [C * N]
 };
 
 // Ns: the SAMPLED negatives per chunk (kge_batch.N).  copies: room for PREP's dense h / t / r rows (the async pipeline)
@@ -508,6 +571,7 @@ static size_t carve_step(Carver &cv, StepBufs &w, const kge_hparams *hp, int B_,
     if (neg_bwd_lc_supported(hp->model, hp->d_e))         // TransE_l1 / RotatE: GN partials of the shared-pair backward
         w.GNp = cv.f(neg_bwd_lc_partial_floats(hp->model, C, chunk, N, hp->d_e));
     if (copies) { w.Hc = cv.f(B * d_e); w.Tc = cv.f(B * d_e); w.Rc = cv.f(B * d_r); }
+    if (hp->model == KGE_PAIRRE) { w.PW = cv.f(B * d_e); w.PGW = cv.f(B * d_e); w.Pnrm = cv.f(CN); }
     return cv.off;
 }
 
@@ -827,6 +891,13 @@ int Step::phase_prep() {
     ef.dpos = w.dP; ef.row_pos = p.want4 ? w.row_pos : nullptr; ef.acc = acc;
     if (p.transr) return prep_transr();
     if (p.rescal) return prep_rescal();
+    if (hp->model == KGE_PAIRRE) {     // own edge forward: P, (a, w), the dense negative rows and their norms; the loss kernel takes the positive part
+        PairreEdgeArgs e; fill_pairre_edge(e, src, b->B, hp->d_e, b->neg_head, hp->gamma, P, w.A, w.PW);
+        e.nbase = ef.nbase; e.nidx = ef.nidx; e.n_neg = ef.n_neg; e.nd_own = ef.nd_own; e.nd_chunk = ef.nd_chunk; e.nd_Ns = ef.nd_Ns;
+        e.Bn = w.Bn; e.nrm = w.Pnrm;
+        KGE_TRY(launch_pairre_edge_fwd(e, s));
+        return KGE_OK;
+    }
     if (c.build_prep) { *c.build_prep = ef; return KGE_OK; }
     if (!p.merged_fwd && !p.merged_pair) KGE_TRY(launch_edge_fwd(ef, s));     // merged: launched together with the forward tiles
     return KGE_OK;
@@ -888,6 +959,10 @@ int Step::phase_fwd() {
             nf.xbase = tb->ent; nf.xidx = b->neg_head ? b->t_gid : b->h_gid; nf.rbase = tb->rel; nf.ridx = b->rel_ids;
             nf.asign = b->neg_head ? -1.f : 1.f;
             KGE_TRY(launch_neg_fwd_bcast_with_edge(nf, ef, s));
+        } else if (hp->model == KGE_PAIRRE) {
+            PairreNegArgs n; fill_pairre_neg(n, b->C, b->chunk, p.N, hp->d_e, hp->gamma, w.A, w.PW, w.Bn, nullptr, w.Pnrm);
+            n.S = w.S;
+            KGE_TRY(launch_pairre_neg_fwd(n, s));
         } else KGE_TRY(launch_neg_fwd_pair(na, s));
     }
     if (p.fused_loss || p.fold_loss) return KGE_OK;  // no stand-alone loss kernel: the backward GEMM / the forward tiles run it
@@ -895,7 +970,7 @@ int Step::phase_fwd() {
     LossArgs la; fill_step_loss(la);
     la.row_pos = p.want4 ? w.row_pos : nullptr;
     if (p.merged_fwd && p.is_l2) { la.l2_raw = 1; la.l2_chunk = b->chunk; la.asq = w.asq; la.bsq = w.bsq; }
-    la.skip_pos = (p.pos_row || p.rescal || p.transr) ? 0 : 1; la.diag_chunk = p.nd ? b->chunk : 0;  // RESCAL / TransR: no edge_fwd -> positive part here
+    la.skip_pos = (p.pos_row || p.rescal || p.transr || hp->model == KGE_PAIRRE) ? 0 : 1; la.diag_chunk = p.nd ? b->chunk : 0;  // RESCAL / TransR: no edge_fwd -> positive part here
     KGE_TRY(launch_loss(la, s, c.known ? c.known_mask : nullptr));
     return KGE_OK;
 }
@@ -994,6 +1069,19 @@ int Step::bwd_rescal() {
 
 int Step::phase_bwd() {
     if (p.transr) return bwd_transr();
+    if (hp->model == KGE_PAIRRE) {
+        PairreNegArgs n; fill_pairre_neg(n, b->C, b->chunk, p.N, hp->d_e, hp->gamma, w.A, w.PW, w.Bn, nullptr, w.Pnrm);
+        n.G = w.S; n.GA = w.GA; n.GW = w.PGW; n.GN = GN;
+        n.reg_coef = (p.reg && !p.nd) ? hp->reg_coef : 0.f; n.reg_norm = hp->reg_norm;   // nd: the update adds it (sampled rows only)
+        KGE_TRY(launch_pairre_neg_bwd(n, s));
+        PairreBwdArgs e{};
+        e.src = src; e.B = b->B; e.d_e = hp->d_e; e.neg_head = b->neg_head; e.dpos = w.dP; e.GA = w.GA; e.GW = w.PGW;
+        e.reg_coef = p.reg ? hp->reg_coef : 0.f; e.reg_norm = hp->reg_norm;
+        e.GH = w.GH; e.GT = w.GT; e.GR = GR;
+        if (p.nd) { e.GNd = GN; e.nd_chunk = b->chunk; e.nd_Np = p.N; }     // in-batch negative rows -> positive trace
+        KGE_TRY(launch_pairre_edge_bwd(e, s));
+        return KGE_OK;
+    }
     if (p.gemm) {
         if (int rc = bwd_neg_gemm()) return rc;
     } else {
@@ -1118,6 +1206,7 @@ size_t kge_sampler_tail_scratch_bytes(int B, int C, int N, int64_t n_ent) {
 static int step_sampling(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
                          size_t ws_bytes, const kge_sampler_job *job, StepCall c, void *stream) {
     if (!job) return run_step(hp, tb, b, out, ws, ws_bytes, stream, c);
+    if (hp && hp->model == KGE_PAIRRE) return no_pairre("kge_step_fused_sampling");
     if (!job->heads || !job->rels || !job->tails || !job->state || !job->slot || !job->scratch || job->n_train <= 0 || job->n_ent <= 0 ||
         job->B <= 0 || job->C <= 0 || job->chunk <= 0 || job->N <= 0 || job->C * job->chunk != job->B || job->k < 0 || job->advance < 0)
         return fail(KGE_ERR_ARG, "kge_step_fused_sampling: bad sampler job");
@@ -1184,6 +1273,7 @@ int kge_step_async(kge_pipe *p, const kge_hparams *hp, const kge_tables *tb, con
                    const kge_step_out *out, void *ws, size_t ws_bytes, void *stream) {
     if (!p || !hp || !tb || !b || !ws) return fail(KGE_ERR_ARG, "kge_step_async: null argument");
     if (hp->model == KGE_QUATE) return no_quate("kge_step_async");
+    if (hp->model == KGE_PAIRRE) return no_pairre("kge_step_async");
     const size_t half = (ws_bytes / 2) & ~(size_t)255;
     void *wsp = (char *)ws + (size_t)p->parity * half;
     void *wsn = (char *)ws + (size_t)(p->parity ^ 1) * half;
@@ -1275,6 +1365,7 @@ int kge_step_phase_known(const kge_hparams *hp, const kge_tables *tb, const kge_
 int kge_step_grads(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, const kge_emit *emit,
                    void *ws, size_t ws_bytes, void *stream) {
     if (hp && hp->model == KGE_QUATE) return no_quate("kge_step_grads");
+    if (hp && hp->model == KGE_PAIRRE) return no_pairre("kge_step_grads");
     if (!emit || !emit->g0 || (!emit->msg_rows && (!emit->gs0 || !emit->g1 || !emit->gs1)))
         return fail(KGE_ERR_ARG, "kge_step_grads: emit buffers g0/gs0/g1/gs1 are required (packed messages: g0 + msg_rows)");
     if ((emit->gr == nullptr) != (emit->gsr == nullptr))
@@ -1309,6 +1400,9 @@ static int rank_pos_side(int model, int neg_head, const float *ent, const float 
             if (!neg_head) { m.y2 = ent; m.y2idx = h; m.r2 = A; }
         }
         KGE_TRY(launch_rescal_matvec(m, s));
+    } else if (model == KGE_PAIRRE) {                   // the pair (a, w) lives in the A and RV entries
+        PairreEdgeArgs e; fill_pairre_edge(e, EdgeSrc{ent, h, ent, t, rel, r}, rows, d_e, neg_head, gamma, P, A, RV);
+        KGE_TRY(launch_pairre_edge_fwd(e, s));
     } else {
         EdgeFwdArgs ef;
         fill_edge(ef, EdgeSrc{ent, h, ent, t, rel, r}, model, rows, d_e, d_r, neg_head, gamma, rot_div);
@@ -1359,6 +1453,7 @@ static int rank_eval_impl(int model, int neg_head, const float *qent, const floa
         nb.bsq = bsq;
         KGE_TRY(launch_edge_fwd(nb, s));
     }
+    if (model == KGE_PAIRRE) KGE_TRY(pairre_norms(cent, cand, N, d_e, bsq, s));       // |x| of every candidate row, once (the bsq entry)
     for (int64_t e0 = 0; e0 < E; e0 += Eb) {
         const int rows = (int)((E - e0) < Eb ? (E - e0) : Eb);
         float *P = pos_score_out ? pos_score_out + e0 : w.P;
@@ -1382,6 +1477,10 @@ static int rank_eval_impl(int model, int neg_head, const float *qent, const floa
             GemmArgs g; fill_gemm(g, model, 1, rows, (int)N, d_e, gamma, A, cent, cand);
             g.S = S; g.asq = asq; g.bsq = bsq;
             KGE_TRY(launch_neg_fwd_gemm(g, s));
+        } else if (model == KGE_PAIRRE) {
+            PairreNegArgs n; fill_pairre_neg(n, 1, rows, (int)N, d_e, gamma, A, w.RV, cent, cand, bsq);
+            n.S = S;
+            KGE_TRY(launch_pairre_neg_fwd(n, s));
         } else {
             NegArgs na; fill_pair(na, model, 1, rows, (int)N, d_e, gamma, A, cent, cand);
             na.S = S;
@@ -1424,6 +1523,7 @@ int kge_rank_eval_split(int model, int neg_head, const float *qent, int64_t n_qe
                         int Eb, int32_t *ranks, float *pos_score_out, void *ws, size_t ws_bytes, unsigned flags, void *stream) {
     if (int rc = check_model(model, d_e, d_r)) return rc;
     if (model == KGE_QUATE) return no_quate("kge_rank_eval_split");
+    if (model == KGE_PAIRRE) return no_pairre("kge_rank_eval_split");
     if (model == KGE_TRANSR && !proj)
         return fail(KGE_ERR_ARG, "kge_rank_eval_split: TransR needs the projection table");
     if (n_qent <= 0 || n_cent < 0) return fail(KGE_ERR_ARG, "kge_rank_eval_split: bad argument");
@@ -1445,16 +1545,17 @@ int kge_rank_eval_split(int model, int neg_head, const float *qent, int64_t n_qe
 // ---- chunked-candidate ranking (kge_rank_chunk.hip) ----
 // one block of whole chunks: pos-side vectors / norms / positive scores of its rows, the candidates' norms (TransE_l2), and - for the
 // score-block route only, but the layout does not depend on the flags - the id list and the score block
-struct ChunkBufs : TransRRows { float *A, *asq, *P, *RV, *bsq_own, *bsq_c, *S; int64_t *ids; };
+struct ChunkBufs : TransRRows { float *A, *asq, *P, *RV, *bsq_own, *bsq_c, *S, *Pnrm; int64_t *ids; };
 static size_t carve_chunked(Carver &cv, ChunkBufs &w, int model, int64_t rows, int chunk, int64_t n_cand, int self_cand, int d_e, int d_r) {
     const size_t nch = (size_t)((rows + chunk - 1) / chunk), R = nch * (size_t)chunk;
     const size_t ncols = (size_t)n_cand + (self_cand ? (size_t)chunk : 0);
     w.A = cv.f(R * d_e); w.asq = cv.f(R); w.P = cv.f(R);
-    w.RV = cv.f(model == KGE_RESCAL ? R * d_e : 0);                    // V = M t (RESCAL)
+    w.RV = cv.f(model == KGE_RESCAL || model == KGE_PAIRRE ? R * d_e : 0);      // V = M t (RESCAL); w of the pair (PairRE)
     carve_transr_rows(cv, w, model == KGE_TRANSR ? R * (size_t)d_r : 0);
     w.bsq_own = cv.f(R); w.bsq_c = cv.f(nch * (size_t)n_cand);
     w.ids = cv.i64(nch * ncols);
     w.S = cv.f(R * ncols);
+    w.Pnrm = model == KGE_PAIRRE ? cv.f(nch * ncols) : nullptr;        // PairRE: |x| per position of the id lists
     return cv.off;
 }
 
@@ -1547,6 +1648,12 @@ int kge_rank_eval_chunked(int model, int neg_head, const float *ent, int64_t n_e
                 tr.P = P + row_off; tr.S = S; tr.Z = nullptr;
                 KGE_TRY(launch_transr_pos(tr, s));
                 KGE_TRY(launch_transr_fwd(tr, s));
+            } else if (model == KGE_PAIRRE) {
+                float *nrm = w.Pnrm + (gidx == 0 ? 0 : (int64_t)nfull * ncols_full);
+                KGE_TRY(pairre_norms(ent, ids, (int64_t)C * ncols, d_e, nrm, s));
+                PairreNegArgs n; fill_pairre_neg(n, C, m, (int)ncols, d_e, gamma, w.A + row_off * d_e, w.RV + row_off * d_e, ent, ids, nrm);
+                n.S = S;
+                KGE_TRY(launch_pairre_neg_fwd(n, s));
             } else {
                 NegArgs na; fill_pair(na, model, C, m, (int)ncols, d_e, gamma, w.A + row_off * d_e, ent, ids);
                 na.S = S;
@@ -1576,7 +1683,7 @@ static size_t carve_rank_rel(Carver &cv, RelBufs &w, int model, int Eb, int64_t 
 size_t kge_rank_rel_workspace_bytes(int model, int Eb, int64_t n_rel, int d_e, int d_r) {
     if (Eb <= 0 || n_rel <= 0 || n_rel > 0x7fffffff || check_model(model, d_e, d_r) != KGE_OK) return 0;
     // ids up to KGE_TRANSR only: a QuatE call takes the DistMult layout followed by the normalised relation table (include/kge_hip.h)
-    if (model == KGE_QUATE) return 0;
+    if (model == KGE_QUATE || model == KGE_PAIRRE) return 0;
     Carver cv; RelBufs w; return carve_rank_rel(cv, w, model, Eb, n_rel, d_e, d_r);
 }
 
@@ -1585,6 +1692,7 @@ int kge_rank_rel_eval(int model, const float *ent, int64_t n_ent, const float *r
                       float gamma, float emb_init, const int64_t *filt_ptr, const int64_t *filt_ids, int Eb,
                       int32_t *ranks, float *pos_score_out, void *ws, size_t ws_bytes, unsigned flags, void *stream) {
     if (int rc = check_model(model, d_e, d_r)) return rc;
+    if (model == KGE_PAIRRE) return no_pairre("kge_rank_rel_eval");
     if (model == KGE_TRANSR && !proj) return fail(KGE_ERR_ARG, "kge_rank_rel_eval: TransR needs the projection table");
     if (!ent || !rel || n_ent <= 0 || n_rel <= 0 || E < 0 || (E && (!h || !r || !t || !ranks)) || !ws)
         return fail(KGE_ERR_ARG, "kge_rank_rel_eval: bad argument (a null pointer or a count that is not positive)");
@@ -1661,6 +1769,7 @@ int kge_step_sharded(const kge_hparams *hp, const kge_shards *sh, const kge_batc
                      const kge_step_out *out, void *ws, size_t ws_bytes, void *stream) {
     if (!sh) return fail(KGE_ERR_ARG, "kge_step_sharded: null shard map");
     if (hp && hp->model == KGE_QUATE) return no_quate("kge_step_sharded");
+    if (hp && hp->model == KGE_PAIRRE) return no_pairre("kge_step_sharded");
     // (RESCAL's relation "row" is a d_e x d_e matrix streamed by its own kernels: only the entity width is bounded)
     if (hp && (hp->d_e % 4 || hp->d_e > 1024 || (hp->model != KGE_RESCAL && (hp->d_r % 4 || hp->d_r > 1024))))
         return fail(KGE_ERR_ARG, "kge_step_sharded: row widths must be multiples of 4 and <= 1024 floats");

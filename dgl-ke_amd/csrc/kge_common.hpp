@@ -684,6 +684,42 @@ int launch_neg_fwd_gemm_with_edge_loss(const GemmArgs &a, const EdgeFwdArgs &e, 
 int launch_neg_bwd_gemm_with_prep(const GemmArgs &a, const EdgeFwdArgs &e, hipStream_t s);
 int launch_neg_fwd_pair(const NegArgs &a, hipStream_t s);
 int launch_neg_bwd_pair(const NegArgs &a, hipStream_t s);
+// ---- PairRE (kge_pairre.hip): local tables only ----
+struct PairreEdgeArgs {              // edge forward + candidate-row jobs of the same launch
+    EdgeSrc src;                     // relation rows are 2 * d_e wide: [rH | rT]
+    int B, d_e, neg_head;
+    float gamma;
+    float *pos_score;                // [B] or null
+    float *A, *W;                    // [B,d_e] the per-edge pair (a, w), or null
+    const float *nbase; const int64_t *nidx; int n_neg;   // candidate rows -> nrm (and Bn)
+    const int64_t *nd_own; int nd_chunk, nd_Ns;           // neg_deg_sample id scheme (EdgeFwdArgs)
+    float *Bn;                       // [n_neg,d_e] dense copy of the candidate rows or null
+    float *nrm;                      // [n_neg] |x|_2 of every candidate row or null
+};
+struct PairreNegArgs {               // chunked scores s_ij = gamma - sum_k |a_ik - w_ik n^_jk| and their adjoint
+    int C, chunk, N, d_e;
+    float gamma;
+    const float *A, *W;              // [C*chunk,d_e]
+    const float *nbase; const int64_t *nidx;   // candidate rows nbase + (nidx ? nidx[j] : j) * d_e
+    const float *nrm;                // [C*N] their norms
+    float *S;                        // fwd: out [C,chunk,N]
+    const float *G;                  // bwd: dL/ds [C,chunk,N]
+    float *GA, *GW;                  // bwd out [C*chunk,d_e]
+    float *GN;                       // bwd out [C*N,d_e]: gradient of the RAW candidate row occurrence (+ regulariser)
+    float reg_coef; int reg_norm;
+};
+struct PairreBwdArgs {               // per-edge gradients of the head, tail and relation rows
+    EdgeSrc src;
+    int B, d_e, neg_head;
+    const float *dpos, *GA, *GW;     // [B], [B,d_e] x 2; dpos or (GA, GW) may be null
+    float reg_coef; int reg_norm;    // regulariser gradient of the relation row
+    float *GH, *GT, *GR;             // [B,d_e], [B,d_e], [B,2 d_e]; any may be null
+    const float *GNd; int nd_chunk, nd_Np;     // neg_deg_sample (EdgeBwdArgs)
+};
+int launch_pairre_edge_fwd(const PairreEdgeArgs &a, hipStream_t s);
+int launch_pairre_neg_fwd(const PairreNegArgs &a, hipStream_t s);
+int launch_pairre_neg_bwd(const PairreNegArgs &a, hipStream_t s);
+int launch_pairre_edge_bwd(const PairreBwdArgs &a, hipStream_t s);
 // ---- RESCAL (kge_rescal.hip) ----
 struct RescalMatvecArgs {            // one pass over M_i = rel + (ridx ? ridx[i] : i) * D*Dc per edge i
     int B, D;                        // D rows; Dc columns (0: square).  y vectors have Dc entries, z / pd vectors D

@@ -29,7 +29,9 @@ using namespace kge;
 #define TK_MCAP 2048                              // entries of one merge workgroup
 
 // accumulator kinds (template) and epilogues (runtime)
-enum { ACC_MFMA = 0, ACC_DOT = 1, ACC_SQ = 2, ACC_L1 = 3, ACC_ROT = 4 };
+enum { ACC_MFMA = 0, ACC_DOT = 1, ACC_SQ = 2, ACC_L1 = 3, ACC_ROT = 4, ACC_PRE = 5 };
+// ACC_PRE (PairRE, include/kge_hip.h): query row i is the pair (a_i, w_i) - abase holds the rows' a block followed by their w block,
+// [rows, D] each - and bn the candidates' norms |x_j|_2: the tile accumulates |a_ik - w_ik x_jk / |x_j||
 enum { EPI_RAW = 0, EPI_L2G = 1, EPI_COS = 2, EPI_JAC = 3, EPI_GMINUS = 4, EPI_GSQRT = 5 };
 
 struct TopkSelArgs {
@@ -149,11 +151,33 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
                     const float v = p[col];
                     g[i] = ok ? v : 0.f;
                 }
+                [[maybe_unused]] float gw[16];
+                if constexpr (ACC == ACC_PRE) {
+                    // the candidate half of the slab normalised (x / |x|, 0 where |x| == 0), and the rows' w slab for the second buffer
+#pragma unroll
+                    for (int i = 16; i < 32; ++i) {
+                        const float nj = a.bn[min(bn * TILE_BN + ((tid + 256 * i) >> 5) - TILE_BM, a.N - 1)];
+                        g[i] = nj > 0.f ? g[i] / nj : 0.f;
+                    }
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const int f = tid + 256 * i, row = f >> 5, k = s * TILE_BK + (f & 31);
+                        const float v = a.abase[((int64_t)a.rows + min(r0 + row, a.rows - 1)) * D + min(k, D - 1)];
+                        gw[i] = k < D ? v : 0.f;
+                    }
+                }
                 __syncthreads();
 #pragma unroll
                 for (int i = 0; i < 32; ++i) {
                     const int f = tid + 256 * i;
                     lds[0][(f >> 5) * TILE_LD + (f & 31)] = g[i];
+                }
+                if constexpr (ACC == ACC_PRE) {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const int f = tid + 256 * i;
+                        lds[1][(f >> 5) * TILE_LD + (f & 31)] = gw[i];
+                    }
                 }
                 __syncthreads();
                 if constexpr (ACC == ACC_ROT) {
@@ -174,6 +198,11 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
                 } else {
                     for (int k = 0; k < TILE_BK; ++k) {
                         float av[8], bv[8];
+                        [[maybe_unused]] float wv[8];
+                        if constexpr (ACC == ACC_PRE) {
+#pragma unroll
+                            for (int i = 0; i < 8; ++i) wv[i] = lds[1][(ty + 16 * i) * TILE_LD + k];
+                        }
 #pragma unroll
                         for (int i = 0; i < 8; ++i) av[i] = lds[0][(ty + 16 * i) * TILE_LD + k];
 #pragma unroll
@@ -184,6 +213,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
                             for (int j = 0; j < 8; ++j) {
                                 if constexpr (ACC == ACC_DOT) acc[i][j] = fmaf(av[i], bv[j], acc[i][j]);
                                 else if constexpr (ACC == ACC_SQ) { const float d = av[i] - bv[j]; acc[i][j] = fmaf(d, d, acc[i][j]); }
+                                else if constexpr (ACC == ACC_PRE) acc[i][j] += fabsf(fmaf(-wv[i], bv[j], av[i]));
                                 else acc[i][j] += fabsf(av[i] - bv[j]);
                             }
                     }
@@ -488,6 +518,7 @@ static int tk_check_model(int model, int d_e, int d_r) {
     else if (model == KGE_COMPLEX || model == KGE_SIMPLE) ok = d_e % 2 == 0 && d_r == d_e;
     else if (model == KGE_ROTATE) ok = d_e % 2 == 0 && d_r == d_e / 2;
     else if (model == KGE_QUATE) ok = d_e % 4 == 0 && d_r == d_e;
+    else if (model == KGE_PAIRRE) ok = (int64_t)d_r == 2 * (int64_t)d_e;
     else ok = d_r == d_e;
     if (ok) return KGE_OK;
     char msg[160];
@@ -510,7 +541,7 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
     char msg[256];
     if (filt_ptr && !filt_ids) return tk_fail("kge_topk_select_filtered: filt_ptr given without filt_ids");
     const bool sim = func >= KGE_SIM_COSINE && func <= KGE_SIM_EXT_JACCARD;
-    if (!sim && (func < KGE_TRANSE_L1 || (func > KGE_RESCAL && func != KGE_QUATE))) {
+    if (!sim && (func < KGE_TRANSE_L1 || (func > KGE_RESCAL && func != KGE_QUATE && func != KGE_PAIRRE))) {
         snprintf(msg, sizeof(msg), "kge_topk_select: unknown score function %d (TransR has no inference path)", func);
         return tk_fail(msg);
     }
@@ -525,7 +556,8 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
     if (rows == 0 || n_cand == 0) return KGE_OK;
     const int64_t N = n_cand;
     const int D = d_e;
-    TkWs w = carve(ws, rows, N, D, K);
+    // PairRE keeps two vectors per query row: the A entry is [a block | w block] (include/kge_hip.h)
+    TkWs w = carve(ws, rows, N, func == KGE_PAIRRE ? 2 * D : D, K);
     if (w.need > ws_bytes) {
         snprintf(msg, sizeof(msg), "kge_topk_select: workspace too small (%zu < %zu)", ws_bytes, w.need);
         return kge_fail(KGE_ERR_WORKSPACE, msg);
@@ -551,6 +583,12 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
             if (side) { m.y1 = ent; m.y1idx = t; m.r1 = w.A; }
             else { m.z1 = ent; m.z1idx = h; m.c1 = w.A; }
             if (int rc = launch_rescal_matvec(m, st)) return rc;
+        } else if (func == KGE_PAIRRE) {
+            PairreEdgeArgs e{};
+            e.src = EdgeSrc{ent, h, ent, t, rel, r};
+            e.B = rows; e.d_e = d_e; e.neg_head = side; e.gamma = gamma; e.A = w.A; e.W = w.A + (size_t)rows * D;
+            e.nbase = ent; e.nidx = cand; e.n_neg = (int)N; e.nrm = w.bn;
+            if (int rc = launch_pairre_edge_fwd(e, st)) return rc;
         } else {
             EdgeFwdArgs ef{};
             ef.src = EdgeSrc{ent, h, ent, t, rel, r};
@@ -560,6 +598,7 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
             if (int rc = launch_edge_fwd(ef, st)) return rc;
         }
         if (func == KGE_TRANSE_L1) { acc = ACC_L1; epi = EPI_GMINUS; }
+        else if (func == KGE_PAIRRE) { acc = ACC_PRE; epi = EPI_GMINUS; }
         else if (func == KGE_ROTATE) { acc = ACC_ROT; epi = EPI_GMINUS; }
         else if (func == KGE_TRANSE_L2) { acc = mf ? ACC_MFMA : ACC_SQ; epi = mf ? EPI_L2G : EPI_GSQRT; }
         else { acc = mf ? ACC_MFMA : ACC_DOT; epi = EPI_RAW; }
@@ -587,6 +626,7 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
         case ACC_DOT: hipLaunchKernelGGL((topk_select_kernel<ACC_DOT, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
         case ACC_SQ: hipLaunchKernelGGL((topk_select_kernel<ACC_SQ, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
         case ACC_L1: hipLaunchKernelGGL((topk_select_kernel<ACC_L1, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
+        case ACC_PRE: hipLaunchKernelGGL((topk_select_kernel<ACC_PRE, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
         default: hipLaunchKernelGGL((topk_select_kernel<ACC_ROT, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
         }
     } else
@@ -595,6 +635,7 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
     case ACC_DOT: hipLaunchKernelGGL(topk_select_kernel<ACC_DOT>, grid, dim3(256), 0, st, a); break;
     case ACC_SQ: hipLaunchKernelGGL(topk_select_kernel<ACC_SQ>, grid, dim3(256), 0, st, a); break;
     case ACC_L1: hipLaunchKernelGGL(topk_select_kernel<ACC_L1>, grid, dim3(256), 0, st, a); break;
+    case ACC_PRE: hipLaunchKernelGGL(topk_select_kernel<ACC_PRE>, grid, dim3(256), 0, st, a); break;
     default: hipLaunchKernelGGL(topk_select_kernel<ACC_ROT>, grid, dim3(256), 0, st, a); break;
     }
     if (int rc = check_launch()) return rc;

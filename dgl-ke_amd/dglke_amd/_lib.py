@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("KGE_LIB") or os.path.join(_HERE, "libkge_hip.so")   #
 
 KGE_ABI_VERSION = 8
 MODEL_IDS = {"TransE_l1": 0, "TransE_l2": 1, "TransE": 1, "DistMult": 2, "ComplEx": 3, "RotatE": 4, "SimplE": 5, "RESCAL": 6, "TransR": 7,
-             "QuatE": 8}
+             "QuatE": 8, "PairRE": 10}      # (9 is not a model)
 LOSS_IDS = {"Logsigmoid": 0, "Logistic": 1, "Hinge": 2, "BCE": 3, "Softmax": 4}
 FLAG_FORCE_PAIRWISE = 1
 FLAG_NO_TRANSE_FAST = 2
@@ -345,6 +345,12 @@ def rank_rel_workspace_bytes(model, Eb, n_rel, d_e, d_r):
         return 0
     base = h.kge_rank_rel_workspace_bytes(MODEL_IDS["DistMult"], Eb, n_rel, d_e, d_r)
     return base + (n_rel * d_r * 4 + 255) // 256 * 256 if base else 0
+
+
+def topk_workspace_bytes(model, rows, n_cand, d_e, K):
+    """bytes of a kge_topk_select / _filtered workspace.  kge_topk_workspace_bytes has no model argument; a PairRE call keeps two
+    vectors per query row, the pair (a, w), in the A entry: the size is the one of rows 2 * d_e wide (include/kge_hip.h)"""
+    return lib().kge_topk_workspace_bytes(rows, n_cand, 2 * d_e if model == MODEL_IDS["PairRE"] else d_e, K)
 
 
 def model_id(name):

@@ -36,6 +36,11 @@ class StepEngine(object):
                                     "(got %d, %d)" % (self.d_e, self.d_r))
             if shards is not None:
                 raise _lib.KgeError("QuatE runs the strict step on local tables only (no sharded tables)")
+        if model_name == 'PairRE':                          # relation rows [rH | rT] (include/kge_hip.h)
+            if self.d_r != 2 * self.d_e:
+                raise _lib.KgeError("PairRE needs relation width == 2 * entity width (-dr without -de; got %d, %d)" % (self.d_e, self.d_r))
+            if shards is not None:
+                raise _lib.KgeError("PairRE runs the strict step on local tables only (no sharded tables)")
         hp = _lib.KgeHParams()
         hp.model = model_id(model_name)
         hp.d_e, hp.d_r = self.d_e, self.d_r

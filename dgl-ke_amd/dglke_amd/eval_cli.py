@@ -21,7 +21,7 @@ class ArgParser(argparse.ArgumentParser):
         super(ArgParser, self).__init__()
         a = self.add_argument
         a('--model_name', default='TransE', choices=['TransE', 'TransE_l1', 'TransE_l2', 'TransR', 'RESCAL', 'DistMult',
-                                                     'ComplEx', 'RotatE', 'SimplE', 'QuatE'])
+                                                     'ComplEx', 'RotatE', 'SimplE', 'QuatE', 'PairRE'])
         a('--data_path', type=str, default='data')
         a('--dataset', type=str, default='FB15k')
         a('--format', type=str, default='built_in')
@@ -94,6 +94,13 @@ def main(argv=None):
         check_quate_widths(args.model_name, args.hidden_dim, args.double_ent, args.double_rel)
         if len(args.gpu) > 1:
             raise KgeError("QuatE is not available on sharded tables (--gpu takes one entry)")
+    if args.model_name == 'PairRE':              # before anything is loaded
+        from .train import check_pairre_widths
+        check_pairre_widths(args.model_name, args.double_ent, args.double_rel)
+        if len(args.gpu) > 1:
+            raise KgeError("PairRE is not available on sharded tables (--gpu takes one entry)")
+        if args.eval_relation:
+            raise KgeError("PairRE has no relation ranking (--eval_relation): the score is not a product with the relation row")
     if args.gpu[0] < 0:
         raise KgeError("dglke_eval ranks on the GPU only: pass --gpu <id> (there is no CPU fallback)")
     if not os.path.isdir(args.model_path):

@@ -13,8 +13,9 @@ Deliberate differences from the reference:
   * equal scores are ordered by position - (head, relation, tail) or (left, right) - where the reference leaves them unordered;
   * a NaN score ranks below every number;
   * the device is a GPU (no CPU path), TransR is refused (as in the reference) and K is limited to 1 .. TOPK_MAX;
-  * the models: TransE_l1 / TransE_l2, DistMult, ComplEx, RotatE, RESCAL as in the reference, and SimplE and QuatE (rows of
-    four quaternion quarters, the relation normalised per quaternion: include/kge_hip.h), which the reference does not have;
+  * the models: TransE_l1 / TransE_l2, DistMult, ComplEx, RotatE, RESCAL as in the reference, and SimplE, QuatE (rows of
+    four quaternion quarters, the relation normalised per quaternion: include/kge_hip.h) and PairRE (relation rows [rH | rT] on
+    unit-normalised entity rows), which the reference does not have;
   * ke_model: attach_graph takes the known triples (head, rel, tail) themselves (there is no DGLGraph here);
   * ke_model: exclude_mode 'exclude' is exact - known combinations are left out inside the selection kernel, where the
     reference takes the 4K best and falls back to a full sort when too few of them survive; results agree wherever
@@ -117,10 +118,11 @@ def select_groups(func, side, ent, rel, d_e, d_r, gamma, emb_init, cand, n_rows,
     N = cand.numel()
     if n_rows == 0 or N == 0:
         return res_s, res_o
+    d_ws = 2 * d_e if func == _lib.MODEL_IDS['PairRE'] else d_e         # PairRE keeps the pair (a, w) per query row (include/kge_hip.h)
     if max_rows is None:
-        max_rows = rows_in_flight(N, d_e, k)
+        max_rows = rows_in_flight(N, d_ws, k)
     per = (max_rows // group_rows) * group_rows if group_rows <= max_rows else max_rows
-    ws = _workspace(h.kge_topk_workspace_bytes(min(per, n_rows), N, d_e, k), dev)
+    ws = _workspace(_lib.topk_workspace_bytes(func, min(per, n_rows), N, d_e, k), dev)
     relp = _lib.ptr(rel) if rel is not None else None
     n_rel = rel.shape[0] if rel is not None else 0
     r0 = 0

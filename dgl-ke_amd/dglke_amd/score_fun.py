@@ -5,7 +5,8 @@
 Hand-written kernels, forward and analytic backward: TransE_l1 / TransE_l2 (score_fun.py:40), DistMult (:222),
 ComplEx (:289), RotatE (:451), SimplE (:556), RESCAL (:378); TransR (:110) per-op = library GEMM projections +
 the TransE_l1 kernels in relation space (its fast path is the fused step).  QuatE (not in the reference; include/kge_hip.h,
-enum kge_model) runs on the same per-op entries as ComplEx.
+enum kge_model) runs on the same per-op entries as ComplEx; PairRE (likewise not in the reference) on the same entries with
+kernels of its own (kge_pairre.hip).
 """
 import torch as th
 
@@ -96,6 +97,15 @@ class QuatEScore(_HipScore):
     """QuatE (Zhang et al., NeurIPS 2019): rows are four quarters [a | b | c | d], one quaternion per column; the relation is
     normalised per quaternion and score = sum <h (x) r^, t> (include/kge_hip.h, enum kge_model).  No gamma, no clamp."""
     model_name = 'QuatE'
+
+
+class PairREScore(_HipScore):
+    """PairRE (Chao et al., ACL 2021): relation rows [rH | rT], twice the entity width; the entity rows are normalised to unit
+    length inside the kernels and score = gamma - |h^ o rH - t^ o rT|_1 (include/kge_hip.h, enum kge_model).  No clamp."""
+    model_name = 'PairRE'
+
+    def __init__(self, gamma):
+        self.gamma = gamma
 
 
 class SimplEScore(_HipScore):

@@ -42,7 +42,7 @@ class ArgParser(argparse.ArgumentParser):
         super(ArgParser, self).__init__(prog="dglke_train")
         a = self.add_argument
         a('--model_name', default='TransE', choices=['TransE', 'TransE_l1', 'TransE_l2', 'TransR', 'RESCAL',
-                                                     'DistMult', 'ComplEx', 'RotatE', 'SimplE', 'QuatE'])
+                                                     'DistMult', 'ComplEx', 'RotatE', 'SimplE', 'QuatE', 'PairRE'])
         a('--data_path', type=str, default='data')
         a('--dataset', type=str, default='FB15k')
         a('--format', type=str, default='built_in')
@@ -815,12 +815,36 @@ def check_quate(args):
                        "plain --async_update runs the strict step and is fine")
 
 
+def check_pairre_widths(model_name, double_ent, double_rel):
+    """PairRE's relation row is [rH | rT], twice the entity row"""
+    if model_name != 'PairRE':
+        return
+    if not double_rel or double_ent:
+        raise KgeError("PairRE: the relation row [rH | rT] is twice as wide as the entity row: pass -dr without -de (got%s%s)"
+                       % (" -de" if double_ent else " no -de", " -dr" if double_rel else ", no -dr"))
+
+
+def check_pairre(args):
+    """PairRE trains on the strict step of one GPU's tables: refuse what has no such step, before anything is loaded"""
+    if args.model_name != 'PairRE':
+        return
+    check_pairre_widths(args.model_name, args.double_ent, args.double_rel)
+    if len(args.gpu) > 1:
+        raise KgeError("PairRE is not available on more than one GPU (--gpu takes one entry)")
+    if args.async_update_pipeline or args.async_update_rel:
+        raise KgeError("PairRE is not available in the one-step-stale pipeline (--async_update_pipeline / --async_update_rel); "
+                       "plain --async_update runs the strict step and is fine")
+    if args.eval_relation:
+        raise KgeError("PairRE has no relation ranking (--eval_relation): the score is not a product with the relation row")
+
+
 def main(argv=None, before_train=None):
     """before_train (one GPU): called with the built Trainer in front of its first step - the tests take the initial tables there"""
     args = ArgParser().parse_args(argv)
     check_loss_flags(args)                       # before anything is loaded or created
     check_exclude_positive(args)                 # before anything is loaded or created
     check_quate(args)                            # before anything is loaded or created
+    check_pairre(args)                           # before anything is loaded or created
     if args.neg_deg_sample_eval:                 # before anything is loaded or created
         if len(args.gpu) > 1:
             raise KgeError("--neg_deg_sample_eval is not available on sharded tables")

@@ -44,7 +44,7 @@ enum kge_model {
                           p = h.(M t); BOTH corruption modes use the pos-side vector M x (:428-447) */
     KGE_SIMPLE    = 5, /* score_fun.py:556 SimplEScore: rows = [x_i | x_j] halves, relation = [r | r_inv];
                           scores are clamped to [-20, 20] like the reference (:568, :622, :641) */
-    KGE_QUATE     = 8  /* QuatE (Zhang et al., NeurIPS 2019; not in the reference).  Rows are four quarters [a | b | c | d] of
+    KGE_QUATE     = 8, /* QuatE (Zhang et al., NeurIPS 2019; not in the reference).  Rows are four quarters [a | b | c | d] of
                           q = d_e / 4 columns each: column k of an entity row is the quaternion a_k + b_k i + c_k j + d_k k.
                           d_e % 4 == 0, d_r == d_e.  The relation row is normalised per column: n_k = sqrt(ra^2 + rb^2 + rc^2 + rd^2),
                           r^_k = r_k / n_k (sqrtf and a true division), r^_k = 0 where n_k == 0.  With h = (a, b, c, d) and
@@ -57,6 +57,29 @@ enum kge_model {
                           n == 0); gradients arriving through A chain the same way.  The regulariser acts on the raw rows.
                           Relation ranking of a fixed pair: s_j = <conj(h) (x) t, r^_j>.  Strict step on local tables, ranking and
                           top-K; kge_step_sharded, kge_step_grads, kge_step_async and kge_rank_eval_split refuse it. */
+    KGE_PAIRRE    = 10 /* PairRE (Chao et al., ACL 2021; not in the reference).  (Id 9 is not a model: it stays "unknown model".)
+                          Entity rows d_e wide, relation rows d_r == 2 * d_e wide, r = [rH | rT].  x^ = x / |x|_2 (sqrtf and a true
+                          division), x^ = 0 where |x|_2 == 0, and
+                            s(h, r, t) = gamma - sum_k |h^_k rH_k - t^_k rT_k|            (no clamp).
+                          Chunked form, one for both corruption sides: per edge the pair (a, w) - tails corrupted a = h^ o rH,
+                          w = rT; heads corrupted a = t^ o rT, w = rH - and s_ij = gamma - sum_k |a_ik - w_ik n^_jk|, n^_j the
+                          normalised candidate row (every kernel forms the difference as fmaf(-w, n^, a)).  Adjoint, with
+                          sigma_ijk = sign(a_ik - w_ik n^_jk), sign(0) = 0, G = dL/ds:  Ga_ik = -sum_j G sigma,
+                          Gw_ik = sum_j G sigma n^_jk, Gn^_jk = sum_i G sigma w_ik; through a normalisation
+                          gx = (gx^ - x^ <x^, gx^>) / |x| (0 where |x| == 0), applied per candidate-row occurrence.  The regulariser
+                          acts on the raw rows.  Layouts: the per-op entries take the RAW rows like every model's (pos_side
+                          [B, d_e], rel [B, 2 d_e], neg [C * N, d_e]; g_pos_side / g_rel / g_neg likewise, through the
+                          normalisations) and keep (a, w), (Ga, Gw) and the candidate norms in their workspace.  Ranking: the pair
+                          lives in the A and RV entries of the kge_rank_eval workspace (kge_rank_workspace_bytes is unchanged),
+                          the candidate norms |x|_2 in its bsq entry, once per call; kge_rank_eval_chunked carves one more entry
+                          of norms per candidate-list position (kge_rank_chunked_workspace_bytes answers for the id);
+                          kge_step_workspace_bytes and kge_score_neg_workspace_bytes answer for the id (entries w, Gw and the
+                          norms behind the common ones).  kge_topk_select / _filtered keep [a block | w block] in the A entry:
+                            workspace = kge_topk_workspace_bytes(rows, n_cand, 2 * d_e, K)
+                          (dglke_amd._lib.topk_workspace_bytes).  Strict step on local tables (kge_step_fused, kge_step_phase and
+                          their _known forms), ranking, chunked ranking and top-K; kge_step_sharded, kge_step_grads,
+                          kge_step_async, kge_step_fused_sampling (with a sampler job), kge_rank_eval_split and kge_rank_rel_eval
+                          refuse it before any launch. */
 };
 
 /* loss criteria (models/pytorch/loss.py:44-59) */
