@@ -20,18 +20,26 @@ struct SamplerArgs {
     uint64_t seed;
     int64_t *state;                  // device {pos, step, ticket, -}: advanced by the launch's last workgroup
     char *slots; int64_t slot_bytes; // output slots
-    int preperm;                     // tail jobs: H / R / T are ALREADY in base-permutation order (perm only says that epochs are shuffled)
+    // the last eight bytes have two users that never meet: the tail jobs' flag and the weighted sampler LAUNCH's weights (a member of
+    // its own would lengthen the argument block of every kernel that takes a SamplerArgs or a SmpTail and move their hidden arguments)
+    union {
+        struct { int preperm, preperm_pad; };  // tail jobs: H / R / T are ALREADY in base-permutation order (perm only says that epochs are shuffled)
+        const float *W;                        // weighted sampler launch: one weight per training triple [n_train], indexed like H / R / T
+    };
 };
+static_assert(sizeof(SamplerArgs) == 104, "SamplerArgs is a kernel argument block: its size and offsets are part of every kernel that takes it");
 
 // slot layout (must match kge_sampler_slot_* in kge_api.hip)
 struct SlotLayout {
     int64_t h_gid, t_gid, rel_ids, neg_ids, ue_id, ur_id;                       // int64 arrays
     int64_t ue_pos_ptr, ue_pos_adj, ue_neg_ptr, ue_neg_slot, ur_ptr, ur_edge;   // int32 arrays
     int64_t ue_rec, ur_rec, counts;
+    int64_t edge_w;                                                             // float [B], weighted slots only (-1: none)
     int64_t total;
 };
 __host__ __device__ inline int64_t al32(int64_t x) { return (x + 31) & ~(int64_t)31; }
-__host__ __device__ inline SlotLayout slot_layout(int B, int CN) {
+// weighted: the slot also carries the B weights of its edges, BEHIND counts - every other offset is the unweighted layout's
+__host__ __device__ inline SlotLayout slot_layout(int B, int CN, bool weighted = false) {
     const int64_t NE = 2 * (int64_t)B + CN;
     SlotLayout L; int64_t o = 0;
     L.h_gid = o; o = al32(o + 8 * B);
@@ -49,6 +57,8 @@ __host__ __device__ inline SlotLayout slot_layout(int B, int CN) {
     L.ue_rec = o; o = al32(o + 32 * NE);
     L.ur_rec = o; o = al32(o + 32 * B);
     L.counts = o; o = al32(o + 16);
+    L.edge_w = -1;
+    if (weighted) { L.edge_w = o; o = al32(o + 4 * (int64_t)B); }
     L.total = al32(o);
     return L;
 }

@@ -133,6 +133,11 @@ _SIGNATURES = {
     "kge_sample_batches": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_i, c_i, C.c_uint64, c_p, c_p, c_sz,
                                  c_i, c_p]),
     "kge_batch_from_slot": (c_i, [c_p, c_sz, c_i, c_i, c_i, c_i, c_i, c_i, C.POINTER(KgeBatch)]),
+    "kge_sampler_slot_bytes_weighted": (c_sz, [c_i, c_i, c_i]),
+    "kge_sample_batches_weighted": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_i, c_i, c_i, C.c_uint64, c_p, c_p, c_sz,
+                                          c_i, c_p]),
+    "kge_batch_from_slot_weighted": (c_i, [c_p, c_sz, c_i, c_i, c_i, c_i, c_i, c_i, C.POINTER(KgeBatch)]),
+    "kge_subsampling_weights": (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_p, c_p]),
     "kge_adagrad_apply_packed": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_p, c_i, c_i64, c_i, c_f, c_f, c_p]),
     "kge_transr_project": (c_i, [c_p, c_p, c_i64, c_i, c_i, c_p, c_p]),
     "kge_transr_project_bwd": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_i, c_p, c_p, c_i, c_p]),

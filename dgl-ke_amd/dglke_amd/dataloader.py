@@ -132,8 +132,10 @@ class DeviceBatch(object):
         self.B, self.C, self.chunk, self.N = sampler.B, sampler.C, sampler.chunk, sampler.N
         self.neg_head = bool(neg_head)
         kb = _lib.KgeBatch()
-        _lib.check(_lib.lib().kge_batch_from_slot(_lib.ptr(sampler.slots), sampler.slot_bytes, slot, self.B,
-                                                  self.C, self.chunk, self.N, int(self.neg_head), C.byref(kb)))
+        # a weighted sampler's slot carries edge_w behind counts; edge_w_mean stays 0: the step's kernels sum the B weights themselves
+        from_slot = _lib.lib().kge_batch_from_slot_weighted if sampler.W is not None else _lib.lib().kge_batch_from_slot
+        _lib.check(from_slot(_lib.ptr(sampler.slots), sampler.slot_bytes, slot, self.B,
+                             self.C, self.chunk, self.N, int(self.neg_head), C.byref(kb)))
         self.c = kb
         self.U, self.UE, self.UR = 0, kb.UE, kb.UR
 
@@ -146,7 +148,10 @@ class DeviceSampler(object):
     replacement over all entities, alternating tail/head corruption, whole batches only)."""
 
     def __init__(self, heads, rels, tails, n_entities, batch_size, neg_sample_size, device, n_slots=64,
-                 neg_chunk_size=None, seed=0, shuffle=True):
+                 neg_chunk_size=None, seed=0, shuffle=True, edge_importance=None):
+        """edge_importance: one float32 weight > 0 per training triple (tensor or array).  The sampler then runs the weighted
+        launch (`kge_sample_batches_weighted`): every slot also carries the weights of its B edges, the batches point
+        `kge_batch.edge_w` at them.  Ids, plan and state are those of the unweighted sampler from the same seed."""
         from . import _lib
         self.dev = th.device(device)
         if self.dev.type != 'cuda':
@@ -166,13 +171,25 @@ class DeviceSampler(object):
             return th.as_tensor(np.asarray(x, np.int64)).to(self.dev)
         self.H, self.R, self.T = put(heads), put(rels), put(tails)
         self.n_train = int(self.H.shape[0])
+        self.W = None
+        if edge_importance is not None:
+            if isinstance(edge_importance, th.Tensor):
+                w = edge_importance.to(self.dev, th.float32).contiguous()
+            else:
+                w = th.as_tensor(np.ascontiguousarray(edge_importance, np.float32)).to(self.dev)
+            if w.dim() != 1 or int(w.shape[0]) != self.n_train:
+                raise ValueError("edge_importance: one weight per training triple (%d), got shape %s" % (self.n_train, tuple(w.shape)))
+            if not bool((w > 0).all()):           # (the dataset's check and message, kgdataset.py; a NaN fails it too)
+                raise ValueError("Edge importance score should > 0")
+            self.W = w
         self.seed = int(seed)
         g = th.Generator(device=self.dev)
         g.manual_seed(self.seed)
         self.perm = th.randperm(self.n_train, device=self.dev, generator=g) if shuffle else None
         self.state = th.tensor([0, 1, 0, 0, -1, 0, 0, 0], dtype=th.int64, device=self.dev)   # {position, step (1-based), ticket, -; cached epoch, mul, add, 1/n (tail jobs)}
         self.n_slots = int(n_slots)
-        self.slot_bytes = int(_lib.lib().kge_sampler_slot_bytes(self.B, self.C, self.N))
+        slot_bytes = _lib.lib().kge_sampler_slot_bytes_weighted if self.W is not None else _lib.lib().kge_sampler_slot_bytes
+        self.slot_bytes = int(slot_bytes(self.B, self.C, self.N))
         self.slots = th.zeros(self.n_slots * self.slot_bytes, dtype=th.uint8, device=self.dev)
         self.host_step = 1                                                     # next step to be sampled
         self._batches = {}                                                     # (slot, corrupt-head) -> DeviceBatch
@@ -187,11 +204,13 @@ class DeviceSampler(object):
         slot0 = int(slot0)
         if slot0 < 0 or slot0 + n > self.n_slots:
             raise ValueError("more batches than slots")
-        _lib.check(_lib.lib().kge_sample_batches(
-            _lib.ptr(self.H), _lib.ptr(self.R), _lib.ptr(self.T),
-            _lib.ptr(self.perm) if self.perm is not None else None, self.n_train, self.n_entities, self.B,
-            self.C, self.chunk, self.N, self.seed, _lib.ptr(self.state),
-            self.slots.data_ptr() + slot0 * self.slot_bytes, self.slot_bytes, n, _lib.stream_ptr()))
+        ids = (_lib.ptr(self.H), _lib.ptr(self.R), _lib.ptr(self.T), _lib.ptr(self.perm) if self.perm is not None else None)
+        rest = (self.n_train, self.n_entities, self.B, self.C, self.chunk, self.N, self.seed, _lib.ptr(self.state),
+                self.slots.data_ptr() + slot0 * self.slot_bytes, self.slot_bytes, n, _lib.stream_ptr())
+        if self.W is not None:
+            _lib.check(_lib.lib().kge_sample_batches_weighted(*(ids + (_lib.ptr(self.W),) + rest)))
+        else:
+            _lib.check(_lib.lib().kge_sample_batches(*(ids + rest)))
         # (a DeviceBatch is pointer arithmetic on a slot: built once per slot and corruption mode - a group of 120 fresh ones was
         #  ~1 ms of ctypes calls in front of every group of the eager multi-GPU step)
         out = []
@@ -221,6 +240,9 @@ class DeviceSampler(object):
         HBM cost: the permuted copies of H, R and T are 24 bytes per training triple (FB15k: 11.6 MB; 338 M Freebase edges: 8.1 GB),
         held for the sampler's lifetime."""
         from . import _lib
+        if self.W is not None:
+            raise _lib.KgeError("DeviceSampler.tail_jobs(): the sampler tail jobs (kge_step_fused_sampling) carry no edge weights; a "
+                                "weighted sampler builds its batches with sample()")
         if getattr(self, "_tail_scratch", None) is not None:
             return
         if th.cuda.is_current_stream_capturing():
@@ -283,11 +305,56 @@ class DeviceSampler(object):
                             ("ue_pos_ptr", NE + 1, np.int32), ("ue_pos_adj", 2 * B, np.int32),
                             ("ue_neg_ptr", NE + 1, np.int32), ("ue_neg_slot", CN, np.int32),
                             ("ur_ptr", B + 1, np.int32), ("ur_edge", B, np.int32),
-                            ("ue_rec", 8 * NE, np.int32), ("ur_rec", 8 * B, np.int32), ("counts", 4, np.int32)):
+                            ("ue_rec", 8 * NE, np.int32), ("ur_rec", 8 * B, np.int32), ("counts", 4, np.int32)) + \
+                ((("edge_w", B, np.float32),) if self.W is not None else ()):
             nb = n * np.dtype(dt).itemsize
             out[name] = raw[o:o + nb].view(dt).copy()
             o = al(o + nb)
         return out
+
+
+def _sorted_keys(a, r, n_relations):
+    """a * R + r of the training split, sorted ascending WITH multiplicity (device tensors)"""
+    key = a * n_relations
+    key += r
+    out = th.sort(key)[0]
+    del key
+    return out
+
+
+def subsampling_weights(h, r, t, n_entities, n_relations, dev):
+    """the frequency ("subsampling") weights of the training triples (h, r, t), float32 [n] on `dev`:
+        w_i = s / sqrt(count(h_i, r_i) + count(t_i, r_i^-1)),   both counts over the split and started at 3
+    (RotatE's count_frequency with start = 4: a pair seen n times counts n + 3; a triple present twice counts twice), by
+    `kge_subsampling_weights` over the two key arrays sorted on the device.  s normalises the weights to MEAN 1 over the split -
+    this build's choice: its loss divides by the batch size, not by the batch's weight sum as RotatE's does, so mean-1 weights
+    keep the loss scale (and --lr) of the unweighted recipe.  Two launches: scale 1, the mean in float64, then scale
+    float32(1 / mean).  Intermediates are deleted as soon as they are used; the sorted keys are not kept."""
+    dev = th.device(dev)
+    if dev.type != 'cuda':
+        raise _lib.KgeError("subsampling_weights needs a CUDA (HIP) device")
+    R, NE = int(n_relations), int(n_entities)
+    if NE * R >= (1 << 62):
+        raise _lib.KgeError("subsampling_weights: n_entities * n_relations >= 2^62 - the keys h * R + r do not fit 64 bits")
+
+    def put(x):
+        if isinstance(x, th.Tensor):
+            return x.to(dev, th.int64).contiguous()
+        return th.as_tensor(np.asarray(x, np.int64)).to(dev)
+    H, Rl, T = put(h), put(r), put(t)
+    n = int(H.shape[0])
+    khr, ktr = _sorted_keys(H, Rl, R), _sorted_keys(T, Rl, R)
+    out = th.empty(n, dtype=th.float32, device=dev)
+
+    def launch(scale):
+        _lib.check(_lib.lib().kge_subsampling_weights(_lib.ptr(khr), n, _lib.ptr(ktr), n, _lib.ptr(H), _lib.ptr(Rl), _lib.ptr(T), n,
+                                                      NE, R, float(scale), _lib.ptr(out), _lib.stream_ptr()))
+    launch(1.0)
+    if n:
+        mean = float(out.sum(dtype=th.float64)) / n
+        launch(np.float32(1.0 / mean))
+    del khr, ktr, H, Rl, T
+    return out
 
 
 class _GraphSeq(object):

@@ -109,6 +109,15 @@ class ArgParser(argparse.ArgumentParser):
                'the training split contributes neither loss nor gradient nor self-adversarial weight (the reference sampler\'s '
                'exclude_positive parameter, which its CLI never sets; "filtered negatives" elsewhere).  One GPU; not with '
                '--neg_deg_sample, --async_update_pipeline or --async_update_rel')
+        a('-sw', '--subsampling_weight', action='store_true',
+          help='weight every training triple by 1 / sqrt(count(h, r) + count(t, r^-1)), the counts over the training split and both '
+               'started at 3 (the subsampling weights of the RotatE, OGB and PairRE code bases), normalised to mean 1 over the split.  '
+               'Computed once on the device; the batches come from the weighted device sampler (captured graphs).  One GPU; not with '
+               '--has_edge_importance, --async_update_pipeline or --async_update_rel; batches the device sampler cannot build are '
+               'refused')
+        a('--edge_importance_on_device', action='store_true',
+          help='with --has_edge_importance: hand the weight column of train.txt to the weighted device sampler instead of the host '
+               'sampler (same refusals as --subsampling_weight)')
         a('--dist_slack', type=float, default=None,
           help='--dist_mode a2a: initial capacity of an owner bucket as a multiple of the mean share of a batch\'s unique entities '
                '(default 1.5, or KGE_DIST_SLACK); buckets grow by themselves when a group of batches needs more')
@@ -130,12 +139,13 @@ class ArgParser(argparse.ArgumentParser):
           help='with --valid: stop as soon as the validation MRR reaches this value and report the time')
 
 
-def get_compatible_batch_size(batch_size, neg_sample_size):
+def get_compatible_batch_size(batch_size, neg_sample_size, quiet=False):
     """utils.py:27-33"""
     if neg_sample_size < batch_size and batch_size % neg_sample_size != 0:
         old = batch_size
         batch_size = int(math.ceil(batch_size / neg_sample_size) * neg_sample_size)
-        print('batch size ({}) is incompatible to the negative sample size ({}). Change the batch size to {}'.format(
+        if not quiet:
+            print('batch size ({}) is incompatible to the negative sample size ({}). Change the batch size to {}'.format(
             old, neg_sample_size, batch_size))
     return batch_size
 
@@ -307,6 +317,12 @@ class _Trainer(object):
         # the on-device sampler builds the batches of a whole group ahead; batches it cannot build - edge importance, or more ids
         # than its launch handles - come from the host sampler (plans built on the host, step by step)
         self.device_sampler = not args.has_edge_importance and 2 * B + self.C * N <= DeviceSampler.MAX_ELEMENTS
+        # weights the DEVICE sampler carries (--subsampling_weight, --has_edge_importance --edge_importance_on_device): one float per
+        # triple of the training split, set by the trainer before its lanes make their samplers
+        self.weighted = weighted_device_sampler(args)
+        if self.weighted:
+            self.device_sampler = True                # (check_weighted_device_sampler has refused what the sampler cannot build)
+        self.edge_weights = None
         self.n_lanes, self.async_update, self.known = 1, False, None
 
     def make_engine(self, n_entities=None, **tables):
@@ -339,8 +355,12 @@ class _Trainer(object):
         a, tr = self.args, self.dataset.train
         h, r, t = (np.asarray(x)[part] for x in tr[:3])
         if self.device_sampler:
+            w = None
+            if self.weighted:                         # the rows of this lane's part; the counts behind them are the whole split's
+                w = self.edge_weights if isinstance(part, slice) else self.edge_weights[th.as_tensor(np.asarray(part), device=self.dev)]
             return DeviceSampler(h, r, t, self.dataset.n_entities, a.batch_size, a.neg_sample_size, self.dev,
-                                 n_slots=max(2, a.graph_steps or 2), neg_chunk_size=self.chunk, seed=a.seed + 1000 * k)
+                                 n_slots=max(2, a.graph_steps or 2), neg_chunk_size=self.chunk, seed=a.seed + 1000 * k,
+                                 edge_importance=w)
         w = np.asarray(tr[3])[part] if a.has_edge_importance else None
         return UniformChunkedSampler(h, r, t, self.dataset.n_entities, a.batch_size, a.neg_sample_size, self.dev,
                                      neg_chunk_size=self.chunk, seed=a.seed + 1000 * k, edge_importance=w)
@@ -409,9 +429,10 @@ class _Trainer(object):
                     timed = None
                 t_interval = 0.0
                 if self.world == 1:
-                    print('[proc {}]sample+forward+backward+update (fused HIP step{}{}{}): {:.3f}'.format(
+                    print('[proc {}]sample+forward+backward+update (fused HIP step{}{}{}{}): {:.3f}'.format(
                         0, ', --async_update pipeline' if self.lanes[0].async_update else '',
                         ', known training triples excluded' if self.known is not None else '',
+                        {None: '', 'subsampling': ', subsampling weights', 'file': ', edge importance on the device'}[self.weighted],
                         '' if self.n_lanes == 1 else ', %d concurrent trainers' % self.n_lanes, t_train))
                 since_log, start = 0, time.time()
             if args.valid and step % args.eval_interval == 0 and step > 1 and self.dataset.valid is not None:
@@ -460,6 +481,19 @@ class Trainer(_Trainer):
         elif args.async_update and not pipeline:
             print('--async_update: running the strict step (no staleness; faster on this GPU than the entity-only one-step-stale '
                   'pipeline - pass --async_update_rel to defer the relation trace too, or --async_update_pipeline to force it)')
+        if self.weighted == 'subsampling':
+            # ONE weight per triple of the whole training split, computed on the device once; every lane's sampler takes its rows
+            from .dataloader import subsampling_weights
+            check_weighted_device_sampler(args)
+            self.edge_weights = subsampling_weights(dataset.train[0], dataset.train[1], dataset.train[2], dataset.n_entities,
+                                                    dataset.n_relations, self.dev)
+            print('[Train] --subsampling_weight: subsampling weights of {} training triples, mean 1, between {:.4f} and {:.4f}'.format(
+                self.edge_weights.numel(), float(self.edge_weights.min()), float(self.edge_weights.max())))
+        elif self.weighted == 'file':
+            check_weighted_device_sampler(args)
+            self.edge_weights = th.as_tensor(np.asarray(dataset.train[3], np.float32)).to(self.dev)
+            print('[Train] --edge_importance_on_device: the edge importance of {} training triples goes through the device '
+                  'sampler'.format(self.edge_weights.numel()))
         # the lanes share the tables (TransR: the projection table too); every lane trains on its own random share of the triples
         parts = self.split(self.n_lanes, refusal="every trainer needs at least batch_size training triples: %(triples)d triples over "
                            "%(n)d trainer(s) < batch_size %(batch)d - lower --batch_size or --num_proc")
@@ -781,6 +815,39 @@ def check_exclude_positive(args):
                        "--async_update_rel); plain --async_update runs the strict step and is fine")
 
 
+def weighted_device_sampler(args):
+    """which weights the device sampler carries: 'subsampling' (--subsampling_weight), 'file' (--has_edge_importance
+    --edge_importance_on_device) or None"""
+    if getattr(args, 'subsampling_weight', False):
+        return 'subsampling'
+    if getattr(args, 'edge_importance_on_device', False):
+        return 'file'
+    return None
+
+
+def check_weighted_device_sampler(args):
+    """--subsampling_weight and --edge_importance_on_device train on batches of the weighted device sampler, on the strict step of
+    one GPU's tables: refuse what has no such batch or step, before anything is loaded"""
+    if args.edge_importance_on_device and not args.has_edge_importance:
+        raise KgeError("--edge_importance_on_device needs --has_edge_importance (the weight column of train.txt)")
+    which = weighted_device_sampler(args)
+    if which is None:
+        return
+    flag = "--subsampling_weight" if which == 'subsampling' else "--edge_importance_on_device"
+    if args.subsampling_weight and args.has_edge_importance:
+        raise KgeError("--subsampling_weight cannot be combined with --has_edge_importance (two weightings of the same edges)")
+    if len(args.gpu) > 1:
+        raise KgeError("%s is not available on more than one GPU (--gpu takes one entry)" % flag)
+    if args.async_update_pipeline or args.async_update_rel:
+        raise KgeError("%s is not available in the one-step-stale pipeline (--async_update_pipeline / --async_update_rel); "
+                       "plain --async_update runs the strict step and is fine" % flag)
+    B, N = get_compatible_batch_size(args.batch_size, args.neg_sample_size, quiet=True), args.neg_sample_size
+    chunk = N if N <= B else B
+    if 2 * B + (B // chunk) * N > DeviceSampler.MAX_ELEMENTS:
+        raise KgeError("%s: the device sampler builds batches of 2 * batch_size + chunks * neg_sample_size <= %d ids (got %d); "
+                       "there is no host sampler for this flag" % (flag, DeviceSampler.MAX_ELEMENTS, 2 * B + (B // chunk) * N))
+
+
 def check_loss_flags(args):
     """--loss_genre Softmax (cross-entropy of the positive against its row): the softmax is the weighting and the row is the pairing"""
     if args.loss_genre != 'Softmax':
@@ -845,7 +912,8 @@ def main(argv=None, before_train=None):
     check_exclude_positive(args)                 # before anything is loaded or created
     check_quate(args)                            # before anything is loaded or created
     check_pairre(args)                           # before anything is loaded or created
-    if args.neg_deg_sample_eval:                 # before anything is loaded or created
+    check_weighted_device_sampler(args)          # before anything is loaded or created
+    if args.neg_deg_sample_eval:                # before anything is loaded or created
         if len(args.gpu) > 1:
             raise KgeError("--neg_deg_sample_eval is not available on sharded tables")
         assert args.no_eval_filter, "if negative sampling based on degree, we can't filter positive edges."   # train.py:878

@@ -647,6 +647,37 @@ int kge_step_fused_sampling(const kge_hparams *hp, const kge_tables *tb, const k
 int kge_batch_from_slot(void *slots, size_t slot_bytes, int slot, int B, int C, int chunk, int N,
                         int neg_head, kge_batch *out);
 
+/* ---- the WEIGHTED sampler launch (dglke_train --subsampling_weight, --edge_importance_on_device) ----
+ * kge_sample_batches with one float per training triple: `weights` [n_train], indexed like heads / rels / tails (i.e. after
+ * perm).  A weighted slot is the unweighted slot - every offset byte for byte - followed by edge_w, float[B], behind `counts`
+ * (kge_sampler_slot_bytes_weighted); the workgroup that loads heads[e] and tails[e] of edge i stores weights[e] to edge_w[i].
+ * The weights enter neither the RNG nor the epoch permutation nor the plan: ids, lists, records, counts and the state after the
+ * launch are those of kge_sample_batches from the same state.  weights == NULL: KGE_ERR_ARG; slot_bytes smaller than
+ * kge_sampler_slot_bytes_weighted(): KGE_ERR_WORKSPACE; nothing is launched in either case.  `hip_stream`: the stream of the
+ * launch (conventions above), the last argument as everywhere.
+ * kge_batch_from_slot_weighted points kge_batch.edge_w at the slot's array and leaves edge_w_mean = 0: the kernels of every step
+ * entry then sum the B weights themselves (one lane-strided pass per wavefront that needs the mean).  The sampler tail jobs
+ * (kge_step_fused_sampling) carry no weights. */
+size_t kge_sampler_slot_bytes_weighted(int B, int C, int N);
+int kge_sample_batches_weighted(const int64_t *heads, const int64_t *rels, const int64_t *tails,
+                                const int64_t *perm, const float *weights, int64_t n_train, int64_t n_ent, int B, int C,
+                                int chunk, int N, uint64_t seed, int64_t *state, void *slots, size_t slot_bytes,
+                                int n_slots, void *hip_stream);
+int kge_batch_from_slot_weighted(void *slots, size_t slot_bytes, int slot, int B, int C, int chunk, int N,
+                                 int neg_head, kge_batch *out);
+
+/* ---- frequency ("subsampling") weights of training triples (csrc/kge_subsample.hip) ----
+ * keys_hr [m_hr] / keys_tr [m_tr]: the training split's h * n_rel + r and t * n_rel + r, each sorted ascending WITH multiplicity
+ * (a triple present twice counts twice).  Per triple i of heads / rels / tails [n]: n_hr, n_tr = the number of keys equal to
+ * heads[i] * n_rel + rels[i] in keys_hr and to tails[i] * n_rel + rels[i] in keys_tr (upper bound - lower bound), and
+ *     out[i] = scale * (1 / sqrtf((float)(n_hr + n_tr + 6)))
+ * - IEEE square root and division; the + 6 is the start value 4 of both counters of RotatE's count_frequency (a pair seen n
+ * times counts n + 3).  scale > 0.  n_ent * n_rel >= 2^62: KGE_ERR_ARG.  One thread per triple; no allocation, no
+ * synchronisation, capturable.  `hip_stream`: the stream of the launch, the last argument as everywhere. */
+int kge_subsampling_weights(const int64_t *keys_hr, int64_t m_hr, const int64_t *keys_tr, int64_t m_tr,
+                            const int64_t *heads, const int64_t *rels, const int64_t *tails, int64_t n, int64_t n_ent,
+                            int64_t n_rel, float scale, float *out, void *hip_stream);
+
 /* owner side, packed messages (one row per message, `ld` floats apart):
  *   msg = [ g_0 (dim) | ... | g_{T-1} (dim) | gs_0 .. gs_{T-1} | (id_lo id_hi as int32 bits when idx == NULL) ]
  * applies the T traces of every row in order (trace t: s += gs_t; row += -lr*g_t/(sqrt(s)+eps)).
