@@ -202,6 +202,7 @@ _SIGNATURES = {
     "kge_ipc_close": (c_i, [c_p]),
     "kge_debug_carve": (c_i, [c_p, c_i, c_sz]),      # test support (include/kge_hip.h): trace is a HOST int64 array
     "kge_debug_carve_count": (c_i, []),
+    "kge_debug_epoch_order": (c_i, [c_i64, C.c_uint64, c_i, c_p, c_p, c_i64, c_p, c_p]),   # test support: the sampler's epoch order
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())

@@ -856,9 +856,17 @@ int kge_step_phase_known(const kge_hparams *hp, const kge_tables *tb, const kge_
  * cap_pairs pairs; further buffers are counted, not recorded), and `gap` extra bytes are left behind every buffer before the
  * 256-byte round-up.  The size functions and the entries share the allocators, so they agree with the gap as without it.  The
  * call resets the count; (NULL, 0, 0) switches the setting off: the layout is then exactly the documented one.
- * kge_debug_carve_count: buffers carved by this thread since its last kge_debug_carve call. */
+ * kge_debug_carve_count: buffers carved by this thread since its last kge_debug_carve call.
+ * kge_debug_epoch_order (csrc/kge_debug.hip): the device sampler's epoch order - edge i of epoch e is perm[(i * mul + add) mod n_train],
+ * (mul, add) hashed from (seed, e) - evaluated by the sampler kernels' own inline functions for n (epoch[k], pos[k]) pairs, without
+ * any triple, so that graphs of 2^32 triples and more can be tested: out[5k .. 5k + 4] = {the index by the sampler launch's
+ * remainder, the index by the tail jobs' cached reciprocal, mul, add, floor((2^64 - 1) / n_train)} (the last three as 64-bit
+ * patterns).  shuffled == 0: a sampler without a base permutation (every epoch the identity).  epoch, pos, out: device memory;
+ * every pos[k] must be in [0, n_train) - the caller's responsibility.  KGE_ERR_ARG: n_train <= 0, n < 0, a null pointer. */
 int kge_debug_carve(int64_t *trace, int cap_pairs, size_t gap);
 int kge_debug_carve_count(void);
+int kge_debug_epoch_order(int64_t n_train, uint64_t seed, int shuffled, const int64_t *epoch, const int64_t *pos, int64_t n,
+                          int64_t *out /* [n][5]: index, index_fast, mul, add, rinv */, void *stream);
 
 #ifdef __cplusplus
 }

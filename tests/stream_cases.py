@@ -79,6 +79,8 @@ STREAM_ENTRIES = {
     "kge_route_build_group": ["route"],
     "kge_gather_rows_req": ["route"],
     "kge_gather_rows_sharded": ["gather_rows_sharded"],
+    # test support
+    "kge_debug_epoch_order": ["debug_epoch_order"],
 }
 
 

@@ -544,6 +544,28 @@ def test_gather_rows_sharded():
 
 
 # --------------------------------------------------------------------------------------------------------------------------
+# test support
+# --------------------------------------------------------------------------------------------------------------------------
+def test_debug_epoch_order():
+    """kge_debug_epoch_order for a graph of 2^32 + 15 triples, shuffled and not; baseline: the Python-integer statement, as in
+    test_epoch_order_of_any_graph_size_equals_the_statement (test_gpu_sampler_statement.py)"""
+    from test_gpu_sampler_statement import epoch_order, order_statement
+    n = (1 << 32) + 15
+    positions = [0, 1, n - 2, n - 1] + [int(x) % n for x in np.random.RandomState(4).randint(0, 1 << 62, 300, dtype=np.int64)]
+    epochs, pos = [ep for ep in (0, 1, 9, 1 << 40) for _ in positions], positions * 4
+
+    def run(verify):
+        res = {}
+        for shuffled in (True, False):
+            got = epoch_order(n, 3, shuffled, epochs, pos)
+            if verify:
+                assert np.array_equal(got.cpu().numpy().view(np.uint64), order_statement(n, 3, shuffled, epochs, pos)), shuffled
+            res["shuffled %d" % shuffled] = got
+        return res
+    _stream_case("debug_epoch_order", run)
+
+
+# --------------------------------------------------------------------------------------------------------------------------
 # two engines, two streams
 # --------------------------------------------------------------------------------------------------------------------------
 def _tables_of(eng):
