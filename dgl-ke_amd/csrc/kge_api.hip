@@ -517,6 +517,7 @@ struct StepCall {
     const kge_known *known = nullptr;        // known triples left out of the negatives (kge_step_*_known): PH_FWD builds the pair mask
     uint32_t *known_mask = nullptr;          // ... into this buffer of the caller's, and the stand-alone loss kernel reads it
     size_t known_mask_bytes = 0;
+    const AdamArgs *adam = nullptr;          // the update launch is the Adam form (kge_step_optim, KGE_OPT_ADAM)
 };
 
 static StepCall phase_call(int phases) { StepCall c; c.phases = phases; return c; }
@@ -698,7 +699,8 @@ static StepPlan plan_step(const kge_hparams *hp, const kge_batch *b, const kge_s
     // stand-alone reduction launch (5.2 us + a boundary) leaves the strict step.  One-call strict step on local tables, no
     // gradient outputs (they read the summed buffers).
     p.fold_nrw = neg_bwd_lc_nrw(model, C, chunk, d_e);
-    p.fold_upd = phases == PH_ALL && p.lc && p.transe_fast && model == KGE_TRANSE_L1 && !p.nd && !sh && !c.emit && !c.build_update &&
+    // (Adam: the stand-alone reduction launch - the Adam instances read summed GN / GA rows, there is no folded Adam instance)
+    p.fold_upd = !c.adam && phases == PH_ALL && p.lc && p.transe_fast && model == KGE_TRANSE_L1 && !p.nd && !sh && !c.emit && !c.build_update &&
                  !c.co_update && !c.co_prep && !(out && (out->g_neg || out->g_rel || out->g_pos_ent)) && d_e % 4 == 0 && d_e <= 512 &&
                  N % 4 == 0 && p.fold_nrw <= 6 && parts <= 4 && !(fl & KGE_FLAG_SPLIT_FWD) && (!p.reg || hp->reg_norm == 3);
     // GA in parts only where the shared-pair kernel runs: its stand-alone partial reduction adds them up in place, the
@@ -1163,7 +1165,8 @@ int Step::phase_update() {
     const bool copy_g0 = emit && out && out->g_pos_ent && (phases & PH_UPD_ENT);
     if (out && out->g_pos_ent && !emit) ua.g0 = out->g_pos_ent;
     if (c.build_update) { *c.build_update = ua; return KGE_OK; }
-    KGE_TRY(launch_update(ua, s, c.tail));
+    if (c.adam) KGE_TRY(launch_update_adam(ua, *c.adam, s));
+    else KGE_TRY(launch_update(ua, s, c.tail));
     if (copy_g0 && hipMemcpyAsync(out->g_pos_ent, emit->g0, (size_t)b->UE * d_e * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
         return fail(KGE_ERR_LAUNCH, "hipMemcpyAsync failed");
     // deterministic reduction of this step's loss terms (only when the caller wants the per-step values; running sums are
@@ -1360,6 +1363,48 @@ int kge_step_phase_known(const kge_hparams *hp, const kge_tables *tb, const kge_
     StepCall c = phase_call(ph | PH_STRICT);
     c.known = known; c.known_mask = mask; c.known_mask_bytes = mask_bytes;
     return run_step(hp, tb, b, out, ws, ws_bytes, stream, c);
+}
+
+// the strict step with the optimizer as an argument: KGE_OPT_ADAGRAD is the existing step, KGE_OPT_ADAM swaps the update launch
+// for its Adam form (kge_adam.hip) - everything in front of the update is the same launches on the same arguments
+int kge_step_optim(const kge_hparams *hp, const kge_optim *opt, const kge_tables *tb, const kge_batch *b, const kge_step_out *out,
+                   void *ws, size_t ws_bytes, int phases, const kge_known *known, uint32_t *mask, size_t mask_bytes, void *hip_stream) {
+    const int all = KGE_PHASE_GATHER | KGE_PHASE_FORWARD | KGE_PHASE_BACKWARD | KGE_PHASE_UPDATE;
+    if (!hp || !opt || !tb || !b || !ws) return fail(KGE_ERR_ARG, "kge_step_optim: null argument");
+    if (phases <= 0 || phases > all) return fail(KGE_ERR_ARG, "kge_step_optim: bad phase mask %d", phases);
+    if (opt->kind != KGE_OPT_ADAGRAD && opt->kind != KGE_OPT_ADAM)
+        return fail(KGE_ERR_ARG, "kge_step_optim: unknown optimizer kind %d (KGE_OPT_ADAGRAD, KGE_OPT_ADAM)", opt->kind);
+    if (opt->kind == KGE_OPT_ADAGRAD) {
+        if (phases != all) return kge_step_phase_known(hp, tb, b, out, ws, ws_bytes, phases, known, mask, mask_bytes, hip_stream);
+        return kge_step_fused_known(hp, tb, b, out, ws, ws_bytes, nullptr, known, mask, mask_bytes, hip_stream);
+    }
+    if (hp->model == KGE_RESCAL || hp->model == KGE_TRANSR)
+        return fail(KGE_ERR_ARG, "kge_step_optim: Adam is not available for RESCAL / TransR (their relation-side tables are updated by "
+                                 "kernels of their own)");
+    if (!opt->ent_mom || !opt->rel_mom)
+        return fail(KGE_ERR_ARG, "kge_step_optim: Adam needs the moment tables ent_mom [n_ent, 2, d_e] and rel_mom [n_rel, 2, d_r]");
+    if (!(opt->beta1 >= 0.f && opt->beta1 < 1.f) || !(opt->beta2 >= 0.f && opt->beta2 < 1.f))
+        return fail(KGE_ERR_ARG, "kge_step_optim: Adam needs beta1 and beta2 in [0, 1) (got %g, %g)", (double)opt->beta1, (double)opt->beta2);
+    if (!(opt->eps > 0.f)) return fail(KGE_ERR_ARG, "kge_step_optim: Adam needs eps > 0 (got %g)", (double)opt->eps);
+    if (hp->d_e <= 0 || hp->d_r <= 0 || hp->d_e % 4 != 0 || hp->d_r % 4 != 0 || hp->d_e > 1024 || hp->d_r > 1024)
+        return fail(KGE_ERR_ARG, "kge_step_optim: Adam runs in the register-resident update - row widths must be multiples of 4 and at "
+                                 "most 1024 floats (d_e=%d d_r=%d)", hp->d_e, hp->d_r);
+    AdamArgs o{};
+    o.ent_mom = opt->ent_mom; o.rel_mom = opt->rel_mom; o.beta1 = opt->beta1; o.beta2 = opt->beta2; o.eps = opt->eps;
+    o.omb1 = (float)(1.0 - (double)opt->beta1); o.omb2 = (float)(1.0 - (double)opt->beta2);
+    o.lb1 = (float)std::log((double)opt->beta1); o.lb2 = (float)std::log((double)opt->beta2);      // (beta 0: -inf, expm1 gives -1)
+    int ph = PH_ALL;
+    if (phases != all) {
+        ph = PH_STRICT;
+        if (phases & KGE_PHASE_GATHER) ph |= PH_PREP;
+        if (phases & KGE_PHASE_FORWARD) ph |= PH_FWD;
+        if (phases & KGE_PHASE_BACKWARD) ph |= PH_BWD;
+        if (phases & KGE_PHASE_UPDATE) ph |= PH_UPDATE;
+    }
+    StepCall c = phase_call(ph);
+    c.adam = &o;
+    if (known) { c.known = known; c.known_mask = mask; c.known_mask_bytes = mask_bytes; }
+    return run_step(hp, tb, b, out, ws, ws_bytes, hip_stream, c);
 }
 
 int kge_step_grads(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, const kge_emit *emit,

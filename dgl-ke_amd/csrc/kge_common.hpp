@@ -541,6 +541,16 @@ struct UpdateArgs {
     const float *GNp; int gn_parts; int64_t gn_stride; float gn_reg_coef; int gn_reg_norm;
     int ga_parts; int64_t ga_stride;
 };
+// lazy row-sparse Adam (kge_step_optim, KGE_OPT_ADAM): what the Adam form of the register-resident update needs beyond UpdateArgs.
+// It travels NEXT TO UpdateArgs, as a kernel parameter of the Adam instances alone (kge_adam.hip): a longer UpdateArgs would move
+// the arguments of every Adagrad launch.  UpdateArgs::ent_state / rel_state hold the per-row counts, UpdateArgs::lr the step size.
+struct AdamArgs {
+    float *ent_mom, *rel_mom;        // [n_ent, 2, d_e], [n_rel, 2, d_r]: the row's m, then its v
+    float omb1, omb2;                // 1 - beta1, 1 - beta2 (rounded once, on the host)
+    float lb1, lb2;                  // log(beta1), log(beta2): the bias corrections are -expm1(c * log(beta))
+    float beta1, beta2, eps;
+};
+int launch_update_adam(const UpdateArgs &a, const AdamArgs &o, hipStream_t s);
 __device__ __forceinline__ int64_t gn_row(const UpdateArgs &a, int slot) {
     return a.nd_chunk ? (int64_t)(slot / a.nd_Ns) * a.nd_Np + a.nd_chunk + slot % a.nd_Ns : (int64_t)slot;
 }

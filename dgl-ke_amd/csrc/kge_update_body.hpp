@@ -40,6 +40,51 @@ __device__ __forceinline__ kge::Pack<4> ld_parts(const float *p, int parts, int6
     }
     return v[0];
 }
+// ---- the Adam form's tail (ADAM instances of update_reg_body / update_rel_row, launched by kge_adam.hip) ----
+// lazy Adam with a per-row count (the rule of DGL's sparse Adam):  c = min(c + 1, 2^24);  m = b1 m + (1 - b1) G;
+// v = b2 v + (1 - b2) G G;  x -= lr (m / (1 - b1^c)) / (sqrt(v / (1 - b2^c)) + eps).  The count lives in the row's state slot
+// (a float holds every integer up to 2^24), so nothing here depends on a host-side step number and a captured graph replays.
+// 1 - b^c = -expm1(c log b): accurate for small c, where 1 - pow(b, c) loses its leading digits.  Wave-uniform, once per row.
+// x, m, v: the row's packs as requested in the first round, G the summed gradient; lanes beyond the row hold zeros and store nothing.
+template <int NIT>
+__device__ __forceinline__ void adam_tail(const AdamArgs &o, float lr, float c0, float *row, float *mom, float *cnt, int d, int nit,
+                                          int lane, const kge::Pack<4> (&x)[NIT], const kge::Pack<4> (&m)[NIT],
+                                          const kge::Pack<4> (&v)[NIT], const kge::Pack<4> (&G)[NIT]) {
+    using namespace kge;
+    const float c = fminf(c0 + 1.f, 16777216.f);
+    const float k1 = lr / -expm1f(c * o.lb1), i2 = 1.f / -expm1f(c * o.lb2);
+#pragma unroll
+    for (int k = 0; k < NIT; ++k) {
+        const int it = lane + 64 * k;
+        if (it < nit) {
+            Pack<4> y, mn, vn;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float g = G[k].v[e];
+                mn.v[e] = fmaf(o.beta1, m[k].v[e], o.omb1 * g);
+                vn.v[e] = fmaf(o.beta2, v[k].v[e], o.omb2 * g * g);
+                y.v[e] = x[k].v[e] - k1 * mn.v[e] / (sqrtf(vn.v[e] * i2) + o.eps);
+            }
+            KGE_ST_ROW<4>(row + it * 4, y);
+            st<4>(mom + it * 4, mn);          // (moments and count: read again by the next update launch only - plain stores)
+            st<4>(mom + d + it * 4, vn);
+        }
+    }
+    if (lane == 0) *cnt = c;
+}
+// regularisation value of one traced row (what the Adagrad tails write behind their stores)
+__device__ __forceinline__ void adam_reg_out(const UpdateArgs &a, bool reg, float rv, float mult, float *part, int64_t u, int64_t slot, int lane) {
+    using namespace kge;
+    if (reg && (part || a.acc)) {
+        rv = wave_sum(rv);
+        const float val = a.reg_coef * rv * mult;
+        if (lane == 0) {
+            if (part) part[u] = val;
+            if (a.acc) acc_add(&a.acc[3 * KGE_ACC_SLOTS + (int)(slot & (KGE_ACC_SLOTS - 1))], val, a.UE + a.UR <= KGE_ACC_SLOTS);
+        }
+    } else if (part && lane == 0) part[u] = 0.f;
+}
+
 #define KGE_GA_MAXP 4          // most GA parts / GN partials the folded update takes (the launcher falls back to the reduction launch)
 #define KGE_GN_MAXP 6
 
@@ -48,8 +93,11 @@ __device__ __forceinline__ kge::Pack<4> ld_parts(const float *p, int parts, int6
 //  a row without any shared list came out 1 ulp apart - device-built batches pick the instance per batch, host plans always COOP.)
 // `u`, `r0`, `r1`, `cnt_r`: this wavefront's relation entry, its plan record (of entry UR - 1 when u is beyond the bound) and the
 // batch's relation count, all requested by update_reg_body's head and already in scalar registers.
-template <int NIT, bool SHARDED, int LEAN, bool COOP, bool FOLD = false>
-__device__ __forceinline__ void update_rel_row(const UpdateArgs &a, int64_t u, UniformI4 r0, UniformI4 r1, int cnt_r, int lane, bool reg, bool qm) {
+// ADAM: the Adam form - same record, list walk and source modes, the row's m and v requested with the row, adam_tail in place of
+// the mean-square reduction (`o`: its constants and moment tables; unused otherwise).
+template <int NIT, bool SHARDED, int LEAN, bool COOP, bool FOLD = false, bool ADAM = false>
+__device__ __forceinline__ void update_rel_row(const UpdateArgs &a, int64_t u, UniformI4 r0, UniformI4 r1, int cnt_r, int lane, bool reg, bool qm,
+                                               const AdamArgs &o = AdamArgs{}) {
     using namespace kge;
     constexpr int LB2 = NIT <= 2 ? 2 : 1;
     constexpr int LBR = NIT <= 2 ? 6 : 2;
@@ -104,9 +152,13 @@ __device__ __forceinline__ void update_rel_row(const UpdateArgs &a, int64_t u, U
 #pragma unroll
     for (int k = 0; k < NIT; ++k) itc[k] = min(lane + 64 * k, nit - 1) * 4;
     Pack<4> fva[NIT], fvb[NIT];
+    Pack<4> am[ADAM ? NIT : 1], av[ADAM ? NIT : 1];         // (ADAM) the row's moments: same record, same round as the row
+    float *mrow = nullptr;
+    if constexpr (ADAM) mrow = o.rel_mom + id * 2 * (int64_t)d;
 #pragma unroll
     for (int k = 0; k < NIT; ++k) {                         // every pack requested before the first use
         x[k] = ld<4>(row + itc[k]);
+        if constexpr (ADAM) { am[k] = ld<4>(mrow + itc[k]); av[k] = ld<4>(mrow + d + itc[k]); }
         fva[k] = ld<4>(pA + itc[k]);
         if constexpr (FOLD) fvb[k] = ld_parts<KGE_GA_MAXP>(pB + itc[k], a.ga_parts, a.ga_stride);    // (FOLD: fast path without Q - pB is a GA row)
         else fvb[k] = ld<4>(pB + itc[k]);
@@ -271,7 +323,7 @@ __device__ __forceinline__ void update_rel_row(const UpdateArgs &a, int64_t u, U
             for (int k = 0; k < NIT; ++k)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) co_part[wv][(lane + 64 * k) * 4 + e] = gp[k].v[e];
-            co_part[wv][NIT * 256 + lane] = pss;
+            if constexpr (!ADAM) co_part[wv][NIT * 256 + lane] = pss;
             __syncthreads();
             if (wv == j) {                           // the owner adds the partials, wavefront 0 first
 #pragma unroll 1
@@ -280,13 +332,18 @@ __device__ __forceinline__ void update_rel_row(const UpdateArgs &a, int64_t u, U
                     for (int k = 0; k < NIT; ++k)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) gsum[k].v[e] += co_part[w2][(lane + 64 * k) * 4 + e];
-                    ss += co_part[w2][NIT * 256 + lane];
+                    if constexpr (!ADAM) ss += co_part[w2][NIT * 256 + lane];
                 }
             }
             __syncthreads();                         // before the next long row overwrites the partials
         }
     }
     if (!valid) return;
+    if constexpr (ADAM) {
+        adam_tail<NIT>(o, a.lr, st0, row, mrow, srow, d, nit, lane, x, am, av, gsum);
+        adam_reg_out(a, reg, rv, (float)(e1 - e0), a.reg_rel, u, u + a.UE, lane);
+        return;
+    }
     ss = wave_sum(ss) / (float)d;
     if (a.dry) return;
     const float sN = st0 + ss;
@@ -393,8 +450,10 @@ __device__ __forceinline__ UpdateHead update_head(UpdateArgs &a, int nb_ent, int
 // instruction cache together, every launch starts cold, and the full-featured kernel was 11 k instructions.
 // `hd`: update_head(a_in, nb_ent, bid, nblk) of this workgroup (`bid` / `nblk`: its index and the number of workgroups doing
 // update work - the body also runs as one half of a horizontally fused launch, see neg_fwd_update_kernel in kge_neg_gemm.hip).
-template <int NIT, bool SHARDED, int LEAN_>     // LEAN: 0 = everything at run time, 1 = in-place + TransE fast path,
-__device__ __forceinline__ void update_reg_body(const UpdateArgs &a_in, const UpdateHead &hd) {   // 2 = in-place + per-edge gradients
+// ADAM (with SHARDED false, LEAN_ 0): the Adam form - un-sharded, in place, every source mode and the regulariser's norm at run
+// time; a row in both entity traces is updated ONCE with the sum of its two traces (adam_tail).  `o`: unused otherwise.
+template <int NIT, bool SHARDED, int LEAN_, bool ADAM = false>     // LEAN: 0 = everything at run time, 1 = in-place + TransE fast path,
+__device__ __forceinline__ void update_reg_body(const UpdateArgs &a_in, const UpdateHead &hd, const AdamArgs &o = AdamArgs{}) {   // 2 = in-place + per-edge gradients
     using namespace kge;                         // 3 = 1 with Q rows; 4 (round 4) = 0 with the regulariser's norm fixed at 3 - the
     constexpr int LEAN = (LEAN_ == 4 || LEAN_ == 6 || LEAN_ == 7) ? 0 : (LEAN_ == 5 ? 1 : LEAN_); // gradient-emitting (sharded all-to-all) step of every BASELINE recipe
     // 6 (round 4) = 4 narrowed to what the all-to-all engine's step asks for when the model has per-edge gradient rows (RotatE /
@@ -418,6 +477,10 @@ __device__ __forceinline__ void update_reg_body(const UpdateArgs &a_in, const Up
         if (LEAN != 3) a.Q = nullptr;
         a.g0 = a.g1 = a.gs0 = a.gs1 = a.gr = a.gsr = nullptr; a.rid = nullptr; a.dry = 0; a.nd_chunk = 0; a.emit_by_id = 0; a.msg_rows = nullptr;
         a.reg_norm = 3;             // (launch_update sends any other norm to the generic instance)
+    }
+    if constexpr (ADAM) {       // in place: no messages, no stale-row copies, no probe
+        a.emit_ent = 0; a.emit_rel = 0; a.g1 = a.gs0 = a.gs1 = a.gr = a.gsr = nullptr; a.rid = nullptr; a.dry = 0; a.emit_by_id = 0;
+        a.msg_rows = nullptr; a.Hs = a.Ts = a.Rs = a.Ns = nullptr;
     }
     const int lane = LANE();
     const bool reg = a.reg_coef > 0.f && a.reg_norm > 0;
@@ -471,9 +534,13 @@ __device__ __forceinline__ void update_reg_body(const UpdateArgs &a_in, const Up
 #pragma unroll
         for (int k = 0; k < NIT; ++k) itc[k] = min(lane + 64 * k, nit - 1) * 4;
         Pack<4> fva[NIT], fvb[NIT], fvc[NIT], fxr[NIT];
+        Pack<4> am[ADAM ? NIT : 1], av[ADAM ? NIT : 1];     // (ADAM) the row's moments: same record, same round as the row
+        float *mrow = nullptr;
+        if constexpr (ADAM) mrow = o.ent_mom + id * 2 * (int64_t)d;
 #pragma unroll
         for (int k = 0; k < NIT; ++k) {
             x[k] = ld<4>(row + itc[k]);
+            if constexpr (ADAM) { am[k] = ld<4>(mrow + itc[k]); av[k] = ld<4>(mrow + d + itc[k]); }
             fva[k] = ld<4>(pA + itc[k]);
             if constexpr (FOLD) {
                 fvb[k] = ld_parts<KGE_GA_MAXP>(pB + itc[k], (ga0 && !qm) ? a.ga_parts : 1, a.ga_stride);
@@ -654,6 +721,20 @@ __device__ __forceinline__ void update_reg_body(const UpdateArgs &a_in, const Up
 #pragma unroll
             for (int k = 0; k < NIT; ++k) g0[k] = zero_pack<4>();
         }
+        if constexpr (ADAM) {      // one update with g0 + g1 (g0 is zero without a positive trace, g1 without a negative one)
+            if (a.g0) {
+#pragma unroll
+                for (int k = 0; k < NIT; ++k)
+                    if (lane + 64 * k < nit) st<4>(a.g0 + u * (int64_t)a.ld_e + (lane + 64 * k) * 4, g0[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < NIT; ++k)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) g0[k].v[e] += g1[k].v[e];
+            adam_tail<NIT>(o, a.lr, st0, row, mrow, srow, d, nit, lane, x, am, av, g0);
+            adam_reg_out(a, reg, rv, (float)((has_pos ? 1 : 0) + (n1 - n0)), a.reg_ent, u, u, lane);
+            return;
+        }
         // two wave reductions (DPP + readlane, see kge_common.hpp)
         s0 = wave_sum(s0); s1 = wave_sum(s1);
         s0 /= (float)d; s1 /= (float)d;
@@ -730,6 +811,10 @@ __device__ __forceinline__ void update_reg_body(const UpdateArgs &a_in, const Up
         constexpr int COOP_MIN_R = 2 * (NIT <= 2 ? 6 : 2) + 1;
         const bool coop = !(a.transe_fast && !qm) && (!dev_counts || cn.w - 1 >= COOP_MIN_R);
         const int cnt_r = dev_counts ? cn.y : a.UR;
+        if constexpr (ADAM) {
+            if (coop) update_rel_row<NIT, false, 0, true, false, true>(a, u, r0, r1, cnt_r, lane, reg, qm, o);
+            else update_rel_row<NIT, false, 0, false, false, true>(a, u, r0, r1, cnt_r, lane, reg, qm, o);
+        } else
         if constexpr (FOLD) update_rel_row<NIT, SHARDED, LEAN, false, true>(a, u, r0, r1, cnt_r, lane, reg, qm);   // (fast path without Q: never the shared-list instance)
         else if (coop) update_rel_row<NIT, SHARDED, LEAN, true>(a, u, r0, r1, cnt_r, lane, reg, qm);
         else update_rel_row<NIT, SHARDED, LEAN, false>(a, u, r0, r1, cnt_r, lane, reg, qm);

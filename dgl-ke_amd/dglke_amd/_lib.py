@@ -84,6 +84,16 @@ class KgeKnown(C.Structure):
                 ("m_head", c_i64), ("n_rel", c_i64)]
 
 
+class KgeOptim(C.Structure):
+    """kge_optim: the optimizer of kge_step_optim; Adam's moment tables [n, 2, d] hold each row's m, then its v"""
+    _fields_ = [("kind", c_i32), ("beta1", c_f), ("beta2", c_f), ("eps", c_f), ("ent_mom", c_p), ("rel_mom", c_p)]
+
+
+OPT_ADAGRAD, OPT_ADAM = 0, 1
+OPT_IDS = {"Adagrad": OPT_ADAGRAD, "Adam": OPT_ADAM}
+PHASE_ALL = 15              # the four phase groups: the whole strict step in one call
+ADAM_MAX_DIM = 1024         # Adam runs in the register-resident update: row widths are multiples of 4, at most this many floats
+
 KNOWN_SCORE = -1.0e6        # KGE_KNOWN_SCORE: the score a known pair takes in the loss and in kge_step_out.neg_score
 
 
@@ -163,6 +173,8 @@ _SIGNATURES = {
                                    c_sz, C.POINTER(KgeSamplerJob), C.POINTER(KgeKnown), c_p, c_sz, c_p]),
     "kge_step_phase_known": (c_i, [C.POINTER(KgeHParams), C.POINTER(KgeTables), C.POINTER(KgeBatch), C.POINTER(KgeStepOut), c_p,
                                    c_sz, c_i, C.POINTER(KgeKnown), c_p, c_sz, c_p]),
+    "kge_step_optim": (c_i, [C.POINTER(KgeHParams), C.POINTER(KgeOptim), C.POINTER(KgeTables), C.POINTER(KgeBatch),
+                             C.POINTER(KgeStepOut), c_p, c_sz, c_i, C.POINTER(KgeKnown), c_p, c_sz, c_p]),
     "kge_pipe_create": (c_i, [C.POINTER(c_p)]),
     "kge_pipe_destroy": (c_i, [c_p]),
     "kge_step_async_workspace_bytes": (c_sz, [C.POINTER(KgeHParams), c_i, c_i, c_i, c_i, c_i, c_i]),

@@ -17,7 +17,10 @@ class StepEngine(object):
                  double_entity_emb=False, double_relation_emb=False, neg_adversarial_sampling=False,
                  adversarial_temperature=1.0, regularization_coef=0.0, regularization_norm=3,
                  loss_genre='Logsigmoid', pairwise=False, margin=1.0, flags=0,
-                 tables=None, shards=None):
+                 tables=None, shards=None, optimizer='Adagrad', adam_betas=(0.9, 0.999), adam_eps=1e-8, moments=None):
+        """optimizer 'Adam': lazy row-sparse Adam with a per-row step count (include/kge_hip.h, kge_step_optim) - the state
+        tables hold the counts, the engine owns the moment tables ent_mom [n_ent, 2, d_e] / rel_mom [n_rel, 2, d_r] (`moments`:
+        a pair the caller shares between engines, as `tables` shares the rows and the state)."""
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise _lib.KgeError("StepEngine needs a CUDA (HIP) device; there is no CPU fallback")
@@ -99,6 +102,13 @@ class StepEngine(object):
                 if len(tables) < 6:
                     raise _lib.KgeError("TransR needs tables = (ent, ent_state, rel, rel_state, proj, proj_state)")
                 self.proj, self.proj_state = tables[4], tables[5]
+        self.optimizer = optimizer
+        self.opt = None
+        self.ent_mom = self.rel_mom = None
+        if optimizer not in _lib.OPT_IDS:
+            raise _lib.KgeError("optimizer %r: Adagrad or Adam" % (optimizer,))
+        if optimizer == 'Adam':
+            self._init_adam(adam_betas, adam_eps, moments)
         self._bind_tables()
         self.loss4 = torch.zeros(4, dtype=torch.float32, device=self.device)
         self.loss_accum = torch.zeros(4 * _lib.ACC_SLOTS, dtype=torch.float32, device=self.device)
@@ -116,7 +126,7 @@ class StepEngine(object):
         self._kmask_bytes = 0
 
     @classmethod
-    def from_args(cls, args, model_name, n_entities, n_relations, device, tables=None, shards=None, **given):
+    def from_args(cls, args, model_name, n_entities, n_relations, device, tables=None, shards=None, moments=None, **given):
         """the engine of an argument namespace (dglke_train's, or a hand-made one: what is missing or None takes the reference's
         default).  `given`: constructor arguments the caller holds itself (KEModel: hidden_dim, gamma, the double_* flags).  The
         step flags are decided here and nowhere else: degree-sampled negatives with --neg_deg_sample for every model, the
@@ -133,7 +143,50 @@ class StepEngine(object):
                    kw['double_entity_emb'], kw['double_relation_emb'], bool(arg('neg_adversarial_sampling')),
                    arg('adversarial_temperature', 1.0), arg('regularization_coef', 0.0),
                    getattr(args, 'regularization_norm', 3) or 0, arg('loss_genre', 'Logsigmoid'), bool(arg('pairwise')),
-                   getattr(args, 'margin', 1.0), flags=flags, tables=tables, shards=shards)
+                   getattr(args, 'margin', 1.0), flags=flags, tables=tables, shards=shards,
+                   optimizer=arg('optimizer', 'Adagrad'), moments=moments,
+                   adam_betas=(getattr(args, 'adam_beta1', None) if getattr(args, 'adam_beta1', None) is not None else 0.9,
+                               getattr(args, 'adam_beta2', None) if getattr(args, 'adam_beta2', None) is not None else 0.999),
+                   adam_eps=arg('adam_eps', 1e-8))
+
+    def _init_adam(self, betas, eps, moments):
+        if self.model_name in ('RESCAL', 'TransR'):
+            raise _lib.KgeError("Adam is not available for RESCAL / TransR (their relation-side tables are updated by kernels of "
+                                "their own)")
+        if self.shards is not None:
+            raise _lib.KgeError("Adam runs the strict step on local tables only (no sharded tables)")
+        if self.d_e % 4 or self.d_r % 4 or max(self.d_e, self.d_r) > _lib.ADAM_MAX_DIM:
+            raise _lib.KgeError("Adam needs row widths that are multiples of 4 and at most %d floats (got %d, %d)"
+                                % (_lib.ADAM_MAX_DIM, self.d_e, self.d_r))
+        b1, b2 = float(betas[0]), float(betas[1])
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise _lib.KgeError("Adam needs beta1 and beta2 in [0, 1) (got %g, %g)" % (b1, b2))
+        if not float(eps) > 0.0:
+            raise _lib.KgeError("Adam needs eps > 0 (got %g)" % float(eps))
+        if moments is not None:
+            self.ent_mom, self.rel_mom = moments
+        else:
+            need = 4 * 2 * (self.ent.shape[0] * self.d_e + self.rel.shape[0] * self.d_r)
+            try:
+                self.ent_mom = torch.zeros(self.ent.shape[0], 2, self.d_e, dtype=torch.float32, device=self.device)
+                self.rel_mom = torch.zeros(self.rel.shape[0], 2, self.d_r, dtype=torch.float32, device=self.device)
+            except RuntimeError as e:
+                raise _lib.KgeError("Adam: the moment tables need %d bytes (twice the embedding tables) and could not be "
+                                    "allocated: %s" % (need, e))
+        if tuple(self.ent_mom.shape) != (self.ent.shape[0], 2, self.d_e) or tuple(self.rel_mom.shape) != (self.rel.shape[0], 2, self.d_r):
+            raise _lib.KgeError("Adam: moment tables must be [n_ent, 2, d_e] and [n_rel, 2, d_r]")
+        o = _lib.KgeOptim()
+        o.kind, o.beta1, o.beta2, o.eps = _lib.OPT_ADAM, b1, b2, float(eps)
+        o.ent_mom, o.rel_mom = ptr(self.ent_mom), ptr(self.rel_mom)
+        self.opt = o
+
+    def _step_optim(self, batch, out, ws, phases):
+        """kge_step_optim: the strict step (or some of its phase groups) with this engine's optimizer"""
+        km, kn, kb = None, None, 0
+        if self._known is not None:
+            km, kn, kb = self.known_mask_for(batch), C.byref(self._known[0]), self._kmask_bytes
+        check(lib().kge_step_optim(C.byref(self.hp), C.byref(self.opt), C.byref(self.tb), C.byref(batch.c), C.byref(out), ptr(ws),
+                                   self._ws_bytes, phases, kn, ptr(km), kb, stream_ptr()))
 
     def attach_known(self, index):
         """leave the triples of `index` (known.KnownIndex on this engine's device; None detaches) out of every step's negatives:
@@ -180,13 +233,26 @@ class StepEngine(object):
         torch.nn.init.uniform_(self.rel, -self.emb_init, self.emb_init)
         self.ent_state.zero_()
         self.rel_state.zero_()
+        if getattr(self, 'ent_mom', None) is not None:
+            self.ent_mom.zero_()
+            self.rel_mom.zero_()
         if self.proj is not None:                 # TransRScore.reset_parameters: projection_emb.init(1.0)
             torch.nn.init.uniform_(self.proj, -1.0, 1.0)
             self.proj_state.zero_()
 
-    def load_tables(self, ent, rel, ent_state=None, rel_state=None):
+    def load_tables(self, ent, rel, ent_state=None, rel_state=None, ent_mom=None, rel_mom=None):
+        """rows, state (Adagrad: running mean squares; Adam: per-row counts) and, under Adam, the moment tables [n, 2, d];
+        what is not given is zeroed"""
         self.ent.copy_(torch.as_tensor(ent))
         self.rel.copy_(torch.as_tensor(rel))
+        if self.opt is None and (ent_mom is not None or rel_mom is not None):
+            raise _lib.KgeError("load_tables: moment tables belong to an engine with optimizer='Adam'")
+        if self.opt is not None:
+            for dst, src in ((self.ent_mom, ent_mom), (self.rel_mom, rel_mom)):
+                if src is None:
+                    dst.zero_()
+                else:
+                    dst.copy_(torch.as_tensor(src).reshape(dst.shape))
         if ent_state is None:
             self.ent_state.zero_()
         else:
@@ -220,6 +286,12 @@ class StepEngine(object):
                 setattr(out, k, ptr(t))
         if sample_job is not None and (self.shards is not None or emit is not None):
             raise _lib.KgeError("the sampler tail rides on the strict single-table step only")
+        if self.opt is not None:
+            if sample_job is not None or emit is not None:
+                raise _lib.KgeError("Adam: the sampler-tail step and the gradient-emitting step have no Adam form "
+                                    "(sample_job / emit must be None)")
+            self._step_optim(batch, out, ws, _lib.PHASE_ALL)
+            return
         if self._known is not None:
             if self.shards is not None or emit is not None:
                 raise _lib.KgeError("known-triple exclusion runs on the strict single-table step only")
@@ -257,7 +329,9 @@ class StepEngine(object):
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
         ev[0].record()
         for k, ph in enumerate((_lib.PHASE_GATHER, _lib.PHASE_FORWARD, _lib.PHASE_BACKWARD, _lib.PHASE_UPDATE)):
-            if self._known is not None:
+            if self.opt is not None:
+                self._step_optim(batch, out, ws, ph)
+            elif self._known is not None:
                 km = self.known_mask_for(batch)
                 check(lib().kge_step_phase_known(C.byref(self.hp), C.byref(self.tb), C.byref(batch.c), C.byref(out), ptr(ws),
                                                  self._ws_bytes, ph, C.byref(self._known[0]), ptr(km), self._kmask_bytes,
@@ -288,6 +362,8 @@ class StepEngine(object):
         stream capture ends)."""
         if self.shards is not None:
             raise _lib.KgeError("--async_update is not available on peer-to-peer sharded tables")
+        if self.opt is not None:
+            raise _lib.KgeError("Adam: the --async_update pipeline has no Adam form")
         if self._known is not None:
             raise _lib.KgeError("known-triple exclusion is not available in the --async_update pipeline")
         if self._pipe is None:

@@ -118,6 +118,14 @@ class ArgParser(argparse.ArgumentParser):
         a('--edge_importance_on_device', action='store_true',
           help='with --has_edge_importance: hand the weight column of train.txt to the weighted device sampler instead of the host '
                'sampler (same refusals as --subsampling_weight)')
+        a('--optimizer', default='Adagrad', choices=['Adagrad', 'Adam'],
+          help='Adagrad: the reference\'s row-sparse Adagrad.  Adam: lazy row-sparse Adam with a per-row step count (the rule of '
+               'DGL\'s sparse Adam) in the strict step\'s update launch; --lr is its step size (1e-4 ... 1e-3 in the published Adam '
+               'recipes).  Moment tables take twice the embedding tables\' memory.  One GPU; not for RESCAL / TransR, not with '
+               '--async_update_pipeline or --async_update_rel; row widths multiples of 4, at most 1024 floats')
+        a('--adam_beta1', type=float, default=0.9, help='--optimizer Adam: decay of the first moment')
+        a('--adam_beta2', type=float, default=0.999, help='--optimizer Adam: decay of the second moment')
+        a('--adam_eps', type=float, default=1e-8, help='--optimizer Adam: the term added to the root of the second moment')
         a('--dist_slack', type=float, default=None,
           help='--dist_mode a2a: initial capacity of an owner bucket as a multiple of the mean share of a batch\'s unique entities '
                '(default 1.5, or KGE_DIST_SLACK); buckets grow by themselves when a group of batches needs more')
@@ -429,8 +437,8 @@ class _Trainer(object):
                     timed = None
                 t_interval = 0.0
                 if self.world == 1:
-                    print('[proc {}]sample+forward+backward+update (fused HIP step{}{}{}{}): {:.3f}'.format(
-                        0, ', --async_update pipeline' if self.lanes[0].async_update else '',
+                    print('[proc {}]sample+forward+backward+update (fused HIP step, {}{}{}{}{}): {:.3f}'.format(
+                        0, args.optimizer, ', --async_update pipeline' if self.lanes[0].async_update else '',
                         ', known training triples excluded' if self.known is not None else '',
                         {None: '', 'subsampling': ', subsampling weights', 'file': ', edge importance on the device'}[self.weighted],
                         '' if self.n_lanes == 1 else ', %d concurrent trainers' % self.n_lanes, t_train))
@@ -497,7 +505,11 @@ class Trainer(_Trainer):
         # the lanes share the tables (TransR: the projection table too); every lane trains on its own random share of the triples
         parts = self.split(self.n_lanes, refusal="every trainer needs at least batch_size training triples: %(triples)d triples over "
                            "%(n)d trainer(s) < batch_size %(batch)d - lower --batch_size or --num_proc")
-        self.lanes = [_Lane(self, k, m.engine if k == 0 else self.make_engine(tables=m.tables()), parts[k])
+        # (... and, under --optimizer Adam, the moment tables, exactly as they share the state)
+        shared = dict(tables=m.tables())
+        if m.engine.opt is not None:
+            shared['moments'] = (m.engine.ent_mom, m.engine.rel_mom)
+        self.lanes = [_Lane(self, k, m.engine if k == 0 else self.make_engine(**shared), parts[k])
                       for k in range(self.n_lanes)]
         if args.exclude_positive:
             # ONE index of the whole training split, sorted on the device once; the lanes' engines only read it
@@ -848,6 +860,31 @@ def check_weighted_device_sampler(args):
                        "there is no host sampler for this flag" % (flag, DeviceSampler.MAX_ELEMENTS, 2 * B + (B // chunk) * N))
 
 
+def check_optimizer(args):
+    """--optimizer Adam runs in the strict single-table step's update launch (kge_step_optim); refused here, before anything is
+    loaded: what that step does not cover"""
+    if getattr(args, 'optimizer', 'Adagrad') != 'Adam':
+        return
+    if args.model_name in ('RESCAL', 'TransR'):
+        raise KgeError("--optimizer Adam is not available for %s (RESCAL / TransR update their relation-side tables with kernels of "
+                       "their own)" % args.model_name)
+    if len(args.gpu) > 1:
+        raise KgeError("--optimizer Adam is not available on more than one GPU (--gpu takes one entry)")
+    if args.async_update_pipeline or args.async_update_rel:
+        raise KgeError("--optimizer Adam is not available in the one-step-stale pipeline (--async_update_pipeline / "
+                       "--async_update_rel); plain --async_update runs the strict step and is fine")
+    d_e = args.hidden_dim * (2 if args.double_ent else 1)
+    d_r = args.hidden_dim * (2 if args.double_rel else 1)
+    if d_e % 4 or d_r % 4 or max(d_e, d_r) > _lib.ADAM_MAX_DIM:
+        raise KgeError("--optimizer Adam: row widths must be multiples of 4 and at most %d floats (entity %d, relation %d)"
+                       % (_lib.ADAM_MAX_DIM, d_e, d_r))
+    if not (0.0 <= args.adam_beta1 < 1.0 and 0.0 <= args.adam_beta2 < 1.0):
+        raise KgeError("--optimizer Adam: --adam_beta1 and --adam_beta2 must be in [0, 1) (got %g, %g)"
+                       % (args.adam_beta1, args.adam_beta2))
+    if not args.adam_eps > 0.0:
+        raise KgeError("--optimizer Adam: --adam_eps must be positive (got %g)" % args.adam_eps)
+
+
 def check_loss_flags(args):
     """--loss_genre Softmax (cross-entropy of the positive against its row): the softmax is the weighting and the row is the pairing"""
     if args.loss_genre != 'Softmax':
@@ -913,6 +950,7 @@ def main(argv=None, before_train=None):
     check_quate(args)                            # before anything is loaded or created
     check_pairre(args)                           # before anything is loaded or created
     check_weighted_device_sampler(args)          # before anything is loaded or created
+    check_optimizer(args)                        # before anything is loaded or created
     if args.neg_deg_sample_eval:                # before anything is loaded or created
         if len(args.gpu) > 1:
             raise KgeError("--neg_deg_sample_eval is not available on sharded tables")

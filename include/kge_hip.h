@@ -850,6 +850,46 @@ int kge_step_fused_known(const kge_hparams *hp, const kge_tables *tb, const kge_
 int kge_step_phase_known(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
                          size_t ws_bytes, int phases, const kge_known *known, uint32_t *mask, size_t mask_bytes, void *stream);
 
+/* ---- the optimizer as an argument of the strict step: --optimizer Adam (csrc/kge_adam.hip) ----
+ * kge_step_optim is the strict single-table step (kge_step_fused / kge_step_phase, with or without a known-triple index) whose
+ * update launch is chosen by `opt->kind`:
+ *  KGE_OPT_ADAGRAD  the existing step: bit for bit the tables and state of kge_step_fused / kge_step_fused_known (all four phase
+ *                   bits) or of kge_step_phase / kge_step_phase_known; beta1, beta2, eps and the moment pointers are ignored.
+ *  KGE_OPT_ADAM     lazy (row-sparse) Adam with a PER-ROW step count, the rule of DGL's sparse Adam.  G = the sum of a table row's
+ *                   gradient traces in the step, formed exactly as the Adagrad step forms them (positive trace, then negative
+ *                   trace, regulariser terms where the Adagrad step adds them; a relation row: its relation trace).  For a row x
+ *                   touched by the step:
+ *                       c  = min(c + 1, 2^24)                 per-row count of updates; a float holds it exactly
+ *                       m  = beta1 m + (1 - beta1) G
+ *                       v  = beta2 v + (1 - beta2) G*G
+ *                       x -= lr (m / (1 - beta1^c)) / (sqrt(v / (1 - beta2^c)) + eps)
+ *                   One update per row per step: a row in both entity traces is updated once with the sum (the Adagrad step
+ *                   applies its two traces one after the other).  Rows the step does not touch keep value, moments and count bit
+ *                   for bit.  A touched row with G == 0 still counts, decays its moments and moves by its momentum; with
+ *                   m = v = 0 too it stays exactly where it is (0 / (0 + eps) = 0).  lr is kge_hparams.lr; kge_hparams.eps is
+ *                   not read.  The count is per row, not a global step number: nothing in a step depends on a host-side value,
+ *                   so a captured graph of many steps replays like any other.
+ * Storage: kge_tables.ent_state [n_ent] and rel_state [n_rel] hold the counts c (zero at start); ent_mom [n_ent, 2, d_e] and
+ * rel_mom [n_rel, 2, d_r] hold each row's m, then its v, contiguous, zero at start - three times the table memory.
+ * `phases`: as in kge_step_phase; all four bits = the whole strict step in one call.  `known` may be NULL (mask is then ignored),
+ * else as in kge_step_fused_known.  The workspace is that of kge_step_workspace_bytes - Adam needs no more.  TransE_l1 under Adam
+ * sums its backward's GN partials in the stand-alone reduction launch (the Adagrad step folds them into its update).
+ * KGE_ERR_ARG before any launch, the message naming this entry and the reason: RESCAL / TransR (their relation-side tables are
+ * updated by kernels of their own), null moments, a beta outside [0, 1), eps <= 0, a row width that is no multiple of 4 or
+ * beyond 1024 floats (the domain of the register-resident update), an unknown kind, a bad phase mask.
+ * `hip_stream`: the stream of the launches, the last argument as everywhere.  The sharded step, kge_step_grads, kge_step_async and
+ * the sampler-tail step have no Adam form. */
+#define KGE_OPT_ADAGRAD 0
+#define KGE_OPT_ADAM 1
+typedef struct kge_optim {
+    int32_t kind;               /* KGE_OPT_ADAGRAD 0, KGE_OPT_ADAM 1 */
+    float beta1, beta2, eps;    /* 0.9, 0.999, 1e-8 */
+    float *ent_mom, *rel_mom;   /* [n_ent, 2, d_e], [n_rel, 2, d_r] */
+} kge_optim;
+int kge_step_optim(const kge_hparams *hp, const kge_optim *opt, const kge_tables *tb, const kge_batch *b, const kge_step_out *out,
+                   void *ws, size_t ws_bytes, int phases, const kge_known *known, uint32_t *mask, size_t mask_bytes,
+                   void *hip_stream);
+
 /* ---- test support: not part of the stable boundary ----
  * kge_debug_carve: while set (per calling thread), every buffer that an entry point or a *_workspace_bytes function carves from a
  * workspace is recorded as trace[2k] = offset from the base that carve started at, trace[2k + 1] = bytes (HOST memory, room for
