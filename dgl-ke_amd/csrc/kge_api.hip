@@ -50,8 +50,13 @@ struct Carver {
 };
 
 int check_model(int model, int d_e, int d_r) {
-    if (model < KGE_TRANSE_L1 || (model > KGE_TRANSR && model != KGE_QUATE && model != KGE_PAIRRE))
+    if (model < KGE_TRANSE_L1 || (model > KGE_TRANSR && model != KGE_QUATE && model != KGE_PAIRRE && model != KGE_TRANSH))
         return fail(KGE_ERR_ARG, "unknown model %d", model);
+    if (model == KGE_TRANSH) {         // every path is a matrix-core product: 16-byte rows
+        if (d_e < 4 || d_e % 4 || (int64_t)d_r != 2 * (int64_t)d_e)
+            return fail(KGE_ERR_ARG, "TransH needs d_e >= 4, d_e %% 4 == 0 and d_r == 2 * d_e, r = [d | w] (got %d, %d)", d_e, d_r);
+        return KGE_OK;
+    }
     if (model == KGE_PAIRRE) {
         if (d_e <= 0 || (int64_t)d_r != 2 * (int64_t)d_e)
             return fail(KGE_ERR_ARG, "PairRE needs d_e > 0 and d_r == 2 * d_e, r = [rH | rT] (got %d, %d)", d_e, d_r);
@@ -89,6 +94,11 @@ int no_quate(const char *who) { return fail(KGE_ERR_ARG, "%s: not available for 
 // PairRE likewise, and it has no relation ranking (the score is not a product of a query row and the relation row)
 int no_pairre(const char *who) {
     return fail(KGE_ERR_ARG, "%s: not available for PairRE (strict step on local tables, single-table entity ranking and top-K)", who);
+}
+
+// TransH likewise
+int no_transh(const char *who) {
+    return fail(KGE_ERR_ARG, "%s: not available for TransH (strict step on local tables, single-table entity ranking and top-K)", who);
 }
 
 inline float rot_div_of(float emb_init) { return (float)((double)emb_init / M_PI); }
@@ -159,6 +169,61 @@ int pairre_norms(const float *base, const int64_t *idx, int64_t n, int d_e, floa
     return launch_pairre_edge_fwd(e, s);
 }
 
+// TransH (kge_transh.hip): the edge forward of B edges whose rows come from src, into the stacked operand of chunks of `chunk` rows
+void fill_transh_edge(TranshEdgeArgs &e, const EdgeSrc &src, int B, int chunk, int d_e, int neg_head, float gamma, float *P, float *AW,
+                      float *alpha, float *cw) {
+    e = TranshEdgeArgs{};
+    e.src = src; e.B = B; e.chunk = chunk; e.d_e = d_e; e.neg_head = neg_head; e.gamma = gamma; e.pos_score = P;
+    e.AW = AW; e.alpha = alpha; e.cw = cw;
+}
+// |x|^2 of n candidate rows base + (idx ? idx[j] : j) * d_e
+int transh_norms(const float *base, const int64_t *idx, int64_t n, int d_e, float *beta, hipStream_t s) {
+    TranshEdgeArgs e{};
+    e.d_e = d_e; e.nbase = base; e.nidx = idx; e.n_neg = (int)n; e.beta = beta;
+    return launch_transh_edge_fwd(e, s);
+}
+// one chunked scoring block: the stacked operand, its row statistics, the candidate rows and theirs, and the blocks behind them
+struct TranshBlock {
+    int C, chunk, N, d_e; float gamma;
+    const float *AW, *alpha, *cw;                     // [C, 2 chunk, d_e], [C*chunk] x 2
+    const float *nbase; const int64_t *nidx; const float *beta;
+    float *PQ;                                        // [C, 2 chunk, N] raw products
+};
+void fill_transh_neg(TranshNegArgs &n, const TranshBlock &k) {
+    n = TranshNegArgs{};
+    n.C = k.C; n.chunk = k.chunk; n.N = k.N; n.d_e = k.d_e; n.gamma = k.gamma; n.alpha = k.alpha; n.cw = k.cw; n.beta = k.beta; n.PQ = k.PQ;
+}
+// p | q = [A ; W^] . N^T on the forward tiles of kge_neg_gemm.hip in their DistMult form (2 chunk rows per chunk), then S
+int transh_products(const TranshBlock &k, hipStream_t s) {
+    GemmArgs g; fill_gemm(g, KGE_DISTMULT, k.C, 2 * k.chunk, k.N, k.d_e, k.gamma, k.AW, k.nbase, k.nidx);
+    g.S = k.PQ;
+    KGE_TRY(launch_neg_fwd_gemm(g, s));
+    return KGE_OK;
+}
+int transh_scores(const TranshBlock &k, float *S, hipStream_t s) {
+    if (int rc = transh_products(k, s)) return rc;
+    TranshNegArgs n; fill_transh_neg(n, k);
+    n.S = S;
+    KGE_TRY(launch_transh_score(n, s));
+    return KGE_OK;
+}
+// G = dL/dS -> the products GAW = Ga | Gw^ [C, 2 chunk, d_e] and GN [C*N, d_e] (their row / column terms: rs, kap, cs; the edge
+// backward adds them).  The backward tiles of kge_neg_gemm.hip in their DistMult form with K = 2 chunk; beyond the rows a tile's
+// workgroup indexes (GB_MAXK) the pairwise kernels, which take any size
+int transh_neg_bwd(const TranshBlock &k, const float *G, float *PQc, float *rs, float *kap, float *cs, float *GAW, float *GN, hipStream_t s) {
+    TranshNegArgs n; fill_transh_neg(n, k);
+    n.G = G; n.PQc = PQc; n.rs = rs; n.kap = kap; n.cs = cs;
+    KGE_TRY(launch_transh_coef(n, s));
+    GemmArgs g; fill_gemm(g, KGE_DISTMULT, k.C, 2 * k.chunk, k.N, k.d_e, k.gamma, k.AW, k.nbase, k.nidx);
+    g.W = PQc; g.GA = GAW; g.GN = GN;
+    if ((2 * k.chunk > k.N ? 2 * k.chunk : k.N) > KGE_NEG_BWD_GEMM_MAXK) {      // (tested here: any error of the launcher stays an error)
+        NegArgs na; fill_pair(na, KGE_DISTMULT, k.C, 2 * k.chunk, k.N, k.d_e, k.gamma, k.AW, k.nbase, k.nidx);
+        na.W = PQc; na.GA = GAW; na.GN = GN;
+        KGE_TRY(launch_neg_bwd_pair(na, s));
+    } else KGE_TRY(launch_neg_bwd_gemm(g, s));
+    return KGE_OK;
+}
+
 // SimplE, modular backward: no gradient through a saturated clamp
 __global__ void clamp_mask_kernel(const float *dneg, const float *score, float c, float *W, int64_t n) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -225,6 +290,11 @@ int kge_score_pos(int model, const float *h, const float *r, const float *t, int
         KGE_TRY(launch_pairre_edge_fwd(e, (hipStream_t)stream));
         return KGE_OK;
     }
+    if (model == KGE_TRANSH) {
+        TranshEdgeArgs e; fill_transh_edge(e, EdgeSrc{h, nullptr, t, nullptr, r, nullptr}, (int)B, (int)B, d_e, 0, gamma, out, nullptr, nullptr, nullptr);
+        KGE_TRY(launch_transh_edge_fwd(e, (hipStream_t)stream));
+        return KGE_OK;
+    }
     EdgeFwdArgs a;
     fill_edge(a, EdgeSrc{h, nullptr, t, nullptr, r, nullptr}, model, (int)B, d_e, d_r, 0, gamma, rot_div_of(emb_init));
     a.pos_score = out;
@@ -257,6 +327,12 @@ int kge_score_pos_bwd(int model, const float *h, const float *r, const float *t,
         KGE_TRY(launch_pairre_edge_bwd(e, (hipStream_t)stream));
         return KGE_OK;
     }
+    if (model == KGE_TRANSH) {
+        TranshBwdArgs e{};
+        e.src = EdgeSrc{h, nullptr, t, nullptr, r, nullptr}; e.B = (int)B; e.chunk = (int)B; e.d_e = d_e; e.dpos = dpos; e.GH = gh; e.GT = gt; e.GR = gr;
+        KGE_TRY(launch_transh_edge_bwd(e, (hipStream_t)stream));
+        return KGE_OK;
+    }
     EdgeBwdArgs a;
     fill_edge_bwd(a, EdgeSrc{h, nullptr, t, nullptr, r, nullptr}, model, (int)B, d_e, d_r, 0, gamma, rot_div_of(emb_init), dpos, nullptr);
     a.clamp_pos = 1; a.GH = gh; a.GT = gt; a.GR = gr;
@@ -265,7 +341,15 @@ int kge_score_pos_bwd(int model, const float *h, const float *r, const float *t,
 }
 
 // the workspace of the modular negative-score entry points (forward and backward share it)
-struct NegBufs { float *A, *asq, *bsq, *W, *GA, *GNp, *PW, *PGW, *Pnrm; };
+struct TranshBufs { float *AW, *cw, *PQ, *PQc, *rs, *kap, *cs, *GAW; };
+// TransH: the stacked operand and its products' blocks, for B edges in chunks against CN candidate rows, N per chunk
+static void carve_transh(Carver &cv, TranshBufs &t, size_t B, size_t CN, size_t N, size_t d_e) {
+    t.AW = cv.f(2 * B * d_e); t.cw = cv.f(B);               // (a, w^) stacked; w^ . a (|a|^2, |n|^2: the asq / bsq entries)
+    t.PQ = cv.f(2 * B * N); t.PQc = cv.f(2 * B * N);        // raw p | q; P' | Q'
+    t.rs = cv.f(B); t.kap = cv.f(B); t.cs = cv.f(CN);       // row and column terms of the backward
+    t.GAW = cv.f(2 * B * d_e);                              // Ga | Gw^ products
+}
+struct NegBufs { float *A, *asq, *bsq, *W, *GA, *GNp, *PW, *PGW, *Pnrm; TranshBufs th; };
 static size_t carve_neg(Carver &cv, NegBufs &w, int model, int C, int chunk, int N, int d_e) {
     const size_t B = (size_t)C * chunk;
     w.A = cv.f(B * d_e);                              // pos-side vectors
@@ -275,6 +359,8 @@ static size_t carve_neg(Carver &cv, NegBufs &w, int model, int C, int chunk, int
     w.GNp = neg_bwd_lc_supported(model, d_e) ? cv.f(neg_bwd_lc_partial_floats(model, C, chunk, N, d_e)) : nullptr;
     w.PW = w.PGW = w.Pnrm = nullptr;
     if (model == KGE_PAIRRE) { w.PW = cv.f(B * d_e); w.PGW = cv.f(B * d_e); w.Pnrm = cv.f((size_t)C * N); }   // w, Gw, candidate norms
+    w.th = TranshBufs{};
+    if (model == KGE_TRANSH) carve_transh(cv, w.th, B, (size_t)C * N, (size_t)N, (size_t)d_e);
     return cv.off;
 }
 
@@ -296,6 +382,13 @@ static int neg_prepare(int model, int neg_head, const float *pos_side, const flo
         PairreEdgeArgs e; fill_pairre_edge(e, EdgeSrc{pos_side, nullptr, pos_side, nullptr, rel, nullptr}, B, d_e, neg_head, gamma, nullptr, w.A, w.PW);
         e.nbase = neg; e.n_neg = C * N; e.nrm = w.Pnrm;
         KGE_TRY(launch_pairre_edge_fwd(e, s));
+        return KGE_OK;
+    }
+    if (model == KGE_TRANSH) {         // the stacked (a, w^) with its row statistics and |n|^2 of every candidate row, one launch
+        TranshEdgeArgs e; fill_transh_edge(e, EdgeSrc{pos_side, nullptr, pos_side, nullptr, rel, nullptr}, B, chunk, d_e, neg_head, gamma, nullptr,
+                                           w.th.AW, w.asq, w.th.cw);
+        e.nbase = neg; e.n_neg = C * N; e.beta = w.bsq;
+        KGE_TRY(launch_transh_edge_fwd(e, s));
         return KGE_OK;
     }
     EdgeFwdArgs a;
@@ -322,6 +415,8 @@ int kge_score_neg_fwd(int model, int neg_head, const float *pos_side, const floa
         PairreNegArgs n; fill_pairre_neg(n, C, chunk, N, d_e, gamma, w.A, w.PW, neg, nullptr, w.Pnrm);
         n.S = out;
         KGE_TRY(launch_pairre_neg_fwd(n, s));
+    } else if (model == KGE_TRANSH) {
+        if (int rc = transh_scores(TranshBlock{C, chunk, N, d_e, gamma, w.th.AW, w.asq, w.th.cw, neg, nullptr, w.bsq, w.th.PQ}, out, s)) return rc;
     } else if (mf) {
         GemmArgs g; fill_gemm(g, model, C, chunk, N, d_e, gamma, w.A, neg, nullptr);
         g.S = out; g.asq = w.asq; g.bsq = w.bsq;
@@ -359,6 +454,18 @@ int kge_score_neg_bwd(int model, int neg_head, const float *pos_side, const floa
         e.GA = w.GA; e.GW = w.PGW; e.GR = g_rel;
         if (neg_head) e.GT = g_pos_side; else e.GH = g_pos_side;
         KGE_TRY(launch_pairre_edge_bwd(e, s));
+        return KGE_OK;
+    }
+    if (model == KGE_TRANSH) {
+        const TranshBlock k{C, chunk, N, d_e, gamma, w.th.AW, w.asq, w.th.cw, neg, nullptr, w.bsq, w.th.PQ};
+        if (int rc = transh_products(k, s)) return rc;
+        if (int rc = transh_neg_bwd(k, dneg, w.th.PQc, w.th.rs, w.th.kap, w.th.cs, w.th.GAW, g_neg, s)) return rc;
+        TranshBwdArgs e{};
+        e.src = EdgeSrc{pos_side, nullptr, pos_side, nullptr, rel, nullptr}; e.B = B; e.chunk = chunk; e.d_e = d_e; e.neg_head = neg_head;
+        e.GAW = w.th.GAW; e.rs = w.th.rs; e.kap = w.th.kap; e.GR = g_rel;
+        if (neg_head) e.GT = g_pos_side; else e.GH = g_pos_side;
+        e.nbase = neg; e.n_neg = C * N; e.cs = w.th.cs; e.GN = g_neg;
+        KGE_TRY(launch_transh_edge_bwd(e, s));
         return KGE_OK;
     }
     const float *Wuse = dneg;
@@ -532,6 +639,7 @@ struct StepBufs {
     float *HP, *TP, *Q, *SG, *DQ, *TR1, *TR2, *GP, *gs0, *gs1, *k0, *k1, *TGNp, *gs1p; signed char *Z;   // TransR
     float *row_pos, *row_neg, *reg_ent, *reg_rel, *GNp, *Hc, *Tc, *Rc;
     float *PW, *PGW, *Pnrm;                                                         // PairRE: w, Gw [B, d_e], candidate norms [C * N]
+    TranshBufs th;                                                                  // TransH
 };
 
 // Ns: the SAMPLED negatives per chunk (kge_batch.N).  copies: room for PREP's dense h / t / r rows (the async pipeline)
@@ -573,6 +681,7 @@ static size_t carve_step(Carver &cv, StepBufs &w, const kge_hparams *hp, int B_,
         w.GNp = cv.f(neg_bwd_lc_partial_floats(hp->model, C, chunk, N, hp->d_e));
     if (copies) { w.Hc = cv.f(B * d_e); w.Tc = cv.f(B * d_e); w.Rc = cv.f(B * d_r); }
     if (hp->model == KGE_PAIRRE) { w.PW = cv.f(B * d_e); w.PGW = cv.f(B * d_e); w.Pnrm = cv.f(CN); }
+    if (hp->model == KGE_TRANSH) carve_transh(cv, w.th, B, CN, (size_t)N, d_e);
     return cv.off;
 }
 
@@ -721,6 +830,9 @@ struct Step {
     TransRArgs tr; EdgeFwdArgs ef; GemmArgs g; NegArgs na;
     int setup(void *ws, size_t ws_bytes), phase_prep(), prep_transr(), prep_rescal(), phase_fwd(), fwd_gemm(), phase_bwd(), bwd_neg_gemm();
     int bwd_transr(), bwd_rescal(), phase_update(); void fill_score(), fill_step_loss(LossArgs &la);
+    TranshBlock transh_block() const {
+        return TranshBlock{b->C, b->chunk, p.N, hp->d_e, hp->gamma, w.th.AW, w.asq, w.th.cw, w.Bn, nullptr, w.bsq, w.th.PQ};
+    }
 };
 
 // argument checks, then the plan, the workspace and the argument blocks every phase shares
@@ -900,6 +1012,13 @@ int Step::phase_prep() {
         KGE_TRY(launch_pairre_edge_fwd(e, s));
         return KGE_OK;
     }
+    if (hp->model == KGE_TRANSH) {     // own edge forward: P, the stacked (a, w^), the dense negative rows and their |n|^2; the loss kernel takes the positive part
+        TranshEdgeArgs e; fill_transh_edge(e, src, b->B, b->chunk, hp->d_e, b->neg_head, hp->gamma, P, w.th.AW, w.asq, w.th.cw);
+        e.nbase = ef.nbase; e.nidx = ef.nidx; e.n_neg = ef.n_neg; e.nd_own = ef.nd_own; e.nd_chunk = ef.nd_chunk; e.nd_Ns = ef.nd_Ns;
+        e.Bn = w.Bn; e.beta = w.bsq;
+        KGE_TRY(launch_transh_edge_fwd(e, s));
+        return KGE_OK;
+    }
     if (c.build_prep) { *c.build_prep = ef; return KGE_OK; }
     if (!p.merged_fwd && !p.merged_pair) KGE_TRY(launch_edge_fwd(ef, s));     // merged: launched together with the forward tiles
     return KGE_OK;
@@ -965,6 +1084,8 @@ int Step::phase_fwd() {
             PairreNegArgs n; fill_pairre_neg(n, b->C, b->chunk, p.N, hp->d_e, hp->gamma, w.A, w.PW, w.Bn, nullptr, w.Pnrm);
             n.S = w.S;
             KGE_TRY(launch_pairre_neg_fwd(n, s));
+        } else if (hp->model == KGE_TRANSH) {
+            if (int rc = transh_scores(transh_block(), w.S, s)) return rc;
         } else KGE_TRY(launch_neg_fwd_pair(na, s));
     }
     if (p.fused_loss || p.fold_loss) return KGE_OK;  // no stand-alone loss kernel: the backward GEMM / the forward tiles run it
@@ -972,7 +1093,7 @@ int Step::phase_fwd() {
     LossArgs la; fill_step_loss(la);
     la.row_pos = p.want4 ? w.row_pos : nullptr;
     if (p.merged_fwd && p.is_l2) { la.l2_raw = 1; la.l2_chunk = b->chunk; la.asq = w.asq; la.bsq = w.bsq; }
-    la.skip_pos = (p.pos_row || p.rescal || p.transr || hp->model == KGE_PAIRRE) ? 0 : 1; la.diag_chunk = p.nd ? b->chunk : 0;  // RESCAL / TransR: no edge_fwd -> positive part here
+    la.skip_pos = (p.pos_row || p.rescal || p.transr || hp->model == KGE_PAIRRE || hp->model == KGE_TRANSH) ? 0 : 1; la.diag_chunk = p.nd ? b->chunk : 0;  // RESCAL / TransR: no edge_fwd -> positive part here
     KGE_TRY(launch_loss(la, s, c.known ? c.known_mask : nullptr));
     return KGE_OK;
 }
@@ -1082,6 +1203,19 @@ int Step::phase_bwd() {
         e.GH = w.GH; e.GT = w.GT; e.GR = GR;
         if (p.nd) { e.GNd = GN; e.nd_chunk = b->chunk; e.nd_Np = p.N; }     // in-batch negative rows -> positive trace
         KGE_TRY(launch_pairre_edge_bwd(e, s));
+        return KGE_OK;
+    }
+    if (hp->model == KGE_TRANSH) {
+        if (int rc = transh_neg_bwd(transh_block(), w.S, w.th.PQc, w.th.rs, w.th.kap, w.th.cs, w.th.GAW, GN, s)) return rc;
+        TranshBwdArgs e{};
+        e.src = src; e.B = b->B; e.chunk = b->chunk; e.d_e = hp->d_e; e.neg_head = b->neg_head; e.dpos = w.dP;
+        e.GAW = w.th.GAW; e.rs = w.th.rs; e.kap = w.th.kap;
+        e.reg_coef = p.reg ? hp->reg_coef : 0.f; e.reg_norm = hp->reg_norm;
+        e.GH = w.GH; e.GT = w.GT; e.GR = GR;
+        e.nbase = w.Bn; e.n_neg = p.CN; e.cs = w.th.cs; e.GN = GN;
+        e.n_reg_coef = (p.reg && !p.nd) ? hp->reg_coef : 0.f;           // nd: the update adds it (sampled rows only)
+        if (p.nd) { e.GNd = GN; e.nd_chunk = b->chunk; e.nd_Np = p.N; }     // in-batch negative rows -> positive trace
+        KGE_TRY(launch_transh_edge_bwd(e, s));
         return KGE_OK;
     }
     if (p.gemm) {
@@ -1210,6 +1344,7 @@ static int step_sampling(const kge_hparams *hp, const kge_tables *tb, const kge_
                          size_t ws_bytes, const kge_sampler_job *job, StepCall c, void *stream) {
     if (!job) return run_step(hp, tb, b, out, ws, ws_bytes, stream, c);
     if (hp && hp->model == KGE_PAIRRE) return no_pairre("kge_step_fused_sampling");
+    if (hp && hp->model == KGE_TRANSH) return no_transh("kge_step_fused_sampling");
     if (!job->heads || !job->rels || !job->tails || !job->state || !job->slot || !job->scratch || job->n_train <= 0 || job->n_ent <= 0 ||
         job->B <= 0 || job->C <= 0 || job->chunk <= 0 || job->N <= 0 || job->C * job->chunk != job->B || job->k < 0 || job->advance < 0)
         return fail(KGE_ERR_ARG, "kge_step_fused_sampling: bad sampler job");
@@ -1277,6 +1412,7 @@ int kge_step_async(kge_pipe *p, const kge_hparams *hp, const kge_tables *tb, con
     if (!p || !hp || !tb || !b || !ws) return fail(KGE_ERR_ARG, "kge_step_async: null argument");
     if (hp->model == KGE_QUATE) return no_quate("kge_step_async");
     if (hp->model == KGE_PAIRRE) return no_pairre("kge_step_async");
+    if (hp->model == KGE_TRANSH) return no_transh("kge_step_async");
     const size_t half = (ws_bytes / 2) & ~(size_t)255;
     void *wsp = (char *)ws + (size_t)p->parity * half;
     void *wsn = (char *)ws + (size_t)(p->parity ^ 1) * half;
@@ -1411,6 +1547,7 @@ int kge_step_grads(const kge_hparams *hp, const kge_tables *tb, const kge_batch 
                    void *ws, size_t ws_bytes, void *stream) {
     if (hp && hp->model == KGE_QUATE) return no_quate("kge_step_grads");
     if (hp && hp->model == KGE_PAIRRE) return no_pairre("kge_step_grads");
+    if (hp && hp->model == KGE_TRANSH) return no_transh("kge_step_grads");
     if (!emit || !emit->g0 || (!emit->msg_rows && (!emit->gs0 || !emit->g1 || !emit->gs1)))
         return fail(KGE_ERR_ARG, "kge_step_grads: emit buffers g0/gs0/g1/gs1 are required (packed messages: g0 + msg_rows)");
     if ((emit->gr == nullptr) != (emit->gsr == nullptr))
@@ -1430,7 +1567,7 @@ static void carve_transr_rows(Carver &cv, TransRRows &w, size_t n) {
 // TransR: only the projections hp, tp - launch_transr_pos, which the caller runs with its own candidates, makes P and q from them.
 static int rank_pos_side(int model, int neg_head, const float *ent, const float *rel, const float *proj, const int64_t *h,
                          const int64_t *r, const int64_t *t, int rows, int d_e, int d_r, float gamma, float rot_div, float *P,
-                         float *A, float *asq, float *RV, const TransRRows &w, hipStream_t s) {
+                         float *A, float *asq, float *RV, const TransRRows &w, hipStream_t s, int th_chunk = 0) {
     if (model == KGE_TRANSR) {
         RescalMatvecArgs m{};
         m.B = rows; m.D = d_e; m.Dc = d_r; m.rel = proj; m.ridx = r;
@@ -1448,6 +1585,12 @@ static int rank_pos_side(int model, int neg_head, const float *ent, const float 
     } else if (model == KGE_PAIRRE) {                   // the pair (a, w) lives in the A and RV entries
         PairreEdgeArgs e; fill_pairre_edge(e, EdgeSrc{ent, h, ent, t, rel, r}, rows, d_e, neg_head, gamma, P, A, RV);
         KGE_TRY(launch_pairre_edge_fwd(e, s));
+    } else if (model == KGE_TRANSH) {
+        // th_chunk == 0 (kge_rank_eval): a in the A entry, w^ in the RV entry; else A is the stacked operand of chunks of th_chunk
+        // rows.  |a|^2 in asq, w^ . a in the first `rows` floats of the THP entry (TransR's, free here)
+        TranshEdgeArgs e; fill_transh_edge(e, EdgeSrc{ent, h, ent, t, rel, r}, rows, th_chunk ? th_chunk : rows, d_e, neg_head, gamma, P, A, asq, w.THP);
+        if (!th_chunk) e.W = RV;
+        KGE_TRY(launch_transh_edge_fwd(e, s));
     } else {
         EdgeFwdArgs ef;
         fill_edge(ef, EdgeSrc{ent, h, ent, t, rel, r}, model, rows, d_e, d_r, neg_head, gamma, rot_div);
@@ -1499,11 +1642,17 @@ static int rank_eval_impl(int model, int neg_head, const float *qent, const floa
         KGE_TRY(launch_edge_fwd(nb, s));
     }
     if (model == KGE_PAIRRE) KGE_TRY(pairre_norms(cent, cand, N, d_e, bsq, s));       // |x| of every candidate row, once (the bsq entry)
+    const bool th = model == KGE_TRANSH;
+    if (th) KGE_TRY(transh_norms(cent, cand, N, d_e, bsq, s));                        // |n|^2 of every candidate row, once
     for (int64_t e0 = 0; e0 < E; e0 += Eb) {
         const int rows = (int)((E - e0) < Eb ? (E - e0) : Eb);
         float *P = pos_score_out ? pos_score_out + e0 : w.P;
         KGE_TRY(rank_pos_side(model, neg_head, qent, rel, proj, h + e0, r + e0, t + e0, rows, d_e, d_r, gamma, rot_div, P, A,
-                              l2g ? asq : nullptr, w.RV, w, s));
+                              (l2g || th) ? asq : nullptr, w.RV, w, s));
+        if (th) {
+            KGE_TRY(launch_rank_gemm_transh(A, w.RV, rows, cent, cand, N, d_e, gamma, asq, w.THP, bsq, P, S, filt_ptr, filt_ids, e0, ranks, s));
+            continue;
+        }
         if (model == KGE_TRANSR) {
             // the training kernels with one chunk = this batch of test triples and the candidates as negatives
             TransRArgs tr{};
@@ -1569,6 +1718,7 @@ int kge_rank_eval_split(int model, int neg_head, const float *qent, int64_t n_qe
     if (int rc = check_model(model, d_e, d_r)) return rc;
     if (model == KGE_QUATE) return no_quate("kge_rank_eval_split");
     if (model == KGE_PAIRRE) return no_pairre("kge_rank_eval_split");
+    if (model == KGE_TRANSH) return no_transh("kge_rank_eval_split");
     if (model == KGE_TRANSR && !proj)
         return fail(KGE_ERR_ARG, "kge_rank_eval_split: TransR needs the projection table");
     if (n_qent <= 0 || n_cent < 0) return fail(KGE_ERR_ARG, "kge_rank_eval_split: bad argument");
@@ -1590,17 +1740,19 @@ int kge_rank_eval_split(int model, int neg_head, const float *qent, int64_t n_qe
 // ---- chunked-candidate ranking (kge_rank_chunk.hip) ----
 // one block of whole chunks: pos-side vectors / norms / positive scores of its rows, the candidates' norms (TransE_l2), and - for the
 // score-block route only, but the layout does not depend on the flags - the id list and the score block
-struct ChunkBufs : TransRRows { float *A, *asq, *P, *RV, *bsq_own, *bsq_c, *S, *Pnrm; int64_t *ids; };
+struct ChunkBufs : TransRRows { float *A, *asq, *P, *RV, *bsq_own, *bsq_c, *S, *Pnrm, *TPQ; int64_t *ids; };
 static size_t carve_chunked(Carver &cv, ChunkBufs &w, int model, int64_t rows, int chunk, int64_t n_cand, int self_cand, int d_e, int d_r) {
     const size_t nch = (size_t)((rows + chunk - 1) / chunk), R = nch * (size_t)chunk;
     const size_t ncols = (size_t)n_cand + (self_cand ? (size_t)chunk : 0);
-    w.A = cv.f(R * d_e); w.asq = cv.f(R); w.P = cv.f(R);
+    const bool th = model == KGE_TRANSH;
+    w.A = cv.f((th ? 2 : 1) * R * d_e); w.asq = cv.f(R); w.P = cv.f(R);         // (TransH: the stacked operand (a, w^))
     w.RV = cv.f(model == KGE_RESCAL || model == KGE_PAIRRE ? R * d_e : 0);      // V = M t (RESCAL); w of the pair (PairRE)
-    carve_transr_rows(cv, w, model == KGE_TRANSR ? R * (size_t)d_r : 0);
+    carve_transr_rows(cv, w, model == KGE_TRANSR ? R * (size_t)d_r : th ? R : 0);      // (TransH: w^ . a in the first entry)
     w.bsq_own = cv.f(R); w.bsq_c = cv.f(nch * (size_t)n_cand);
     w.ids = cv.i64(nch * ncols);
     w.S = cv.f(R * ncols);
-    w.Pnrm = model == KGE_PAIRRE ? cv.f(nch * ncols) : nullptr;        // PairRE: |x| per position of the id lists
+    w.Pnrm = (model == KGE_PAIRRE || th) ? cv.f(nch * ncols) : nullptr;       // PairRE: |x| per position of the id lists; TransH: |x|^2
+    w.TPQ = th ? cv.f(2 * R * ncols) : nullptr;                        // TransH: the raw products p | q
     return cv.off;
 }
 
@@ -1661,7 +1813,7 @@ int kge_rank_eval_chunked(int model, int neg_head, const float *ent, int64_t n_e
         const int rows = (int)std::min<int64_t>((int64_t)nch * chunk, E - e0);
         float *P = pos_score_out ? pos_score_out + e0 : w.P;
         KGE_TRY(rank_pos_side(model, neg_head, ent, rel, proj, h + e0, r + e0, t + e0, rows, d_e, d_r, gamma, rot_div, P, w.A,
-                              l2g ? w.asq : nullptr, w.RV, w, s));
+                              (l2g || model == KGE_TRANSH) ? w.asq : nullptr, w.RV, w, s, chunk));
         if (gemm) {
             if (l2g && (!shared || self_cand)) {
                 ChunkCands c1 = cc; if (shared) c1.cand = nullptr;
@@ -1699,6 +1851,12 @@ int kge_rank_eval_chunked(int model, int neg_head, const float *ent, int64_t n_e
                 PairreNegArgs n; fill_pairre_neg(n, C, m, (int)ncols, d_e, gamma, w.A + row_off * d_e, w.RV + row_off * d_e, ent, ids, nrm);
                 n.S = S;
                 KGE_TRY(launch_pairre_neg_fwd(n, s));
+            } else if (model == KGE_TRANSH) {       // (the stacked operand and the product block: two rows per test row)
+                float *beta = w.Pnrm + (gidx == 0 ? 0 : (int64_t)nfull * ncols_full);
+                KGE_TRY(transh_norms(ent, ids, (int64_t)C * ncols, d_e, beta, s));
+                const TranshBlock k{C, m, (int)ncols, d_e, gamma, w.A + 2 * row_off * d_e, w.asq + row_off, w.THP + row_off, ent, ids, beta,
+                                    w.TPQ + 2 * row_off * ncols_full};
+                if (int rc = transh_scores(k, S, s)) return rc;
             } else {
                 NegArgs na; fill_pair(na, model, C, m, (int)ncols, d_e, gamma, w.A + row_off * d_e, ent, ids);
                 na.S = S;
@@ -1728,7 +1886,7 @@ static size_t carve_rank_rel(Carver &cv, RelBufs &w, int model, int Eb, int64_t 
 size_t kge_rank_rel_workspace_bytes(int model, int Eb, int64_t n_rel, int d_e, int d_r) {
     if (Eb <= 0 || n_rel <= 0 || n_rel > 0x7fffffff || check_model(model, d_e, d_r) != KGE_OK) return 0;
     // ids up to KGE_TRANSR only: a QuatE call takes the DistMult layout followed by the normalised relation table (include/kge_hip.h)
-    if (model == KGE_QUATE || model == KGE_PAIRRE) return 0;
+    if (model == KGE_QUATE || model == KGE_PAIRRE || model == KGE_TRANSH) return 0;
     Carver cv; RelBufs w; return carve_rank_rel(cv, w, model, Eb, n_rel, d_e, d_r);
 }
 
@@ -1738,6 +1896,7 @@ int kge_rank_rel_eval(int model, const float *ent, int64_t n_ent, const float *r
                       int32_t *ranks, float *pos_score_out, void *ws, size_t ws_bytes, unsigned flags, void *stream) {
     if (int rc = check_model(model, d_e, d_r)) return rc;
     if (model == KGE_PAIRRE) return no_pairre("kge_rank_rel_eval");
+    if (model == KGE_TRANSH) return no_transh("kge_rank_rel_eval");
     if (model == KGE_TRANSR && !proj) return fail(KGE_ERR_ARG, "kge_rank_rel_eval: TransR needs the projection table");
     if (!ent || !rel || n_ent <= 0 || n_rel <= 0 || E < 0 || (E && (!h || !r || !t || !ranks)) || !ws)
         return fail(KGE_ERR_ARG, "kge_rank_rel_eval: bad argument (a null pointer or a count that is not positive)");
@@ -1815,6 +1974,7 @@ int kge_step_sharded(const kge_hparams *hp, const kge_shards *sh, const kge_batc
     if (!sh) return fail(KGE_ERR_ARG, "kge_step_sharded: null shard map");
     if (hp && hp->model == KGE_QUATE) return no_quate("kge_step_sharded");
     if (hp && hp->model == KGE_PAIRRE) return no_pairre("kge_step_sharded");
+    if (hp && hp->model == KGE_TRANSH) return no_transh("kge_step_sharded");
     // (RESCAL's relation "row" is a d_e x d_e matrix streamed by its own kernels: only the entity width is bounded)
     if (hp && (hp->d_e % 4 || hp->d_e > 1024 || (hp->model != KGE_RESCAL && (hp->d_r % 4 || hp->d_r > 1024))))
         return fail(KGE_ERR_ARG, "kge_step_sharded: row widths must be multiples of 4 and <= 1024 floats");

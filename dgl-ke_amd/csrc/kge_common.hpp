@@ -610,6 +610,9 @@ int launch_rank_count(const float *S, const float *P, int rows, int64_t N, const
                       bool transposed = false);          // transposed: S is [N, rows]
 bool rank_gemm_supported(int model, int d_e);          // kge_rank_gemm.hip: LDS-tiled fp32-MFMA ranking of the matrix-form models
 size_t rank_gemm_mask_bytes(int rows, int64_t N);
+int launch_rank_gemm_transh(const float *A, const float *W, int rows, const float *nbase, const int64_t *nidx, int64_t N, int D, float gamma,
+                            const float *alpha, const float *cw, const float *beta, const float *P, void *mask, const int64_t *filt_ptr,
+                            const int64_t *filt_ids, int64_t e0, int32_t *ranks, hipStream_t s);
 int launch_rank_gemm(int model, const float *A, int rows, const float *nbase, const int64_t *nidx, int64_t N, int D, float gamma,
                      float clampv, const float *asq, const float *bsq, const float *P, void *mask, const int64_t *filt_ptr,
                      const int64_t *filt_ids, int64_t e0, int32_t *ranks, hipStream_t s);
@@ -676,6 +679,8 @@ struct GemmArgs {                   // LDS-staged fp32-MFMA negative scoring (kg
     float *row_neg;                  // [B] per-row negative loss terms or null
     float *acc;                      // running sums or null
 };
+// rows of a chunk operand (chunk or N) up to which launch_neg_bwd_gemm runs: GB_MAXK of kge_neg_gemm.hip, beyond it KGE_ERR_ARG
+#define KGE_NEG_BWD_GEMM_MAXK 2048
 bool neg_mfma_supported(int model, int d_e, int N);
 bool neg_gemm_fused_loss_supported(int chunk, int N);   // fused loss of the matrix-core path (else: stand-alone loss kernel)
 int launch_neg_fwd_gemm(const GemmArgs &a, hipStream_t s);
@@ -730,6 +735,51 @@ int launch_pairre_edge_fwd(const PairreEdgeArgs &a, hipStream_t s);
 int launch_pairre_neg_fwd(const PairreNegArgs &a, hipStream_t s);
 int launch_pairre_neg_bwd(const PairreNegArgs &a, hipStream_t s);
 int launch_pairre_edge_bwd(const PairreBwdArgs &a, hipStream_t s);
+// ---- TransH (kge_transh.hip): local tables only ----
+// Stacked layout of the per-edge pair (a, w^): chunk c of m rows owns 2 m consecutive rows of the operand - rows [0, m) its a
+// vectors, rows [m, 2 m) its w^ vectors - so that ONE matrix product with the candidate rows gives p | q (forward), Ga | Gw^
+// (backward) and Gn.  Row i of the batch: c = i / chunk, m = min(chunk, B - c * chunk) (a short last chunk), l = i - c * chunk;
+// a at row 2 c chunk + l, w^ at row 2 c chunk + m + l.  The score blocks PQ / the coefficient blocks are stacked the same way.
+struct TranshEdgeArgs {              // edge forward + candidate-row jobs of the same launch
+    EdgeSrc src;                     // relation rows are 2 * d_e wide: [d | w]
+    int B, d_e, neg_head, chunk;
+    float gamma;
+    float *pos_score;                // [B] or null
+    float *AW;                       // [2 B, d_e] stacked (a, w^), or null
+    float *W;                        // not null: two blocks instead of the stacked layout - a in AW [B, d_e], w^ here [B, d_e]
+    float *alpha, *cw;               // [B] |a|^2 and w^ . a (with AW)
+    const float *nbase; const int64_t *nidx; int n_neg;   // candidate rows -> beta (and Bn)
+    const int64_t *nd_own; int nd_chunk, nd_Ns;           // neg_deg_sample id scheme (EdgeFwdArgs)
+    float *Bn;                       // [n_neg,d_e] dense copy of the candidate rows or null
+    float *beta;                     // [n_neg] |x|^2 of every candidate row or null
+};
+struct TranshNegArgs {               // the row-wise kernels around the two products of the chunked score
+    int C, chunk, N, d_e;
+    float gamma;
+    const float *alpha, *cw;         // [C*chunk]
+    const float *beta;               // [C*N]
+    const float *PQ;                 // [C, 2 chunk, N] raw products p | q
+    float *S;                        // score kernel: out [C,chunk,N]
+    const float *G;                  // coefficient kernel: dL/ds [C,chunk,N]
+    float *PQc;                      // coefficient kernel: out [C, 2 chunk, N] stacked P' | Q'
+    float *rs, *kap;                 // coefficient kernel: out [C*chunk] sum_j E_ij, sum_j 2 E_ij q_ij
+    float *cs;                       // coefficient kernel: out [C*N] sum_i E_ij
+};
+struct TranshBwdArgs {               // per-edge gradients of the head, tail and relation rows + the candidate rows' own term
+    EdgeSrc src;
+    int B, d_e, neg_head, chunk;
+    const float *dpos;               // [B] or null
+    const float *GAW, *rs, *kap;     // [2 B, d_e] stacked products Ga | Gw^ of the backward GEMM, their row terms [B]; or null
+    float reg_coef; int reg_norm;    // regulariser gradient of the relation row
+    float *GH, *GT, *GR;             // [B,d_e], [B,d_e], [B,2 d_e]; any may be null
+    const float *GNd; int nd_chunk, nd_Np;     // neg_deg_sample (EdgeBwdArgs)
+    // candidate rows: GN[j] += 2 n_j cs[j] (+ regulariser of the row)
+    const float *nbase; const int64_t *nidx; int n_neg; const float *cs; float *GN; float n_reg_coef;
+};
+int launch_transh_edge_fwd(const TranshEdgeArgs &a, hipStream_t s);
+int launch_transh_score(const TranshNegArgs &a, hipStream_t s);
+int launch_transh_coef(const TranshNegArgs &a, hipStream_t s);
+int launch_transh_edge_bwd(const TranshBwdArgs &a, hipStream_t s);
 // ---- RESCAL (kge_rescal.hip) ----
 struct RescalMatvecArgs {            // one pass over M_i = rel + (ridx ? ridx[i] : i) * D*Dc per edge i
     int B, D;                        // D rows; Dc columns (0: square).  y vectors have Dc entries, z / pd vectors D

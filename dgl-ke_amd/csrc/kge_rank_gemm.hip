@@ -81,6 +81,72 @@ __global__ __launch_bounds__(256) void rank_gemm_kernel(RankGemmArgs a) {
     if (myrow < a.rows) a.mask[(int64_t)myrow * a.words + (j0 >> 6)] = word;     // (columns beyond N: zero bits)
 }
 
+// TransH (include/kge_hip.h): the same tile with its 128 pos-side rows holding the pairs (a, w^) of 64 test rows, interleaved by
+// 16-row strips (transh_tile_query, kge_tile_gemm.hpp) so that a lane holds p = a . n and q = w^ . n of one (row, candidate) pair;
+// the epilogue scores with transh_score and keeps the same bits in the same mask layout (rank_mask_kernel counts them)
+#define RANK_TH_BM (TILE_BM / 2)
+struct RankTranshArgs {
+    const float *A, *W; int rows;                 // [rows, D] x 2: the pairs of this batch (dense)
+    const float *nbase; const int64_t *nidx;
+    int64_t N; int D;
+    float gamma;
+    const float *alpha, *cw, *beta, *P;           // [rows] |a|^2, w^ . a; [N] |n|^2; [rows] positive scores
+    unsigned long long *mask; int64_t words;
+};
+
+__global__ __launch_bounds__(256) void rank_gemm_transh_kernel(RankTranshArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[2][(TILE_BM + TILE_BN) * TILE_LD];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nbn = (int)((a.N + TILE_BN - 1) / TILE_BN);
+    const int bm = (int)blockIdx.x / nbn, bn = (int)blockIdx.x % nbn;
+    f32x4 acc[4][4];
+    tile_gemm_128x128(
+        lds, a.D, wave,
+        [&](int R) { return (transh_tile_is_w(R) ? a.W : a.A) + (int64_t)min(bm * RANK_TH_BM + transh_tile_query(R), a.rows - 1) * a.D; },
+        [&](int j) { return row_ptr(a.nbase, a.nidx, min((int64_t)bn * TILE_BN + j, a.N - 1), a.D); }, acc);
+    // ---- epilogue: p = acc[i][j][r], q = acc[i + 2][j][r] of (row 32 wr + 16 i + 4 q + r, candidate 64 wc + 16 j + m), i < 2 ----------
+    const int wr = wave >> 1, wc = wave & 1;
+    const int m = lane & 15, q = lane >> 4;
+    const int64_t j0 = (int64_t)bn * TILE_BN + wc * 64;
+    float bs[4];
+    bool jok[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t col = j0 + 16 * j + m;
+        jok[j] = col < a.N;
+        bs[j] = jok[j] ? a.beta[col] : 0.f;
+    }
+    const int myrow = bm * RANK_TH_BM + wr * 32 + lane;              // lanes 0 .. 31: the row whose word this lane writes
+    unsigned long long word = 0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        unsigned long long bal[4][4];                               // [r][j]: bit 16 q' + m' = (row 16 i + 4 q' + r, column 16 j + m')
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = min(bm * RANK_TH_BM + wr * 32 + 16 * i + 4 * q + r, a.rows - 1);
+            const float p = a.P[row], as = a.alpha[row], cw = a.cw[row];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float x = transh_score(acc[i][j][r], acc[i + 2][j][r], a.gamma, as, bs[j], cw);
+                bal[r][j] = __ballot(jok[j] && x >= p);
+            }
+        }
+        if ((lane >> 4) == i) {                                     // lanes 16 i .. 16 i + 15 own rows 16 i + (lane & 15) of the strip
+            const int qq = (lane & 15) >> 2, rr = lane & 3;
+            unsigned long long w = 0;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (r == rr) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) w |= ((bal[r][j] >> (16 * qq)) & 0xffffull) << (16 * j);
+                }
+            word = w;
+        }
+    }
+    if (lane < 32 && myrow < a.rows) a.mask[(int64_t)myrow * a.words + (j0 >> 6)] = word;
+}
+
 // rank_i = 1 + #{j : bit(i, j)} - #{j in filt_i : bit(i, j)};  filt_i = filt_ids[filt_ptr[2 (e0 + i)] .. filt_ptr[2 (e0 + i) + 1])
 __global__ __launch_bounds__(KGE_BLOCK) void rank_mask_kernel(const unsigned long long *__restrict__ mask, int64_t words, int64_t N,
                                                              int rows, const int64_t *__restrict__ filt_ptr,
@@ -124,6 +190,24 @@ int launch_rank_gemm(int model, const float *A, int rows, const float *nbase, co
     a.words = (N + 127) / 128 * 2;                                // whole 128-candidate tiles: every word of a row is written
     const int64_t nb = (int64_t)((rows + TILE_BM - 1) / TILE_BM) * ((N + TILE_BN - 1) / TILE_BN);
     hipLaunchKernelGGL(rank_gemm_kernel, dim3((unsigned)nb), dim3(256), 0, s, a);
+    if (int rc = check_launch()) return rc;
+    hipLaunchKernelGGL(rank_mask_kernel, dim3((unsigned)((rows + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK)), dim3(KGE_BLOCK), 0, s,
+                       a.mask, a.words, N, rows, filt_ptr, filt_ids, e0, ranks);
+    return check_launch();
+}
+
+// TransH: A, W, alpha, cw, P: this batch's pairs, their statistics and positive scores (transh_edge_fwd); beta: the candidates' |n|^2
+int launch_rank_gemm_transh(const float *A, const float *W, int rows, const float *nbase, const int64_t *nidx, int64_t N, int D, float gamma,
+                            const float *alpha, const float *cw, const float *beta, const float *P, void *mask, const int64_t *filt_ptr,
+                            const int64_t *filt_ids, int64_t e0, int32_t *ranks, hipStream_t s) {
+    if (rows <= 0) return KGE_OK;
+    RankTranshArgs a{};
+    a.A = A; a.W = W; a.rows = rows; a.nbase = nbase; a.nidx = nidx; a.N = N; a.D = D; a.gamma = gamma;
+    a.alpha = alpha; a.cw = cw; a.beta = beta; a.P = P;
+    a.mask = reinterpret_cast<unsigned long long *>(mask);
+    a.words = (N + 127) / 128 * 2;
+    const int64_t nb = (int64_t)((rows + RANK_TH_BM - 1) / RANK_TH_BM) * ((N + TILE_BN - 1) / TILE_BN);
+    hipLaunchKernelGGL(rank_gemm_transh_kernel, dim3((unsigned)nb), dim3(256), 0, s, a);
     if (int rc = check_launch()) return rc;
     hipLaunchKernelGGL(rank_mask_kernel, dim3((unsigned)((rows + KGE_WAVES_PER_BLOCK - 1) / KGE_WAVES_PER_BLOCK)), dim3(KGE_BLOCK), 0, s,
                        a.mask, a.words, N, rows, filt_ptr, filt_ids, e0, ranks);

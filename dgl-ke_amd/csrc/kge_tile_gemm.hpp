@@ -15,6 +15,21 @@ namespace kge {
 __device__ __forceinline__ float l2_score(float x, float gamma, float as, float bs) {
     return gamma - sqrtf(fmaxf(fmaf(-2.f, x, as + bs), 1e-30f));
 }
+// TransH (include/kge_hip.h): |a - n + (w^ . n) w^|^2 from the two products p = a . n and q = w^ . n, the squared norms as = |a|^2,
+// bs = |n|^2 and c = w^ . a:  as + bs - 2 p + 2 c q - q^2  (|w^| is 1 or w^ = 0, and then q = 0).  One routine for the step's score
+// kernel, its coefficient kernel, ranking and top-K: the same operands give the same bits everywhere
+__device__ __forceinline__ float transh_dist2(float p, float q, float as, float bs, float c) {
+    return fmaxf(fmaf(q, fmaf(2.f, c, -q), fmaf(-2.f, p, as + bs)), 1e-30f);
+}
+__device__ __forceinline__ float transh_score(float p, float q, float gamma, float as, float bs, float c) {
+    return gamma - sqrtf(transh_dist2(p, q, as, bs, c));
+}
+// the two operands of a 64-query TransH tile inside the 128 pos-side rows of tile_gemm_128x128: 16-row strips 0, 1 of each
+// wavefront's 64 rows are the a vectors of 32 queries and strips 2, 3 the w^ vectors of the same queries, so that with
+// acc[i][j][r] as documented below a lane holds p in acc[i][j][r] and q in acc[i + 2][j][r] (i < 2) of ONE (query, candidate) pair:
+// query 32 wr + 16 i + 4 q + r of the tile.  Tile row R -> (query of the tile, 0 = a / 1 = w^)
+__device__ __forceinline__ int transh_tile_query(int R) { return 32 * (R >> 6) + (R & 31); }
+__device__ __forceinline__ int transh_tile_is_w(int R) { return (R >> 5) & 1; }
 // the score of a (pos-side row, candidate) pair from its raw product: TransE_l2 (l2; as / bs = |a|^2 / |b|^2), SimplE (clampv > 0:
 // clamp), the other matrix forms (the product itself)
 __device__ __forceinline__ float tile_score(float x, int l2, float gamma, float as, float bs, float clampv) {

@@ -29,9 +29,13 @@ using namespace kge;
 #define TK_MCAP 2048                              // entries of one merge workgroup
 
 // accumulator kinds (template) and epilogues (runtime)
-enum { ACC_MFMA = 0, ACC_DOT = 1, ACC_SQ = 2, ACC_L1 = 3, ACC_ROT = 4, ACC_PRE = 5 };
+enum { ACC_MFMA = 0, ACC_DOT = 1, ACC_SQ = 2, ACC_L1 = 3, ACC_ROT = 4, ACC_PRE = 5, ACC_TH = 6, ACC_THV = 7 };
 // ACC_PRE (PairRE, include/kge_hip.h): query row i is the pair (a_i, w_i) - abase holds the rows' a block followed by their w block,
 // [rows, D] each - and bn the candidates' norms |x_j|_2: the tile accumulates |a_ik - w_ik x_jk / |x_j||
+// ACC_TH / ACC_THV (TransH, include/kge_hip.h): query row i is the pair (a_i, w^_i) - abase holds the rows' a block, their w^ block
+// ([rows, D] each) and then c_i = w^_i . a_i [rows]; an = |a|^2, bn = |n|^2.  The tile accumulates p = a . n and q = w^ . n and
+// scores with transh_score.  ACC_TH: the shared MFMA tile twice per candidate tile, 64 queries each with the two operands
+// interleaved by strips (transh_tile_query, kge_tile_gemm.hpp); ACC_THV: the VALU tile with a second accumulator (D < 32)
 enum { EPI_RAW = 0, EPI_L2G = 1, EPI_COS = 2, EPI_JAC = 3, EPI_GMINUS = 4, EPI_GSQRT = 5 };
 
 struct TopkSelArgs {
@@ -128,6 +132,43 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
                         sc[row * TILE_BN + col] = epilogue(a, acc[i][j][r], grow, gcol);
                     }
                 }
+        } else if constexpr (ACC == ACC_TH) {
+            const float *wb = a.abase + (int64_t)a.rows * D, *cb = wb + (int64_t)a.rows * D;
+            const int wr = wave >> 1, wc = wave & 1;
+            const int m = lane & 15, q = lane >> 4;
+            float sv[2][2][4][4];                                               // [half][strip][j][r]: lds is the tile's until both halves are done
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                f32x4 acc[4][4];
+                tile_gemm_128x128(
+                    lds, D, wave,
+                    [=](int R) {
+                        const int64_t row = min(r0 + 64 * half + transh_tile_query(R), a.rows - 1);
+                        return (transh_tile_is_w(R) ? wb : a.abase) + row * D;
+                    },
+                    [=](int j) { return row_ptr(a.nbase, a.nidx, min(bn * TILE_BN + j, a.N - 1), D); }, acc);
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int64_t grow = min(r0 + 64 * half + 32 * wr + 16 * i + 4 * q + r, a.rows - 1);
+                        const float as = a.an[grow], cw = cb[grow];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const int64_t gcol = min(bn * TILE_BN + wc * 64 + 16 * j + m, a.N - 1);
+                            sv[half][i][j][r] = transh_score(acc[i][j][r], acc[i + 2][j][r], a.gamma, as, a.bn[gcol], cw);
+                        }
+                    }
+            }
+#pragma unroll
+            for (int half = 0; half < 2; ++half)
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            sc[(64 * half + 32 * wr + 16 * i + 4 * q + r) * TILE_BN + wc * 64 + 16 * j + m] = sv[half][i][j][r];
         } else {
             // ---- VALU tile: thread (tx, ty) owns rows ty + 16 i, columns tx + 16 j; scalar staging (any D) ------------------
             const int tx = tid & 15, ty = tid >> 4;
@@ -138,6 +179,13 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
             for (int i = 0; i < 8; ++i)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) acc[i][j] = 0.f;
+            [[maybe_unused]] float acc2[ACC == ACC_THV ? 8 : 1][8];                // TransH: q = w^ . n next to p = a . n
+            if constexpr (ACC == ACC_THV) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) acc2[i][j] = 0.f;
+            }
             for (int s = 0; s < nst; ++s) {
                 float g[32];
 #pragma unroll
@@ -153,12 +201,15 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
                 }
                 [[maybe_unused]] float gw[16];
                 if constexpr (ACC == ACC_PRE) {
-                    // the candidate half of the slab normalised (x / |x|, 0 where |x| == 0), and the rows' w slab for the second buffer
+                    // the candidate half of the slab normalised (x / |x|, 0 where |x| == 0)
 #pragma unroll
                     for (int i = 16; i < 32; ++i) {
                         const float nj = a.bn[min(bn * TILE_BN + ((tid + 256 * i) >> 5) - TILE_BM, a.N - 1)];
                         g[i] = nj > 0.f ? g[i] / nj : 0.f;
                     }
+                }
+                if constexpr (ACC == ACC_PRE || ACC == ACC_THV) {
+                    // the rows' w slab for the second buffer
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
                         const int f = tid + 256 * i, row = f >> 5, k = s * TILE_BK + (f & 31);
@@ -172,7 +223,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
                     const int f = tid + 256 * i;
                     lds[0][(f >> 5) * TILE_LD + (f & 31)] = g[i];
                 }
-                if constexpr (ACC == ACC_PRE) {
+                if constexpr (ACC == ACC_PRE || ACC == ACC_THV) {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
                         const int f = tid + 256 * i;
@@ -199,7 +250,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
                     for (int k = 0; k < TILE_BK; ++k) {
                         float av[8], bv[8];
                         [[maybe_unused]] float wv[8];
-                        if constexpr (ACC == ACC_PRE) {
+                        if constexpr (ACC == ACC_PRE || ACC == ACC_THV) {
 #pragma unroll
                             for (int i = 0; i < 8; ++i) wv[i] = lds[1][(ty + 16 * i) * TILE_LD + k];
                         }
@@ -211,7 +262,8 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
                         for (int i = 0; i < 8; ++i)
 #pragma unroll
                             for (int j = 0; j < 8; ++j) {
-                                if constexpr (ACC == ACC_DOT) acc[i][j] = fmaf(av[i], bv[j], acc[i][j]);
+                                if constexpr (ACC == ACC_THV) { acc[i][j] = fmaf(av[i], bv[j], acc[i][j]); acc2[i][j] = fmaf(wv[i], bv[j], acc2[i][j]); }
+                                else if constexpr (ACC == ACC_DOT) acc[i][j] = fmaf(av[i], bv[j], acc[i][j]);
                                 else if constexpr (ACC == ACC_SQ) { const float d = av[i] - bv[j]; acc[i][j] = fmaf(d, d, acc[i][j]); }
                                 else if constexpr (ACC == ACC_PRE) acc[i][j] += fabsf(fmaf(-wv[i], bv[j], av[i]));
                                 else acc[i][j] += fabsf(av[i] - bv[j]);
@@ -227,7 +279,10 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const int col = tx + 16 * j;
-                    sc[row * TILE_BN + col] = epilogue(a, acc[i][j], grow, min(bn * TILE_BN + col, a.N - 1));
+                    if constexpr (ACC == ACC_THV)
+                        sc[row * TILE_BN + col] = transh_score(acc[i][j], acc2[i][j], a.gamma, a.an[grow], a.bn[min(bn * TILE_BN + col, a.N - 1)],
+                                                               a.abase[2 * (int64_t)a.rows * D + grow]);
+                    else sc[row * TILE_BN + col] = epilogue(a, acc[i][j], grow, min(bn * TILE_BN + col, a.N - 1));
                 }
             }
         }
@@ -519,10 +574,12 @@ static int tk_check_model(int model, int d_e, int d_r) {
     else if (model == KGE_ROTATE) ok = d_e % 2 == 0 && d_r == d_e / 2;
     else if (model == KGE_QUATE) ok = d_e % 4 == 0 && d_r == d_e;
     else if (model == KGE_PAIRRE) ok = (int64_t)d_r == 2 * (int64_t)d_e;
+    else if (model == KGE_TRANSH) ok = d_e >= 4 && d_e % 4 == 0 && (int64_t)d_r == 2 * (int64_t)d_e;
     else ok = d_r == d_e;
     if (ok) return KGE_OK;
     char msg[160];
-    snprintf(msg, sizeof(msg), "kge_topk_select: dims d_e=%d d_r=%d do not fit model %d", d_e, d_r, model);
+    if (model == KGE_TRANSH) snprintf(msg, sizeof(msg), "kge_topk_select: TransH needs d_e >= 4, d_e %% 4 == 0 and d_r == 2 * d_e (got %d, %d)", d_e, d_r);
+    else snprintf(msg, sizeof(msg), "kge_topk_select: dims d_e=%d d_r=%d do not fit model %d", d_e, d_r, model);
     return tk_fail(msg);
 }
 
@@ -541,7 +598,7 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
     char msg[256];
     if (filt_ptr && !filt_ids) return tk_fail("kge_topk_select_filtered: filt_ptr given without filt_ids");
     const bool sim = func >= KGE_SIM_COSINE && func <= KGE_SIM_EXT_JACCARD;
-    if (!sim && (func < KGE_TRANSE_L1 || (func > KGE_RESCAL && func != KGE_QUATE && func != KGE_PAIRRE))) {
+    if (!sim && (func < KGE_TRANSE_L1 || (func > KGE_RESCAL && func != KGE_QUATE && func != KGE_PAIRRE && func != KGE_TRANSH))) {
         snprintf(msg, sizeof(msg), "kge_topk_select: unknown score function %d (TransR has no inference path)", func);
         return tk_fail(msg);
     }
@@ -557,7 +614,8 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
     const int64_t N = n_cand;
     const int D = d_e;
     // PairRE keeps two vectors per query row: the A entry is [a block | w block] (include/kge_hip.h)
-    TkWs w = carve(ws, rows, N, func == KGE_PAIRRE ? 2 * D : D, K);
+    // TransH: [a block | w^ block | c] (2 D + 1 floats per row)
+    TkWs w = carve(ws, rows, N, func == KGE_PAIRRE ? 2 * D : func == KGE_TRANSH ? 2 * D + 1 : D, K);
     if (w.need > ws_bytes) {
         snprintf(msg, sizeof(msg), "kge_topk_select: workspace too small (%zu < %zu)", ws_bytes, w.need);
         return kge_fail(KGE_ERR_WORKSPACE, msg);
@@ -589,6 +647,13 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
             e.B = rows; e.d_e = d_e; e.neg_head = side; e.gamma = gamma; e.A = w.A; e.W = w.A + (size_t)rows * D;
             e.nbase = ent; e.nidx = cand; e.n_neg = (int)N; e.nrm = w.bn;
             if (int rc = launch_pairre_edge_fwd(e, st)) return rc;
+        } else if (func == KGE_TRANSH) {
+            TranshEdgeArgs e{};
+            e.src = EdgeSrc{ent, h, ent, t, rel, r};
+            e.B = rows; e.chunk = rows; e.d_e = d_e; e.neg_head = side; e.gamma = gamma;
+            e.AW = w.A; e.alpha = w.an; e.cw = w.A + 2 * (size_t)rows * D;
+            e.nbase = ent; e.nidx = cand; e.n_neg = (int)N; e.beta = w.bn;
+            if (int rc = launch_transh_edge_fwd(e, st)) return rc;
         } else {
             EdgeFwdArgs ef{};
             ef.src = EdgeSrc{ent, h, ent, t, rel, r};
@@ -599,6 +664,7 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
         }
         if (func == KGE_TRANSE_L1) { acc = ACC_L1; epi = EPI_GMINUS; }
         else if (func == KGE_PAIRRE) { acc = ACC_PRE; epi = EPI_GMINUS; }
+        else if (func == KGE_TRANSH) { acc = mf ? ACC_TH : ACC_THV; epi = EPI_RAW; }
         else if (func == KGE_ROTATE) { acc = ACC_ROT; epi = EPI_GMINUS; }
         else if (func == KGE_TRANSE_L2) { acc = mf ? ACC_MFMA : ACC_SQ; epi = mf ? EPI_L2G : EPI_GSQRT; }
         else { acc = mf ? ACC_MFMA : ACC_DOT; epi = EPI_RAW; }
@@ -627,6 +693,8 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
         case ACC_SQ: hipLaunchKernelGGL((topk_select_kernel<ACC_SQ, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
         case ACC_L1: hipLaunchKernelGGL((topk_select_kernel<ACC_L1, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
         case ACC_PRE: hipLaunchKernelGGL((topk_select_kernel<ACC_PRE, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
+        case ACC_TH: hipLaunchKernelGGL((topk_select_kernel<ACC_TH, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
+        case ACC_THV: hipLaunchKernelGGL((topk_select_kernel<ACC_THV, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
         default: hipLaunchKernelGGL((topk_select_kernel<ACC_ROT, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
         }
     } else
@@ -636,6 +704,8 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
     case ACC_SQ: hipLaunchKernelGGL(topk_select_kernel<ACC_SQ>, grid, dim3(256), 0, st, a); break;
     case ACC_L1: hipLaunchKernelGGL(topk_select_kernel<ACC_L1>, grid, dim3(256), 0, st, a); break;
     case ACC_PRE: hipLaunchKernelGGL(topk_select_kernel<ACC_PRE>, grid, dim3(256), 0, st, a); break;
+    case ACC_TH: hipLaunchKernelGGL(topk_select_kernel<ACC_TH>, grid, dim3(256), 0, st, a); break;
+    case ACC_THV: hipLaunchKernelGGL(topk_select_kernel<ACC_THV>, grid, dim3(256), 0, st, a); break;
     default: hipLaunchKernelGGL(topk_select_kernel<ACC_ROT>, grid, dim3(256), 0, st, a); break;
     }
     if (int rc = check_launch()) return rc;

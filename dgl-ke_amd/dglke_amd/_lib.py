@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("KGE_LIB") or os.path.join(_HERE, "libkge_hip.so")   #
 
 KGE_ABI_VERSION = 8
 MODEL_IDS = {"TransE_l1": 0, "TransE_l2": 1, "TransE": 1, "DistMult": 2, "ComplEx": 3, "RotatE": 4, "SimplE": 5, "RESCAL": 6, "TransR": 7,
-             "QuatE": 8, "PairRE": 10}      # (9 is not a model)
+             "QuatE": 8, "PairRE": 10, "TransH": 12}      # (9 and 11 are not models)
 LOSS_IDS = {"Logsigmoid": 0, "Logistic": 1, "Hinge": 2, "BCE": 3, "Softmax": 4}
 FLAG_FORCE_PAIRWISE = 1
 FLAG_NO_TRANSE_FAST = 2
@@ -368,7 +368,16 @@ def rank_rel_workspace_bytes(model, Eb, n_rel, d_e, d_r):
 def topk_workspace_bytes(model, rows, n_cand, d_e, K):
     """bytes of a kge_topk_select / _filtered workspace.  kge_topk_workspace_bytes has no model argument; a PairRE call keeps two
     vectors per query row, the pair (a, w), in the A entry: the size is the one of rows 2 * d_e wide (include/kge_hip.h)"""
-    return lib().kge_topk_workspace_bytes(rows, n_cand, 2 * d_e if model == MODEL_IDS["PairRE"] else d_e, K)
+    return lib().kge_topk_workspace_bytes(rows, n_cand, topk_row_width(model, d_e), K)
+
+
+def topk_row_width(model, d_e):
+    """floats per query row in the A entry of a top-K workspace: PairRE the pair (a, w), TransH the pair (a, w^) and c = w^ . a"""
+    if model == MODEL_IDS["PairRE"]:
+        return 2 * d_e
+    if model == MODEL_IDS["TransH"]:
+        return 2 * d_e + 1
+    return d_e
 
 
 def model_id(name):

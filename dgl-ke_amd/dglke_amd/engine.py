@@ -44,6 +44,12 @@ class StepEngine(object):
                 raise _lib.KgeError("PairRE needs relation width == 2 * entity width (-dr without -de; got %d, %d)" % (self.d_e, self.d_r))
             if shards is not None:
                 raise _lib.KgeError("PairRE runs the strict step on local tables only (no sharded tables)")
+        if model_name == 'TransH':                          # relation rows [d | w] (include/kge_hip.h)
+            if self.d_r != 2 * self.d_e or self.d_e % 4 or self.d_e < 4:
+                raise _lib.KgeError("TransH needs an entity width that is a multiple of 4 and relation width == 2 * entity width "
+                                    "(-dr without -de; got %d, %d)" % (self.d_e, self.d_r))
+            if shards is not None:
+                raise _lib.KgeError("TransH runs the strict step on local tables only (no sharded tables)")
         hp = _lib.KgeHParams()
         hp.model = model_id(model_name)
         hp.d_e, hp.d_r = self.d_e, self.d_r

@@ -198,6 +198,9 @@ class Ranker(object):
         if need == 0 and self.model == _lib.MODEL_IDS['PairRE']:
             raise _lib.KgeError("kge_rank_rel_eval: not available for PairRE (the score is not a product of a query row and the "
                                 "relation row: no relation ranking)")
+        if need == 0 and self.model == _lib.MODEL_IDS['TransH']:
+            raise _lib.KgeError("kge_rank_rel_eval: not available for TransH (the relation row enters through two projections: no "
+                                "relation ranking)")
         if need == 0:
             raise _lib.KgeError("relation_ranks: the tables are %s / %s, which this model does not take"
                                 % (tuple(self.ent.shape), tuple(self.rel.shape)))

@@ -21,7 +21,7 @@ class ArgParser(argparse.ArgumentParser):
         super(ArgParser, self).__init__()
         a = self.add_argument
         a('--model_name', default='TransE', choices=['TransE', 'TransE_l1', 'TransE_l2', 'TransR', 'RESCAL', 'DistMult',
-                                                     'ComplEx', 'RotatE', 'SimplE', 'QuatE', 'PairRE'])
+                                                     'ComplEx', 'RotatE', 'SimplE', 'QuatE', 'PairRE', 'TransH'])
         a('--data_path', type=str, default='data')
         a('--dataset', type=str, default='FB15k')
         a('--format', type=str, default='built_in')
@@ -101,6 +101,13 @@ def main(argv=None):
             raise KgeError("PairRE is not available on sharded tables (--gpu takes one entry)")
         if args.eval_relation:
             raise KgeError("PairRE has no relation ranking (--eval_relation): the score is not a product with the relation row")
+    if args.model_name == 'TransH':              # before anything is loaded
+        from .train import check_transh_widths
+        check_transh_widths(args.model_name, args.hidden_dim, args.double_ent, args.double_rel)
+        if len(args.gpu) > 1:
+            raise KgeError("TransH is not available on sharded tables (--gpu takes one entry)")
+        if args.eval_relation:
+            raise KgeError("TransH has no relation ranking (--eval_relation): the relation row enters through two projections")
     if args.gpu[0] < 0:
         raise KgeError("dglke_eval ranks on the GPU only: pass --gpu <id> (there is no CPU fallback)")
     if not os.path.isdir(args.model_path):

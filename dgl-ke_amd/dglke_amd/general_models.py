@@ -14,7 +14,7 @@ from . import ops
 from .engine import StepEngine
 from .loss import LossGenerator
 from .score_fun import (ComplExScore, DistMultScore, PairREScore, QuatEScore, RESCALScore, RotatEScore, SimplEScore, TransEScore,
-                        TransRScore)
+                        TransHScore, TransRScore)
 from .tensor_models import (ExternalEmbedding, cuda, get_dev, get_device, get_scalar, norm,
                             reshape)
 from ._lib import LOSS_IDS, KgeError
@@ -50,6 +50,9 @@ class KEModel(object):
                            % (entity_dim, relation_dim))
         if model_name == 'PairRE' and relation_dim != 2 * entity_dim:
             raise KgeError("PairRE needs relation_dim == 2 * entity_dim, r = [rH | rT] (got %d, %d)" % (entity_dim, relation_dim))
+        if model_name == 'TransH' and (entity_dim % 4 or entity_dim < 4 or relation_dim != 2 * entity_dim):
+            raise KgeError("TransH needs an entity width that is a multiple of 4 and relation_dim == 2 * entity_dim, r = [d | w] "
+                           "(got %d, %d)" % (entity_dim, relation_dim))
         self.entity_emb = ExternalEmbedding(args, n_entities, entity_dim, device)
         if model_name == 'RESCAL':        # relation_emb = relation_dim * entity_dim (general_models.py:232-236)
             if relation_dim != entity_dim:
@@ -81,6 +84,8 @@ class KEModel(object):
             self.score_func = QuatEScore()
         elif model_name == 'PairRE':
             self.score_func = PairREScore(gamma)
+        elif model_name == 'TransH':
+            self.score_func = TransHScore(gamma)
         elif model_name == 'RESCAL':
             self.score_func = RESCALScore(relation_dim // entity_dim, entity_dim)
         elif model_name == 'TransR':

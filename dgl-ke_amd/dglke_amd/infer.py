@@ -15,7 +15,8 @@ Deliberate differences from the reference:
   * the device is a GPU (no CPU path), TransR is refused (as in the reference) and K is limited to 1 .. TOPK_MAX;
   * the models: TransE_l1 / TransE_l2, DistMult, ComplEx, RotatE, RESCAL as in the reference, and SimplE, QuatE (rows of
     four quaternion quarters, the relation normalised per quaternion: include/kge_hip.h) and PairRE (relation rows [rH | rT] on
-    unit-normalised entity rows), which the reference does not have;
+    unit-normalised entity rows) and TransH (relation rows [d | w], both ends projected onto the hyperplane of normal w), which the
+    reference does not have;
   * ke_model: attach_graph takes the known triples (head, rel, tail) themselves (there is no DGLGraph here);
   * ke_model: exclude_mode 'exclude' is exact - known combinations are left out inside the selection kernel, where the
     reference takes the 4K best and falls back to a full sort when too few of them survive; results agree wherever
@@ -118,7 +119,7 @@ def select_groups(func, side, ent, rel, d_e, d_r, gamma, emb_init, cand, n_rows,
     N = cand.numel()
     if n_rows == 0 or N == 0:
         return res_s, res_o
-    d_ws = 2 * d_e if func == _lib.MODEL_IDS['PairRE'] else d_e         # PairRE keeps the pair (a, w) per query row (include/kge_hip.h)
+    d_ws = _lib.topk_row_width(func, d_e)          # PairRE / TransH keep a pair of vectors per query row (include/kge_hip.h)
     if max_rows is None:
         max_rows = rows_in_flight(N, d_ws, k)
     per = (max_rows // group_rows) * group_rows if group_rows <= max_rows else max_rows

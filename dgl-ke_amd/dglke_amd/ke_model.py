@@ -14,8 +14,8 @@ object with `.train` of that shape (kgdataset.KGDataset) - where the reference t
 are accepted and ignored.  The model classes score with the gamma they were constructed with under both sfunc values
 (ke_model.py:868-893); everything else follows infer.py's stated differences (ties by position, NaN last, K <= 128, GPU
 only, TransR refused, 'exclude' exact).  fit / save / eval are not supported, as in the reference.  The classes: TransE, TransE_l1,
-TransE_l2, TransR (loads, refuses link_predict), DistMult, ComplEx, RotatE, RESCAL as in the reference, and SimplE, QuatE and
-PairRE, which the reference does not have."""
+TransE_l2, TransR (loads, refuses link_predict), DistMult, ComplEx, RotatE, RESCAL as in the reference, and SimplE, QuatE,
+PairRE and TransH, which the reference does not have."""
 import json
 import os
 
@@ -229,6 +229,21 @@ class PairREModel(KGEModel):
         if self._relation_emb.shape[1] != 2 * d:
             raise KgeError("PairRE: rows of %d (entity) and %d (relation) values: the relation row must be twice as wide"
                            % (d, self._relation_emb.shape[1]))
+
+
+class TransHModel(KGEModel):
+    """(not among the reference's classes) TransH: relation rows [d | w], twice as wide as the entity rows; both ends are projected
+    onto the hyperplane of normal w and score = gamma - |h_perp + d - t_perp|_2 (include/kge_hip.h, enum kge_model)"""
+
+    def __init__(self, device, gamma):
+        self._gamma = gamma
+        super(TransHModel, self).__init__(device, 'TransH')
+
+    def _after_load(self):
+        d = self._entity_emb.shape[1]
+        if d % 4 or self._relation_emb.shape[1] != 2 * d:
+            raise KgeError("TransH: rows of %d (entity) and %d (relation) values: the entity width must be a multiple of 4 and the "
+                           "relation row twice as wide" % (d, self._relation_emb.shape[1]))
 
 
 class RESCALModel(KGEModel):

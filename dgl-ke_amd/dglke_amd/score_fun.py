@@ -6,7 +6,8 @@ Hand-written kernels, forward and analytic backward: TransE_l1 / TransE_l2 (scor
 ComplEx (:289), RotatE (:451), SimplE (:556), RESCAL (:378); TransR (:110) per-op = library GEMM projections +
 the TransE_l1 kernels in relation space (its fast path is the fused step).  QuatE (not in the reference; include/kge_hip.h,
 enum kge_model) runs on the same per-op entries as ComplEx; PairRE (likewise not in the reference) on the same entries with
-kernels of its own (kge_pairre.hip).
+kernels of its own (kge_pairre.hip); TransH (likewise) on the same entries: row-wise kernels of its own (kge_transh.hip) around
+the matrix-core products of the DistMult form.
 """
 import torch as th
 
@@ -103,6 +104,15 @@ class PairREScore(_HipScore):
     """PairRE (Chao et al., ACL 2021): relation rows [rH | rT], twice the entity width; the entity rows are normalised to unit
     length inside the kernels and score = gamma - |h^ o rH - t^ o rT|_1 (include/kge_hip.h, enum kge_model).  No clamp."""
     model_name = 'PairRE'
+
+    def __init__(self, gamma):
+        self.gamma = gamma
+
+
+class TransHScore(_HipScore):
+    """TransH (Wang et al., AAAI 2014): relation rows [d | w], twice the entity width; both ends are projected onto the hyperplane
+    of unit normal w / |w| inside the kernels and score = gamma - |h_perp + d - t_perp|_2 (include/kge_hip.h, enum kge_model)."""
+    model_name = 'TransH'
 
     def __init__(self, gamma):
         self.gamma = gamma

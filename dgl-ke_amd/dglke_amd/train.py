@@ -42,7 +42,7 @@ class ArgParser(argparse.ArgumentParser):
         super(ArgParser, self).__init__(prog="dglke_train")
         a = self.add_argument
         a('--model_name', default='TransE', choices=['TransE', 'TransE_l1', 'TransE_l2', 'TransR', 'RESCAL',
-                                                     'DistMult', 'ComplEx', 'RotatE', 'SimplE', 'QuatE', 'PairRE'])
+                                                     'DistMult', 'ComplEx', 'RotatE', 'SimplE', 'QuatE', 'PairRE', 'TransH'])
         a('--data_path', type=str, default='data')
         a('--dataset', type=str, default='FB15k')
         a('--format', type=str, default='built_in')
@@ -942,6 +942,31 @@ def check_pairre(args):
         raise KgeError("PairRE has no relation ranking (--eval_relation): the score is not a product with the relation row")
 
 
+def check_transh_widths(model_name, hidden_dim, double_ent, double_rel):
+    """TransH's relation row is [d | w], twice the entity row, and every path is a matrix-core product over 16-byte rows"""
+    if model_name != 'TransH':
+        return
+    if not double_rel or double_ent:
+        raise KgeError("TransH: the relation row [d | w] is twice as wide as the entity row: pass -dr without -de (got%s%s)"
+                       % (" -de" if double_ent else " no -de", " -dr" if double_rel else ", no -dr"))
+    if hidden_dim < 4 or hidden_dim % 4:
+        raise KgeError("TransH: --hidden_dim must be a multiple of 4 (got %d)" % hidden_dim)
+
+
+def check_transh(args):
+    """TransH trains on the strict step of one GPU's tables: refuse what has no such step, before anything is loaded"""
+    if args.model_name != 'TransH':
+        return
+    check_transh_widths(args.model_name, args.hidden_dim, args.double_ent, args.double_rel)
+    if len(args.gpu) > 1:
+        raise KgeError("TransH is not available on more than one GPU (--gpu takes one entry)")
+    if args.async_update_pipeline or args.async_update_rel:
+        raise KgeError("TransH is not available in the one-step-stale pipeline (--async_update_pipeline / --async_update_rel); "
+                       "plain --async_update runs the strict step and is fine")
+    if args.eval_relation:
+        raise KgeError("TransH has no relation ranking (--eval_relation): the relation row enters through two projections")
+
+
 def main(argv=None, before_train=None):
     """before_train (one GPU): called with the built Trainer in front of its first step - the tests take the initial tables there"""
     args = ArgParser().parse_args(argv)
@@ -949,6 +974,7 @@ def main(argv=None, before_train=None):
     check_exclude_positive(args)                 # before anything is loaded or created
     check_quate(args)                            # before anything is loaded or created
     check_pairre(args)                           # before anything is loaded or created
+    check_transh(args)                           # before anything is loaded or created
     check_weighted_device_sampler(args)          # before anything is loaded or created
     check_optimizer(args)                        # before anything is loaded or created
     if args.neg_deg_sample_eval:                # before anything is loaded or created

@@ -57,7 +57,7 @@ enum kge_model {
                           n == 0); gradients arriving through A chain the same way.  The regulariser acts on the raw rows.
                           Relation ranking of a fixed pair: s_j = <conj(h) (x) t, r^_j>.  Strict step on local tables, ranking and
                           top-K; kge_step_sharded, kge_step_grads, kge_step_async and kge_rank_eval_split refuse it. */
-    KGE_PAIRRE    = 10 /* PairRE (Chao et al., ACL 2021; not in the reference).  (Id 9 is not a model: it stays "unknown model".)
+    KGE_PAIRRE    = 10,/* PairRE (Chao et al., ACL 2021; not in the reference).  (Id 9 is not a model: it stays "unknown model".)
                           Entity rows d_e wide, relation rows d_r == 2 * d_e wide, r = [rH | rT].  x^ = x / |x|_2 (sqrtf and a true
                           division), x^ = 0 where |x|_2 == 0, and
                             s(h, r, t) = gamma - sum_k |h^_k rH_k - t^_k rT_k|            (no clamp).
@@ -80,6 +80,35 @@ enum kge_model {
                           their _known forms), ranking, chunked ranking and top-K; kge_step_sharded, kge_step_grads,
                           kge_step_async, kge_step_fused_sampling (with a sampler job), kge_rank_eval_split and kge_rank_rel_eval
                           refuse it before any launch. */
+    KGE_TRANSH    = 12 /* TransH (Wang et al., AAAI 2014; not in the reference).  (Ids 9 and 11 are not models: "unknown model".)
+                          Entity rows d_e wide, d_e >= 4 and d_e % 4 == 0 (every path is a matrix-core product); relation rows
+                          d_r == 2 * d_e wide, r = [d | w]: a translation and a hyperplane normal.  w^ = w / |w|_2 (sqrtf and a true
+                          division), w^ = 0 where |w|_2 == 0; x_perp = x - (w^ . x) w^ and
+                            s(h, r, t) = gamma - |h_perp + d - t_perp|_2                  (the norm, no clamp).
+                          Only the direction of w is trained; the paper's soft constraints are not implemented; the regulariser
+                          acts on the raw rows.  Chunked form, one for both corruption sides: per edge the pair (a, w^) - tails
+                          corrupted a = h_perp + d, heads corrupted a = t_perp - d - and
+                            s_ij = gamma - |a_i - n_j + (w^_i . n_j) w^_i|_2,
+                          evaluated in its matrix form: with p = a_i . n_j, q = w^_i . n_j, alpha_i = |a_i|^2, beta_j = |n_j|^2,
+                          c_i = w^_i . a_i the squared distance is alpha_i + beta_j - 2 p + 2 c_i q - q^2 (|w^_i| is 1, or w^_i = 0
+                          and then q = 0), floored at 1e-30 like TransE_l2's.  Adjoint, with E_ij = -(dL/ds_ij) / (2 dist_ij):
+                          P' = -2 E, Q' = 2 E (c_i - q_ij), kappa_i = sum_j 2 E_ij q_ij,
+                            Ga_i = sum_j P'_ij n_j + 2 a_i sum_j E_ij + kappa_i w^_i,   Gw^_i = sum_j Q'_ij n_j + kappa_i a_i,
+                            Gn_j = sum_i (P'_ij a_i + Q'_ij w^_i) + 2 n_j sum_i E_ij,
+                          then through the projections and Gw = (Gw^ - (Gw^ . w^) w^) / |w| (0 where |w| == 0).  The products
+                          run on the stacked operand [A ; W^] - 2 * chunk rows per chunk, a rows first - with the matrix-core
+                          kernels of the DistMult form.  Layouts: the per-op entries take the RAW rows like every model's
+                          (pos_side [B, d_e], rel [B, 2 d_e], neg [C * N, d_e]) and keep the stacked operand, the product blocks
+                          and the row / column terms in their workspace; kge_step_workspace_bytes,
+                          kge_score_neg_workspace_bytes and kge_rank_chunked_workspace_bytes answer for the id.  Ranking: a lives
+                          in the A entry of the kge_rank_eval workspace, w^ in its RV entry, alpha in asq, c in the first Eb floats
+                          of the TransR rows, beta in bsq (kge_rank_workspace_bytes is unchanged).  kge_topk_select / _filtered
+                          keep [a block | w^ block | c] in the A entry:
+                            workspace = kge_topk_workspace_bytes(rows, n_cand, 2 * d_e + 1, K)
+                          (dglke_amd._lib.topk_workspace_bytes).  Strict step on local tables (kge_step_fused, kge_step_phase,
+                          their _known forms, kge_step_optim), ranking, chunked ranking and top-K; kge_step_sharded,
+                          kge_step_grads, kge_step_async, kge_step_fused_sampling (with a sampler job), kge_rank_eval_split and
+                          kge_rank_rel_eval refuse it before any launch; kge_rank_rel_workspace_bytes answers 0. */
 };
 
 /* loss criteria (models/pytorch/loss.py:44-59) */
@@ -111,7 +140,9 @@ enum kge_status {
 
 /* flags for kge_score_neg_* / kge_step_* : force the VALU pairwise kernels instead of the MFMA
  * GEMM kernels for the models that have a GEMM form (validation aid; TransE_l1 / RotatE always
- * use the pairwise kernels). */
+ * use the pairwise kernels).  TransH ignores the flag in every entry - its score exists in the matrix form alone, so a call made
+ * with the flag to cross-check runs the same kernels as one without; its backward products beyond 2048 rows of a chunk operand
+ * (2 * chunk or N) run on the pairwise kernels whatever the flag says. */
 #define KGE_FLAG_FORCE_PAIRWISE 1u
 /* keep the generic edge-gradient kernel: TransE - instead of rebuilding the per-edge gradients inside the
  * update kernel; DistMult - instead of writing them from the epilogue of the backward GEMM's GA tiles
