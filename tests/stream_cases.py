@@ -2,7 +2,8 @@
 takes an explicit stream ... and only enqueues kernels on it, so calls can be captured into a hipGraph"), as a table and helpers.
 Their CPU checks: tests/test_stream_inputs.py; the GPU runs: tests/test_gpu_stream_contract.py.
 
-STREAM_ENTRIES names every exported function whose prototype has a `void *stream` parameter and the GPU case(s) - test functions of
+STREAM_ENTRIES names every exported function whose prototype has a `void *` parameter named `stream` or ending in `_stream`
+(`void *hip_stream`) and the GPU case(s) - test functions of
 test_gpu_stream_contract.py without their `test_` - that run it on torch's default stream, on a side stream, and captured alone into
 a graph that is replayed on the side stream (kge_step_phase and kge_step_async also run in test_two_engines_two_streams, which is
 no three-mode case).  The helpers below read the C sources the way the CPU checks need them: comments and
@@ -39,6 +40,9 @@ STREAM_ENTRIES = {
     "kge_step_fused_sampling": ["step_fused_sampling"],
     "kge_sample_batches": ["step_fused_sampling"],
     "kge_step_grads": ["step_grads"],
+    "kge_step_optim": ["step_optim_adam", "step_optim_adagrad"],
+    "kge_sample_batches_weighted": ["sample_batches_weighted"],
+    "kge_subsampling_weights": ["subsampling_weights"],
     "kge_reduce_loss": ["reduce_loss"],
     # the per-op entries behind dglke_amd.ops
     "kge_gather_rows": ["gather_and_scatter_rows"],
@@ -348,5 +352,24 @@ def prototypes(header_text):
     return out
 
 
+STREAM_PARAM = r"^void\s*\*\s*(?:\w+_)?stream$"        # `void *stream`, `void *hip_stream`: any name that is or ends in _stream
+STREAM_NAME = r"(?:\b|_)stream$"
+
+
+def is_stream_param(param):
+    return bool(re.match(STREAM_PARAM, param.strip()))
+
+
 def stream_functions(protos):
-    return {n: p for n, p in protos.items() if any(re.match(r"^void\s*\*\s*stream$", x) for x in p)}
+    return {n: p for n, p in protos.items() if any(is_stream_param(x) for x in p)}
+
+
+def workspace_functions(protos):
+    """{name: index of `ws`} of every prototype with the adjacent parameters `void *ws, size_t ws_bytes`"""
+    out = {}
+    for n, p in protos.items():
+        at = [i for i in range(len(p) - 1) if re.match(r"^void\s*\*\s*ws$", p[i]) and re.match(r"^size_t\s+ws_bytes$", p[i + 1])]
+        assert len(at) <= 1, n
+        if at:
+            out[n] = at[0]
+    return out

@@ -154,7 +154,7 @@ def _through(case, entries=None):
     workspace contract (same runner, same float64 baseline on the first run; `entries`: what that test expects to be called)"""
     saved, state = WC._contract, dict(WC._STATE)
 
-    def contract(run, expected, donor=None):
+    def contract(run, expected, donor=None, transh=True):
         return _stream_case(case, run, entries if entries is not None else [e for e in expected if e in S.entries_of(case)])
     WC._contract = contract
     try:
@@ -229,7 +229,7 @@ def test_step_sharded():
 
 def test_step_fused_known():
     with _through("step_fused_known"):
-        WC.test_step_fused_known(24)
+        WC.test_step_fused_known(24, None)
 
 
 def test_step_phase_known():
@@ -303,6 +303,110 @@ def test_step_grads(k):
         WC.test_step_grads(c, lay)
 
 
+# ---- QuatE, PairRE, TransH through the workspace-contract cases: one case per (entry, model) ----
+MODEL_STEPS = list(W.MODEL_PHASE_CASES)              # the -D36-N24 case of each model
+
+
+@pytest.mark.parametrize("c", MODEL_STEPS, ids=lambda c: c["id"])
+def test_step_fused_of_quate_pairre_transh(c):
+    with _through("step_fused"):
+        WC.test_step_fused_of_quate_pairre_transh(c)
+        _STATE[("fused", c["id"])] = WC._STATE[("fused", c["id"])]
+
+
+@pytest.mark.parametrize("c", MODEL_STEPS, ids=lambda c: c["id"])
+def test_step_phase_of_quate_pairre_transh(c, monkeypatch):
+    monkeypatch.setattr(WC, "_phase_step", _phase_step)
+    ref = _STATE.get(("fused", c["id"]))
+    if ref is None:
+        ref = _tensors(WC._run_model_steps(c, False))
+        torch.cuda.synchronize()
+    with _through("step_phase"):
+        WC._STATE[("fused", c["id"])] = ref
+        WC.test_step_phase_of_quate_pairre_transh_equals_the_fused_step(c)
+
+
+@pytest.mark.parametrize("model", W.NEW_MODELS)
+def test_step_fused_known_of_quate_pairre_transh(model):
+    """kge_step_fused_known, then the four kge_step_phase_known groups (step_timed), each in the three modes"""
+    with _through("step_fused_known"):
+        WC.test_step_fused_known(24, model)
+
+
+@pytest.mark.parametrize("model", W.NEW_MODELS)
+def test_step_phase_known_of_quate_pairre_transh(model):
+    c = W.MODEL_KNOWN_CASES[model]
+    _stream_case("step_phase_known", lambda verify: WC._run_model_steps(c, False, "phase", known=True))
+
+
+def test_step_optim_adam():
+    """Adam through kge_step_optim: a plain case, TransH, a width above 512, and with a known index the whole step and then its
+    four phase groups as four captures"""
+    by_id = {o["id"]: o for o in W.OPTIM_ADAM}
+    with _through("step_optim_adam"):
+        for i in ("TransE_l2-w16", "TransH-w16", "DistMult-w516", "l2-known", "l2-known-phases"):
+            WC.test_step_optim_adam(by_id[i])
+
+
+def test_step_optim_adagrad():
+    """kind = KGE_OPT_ADAGRAD through kge_step_optim, with a known index (the fused entry it is compared with runs in the modes too)"""
+    with _through("step_optim_adagrad"):
+        WC.test_step_optim_adagrad_kind_is_the_existing_step("l2-known")
+        WC.test_step_optim_adagrad_kind_is_the_existing_step("TransE_l1-w16")
+
+
+def test_subsampling_weights():
+    """dataloader.subsampling_weights on the table's graph; bound: test_weights_match_the_float64_statement (test_gpu_subsampling.py)"""
+    import subsampling_cases as SC
+    from dglke_amd.dataloader import subsampling_weights
+    h, r, t = SC.graph()
+    ref = SC.weights64(h, r, t, SC.N_REL)
+
+    def run(verify):
+        w = subsampling_weights(h, r, t, SC.N_ENT, SC.N_REL, DEV)
+        torch.cuda.current_stream().synchronize()
+        if verify:
+            got = w.cpu().numpy().astype(np.float64)
+            assert (np.abs(got - ref) / ref).max() <= 4 * 2.0 ** -24
+        return dict(weights=w)
+    _stream_case("subsampling_weights", run)
+
+
+def test_sample_batches_weighted():
+    """two launches of a weighted DeviceSampler (the second crosses an epoch boundary): every slot whole - ids, plan, counts and the
+    weights behind the plan - and the device state.  Baseline: test_weighted_sampler_carries_the_weights_and_changes_nothing_else
+    (test_gpu_subsampling.py) - every array the unweighted sampler's, edge_w the weights of the slot's triples bit for bit"""
+    import subsampling_cases as SC
+    from dglke_amd.dataloader import DeviceSampler
+    B, N, n_train, n_ent, n_slots = 64, 16, 163, 500, 3
+    h, r, t, w = SC.unique_triples(n_train, n_ent)
+    weight_of = dict(zip(zip(h.tolist(), r.tolist(), t.tolist()), w.tolist()))
+
+    def run(verify):
+        smp = DeviceSampler(h, r, t, n_ent, B, N, DEV, n_slots=n_slots, seed=2, edge_importance=w)
+        plain = DeviceSampler(h, r, t, n_ent, B, N, DEV, n_slots=n_slots, seed=2) if verify else None
+        res = {}
+        for launch in range(2):
+            smp.sample(n_slots)
+            torch.cuda.current_stream().synchronize()
+            res["slots %d" % launch], res["state %d" % launch] = smp.slots.clone(), smp.state.clone()
+            if verify:
+                plain.sample(n_slots)
+                torch.cuda.current_stream().synchronize()
+                assert torch.equal(plain.state, smp.state)
+                for k in range(n_slots):
+                    a, b = plain.slot_arrays(k), smp.slot_arrays(k)
+                    UE, UR = int(a["counts"][0]), int(a["counts"][1])
+                    assert np.array_equal(a["counts"], b["counts"])
+                    for name, n in (("h_gid", B), ("t_gid", B), ("rel_ids", B), ("neg_ids", smp.C * N), ("ue_id", UE), ("ur_id", UR),
+                                    ("ue_pos_ptr", UE + 1), ("ue_neg_ptr", UE + 1), ("ur_ptr", UR + 1), ("ue_rec", 8 * UE), ("ur_rec", 8 * UR)):
+                        assert np.array_equal(a[name][:n], b[name][:n]), (launch, k, name)
+                    want = np.array([weight_of[x] for x in zip(b["h_gid"].tolist(), b["rel_ids"].tolist(), b["t_gid"].tolist())], np.float32)
+                    assert np.array_equal(b["edge_w"].view(np.int32), want.view(np.int32)), (launch, k)
+        return res
+    _stream_case("sample_batches_weighted", run)
+
+
 def test_reduce_loss():
     """StepEngine.read_loss_sums after two steps.  Baseline: the float64 sums of the 4 x 4096 slots within 4096 * 2^-24 * sum |x| (a
     fixed-order float32 sum at most that deep), and the slots zeroed"""
@@ -333,6 +437,12 @@ def test_reduce_loss():
 def test_score_neg(c):
     with _through("score_neg"):
         WC.test_score_neg_fwd_bwd(c)
+
+
+@pytest.mark.parametrize("c", _pick(W.MODEL_NEG_CASES, "QuatE-D36-C2-c8-N24-f0", "PairRE-D36-C2-c5-N33-f0", "TransH-D36-C1-c12-N20-f0"), ids=lambda c: c["id"])
+def test_score_neg_of_quate_pairre_transh(c):
+    with _through("score_neg"):
+        WC.test_score_neg_fwd_bwd_of_quate_pairre_transh(c)
 
 
 @pytest.mark.parametrize("c", _pick(M.POS_CASES, "DistMult-D36", "RotatE-D48", "RESCAL-D18"), ids=lambda c: c["id"])
@@ -387,6 +497,30 @@ def test_transr_projections():
 def test_rank_eval_ex(c):
     with _through("rank_eval_ex"):
         WC.test_rank_eval_ex(c)
+
+
+@pytest.mark.parametrize("c", _pick(W.MODEL_RANK_CASES, "QuatE-D36-filt", "PairRE-D36-raw", "TransH-D16-filt"), ids=lambda c: c["id"])
+def test_rank_eval_ex_of_quate_pairre_transh(c):
+    with _through("rank_eval_ex"):
+        WC.test_rank_eval_ex_of_quate_pairre_transh(c)
+
+
+@pytest.mark.parametrize("c", _pick(W.MODEL_CHUNKED_CASES, "QuatE-D36-lists", "PairRE-D36-self", "TransH-D36-all"), ids=lambda c: c["id"])
+def test_rank_eval_chunked_of_quate_pairre_transh(c):
+    with _through("rank_eval_chunked"):
+        WC.test_rank_eval_chunked_of_quate_pairre_transh(c)
+
+
+def test_rank_rel_eval_of_quate():
+    with _through("rank_rel_eval"):
+        WC.test_rank_rel_eval_of_quate(W.MODEL_REL_CASES[1])
+
+
+@pytest.mark.parametrize("filtered", [False, True], ids=["select", "filtered"])
+@pytest.mark.parametrize("c", _pick(W.MODEL_TOPK_CASES, "QuatE-D36-K10-g1", "PairRE-D36-K128-g9", "TransH-D16-K10-g1", "TransH-D36-K128-g9"), ids=lambda c: c["id"])
+def test_topk_select_of_quate_pairre_transh(c, filtered):
+    with _through("topk_select"):
+        WC.test_topk_select_of_quate_pairre_transh(c, filtered)
 
 
 def test_rank_eval_split_and_plain():
@@ -656,6 +790,8 @@ def test_the_proxy_holds_a_call_to_its_stream_and_passes_a_refusal_through():
             _lib.lib().kge_mask_diag(_lib.ptr(x), 2, 3, 3, p.side.cuda_stream)
     assert bool((x == 1).all()), "a call the proxy stopped reached the library"
     assert {m: set(CALLED[m]) for m in MODES} == before
+
+
 def test_every_entry_ran_in_all_three_modes():
     """over the proxy's call log of the whole file (run it whole: a selection of cases leaves entries out)"""
     due = {n for n in S.STREAM_ENTRIES if S.cases_of(n)}

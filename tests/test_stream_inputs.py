@@ -1,7 +1,9 @@
 """CPU guard of the stream contract (include/kge_hip.h, conventions): what can be read from the sources without a GPU.
 
-  header and table agree        every prototype with a `void *stream` is in stream_cases.STREAM_ENTRIES, takes it LAST (the GPU proxy
-                                of tests/test_gpu_stream_contract.py reads it there), and has a case or a reasoned exemption;
+  header and table agree        every prototype with a `void *stream` (or `void *..._stream`) is in stream_cases.STREAM_ENTRIES, takes
+                                it LAST (the GPU proxy of tests/test_gpu_stream_contract.py reads it there), and has a case or a
+                                reasoned exemption; every prototype with `void *ws, size_t ws_bytes` is in
+                                workspace_cases.WS_ENTRIES with the position of `ws`;
   every launch names a stream   the fifth argument of every hipLaunchKernelGGL and the last of every hip*Async call in csrc/ is a
                                 variable - never 0, nullptr or one of the runtime's own stream names;
   nothing synchronous           no blocking copy / memset, allocation or synchronisation call in csrc/ (outside the developer timeline
@@ -34,12 +36,32 @@ def test_header_and_table_agree():
     assert not missing, "entry points with a stream and no case in stream_cases.STREAM_ENTRIES: %s" % missing
     assert not stale, "STREAM_ENTRIES names functions the header does not declare with a stream: %s" % stale
     for name, params in streamed.items():
-        assert re.match(r"^void\s*\*\s*stream$", params[-1]), "%s: `stream` is not its last parameter (%s)" % (name, params[-1])
-        assert sum(bool(re.search(r"\bstream$", p)) for p in params) == 1, name
+        assert S.is_stream_param(params[-1]), "%s: the stream is not its last parameter (%s)" % (name, params[-1])
+        assert sum(bool(re.search(S.STREAM_NAME, p)) for p in params) == 1, name
+    for name in ("kge_step_optim", "kge_sample_batches_weighted", "kge_subsampling_weights"):     # spelled `void *hip_stream`
+        assert name in streamed and streamed[name][-1].endswith("hip_stream"), name
     # what takes no stream: host-side helpers, the size functions, the hipIpc plumbing
     for name in ("kge_ipc_export", "kge_ipc_open", "kge_ipc_close", "kge_pipe_create", "kge_pipe_destroy", "kge_batch_from_slot",
                  "kge_batch_localized", "kge_step_workspace_bytes", "kge_known_mask_bytes"):
         assert name in protos and name not in streamed, name
+
+
+def test_header_and_workspace_table_agree():
+    """every prototype with the adjacent parameters `void *ws, size_t ws_bytes` is a key of workspace_cases.WS_ENTRIES and the
+    reverse; Entry.ws is the position of `ws` in the prototype (the GPU proxy swaps the pair it finds there)"""
+    import workspace_cases as W
+    protos = S.prototypes(_header())
+    takes = S.workspace_functions(protos)
+    assert len(takes) >= 21 and takes["kge_step_fused"] == 4, sorted(takes)
+    missing, stale = sorted(set(takes) - set(W.WS_ENTRIES)), sorted(set(W.WS_ENTRIES) - set(takes))
+    assert not missing, "entry points with (ws, ws_bytes) and no entry in workspace_cases.WS_ENTRIES: %s" % missing
+    assert not stale, "WS_ENTRIES names functions the header does not declare with (ws, ws_bytes): %s" % stale
+    for name, at in sorted(takes.items()):
+        assert W.WS_ENTRIES[name].ws == at, "%s: `ws` is parameter %d of the prototype, WS_ENTRIES says %d" % (name, at, W.WS_ENTRIES[name].ws)
+    # a size function takes none; a planted prototype is found with its index
+    assert "kge_step_workspace_bytes" in protos and "kge_step_workspace_bytes" not in takes
+    more = S.prototypes(_header().replace("int kge_mask_diag(", "int kge_planted(int n, void *ws, size_t ws_bytes, void *stream);\nint kge_mask_diag(", 1))
+    assert S.workspace_functions(more).get("kge_planted") == 1
 
 
 def test_every_entry_has_a_case_or_an_exemption():
@@ -177,8 +199,18 @@ def test_each_scan_finds_a_planted_violation():
     head = _header()
     more = head.replace("int kge_mask_diag(", "int kge_planted(float *x, void *stream);\nint kge_mask_diag(", 1)
     assert set(S.stream_functions(S.prototypes(more))) - set(S.STREAM_ENTRIES) == {"kge_planted"}
+    for spelled in ("void *hip_stream", "void * side_stream", "void *stream"):
+        more = head.replace("int kge_mask_diag(", "int kge_planted(float *x, %s);\nint kge_mask_diag(" % spelled, 1)
+        assert set(S.stream_functions(S.prototypes(more))) - set(S.STREAM_ENTRIES) == {"kge_planted"}, spelled
+    for none in ("void *streams", "int stream", "void *upstream", "const void *stream_of"):
+        more = head.replace("int kge_mask_diag(", "int kge_planted(float *x, %s);\nint kge_mask_diag(" % none, 1)
+        assert "kge_planted" not in S.stream_functions(S.prototypes(more)), none
+    # a `stream` of the header renamed to `hip_stream` is still found, still last
+    renamed = head.replace("int kge_mask_diag(float *x, int C, int chunk, int Np, void *stream);",
+                           "int kge_mask_diag(float *x, int C, int chunk, int Np, void *hip_stream);", 1)
+    assert renamed != head and S.is_stream_param(S.stream_functions(S.prototypes(renamed))["kge_mask_diag"][-1])
     moved = head.replace("int kge_mask_diag(float *x, int C, int chunk, int Np, void *stream);",
                          "int kge_mask_diag(float *x, void *stream, int C, int chunk, int Np);", 1)
     assert moved != head
     p = S.stream_functions(S.prototypes(moved))["kge_mask_diag"]
-    assert not re.match(r"^void\s*\*\s*stream$", p[-1])
+    assert not S.is_stream_param(p[-1])

@@ -1,6 +1,7 @@
 """CPU guard of tests/test_gpu_workspace_contract.py: the carve trace (kge_debug_carve) at every case's shape, and the helpers
 that decide which bytes of a guarded buffer belong to no carved buffer (tests/workspace_cases.py)."""
 import ctypes as C
+import os
 import threading
 
 import numpy as np
@@ -121,6 +122,145 @@ def test_selection_rules_behind_the_case_table():
     for K in (1, 10, 128):
         got = sorted(rounds((n + K - 1) // K, K) for k_, n in W.TOPK_VECTOR if k_ == K and n > K)
         assert got[0] == 1 and got[-1] == 2, (K, got)
+
+
+def test_selection_rules_of_quate_pairre_transh_behind_the_case_table():
+    """restated from the sources, and the case table held to them:
+      use_mfma / neg_mfma_supported (kge_api.hip, kge_neg_gemm.hip): of the three only QuatE has a matrix-core route (d_e % 4 == 0)
+          next to its pairwise one, so only QuatE sees KGE_FLAG_FORCE_PAIRWISE - PairRE and TransH carve the same layout under it;
+      quate_cases.neg_route / vector_packs: the broadcast kernels at d_e % 16 == 0, 16-byte packs where a quarter is a multiple of 4;
+      TransH top-K (kge_topk.hip `mf`): the matrix-core tile at d_e % 4 == 0 and d_e >= TILE_BK, the VALU tile below;
+      the 32-wide k stages / slabs (TILE_BK; pairre_cases.OP_WIDTHS): 36 leaves a partial one, 260 is past 256"""
+    import quate_cases as QT
+    h = _h()
+    BK = _define("kge_tile_gemm.hpp", "TILE_BK")
+    api = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dgl-ke_amd", "csrc", "kge_neg_gemm.hip")).read()
+    body = api[api.index("bool neg_mfma_supported("):api.index("bool neg_gemm_fused_loss_supported(")]
+    assert "KGE_QUATE" in body and "KGE_PAIRRE" not in body and "KGE_TRANSH" not in body and "d_e % 4 == 0" in body
+    topk = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "dgl-ke_amd", "csrc", "kge_topk.hip")).read()
+    assert "const int mf = D % 4 == 0 && D >= TILE_BK;" in topk and "acc = mf ? ACC_TH : ACC_THV" in topk
+    by_id = {c["id"]: c for c in W.MODEL_STEP_CASES}
+    for m in W.NEW_MODELS:
+        widths = sorted({c["d_e"] for c in W.MODEL_STEP_CASES if c["model"] == m})
+        assert widths == [16, 36, 260], (m, widths)
+        assert all(d % 4 == 0 for d in widths) and 16 < BK < 36 and 36 % BK != 0 and 260 > 256 and 260 % BK != 0
+        tags = {c["id"].split("-", 2)[2] for c in W.MODEL_STEP_CASES if c["model"] == m}
+        assert {"N24", "N21", "plain", "neg-deg", "softmax", "hinge-pw", "impts", "w16", "w260"} <= tags, (m, tags)
+        assert ("f1" in tags) == (m == "QuatE"), (m, tags)
+        for tag, key, val in (("neg-deg", "neg_deg", True), ("softmax", "genre", "Softmax"), ("hinge-pw", "pairwise", True), ("impts", "impts", True)):
+            c = by_id["%s-D36-%s" % (m, tag)]
+            assert c[key] == val and (tag != "hinge-pw" or c["genre"] == "Hinge"), c["id"]
+        assert by_id["%s-D36-N21" % m]["N"] == 21 and not by_id["%s-D36-plain" % m]["outputs"]
+    assert QT.neg_route(36, 0) == "gemm" and QT.neg_route(36, W.FORCE_PAIRWISE) == "pair32" and QT.neg_route(16, W.FORCE_PAIRWISE) == "bcast"
+    assert QT.vector_packs(16) and not QT.vector_packs(36) and not QT.vector_packs(260)
+    assert by_id["QuatE-D36-f1"]["flags"] == W.FORCE_PAIRWISE
+    # the layout under the flag: PairRE's and TransH's are their flags = 0 layout, buffer for buffer
+    for m in ("PairRE", "TransH"):
+        c = by_id["%s-D36-N24" % m]
+        lay = []
+        for flags in (0, W.FORCE_PAIRWISE):
+            with W.Trace(h, W.GAP) as t:
+                need = W.model_step_size(h, c, flags=flags)
+                lay.append((need, t.pairs()))
+        assert lay[0] == lay[1], m
+    # what the three models carve beyond the shared step buffers: PairRE three (PW, PGW, Pnrm), TransH eight, four of them stacked
+    B, N, d = 40, 24, 36
+    with W.Trace(h, 0) as t:
+        W.model_step_size(h, by_id["QuatE-D36-N24"])
+        nq = t.pairs()
+    with W.Trace(h, 0) as t:
+        W.model_step_size(h, by_id["PairRE-D36-N24"])
+        np_ = t.pairs()
+    with W.Trace(h, 0) as t:
+        W.model_step_size(h, by_id["TransH-D36-N24"])
+        nt = t.pairs()
+    assert [n for _, n in np_[-3:]] == [4 * B * d, 4 * B * d, 4 * (B // 8) * N]
+    assert [n for _, n in nt[-8:]] == [4 * 2 * B * d, 4 * B, 4 * 2 * B * N, 4 * 2 * B * N, 4 * B, 4 * B, 4 * (B // 8) * N, 4 * 2 * B * d]
+    assert len(np_) - 3 == len(nt) - 8 and len(nq) <= len(np_) - 3 + 1
+
+
+@pytest.mark.parametrize("c", W.MODEL_STEP_CASES + [W.DONOR_TRANSH], ids=lambda c: c["id"])
+def test_model_step_cases_hold_the_conditions_of_their_statements(c):
+    """every step of every QuatE / PairRE / TransH case - and the steps with the planted known pairs - on the float64 statement
+    alone, from the fixed tables: no sign-ambiguous element (PairRE); every distance at least DIST_SHARE of sqrt(alpha + beta) and no
+    gradient row a cancellation residual (TransH).  Nothing is excluded."""
+    Q = W.model_cases(c["model"])
+    ent, rel = W.model_tables(c)
+    bts = W.model_batches(c)
+    assert [bt["neg_head"] for bt in bts] == [False, True] and all(len(bt["h"]) == c["B"] and len(bt["neg"]) == c["B"] // c["chunk"] * c["N"] for bt in bts)
+    assert all((bt["w"] is not None) == c["impts"] for bt in bts)
+    for known in ((False, True) if c is W.MODEL_KNOWN_CASES.get(c["model"]) else (False,)):
+        for bt in bts:
+            e64, r64 = ent.astype(np.float64), rel.astype(np.float64)
+            kn = Q.planted_known(bt, c["chunk"], c["N"])[1] if known else None
+            out = Q.step(c, e64, np.zeros(len(e64)), r64, np.zeros(len(r64)), bt, kn)
+            W.model_conditions(c, out)
+            assert all(np.isfinite(out[k]).all() for k in ("pos_score", "neg_score", "g_pos_ent", "g_neg", "g_rel")) and np.abs(out["g_neg"]).max() > 0
+    # entities and relations repeat inside a batch and among the negatives: the update walks lists longer than one
+    ids = lambda bt: np.concatenate([bt["h"], bt["t"], bt["neg"]])
+    assert all(len(np.unique(ids(bt))) < len(ids(bt)) for bt in bts) and all(len(np.unique(bt["r"])) < c["B"] for bt in bts)
+
+
+@pytest.mark.parametrize("c", W.MODEL_REL_CASES, ids=lambda c: c["id"])
+def test_traced_layout_of_quate_relation_ranking(c):
+    """kge_rank_rel_workspace_bytes does not answer for QuatE (a QuatE call takes the DistMult layout followed by the normalised
+    relation table), so there is no size function to trace: the entry itself is, refused one byte short before any launch.  Its
+    buffers are ascending, disjoint and gapped, the DistMult buffers first, and end at workspace_cases.rel_need - without the gap the
+    bytes of _lib.rank_rel_workspace_bytes"""
+    from dglke_amd import _lib
+    h = _h()
+    one, d = 1, c["d_e"]
+    assert _lib.model_id("QuatE") == W.QUATE_ID and _lib.model_id("DistMult") == W.DISTMULT_ID
+    for gap in (W.GAP, 0):
+        with W.Trace(h, gap) as t:
+            base = int(h.kge_rank_rel_workspace_bytes(W.DISTMULT_ID, W.RANK_EB, W.TIE_N, d, d))
+            p0 = t.pairs()
+            need = W.rel_need(h, W.QUATE_ID, W.RANK_EB, W.TIE_N, d, d, gap)
+            t.reset()
+            args = lambda n: (W.QUATE_ID, one, W.TIE_N, one, W.TIE_N, None, one, one, one, W.TIE_E, d, d, 0.0, 1.0, one, one, W.RANK_EB, one, None, one, n, 0, None)
+            assert h.kge_rank_rel_eval(*args(need - 1)) == W.ERR_WORKSPACE
+            p1 = t.pairs()
+        W.check_layout(p1, need, gap)
+        assert p1[:len(p0)] == p0 and len(p1) == len(p0) + 1 and p1[-1][1] == 4 * W.TIE_N * d and need > base
+        if gap == 0:
+            assert need == _lib.rank_rel_workspace_bytes(W.QUATE_ID, W.RANK_EB, W.TIE_N, d, d)
+    assert W.WS_ENTRIES["kge_rank_rel_eval"].more([W.QUATE_ID]) == 1 and W.WS_ENTRIES["kge_rank_rel_eval"].more([W.DISTMULT_ID]) == 0
+
+
+@pytest.mark.parametrize("cid", sorted({o["case"] for o in W.OPTIM_ADAM}))
+def test_optim_cases_keep_the_ambiguity_cap(cid):
+    """the steps the kge_step_optim cases run, on adam_cases.step in float64: the ambiguity rule takes out at most AMBIGUITY_CAP of
+    either table; TransH keeps its distance condition; the table names the models, widths and options it says"""
+    import adam_cases as A
+    import transh_cases as TH
+    from dglke_amd import _lib
+    c = W.optim_case(cid)
+    d_e, d_r = A.widths(c)
+    assert d_e % 4 == 0 and d_r % 4 == 0 and max(d_e, d_r) <= _lib.ADAM_MAX_DIM
+    ent, rel = A.tables(c)
+    st = A.zero_state(c, ent, rel)
+    amb = dict(ent=np.zeros(ent.shape, bool), rel=np.zeros(rel.shape, bool))
+    for bt in A.batches(c, W.OPTIM_STEPS):
+        known = A.known_pairs(c, bt)[0] if c["known"] else None
+        with TH.adam_gradients():
+            info = A.step(c, st, bt, known)
+        if c["model"] == "TransH":
+            assert info["out"]["share"] >= TH.DIST_SHARE
+        for tab in ("ent", "rel"):
+            amb[tab] |= A.ambiguous(info[tab][0], info[tab][1], amb[tab].shape[0])
+            assert amb[tab].mean() <= A.AMBIGUITY_CAP, "%s: %.4f of %s is ambiguous" % (cid, amb[tab].mean(), tab)
+        assert len(info["ent"][0]) < c["n_ent"], "no untouched entity row"
+
+
+def test_optim_table_names_what_it_says():
+    import adam_cases as A
+    cases = {o["id"]: (W.optim_case(o["case"]), o["phases"]) for o in W.OPTIM_ADAM}
+    assert {c["model"] for c, _ in cases.values()} >= {"TransE_l2", "TransE_l1", "DistMult", "ComplEx", "QuatE", "PairRE", "TransH"}
+    assert any(max(A.widths(c)) > 512 for c, _ in cases.values()) and any(ph for _, ph in cases.values())
+    assert any(c["known"] and not ph for c, ph in cases.values()) and any(c["known"] and ph for c, ph in cases.values())
+    assert any(W.optim_case(i)["known"] for i in W.OPTIM_ADAGRAD) and not all(W.optim_case(i)["known"] for i in W.OPTIM_ADAGRAD)
+    e = W.WS_ENTRIES["kge_step_optim"]
+    assert (e.ws, e.phases, e.known) == (5, 7, 8)
 
 
 @pytest.mark.parametrize("c", W.SAMPLING_CASES, ids=lambda c: c["id"])

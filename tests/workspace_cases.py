@@ -112,17 +112,41 @@ def _loss_need(h, a, gap):
     return 2 * al(4 * B + gap) + (al(16 + gap) if a[10] else 0)
 
 
+QUATE_ID, DISTMULT_ID = 8, 2      # include/kge_hip.h KGE_QUATE, KGE_DISTMULT
+
+
+def rel_need(h, model, Eb, n_rel, d_e, d_r, gap):
+    """kge_rank_rel_workspace_bytes answers for the ids up to TransR; a QuatE call takes the DistMult layout followed by the
+    normalised relation table [n_rel, d_r] (include/kge_hip.h; _lib.rank_rel_workspace_bytes) - behind its own gap here"""
+    if int(model) != QUATE_ID:
+        return int(h.kge_rank_rel_workspace_bytes(model, Eb, n_rel, d_e, d_r))
+    base = int(h.kge_rank_rel_workspace_bytes(DISTMULT_ID, Eb, n_rel, d_e, d_r))
+    return base + al(4 * int(n_rel) * int(d_r) + gap) if base else 0
+
+
+def _topk_width(model, d_e):
+    from dglke_amd import _lib
+    return _lib.topk_row_width(int(model), int(d_e))
+
+
 class Entry(object):
-    def __init__(self, ws, need, halves=1, explicit=None):
-        self.ws, self.need, self.halves, self.explicit = ws, need, halves, explicit
+    """ws: the position of `ws` in the prototype (ws_bytes follows it); phases: the position of a `phases` argument - calls of one
+    step without PHASE_GATHER share the workspace of the call that had it; known: the position of `known`, followed by the pair
+    mask and its bytes (guarded in a buffer of its own)"""
+
+    def __init__(self, ws, need, halves=1, explicit=None, phases=None, known=None, more=None):
+        self.ws, self.need, self.halves, self.explicit, self.phases, self.known = ws, need, halves, explicit, phases, known
+        self.more = more          # more(args) -> buffers the entry carves beyond those its size function traced
 
 
 WS_ENTRIES = {
     "kge_step_fused": Entry(4, _step_need("kge_step_workspace_bytes", 0, 2)),
     "kge_step_fused_sampling": Entry(4, _step_need("kge_step_workspace_bytes", 0, 2)),
-    "kge_step_fused_known": Entry(4, _step_need("kge_step_workspace_bytes", 0, 2)),
-    "kge_step_phase": Entry(4, _step_need("kge_step_workspace_bytes", 0, 2)),
-    "kge_step_phase_known": Entry(4, _step_need("kge_step_workspace_bytes", 0, 2)),
+    "kge_step_fused_known": Entry(4, _step_need("kge_step_workspace_bytes", 0, 2), known=7),
+    "kge_step_phase": Entry(4, _step_need("kge_step_workspace_bytes", 0, 2), phases=6),
+    "kge_step_phase_known": Entry(4, _step_need("kge_step_workspace_bytes", 0, 2), phases=6, known=7),
+    # (hp, opt, tb, b, out, ws, ws_bytes, phases, known, mask, mask_bytes, stream)
+    "kge_step_optim": Entry(5, _step_need("kge_step_workspace_bytes", 0, 3), phases=7, known=8),
     "kge_step_grads": Entry(5, _step_need("kge_step_workspace_bytes", 0, 2)),
     "kge_step_sharded": Entry(4, _step_need("kge_step_workspace_bytes", 0, 2)),
     "kge_step_async": Entry(6, _step_need("kge_step_async_workspace_bytes", 1, 3), halves=2),
@@ -136,18 +160,19 @@ WS_ENTRIES = {
     "kge_rank_eval_split": Entry(24, lambda h, a, gap: int(h.kge_rank_workspace_bytes(a[21], a[18], a[13]))),
     # ONE chunk's workspace: the entry walks its blocks over it
     "kge_rank_eval_chunked": Entry(24, lambda h, a, gap: int(h.kge_rank_chunked_workspace_bytes(a[0], a[15], a[15], a[17], a[19], a[11], a[12]))),
-    "kge_rank_rel_eval": Entry(19, lambda h, a, gap: int(h.kge_rank_rel_workspace_bytes(a[0], a[16], a[4], a[10], a[11]))),
-    "kge_topk_select": Entry(22, lambda h, a, gap: int(h.kge_topk_workspace_bytes(a[9], a[15], a[10], a[19]))),
-    "kge_topk_select_filtered": Entry(22, lambda h, a, gap: int(h.kge_topk_workspace_bytes(a[9], a[15], a[10], a[19]))),
+    "kge_rank_rel_eval": Entry(19, lambda h, a, gap: rel_need(h, a[0], a[16], a[4], a[10], a[11], gap), more=lambda a: int(a[0] == QUATE_ID)),
+    # (no model argument: a PairRE / TransH call keeps the pair (a, w) / (a, w^, c) per query row - _lib.topk_row_width)
+    "kge_topk_select": Entry(22, lambda h, a, gap: int(h.kge_topk_workspace_bytes(a[9], a[15], _topk_width(a[0], a[10]), a[19]))),
+    "kge_topk_select_filtered": Entry(22, lambda h, a, gap: int(h.kge_topk_workspace_bytes(a[9], a[15], _topk_width(a[0], a[10]), a[19]))),
     "kge_topk_vector": Entry(5, lambda h, a, gap: int(h.kge_topk_workspace_bytes(0, a[1], 0, a[2]))),
 }
 
 
 # ---- the cases -----------------------------------------------------------------------------------------------------------------
 def _step(id, model, hidden, B=40, chunk=8, N=24, flags=0, de=False, dr=False, outputs=True, n_ent=300, n_rel=7, adv=True,
-          reg=1e-6, d_r=None):
+          reg=1e-6, d_r=None, genre="Logsigmoid"):
     return dict(id=id, model=model, hidden=hidden, B=B, chunk=chunk, N=N, flags=flags, de=de, dr=dr, outputs=outputs, n_ent=n_ent,
-                n_rel=n_rel, adv=adv, reg=reg, gamma=8.0, lr=0.1, d_r=d_r)
+                n_rel=n_rel, adv=adv, reg=reg, gamma=8.0, lr=0.1, d_r=d_r, genre=genre)
 
 
 DOUBLED = {"ComplEx": (True, True), "RotatE": (True, False)}      # rows twice the hidden width (72 at hidden 36)
@@ -187,6 +212,8 @@ def _steps():
     for m in ("TransE_l2", "ComplEx", "RotatE", "RESCAL", "TransR"):   # the plain training step: no optional output
         de, dr = DOUBLED.get(m, (False, False))
         out.append(_step("%s-h36-N24-plain" % m, m, 36, de=de, dr=dr, outputs=False))
+    for m in ("TransE_l2", "DistMult"):                           # the Softmax genre (no -adv form): the row-wise loss kernel's softmax rows
+        out.append(_step("%s-h36-N24-softmax" % m, m, 36, adv=False, genre="Softmax"))
     return out
 
 
@@ -199,6 +226,216 @@ PHASE_CASES = [c for c in STEP_CASES if c["id"] in ("TransE_l2-h36-N24", "DistMu
                                                       "RESCAL-h20", "TransR-36x72", "TransE_l2-h36-N24-f8", "TransE_l2-h36-N24-f128")]
 ASYNC_CASES = [dict(c, id=c["id"] + ("-rel" if f else ""), flags=f) for c in STEP_CASES
                if c["id"] in ("TransE_l2-h36-N24", "DistMult-h36-N21", "ComplEx-h36-N24", "RotatE-h36-N24", "TransE_l1-h36-N24") for f in (0, 64)]
+
+
+# ---- QuatE, PairRE, TransH: the steps ----------------------------------------------------------------------------------------
+# Cases, float64 statements, bounds and the conditions on the inputs are those of quate_cases.py / pairre_cases.py / transh_cases.py
+# (their step_case options by id, their step_tables / step_batches builders) at this file's shapes: B = 40, chunk = 8, N = 24 / 21
+# on 300 entities and 7 relations.  Widths: 36 (a multiple of 4 - QuatE's matrix-core route - and a partial 32-wide k stage / slab of
+# the TransH tiles and the PairRE kernels), 16 (below one k stage: TransH's top-K takes its VALU tile; QuatE's vector packs and
+# broadcast kernels), 260 (past 256, q = 65 scalar packs) at B = 16, N = 8.  Every step starts from the fixed tables (as in the
+# PairRE / TransH tests), so test_workspace_inputs.py can assert the conditions on the float64 statement alone.  `seed`: of the
+# batches, chosen so that the conditions hold (asserted there).
+NEW_MODELS = ("QuatE", "PairRE", "TransH")
+FORCE_PAIRWISE, NEG_DEG = 1, 32
+
+
+def model_cases(model):
+    import importlib
+    return importlib.import_module({"QuatE": "quate_cases", "PairRE": "pairre_cases", "TransH": "transh_cases"}[model])
+
+
+def model_gamma(model):
+    return 12.0 if model == "QuatE" else model_cases(model).GAMMA        # (test_gpu_quate.py's engine: 12)
+
+
+def model_d_r(model, d_e):
+    return d_e if model == "QuatE" else 2 * d_e
+
+
+def _mstep(model, d_e, tag, base="logsigmoid-adv", N=24, flags=0, outputs=True, B=40, chunk=8, n_ent=300, n_rel=7, seed=0):
+    Q = model_cases(model)
+    c = dict([x for x in Q.STEP_CASES if x["id"] == base][0])
+    c.update(id="%s-D%d-%s" % (model, d_e, tag), base=base, model=model, d_e=d_e, B=B, chunk=chunk, N=N, n_ent=n_ent, n_rel=n_rel,
+             flags=flags, outputs=outputs, seed=seed, gamma=model_gamma(model))
+    return c
+
+
+# (model, tag) -> seed of the batches where 0 does not hold the model's conditions
+MODEL_SEEDS = {("PairRE", "N24"): 1, ("PairRE", "w260"): 1}
+
+
+def _model_steps():
+    out = []
+    for m in NEW_MODELS:
+        k = lambda tag, **kw: _mstep(m, kw.pop("d_e", 36), tag, seed=MODEL_SEEDS.get((m, tag), 0), **kw)
+        out += [k("N24"), k("N21", N=21), k("plain", outputs=False), k("neg-deg", base="neg-deg"), k("softmax", base="softmax"),
+                k("hinge-pw", base="hinge-pw"), k("impts", base="impts")]
+        if m == "QuatE":             # (use_mfma knows QuatE only: PairRE and TransH have one route and ignore the flag - their layout
+            out.append(k("f1", flags=FORCE_PAIRWISE))        # under it is asserted equal on the CPU)
+        out += [k("w16", d_e=16), k("w260", d_e=260, B=16, N=8)]
+    return out
+
+
+MODEL_STEP_CASES = _model_steps()
+MODEL_PHASE_CASES = [c for c in MODEL_STEP_CASES if c["id"].endswith("-D36-N24")]
+MODEL_KNOWN_CASES = {c["model"]: c for c in MODEL_PHASE_CASES}
+# the second dirty donor: a larger TransH step (eight more buffers, four of them stacked) in front of every case that is not TransH
+DONOR_TRANSH = _mstep("TransH", 64, "donor", B=96, chunk=32, N=48)
+
+
+class _Shapes(object):
+    """the model module's builders at a case's shapes: its STEP_ENT / STEP_REL and the batch seed of the case, for the duration"""
+
+    def __init__(self, c):
+        self.c, self.Q = c, model_cases(c["model"])
+
+    def __enter__(self):
+        Q, c = self.Q, self.c
+        self.saved = (Q.STEP_ENT, Q.STEP_REL)
+        Q.STEP_ENT, Q.STEP_REL = c["n_ent"], c["n_rel"]
+        if hasattr(Q, "STEP_SEEDS"):
+            Q.STEP_SEEDS[c["id"]] = c["seed"]
+        return Q
+
+    def __exit__(self, *exc):
+        self.Q.STEP_ENT, self.Q.STEP_REL = self.saved
+        getattr(self.Q, "STEP_SEEDS", {}).pop(self.c["id"], None)
+        return False
+
+
+def model_shapes(c):
+    return _Shapes(c)
+
+
+def model_tables(c):
+    with _Shapes(c) as Q:
+        ent, rel = Q.step_tables(c["d_e"])
+    assert ent.shape == (c["n_ent"], c["d_e"]) and rel.shape == (c["n_rel"], model_d_r(c["model"], c["d_e"]))
+    return ent, rel
+
+
+def model_batches(c, steps=2):
+    with _Shapes(c) as Q:
+        if c["model"] == "QuatE" and c["seed"]:
+            return Q.step_batches(dict(c, id="%s#%d" % (c["id"], c["seed"])), steps)
+        return Q.step_batches(c, steps)
+
+
+def model_conditions(c, out):
+    """what the model's own step test asserts of its float64 statement's inputs"""
+    Q = model_cases(c["model"])
+    if c["model"] == "PairRE":
+        assert not out["amb"], c["id"] + ": a sign-ambiguous element in a step input"
+    if c["model"] == "TransH":
+        assert out["share"] >= Q.DIST_SHARE, "%s: a distance at %.3f of sqrt(alpha + beta)" % (c["id"], out["share"])
+        assert Q.residual_rows(out) == 0, c["id"] + ": a gradient row that is a cancellation residual"
+
+
+def model_hparams(c):
+    from dglke_amd import _lib
+    hp = _lib.KgeHParams()
+    hp.model = _lib.model_id(c["model"])
+    hp.d_e, hp.d_r = c["d_e"], model_d_r(c["model"], c["d_e"])
+    hp.loss_genre, hp.adv, hp.pairwise, hp.reg_norm = _lib.LOSS_IDS[c["genre"]], int(c["adv"]), int(c["pairwise"]), c["reg_norm"]
+    hp.flags = c["flags"] | (NEG_DEG if c["neg_deg"] else 0)
+    hp.gamma, hp.lr, hp.adv_temp, hp.reg_coef, hp.eps, hp.margin = c["gamma"], c["lr"], c["adv_temp"], c["reg_coef"], 1e-10, c["margin"]
+    hp.emb_init = (c["gamma"] + 2.0) / c["d_e"]
+    return hp
+
+
+def model_step_size(h, c, flags=None):
+    bt = model_batches(c, 1)[0]
+    UE = len(np.unique(np.concatenate([bt["h"], bt["t"], bt["neg"]])))
+    UR = len(np.unique(bt["r"]))
+    hp = model_hparams(c)
+    if flags is not None:
+        hp.flags = flags
+    return int(h.kge_step_workspace_bytes(C.byref(hp), c["B"], c["B"] // c["chunk"], c["chunk"], c["N"], UE, UR))
+
+
+# ---- QuatE, PairRE, TransH: the per-op negative scores, ranking, top-K ---------------------------------------------------------------
+# kge_score_neg_fwd / _bwd on the models' own op inputs (op_inputs / op_reference, whose conditions their CPU files assert for every
+# width and shape of their tables), both corruption sides.  QuatE: the matrix-core route and, under KGE_FLAG_FORCE_PAIRWISE, the pair
+# kernels; PairRE: a partial and a whole + 4 slab; TransH: below one k stage and a partial one, and (1, 12, 20), whose STACKED 24 rows
+# cross a 16-row tile that the 12 rows do not
+MODEL_NEG_CASES = [dict(id="%s-D%d-C%d-c%d-N%d-f%d" % ((m, d) + sh + (f,)), model=m, d_e=d, shape=sh, flags=f)
+                   for m, d, sh, f in (("QuatE", 36, (2, 8, 24), 0), ("QuatE", 36, (2, 8, 24), FORCE_PAIRWISE), ("QuatE", 48, (2, 8, 24), 0),
+                                       ("PairRE", 30, (2, 5, 33), 0), ("PairRE", 36, (2, 5, 33), 0),
+                                       ("TransH", 8, (2, 5, 33), 0), ("TransH", 36, (2, 5, 33), 0), ("TransH", 36, (1, 12, 20), 0))]
+# ranking and top-K on the models' integer-grid tables (tie_inputs: float32 scores are exact, so ranks and order EQUAL the float64
+# ones) with 300 entities = relations = candidates and 90 test triples; Eb = 32 leaves a last batch of 26
+TIE_N, TIE_E = 300, 90
+MODEL_RANK_CASES = [dict(id="%s-D%d-%s" % (m, d, "filt" if filt else "raw"), model=m, d_e=d, filt=filt)
+                    for m in NEW_MODELS for d in (16, 36) for filt in (False, True)]
+# every kind of CHUNKED_CASES: (kind, chunk, n_cand)
+MODEL_CHUNKED_CASES = [dict(id="%s-D36-%s" % (m, kind), model=m, d_e=36, kind=kind, chunk=chunk, n_cand=n)
+                       for m in NEW_MODELS for kind, chunk, n in (("all", 8, None), ("lists", 24, 40), ("lists1", 1, 130), ("self", 24, 40))]
+MODEL_REL_CASES = [dict(id="QuatE-D%d" % d, model="QuatE", d_e=d) for d in (16, 36)]
+# top-K: both modes of TOPK_CASES' table (one row per group against every candidate; groups of rows merged); TransH on both tiles
+MODEL_TOPK_CASES = [dict(id="%s-D%d-K%d-g%d" % (m, d, K, g), model=m, d_e=d, K=K, group=g)
+                    for m, ds in (("QuatE", (36,)), ("PairRE", (36,)), ("TransH", (16, 36))) for d in ds for K, g in ((10, 1), (128, 9))]
+
+
+def model_tie_inputs(model, d_e):
+    """the model module's tie_inputs at TIE_N entities and TIE_E test triples"""
+    Q = model_cases(model)
+    saved = Q.TIE_E
+    Q.TIE_E = TIE_E
+    if hasattr(Q, "TIE_SEEDS"):
+        Q.TIE_SEEDS.setdefault((TIE_N, d_e), 0)
+    try:
+        c = Q.tie_inputs(TIE_N, d_e)
+    finally:
+        Q.TIE_E = saved
+    assert len(c.h) == TIE_E and c.ent.shape == (TIE_N, d_e)
+    return c
+
+
+def chunk_candidates(kind, chunk, n_cand):
+    """[ceil(TIE_E / chunk), n_cand] entity ids per chunk, -1 = an empty slot (none in the first column); None: every entity"""
+    if n_cand is None:
+        return None
+    rng = np.random.RandomState(chunk * 1000 + n_cand)
+    nch = (TIE_E + chunk - 1) // chunk
+    cand = np.stack([rng.choice(TIE_N, n_cand, replace=False) for _ in range(nch)]).astype(np.int64)
+    cand[:, 1:][rng.rand(nch, n_cand - 1) < 0.2] = -1
+    return cand
+
+
+# ---- kge_step_optim ------------------------------------------------------------------------------------------------------------
+# Cases of adam_cases.py (adam_cases.case at gamma 4: its ambiguity rule then takes out a few per cent of the elements at most -
+# AMBIGUITY_CAP, asserted per case in test_workspace_inputs.py), two steps each.  Adam kind: one model of each update family at a
+# width that is a multiple of 4 - TransE_l1 sums its GN partials in a stand-alone reduction launch under Adam (the Adagrad step folds
+# that into its update) -, a width above 512 (the third instance of the update kernel), the four phase groups one by one, a known
+# index.  Adagrad kind: the existing step through the new entry.
+def optim_case(cid):
+    import adam_cases as A
+    import transh_cases as TH
+    c = TH.ADAM_CASE if cid == TH.ADAM_CASE["id"] else A.by_id(cid)
+    assert c["gamma"] == 4.0, cid
+    return c
+
+
+OPTIM_STEPS = 2
+OPTIM_ADAM = [dict(id=i, case=i, phases=False) for i in ("TransE_l2-w16", "TransE_l1-w16", "DistMult-w16", "ComplEx-w16", "QuatE-w16", "PairRE-w16",
+                                                         "TransH-w16", "DistMult-w516", "l2-known")] + [
+    dict(id="TransE_l1-w16-phases", case="TransE_l1-w16", phases=True), dict(id="l2-known-phases", case="l2-known", phases=True)]
+OPTIM_ADAGRAD = ["TransE_l2-w16", "TransE_l1-w16", "l2-known"]
+
+
+def optim_size(h, cid):
+    """kge_step_workspace_bytes of the case's first batch (Adam and Adagrad carve the same layout: the entry has no size of its own)"""
+    import adam_cases as A
+    from dglke_amd import _lib
+    c = optim_case(cid)
+    bt = A.batches(c, 1)[0]
+    hp = _lib.KgeHParams()
+    hp.model = _lib.model_id(c["model"])
+    hp.d_e, hp.d_r = A.widths(c)
+    hp.flags = NEG_DEG if c["neg_deg"] else 0
+    UE, UR = len(np.union1d(bt["nid"], bt["neg"])), len(np.unique(bt["r"]))
+    return int(h.kge_step_workspace_bytes(C.byref(hp), c["B"], c["B"] // c["chunk"], c["chunk"], c["N"], UE, UR))
 
 
 def step_dims(c):
@@ -331,12 +568,25 @@ def size_cases(h):
         out.append(("step-" + c["id"], lambda c=c: step_size(h, c)))
     for c in OTHER_STEP_SHAPES:
         out.append(("step-" + c["id"], lambda c=c: step_size(h, c)))
+    for c in MODEL_STEP_CASES + [DONOR_TRANSH]:
+        out.append(("step-" + c["id"], lambda c=c: model_step_size(h, c)))
+    for cid in sorted({o["case"] for o in OPTIM_ADAM} | set(OPTIM_ADAGRAD)):
+        out.append(("optim-" + cid, lambda cid=cid: optim_size(h, cid)))
     for c in ASYNC_CASES:
         out.append(("async-" + c["id"], lambda c=c: step_size(h, c, "kge_step_async_workspace_bytes") // 2))
     # kge_rank_eval / kge_rank_eval_split on every entity (test_rank_eval_split_and_plain)
     out.append(("rank-every-entity", lambda: int(h.kge_rank_workspace_bytes(RANK_EB, 300, rank_dims(RANK_CASES[0])[0]))))
     for c in NEG_CASES:
         out.append(("neg-" + c["id"], lambda c=c: int(h.kge_score_neg_workspace_bytes(mid(c["model"]), c["C"], c["chunk"], c["N"], c["d_e"]))))
+    for c in MODEL_NEG_CASES:
+        out.append(("neg-" + c["id"], lambda c=c: int(h.kge_score_neg_workspace_bytes(mid(c["model"]), c["shape"][0], c["shape"][1], c["shape"][2], c["d_e"]))))
+    for c in MODEL_RANK_CASES:
+        out.append(("rank-" + c["id"], lambda c=c: int(h.kge_rank_workspace_bytes(RANK_EB, TIE_N, c["d_e"]))))
+    for c in MODEL_CHUNKED_CASES:
+        out.append(("chunked-" + c["id"], lambda c=c: int(h.kge_rank_chunked_workspace_bytes(
+            mid(c["model"]), c["chunk"], c["chunk"], c["n_cand"] or TIE_N, int(c["kind"] == "self"), c["d_e"], model_d_r(c["model"], c["d_e"])))))
+    for c in MODEL_TOPK_CASES:
+        out.append(("topk-" + c["id"], lambda c=c: int(h.kge_topk_workspace_bytes(TIE_E, TIE_N, _topk_width(mid(c["model"]), c["d_e"]), c["K"]))))
     for c in RANK_CASES:
         out.append(("rank-" + c["id"], lambda c=c: int(h.kge_rank_workspace_bytes(RANK_EB, c["n_cand"], rank_dims(c)[0]))))
     for c in CHUNKED_CASES:
