@@ -109,6 +109,30 @@ class UniformChunkedSampler(object):
     def next_batches(self, count):
         return _plan.upload(self.next_plans(count), self.device)
 
+    def get_state(self):
+        """what the next plans depend on besides the constructor's arguments: the step count, the position in the current
+        permutation, that permutation (an int64 array, or None before the first plan) and the generator's state.  Batches that
+        __next__ has prefetched and not handed out are not part of it (the training loop draws with next_batches)."""
+        name, keys, pos, has_gauss, gauss = self.rng.get_state()
+        return dict(kind='host', step=int(self.step), pos=int(self._pos),
+                    perm=None if self._perm is None else np.array(self._perm, np.int64),
+                    rng=[str(name), [int(x) for x in keys], int(pos), int(has_gauss), float(gauss)])
+
+    def set_state(self, st):
+        """continue the sequence of the sampler get_state() was taken from (same triples and constructor arguments)"""
+        if st.get('kind') != 'host':
+            raise ValueError("UniformChunkedSampler.set_state: not a host sampler's state (kind %r)" % (st.get('kind'),))
+        perm = st['perm']
+        if perm is not None:
+            perm = np.array(perm, np.int64)
+            if perm.shape != (self.h.shape[0],):
+                raise ValueError("UniformChunkedSampler.set_state: a permutation of %d triples, the sampler has %d"
+                                 % (perm.shape[0], self.h.shape[0]))
+        name, keys, pos, has_gauss, gauss = st['rng']
+        self.rng.set_state((str(name), np.asarray(keys, np.uint32), int(pos), int(has_gauss), float(gauss)))
+        self.step, self._pos, self._perm = int(st['step']), int(st['pos']), perm
+        self._queue = []
+
     def __iter__(self):
         return self
 
@@ -226,6 +250,19 @@ class DeviceSampler(object):
         self.launches += 1
         self.host_step += n
         return out
+
+    def get_state(self):
+        """the eight int64 words of `state`, verbatim (position, step, ticket, -, and the tail jobs' cached epoch constants), and
+        the host's step counter.  Reads the device: call it when the sampler's stream is idle (the training loop's marks)."""
+        return dict(kind='device', state=[int(x) for x in self.state.tolist()], host_step=int(self.host_step))
+
+    def set_state(self, st):
+        """continue the sequence of the sampler get_state() was taken from (same triples, seed and batch geometry): the words are
+        copied INTO `state` - jobs and graphs that hold its address stay valid; the slots are refilled by the next launch"""
+        if st.get('kind') != 'device' or len(st['state']) != int(self.state.numel()):
+            raise ValueError("DeviceSampler.set_state: not a device sampler's state (kind %r)" % (st.get('kind'),))
+        self.state.copy_(th.tensor([int(x) for x in st['state']], dtype=th.int64))
+        self.host_step = int(st['host_step'])
 
     # elements (2 * batch + chunks * neg) of a batch the sampler LAUNCH builds (csrc/kge_sampler_common.hpp SP_MAXE_BIG: the reference's
     # batch-2048 recipes are 6144) and the tail jobs that ride on a step's launches (SP_MAXE)

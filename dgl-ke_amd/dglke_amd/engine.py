@@ -268,6 +268,41 @@ class StepEngine(object):
         else:
             self.rel_state.copy_(torch.as_tensor(rel_state))
 
+    def named_tensors(self):
+        """the live tensors a restart needs, by name: 'entity', 'relation' (rows), '..._state' (Adagrad: running mean squares;
+        Adam: per-row counts), TransR's 'projection' / 'projection_state', Adam's 'entity_mom' / 'relation_mom' [n, 2, d].  The
+        tensors themselves, not copies: engines that share tables name the same ones."""
+        t = {'entity': self.ent, 'relation': self.rel, 'entity_state': self.ent_state, 'relation_state': self.rel_state}
+        if self.proj is not None:
+            t['projection'], t['projection_state'] = self.proj, self.proj_state
+        if self.opt is not None:
+            t['entity_mom'], t['relation_mom'] = self.ent_mom, self.rel_mom
+        return t
+
+    def load_named(self, src, block_bytes=64 << 20):
+        """overwrite every tensor of named_tensors() IN PLACE from `src` (name -> array or tensor of the same shape and dtype; a
+        memory-mapped file is read row block by row block, at most block_bytes at a time): the table pointers of `tb`, engines
+        that share the tables and graphs captured on them stay valid.  Unlike load_tables nothing is zeroed by default: a name
+        that is missing, or one this engine does not have, is refused."""
+        dst = self.named_tensors()
+        if set(src) != set(dst):
+            raise _lib.KgeError("load_named: the engine has %s, given %s" % (sorted(dst), sorted(src)))
+        for name, d in dst.items():
+            s = src[name]
+            if tuple(s.shape) != tuple(d.shape):
+                raise _lib.KgeError("load_named: %s is %s, the engine's is %s" % (name, tuple(s.shape), tuple(d.shape)))
+            n = int(d.shape[0])
+            row_bytes = max(1, d[0].numel() * d.element_size()) if n else 1
+            per = max(1, int(block_bytes) // row_bytes)
+            for a in range(0, n, per):
+                blk = s[a:a + per]
+                if not isinstance(blk, torch.Tensor):
+                    import numpy as np
+                    blk = torch.from_numpy(np.array(blk))         # (one block in host memory)
+                if blk.dtype != d.dtype:
+                    raise _lib.KgeError("load_named: %s is %s, the engine's is %s" % (name, blk.dtype, d.dtype))
+                d[a:a + per].copy_(blk)
+
     def workspace_for(self, b):
         need = lib().kge_step_workspace_bytes(C.byref(self.hp), b.B, b.C, b.chunk, b.N, b.UE, b.UR)
         if need > self._ws_bytes:

@@ -28,6 +28,7 @@ import numpy as np
 import torch as th
 
 from . import _lib
+from . import checkpoint as ckpt
 from . import dist as kd
 from . import eval as kev
 from ._lib import KgeError
@@ -141,6 +142,16 @@ class ArgParser(argparse.ArgumentParser):
                'next step\'s pull, or every exchange, on a side stream next to the compute (overlap: default with --async_update).  '
                'With --graph_steps > 0 the group - kernels and RCCL collectives - replays from one hipGraph; --graph_steps 0 launches '
                'eagerly (the way out if a recorded schedule ever stalls on a new software stack)')
+        a('--checkpoint_interval', type=int, default=0,
+          help='write a checkpoint to <run directory>/checkpoint every this many steps and at --max_step (0: none): the tables, the '
+               'optimizer state (Adam: the moment tables too), every trainer\'s sampler state and loss sums - what --resume needs to '
+               'continue the run bit for bit.  Only the newest is kept; the directory is also a model directory for dglke_eval / '
+               'dglke_predict.  One GPU; not with --async_update_pipeline or --async_update_rel')
+        a('--resume', type=str, default=None, metavar='PATH',
+          help='continue the run whose checkpoint PATH holds (a run directory with checkpoint/, or a checkpoint directory) at its '
+               'step + 1 up to --max_step, in a new run directory.  "latest": the newest checkpoint of this model and dataset under '
+               '--save_path, a fresh run if there is none.  Model, widths, optimizer, --num_proc, batch geometry, --seed, the '
+               'weighting flags and the dataset must be the checkpointed run\'s; every other flag may change (--lr, --max_step, ...)')
         a('--seed', type=int, default=0, help='seed of the table initialisation and of the device sampler')
         a('--graph_steps', type=int, default=100, help='steps per captured hipGraph (0: eager launches)')
         a('--target_mrr', type=float, default=None,
@@ -167,11 +178,12 @@ def prepare_save_path(args):
     os.makedirs(args.save_path, exist_ok=True)
 
 
-def write_config(args, emap_file, rmap_file):
-    """config.json of utils.py:35-49 (same keys, including the reference's 'emp_file' spelling)"""
+def write_config(args, emap_file, rmap_file, path=None):
+    """config.json of utils.py:35-49 (same keys, including the reference's 'emp_file' spelling); path: the directory it goes to
+    (default: args.save_path)"""
     conf = dict(vars(args))
     conf.update({'emp_file': emap_file, 'rmap_file': rmap_file})
-    with open(os.path.join(args.save_path, 'config.json'), 'w') as f:
+    with open(os.path.join(path or args.save_path, 'config.json'), 'w') as f:
         json.dump(conf, f, indent=4)
 
 
@@ -183,14 +195,16 @@ def save_model(args, model, emap_file=None, rmap_file=None):
     write_config(args, emap_file, rmap_file)
 
 
-def step_marks(max_step, log_interval, eval_interval, valid, force_sync_interval=-1, force_sync=False):
+def step_marks(max_step, log_interval, eval_interval, valid, force_sync_interval=-1, force_sync=False, checkpoint_interval=0,
+               start_step=0):
     """the sorted steps at which the training loop stops enqueueing: every multiple of --log_interval, with --valid of
-    --eval_interval, where the trainers wait for each other (force_sync) of --force_sync_interval, and max_step"""
+    --eval_interval, where the trainers wait for each other (force_sync) of --force_sync_interval, of --checkpoint_interval, and
+    max_step; start_step (a resumed run): only the marks above it"""
     marks = {max_step}
-    for iv in (log_interval, eval_interval if valid else 0, force_sync_interval if force_sync else 0):
+    for iv in (log_interval, eval_interval if valid else 0, force_sync_interval if force_sync else 0, checkpoint_interval):
         if iv and iv > 0:
             marks.update(range(iv, max_step + 1, iv))
-    return sorted(marks)
+    return sorted(m for m in marks if m > start_step) if start_step else sorted(marks)
 
 
 def plan_enqueue(n, G, host_step, have_group_graph, n_slots, rem_keys):
@@ -383,7 +397,9 @@ class _Trainer(object):
     def sync_tables(self):
         pass
 
-    def train(self):
+    def train(self, start_step=0, start_since_log=0):
+        """start_step, start_since_log (a resumed run, whose state the caller has put back): the steps already trained and how many
+        of them the lanes' loss sums hold - the loop goes on with step start_step + 1"""
         args = self.args
         keys = ['loss'] if args.pairwise or args.loss_genre == 'Softmax' else ['pos_loss', 'neg_loss', 'loss']
         if args.regularization_coef > 0 and args.regularization_norm > 0:
@@ -402,10 +418,11 @@ class _Trainer(object):
         th.cuda.synchronize()
         self.barrier()
         train_start = start = time.time()
-        step = since_log = 0
+        step, since_log = int(start_step), int(start_since_log)
         t_train = t_interval = 0.0
         timed = reached = None
-        for nxt in step_marks(args.max_step, args.log_interval, args.eval_interval, args.valid, fsi, force_sync):
+        ckpt_iv = getattr(args, 'checkpoint_interval', 0) or 0
+        for nxt in step_marks(args.max_step, args.log_interval, args.eval_interval, args.valid, fsi, force_sync, ckpt_iv, step):
             n = nxt - step
             at_log = args.log_interval > 0 and nxt % args.log_interval == 0
             if n > 0:
@@ -460,6 +477,9 @@ class _Trainer(object):
                 self.barrier()
                 # (no reset of `start` here: the reference's '[Train] N steps take' interval includes a validation that falls
                 #  inside it, train_pytorch.py:168-176)
+            if ckpt_iv > 0 and (step % ckpt_iv == 0 or step == args.max_step):
+                # between two steps, behind the mark's synchronize, its [Train] lines and its validation: only reads
+                self.write_checkpoint(step, since_log)
         th.cuda.synchronize()
         print('proc {} takes {:.3f} seconds'.format(self.rank, time.time() - train_start))
         self.barrier()
@@ -529,6 +549,11 @@ class Trainer(_Trainer):
 
     def loss_engines(self):
         return [(lane.k, lane.engine) for lane in self.lanes]
+
+    def write_checkpoint(self, step, since_log):
+        """--checkpoint_interval: <run directory>/checkpoint as of `step` (checkpoint.save_trainer)"""
+        nbytes, secs = ckpt.save_trainer(self, step, since_log, getattr(self, 'args_parsed', None))
+        print('[proc 0]checkpoint at step {}: {} bytes in {:.3f} s'.format(step, nbytes, secs))
 
     def evaluate(self, which, mode):
         args, m = self.args, self.model
@@ -977,12 +1002,17 @@ def main(argv=None, before_train=None):
     check_transh(args)                           # before anything is loaded or created
     check_weighted_device_sampler(args)          # before anything is loaded or created
     check_optimizer(args)                        # before anything is loaded or created
+    ckpt.check_flags(args)                       # before anything is loaded or created
     if args.neg_deg_sample_eval:                # before anything is loaded or created
         if len(args.gpu) > 1:
             raise KgeError("--neg_deg_sample_eval is not available on sharded tables")
         assert args.no_eval_filter, "if negative sampling based on degree, we can't filter positive edges."   # train.py:878
     if args.eval_relation and len(args.gpu) > 1:
         raise KgeError("--eval_relation is not available on sharded tables")
+    args_parsed = dict(vars(args))               # the command line as given: what a later --resume reports changes against
+    # --resume reads its checkpoint's description, checks the flags against it and --max_step against its step here: before the
+    # dataset is loaded and before this run's own directory is made (None: --resume latest found nothing, a fresh run)
+    resume = ckpt.open_resume(args) if args.resume else None
     prepare_save_path(args)
     init_time_start = time.time()
     multi = len(args.gpu) > 1                    # one trainer process per listed GPU (the same GPU may be listed twice)
@@ -1010,11 +1040,17 @@ def main(argv=None, before_train=None):
         kd.spawn_ranks(_mp_worker, args)
         return None
     trainer = Trainer(args, dataset)
+    trainer.args_parsed = args_parsed
+    if resume is not None:
+        ckpt.restore_trainer(trainer, resume)     # (in place, and before the hook: it sees the restored state)
     if before_train is not None:
         before_train(trainer)
     print('Total initialize time {:.3f} seconds'.format(time.time() - init_time_start))
     start = time.time()
-    trainer.train()
+    if resume is not None:
+        trainer.train(start_step=resume.step, start_since_log=resume.since_log)
+    else:
+        trainer.train()
     print('training takes {} seconds'.format(time.time() - start))
     if not args.no_save_emb:
         save_model(args, trainer.model, emap_file=dataset.emap_fname, rmap_file=dataset.rmap_fname)
