@@ -339,6 +339,12 @@ def planted_known(bt, chunk, N):
 TIE_CASES = [(7, 8), (130, 8), (130, 32)]            # (entities = relations = candidates, d_e)
 TIE_E = 40                      # test triples
 TIE_CHUNK = 16                  # chunked_ranks: two chunks of 16 and one of 8
+# several tiles (tests/test_gpu_new_model_shapes.py): 300 candidates are three 128-column tiles, the last of 44; 150 test triples are
+# two 128-row tiles, the last of 22; chunks of 100 triples: the second one spans both row tiles.  Width 36 = one 32-wide slab + 4:
+# four entries +-1 keep |x| = 2 at any width, so both widths stay exact
+TIE_WIDE_CASES = [(300, 32), (300, 36)]
+TIE_WIDE_E = 150
+TIE_WIDE_CHUNK = 100
 TIE_GAMMA = 6.0
 
 
@@ -355,9 +361,10 @@ def tie_scores(c, h, r, t, neg_head, dtype=np.float64):
 
 
 @functools.lru_cache(maxsize=None)
-def tie_inputs(n, d_e):
-    """tables, TIE_E test triples and known triples: the test triples and, for the first 12 of them and both sides, one planted
-    triple whose corrupted entity TIES the positive where there is one"""
+def tie_inputs(n, d_e, E=None):
+    """tables, E (default: TIE_E, read at the call) test triples and known triples: the test triples and, for the first 12 of them
+    and both sides, one planted triple whose corrupted entity TIES the positive where there is one"""
+    E = TIE_E if E is None else E
     rng = np.random.RandomState(_seed("pairre-tie", n, d_e))
     c = Case()
     c.n, c.d_e = n, d_e
@@ -365,7 +372,7 @@ def tie_inputs(n, d_e):
     for i in range(n):
         c.ent[i, rng.choice(d_e, 4, replace=False)] = rng.choice([-1.0, 1.0], 4)
     c.rel = rng.randint(-2, 3, (n, 2 * d_e)).astype(np.float32)
-    c.h, c.r, c.t = rng.randint(0, n, TIE_E), rng.randint(0, n, TIE_E), rng.randint(0, n, TIE_E)
+    c.h, c.r, c.t = rng.randint(0, n, E), rng.randint(0, n, E), rng.randint(0, n, E)
     extra = []
     for side in ("tail", "head"):
         p, S = tie_scores(c, c.h, c.r, c.t, side == "head")
@@ -407,9 +414,11 @@ def ranks_of(p, S, lists=None, strict=False):
     return out
 
 
-def tie_candidates(n):
-    """[n_chunks, 12] candidate ids per chunk of TIE_CHUNK triples, drawn with replacement, two slots per list -1"""
-    n_chunks = (TIE_E + TIE_CHUNK - 1) // TIE_CHUNK
+def tie_candidates(n, E=None, chunk=None):
+    """[n_chunks, 12] candidate ids per chunk of `chunk` (default: TIE_CHUNK) of E (default: TIE_E) triples, drawn with replacement,
+    two slots per list -1"""
+    E, chunk = TIE_E if E is None else E, TIE_CHUNK if chunk is None else chunk
+    n_chunks = (E + chunk - 1) // chunk
     rng = np.random.RandomState(_seed("pairre-tie-cand", n))
     cand = rng.randint(0, n, (n_chunks, 12)).astype(np.int64)
     for k in range(n_chunks):
@@ -417,20 +426,21 @@ def tie_candidates(n):
     return cand
 
 
-def chunked_ranks_of(c, p, S, neg_head, cand=None, self_cand=False):
+def chunked_ranks_of(c, p, S, neg_head, cand=None, self_cand=False, chunk=None):
     """ranks against per-chunk candidate lists (-1: an empty slot); self_cand: the chunk's own corrupted-side entities are prepended
     and the triple's own column scores 0.0 (the --neg_deg_sample_eval protocol, tests/chunked_eval_cases.py)"""
     side = c.h if neg_head else c.t
     E = len(p)
+    chunk = TIE_CHUNK if chunk is None else chunk
     out = np.zeros(E, np.int64)
     for i in range(E):
-        k = i // TIE_CHUNK
+        k = i // chunk
         ids = cand[k][cand[k] >= 0] if cand is not None else np.arange(c.n)
         s = S[i, ids]
         if self_cand:
-            own_ids = side[k * TIE_CHUNK:min(E, (k + 1) * TIE_CHUNK)]
+            own_ids = side[k * chunk:min(E, (k + 1) * chunk)]
             so = S[i, own_ids].copy()
-            so[i - k * TIE_CHUNK] = 0.0
+            so[i - k * chunk] = 0.0
             s = np.concatenate([so, s])
         out[i] = 1 + int((s >= p[i]).sum())
     return out

@@ -309,6 +309,11 @@ TIE_CASES = [(n, d) for n in TIE_SIZES for d in TIE_WIDTHS]
 TIE_E = 40                      # test triples
 TIE_SEEDS = {(7, 8): 0, (7, 32): 0, (130, 8): 0, (130, 32): 0}      # (asserted to give the ties the tests need: test_quate_inputs.py)
 TIE_CHUNK = 16                  # chunked_ranks: two chunks of 16 and one of 8
+# several tiles, as pairre_cases.TIE_WIDE_CASES (width 36: quarter 9, scalar packs; integer entries stay exact at any width)
+TIE_WIDE_CASES = [(300, 32), (300, 36)]
+TIE_WIDE_E = 150
+TIE_WIDE_CHUNK = 100
+TIE_SEEDS.update({(300, 32, TIE_WIDE_E): 0, (300, 36, TIE_WIDE_E): 0})
 
 
 class Case(object):
@@ -341,11 +346,13 @@ def rel_tie_scores(c, h, r, t, dtype=np.float64):
 
 
 @functools.lru_cache(maxsize=None)
-def tie_inputs(n, d_e):
-    """tables, TIE_E test triples - the first half picked from a pool for a candidate other than the own entity that ties the
-    positive score on the tail side, the head side or the relation side, in turn - and known triples: the test triples and, for
+def tie_inputs(n, d_e, E=None):
+    """tables, E (default: TIE_E, read at the call) test triples - the first half picked from a pool for a candidate other than the
+    own entity that ties the positive score on the tail side, the head side or the relation side, in turn - and known triples: the test triples and, for
     the first 12 of them and every side, one planted triple whose corrupted entity (relation) TIES the positive where there is one"""
-    rng = np.random.RandomState(_seed("quate-tie", n, d_e, TIE_SEEDS[(n, d_e)]))
+    key = (n, d_e) if E is None else (n, d_e, E)
+    E = TIE_E if E is None else E
+    rng = np.random.RandomState(_seed("quate-tie", n, d_e, TIE_SEEDS[key]))
     c = Case()
     c.n, c.d_e = n, d_e
     c.ent = rng.randint(-3, 4, (n, d_e)).astype(np.float32)
@@ -364,12 +371,12 @@ def tie_inputs(n, d_e):
         m[np.arange(P), own] = False
         tied.append(m.any(1))
     pick, k = [], 0
-    while len(pick) < TIE_E // 2 and k < 3 * P:
+    while len(pick) < E // 2 and k < 3 * P:
         i = k // 3
         if tied[k % 3][i] and i not in pick:
             pick.append(i)
         k += 1
-    rest = [i for i in range(P) if i not in pick][:TIE_E - len(pick)]
+    rest = [i for i in range(P) if i not in pick][:E - len(pick)]
     idx = rng.permutation(np.array(pick + rest))
     c.h, c.r, c.t = ph[idx].copy(), pr[idx].copy(), pt[idx].copy()
     extra = []

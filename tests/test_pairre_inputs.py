@@ -198,8 +198,8 @@ def test_planted_known_pairs_take_their_columns_out():
 # the integer-grid ranking inputs
 # --------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n,d_e", Q.TIE_CASES, ids=["n%d-D%d" % c for c in Q.TIE_CASES])
-def test_grid_inputs_are_exact_in_float32_and_hold_ties(n, d_e):
-    c = Q.tie_inputs(n, d_e)
+def test_grid_inputs_are_exact_in_float32_and_hold_ties(n, d_e, wide_e=None, chunk=None):
+    c = Q.tie_inputs(n, d_e) if wide_e is None else Q.tie_inputs(n, d_e, wide_e)      # (the several-tile sizes)
     assert np.all((c.ent != 0).sum(1) == 4) and set(np.unique(c.ent).tolist()) == {-1.0, 0.0, 1.0}
     assert np.all(Q.norm(c.ent) == 2.0)
     eu = Q.unit(c.ent)
@@ -227,9 +227,9 @@ def test_grid_inputs_are_exact_in_float32_and_hold_ties(n, d_e):
             assert own[i] in ids
             filt_ties += int(((S[i, ids] == p[i]) & (ids != own[i])).sum())
         assert np.all(filt <= raw - 1)
-        cand = Q.tie_candidates(n)
+        cand = Q.tie_candidates(n) if wide_e is None else Q.tie_candidates(n, wide_e, chunk)
         assert (cand == -1).sum(1).min() == 2 and cand.max() < n
-        listed, selfc = Q.chunked_ranks_of(c, p, S, neg_head, cand), Q.chunked_ranks_of(c, p, S, neg_head, cand, True)
+        listed, selfc = (Q.chunked_ranks_of(c, p, S, neg_head, cand, sc, chunk) for sc in (False, True))
         assert listed.max() > 1 and np.any(selfc != listed)
     assert filt_ties >= 1, "no tie on the filtered side"
 

@@ -185,8 +185,8 @@ def test_planted_known_pairs_take_their_columns_out():
 # the integer-grid ranking inputs
 # --------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n,d_e", Q.TIE_CASES, ids=["n%d-D%d" % c for c in Q.TIE_CASES])
-def test_grid_inputs_are_exact_in_float32_and_hold_ties(n, d_e):
-    c = Q.tie_inputs(n, d_e)
+def test_grid_inputs_are_exact_in_float32_and_hold_ties(n, d_e, wide_e=None):
+    c = Q.tie_inputs(n, d_e) if wide_e is None else Q.tie_inputs(n, d_e, wide_e)      # (the several-tile size)
     assert c.ent.min() == -3 and c.ent.max() == 3 and np.array_equal(c.ent, np.rint(c.ent))
     nr = Q.norms(c.rel.astype(np.float64))
     assert np.array_equal(np.log2(nr), np.rint(np.log2(nr))), "every relation norm is a power of two"

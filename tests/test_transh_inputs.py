@@ -250,10 +250,10 @@ def test_adam_case_keeps_the_distance_condition_and_the_ambiguity_cap():
 # the integer-grid ranking inputs
 # --------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n,d_e", Q.TIE_CASES, ids=["n%d-D%d" % c for c in Q.TIE_CASES])
-def test_grid_inputs_are_exact_in_float32_and_hold_ties(n, d_e):
+def test_grid_inputs_are_exact_in_float32_and_hold_ties(n, d_e, wide_e=None, chunk=None):
     import pairre_cases as PR
     assert Q.TIE_CASES == PR.TIE_CASES and (Q.TIE_E, Q.TIE_CHUNK) == (PR.TIE_E, PR.TIE_CHUNK)
-    c = Q.tie_inputs(n, d_e)
+    c = Q.tie_inputs(n, d_e) if wide_e is None else Q.tie_inputs(n, d_e, wide_e)      # (the several-tile sizes)
     w = c.rel[:, d_e:]
     assert np.all((w[1:] != 0).sum(1) == 4) and set(np.unique(w).tolist()) == {-1.0, 0.0, 1.0} and not w[0].any()
     wu = Q.unit(w)
@@ -289,9 +289,9 @@ def test_grid_inputs_are_exact_in_float32_and_hold_ties(n, d_e):
             assert own[i] in ids
             filt_ties += int(((S[i, ids] == p[i]) & (ids != own[i])).sum())
         assert np.all(filt <= raw - 1)
-        cand = Q.tie_candidates(n)
+        cand = Q.tie_candidates(n) if wide_e is None else Q.tie_candidates(n, wide_e, chunk)
         assert (cand == -1).sum(1).min() == 2 and cand.max() < n
-        listed, selfc = Q.chunked_ranks_of(c, p, S, neg_head, cand), Q.chunked_ranks_of(c, p, S, neg_head, cand, True)
+        listed, selfc = (Q.chunked_ranks_of(c, p, S, neg_head, cand, sc, chunk) for sc in (False, True))
         assert listed.max() > 1 and np.any(selfc != listed)
     assert filt_ties >= 1, "no tie on the filtered side"
 

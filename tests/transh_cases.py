@@ -378,6 +378,11 @@ def adam_gradients():
 TIE_CASES = [(7, 8), (130, 8), (130, 32)]            # (entities = relations = candidates, d_e), as pairre_cases.TIE_CASES
 TIE_E = 40                      # test triples
 TIE_CHUNK = 16                  # chunked_ranks: two chunks of 16 and one of 8
+# several tiles, as pairre_cases.TIE_WIDE_CASES: 150 test triples are also three of rank_gemm_transh_kernel's 64-query tiles
+# (RANK_TH_BM), the last of 22.  Four entries +-1 keep |w| = 2 at any width: both widths stay exact
+TIE_WIDE_CASES = [(300, 32), (300, 36)]
+TIE_WIDE_E = 150
+TIE_WIDE_CHUNK = 100
 TIE_GAMMA = 6.0
 
 
@@ -394,10 +399,11 @@ def tie_scores(c, h, r, t, neg_head, dtype=np.float64):
 
 
 @functools.lru_cache(maxsize=None)
-def tie_inputs(n, d_e):
-    """tables, TIE_E test triples and known triples: the test triples and, for the first 12 of them and both sides, one planted
-    triple whose corrupted entity TIES the positive where there is one.  Entity entries are sparse (most are 0) so that few distinct
-    distances are shared by many candidates."""
+def tie_inputs(n, d_e, E=None):
+    """tables, E (default: TIE_E, read at the call) test triples and known triples: the test triples and, for the first 12 of them
+    and both sides, one planted triple whose corrupted entity TIES the positive where there is one.  Entity entries are sparse
+    (most are 0) so that few distinct distances are shared by many candidates."""
+    E = TIE_E if E is None else E
     rng = np.random.RandomState(_seed("transh-tie", n, d_e))
     c = Case()
     c.n, c.d_e = n, d_e
@@ -409,7 +415,7 @@ def tie_inputs(n, d_e):
         c.rel[i, rng.choice(d_e, 2, replace=False)] = rng.choice([-1.0, 1.0], 2)
         c.rel[i, d_e + rng.choice(d_e, 4, replace=False)] = rng.choice([-1.0, 1.0], 4)
     c.rel[0, d_e:] = 0.0                                  # one relation without a hyperplane
-    c.h, c.r, c.t = rng.randint(0, n, TIE_E), rng.randint(0, n, TIE_E), rng.randint(0, n, TIE_E)
+    c.h, c.r, c.t = rng.randint(0, n, E), rng.randint(0, n, E), rng.randint(0, n, E)
     c.r[0] = 0
     extra = []
     for side in ("tail", "head"):
