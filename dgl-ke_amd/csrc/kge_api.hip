@@ -50,8 +50,13 @@ struct Carver {
 };
 
 int check_model(int model, int d_e, int d_r) {
-    if (model < KGE_TRANSE_L1 || (model > KGE_TRANSR && model != KGE_QUATE && model != KGE_PAIRRE && model != KGE_TRANSH))
+    if (model < KGE_TRANSE_L1 || (model > KGE_TRANSR && model != KGE_QUATE && model != KGE_PAIRRE && model != KGE_TRANSH && model != KGE_TRANSD))
         return fail(KGE_ERR_ARG, "unknown model %d", model);
+    if (model == KGE_TRANSD) {         // rows [x | x_p] of two halves, every path a matrix-core product over the first: 16-byte halves
+        if (d_e < 8 || d_e % 8 || d_r != d_e)
+            return fail(KGE_ERR_ARG, "TransD needs d_e == d_r and d_e %% 8 == 0, rows [x | x_p] of two halves (got %d, %d)", d_e, d_r);
+        return KGE_OK;
+    }
     if (model == KGE_TRANSH) {         // every path is a matrix-core product: 16-byte rows
         if (d_e < 4 || d_e % 4 || (int64_t)d_r != 2 * (int64_t)d_e)
             return fail(KGE_ERR_ARG, "TransH needs d_e >= 4, d_e %% 4 == 0 and d_r == 2 * d_e, r = [d | w] (got %d, %d)", d_e, d_r);
@@ -99,6 +104,11 @@ int no_pairre(const char *who) {
 // TransH likewise
 int no_transh(const char *who) {
     return fail(KGE_ERR_ARG, "%s: not available for TransH (strict step on local tables, single-table entity ranking and top-K)", who);
+}
+
+// TransD likewise
+int no_transd(const char *who) {
+    return fail(KGE_ERR_ARG, "%s: not available for TransD (strict step on local tables, single-table entity ranking and top-K)", who);
 }
 
 inline float rot_div_of(float emb_init) { return (float)((double)emb_init / M_PI); }
@@ -224,6 +234,65 @@ int transh_neg_bwd(const TranshBlock &k, const float *G, float *PQc, float *rs, 
     return KGE_OK;
 }
 
+// TransD (kge_transd.hip): the edge forward of B edges whose rows come from src, into the stacked operand of chunks of `chunk` rows
+void fill_transd_edge(TransdEdgeArgs &e, const EdgeSrc &src, int B, int chunk, int d_e, int neg_head, float gamma, float *P, float *AP,
+                      float *alpha, float *sig, float *u) {
+    e = TransdEdgeArgs{};
+    e.src = src; e.B = B; e.chunk = chunk; e.d_e = d_e; e.neg_head = neg_head; e.gamma = gamma; e.pos_score = P;
+    e.AP = AP; e.alpha = alpha; e.sig = sig; e.u = u;
+}
+// |n|^2, m . n and the dense first halves of n candidate rows base + (idx ? idx[j] : j) * d_e
+int transd_cands(const float *base, const int64_t *idx, int64_t n, int d_e, float *beta, float *cj, float *Nh, hipStream_t s) {
+    TransdEdgeArgs e{};
+    e.d_e = d_e; e.nbase = base; e.nidx = idx; e.n_neg = (int)n; e.beta = beta; e.cj = cj; e.Nh = Nh;
+    return launch_transd_edge_fwd(e, s);
+}
+// one chunked scoring block: the stacked operand (k = d_e / 2 columns), its row statistics, the candidates' dense first halves
+// and their scalars, and the blocks behind them
+struct TransdBlock {
+    int C, chunk, N, d_e; float gamma;
+    const float *AP, *alpha, *sig, *u;                // [C, 2 chunk, k], [C*chunk] x 3
+    const float *Nh, *beta, *cj;                      // [C*N, k], [C*N] x 2
+    float *PQ;                                        // [C, 2 chunk, N] raw products
+};
+void fill_transd_neg(TransdNegArgs &n, const TransdBlock &k) {
+    n = TransdNegArgs{};
+    n.C = k.C; n.chunk = k.chunk; n.N = k.N; n.gamma = k.gamma; n.alpha = k.alpha; n.sig = k.sig; n.u = k.u; n.beta = k.beta; n.cj = k.cj;
+    n.PQ = k.PQ;
+}
+// p | q = [A ; P] . Nh^T on the forward tiles of kge_neg_gemm.hip in their DistMult form (2 chunk rows per chunk, k columns), then S
+int transd_products(const TransdBlock &k, hipStream_t s) {
+    GemmArgs g; fill_gemm(g, KGE_DISTMULT, k.C, 2 * k.chunk, k.N, k.d_e / 2, k.gamma, k.AP, k.Nh, nullptr);
+    g.S = k.PQ;
+    KGE_TRY(launch_neg_fwd_gemm(g, s));
+    return KGE_OK;
+}
+int transd_scores(const TransdBlock &k, float *S, hipStream_t s) {
+    if (int rc = transd_products(k, s)) return rc;
+    TransdNegArgs n; fill_transd_neg(n, k);
+    n.S = S;
+    KGE_TRY(launch_transd_score(n, s));
+    return KGE_OK;
+}
+// the buffers of a TransD block, for B edges in chunks against CN candidate rows, N per chunk (d_e: the row width 2 k)
+struct TransdBufs { float *AP, *sig, *u, *cj, *Nh, *PQ, *PQc, *rs, *rc, *rc2, *cs, *gc, *GAP, *GNp; };
+// G = dL/dS -> the products GAP = Ga | Grho [C, 2 chunk, k] and GNp [C*N, k] (their row / column terms: rs, rc, rc2, cs, gc; the edge
+// backward adds them).  The backward tiles of kge_neg_gemm.hip in their DistMult form with K = 2 chunk; beyond the rows a tile's
+// workgroup indexes (GB_MAXK) the pairwise kernels, which take any size
+int transd_neg_bwd(const TransdBlock &k, const float *G, const TransdBufs &t, hipStream_t s) {
+    TransdNegArgs n; fill_transd_neg(n, k);
+    n.G = G; n.PQc = t.PQc; n.rs = t.rs; n.rc = t.rc; n.rc2 = t.rc2; n.cs = t.cs; n.gc = t.gc;
+    KGE_TRY(launch_transd_coef(n, s));
+    GemmArgs g; fill_gemm(g, KGE_DISTMULT, k.C, 2 * k.chunk, k.N, k.d_e / 2, k.gamma, k.AP, k.Nh, nullptr);
+    g.W = t.PQc; g.GA = t.GAP; g.GN = t.GNp;
+    if ((2 * k.chunk > k.N ? 2 * k.chunk : k.N) > KGE_NEG_BWD_GEMM_MAXK) {
+        NegArgs na; fill_pair(na, KGE_DISTMULT, k.C, 2 * k.chunk, k.N, k.d_e / 2, k.gamma, k.AP, k.Nh, nullptr);
+        na.W = t.PQc; na.GA = t.GAP; na.GN = t.GNp;
+        KGE_TRY(launch_neg_bwd_pair(na, s));
+    } else KGE_TRY(launch_neg_bwd_gemm(g, s));
+    return KGE_OK;
+}
+
 // SimplE, modular backward: no gradient through a saturated clamp
 __global__ void clamp_mask_kernel(const float *dneg, const float *score, float c, float *W, int64_t n) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -295,6 +364,11 @@ int kge_score_pos(int model, const float *h, const float *r, const float *t, int
         KGE_TRY(launch_transh_edge_fwd(e, (hipStream_t)stream));
         return KGE_OK;
     }
+    if (model == KGE_TRANSD) {
+        TransdEdgeArgs e; fill_transd_edge(e, EdgeSrc{h, nullptr, t, nullptr, r, nullptr}, (int)B, (int)B, d_e, 0, gamma, out, nullptr, nullptr, nullptr, nullptr);
+        KGE_TRY(launch_transd_edge_fwd(e, (hipStream_t)stream));
+        return KGE_OK;
+    }
     EdgeFwdArgs a;
     fill_edge(a, EdgeSrc{h, nullptr, t, nullptr, r, nullptr}, model, (int)B, d_e, d_r, 0, gamma, rot_div_of(emb_init));
     a.pos_score = out;
@@ -333,6 +407,12 @@ int kge_score_pos_bwd(int model, const float *h, const float *r, const float *t,
         KGE_TRY(launch_transh_edge_bwd(e, (hipStream_t)stream));
         return KGE_OK;
     }
+    if (model == KGE_TRANSD) {
+        TransdBwdArgs e{};
+        e.src = EdgeSrc{h, nullptr, t, nullptr, r, nullptr}; e.B = (int)B; e.chunk = (int)B; e.d_e = d_e; e.dpos = dpos; e.GH = gh; e.GT = gt; e.GR = gr;
+        KGE_TRY(launch_transd_edge_bwd(e, (hipStream_t)stream));
+        return KGE_OK;
+    }
     EdgeBwdArgs a;
     fill_edge_bwd(a, EdgeSrc{h, nullptr, t, nullptr, r, nullptr}, model, (int)B, d_e, d_r, 0, gamma, rot_div_of(emb_init), dpos, nullptr);
     a.clamp_pos = 1; a.GH = gh; a.GT = gt; a.GR = gr;
@@ -349,7 +429,16 @@ static void carve_transh(Carver &cv, TranshBufs &t, size_t B, size_t CN, size_t 
     t.rs = cv.f(B); t.kap = cv.f(B); t.cs = cv.f(CN);       // row and column terms of the backward
     t.GAW = cv.f(2 * B * d_e);                              // Ga | Gw^ products
 }
-struct NegBufs { float *A, *asq, *bsq, *W, *GA, *GNp, *PW, *PGW, *Pnrm; TranshBufs th; };
+static void carve_transd(Carver &cv, TransdBufs &t, size_t B, size_t CN, size_t N, size_t d_e) {
+    const size_t k = d_e / 2;
+    t.AP = cv.f(2 * B * k); t.sig = cv.f(B); t.u = cv.f(B);         // (a, rho) stacked; |rho|^2, a . rho (|a|^2, |n|^2: the asq / bsq entries)
+    t.cj = cv.f(CN); t.Nh = cv.f(CN * k);                           // m . n and the dense first half of every candidate row
+    t.PQ = cv.f(2 * B * N); t.PQc = cv.f(2 * B * N);                // raw p | q; P' | Q'
+    t.rs = cv.f(B); t.rc = cv.f(B); t.rc2 = cv.f(B);                // row sums of the backward
+    t.cs = cv.f(CN); t.gc = cv.f(CN);                               // its column sums
+    t.GAP = cv.f(2 * B * k); t.GNp = cv.f(CN * k);                  // Ga | Grho and Gn products
+}
+struct NegBufs { float *A, *asq, *bsq, *W, *GA, *GNp, *PW, *PGW, *Pnrm; TranshBufs th; TransdBufs td; };
 static size_t carve_neg(Carver &cv, NegBufs &w, int model, int C, int chunk, int N, int d_e) {
     const size_t B = (size_t)C * chunk;
     w.A = cv.f(B * d_e);                              // pos-side vectors
@@ -361,6 +450,8 @@ static size_t carve_neg(Carver &cv, NegBufs &w, int model, int C, int chunk, int
     if (model == KGE_PAIRRE) { w.PW = cv.f(B * d_e); w.PGW = cv.f(B * d_e); w.Pnrm = cv.f((size_t)C * N); }   // w, Gw, candidate norms
     w.th = TranshBufs{};
     if (model == KGE_TRANSH) carve_transh(cv, w.th, B, (size_t)C * N, (size_t)N, (size_t)d_e);
+    w.td = TransdBufs{};
+    if (model == KGE_TRANSD) carve_transd(cv, w.td, B, (size_t)C * N, (size_t)N, (size_t)d_e);
     return cv.off;
 }
 
@@ -391,6 +482,13 @@ static int neg_prepare(int model, int neg_head, const float *pos_side, const flo
         KGE_TRY(launch_transh_edge_fwd(e, s));
         return KGE_OK;
     }
+    if (model == KGE_TRANSD) {         // the stacked (a, rho) with its row statistics and the candidates' scalars and first halves, one launch
+        TransdEdgeArgs e; fill_transd_edge(e, EdgeSrc{pos_side, nullptr, pos_side, nullptr, rel, nullptr}, B, chunk, d_e, neg_head, gamma, nullptr,
+                                           w.td.AP, w.asq, w.td.sig, w.td.u);
+        e.nbase = neg; e.n_neg = C * N; e.beta = w.bsq; e.cj = w.td.cj; e.Nh = w.td.Nh;
+        KGE_TRY(launch_transd_edge_fwd(e, s));
+        return KGE_OK;
+    }
     EdgeFwdArgs a;
     fill_edge(a, EdgeSrc{pos_side, nullptr, pos_side, nullptr, rel, nullptr}, model, B, d_e, d_r, neg_head, gamma, rot_div_of(emb_init));
     a.A = w.A;
@@ -417,6 +515,9 @@ int kge_score_neg_fwd(int model, int neg_head, const float *pos_side, const floa
         KGE_TRY(launch_pairre_neg_fwd(n, s));
     } else if (model == KGE_TRANSH) {
         if (int rc = transh_scores(TranshBlock{C, chunk, N, d_e, gamma, w.th.AW, w.asq, w.th.cw, neg, nullptr, w.bsq, w.th.PQ}, out, s)) return rc;
+    } else if (model == KGE_TRANSD) {
+        if (int rc = transd_scores(TransdBlock{C, chunk, N, d_e, gamma, w.td.AP, w.asq, w.td.sig, w.td.u, w.td.Nh, w.bsq, w.td.cj, w.td.PQ}, out, s))
+            return rc;
     } else if (mf) {
         GemmArgs g; fill_gemm(g, model, C, chunk, N, d_e, gamma, w.A, neg, nullptr);
         g.S = out; g.asq = w.asq; g.bsq = w.bsq;
@@ -466,6 +567,18 @@ int kge_score_neg_bwd(int model, int neg_head, const float *pos_side, const floa
         if (neg_head) e.GT = g_pos_side; else e.GH = g_pos_side;
         e.nbase = neg; e.n_neg = C * N; e.cs = w.th.cs; e.GN = g_neg;
         KGE_TRY(launch_transh_edge_bwd(e, s));
+        return KGE_OK;
+    }
+    if (model == KGE_TRANSD) {
+        const TransdBlock k{C, chunk, N, d_e, gamma, w.td.AP, w.asq, w.td.sig, w.td.u, w.td.Nh, w.bsq, w.td.cj, w.td.PQ};
+        if (int rc = transd_products(k, s)) return rc;
+        if (int rc = transd_neg_bwd(k, dneg, w.td, s)) return rc;
+        TransdBwdArgs e{};
+        e.src = EdgeSrc{pos_side, nullptr, pos_side, nullptr, rel, nullptr}; e.B = B; e.chunk = chunk; e.d_e = d_e; e.neg_head = neg_head;
+        e.GAP = w.td.GAP; e.rs = w.td.rs; e.rc = w.td.rc; e.rc2 = w.td.rc2; e.GR = g_rel;
+        if (neg_head) e.GT = g_pos_side; else e.GH = g_pos_side;
+        e.nbase = neg; e.n_neg = C * N; e.cs = w.td.cs; e.gc = w.td.gc; e.GNp = w.td.GNp; e.GN = g_neg;
+        KGE_TRY(launch_transd_edge_bwd(e, s));
         return KGE_OK;
     }
     const float *Wuse = dneg;
@@ -640,6 +753,7 @@ struct StepBufs {
     float *row_pos, *row_neg, *reg_ent, *reg_rel, *GNp, *Hc, *Tc, *Rc;
     float *PW, *PGW, *Pnrm;                                                         // PairRE: w, Gw [B, d_e], candidate norms [C * N]
     TranshBufs th;                                                                  // TransH
+    TransdBufs td;                                                                  // TransD
 };
 
 // Ns: the SAMPLED negatives per chunk (kge_batch.N).  copies: room for PREP's dense h / t / r rows (the async pipeline)
@@ -682,6 +796,7 @@ static size_t carve_step(Carver &cv, StepBufs &w, const kge_hparams *hp, int B_,
     if (copies) { w.Hc = cv.f(B * d_e); w.Tc = cv.f(B * d_e); w.Rc = cv.f(B * d_r); }
     if (hp->model == KGE_PAIRRE) { w.PW = cv.f(B * d_e); w.PGW = cv.f(B * d_e); w.Pnrm = cv.f(CN); }
     if (hp->model == KGE_TRANSH) carve_transh(cv, w.th, B, CN, (size_t)N, d_e);
+    if (hp->model == KGE_TRANSD) carve_transd(cv, w.td, B, CN, (size_t)N, d_e);
     return cv.off;
 }
 
@@ -832,6 +947,9 @@ struct Step {
     int bwd_transr(), bwd_rescal(), phase_update(); void fill_score(), fill_step_loss(LossArgs &la);
     TranshBlock transh_block() const {
         return TranshBlock{b->C, b->chunk, p.N, hp->d_e, hp->gamma, w.th.AW, w.asq, w.th.cw, w.Bn, nullptr, w.bsq, w.th.PQ};
+    }
+    TransdBlock transd_block() const {
+        return TransdBlock{b->C, b->chunk, p.N, hp->d_e, hp->gamma, w.td.AP, w.asq, w.td.sig, w.td.u, w.td.Nh, w.bsq, w.td.cj, w.td.PQ};
     }
 };
 
@@ -1019,6 +1137,13 @@ int Step::phase_prep() {
         KGE_TRY(launch_transh_edge_fwd(e, s));
         return KGE_OK;
     }
+    if (hp->model == KGE_TRANSD) {     // own edge forward: P, the stacked (a, rho), the dense negative rows, their first halves and scalars
+        TransdEdgeArgs e; fill_transd_edge(e, src, b->B, b->chunk, hp->d_e, b->neg_head, hp->gamma, P, w.td.AP, w.asq, w.td.sig, w.td.u);
+        e.nbase = ef.nbase; e.nidx = ef.nidx; e.n_neg = ef.n_neg; e.nd_own = ef.nd_own; e.nd_chunk = ef.nd_chunk; e.nd_Ns = ef.nd_Ns;
+        e.Bn = w.Bn; e.Nh = w.td.Nh; e.beta = w.bsq; e.cj = w.td.cj;
+        KGE_TRY(launch_transd_edge_fwd(e, s));
+        return KGE_OK;
+    }
     if (c.build_prep) { *c.build_prep = ef; return KGE_OK; }
     if (!p.merged_fwd && !p.merged_pair) KGE_TRY(launch_edge_fwd(ef, s));     // merged: launched together with the forward tiles
     return KGE_OK;
@@ -1086,6 +1211,8 @@ int Step::phase_fwd() {
             KGE_TRY(launch_pairre_neg_fwd(n, s));
         } else if (hp->model == KGE_TRANSH) {
             if (int rc = transh_scores(transh_block(), w.S, s)) return rc;
+        } else if (hp->model == KGE_TRANSD) {
+            if (int rc = transd_scores(transd_block(), w.S, s)) return rc;
         } else KGE_TRY(launch_neg_fwd_pair(na, s));
     }
     if (p.fused_loss || p.fold_loss) return KGE_OK;  // no stand-alone loss kernel: the backward GEMM / the forward tiles run it
@@ -1093,7 +1220,7 @@ int Step::phase_fwd() {
     LossArgs la; fill_step_loss(la);
     la.row_pos = p.want4 ? w.row_pos : nullptr;
     if (p.merged_fwd && p.is_l2) { la.l2_raw = 1; la.l2_chunk = b->chunk; la.asq = w.asq; la.bsq = w.bsq; }
-    la.skip_pos = (p.pos_row || p.rescal || p.transr || hp->model == KGE_PAIRRE || hp->model == KGE_TRANSH) ? 0 : 1; la.diag_chunk = p.nd ? b->chunk : 0;  // RESCAL / TransR: no edge_fwd -> positive part here
+    la.skip_pos = (p.pos_row || p.rescal || p.transr || hp->model == KGE_PAIRRE || hp->model == KGE_TRANSH || hp->model == KGE_TRANSD) ? 0 : 1; la.diag_chunk = p.nd ? b->chunk : 0;  // RESCAL / TransR: no edge_fwd -> positive part here
     KGE_TRY(launch_loss(la, s, c.known ? c.known_mask : nullptr));
     return KGE_OK;
 }
@@ -1216,6 +1343,19 @@ int Step::phase_bwd() {
         e.n_reg_coef = (p.reg && !p.nd) ? hp->reg_coef : 0.f;           // nd: the update adds it (sampled rows only)
         if (p.nd) { e.GNd = GN; e.nd_chunk = b->chunk; e.nd_Np = p.N; }     // in-batch negative rows -> positive trace
         KGE_TRY(launch_transh_edge_bwd(e, s));
+        return KGE_OK;
+    }
+    if (hp->model == KGE_TRANSD) {
+        if (int rc = transd_neg_bwd(transd_block(), w.S, w.td, s)) return rc;
+        TransdBwdArgs e{};
+        e.src = src; e.B = b->B; e.chunk = b->chunk; e.d_e = hp->d_e; e.neg_head = b->neg_head; e.dpos = w.dP;
+        e.GAP = w.td.GAP; e.rs = w.td.rs; e.rc = w.td.rc; e.rc2 = w.td.rc2;
+        e.reg_coef = p.reg ? hp->reg_coef : 0.f; e.reg_norm = hp->reg_norm;
+        e.GH = w.GH; e.GT = w.GT; e.GR = GR;
+        e.nbase = w.Bn; e.n_neg = p.CN; e.cs = w.td.cs; e.gc = w.td.gc; e.GNp = w.td.GNp; e.GN = GN;
+        e.n_reg_coef = (p.reg && !p.nd) ? hp->reg_coef : 0.f;           // nd: the update adds it (sampled rows only)
+        if (p.nd) { e.GNd = GN; e.nd_chunk = b->chunk; e.nd_Np = p.N; }     // in-batch negative rows -> positive trace
+        KGE_TRY(launch_transd_edge_bwd(e, s));
         return KGE_OK;
     }
     if (p.gemm) {
@@ -1345,6 +1485,7 @@ static int step_sampling(const kge_hparams *hp, const kge_tables *tb, const kge_
     if (!job) return run_step(hp, tb, b, out, ws, ws_bytes, stream, c);
     if (hp && hp->model == KGE_PAIRRE) return no_pairre("kge_step_fused_sampling");
     if (hp && hp->model == KGE_TRANSH) return no_transh("kge_step_fused_sampling");
+    if (hp && hp->model == KGE_TRANSD) return no_transd("kge_step_fused_sampling");
     if (!job->heads || !job->rels || !job->tails || !job->state || !job->slot || !job->scratch || job->n_train <= 0 || job->n_ent <= 0 ||
         job->B <= 0 || job->C <= 0 || job->chunk <= 0 || job->N <= 0 || job->C * job->chunk != job->B || job->k < 0 || job->advance < 0)
         return fail(KGE_ERR_ARG, "kge_step_fused_sampling: bad sampler job");
@@ -1413,6 +1554,7 @@ int kge_step_async(kge_pipe *p, const kge_hparams *hp, const kge_tables *tb, con
     if (hp->model == KGE_QUATE) return no_quate("kge_step_async");
     if (hp->model == KGE_PAIRRE) return no_pairre("kge_step_async");
     if (hp->model == KGE_TRANSH) return no_transh("kge_step_async");
+    if (hp->model == KGE_TRANSD) return no_transd("kge_step_async");
     const size_t half = (ws_bytes / 2) & ~(size_t)255;
     void *wsp = (char *)ws + (size_t)p->parity * half;
     void *wsn = (char *)ws + (size_t)(p->parity ^ 1) * half;
@@ -1548,6 +1690,7 @@ int kge_step_grads(const kge_hparams *hp, const kge_tables *tb, const kge_batch 
     if (hp && hp->model == KGE_QUATE) return no_quate("kge_step_grads");
     if (hp && hp->model == KGE_PAIRRE) return no_pairre("kge_step_grads");
     if (hp && hp->model == KGE_TRANSH) return no_transh("kge_step_grads");
+    if (hp && hp->model == KGE_TRANSD) return no_transd("kge_step_grads");
     if (!emit || !emit->g0 || (!emit->msg_rows && (!emit->gs0 || !emit->g1 || !emit->gs1)))
         return fail(KGE_ERR_ARG, "kge_step_grads: emit buffers g0/gs0/g1/gs1 are required (packed messages: g0 + msg_rows)");
     if ((emit->gr == nullptr) != (emit->gsr == nullptr))
@@ -1591,6 +1734,13 @@ static int rank_pos_side(int model, int neg_head, const float *ent, const float 
         TranshEdgeArgs e; fill_transh_edge(e, EdgeSrc{ent, h, ent, t, rel, r}, rows, th_chunk ? th_chunk : rows, d_e, neg_head, gamma, P, A, asq, w.THP);
         if (!th_chunk) e.W = RV;
         KGE_TRY(launch_transh_edge_fwd(e, s));
+    } else if (model == KGE_TRANSD) {
+        // as TransH: a in the A entry and rho in the RV entry (kge_rank_eval), or the stacked operand in A.  |a|^2 in asq, |rho|^2 and
+        // a . rho in the first `rows` floats of the THP and TTP entries
+        TransdEdgeArgs e; fill_transd_edge(e, EdgeSrc{ent, h, ent, t, rel, r}, rows, th_chunk ? th_chunk : rows, d_e, neg_head, gamma, P, A, asq,
+                                           w.THP, w.TTP);
+        if (!th_chunk) e.W = RV;
+        KGE_TRY(launch_transd_edge_fwd(e, s));
     } else {
         EdgeFwdArgs ef;
         fill_edge(ef, EdgeSrc{ent, h, ent, t, rel, r}, model, rows, d_e, d_r, neg_head, gamma, rot_div);
@@ -1628,8 +1778,10 @@ static int rank_eval_impl(int model, int neg_head, const float *qent, const floa
                           const int64_t *h, const int64_t *r, const int64_t *t, int64_t E, int d_e, int d_r, float gamma, float emb_init,
                           const int64_t *cand, int64_t N, const int64_t *filt_ptr, const int64_t *filt_ids, int Eb, int32_t *ranks,
                           float *pos_score_out, void *ws, size_t ws_bytes, unsigned flags, hipStream_t s) {
+    // TransD keeps TWO scalars per candidate, [beta | c], in the bsq entry: its workspace is the one of 2 N candidates (include/kge_hip.h)
+    const bool td = model == KGE_TRANSD;
     Carver cv(ws, ws_bytes); RankBufs w;
-    const size_t need = carve_rank(cv, w, Eb, N, d_e);
+    const size_t need = carve_rank(cv, w, Eb, td ? 2 * N : N, d_e);
     if (need > ws_bytes) return fail(KGE_ERR_WORKSPACE, "kge_rank_eval: workspace too small (%zu < %zu)", ws_bytes, need);
     float *A = w.A, *asq = w.asq, *bsq = w.bsq, *S = w.S;
     const bool gemm = use_mfma(model, d_e, (int)N, flags);
@@ -1644,11 +1796,17 @@ static int rank_eval_impl(int model, int neg_head, const float *qent, const floa
     if (model == KGE_PAIRRE) KGE_TRY(pairre_norms(cent, cand, N, d_e, bsq, s));       // |x| of every candidate row, once (the bsq entry)
     const bool th = model == KGE_TRANSH;
     if (th) KGE_TRY(transh_norms(cent, cand, N, d_e, bsq, s));                        // |n|^2 of every candidate row, once
+    if (td) KGE_TRY(transd_cands(cent, cand, N, d_e, bsq, bsq + N, nullptr, s));       // |n|^2 and m . n of every candidate row, once
     for (int64_t e0 = 0; e0 < E; e0 += Eb) {
         const int rows = (int)((E - e0) < Eb ? (E - e0) : Eb);
         float *P = pos_score_out ? pos_score_out + e0 : w.P;
         KGE_TRY(rank_pos_side(model, neg_head, qent, rel, proj, h + e0, r + e0, t + e0, rows, d_e, d_r, gamma, rot_div, P, A,
-                              (l2g || th) ? asq : nullptr, w.RV, w, s));
+                              (l2g || th || td) ? asq : nullptr, w.RV, w, s));
+        if (td) {       // the candidate operand is the table row's first half: the table is not copied
+            KGE_TRY(launch_rank_gemm_transd(A, w.RV, rows, cent, cand, N, d_e / 2, gamma, asq, w.THP, w.TTP, bsq, bsq + N, P, S, filt_ptr, filt_ids,
+                                            e0, ranks, s));
+            continue;
+        }
         if (th) {
             KGE_TRY(launch_rank_gemm_transh(A, w.RV, rows, cent, cand, N, d_e, gamma, asq, w.THP, bsq, P, S, filt_ptr, filt_ids, e0, ranks, s));
             continue;
@@ -1719,6 +1877,7 @@ int kge_rank_eval_split(int model, int neg_head, const float *qent, int64_t n_qe
     if (model == KGE_QUATE) return no_quate("kge_rank_eval_split");
     if (model == KGE_PAIRRE) return no_pairre("kge_rank_eval_split");
     if (model == KGE_TRANSH) return no_transh("kge_rank_eval_split");
+    if (model == KGE_TRANSD) return no_transd("kge_rank_eval_split");
     if (model == KGE_TRANSR && !proj)
         return fail(KGE_ERR_ARG, "kge_rank_eval_split: TransR needs the projection table");
     if (n_qent <= 0 || n_cent < 0) return fail(KGE_ERR_ARG, "kge_rank_eval_split: bad argument");
@@ -1740,19 +1899,21 @@ int kge_rank_eval_split(int model, int neg_head, const float *qent, int64_t n_qe
 // ---- chunked-candidate ranking (kge_rank_chunk.hip) ----
 // one block of whole chunks: pos-side vectors / norms / positive scores of its rows, the candidates' norms (TransE_l2), and - for the
 // score-block route only, but the layout does not depend on the flags - the id list and the score block
-struct ChunkBufs : TransRRows { float *A, *asq, *P, *RV, *bsq_own, *bsq_c, *S, *Pnrm, *TPQ; int64_t *ids; };
+struct ChunkBufs : TransRRows { float *A, *asq, *P, *RV, *bsq_own, *bsq_c, *S, *Pnrm, *TPQ, *TNh; int64_t *ids; };
 static size_t carve_chunked(Carver &cv, ChunkBufs &w, int model, int64_t rows, int chunk, int64_t n_cand, int self_cand, int d_e, int d_r) {
     const size_t nch = (size_t)((rows + chunk - 1) / chunk), R = nch * (size_t)chunk;
     const size_t ncols = (size_t)n_cand + (self_cand ? (size_t)chunk : 0);
-    const bool th = model == KGE_TRANSH;
+    const bool th = model == KGE_TRANSH, td = model == KGE_TRANSD;       // (TransD: the stacked (a, rho) is 2 R rows of d_e / 2)
     w.A = cv.f((th ? 2 : 1) * R * d_e); w.asq = cv.f(R); w.P = cv.f(R);         // (TransH: the stacked operand (a, w^))
     w.RV = cv.f(model == KGE_RESCAL || model == KGE_PAIRRE ? R * d_e : 0);      // V = M t (RESCAL); w of the pair (PairRE)
-    carve_transr_rows(cv, w, model == KGE_TRANSR ? R * (size_t)d_r : th ? R : 0);      // (TransH: w^ . a in the first entry)
+    carve_transr_rows(cv, w, model == KGE_TRANSR ? R * (size_t)d_r : (th || td) ? R : 0);   // (TransH: w^ . a in the first entry; TransD: |rho|^2, a . rho)
     w.bsq_own = cv.f(R); w.bsq_c = cv.f(nch * (size_t)n_cand);
     w.ids = cv.i64(nch * ncols);
     w.S = cv.f(R * ncols);
     w.Pnrm = (model == KGE_PAIRRE || th) ? cv.f(nch * ncols) : nullptr;       // PairRE: |x| per position of the id lists; TransH: |x|^2
-    w.TPQ = th ? cv.f(2 * R * ncols) : nullptr;                        // TransH: the raw products p | q
+    w.TPQ = (th || td) ? cv.f(2 * R * ncols) : nullptr;                // TransH / TransD: the raw products p | q
+    if (td) w.Pnrm = cv.f(2 * nch * ncols);                            // TransD: [beta | c] per position of the id lists
+    w.TNh = td ? cv.f(nch * ncols * (size_t)(d_e / 2)) : nullptr;      // TransD: the listed rows' first halves, dense (the products' operand)
     return cv.off;
 }
 
@@ -1813,7 +1974,7 @@ int kge_rank_eval_chunked(int model, int neg_head, const float *ent, int64_t n_e
         const int rows = (int)std::min<int64_t>((int64_t)nch * chunk, E - e0);
         float *P = pos_score_out ? pos_score_out + e0 : w.P;
         KGE_TRY(rank_pos_side(model, neg_head, ent, rel, proj, h + e0, r + e0, t + e0, rows, d_e, d_r, gamma, rot_div, P, w.A,
-                              (l2g || model == KGE_TRANSH) ? w.asq : nullptr, w.RV, w, s, chunk));
+                              (l2g || model == KGE_TRANSH || model == KGE_TRANSD) ? w.asq : nullptr, w.RV, w, s, chunk));
         if (gemm) {
             if (l2g && (!shared || self_cand)) {
                 ChunkCands c1 = cc; if (shared) c1.cand = nullptr;
@@ -1857,6 +2018,13 @@ int kge_rank_eval_chunked(int model, int neg_head, const float *ent, int64_t n_e
                 const TranshBlock k{C, m, (int)ncols, d_e, gamma, w.A + 2 * row_off * d_e, w.asq + row_off, w.THP + row_off, ent, ids, beta,
                                     w.TPQ + 2 * row_off * ncols_full};
                 if (int rc = transh_scores(k, S, s)) return rc;
+            } else if (model == KGE_TRANSD) {       // TransH's route; the candidate scalars and first halves per position of the lists
+                const int64_t poff = gidx == 0 ? 0 : (int64_t)nfull * ncols_full, k2 = d_e / 2;
+                float *beta = w.Pnrm + poff, *cj = w.Pnrm + nchb * ncols_full + poff, *Nh = w.TNh + poff * k2;
+                KGE_TRY(transd_cands(ent, ids, (int64_t)C * ncols, d_e, beta, cj, Nh, s));
+                const TransdBlock k{C, m, (int)ncols, d_e, gamma, w.A + row_off * d_e, w.asq + row_off, w.THP + row_off, w.TTP + row_off, Nh, beta, cj,
+                                    w.TPQ + 2 * row_off * ncols_full};
+                if (int rc = transd_scores(k, S, s)) return rc;
             } else {
                 NegArgs na; fill_pair(na, model, C, m, (int)ncols, d_e, gamma, w.A + row_off * d_e, ent, ids);
                 na.S = S;
@@ -1886,7 +2054,7 @@ static size_t carve_rank_rel(Carver &cv, RelBufs &w, int model, int Eb, int64_t 
 size_t kge_rank_rel_workspace_bytes(int model, int Eb, int64_t n_rel, int d_e, int d_r) {
     if (Eb <= 0 || n_rel <= 0 || n_rel > 0x7fffffff || check_model(model, d_e, d_r) != KGE_OK) return 0;
     // ids up to KGE_TRANSR only: a QuatE call takes the DistMult layout followed by the normalised relation table (include/kge_hip.h)
-    if (model == KGE_QUATE || model == KGE_PAIRRE || model == KGE_TRANSH) return 0;
+    if (model == KGE_QUATE || model == KGE_PAIRRE || model == KGE_TRANSH || model == KGE_TRANSD) return 0;
     Carver cv; RelBufs w; return carve_rank_rel(cv, w, model, Eb, n_rel, d_e, d_r);
 }
 
@@ -1897,6 +2065,7 @@ int kge_rank_rel_eval(int model, const float *ent, int64_t n_ent, const float *r
     if (int rc = check_model(model, d_e, d_r)) return rc;
     if (model == KGE_PAIRRE) return no_pairre("kge_rank_rel_eval");
     if (model == KGE_TRANSH) return no_transh("kge_rank_rel_eval");
+    if (model == KGE_TRANSD) return no_transd("kge_rank_rel_eval");
     if (model == KGE_TRANSR && !proj) return fail(KGE_ERR_ARG, "kge_rank_rel_eval: TransR needs the projection table");
     if (!ent || !rel || n_ent <= 0 || n_rel <= 0 || E < 0 || (E && (!h || !r || !t || !ranks)) || !ws)
         return fail(KGE_ERR_ARG, "kge_rank_rel_eval: bad argument (a null pointer or a count that is not positive)");
@@ -1975,6 +2144,7 @@ int kge_step_sharded(const kge_hparams *hp, const kge_shards *sh, const kge_batc
     if (hp && hp->model == KGE_QUATE) return no_quate("kge_step_sharded");
     if (hp && hp->model == KGE_PAIRRE) return no_pairre("kge_step_sharded");
     if (hp && hp->model == KGE_TRANSH) return no_transh("kge_step_sharded");
+    if (hp && hp->model == KGE_TRANSD) return no_transd("kge_step_sharded");
     // (RESCAL's relation "row" is a d_e x d_e matrix streamed by its own kernels: only the entity width is bounded)
     if (hp && (hp->d_e % 4 || hp->d_e > 1024 || (hp->model != KGE_RESCAL && (hp->d_r % 4 || hp->d_r > 1024))))
         return fail(KGE_ERR_ARG, "kge_step_sharded: row widths must be multiples of 4 and <= 1024 floats");

@@ -613,6 +613,11 @@ size_t rank_gemm_mask_bytes(int rows, int64_t N);
 int launch_rank_gemm_transh(const float *A, const float *W, int rows, const float *nbase, const int64_t *nidx, int64_t N, int D, float gamma,
                             const float *alpha, const float *cw, const float *beta, const float *P, void *mask, const int64_t *filt_ptr,
                             const int64_t *filt_ids, int64_t e0, int32_t *ranks, hipStream_t s);
+// TransD: A, R [rows, D] the pairs (a, rho), D = k; candidate j is the first D columns of nbase + (nidx ? nidx[j] : j) * 2 D;
+// alpha, sig, u [rows] and beta, cj [N]: the epilogue's scalars (transd_score)
+int launch_rank_gemm_transd(const float *A, const float *R, int rows, const float *nbase, const int64_t *nidx, int64_t N, int D, float gamma,
+                            const float *alpha, const float *sig, const float *u, const float *beta, const float *cj, const float *P,
+                            void *mask, const int64_t *filt_ptr, const int64_t *filt_ids, int64_t e0, int32_t *ranks, hipStream_t s);
 int launch_rank_gemm(int model, const float *A, int rows, const float *nbase, const int64_t *nidx, int64_t N, int D, float gamma,
                      float clampv, const float *asq, const float *bsq, const float *P, void *mask, const int64_t *filt_ptr,
                      const int64_t *filt_ids, int64_t e0, int32_t *ranks, hipStream_t s);
@@ -780,6 +785,51 @@ int launch_transh_edge_fwd(const TranshEdgeArgs &a, hipStream_t s);
 int launch_transh_score(const TranshNegArgs &a, hipStream_t s);
 int launch_transh_coef(const TranshNegArgs &a, hipStream_t s);
 int launch_transh_edge_bwd(const TranshBwdArgs &a, hipStream_t s);
+// ---- TransD (kge_transd.hip): local tables only ----
+// Entity rows [e | e_p] and relation rows [r | r_p] are d_e == d_r == 2 k floats wide.  The per-edge pair (a, rho) - k floats each -
+// is stacked exactly as TransH's (a, w^): chunk c of m rows owns 2 m consecutive rows of the operand, its a vectors first.  Only the
+// FIRST k columns of a candidate row enter a product; c_j = m_j . n_j of the candidate's two halves rides along as a scalar.
+struct TransdEdgeArgs {              // edge forward + candidate-row jobs of the same launch
+    EdgeSrc src;
+    int B, d_e, neg_head, chunk;     // d_e: the ROW width 2 k
+    float gamma;
+    float *pos_score;                // [B] or null
+    float *AP;                       // [2 B, k] stacked (a, rho), or null
+    float *W;                        // not null: two blocks instead of the stacked layout - a in AP [B, k], rho here [B, k]
+    float *alpha, *sig, *u;          // [B] |a|^2, |rho|^2, a . rho (with AP)
+    const float *nbase; const int64_t *nidx; int n_neg;   // candidate rows -> beta, cj (and Bn, Nh)
+    const int64_t *nd_own; int nd_chunk, nd_Ns;           // neg_deg_sample id scheme (EdgeFwdArgs)
+    float *Bn;                       // [n_neg, 2 k] dense copy of the candidate rows or null
+    float *Nh;                       // [n_neg, k] dense copy of their first halves (the products' operand) or null
+    float *beta, *cj;                // [n_neg] |n|^2 and m . n of every candidate row, or null
+};
+struct TransdNegArgs {               // the row-wise kernels around the two products of the chunked score
+    int C, chunk, N;
+    float gamma;
+    const float *alpha, *sig, *u;    // [C*chunk]
+    const float *beta, *cj;          // [C*N]
+    const float *PQ;                 // [C, 2 chunk, N] raw products p | q
+    float *S;                        // score kernel: out [C,chunk,N]
+    const float *G;                  // coefficient kernel: dL/ds [C,chunk,N]
+    float *PQc;                      // coefficient kernel: out [C, 2 chunk, N] stacked P' | Q'
+    float *rs, *rc, *rc2;            // coefficient kernel: out [C*chunk] sum_j E_ij, sum_j E_ij c_j, sum_j E_ij c_j^2
+    float *cs, *gc;                  // coefficient kernel: out [C*N] sum_i E_ij, Gc_j
+};
+struct TransdBwdArgs {               // per-edge gradients of the head, tail and relation rows + the candidates' gradient rows
+    EdgeSrc src;
+    int B, d_e, neg_head, chunk;
+    const float *dpos;               // [B] or null
+    const float *GAP, *rs, *rc, *rc2;    // [2 B, k] stacked products Ga | Grho of the backward GEMM, their row sums [B]; or null
+    float reg_coef; int reg_norm;    // regulariser gradient of the relation row
+    float *GH, *GT, *GR;             // [B, 2 k] each; any may be null
+    const float *GNd; int nd_chunk, nd_Np;     // neg_deg_sample (EdgeBwdArgs)
+    // candidate rows: GN[j] = [GNp[j] + 2 n_j cs[j] + gc[j] m_j | gc[j] n_j] (+ regulariser of the row)
+    const float *nbase; const int64_t *nidx; int n_neg; const float *cs, *gc, *GNp; float *GN; float n_reg_coef;
+};
+int launch_transd_edge_fwd(const TransdEdgeArgs &a, hipStream_t s);
+int launch_transd_score(const TransdNegArgs &a, hipStream_t s);
+int launch_transd_coef(const TransdNegArgs &a, hipStream_t s);
+int launch_transd_edge_bwd(const TransdBwdArgs &a, hipStream_t s);
 // ---- RESCAL (kge_rescal.hip) ----
 struct RescalMatvecArgs {            // one pass over M_i = rel + (ridx ? ridx[i] : i) * D*Dc per edge i
     int B, D;                        // D rows; Dc columns (0: square).  y vectors have Dc entries, z / pd vectors D

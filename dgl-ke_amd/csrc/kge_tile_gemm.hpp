@@ -30,6 +30,16 @@ __device__ __forceinline__ float transh_score(float p, float q, float gamma, flo
 // query 32 wr + 16 i + 4 q + r of the tile.  Tile row R -> (query of the tile, 0 = a / 1 = w^)
 __device__ __forceinline__ int transh_tile_query(int R) { return 32 * (R >> 6) + (R & 31); }
 __device__ __forceinline__ int transh_tile_is_w(int R) { return (R >> 5) & 1; }
+// TransD (include/kge_hip.h): |a - n - c rho|^2 from the two products p = a . n and q = rho . n, the row scalars as = |a|^2,
+// sg = |rho|^2, u = a . rho and the candidate scalars bs = |n|^2, c = m . n:  as + bs + c^2 sg - 2 p + 2 c (q - u).  One routine
+// for the step's score kernel, its coefficient kernel, ranking and top-K, as for TransH.  The pair (a, rho) of 64 queries sits in
+// a tile exactly as TransH's (transh_tile_query / transh_tile_is_w)
+__device__ __forceinline__ float transd_dist2(float p, float q, float as, float sg, float u, float bs, float c) {
+    return fmaxf(fmaf(c, fmaf(c, sg, 2.f * (q - u)), fmaf(-2.f, p, as + bs)), 1e-30f);
+}
+__device__ __forceinline__ float transd_score(float p, float q, float gamma, float as, float sg, float u, float bs, float c) {
+    return gamma - sqrtf(transd_dist2(p, q, as, sg, u, bs, c));
+}
 // the score of a (pos-side row, candidate) pair from its raw product: TransE_l2 (l2; as / bs = |a|^2 / |b|^2), SimplE (clampv > 0:
 // clamp), the other matrix forms (the product itself)
 __device__ __forceinline__ float tile_score(float x, int l2, float gamma, float as, float bs, float clampv) {

@@ -29,13 +29,17 @@ using namespace kge;
 #define TK_MCAP 2048                              // entries of one merge workgroup
 
 // accumulator kinds (template) and epilogues (runtime)
-enum { ACC_MFMA = 0, ACC_DOT = 1, ACC_SQ = 2, ACC_L1 = 3, ACC_ROT = 4, ACC_PRE = 5, ACC_TH = 6, ACC_THV = 7 };
+enum { ACC_MFMA = 0, ACC_DOT = 1, ACC_SQ = 2, ACC_L1 = 3, ACC_ROT = 4, ACC_PRE = 5, ACC_TH = 6, ACC_THV = 7, ACC_TD = 8, ACC_TDV = 9 };
 // ACC_PRE (PairRE, include/kge_hip.h): query row i is the pair (a_i, w_i) - abase holds the rows' a block followed by their w block,
 // [rows, D] each - and bn the candidates' norms |x_j|_2: the tile accumulates |a_ik - w_ik x_jk / |x_j||
 // ACC_TH / ACC_THV (TransH, include/kge_hip.h): query row i is the pair (a_i, w^_i) - abase holds the rows' a block, their w^ block
 // ([rows, D] each) and then c_i = w^_i . a_i [rows]; an = |a|^2, bn = |n|^2.  The tile accumulates p = a . n and q = w^ . n and
 // scores with transh_score.  ACC_TH: the shared MFMA tile twice per candidate tile, 64 queries each with the two operands
 // interleaved by strips (transh_tile_query, kge_tile_gemm.hpp); ACC_THV: the VALU tile with a second accumulator (D < 32)
+// ACC_TD / ACC_TDV (TransD, include/kge_hip.h): the same two tiles as ACC_TH / ACC_THV on the pair (a_i, rho_i), D = k floats each -
+// abase holds the rows' a block, their rho block ([rows, D] each), then sigma_i = |rho_i|^2 [rows] and u_i = a_i . rho_i [rows];
+// an = |a|^2; bn = [beta | c], N floats each.  Candidate j is the FIRST D columns of its table row, which is 2 D wide
+// (the kernel's TD); the score is transd_score
 enum { EPI_RAW = 0, EPI_L2G = 1, EPI_COS = 2, EPI_JAC = 3, EPI_GMINUS = 4, EPI_GSQRT = 5 };
 
 struct TopkSelArgs {
@@ -95,6 +99,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
     const int64_t nbn = (a.N + TILE_BN - 1) / TILE_BN, tps = (nbn + a.S - 1) / a.S;
     const int64_t tile0 = (int64_t)seg * tps, tile1 = min(nbn, tile0 + tps);
     const int r0 = rb * TILE_BM, D = a.D, K = a.K;
+    constexpr bool TD = ACC == ACC_TD || ACC == ACC_TDV;                        // TransD: candidate rows 2 D wide, their first half enters
     float *sc = &lds[0][0];                                                    // [128][128] score tile (after the main loop)
     unsigned long long *un = reinterpret_cast<unsigned long long *>(&lds[0][0] + TILE_BM * TILE_BN) + wave * 256;
     for (int e = tid; e < TILE_BM * K; e += 256) {
@@ -132,8 +137,8 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
                         sc[row * TILE_BN + col] = epilogue(a, acc[i][j][r], grow, gcol);
                     }
                 }
-        } else if constexpr (ACC == ACC_TH) {
-            const float *wb = a.abase + (int64_t)a.rows * D, *cb = wb + (int64_t)a.rows * D;
+        } else if constexpr (ACC == ACC_TH || ACC == ACC_TD) {
+            const float *wb = a.abase + (int64_t)a.rows * D, *cb = wb + (int64_t)a.rows * D;     // (TransD: cb = sigma, u behind it)
             const int wr = wave >> 1, wc = wave & 1;
             const int m = lane & 15, q = lane >> 4;
             float sv[2][2][4][4];                                               // [half][strip][j][r]: lds is the tile's until both halves are done
@@ -146,17 +151,21 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
                         const int64_t row = min(r0 + 64 * half + transh_tile_query(R), a.rows - 1);
                         return (transh_tile_is_w(R) ? wb : a.abase) + row * D;
                     },
-                    [=](int j) { return row_ptr(a.nbase, a.nidx, min(bn * TILE_BN + j, a.N - 1), D); }, acc);
+                    [=](int j) { return row_ptr(a.nbase, a.nidx, min(bn * TILE_BN + j, a.N - 1), TD ? 2 * D : D); }, acc);
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int64_t grow = min(r0 + 64 * half + 32 * wr + 16 * i + 4 * q + r, a.rows - 1);
                         const float as = a.an[grow], cw = cb[grow];
+                        [[maybe_unused]] float uu = 0.f;
+                        if constexpr (TD) uu = cb[a.rows + grow];
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             const int64_t gcol = min(bn * TILE_BN + wc * 64 + 16 * j + m, a.N - 1);
-                            sv[half][i][j][r] = transh_score(acc[i][j][r], acc[i + 2][j][r], a.gamma, as, a.bn[gcol], cw);
+                            if constexpr (TD)
+                                sv[half][i][j][r] = transd_score(acc[i][j][r], acc[i + 2][j][r], a.gamma, as, cw, uu, a.bn[gcol], a.bn[a.N + gcol]);
+                            else sv[half][i][j][r] = transh_score(acc[i][j][r], acc[i + 2][j][r], a.gamma, as, a.bn[gcol], cw);
                         }
                     }
             }
@@ -179,8 +188,9 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
             for (int i = 0; i < 8; ++i)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) acc[i][j] = 0.f;
-            [[maybe_unused]] float acc2[ACC == ACC_THV ? 8 : 1][8];                // TransH: q = w^ . n next to p = a . n
-            if constexpr (ACC == ACC_THV) {
+            constexpr bool PV = ACC == ACC_THV || ACC == ACC_TDV;                  // TransH / TransD: q = w^ . n next to p = a . n
+            [[maybe_unused]] float acc2[PV ? 8 : 1][8];
+            if constexpr (PV) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -192,7 +202,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
                 for (int i = 0; i < 32; ++i) {
                     const int f = tid + 256 * i, row = f >> 5, c = f & 31;
                     const float *p = row < TILE_BM ? row_ptr(a.abase, a.aidx, min(r0 + row, a.rows - 1), D)
-                                                 : row_ptr(a.nbase, a.nidx, min(bn * TILE_BN + row - TILE_BM, a.N - 1), D);
+                                                 : row_ptr(a.nbase, a.nidx, min(bn * TILE_BN + row - TILE_BM, a.N - 1), TD ? 2 * D : D);
                     int col; bool ok;
                     if constexpr (ACC == ACC_ROT) { const int k = s * 16 + (c & 15); ok = k < hd; col = (c < 16 ? 0 : hd) + min(k, hd - 1); }
                     else { const int k = s * TILE_BK + c; ok = k < D; col = min(k, D - 1); }
@@ -208,7 +218,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
                         g[i] = nj > 0.f ? g[i] / nj : 0.f;
                     }
                 }
-                if constexpr (ACC == ACC_PRE || ACC == ACC_THV) {
+                if constexpr (ACC == ACC_PRE || PV) {
                     // the rows' w slab for the second buffer
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
@@ -223,7 +233,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
                     const int f = tid + 256 * i;
                     lds[0][(f >> 5) * TILE_LD + (f & 31)] = g[i];
                 }
-                if constexpr (ACC == ACC_PRE || ACC == ACC_THV) {
+                if constexpr (ACC == ACC_PRE || PV) {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
                         const int f = tid + 256 * i;
@@ -250,7 +260,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
                     for (int k = 0; k < TILE_BK; ++k) {
                         float av[8], bv[8];
                         [[maybe_unused]] float wv[8];
-                        if constexpr (ACC == ACC_PRE || ACC == ACC_THV) {
+                        if constexpr (ACC == ACC_PRE || PV) {
 #pragma unroll
                             for (int i = 0; i < 8; ++i) wv[i] = lds[1][(ty + 16 * i) * TILE_LD + k];
                         }
@@ -262,7 +272,7 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
                         for (int i = 0; i < 8; ++i)
 #pragma unroll
                             for (int j = 0; j < 8; ++j) {
-                                if constexpr (ACC == ACC_THV) { acc[i][j] = fmaf(av[i], bv[j], acc[i][j]); acc2[i][j] = fmaf(wv[i], bv[j], acc2[i][j]); }
+                                if constexpr (PV) { acc[i][j] = fmaf(av[i], bv[j], acc[i][j]); acc2[i][j] = fmaf(wv[i], bv[j], acc2[i][j]); }
                                 else if constexpr (ACC == ACC_DOT) acc[i][j] = fmaf(av[i], bv[j], acc[i][j]);
                                 else if constexpr (ACC == ACC_SQ) { const float d = av[i] - bv[j]; acc[i][j] = fmaf(d, d, acc[i][j]); }
                                 else if constexpr (ACC == ACC_PRE) acc[i][j] += fabsf(fmaf(-wv[i], bv[j], av[i]));
@@ -279,7 +289,12 @@ __global__ __launch_bounds__(256) void topk_select_kernel(Args a) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const int col = tx + 16 * j;
-                    if constexpr (ACC == ACC_THV)
+                    if constexpr (ACC == ACC_TDV) {
+                        const int64_t gcol = min(bn * TILE_BN + col, a.N - 1);
+                        const float *sgb = a.abase + 2 * (int64_t)a.rows * D;
+                        sc[row * TILE_BN + col] = transd_score(acc[i][j], acc2[i][j], a.gamma, a.an[grow], sgb[grow], sgb[a.rows + grow], a.bn[gcol],
+                                                               a.bn[a.N + gcol]);
+                    } else if constexpr (ACC == ACC_THV)
                         sc[row * TILE_BN + col] = transh_score(acc[i][j], acc2[i][j], a.gamma, a.an[grow], a.bn[min(bn * TILE_BN + col, a.N - 1)],
                                                                a.abase[2 * (int64_t)a.rows * D + grow]);
                     else sc[row * TILE_BN + col] = epilogue(a, acc[i][j], grow, min(bn * TILE_BN + col, a.N - 1));
@@ -575,10 +590,12 @@ static int tk_check_model(int model, int d_e, int d_r) {
     else if (model == KGE_QUATE) ok = d_e % 4 == 0 && d_r == d_e;
     else if (model == KGE_PAIRRE) ok = (int64_t)d_r == 2 * (int64_t)d_e;
     else if (model == KGE_TRANSH) ok = d_e >= 4 && d_e % 4 == 0 && (int64_t)d_r == 2 * (int64_t)d_e;
+    else if (model == KGE_TRANSD) ok = d_e >= 8 && d_e % 8 == 0 && d_r == d_e;
     else ok = d_r == d_e;
     if (ok) return KGE_OK;
     char msg[160];
-    if (model == KGE_TRANSH) snprintf(msg, sizeof(msg), "kge_topk_select: TransH needs d_e >= 4, d_e %% 4 == 0 and d_r == 2 * d_e (got %d, %d)", d_e, d_r);
+    if (model == KGE_TRANSD) snprintf(msg, sizeof(msg), "kge_topk_select: TransD needs d_e == d_r and d_e %% 8 == 0, rows [x | x_p] (got %d, %d)", d_e, d_r);
+    else if (model == KGE_TRANSH) snprintf(msg, sizeof(msg), "kge_topk_select: TransH needs d_e >= 4, d_e %% 4 == 0 and d_r == 2 * d_e (got %d, %d)", d_e, d_r);
     else snprintf(msg, sizeof(msg), "kge_topk_select: dims d_e=%d d_r=%d do not fit model %d", d_e, d_r, model);
     return tk_fail(msg);
 }
@@ -598,7 +615,7 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
     char msg[256];
     if (filt_ptr && !filt_ids) return tk_fail("kge_topk_select_filtered: filt_ptr given without filt_ids");
     const bool sim = func >= KGE_SIM_COSINE && func <= KGE_SIM_EXT_JACCARD;
-    if (!sim && (func < KGE_TRANSE_L1 || (func > KGE_RESCAL && func != KGE_QUATE && func != KGE_PAIRRE && func != KGE_TRANSH))) {
+    if (!sim && (func < KGE_TRANSE_L1 || (func > KGE_RESCAL && func != KGE_QUATE && func != KGE_PAIRRE && func != KGE_TRANSH && func != KGE_TRANSD))) {
         snprintf(msg, sizeof(msg), "kge_topk_select: unknown score function %d (TransR has no inference path)", func);
         return tk_fail(msg);
     }
@@ -615,7 +632,10 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
     const int D = d_e;
     // PairRE keeps two vectors per query row: the A entry is [a block | w block] (include/kge_hip.h)
     // TransH: [a block | w^ block | c] (2 D + 1 floats per row)
-    TkWs w = carve(ws, rows, N, func == KGE_PAIRRE ? 2 * D : func == KGE_TRANSH ? 2 * D + 1 : D, K);
+    // TransD: [a block | rho block | sigma | u] (2 k + 2 = d_e + 2 floats per row) and TWO scalars per candidate, [beta | c]: the bn
+    // entry of a workspace sized for 2 N candidates (nothing else of the layout depends on the candidate count)
+    const bool td = func == KGE_TRANSD;
+    TkWs w = carve(ws, rows, td ? 2 * N : N, func == KGE_PAIRRE ? 2 * D : func == KGE_TRANSH ? 2 * D + 1 : td ? D + 2 : D, K);
     if (w.need > ws_bytes) {
         snprintf(msg, sizeof(msg), "kge_topk_select: workspace too small (%zu < %zu)", ws_bytes, w.need);
         return kge_fail(KGE_ERR_WORKSPACE, msg);
@@ -654,6 +674,14 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
             e.AW = w.A; e.alpha = w.an; e.cw = w.A + 2 * (size_t)rows * D;
             e.nbase = ent; e.nidx = cand; e.n_neg = (int)N; e.beta = w.bn;
             if (int rc = launch_transh_edge_fwd(e, st)) return rc;
+        } else if (td) {
+            const size_t k = (size_t)D / 2;
+            TransdEdgeArgs e{};
+            e.src = EdgeSrc{ent, h, ent, t, rel, r};
+            e.B = rows; e.chunk = rows; e.d_e = d_e; e.neg_head = side; e.gamma = gamma;
+            e.AP = w.A; e.alpha = w.an; e.sig = w.A + 2 * (size_t)rows * k; e.u = e.sig + rows;
+            e.nbase = ent; e.nidx = cand; e.n_neg = (int)N; e.beta = w.bn; e.cj = w.bn + N;
+            if (int rc = launch_transd_edge_fwd(e, st)) return rc;
         } else {
             EdgeFwdArgs ef{};
             ef.src = EdgeSrc{ent, h, ent, t, rel, r};
@@ -665,6 +693,7 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
         if (func == KGE_TRANSE_L1) { acc = ACC_L1; epi = EPI_GMINUS; }
         else if (func == KGE_PAIRRE) { acc = ACC_PRE; epi = EPI_GMINUS; }
         else if (func == KGE_TRANSH) { acc = mf ? ACC_TH : ACC_THV; epi = EPI_RAW; }
+        else if (td) { acc = D / 2 >= 32 ? ACC_TD : ACC_TDV; epi = EPI_RAW; }
         else if (func == KGE_ROTATE) { acc = ACC_ROT; epi = EPI_GMINUS; }
         else if (func == KGE_TRANSE_L2) { acc = mf ? ACC_MFMA : ACC_SQ; epi = mf ? EPI_L2G : EPI_GSQRT; }
         else { acc = mf ? ACC_MFMA : ACC_DOT; epi = EPI_RAW; }
@@ -680,7 +709,7 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
     }
     // ---- score + select ----------------------------------------------------------------------------------------------------------
     TopkSelArgs a{};
-    a.abase = abase; a.aidx = aidx; a.rows = rows; a.nbase = ent; a.nidx = cand; a.N = N; a.D = D; a.epi = epi;
+    a.abase = abase; a.aidx = aidx; a.rows = rows; a.nbase = ent; a.nidx = cand; a.N = N; a.D = td ? D / 2 : D; a.epi = epi;
     a.S = topk_segments(rows, N, K); a.K = K; a.gamma = gamma; a.an = w.an; a.bn = w.bn; a.part = w.part;
     const dim3 grid((unsigned)((int64_t)((rows + TILE_BM - 1) / TILE_BM) * a.S));
     if (filt_ptr) {
@@ -695,6 +724,8 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
         case ACC_PRE: hipLaunchKernelGGL((topk_select_kernel<ACC_PRE, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
         case ACC_TH: hipLaunchKernelGGL((topk_select_kernel<ACC_TH, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
         case ACC_THV: hipLaunchKernelGGL((topk_select_kernel<ACC_THV, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
+        case ACC_TD: hipLaunchKernelGGL((topk_select_kernel<ACC_TD, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
+        case ACC_TDV: hipLaunchKernelGGL((topk_select_kernel<ACC_TDV, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
         default: hipLaunchKernelGGL((topk_select_kernel<ACC_ROT, TopkSelArgsF>), grid, dim3(256), 0, st, f); break;
         }
     } else
@@ -706,6 +737,8 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
     case ACC_PRE: hipLaunchKernelGGL(topk_select_kernel<ACC_PRE>, grid, dim3(256), 0, st, a); break;
     case ACC_TH: hipLaunchKernelGGL(topk_select_kernel<ACC_TH>, grid, dim3(256), 0, st, a); break;
     case ACC_THV: hipLaunchKernelGGL(topk_select_kernel<ACC_THV>, grid, dim3(256), 0, st, a); break;
+    case ACC_TD: hipLaunchKernelGGL(topk_select_kernel<ACC_TD>, grid, dim3(256), 0, st, a); break;
+    case ACC_TDV: hipLaunchKernelGGL(topk_select_kernel<ACC_TDV>, grid, dim3(256), 0, st, a); break;
     default: hipLaunchKernelGGL(topk_select_kernel<ACC_ROT>, grid, dim3(256), 0, st, a); break;
     }
     if (int rc = check_launch()) return rc;

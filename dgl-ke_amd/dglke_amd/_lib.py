@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("KGE_LIB") or os.path.join(_HERE, "libkge_hip.so")   #
 
 KGE_ABI_VERSION = 8
 MODEL_IDS = {"TransE_l1": 0, "TransE_l2": 1, "TransE": 1, "DistMult": 2, "ComplEx": 3, "RotatE": 4, "SimplE": 5, "RESCAL": 6, "TransR": 7,
-             "QuatE": 8, "PairRE": 10, "TransH": 12}      # (9 and 11 are not models)
+             "QuatE": 8, "PairRE": 10, "TransH": 12, "TransD": 14}      # (9, 11 and 13 are not models)
 LOSS_IDS = {"Logsigmoid": 0, "Logistic": 1, "Hinge": 2, "BCE": 3, "Softmax": 4}
 FLAG_FORCE_PAIRWISE = 1
 FLAG_NO_TRANSE_FAST = 2
@@ -367,12 +367,22 @@ def rank_rel_workspace_bytes(model, Eb, n_rel, d_e, d_r):
 
 def topk_workspace_bytes(model, rows, n_cand, d_e, K):
     """bytes of a kge_topk_select / _filtered workspace.  kge_topk_workspace_bytes has no model argument; a PairRE call keeps two
-    vectors per query row, the pair (a, w), in the A entry: the size is the one of rows 2 * d_e wide (include/kge_hip.h)"""
-    return lib().kge_topk_workspace_bytes(rows, n_cand, topk_row_width(model, d_e), K)
+    vectors per query row, the pair (a, w), in the A entry: the size is the one of rows 2 * d_e wide (include/kge_hip.h).  A TransD
+    call keeps two scalars per candidate, [beta | c]: the size is the one of 2 * n_cand candidates"""
+    return lib().kge_topk_workspace_bytes(rows, rank_ws_cands(model, n_cand), topk_row_width(model, d_e), K)
+
+
+def rank_ws_cands(model, n_cand):
+    """the candidate count a kge_rank_workspace_bytes / kge_topk_workspace_bytes call is made with: TransD keeps two scalars per
+    candidate (|n|^2 and c = m . n) in the entry of the candidate norms, every other model one or none (include/kge_hip.h)"""
+    return 2 * n_cand if model == MODEL_IDS["TransD"] else n_cand
 
 
 def topk_row_width(model, d_e):
-    """floats per query row in the A entry of a top-K workspace: PairRE the pair (a, w), TransH the pair (a, w^) and c = w^ . a"""
+    """floats per query row in the A entry of a top-K workspace: PairRE the pair (a, w), TransH the pair (a, w^) and c = w^ . a,
+    TransD the pair (a, rho) of half rows and the scalars |rho|^2, a . rho"""
+    if model == MODEL_IDS["TransD"]:
+        return d_e + 2
     if model == MODEL_IDS["PairRE"]:
         return 2 * d_e
     if model == MODEL_IDS["TransH"]:

@@ -50,6 +50,12 @@ class StepEngine(object):
                                     "(-dr without -de; got %d, %d)" % (self.d_e, self.d_r))
             if shards is not None:
                 raise _lib.KgeError("TransH runs the strict step on local tables only (no sharded tables)")
+        if model_name == 'TransD':                          # rows [x | x_p] on both tables (include/kge_hip.h)
+            if self.d_r != self.d_e or self.d_e % 8 or self.d_e < 8:
+                raise _lib.KgeError("TransD needs entity and relation rows of the same width, two halves of a multiple of 4 each "
+                                    "(-de and -dr, --hidden_dim %% 4 == 0; got %d, %d)" % (self.d_e, self.d_r))
+            if shards is not None:
+                raise _lib.KgeError("TransD runs the strict step on local tables only (no sharded tables)")
         hp = _lib.KgeHParams()
         hp.model = model_id(model_name)
         hp.d_e, hp.d_r = self.d_e, self.d_r

@@ -201,6 +201,9 @@ class Ranker(object):
         if need == 0 and self.model == _lib.MODEL_IDS['TransH']:
             raise _lib.KgeError("kge_rank_rel_eval: not available for TransH (the relation row enters through two projections: no "
                                 "relation ranking)")
+        if need == 0 and self.model == _lib.MODEL_IDS['TransD']:
+            raise _lib.KgeError("kge_rank_rel_eval: not available for TransD (the relation row enters through two projections: no "
+                                "relation ranking)")
         if need == 0:
             raise _lib.KgeError("relation_ranks: the tables are %s / %s, which this model does not take"
                                 % (tuple(self.ent.shape), tuple(self.rel.shape)))
@@ -297,7 +300,7 @@ class Ranker(object):
             if fids.shape[0] == 0:
                 fids = torch.zeros(1, dtype=torch.int64, device=dev)
         Eb = max(1, min(self.batch, E))
-        need = _lib.lib().kge_rank_workspace_bytes(Eb, n_cand, self.ent.shape[1])
+        need = _lib.lib().kge_rank_workspace_bytes(Eb, _lib.rank_ws_cands(self.model, n_cand), self.ent.shape[1])
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need + 4096, dtype=torch.uint8, device=dev)
         ranks = torch.zeros(E, dtype=torch.int32, device=dev)

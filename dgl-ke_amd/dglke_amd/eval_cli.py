@@ -21,7 +21,7 @@ class ArgParser(argparse.ArgumentParser):
         super(ArgParser, self).__init__()
         a = self.add_argument
         a('--model_name', default='TransE', choices=['TransE', 'TransE_l1', 'TransE_l2', 'TransR', 'RESCAL', 'DistMult',
-                                                     'ComplEx', 'RotatE', 'SimplE', 'QuatE', 'PairRE', 'TransH'])
+                                                     'ComplEx', 'RotatE', 'SimplE', 'QuatE', 'PairRE', 'TransH', 'TransD'])
         a('--data_path', type=str, default='data')
         a('--dataset', type=str, default='FB15k')
         a('--format', type=str, default='built_in')
@@ -108,6 +108,13 @@ def main(argv=None):
             raise KgeError("TransH is not available on sharded tables (--gpu takes one entry)")
         if args.eval_relation:
             raise KgeError("TransH has no relation ranking (--eval_relation): the relation row enters through two projections")
+    if args.model_name == 'TransD':              # before anything is loaded
+        from .train import check_transd_widths
+        check_transd_widths(args.model_name, args.hidden_dim, args.double_ent, args.double_rel)
+        if len(args.gpu) > 1:
+            raise KgeError("TransD is not available on sharded tables (--gpu takes one entry)")
+        if args.eval_relation:
+            raise KgeError("TransD has no relation ranking (--eval_relation): the relation row enters through two projections")
     if args.gpu[0] < 0:
         raise KgeError("dglke_eval ranks on the GPU only: pass --gpu <id> (there is no CPU fallback)")
     if not os.path.isdir(args.model_path):

@@ -14,7 +14,7 @@ from . import ops
 from .engine import StepEngine
 from .loss import LossGenerator
 from .score_fun import (ComplExScore, DistMultScore, PairREScore, QuatEScore, RESCALScore, RotatEScore, SimplEScore, TransEScore,
-                        TransHScore, TransRScore)
+                        TransDScore, TransHScore, TransRScore)
 from .tensor_models import (ExternalEmbedding, cuda, get_dev, get_device, get_scalar, norm,
                             reshape)
 from ._lib import LOSS_IDS, KgeError
@@ -53,6 +53,9 @@ class KEModel(object):
         if model_name == 'TransH' and (entity_dim % 4 or entity_dim < 4 or relation_dim != 2 * entity_dim):
             raise KgeError("TransH needs an entity width that is a multiple of 4 and relation_dim == 2 * entity_dim, r = [d | w] "
                            "(got %d, %d)" % (entity_dim, relation_dim))
+        if model_name == 'TransD' and (entity_dim % 8 or entity_dim < 8 or relation_dim != entity_dim):
+            raise KgeError("TransD needs entity_dim == relation_dim, rows [x | x_p] of two halves that are multiples of 4 "
+                           "(got %d, %d)" % (entity_dim, relation_dim))
         self.entity_emb = ExternalEmbedding(args, n_entities, entity_dim, device)
         if model_name == 'RESCAL':        # relation_emb = relation_dim * entity_dim (general_models.py:232-236)
             if relation_dim != entity_dim:
@@ -86,6 +89,8 @@ class KEModel(object):
             self.score_func = PairREScore(gamma)
         elif model_name == 'TransH':
             self.score_func = TransHScore(gamma)
+        elif model_name == 'TransD':
+            self.score_func = TransDScore(gamma)
         elif model_name == 'RESCAL':
             self.score_func = RESCALScore(relation_dim // entity_dim, entity_dim)
         elif model_name == 'TransR':

@@ -15,8 +15,9 @@ Deliberate differences from the reference:
   * the device is a GPU (no CPU path), TransR is refused (as in the reference) and K is limited to 1 .. TOPK_MAX;
   * the models: TransE_l1 / TransE_l2, DistMult, ComplEx, RotatE, RESCAL as in the reference, and SimplE, QuatE (rows of
     four quaternion quarters, the relation normalised per quaternion: include/kge_hip.h) and PairRE (relation rows [rH | rT] on
-    unit-normalised entity rows) and TransH (relation rows [d | w], both ends projected onto the hyperplane of normal w), which the
-    reference does not have;
+    unit-normalised entity rows), TransH (relation rows [d | w], both ends projected onto the hyperplane of normal w) and TransD
+    (entity rows [e | e_p], relation rows [r | r_p], both ends through the rank-one map r_p e_p^T + I), which the reference does not
+    have;
   * ke_model: attach_graph takes the known triples (head, rel, tail) themselves (there is no DGLGraph here);
   * ke_model: exclude_mode 'exclude' is exact - known combinations are left out inside the selection kernel, where the
     reference takes the 4K best and falls back to a full sort when too few of them survive; results agree wherever

@@ -15,7 +15,7 @@ are accepted and ignored.  The model classes score with the gamma they were cons
 (ke_model.py:868-893); everything else follows infer.py's stated differences (ties by position, NaN last, K <= 128, GPU
 only, TransR refused, 'exclude' exact).  fit / save / eval are not supported, as in the reference.  The classes: TransE, TransE_l1,
 TransE_l2, TransR (loads, refuses link_predict), DistMult, ComplEx, RotatE, RESCAL as in the reference, and SimplE, QuatE,
-PairRE and TransH, which the reference does not have."""
+PairRE, TransH and TransD, which the reference does not have."""
 import json
 import os
 
@@ -244,6 +244,22 @@ class TransHModel(KGEModel):
         if d % 4 or self._relation_emb.shape[1] != 2 * d:
             raise KgeError("TransH: rows of %d (entity) and %d (relation) values: the entity width must be a multiple of 4 and the "
                            "relation row twice as wide" % (d, self._relation_emb.shape[1]))
+
+
+class TransDModel(KGEModel):
+    """(not among the reference's classes) TransD: entity rows [e | e_p] and relation rows [r | r_p] of the same width; both ends go
+    through the relation's rank-one map x + (x_p . x) r_p and score = gamma - |h_perp + r - t_perp|_2 (include/kge_hip.h, enum
+    kge_model)"""
+
+    def __init__(self, device, gamma):
+        self._gamma = gamma
+        super(TransDModel, self).__init__(device, 'TransD')
+
+    def _after_load(self):
+        d = self._entity_emb.shape[1]
+        if d % 8 or self._relation_emb.shape[1] != d:
+            raise KgeError("TransD: rows of %d (entity) and %d (relation) values: both must be [x | x_p], the same width and a "
+                           "multiple of 8" % (d, self._relation_emb.shape[1]))
 
 
 class RESCALModel(KGEModel):

@@ -7,7 +7,7 @@ ComplEx (:289), RotatE (:451), SimplE (:556), RESCAL (:378); TransR (:110) per-o
 the TransE_l1 kernels in relation space (its fast path is the fused step).  QuatE (not in the reference; include/kge_hip.h,
 enum kge_model) runs on the same per-op entries as ComplEx; PairRE (likewise not in the reference) on the same entries with
 kernels of its own (kge_pairre.hip); TransH (likewise) on the same entries: row-wise kernels of its own (kge_transh.hip) around
-the matrix-core products of the DistMult form.
+the matrix-core products of the DistMult form; TransD (likewise) the same way (kge_transd.hip).
 """
 import torch as th
 
@@ -113,6 +113,16 @@ class TransHScore(_HipScore):
     """TransH (Wang et al., AAAI 2014): relation rows [d | w], twice the entity width; both ends are projected onto the hyperplane
     of unit normal w / |w| inside the kernels and score = gamma - |h_perp + d - t_perp|_2 (include/kge_hip.h, enum kge_model)."""
     model_name = 'TransH'
+
+    def __init__(self, gamma):
+        self.gamma = gamma
+
+
+class TransDScore(_HipScore):
+    """TransD (Ji et al., ACL 2015): entity rows [e | e_p] and relation rows [r | r_p], both twice --hidden_dim; the projection
+    x_perp = x + (x_p . x) r_p is formed inside the kernels and score = gamma - |h_perp + r - t_perp|_2 (include/kge_hip.h, enum
+    kge_model)."""
+    model_name = 'TransD'
 
     def __init__(self, gamma):
         self.gamma = gamma

@@ -43,7 +43,7 @@ class ArgParser(argparse.ArgumentParser):
         super(ArgParser, self).__init__(prog="dglke_train")
         a = self.add_argument
         a('--model_name', default='TransE', choices=['TransE', 'TransE_l1', 'TransE_l2', 'TransR', 'RESCAL',
-                                                     'DistMult', 'ComplEx', 'RotatE', 'SimplE', 'QuatE', 'PairRE', 'TransH'])
+                                                     'DistMult', 'ComplEx', 'RotatE', 'SimplE', 'QuatE', 'PairRE', 'TransH', 'TransD'])
         a('--data_path', type=str, default='data')
         a('--dataset', type=str, default='FB15k')
         a('--format', type=str, default='built_in')
@@ -992,6 +992,31 @@ def check_transh(args):
         raise KgeError("TransH has no relation ranking (--eval_relation): the relation row enters through two projections")
 
 
+def check_transd_widths(model_name, hidden_dim, double_ent, double_rel):
+    """TransD's entity and relation rows are [x | x_p], twice --hidden_dim, and every path is a matrix-core product over 16-byte halves"""
+    if model_name != 'TransD':
+        return
+    if not double_ent or not double_rel:
+        raise KgeError("TransD: entity rows [e | e_p] and relation rows [r | r_p] are both twice --hidden_dim: pass -de and -dr (got%s%s)"
+                       % (" -de" if double_ent else " no -de", ", -dr" if double_rel else ", no -dr"))
+    if hidden_dim < 4 or hidden_dim % 4:
+        raise KgeError("TransD: --hidden_dim must be a multiple of 4 (got %d)" % hidden_dim)
+
+
+def check_transd(args):
+    """TransD trains on the strict step of one GPU's tables: refuse what has no such step, before anything is loaded"""
+    if args.model_name != 'TransD':
+        return
+    check_transd_widths(args.model_name, args.hidden_dim, args.double_ent, args.double_rel)
+    if len(args.gpu) > 1:
+        raise KgeError("TransD is not available on more than one GPU (--gpu takes one entry)")
+    if args.async_update_pipeline or args.async_update_rel:
+        raise KgeError("TransD is not available in the one-step-stale pipeline (--async_update_pipeline / --async_update_rel); "
+                       "plain --async_update runs the strict step and is fine")
+    if args.eval_relation:
+        raise KgeError("TransD has no relation ranking (--eval_relation): the relation row enters through two projections")
+
+
 def main(argv=None, before_train=None):
     """before_train (one GPU): called with the built Trainer in front of its first step - the tests take the initial tables there"""
     args = ArgParser().parse_args(argv)
@@ -1000,6 +1025,7 @@ def main(argv=None, before_train=None):
     check_quate(args)                            # before anything is loaded or created
     check_pairre(args)                           # before anything is loaded or created
     check_transh(args)                           # before anything is loaded or created
+    check_transd(args)                           # before anything is loaded or created
     check_weighted_device_sampler(args)          # before anything is loaded or created
     check_optimizer(args)                        # before anything is loaded or created
     ckpt.check_flags(args)                       # before anything is loaded or created

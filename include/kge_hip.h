@@ -80,7 +80,7 @@ enum kge_model {
                           their _known forms), ranking, chunked ranking and top-K; kge_step_sharded, kge_step_grads,
                           kge_step_async, kge_step_fused_sampling (with a sampler job), kge_rank_eval_split and kge_rank_rel_eval
                           refuse it before any launch. */
-    KGE_TRANSH    = 12 /* TransH (Wang et al., AAAI 2014; not in the reference).  (Ids 9 and 11 are not models: "unknown model".)
+    KGE_TRANSH    = 12,/* TransH (Wang et al., AAAI 2014; not in the reference).  (Ids 9 and 11 are not models: "unknown model".)
                           Entity rows d_e wide, d_e >= 4 and d_e % 4 == 0 (every path is a matrix-core product); relation rows
                           d_r == 2 * d_e wide, r = [d | w]: a translation and a hyperplane normal.  w^ = w / |w|_2 (sqrtf and a true
                           division), w^ = 0 where |w|_2 == 0; x_perp = x - (w^ . x) w^ and
@@ -109,6 +109,43 @@ enum kge_model {
                           their _known forms, kge_step_optim), ranking, chunked ranking and top-K; kge_step_sharded,
                           kge_step_grads, kge_step_async, kge_step_fused_sampling (with a sampler job), kge_rank_eval_split and
                           kge_rank_rel_eval refuse it before any launch; kge_rank_rel_workspace_bytes answers 0. */
+    KGE_TRANSD    = 14 /* TransD (Ji et al., ACL 2015; not in the reference).  (Ids 9, 11 and 13 are not models: "unknown model".)
+                          Entity rows [e | e_p] and relation rows [r | r_p] are both d_e == d_r == 2 k floats wide, k % 4 == 0
+                          (d_e % 8 == 0: every path is a matrix-core product over the first halves).  The relation's projection of
+                          an entity is the rank-one map x_perp = x + (x_p . x) r_p  (M_rx = r_p x_p^T + I, equal widths) and
+                            s(h, r, t) = gamma - |h_perp + r - t_perp|_2                  (the norm, no clamp).
+                          Nothing is normalised; the paper's norm constraints are not implemented; the regulariser acts on the
+                          raw rows.  With r_p = 0, or every e_p = 0, the model is TransE_l2 on the first halves.  Chunked form,
+                          one for both corruption sides: per edge the pair (a, rho), rho = r_p - tails corrupted a = h_perp + r,
+                          heads corrupted a = t_perp - r - per candidate row [n | m] the scalar c = m . n, and
+                            s_ij = gamma - |a_i - n_j - c_j rho_i|_2,
+                          evaluated in its matrix form: with p = a_i . n_j, q = rho_i . n_j, alpha_i = |a_i|^2, beta_j = |n_j|^2,
+                          sigma_i = |rho_i|^2, u_i = a_i . rho_i the squared distance is
+                            alpha_i + beta_j + c_j^2 sigma_i - 2 p + 2 c_j (q - u_i),     floored at 1e-30 like TransE_l2's.
+                          Adjoint, with E_ij = -(dL/ds_ij) / (2 dist_ij): P' = -2 E, Q'_ij = 2 E_ij c_j,
+                            Ga_i   = sum_j P'_ij n_j + 2 a_i sum_j E_ij - 2 rho_i sum_j E_ij c_j,
+                            Grho_i = sum_j Q'_ij n_j + 2 rho_i sum_j E_ij c_j^2 - 2 a_i sum_j E_ij c_j,
+                            Gc_j   = sum_i E_ij (2 c_j sigma_i - 2 u_i + 2 q_ij),
+                            Gn_j   = sum_i (P'_ij a_i + Q'_ij rho_i) + 2 n_j sum_i E_ij + Gc_j m_j,     Gm_j = Gc_j n_j,
+                          then the adjoint of a projection: Gx = Gx_perp + (Gx_perp . r_p) x_p, Gx_p = (Gx_perp . r_p) x,
+                          Gr_p += (x_p . x) Gx_perp.  The products run on the stacked operand [A ; P] - 2 * chunk rows per chunk,
+                          a rows first, k columns - against the candidates' FIRST halves with the matrix-core kernels of the
+                          DistMult form.  Layouts: the per-op entries take the RAW rows like every model's (pos_side, rel
+                          [B, d_e], neg [C * N, d_e]) and keep the stacked operand, a dense copy of the candidates' first halves,
+                          the product blocks and the row / column terms in their workspace; kge_step_workspace_bytes,
+                          kge_score_neg_workspace_bytes and kge_rank_chunked_workspace_bytes answer for the id.  Ranking and top-K
+                          read the candidate operand from the table rows themselves (row stride d_e, k columns: no copy) and keep
+                          TWO scalars per candidate, [beta | c] - 8 N bytes where TransH keeps 4 N - in the entry that holds the
+                          candidate norms, so their workspaces are those of 2 * n_cand candidates:
+                            kge_rank_eval:    kge_rank_workspace_bytes(Eb, 2 * n_cand, d_e)   (a in the A entry, rho in RV, alpha in
+                                              asq, sigma and u in the first Eb floats of the first two TransR rows)
+                            kge_topk_select / _filtered:  kge_topk_workspace_bytes(rows, 2 * n_cand, d_e + 2, K)   (the A entry is
+                                              [a block | rho block | sigma | u]; dglke_amd._lib.topk_workspace_bytes).
+                          KGE_FLAG_FORCE_PAIRWISE is ignored as for TransH.  Strict step on local tables (kge_step_fused,
+                          kge_step_phase, their _known forms, kge_step_optim), ranking, chunked ranking and top-K;
+                          kge_step_sharded, kge_step_grads, kge_step_async, kge_step_fused_sampling (with a sampler job),
+                          kge_rank_eval_split and kge_rank_rel_eval refuse it before any launch; kge_rank_rel_workspace_bytes
+                          answers 0. */
 };
 
 /* loss criteria (models/pytorch/loss.py:44-59) */
