@@ -8,9 +8,14 @@
 #include <new>
 #include <algorithm>
 #include "kge_common.hpp"
+#include "kge_models.hpp"
+#include "kge_own_fwd.hpp"
 #include "kge_sampler_common.hpp"
 
 namespace {
+
+using kge::clamp_of; using kge::fill_gemm; using kge::fill_pair;
+using kge::OwnBlock; using kge::OwnBufs; using kge::OwnBwd; using kge::OwnCands; using kge::OwnOperand;
 
 thread_local char g_err[512] = "";
 
@@ -50,69 +55,22 @@ struct Carver {
 };
 
 int check_model(int model, int d_e, int d_r) {
-    if (model < KGE_TRANSE_L1 || (model > KGE_TRANSR && model != KGE_QUATE && model != KGE_PAIRRE && model != KGE_TRANSH && model != KGE_TRANSD))
-        return fail(KGE_ERR_ARG, "unknown model %d", model);
-    if (model == KGE_TRANSD) {         // rows [x | x_p] of two halves, every path a matrix-core product over the first: 16-byte halves
-        if (d_e < 8 || d_e % 8 || d_r != d_e)
-            return fail(KGE_ERR_ARG, "TransD needs d_e == d_r and d_e %% 8 == 0, rows [x | x_p] of two halves (got %d, %d)", d_e, d_r);
-        return KGE_OK;
-    }
-    if (model == KGE_TRANSH) {         // every path is a matrix-core product: 16-byte rows
-        if (d_e < 4 || d_e % 4 || (int64_t)d_r != 2 * (int64_t)d_e)
-            return fail(KGE_ERR_ARG, "TransH needs d_e >= 4, d_e %% 4 == 0 and d_r == 2 * d_e, r = [d | w] (got %d, %d)", d_e, d_r);
-        return KGE_OK;
-    }
-    if (model == KGE_PAIRRE) {
-        if (d_e <= 0 || (int64_t)d_r != 2 * (int64_t)d_e)
-            return fail(KGE_ERR_ARG, "PairRE needs d_e > 0 and d_r == 2 * d_e, r = [rH | rT] (got %d, %d)", d_e, d_r);
-        return KGE_OK;
-    }
-    if (model == KGE_QUATE) {
-        if (d_e <= 0 || d_e % 4 || d_r != d_e)
-            return fail(KGE_ERR_ARG, "QuatE needs d_e a positive multiple of 4 and d_r == d_e (got %d, %d)", d_e, d_r);
-        return KGE_OK;
-    }
-    if (model == KGE_TRANSR) {
-        if (d_e <= 0 || d_r <= 0 || d_r > 1024) return fail(KGE_ERR_ARG, "TransR needs 0 < d_r <= 1024 (got d_e=%d d_r=%d)", d_e, d_r);
-        return KGE_OK;
-    }
-    if (model == KGE_RESCAL) {
-        if (d_e <= 0 || d_e > 1024 || (int64_t)d_r != (int64_t)d_e * d_e)
-            return fail(KGE_ERR_ARG, "RESCAL needs d_r == d_e*d_e and d_e <= 1024 (got d_e=%d d_r=%d)", d_e, d_r);
-        return KGE_OK;
-    }
-    if (d_e <= 0 || d_r <= 0) return fail(KGE_ERR_ARG, "bad dims d_e=%d d_r=%d", d_e, d_r);
-    if (model == KGE_COMPLEX || model == KGE_SIMPLE) {
-        if (d_e % 2 || d_r != d_e) return fail(KGE_ERR_ARG, "%s needs even d_e and d_r == d_e (got %d, %d)",
-                                               model == KGE_COMPLEX ? "ComplEx" : "SimplE", d_e, d_r);
-    } else if (model == KGE_ROTATE) {
-        if (d_e % 2 || d_r != d_e / 2) return fail(KGE_ERR_ARG, "RotatE needs d_r == d_e/2 (got d_e=%d d_r=%d)", d_e, d_r);
-    } else if (d_r != d_e) {
-        return fail(KGE_ERR_ARG, "%s needs d_r == d_e (got %d, %d)", "TransE/DistMult", d_e, d_r);
-    }
+    const kge::ModelRow *m = kge::model_row(model);
+    if (!m) return fail(KGE_ERR_ARG, "unknown model %d", model);
+    if (m->bad_dims_first && (d_e <= 0 || d_r <= 0)) return fail(KGE_ERR_ARG, "bad dims d_e=%d d_r=%d", d_e, d_r);
+    if (!kge::widths_ok(*m, d_e, d_r)) return fail(KGE_ERR_ARG, m->widths_msg, d_e, d_r);
     return KGE_OK;
 }
 
-// QuatE runs the strict step on local tables and single-table ranking; the other entries open with their own tests
-int no_quate(const char *who) { return fail(KGE_ERR_ARG, "%s: not available for QuatE (strict step on local tables, single-table ranking)", who); }
-
-// PairRE likewise, and it has no relation ranking (the score is not a product of a query row and the relation row)
-int no_pairre(const char *who) {
-    return fail(KGE_ERR_ARG, "%s: not available for PairRE (strict step on local tables, single-table entity ranking and top-K)", who);
-}
-
-// TransH likewise
-int no_transh(const char *who) {
-    return fail(KGE_ERR_ARG, "%s: not available for TransH (strict step on local tables, single-table entity ranking and top-K)", who);
-}
-
-// TransD likewise
-int no_transd(const char *who) {
-    return fail(KGE_ERR_ARG, "%s: not available for TransD (strict step on local tables, single-table entity ranking and top-K)", who);
+// the entry `who` is closed to the model (kge_models.hpp): every other id passes
+int closed(kge::Entry e, int model, const char *who) {
+    const kge::ModelRow *m = kge::model_row(model);
+    if (!m || !(m->closed & e)) return KGE_OK;
+    if (e == kge::E_MODULAR) return fail(KGE_ERR_ARG, "%s has no modular score ops: use kge_step_fused / kge_rank_eval_ex", m->name);
+    return fail(KGE_ERR_ARG, "%s: not available for %s (%s)", who, m->name, m->closed_why);
 }
 
 inline float rot_div_of(float emb_init) { return (float)((double)emb_init / M_PI); }
-inline float clamp_of(int model) { return model == KGE_SIMPLE ? KGE_SIMPLE_CLAMP : 0.f; }
 
 bool use_mfma(int model, int d_e, int N, unsigned flags) {
     return !(flags & KGE_FLAG_FORCE_PAIRWISE) && neg_mfma_supported(model, d_e, N);
@@ -127,23 +85,12 @@ int check_loss(int genre, int adv, int pairwise) {
         return fail(KGE_ERR_ARG, "this loss cannot be applied to pairwise loss function");
     return KGE_OK;
 }
-int no_modular_transr() { return fail(KGE_ERR_ARG, "TransR has no modular score ops: use kge_step_fused / kge_rank_eval_ex"); }
 
 // no per-step output asked: the plain training step
 bool plain_out(const kge_step_out *out) {
     return !out || (!out->loss4 && !out->pos_score && !out->neg_score && !out->g_pos_ent && !out->g_neg && !out->g_rel);
 }
 
-void fill_gemm(GemmArgs &g, int model, int C, int chunk, int N, int d_e, float gamma, const float *A, const float *nbase, const int64_t *nidx) {
-    g = GemmArgs{};
-    g.model = model; g.C = C; g.chunk = chunk; g.N = N; g.D = d_e; g.gamma = gamma;
-    g.A = A; g.nbase = nbase; g.nidx = nidx; g.B = C * chunk; g.clampv = clamp_of(model);
-}
-void fill_pair(NegArgs &na, int model, int C, int chunk, int N, int d_e, float gamma, const float *A, const float *nbase, const int64_t *nidx) {
-    na = NegArgs{};
-    na.model = model; na.C = C; na.chunk = chunk; na.N = N; na.d_e = d_e; na.gamma = gamma;
-    na.A = A; na.nbase = nbase; na.nidx = nidx; na.clampv = clamp_of(model);
-}
 // the criterion and its operands; everything else (row terms, running sums, score transforms) is the caller's
 void fill_loss(LossArgs &a, const LossParams &lp, int B, int N, const float *pos, const float *neg, const float *w, float *dpos, float *dneg) {
     a = LossArgs{};
@@ -160,137 +107,6 @@ void fill_edge_bwd(EdgeBwdArgs &e, const EdgeSrc &src, int model, int B, int d_e
                    const float *dpos, const float *GA) {
     fill_edge(e, src, model, B, d_e, d_r, neg_head, gamma, rot_div);
     e.dpos = dpos; e.GA = GA;
-}
-
-// PairRE (kge_pairre.hip): the edge forward of B edges whose rows come from src, and the chunked scoring block
-void fill_pairre_edge(PairreEdgeArgs &e, const EdgeSrc &src, int B, int d_e, int neg_head, float gamma, float *P, float *A, float *W) {
-    e = PairreEdgeArgs{};
-    e.src = src; e.B = B; e.d_e = d_e; e.neg_head = neg_head; e.gamma = gamma; e.pos_score = P; e.A = A; e.W = W;
-}
-void fill_pairre_neg(PairreNegArgs &n, int C, int chunk, int N, int d_e, float gamma, const float *A, const float *W, const float *nbase,
-                     const int64_t *nidx, const float *nrm) {
-    n = PairreNegArgs{};
-    n.C = C; n.chunk = chunk; n.N = N; n.d_e = d_e; n.gamma = gamma; n.A = A; n.W = W; n.nbase = nbase; n.nidx = nidx; n.nrm = nrm;
-}
-// the norms of n candidate rows base + (idx ? idx[j] : j) * d_e
-int pairre_norms(const float *base, const int64_t *idx, int64_t n, int d_e, float *nrm, hipStream_t s) {
-    PairreEdgeArgs e{};
-    e.d_e = d_e; e.nbase = base; e.nidx = idx; e.n_neg = (int)n; e.nrm = nrm;
-    return launch_pairre_edge_fwd(e, s);
-}
-
-// TransH (kge_transh.hip): the edge forward of B edges whose rows come from src, into the stacked operand of chunks of `chunk` rows
-void fill_transh_edge(TranshEdgeArgs &e, const EdgeSrc &src, int B, int chunk, int d_e, int neg_head, float gamma, float *P, float *AW,
-                      float *alpha, float *cw) {
-    e = TranshEdgeArgs{};
-    e.src = src; e.B = B; e.chunk = chunk; e.d_e = d_e; e.neg_head = neg_head; e.gamma = gamma; e.pos_score = P;
-    e.AW = AW; e.alpha = alpha; e.cw = cw;
-}
-// |x|^2 of n candidate rows base + (idx ? idx[j] : j) * d_e
-int transh_norms(const float *base, const int64_t *idx, int64_t n, int d_e, float *beta, hipStream_t s) {
-    TranshEdgeArgs e{};
-    e.d_e = d_e; e.nbase = base; e.nidx = idx; e.n_neg = (int)n; e.beta = beta;
-    return launch_transh_edge_fwd(e, s);
-}
-// one chunked scoring block: the stacked operand, its row statistics, the candidate rows and theirs, and the blocks behind them
-struct TranshBlock {
-    int C, chunk, N, d_e; float gamma;
-    const float *AW, *alpha, *cw;                     // [C, 2 chunk, d_e], [C*chunk] x 2
-    const float *nbase; const int64_t *nidx; const float *beta;
-    float *PQ;                                        // [C, 2 chunk, N] raw products
-};
-void fill_transh_neg(TranshNegArgs &n, const TranshBlock &k) {
-    n = TranshNegArgs{};
-    n.C = k.C; n.chunk = k.chunk; n.N = k.N; n.d_e = k.d_e; n.gamma = k.gamma; n.alpha = k.alpha; n.cw = k.cw; n.beta = k.beta; n.PQ = k.PQ;
-}
-// p | q = [A ; W^] . N^T on the forward tiles of kge_neg_gemm.hip in their DistMult form (2 chunk rows per chunk), then S
-int transh_products(const TranshBlock &k, hipStream_t s) {
-    GemmArgs g; fill_gemm(g, KGE_DISTMULT, k.C, 2 * k.chunk, k.N, k.d_e, k.gamma, k.AW, k.nbase, k.nidx);
-    g.S = k.PQ;
-    KGE_TRY(launch_neg_fwd_gemm(g, s));
-    return KGE_OK;
-}
-int transh_scores(const TranshBlock &k, float *S, hipStream_t s) {
-    if (int rc = transh_products(k, s)) return rc;
-    TranshNegArgs n; fill_transh_neg(n, k);
-    n.S = S;
-    KGE_TRY(launch_transh_score(n, s));
-    return KGE_OK;
-}
-// G = dL/dS -> the products GAW = Ga | Gw^ [C, 2 chunk, d_e] and GN [C*N, d_e] (their row / column terms: rs, kap, cs; the edge
-// backward adds them).  The backward tiles of kge_neg_gemm.hip in their DistMult form with K = 2 chunk; beyond the rows a tile's
-// workgroup indexes (GB_MAXK) the pairwise kernels, which take any size
-int transh_neg_bwd(const TranshBlock &k, const float *G, float *PQc, float *rs, float *kap, float *cs, float *GAW, float *GN, hipStream_t s) {
-    TranshNegArgs n; fill_transh_neg(n, k);
-    n.G = G; n.PQc = PQc; n.rs = rs; n.kap = kap; n.cs = cs;
-    KGE_TRY(launch_transh_coef(n, s));
-    GemmArgs g; fill_gemm(g, KGE_DISTMULT, k.C, 2 * k.chunk, k.N, k.d_e, k.gamma, k.AW, k.nbase, k.nidx);
-    g.W = PQc; g.GA = GAW; g.GN = GN;
-    if ((2 * k.chunk > k.N ? 2 * k.chunk : k.N) > KGE_NEG_BWD_GEMM_MAXK) {      // (tested here: any error of the launcher stays an error)
-        NegArgs na; fill_pair(na, KGE_DISTMULT, k.C, 2 * k.chunk, k.N, k.d_e, k.gamma, k.AW, k.nbase, k.nidx);
-        na.W = PQc; na.GA = GAW; na.GN = GN;
-        KGE_TRY(launch_neg_bwd_pair(na, s));
-    } else KGE_TRY(launch_neg_bwd_gemm(g, s));
-    return KGE_OK;
-}
-
-// TransD (kge_transd.hip): the edge forward of B edges whose rows come from src, into the stacked operand of chunks of `chunk` rows
-void fill_transd_edge(TransdEdgeArgs &e, const EdgeSrc &src, int B, int chunk, int d_e, int neg_head, float gamma, float *P, float *AP,
-                      float *alpha, float *sig, float *u) {
-    e = TransdEdgeArgs{};
-    e.src = src; e.B = B; e.chunk = chunk; e.d_e = d_e; e.neg_head = neg_head; e.gamma = gamma; e.pos_score = P;
-    e.AP = AP; e.alpha = alpha; e.sig = sig; e.u = u;
-}
-// |n|^2, m . n and the dense first halves of n candidate rows base + (idx ? idx[j] : j) * d_e
-int transd_cands(const float *base, const int64_t *idx, int64_t n, int d_e, float *beta, float *cj, float *Nh, hipStream_t s) {
-    TransdEdgeArgs e{};
-    e.d_e = d_e; e.nbase = base; e.nidx = idx; e.n_neg = (int)n; e.beta = beta; e.cj = cj; e.Nh = Nh;
-    return launch_transd_edge_fwd(e, s);
-}
-// one chunked scoring block: the stacked operand (k = d_e / 2 columns), its row statistics, the candidates' dense first halves
-// and their scalars, and the blocks behind them
-struct TransdBlock {
-    int C, chunk, N, d_e; float gamma;
-    const float *AP, *alpha, *sig, *u;                // [C, 2 chunk, k], [C*chunk] x 3
-    const float *Nh, *beta, *cj;                      // [C*N, k], [C*N] x 2
-    float *PQ;                                        // [C, 2 chunk, N] raw products
-};
-void fill_transd_neg(TransdNegArgs &n, const TransdBlock &k) {
-    n = TransdNegArgs{};
-    n.C = k.C; n.chunk = k.chunk; n.N = k.N; n.gamma = k.gamma; n.alpha = k.alpha; n.sig = k.sig; n.u = k.u; n.beta = k.beta; n.cj = k.cj;
-    n.PQ = k.PQ;
-}
-// p | q = [A ; P] . Nh^T on the forward tiles of kge_neg_gemm.hip in their DistMult form (2 chunk rows per chunk, k columns), then S
-int transd_products(const TransdBlock &k, hipStream_t s) {
-    GemmArgs g; fill_gemm(g, KGE_DISTMULT, k.C, 2 * k.chunk, k.N, k.d_e / 2, k.gamma, k.AP, k.Nh, nullptr);
-    g.S = k.PQ;
-    KGE_TRY(launch_neg_fwd_gemm(g, s));
-    return KGE_OK;
-}
-int transd_scores(const TransdBlock &k, float *S, hipStream_t s) {
-    if (int rc = transd_products(k, s)) return rc;
-    TransdNegArgs n; fill_transd_neg(n, k);
-    n.S = S;
-    KGE_TRY(launch_transd_score(n, s));
-    return KGE_OK;
-}
-// the buffers of a TransD block, for B edges in chunks against CN candidate rows, N per chunk (d_e: the row width 2 k)
-struct TransdBufs { float *AP, *sig, *u, *cj, *Nh, *PQ, *PQc, *rs, *rc, *rc2, *cs, *gc, *GAP, *GNp; };
-// G = dL/dS -> the products GAP = Ga | Grho [C, 2 chunk, k] and GNp [C*N, k] (their row / column terms: rs, rc, rc2, cs, gc; the edge
-// backward adds them).  The backward tiles of kge_neg_gemm.hip in their DistMult form with K = 2 chunk; beyond the rows a tile's
-// workgroup indexes (GB_MAXK) the pairwise kernels, which take any size
-int transd_neg_bwd(const TransdBlock &k, const float *G, const TransdBufs &t, hipStream_t s) {
-    TransdNegArgs n; fill_transd_neg(n, k);
-    n.G = G; n.PQc = t.PQc; n.rs = t.rs; n.rc = t.rc; n.rc2 = t.rc2; n.cs = t.cs; n.gc = t.gc;
-    KGE_TRY(launch_transd_coef(n, s));
-    GemmArgs g; fill_gemm(g, KGE_DISTMULT, k.C, 2 * k.chunk, k.N, k.d_e / 2, k.gamma, k.AP, k.Nh, nullptr);
-    g.W = t.PQc; g.GA = t.GAP; g.GN = t.GNp;
-    if ((2 * k.chunk > k.N ? 2 * k.chunk : k.N) > KGE_NEG_BWD_GEMM_MAXK) {
-        NegArgs na; fill_pair(na, KGE_DISTMULT, k.C, 2 * k.chunk, k.N, k.d_e / 2, k.gamma, k.AP, k.Nh, nullptr);
-        na.W = t.PQc; na.GA = t.GAP; na.GN = t.GNp;
-        KGE_TRY(launch_neg_bwd_pair(na, s));
-    } else KGE_TRY(launch_neg_bwd_gemm(g, s));
-    return KGE_OK;
 }
 
 // SimplE, modular backward: no gradient through a saturated clamp
@@ -347,26 +163,15 @@ int kge_score_pos(int model, const float *h, const float *r, const float *t, int
                   int d_r, float gamma, float emb_init, float *out, void *stream) {
     if (int rc = check_model(model, d_e, d_r)) return rc;
     if (!h || !r || !t || !out || B < 0) return fail(KGE_ERR_ARG, "kge_score_pos: bad argument");
-    if (model == KGE_TRANSR) return no_modular_transr();
+    if (int rc = closed(kge::E_MODULAR, model, "kge_score_pos")) return rc;
     if (model == KGE_RESCAL) {                       // p = h . (M t), one pass over M per edge
         RescalMatvecArgs m{};
         m.B = (int)B; m.D = d_e; m.rel = r; m.y1 = t; m.pd = h; m.p = out;
         KGE_TRY(launch_rescal_matvec(m, (hipStream_t)stream));
         return KGE_OK;
     }
-    if (model == KGE_PAIRRE) {
-        PairreEdgeArgs e; fill_pairre_edge(e, EdgeSrc{h, nullptr, t, nullptr, r, nullptr}, (int)B, d_e, 0, gamma, out, nullptr, nullptr);
-        KGE_TRY(launch_pairre_edge_fwd(e, (hipStream_t)stream));
-        return KGE_OK;
-    }
-    if (model == KGE_TRANSH) {
-        TranshEdgeArgs e; fill_transh_edge(e, EdgeSrc{h, nullptr, t, nullptr, r, nullptr}, (int)B, (int)B, d_e, 0, gamma, out, nullptr, nullptr, nullptr);
-        KGE_TRY(launch_transh_edge_fwd(e, (hipStream_t)stream));
-        return KGE_OK;
-    }
-    if (model == KGE_TRANSD) {
-        TransdEdgeArgs e; fill_transd_edge(e, EdgeSrc{h, nullptr, t, nullptr, r, nullptr}, (int)B, (int)B, d_e, 0, gamma, out, nullptr, nullptr, nullptr, nullptr);
-        KGE_TRY(launch_transd_edge_fwd(e, (hipStream_t)stream));
+    if (kge::model_row(model)->own_fwd) {
+        KGE_TRY(kge::own_prepare(model, EdgeSrc{h, nullptr, t, nullptr, r, nullptr}, (int)B, 0, d_e, 0, gamma, out, OwnOperand{}, nullptr, (hipStream_t)stream));
         return KGE_OK;
     }
     EdgeFwdArgs a;
@@ -381,7 +186,7 @@ int kge_score_pos_bwd(int model, const float *h, const float *r, const float *t,
                       float *gt, void *stream) {
     if (int rc = check_model(model, d_e, d_r)) return rc;
     if (!h || !r || !t || !dpos || B < 0) return fail(KGE_ERR_ARG, "kge_score_pos_bwd: bad argument");
-    if (model == KGE_TRANSR) return no_modular_transr();
+    if (int rc = closed(kge::E_MODULAR, model, "kge_score_pos_bwd")) return rc;
     if (model == KGE_RESCAL) {                       // gh = dp M t, gt = dp M^T h, gr = dp h t^T
         if (!gh || !gt || !gr) return fail(KGE_ERR_ARG, "kge_score_pos_bwd: RESCAL needs all three outputs");
         hipStream_t s = (hipStream_t)stream;
@@ -395,22 +200,10 @@ int kge_score_pos_bwd(int model, const float *h, const float *r, const float *t,
         KGE_TRY(launch_rescal_outer(o, s));
         return KGE_OK;
     }
-    if (model == KGE_PAIRRE) {
-        PairreBwdArgs e{};
-        e.src = EdgeSrc{h, nullptr, t, nullptr, r, nullptr}; e.B = (int)B; e.d_e = d_e; e.dpos = dpos; e.GH = gh; e.GT = gt; e.GR = gr;
-        KGE_TRY(launch_pairre_edge_bwd(e, (hipStream_t)stream));
-        return KGE_OK;
-    }
-    if (model == KGE_TRANSH) {
-        TranshBwdArgs e{};
-        e.src = EdgeSrc{h, nullptr, t, nullptr, r, nullptr}; e.B = (int)B; e.chunk = (int)B; e.d_e = d_e; e.dpos = dpos; e.GH = gh; e.GT = gt; e.GR = gr;
-        KGE_TRY(launch_transh_edge_bwd(e, (hipStream_t)stream));
-        return KGE_OK;
-    }
-    if (model == KGE_TRANSD) {
-        TransdBwdArgs e{};
-        e.src = EdgeSrc{h, nullptr, t, nullptr, r, nullptr}; e.B = (int)B; e.chunk = (int)B; e.d_e = d_e; e.dpos = dpos; e.GH = gh; e.GT = gt; e.GR = gr;
-        KGE_TRY(launch_transd_edge_bwd(e, (hipStream_t)stream));
+    if (kge::model_row(model)->own_fwd) {             // the positive edges alone: no block behind them
+        OwnBwd x{}; x.dpos = dpos; x.GH = gh; x.GT = gt; x.GR = gr;
+        KGE_TRY(kge::own_backward(model, OwnBlock{1, (int)B, 0, d_e, gamma, OwnOperand{}, nullptr, nullptr, nullptr}, nullptr,
+                                  EdgeSrc{h, nullptr, t, nullptr, r, nullptr}, 0, nullptr, nullptr, x, (hipStream_t)stream));
         return KGE_OK;
     }
     EdgeBwdArgs a;
@@ -421,24 +214,7 @@ int kge_score_pos_bwd(int model, const float *h, const float *r, const float *t,
 }
 
 // the workspace of the modular negative-score entry points (forward and backward share it)
-struct TranshBufs { float *AW, *cw, *PQ, *PQc, *rs, *kap, *cs, *GAW; };
-// TransH: the stacked operand and its products' blocks, for B edges in chunks against CN candidate rows, N per chunk
-static void carve_transh(Carver &cv, TranshBufs &t, size_t B, size_t CN, size_t N, size_t d_e) {
-    t.AW = cv.f(2 * B * d_e); t.cw = cv.f(B);               // (a, w^) stacked; w^ . a (|a|^2, |n|^2: the asq / bsq entries)
-    t.PQ = cv.f(2 * B * N); t.PQc = cv.f(2 * B * N);        // raw p | q; P' | Q'
-    t.rs = cv.f(B); t.kap = cv.f(B); t.cs = cv.f(CN);       // row and column terms of the backward
-    t.GAW = cv.f(2 * B * d_e);                              // Ga | Gw^ products
-}
-static void carve_transd(Carver &cv, TransdBufs &t, size_t B, size_t CN, size_t N, size_t d_e) {
-    const size_t k = d_e / 2;
-    t.AP = cv.f(2 * B * k); t.sig = cv.f(B); t.u = cv.f(B);         // (a, rho) stacked; |rho|^2, a . rho (|a|^2, |n|^2: the asq / bsq entries)
-    t.cj = cv.f(CN); t.Nh = cv.f(CN * k);                           // m . n and the dense first half of every candidate row
-    t.PQ = cv.f(2 * B * N); t.PQc = cv.f(2 * B * N);                // raw p | q; P' | Q'
-    t.rs = cv.f(B); t.rc = cv.f(B); t.rc2 = cv.f(B);                // row sums of the backward
-    t.cs = cv.f(CN); t.gc = cv.f(CN);                               // its column sums
-    t.GAP = cv.f(2 * B * k); t.GNp = cv.f(CN * k);                  // Ga | Grho and Gn products
-}
-struct NegBufs { float *A, *asq, *bsq, *W, *GA, *GNp, *PW, *PGW, *Pnrm; TranshBufs th; TransdBufs td; };
+struct NegBufs { float *A, *asq, *bsq, *W, *GA, *GNp; OwnBufs own; };
 static size_t carve_neg(Carver &cv, NegBufs &w, int model, int C, int chunk, int N, int d_e) {
     const size_t B = (size_t)C * chunk;
     w.A = cv.f(B * d_e);                              // pos-side vectors
@@ -446,12 +222,7 @@ static size_t carve_neg(Carver &cv, NegBufs &w, int model, int C, int chunk, int
     w.W = cv.f(B * (size_t)N);                        // L2-scaled / clamp-masked dneg
     w.GA = cv.f(B * d_e);
     w.GNp = neg_bwd_lc_supported(model, d_e) ? cv.f(neg_bwd_lc_partial_floats(model, C, chunk, N, d_e)) : nullptr;
-    w.PW = w.PGW = w.Pnrm = nullptr;
-    if (model == KGE_PAIRRE) { w.PW = cv.f(B * d_e); w.PGW = cv.f(B * d_e); w.Pnrm = cv.f((size_t)C * N); }   // w, Gw, candidate norms
-    w.th = TranshBufs{};
-    if (model == KGE_TRANSH) carve_transh(cv, w.th, B, (size_t)C * N, (size_t)N, (size_t)d_e);
-    w.td = TransdBufs{};
-    if (model == KGE_TRANSD) carve_transd(cv, w.td, B, (size_t)C * N, (size_t)N, (size_t)d_e);
+    kge::own_carve(model, cv, w.own, w.A, w.asq, w.bsq, w.GA, B, (size_t)C * N, (size_t)N, (size_t)d_e);      // (nothing for the other models)
     return cv.off;
 }
 
@@ -469,24 +240,9 @@ static int neg_prepare(int model, int neg_head, const float *pos_side, const flo
         KGE_TRY(launch_rescal_matvec(m, s));
         return KGE_OK;
     }
-    if (model == KGE_PAIRRE) {         // (a, w) of every edge and the norm of every candidate row, one launch
-        PairreEdgeArgs e; fill_pairre_edge(e, EdgeSrc{pos_side, nullptr, pos_side, nullptr, rel, nullptr}, B, d_e, neg_head, gamma, nullptr, w.A, w.PW);
-        e.nbase = neg; e.n_neg = C * N; e.nrm = w.Pnrm;
-        KGE_TRY(launch_pairre_edge_fwd(e, s));
-        return KGE_OK;
-    }
-    if (model == KGE_TRANSH) {         // the stacked (a, w^) with its row statistics and |n|^2 of every candidate row, one launch
-        TranshEdgeArgs e; fill_transh_edge(e, EdgeSrc{pos_side, nullptr, pos_side, nullptr, rel, nullptr}, B, chunk, d_e, neg_head, gamma, nullptr,
-                                           w.th.AW, w.asq, w.th.cw);
-        e.nbase = neg; e.n_neg = C * N; e.beta = w.bsq;
-        KGE_TRY(launch_transh_edge_fwd(e, s));
-        return KGE_OK;
-    }
-    if (model == KGE_TRANSD) {         // the stacked (a, rho) with its row statistics and the candidates' scalars and first halves, one launch
-        TransdEdgeArgs e; fill_transd_edge(e, EdgeSrc{pos_side, nullptr, pos_side, nullptr, rel, nullptr}, B, chunk, d_e, neg_head, gamma, nullptr,
-                                           w.td.AP, w.asq, w.td.sig, w.td.u);
-        e.nbase = neg; e.n_neg = C * N; e.beta = w.bsq; e.cj = w.td.cj; e.Nh = w.td.Nh;
-        KGE_TRY(launch_transd_edge_fwd(e, s));
+    if (kge::model_row(model)->own_fwd) {      // the operand of every edge and the scalars of every candidate row, one launch
+        const OwnCands c{neg, nullptr, C * N, nullptr, 0, 0, nullptr};
+        KGE_TRY(kge::own_prepare(model, EdgeSrc{pos_side, nullptr, pos_side, nullptr, rel, nullptr}, B, chunk, d_e, neg_head, gamma, nullptr, w.own.o, &c, s));
         return KGE_OK;
     }
     EdgeFwdArgs a;
@@ -502,22 +258,15 @@ int kge_score_neg_fwd(int model, int neg_head, const float *pos_side, const floa
     if (int rc = check_model(model, d_e, d_r)) return rc;
     if (!pos_side || !rel || !neg || !out || !ws || C < 0 || chunk <= 0 || N <= 0)
         return fail(KGE_ERR_ARG, "kge_score_neg_fwd: bad argument");
-    if (model == KGE_TRANSR) return no_modular_transr();
+    if (int rc = closed(kge::E_MODULAR, model, "kge_score_neg_fwd")) return rc;
     if (C == 0) return KGE_OK;
     hipStream_t s = (hipStream_t)stream;
     Carver cv(ws, ws_bytes); NegBufs w;
     if (carve_neg(cv, w, model, C, chunk, N, d_e) > ws_bytes) return fail(KGE_ERR_WORKSPACE, "workspace too small");
     const bool mf = use_mfma(model, d_e, N, flags);
     if (int rc = neg_prepare(model, neg_head, pos_side, rel, neg, C, chunk, N, d_e, d_r, gamma, emb_init, mf && model == KGE_TRANSE_L2, w, s)) return rc;
-    if (model == KGE_PAIRRE) {
-        PairreNegArgs n; fill_pairre_neg(n, C, chunk, N, d_e, gamma, w.A, w.PW, neg, nullptr, w.Pnrm);
-        n.S = out;
-        KGE_TRY(launch_pairre_neg_fwd(n, s));
-    } else if (model == KGE_TRANSH) {
-        if (int rc = transh_scores(TranshBlock{C, chunk, N, d_e, gamma, w.th.AW, w.asq, w.th.cw, neg, nullptr, w.bsq, w.th.PQ}, out, s)) return rc;
-    } else if (model == KGE_TRANSD) {
-        if (int rc = transd_scores(TransdBlock{C, chunk, N, d_e, gamma, w.td.AP, w.asq, w.td.sig, w.td.u, w.td.Nh, w.bsq, w.td.cj, w.td.PQ}, out, s))
-            return rc;
+    if (kge::model_row(model)->own_fwd) {
+        KGE_TRY(kge::own_scores(model, OwnBlock{C, chunk, N, d_e, gamma, w.own.o, neg, nullptr, w.own.PQ}, out, s));
     } else if (mf) {
         GemmArgs g; fill_gemm(g, model, C, chunk, N, d_e, gamma, w.A, neg, nullptr);
         g.S = out; g.asq = w.asq; g.bsq = w.bsq;
@@ -536,7 +285,7 @@ int kge_score_neg_bwd(int model, int neg_head, const float *pos_side, const floa
     if (int rc = check_model(model, d_e, d_r)) return rc;
     if (!pos_side || !rel || !neg || !dneg || !g_pos_side || !g_rel || !g_neg || !ws || C < 0 || chunk <= 0 || N <= 0)
         return fail(KGE_ERR_ARG, "kge_score_neg_bwd: bad argument");
-    if (model == KGE_TRANSR) return no_modular_transr();
+    if (int rc = closed(kge::E_MODULAR, model, "kge_score_neg_bwd")) return rc;
     if ((model == KGE_TRANSE_L2 || model == KGE_SIMPLE) && !neg_score)
         return fail(KGE_ERR_ARG, "kge_score_neg_bwd: TransE_l2 / SimplE need the forward scores");
     if (C == 0) return KGE_OK;
@@ -546,39 +295,11 @@ int kge_score_neg_bwd(int model, int neg_head, const float *pos_side, const floa
     const size_t need = carve_neg(cv, w, model, C, chunk, N, d_e);
     if (need > ws_bytes) return fail(KGE_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
     if (int rc = neg_prepare(model, neg_head, pos_side, rel, neg, C, chunk, N, d_e, d_r, gamma, emb_init, false, w, s)) return rc;
-    if (model == KGE_PAIRRE) {
-        PairreNegArgs n; fill_pairre_neg(n, C, chunk, N, d_e, gamma, w.A, w.PW, neg, nullptr, w.Pnrm);
-        n.G = dneg; n.GA = w.GA; n.GW = w.PGW; n.GN = g_neg;
-        KGE_TRY(launch_pairre_neg_bwd(n, s));
-        PairreBwdArgs e{};
-        e.src = EdgeSrc{pos_side, nullptr, pos_side, nullptr, rel, nullptr}; e.B = B; e.d_e = d_e; e.neg_head = neg_head;
-        e.GA = w.GA; e.GW = w.PGW; e.GR = g_rel;
-        if (neg_head) e.GT = g_pos_side; else e.GH = g_pos_side;
-        KGE_TRY(launch_pairre_edge_bwd(e, s));
-        return KGE_OK;
-    }
-    if (model == KGE_TRANSH) {
-        const TranshBlock k{C, chunk, N, d_e, gamma, w.th.AW, w.asq, w.th.cw, neg, nullptr, w.bsq, w.th.PQ};
-        if (int rc = transh_products(k, s)) return rc;
-        if (int rc = transh_neg_bwd(k, dneg, w.th.PQc, w.th.rs, w.th.kap, w.th.cs, w.th.GAW, g_neg, s)) return rc;
-        TranshBwdArgs e{};
-        e.src = EdgeSrc{pos_side, nullptr, pos_side, nullptr, rel, nullptr}; e.B = B; e.chunk = chunk; e.d_e = d_e; e.neg_head = neg_head;
-        e.GAW = w.th.GAW; e.rs = w.th.rs; e.kap = w.th.kap; e.GR = g_rel;
-        if (neg_head) e.GT = g_pos_side; else e.GH = g_pos_side;
-        e.nbase = neg; e.n_neg = C * N; e.cs = w.th.cs; e.GN = g_neg;
-        KGE_TRY(launch_transh_edge_bwd(e, s));
-        return KGE_OK;
-    }
-    if (model == KGE_TRANSD) {
-        const TransdBlock k{C, chunk, N, d_e, gamma, w.td.AP, w.asq, w.td.sig, w.td.u, w.td.Nh, w.bsq, w.td.cj, w.td.PQ};
-        if (int rc = transd_products(k, s)) return rc;
-        if (int rc = transd_neg_bwd(k, dneg, w.td, s)) return rc;
-        TransdBwdArgs e{};
-        e.src = EdgeSrc{pos_side, nullptr, pos_side, nullptr, rel, nullptr}; e.B = B; e.chunk = chunk; e.d_e = d_e; e.neg_head = neg_head;
-        e.GAP = w.td.GAP; e.rs = w.td.rs; e.rc = w.td.rc; e.rc2 = w.td.rc2; e.GR = g_rel;
-        if (neg_head) e.GT = g_pos_side; else e.GH = g_pos_side;
-        e.nbase = neg; e.n_neg = C * N; e.cs = w.td.cs; e.gc = w.td.gc; e.GNp = w.td.GNp; e.GN = g_neg;
-        KGE_TRY(launch_transd_edge_bwd(e, s));
+    if (kge::model_row(model)->own_fwd) {
+        OwnBwd x{}; x.GR = g_rel; x.products = true;
+        (neg_head ? x.GT : x.GH) = g_pos_side;
+        KGE_TRY(kge::own_backward(model, OwnBlock{C, chunk, N, d_e, gamma, w.own.o, neg, nullptr, w.own.PQ}, &w.own,
+                                  EdgeSrc{pos_side, nullptr, pos_side, nullptr, rel, nullptr}, neg_head, dneg, g_neg, x, s));
         return KGE_OK;
     }
     const float *Wuse = dneg;
@@ -751,9 +472,7 @@ struct StepBufs {
     float *Xd; int64_t *iota, *ndids;                                               // RESCAL / TransR
     float *HP, *TP, *Q, *SG, *DQ, *TR1, *TR2, *GP, *gs0, *gs1, *k0, *k1, *TGNp, *gs1p; signed char *Z;   // TransR
     float *row_pos, *row_neg, *reg_ent, *reg_rel, *GNp, *Hc, *Tc, *Rc;
-    float *PW, *PGW, *Pnrm;                                                         // PairRE: w, Gw [B, d_e], candidate norms [C * N]
-    TranshBufs th;                                                                  // TransH
-    TransdBufs td;                                                                  // TransD
+    OwnBufs own;                                                                    // PairRE, TransH, TransD (kge_own_fwd.hpp)
 };
 
 // Ns: the SAMPLED negatives per chunk (kge_batch.N).  copies: room for PREP's dense h / t / r rows (the async pipeline)
@@ -794,9 +513,7 @@ static size_t carve_step(Carver &cv, StepBufs &w, const kge_hparams *hp, int B_,
     if (neg_bwd_lc_supported(hp->model, hp->d_e))         // TransE_l1 / RotatE: GN partials of the shared-pair backward
         w.GNp = cv.f(neg_bwd_lc_partial_floats(hp->model, C, chunk, N, hp->d_e));
     if (copies) { w.Hc = cv.f(B * d_e); w.Tc = cv.f(B * d_e); w.Rc = cv.f(B * d_r); }
-    if (hp->model == KGE_PAIRRE) { w.PW = cv.f(B * d_e); w.PGW = cv.f(B * d_e); w.Pnrm = cv.f(CN); }
-    if (hp->model == KGE_TRANSH) carve_transh(cv, w.th, B, CN, (size_t)N, d_e);
-    if (hp->model == KGE_TRANSD) carve_transd(cv, w.td, B, CN, (size_t)N, d_e);
+    kge::own_carve(hp->model, cv, w.own, w.A, w.asq, w.bsq, w.GA, B, CN, (size_t)N, d_e);
     return cv.off;
 }
 
@@ -843,7 +560,7 @@ int kge_known_neg_mask(const kge_batch *b, const kge_known *known, uint32_t *mas
 // every path decision of one step call, from its inputs alone
 struct StepPlan {
     int N, CN;                 // negative rows per chunk / per batch as the scoring, loss and gradient kernels see them
-    bool nd, reg, pos_row, is_l2, transr, rescal, rescal_rel, sh_dense, pipelined, want4;
+    bool nd, reg, pos_row, is_l2, transr, rescal, own, rescal_rel, sh_dense, pipelined, want4;   // own: an edge forward of its own (kge_own_fwd.hpp)
     bool gemm, fused_loss, transe_fast, qfuse, need_cp, dense_neg, l2g, merged_fwd, merged_pair, fold_loss, dense_bwd;
     bool ew_bwd, lc, fuse_gnred, fold_upd; int ga_parts, fold_nrw;
 };
@@ -858,6 +575,7 @@ static StepPlan plan_step(const kge_hparams *hp, const kge_batch *b, const kge_s
     const int N = p.N = p.nd ? chunk + b->N : b->N; p.CN = C * N;
     p.reg = hp->reg_coef > 0.f && hp->reg_norm > 0; p.pos_row = loss_pos_row(hp->loss_genre, hp->pairwise) != 0; p.want4 = out && out->loss4;
     p.is_l2 = model == KGE_TRANSE_L2; p.transr = model == KGE_TRANSR; p.rescal = model == KGE_RESCAL;
+    p.own = kge::model_row(model)->own_fwd;
     p.rescal_rel = p.rescal && d_e % 4 == 0;         // RESCAL's passes over M per unique relation (16-byte accesses)
     p.sh_dense = sh && (p.transr || p.rescal);       // the two families run on a dense block of the batch's entity rows (Step::setup)
     p.pipelined = phases != PH_ALL && !(phases & PH_STRICT);      // the async pipeline (kge_step_async)
@@ -945,12 +663,7 @@ struct Step {
     TransRArgs tr; EdgeFwdArgs ef; GemmArgs g; NegArgs na;
     int setup(void *ws, size_t ws_bytes), phase_prep(), prep_transr(), prep_rescal(), phase_fwd(), fwd_gemm(), phase_bwd(), bwd_neg_gemm();
     int bwd_transr(), bwd_rescal(), phase_update(); void fill_score(), fill_step_loss(LossArgs &la);
-    TranshBlock transh_block() const {
-        return TranshBlock{b->C, b->chunk, p.N, hp->d_e, hp->gamma, w.th.AW, w.asq, w.th.cw, w.Bn, nullptr, w.bsq, w.th.PQ};
-    }
-    TransdBlock transd_block() const {
-        return TransdBlock{b->C, b->chunk, p.N, hp->d_e, hp->gamma, w.td.AP, w.asq, w.td.sig, w.td.u, w.td.Nh, w.bsq, w.td.cj, w.td.PQ};
-    }
+    OwnBlock own_block() const { return OwnBlock{b->C, b->chunk, p.N, hp->d_e, hp->gamma, w.own.o, w.Bn, nullptr, w.own.PQ}; }
 };
 
 // argument checks, then the plan, the workspace and the argument blocks every phase shares
@@ -1123,25 +836,9 @@ int Step::phase_prep() {
     ef.dpos = w.dP; ef.row_pos = p.want4 ? w.row_pos : nullptr; ef.acc = acc;
     if (p.transr) return prep_transr();
     if (p.rescal) return prep_rescal();
-    if (hp->model == KGE_PAIRRE) {     // own edge forward: P, (a, w), the dense negative rows and their norms; the loss kernel takes the positive part
-        PairreEdgeArgs e; fill_pairre_edge(e, src, b->B, hp->d_e, b->neg_head, hp->gamma, P, w.A, w.PW);
-        e.nbase = ef.nbase; e.nidx = ef.nidx; e.n_neg = ef.n_neg; e.nd_own = ef.nd_own; e.nd_chunk = ef.nd_chunk; e.nd_Ns = ef.nd_Ns;
-        e.Bn = w.Bn; e.nrm = w.Pnrm;
-        KGE_TRY(launch_pairre_edge_fwd(e, s));
-        return KGE_OK;
-    }
-    if (hp->model == KGE_TRANSH) {     // own edge forward: P, the stacked (a, w^), the dense negative rows and their |n|^2; the loss kernel takes the positive part
-        TranshEdgeArgs e; fill_transh_edge(e, src, b->B, b->chunk, hp->d_e, b->neg_head, hp->gamma, P, w.th.AW, w.asq, w.th.cw);
-        e.nbase = ef.nbase; e.nidx = ef.nidx; e.n_neg = ef.n_neg; e.nd_own = ef.nd_own; e.nd_chunk = ef.nd_chunk; e.nd_Ns = ef.nd_Ns;
-        e.Bn = w.Bn; e.beta = w.bsq;
-        KGE_TRY(launch_transh_edge_fwd(e, s));
-        return KGE_OK;
-    }
-    if (hp->model == KGE_TRANSD) {     // own edge forward: P, the stacked (a, rho), the dense negative rows, their first halves and scalars
-        TransdEdgeArgs e; fill_transd_edge(e, src, b->B, b->chunk, hp->d_e, b->neg_head, hp->gamma, P, w.td.AP, w.asq, w.td.sig, w.td.u);
-        e.nbase = ef.nbase; e.nidx = ef.nidx; e.n_neg = ef.n_neg; e.nd_own = ef.nd_own; e.nd_chunk = ef.nd_chunk; e.nd_Ns = ef.nd_Ns;
-        e.Bn = w.Bn; e.Nh = w.td.Nh; e.beta = w.bsq; e.cj = w.td.cj;
-        KGE_TRY(launch_transd_edge_fwd(e, s));
+    if (p.own) {       // own edge forward: P, the operand, the dense negative rows and their scalars; the loss kernel takes the positive part
+        const OwnCands cn{ef.nbase, ef.nidx, ef.n_neg, ef.nd_own, ef.nd_chunk, ef.nd_Ns, w.Bn};
+        KGE_TRY(kge::own_prepare(hp->model, src, b->B, b->chunk, hp->d_e, b->neg_head, hp->gamma, P, w.own.o, &cn, s));
         return KGE_OK;
     }
     if (c.build_prep) { *c.build_prep = ef; return KGE_OK; }
@@ -1205,14 +902,8 @@ int Step::phase_fwd() {
             nf.xbase = tb->ent; nf.xidx = b->neg_head ? b->t_gid : b->h_gid; nf.rbase = tb->rel; nf.ridx = b->rel_ids;
             nf.asign = b->neg_head ? -1.f : 1.f;
             KGE_TRY(launch_neg_fwd_bcast_with_edge(nf, ef, s));
-        } else if (hp->model == KGE_PAIRRE) {
-            PairreNegArgs n; fill_pairre_neg(n, b->C, b->chunk, p.N, hp->d_e, hp->gamma, w.A, w.PW, w.Bn, nullptr, w.Pnrm);
-            n.S = w.S;
-            KGE_TRY(launch_pairre_neg_fwd(n, s));
-        } else if (hp->model == KGE_TRANSH) {
-            if (int rc = transh_scores(transh_block(), w.S, s)) return rc;
-        } else if (hp->model == KGE_TRANSD) {
-            if (int rc = transd_scores(transd_block(), w.S, s)) return rc;
+        } else if (p.own) {
+            KGE_TRY(kge::own_scores(hp->model, own_block(), w.S, s));
         } else KGE_TRY(launch_neg_fwd_pair(na, s));
     }
     if (p.fused_loss || p.fold_loss) return KGE_OK;  // no stand-alone loss kernel: the backward GEMM / the forward tiles run it
@@ -1220,7 +911,7 @@ int Step::phase_fwd() {
     LossArgs la; fill_step_loss(la);
     la.row_pos = p.want4 ? w.row_pos : nullptr;
     if (p.merged_fwd && p.is_l2) { la.l2_raw = 1; la.l2_chunk = b->chunk; la.asq = w.asq; la.bsq = w.bsq; }
-    la.skip_pos = (p.pos_row || p.rescal || p.transr || hp->model == KGE_PAIRRE || hp->model == KGE_TRANSH || hp->model == KGE_TRANSD) ? 0 : 1; la.diag_chunk = p.nd ? b->chunk : 0;  // RESCAL / TransR: no edge_fwd -> positive part here
+    la.skip_pos = (p.pos_row || p.rescal || p.transr || p.own) ? 0 : 1; la.diag_chunk = p.nd ? b->chunk : 0;  // RESCAL / TransR / own edge forward: no edge_fwd -> positive part here
     KGE_TRY(launch_loss(la, s, c.known ? c.known_mask : nullptr));
     return KGE_OK;
 }
@@ -1319,43 +1010,9 @@ int Step::bwd_rescal() {
 
 int Step::phase_bwd() {
     if (p.transr) return bwd_transr();
-    if (hp->model == KGE_PAIRRE) {
-        PairreNegArgs n; fill_pairre_neg(n, b->C, b->chunk, p.N, hp->d_e, hp->gamma, w.A, w.PW, w.Bn, nullptr, w.Pnrm);
-        n.G = w.S; n.GA = w.GA; n.GW = w.PGW; n.GN = GN;
-        n.reg_coef = (p.reg && !p.nd) ? hp->reg_coef : 0.f; n.reg_norm = hp->reg_norm;   // nd: the update adds it (sampled rows only)
-        KGE_TRY(launch_pairre_neg_bwd(n, s));
-        PairreBwdArgs e{};
-        e.src = src; e.B = b->B; e.d_e = hp->d_e; e.neg_head = b->neg_head; e.dpos = w.dP; e.GA = w.GA; e.GW = w.PGW;
-        e.reg_coef = p.reg ? hp->reg_coef : 0.f; e.reg_norm = hp->reg_norm;
-        e.GH = w.GH; e.GT = w.GT; e.GR = GR;
-        if (p.nd) { e.GNd = GN; e.nd_chunk = b->chunk; e.nd_Np = p.N; }     // in-batch negative rows -> positive trace
-        KGE_TRY(launch_pairre_edge_bwd(e, s));
-        return KGE_OK;
-    }
-    if (hp->model == KGE_TRANSH) {
-        if (int rc = transh_neg_bwd(transh_block(), w.S, w.th.PQc, w.th.rs, w.th.kap, w.th.cs, w.th.GAW, GN, s)) return rc;
-        TranshBwdArgs e{};
-        e.src = src; e.B = b->B; e.chunk = b->chunk; e.d_e = hp->d_e; e.neg_head = b->neg_head; e.dpos = w.dP;
-        e.GAW = w.th.GAW; e.rs = w.th.rs; e.kap = w.th.kap;
-        e.reg_coef = p.reg ? hp->reg_coef : 0.f; e.reg_norm = hp->reg_norm;
-        e.GH = w.GH; e.GT = w.GT; e.GR = GR;
-        e.nbase = w.Bn; e.n_neg = p.CN; e.cs = w.th.cs; e.GN = GN;
-        e.n_reg_coef = (p.reg && !p.nd) ? hp->reg_coef : 0.f;           // nd: the update adds it (sampled rows only)
-        if (p.nd) { e.GNd = GN; e.nd_chunk = b->chunk; e.nd_Np = p.N; }     // in-batch negative rows -> positive trace
-        KGE_TRY(launch_transh_edge_bwd(e, s));
-        return KGE_OK;
-    }
-    if (hp->model == KGE_TRANSD) {
-        if (int rc = transd_neg_bwd(transd_block(), w.S, w.td, s)) return rc;
-        TransdBwdArgs e{};
-        e.src = src; e.B = b->B; e.chunk = b->chunk; e.d_e = hp->d_e; e.neg_head = b->neg_head; e.dpos = w.dP;
-        e.GAP = w.td.GAP; e.rs = w.td.rs; e.rc = w.td.rc; e.rc2 = w.td.rc2;
-        e.reg_coef = p.reg ? hp->reg_coef : 0.f; e.reg_norm = hp->reg_norm;
-        e.GH = w.GH; e.GT = w.GT; e.GR = GR;
-        e.nbase = w.Bn; e.n_neg = p.CN; e.cs = w.td.cs; e.gc = w.td.gc; e.GNp = w.td.GNp; e.GN = GN;
-        e.n_reg_coef = (p.reg && !p.nd) ? hp->reg_coef : 0.f;           // nd: the update adds it (sampled rows only)
-        if (p.nd) { e.GNd = GN; e.nd_chunk = b->chunk; e.nd_Np = p.N; }     // in-batch negative rows -> positive trace
-        KGE_TRY(launch_transd_edge_bwd(e, s));
+    if (p.own) {       // nd: the update adds the sampled rows' regulariser, and the in-batch rows' gradient joins the positive trace
+        const OwnBwd x{w.dP, p.reg ? hp->reg_coef : 0.f, hp->reg_norm, (p.reg && !p.nd) ? hp->reg_coef : 0.f, p.nd, w.GH, w.GT, GR, false};
+        KGE_TRY(kge::own_backward(hp->model, own_block(), &w.own, src, b->neg_head, w.S, GN, x, s));
         return KGE_OK;
     }
     if (p.gemm) {
@@ -1483,9 +1140,7 @@ size_t kge_sampler_tail_scratch_bytes(int B, int C, int N, int64_t n_ent) {
 static int step_sampling(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
                          size_t ws_bytes, const kge_sampler_job *job, StepCall c, void *stream) {
     if (!job) return run_step(hp, tb, b, out, ws, ws_bytes, stream, c);
-    if (hp && hp->model == KGE_PAIRRE) return no_pairre("kge_step_fused_sampling");
-    if (hp && hp->model == KGE_TRANSH) return no_transh("kge_step_fused_sampling");
-    if (hp && hp->model == KGE_TRANSD) return no_transd("kge_step_fused_sampling");
+    if (hp) if (int rc = closed(kge::E_STEP_FUSED_SAMPLING, hp->model, "kge_step_fused_sampling")) return rc;
     if (!job->heads || !job->rels || !job->tails || !job->state || !job->slot || !job->scratch || job->n_train <= 0 || job->n_ent <= 0 ||
         job->B <= 0 || job->C <= 0 || job->chunk <= 0 || job->N <= 0 || job->C * job->chunk != job->B || job->k < 0 || job->advance < 0)
         return fail(KGE_ERR_ARG, "kge_step_fused_sampling: bad sampler job");
@@ -1551,10 +1206,7 @@ size_t kge_step_async_workspace_bytes(const kge_hparams *hp, int B, int C, int c
 int kge_step_async(kge_pipe *p, const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_batch *b_next,
                    const kge_step_out *out, void *ws, size_t ws_bytes, void *stream) {
     if (!p || !hp || !tb || !b || !ws) return fail(KGE_ERR_ARG, "kge_step_async: null argument");
-    if (hp->model == KGE_QUATE) return no_quate("kge_step_async");
-    if (hp->model == KGE_PAIRRE) return no_pairre("kge_step_async");
-    if (hp->model == KGE_TRANSH) return no_transh("kge_step_async");
-    if (hp->model == KGE_TRANSD) return no_transd("kge_step_async");
+    if (int rc = closed(kge::E_STEP_ASYNC, hp->model, "kge_step_async")) return rc;
     const size_t half = (ws_bytes / 2) & ~(size_t)255;
     void *wsp = (char *)ws + (size_t)p->parity * half;
     void *wsn = (char *)ws + (size_t)(p->parity ^ 1) * half;
@@ -1687,10 +1339,7 @@ int kge_step_optim(const kge_hparams *hp, const kge_optim *opt, const kge_tables
 
 int kge_step_grads(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, const kge_emit *emit,
                    void *ws, size_t ws_bytes, void *stream) {
-    if (hp && hp->model == KGE_QUATE) return no_quate("kge_step_grads");
-    if (hp && hp->model == KGE_PAIRRE) return no_pairre("kge_step_grads");
-    if (hp && hp->model == KGE_TRANSH) return no_transh("kge_step_grads");
-    if (hp && hp->model == KGE_TRANSD) return no_transd("kge_step_grads");
+    if (hp) if (int rc = closed(kge::E_STEP_GRADS, hp->model, "kge_step_grads")) return rc;
     if (!emit || !emit->g0 || (!emit->msg_rows && (!emit->gs0 || !emit->g1 || !emit->gs1)))
         return fail(KGE_ERR_ARG, "kge_step_grads: emit buffers g0/gs0/g1/gs1 are required (packed messages: g0 + msg_rows)");
     if ((emit->gr == nullptr) != (emit->gsr == nullptr))
@@ -1725,22 +1374,12 @@ static int rank_pos_side(int model, int neg_head, const float *ent, const float 
             if (!neg_head) { m.y2 = ent; m.y2idx = h; m.r2 = A; }
         }
         KGE_TRY(launch_rescal_matvec(m, s));
-    } else if (model == KGE_PAIRRE) {                   // the pair (a, w) lives in the A and RV entries
-        PairreEdgeArgs e; fill_pairre_edge(e, EdgeSrc{ent, h, ent, t, rel, r}, rows, d_e, neg_head, gamma, P, A, RV);
-        KGE_TRY(launch_pairre_edge_fwd(e, s));
-    } else if (model == KGE_TRANSH) {
-        // th_chunk == 0 (kge_rank_eval): a in the A entry, w^ in the RV entry; else A is the stacked operand of chunks of th_chunk
-        // rows.  |a|^2 in asq, w^ . a in the first `rows` floats of the THP entry (TransR's, free here)
-        TranshEdgeArgs e; fill_transh_edge(e, EdgeSrc{ent, h, ent, t, rel, r}, rows, th_chunk ? th_chunk : rows, d_e, neg_head, gamma, P, A, asq, w.THP);
-        if (!th_chunk) e.W = RV;
-        KGE_TRY(launch_transh_edge_fwd(e, s));
-    } else if (model == KGE_TRANSD) {
-        // as TransH: a in the A entry and rho in the RV entry (kge_rank_eval), or the stacked operand in A.  |a|^2 in asq, |rho|^2 and
-        // a . rho in the first `rows` floats of the THP and TTP entries
-        TransdEdgeArgs e; fill_transd_edge(e, EdgeSrc{ent, h, ent, t, rel, r}, rows, th_chunk ? th_chunk : rows, d_e, neg_head, gamma, P, A, asq,
-                                           w.THP, w.TTP);
-        if (!th_chunk) e.W = RV;
-        KGE_TRY(launch_transd_edge_fwd(e, s));
+    } else if (kge::model_row(model)->own_fwd) {
+        // th_chunk == 0 (kge_rank_eval): a in the A entry, the second vector (w, w^, rho) in the RV entry; else A is the stacked operand
+        // of chunks of th_chunk rows (PairRE: the pair always lives in A and RV).  |a|^2 in asq; the rows' other scalars (TransH: w^ . a;
+        // TransD: |rho|^2, a . rho) in the first `rows` floats of the THP and TTP entries (TransR's, free here)
+        KGE_TRY(kge::own_prepare(model, EdgeSrc{ent, h, ent, t, rel, r}, rows, th_chunk, d_e, neg_head, gamma, P,
+                                 OwnOperand{A, RV, asq, w.THP, w.TTP, nullptr, nullptr, nullptr}, nullptr, s));
     } else {
         EdgeFwdArgs ef;
         fill_edge(ef, EdgeSrc{ent, h, ent, t, rel, r}, model, rows, d_e, d_r, neg_head, gamma, rot_div);
@@ -1778,10 +1417,10 @@ static int rank_eval_impl(int model, int neg_head, const float *qent, const floa
                           const int64_t *h, const int64_t *r, const int64_t *t, int64_t E, int d_e, int d_r, float gamma, float emb_init,
                           const int64_t *cand, int64_t N, const int64_t *filt_ptr, const int64_t *filt_ids, int Eb, int32_t *ranks,
                           float *pos_score_out, void *ws, size_t ws_bytes, unsigned flags, hipStream_t s) {
-    // TransD keeps TWO scalars per candidate, [beta | c], in the bsq entry: its workspace is the one of 2 N candidates (include/kge_hip.h)
+    // (TransD keeps TWO scalars per candidate, [beta | c], in the bsq entry: the workspace of 2 N candidates, include/kge_hip.h)
     const bool td = model == KGE_TRANSD;
     Carver cv(ws, ws_bytes); RankBufs w;
-    const size_t need = carve_rank(cv, w, Eb, td ? 2 * N : N, d_e);
+    const size_t need = carve_rank(cv, w, Eb, kge::model_row(model)->cand_factor * N, d_e);
     if (need > ws_bytes) return fail(KGE_ERR_WORKSPACE, "kge_rank_eval: workspace too small (%zu < %zu)", ws_bytes, need);
     float *A = w.A, *asq = w.asq, *bsq = w.bsq, *S = w.S;
     const bool gemm = use_mfma(model, d_e, (int)N, flags);
@@ -1793,10 +1432,10 @@ static int rank_eval_impl(int model, int neg_head, const float *qent, const floa
         nb.bsq = bsq;
         KGE_TRY(launch_edge_fwd(nb, s));
     }
-    if (model == KGE_PAIRRE) KGE_TRY(pairre_norms(cent, cand, N, d_e, bsq, s));       // |x| of every candidate row, once (the bsq entry)
+    // the scalars of every candidate row, once: PairRE |x|, TransH |n|^2, TransD |n|^2 and m . n (the bsq entry)
+    const OwnOperand cands{nullptr, nullptr, nullptr, nullptr, nullptr, bsq, bsq + N, nullptr};
+    if (kge::model_row(model)->own_fwd) KGE_TRY(kge::own_cand_rows(model, cent, cand, N, d_e, cands, s));
     const bool th = model == KGE_TRANSH;
-    if (th) KGE_TRY(transh_norms(cent, cand, N, d_e, bsq, s));                        // |n|^2 of every candidate row, once
-    if (td) KGE_TRY(transd_cands(cent, cand, N, d_e, bsq, bsq + N, nullptr, s));       // |n|^2 and m . n of every candidate row, once
     for (int64_t e0 = 0; e0 < E; e0 += Eb) {
         const int rows = (int)((E - e0) < Eb ? (E - e0) : Eb);
         float *P = pos_score_out ? pos_score_out + e0 : w.P;
@@ -1830,9 +1469,7 @@ static int rank_eval_impl(int model, int neg_head, const float *qent, const floa
             g.S = S; g.asq = asq; g.bsq = bsq;
             KGE_TRY(launch_neg_fwd_gemm(g, s));
         } else if (model == KGE_PAIRRE) {
-            PairreNegArgs n; fill_pairre_neg(n, 1, rows, (int)N, d_e, gamma, A, w.RV, cent, cand, bsq);
-            n.S = S;
-            KGE_TRY(launch_pairre_neg_fwd(n, s));
+            KGE_TRY(kge::own_scores(model, OwnBlock{1, rows, (int)N, d_e, gamma, OwnOperand{A, w.RV, nullptr, nullptr, nullptr, bsq}, cent, cand, nullptr}, S, s));
         } else {
             NegArgs na; fill_pair(na, model, 1, rows, (int)N, d_e, gamma, A, cent, cand);
             na.S = S;
@@ -1874,10 +1511,7 @@ int kge_rank_eval_split(int model, int neg_head, const float *qent, int64_t n_qe
                         float gamma, float emb_init, const int64_t *cand, int64_t n_cand, const int64_t *filt_ptr, const int64_t *filt_ids,
                         int Eb, int32_t *ranks, float *pos_score_out, void *ws, size_t ws_bytes, unsigned flags, void *stream) {
     if (int rc = check_model(model, d_e, d_r)) return rc;
-    if (model == KGE_QUATE) return no_quate("kge_rank_eval_split");
-    if (model == KGE_PAIRRE) return no_pairre("kge_rank_eval_split");
-    if (model == KGE_TRANSH) return no_transh("kge_rank_eval_split");
-    if (model == KGE_TRANSD) return no_transd("kge_rank_eval_split");
+    if (int rc = closed(kge::E_RANK_EVAL_SPLIT, model, "kge_rank_eval_split")) return rc;
     if (model == KGE_TRANSR && !proj)
         return fail(KGE_ERR_ARG, "kge_rank_eval_split: TransR needs the projection table");
     if (n_qent <= 0 || n_cent < 0) return fail(KGE_ERR_ARG, "kge_rank_eval_split: bad argument");
@@ -1899,12 +1533,13 @@ int kge_rank_eval_split(int model, int neg_head, const float *qent, int64_t n_qe
 // ---- chunked-candidate ranking (kge_rank_chunk.hip) ----
 // one block of whole chunks: pos-side vectors / norms / positive scores of its rows, the candidates' norms (TransE_l2), and - for the
 // score-block route only, but the layout does not depend on the flags - the id list and the score block
-struct ChunkBufs : TransRRows { float *A, *asq, *P, *RV, *bsq_own, *bsq_c, *S, *Pnrm, *TPQ, *TNh; int64_t *ids; };
+struct ChunkBufs : TransRRows { float *A, *asq, *P, *RV, *bsq_own, *bsq_c, *S, *Pnrm, *TPQ, *TNh; int64_t *ids; size_t arow; };
 static size_t carve_chunked(Carver &cv, ChunkBufs &w, int model, int64_t rows, int chunk, int64_t n_cand, int self_cand, int d_e, int d_r) {
     const size_t nch = (size_t)((rows + chunk - 1) / chunk), R = nch * (size_t)chunk;
     const size_t ncols = (size_t)n_cand + (self_cand ? (size_t)chunk : 0);
     const bool th = model == KGE_TRANSH, td = model == KGE_TRANSD;       // (TransD: the stacked (a, rho) is 2 R rows of d_e / 2)
-    w.A = cv.f((th ? 2 : 1) * R * d_e); w.asq = cv.f(R); w.P = cv.f(R);         // (TransH: the stacked operand (a, w^))
+    w.arow = (th ? 2 : 1) * (size_t)d_e;                                        // floats per test row of the A entry (TransH: the stacked operand (a, w^))
+    w.A = cv.f(R * w.arow); w.asq = cv.f(R); w.P = cv.f(R);
     w.RV = cv.f(model == KGE_RESCAL || model == KGE_PAIRRE ? R * d_e : 0);      // V = M t (RESCAL); w of the pair (PairRE)
     carve_transr_rows(cv, w, model == KGE_TRANSR ? R * (size_t)d_r : (th || td) ? R : 0);   // (TransH: w^ . a in the first entry; TransD: |rho|^2, a . rho)
     w.bsq_own = cv.f(R); w.bsq_c = cv.f(nch * (size_t)n_cand);
@@ -1974,7 +1609,7 @@ int kge_rank_eval_chunked(int model, int neg_head, const float *ent, int64_t n_e
         const int rows = (int)std::min<int64_t>((int64_t)nch * chunk, E - e0);
         float *P = pos_score_out ? pos_score_out + e0 : w.P;
         KGE_TRY(rank_pos_side(model, neg_head, ent, rel, proj, h + e0, r + e0, t + e0, rows, d_e, d_r, gamma, rot_div, P, w.A,
-                              (l2g || model == KGE_TRANSH || model == KGE_TRANSD) ? w.asq : nullptr, w.RV, w, s, chunk));
+                              (l2g || kge::model_row(model)->own_fwd) ? w.asq : nullptr, w.RV, w, s, chunk));
         if (gemm) {
             if (l2g && (!shared || self_cand)) {
                 ChunkCands c1 = cc; if (shared) c1.cand = nullptr;
@@ -2006,25 +1641,14 @@ int kge_rank_eval_chunked(int model, int neg_head, const float *ent, int64_t n_e
                 tr.P = P + row_off; tr.S = S; tr.Z = nullptr;
                 KGE_TRY(launch_transr_pos(tr, s));
                 KGE_TRY(launch_transr_fwd(tr, s));
-            } else if (model == KGE_PAIRRE) {
-                float *nrm = w.Pnrm + (gidx == 0 ? 0 : (int64_t)nfull * ncols_full);
-                KGE_TRY(pairre_norms(ent, ids, (int64_t)C * ncols, d_e, nrm, s));
-                PairreNegArgs n; fill_pairre_neg(n, C, m, (int)ncols, d_e, gamma, w.A + row_off * d_e, w.RV + row_off * d_e, ent, ids, nrm);
-                n.S = S;
-                KGE_TRY(launch_pairre_neg_fwd(n, s));
-            } else if (model == KGE_TRANSH) {       // (the stacked operand and the product block: two rows per test row)
-                float *beta = w.Pnrm + (gidx == 0 ? 0 : (int64_t)nfull * ncols_full);
-                KGE_TRY(transh_norms(ent, ids, (int64_t)C * ncols, d_e, beta, s));
-                const TranshBlock k{C, m, (int)ncols, d_e, gamma, w.A + 2 * row_off * d_e, w.asq + row_off, w.THP + row_off, ent, ids, beta,
-                                    w.TPQ + 2 * row_off * ncols_full};
-                if (int rc = transh_scores(k, S, s)) return rc;
-            } else if (model == KGE_TRANSD) {       // TransH's route; the candidate scalars and first halves per position of the lists
-                const int64_t poff = gidx == 0 ? 0 : (int64_t)nfull * ncols_full, k2 = d_e / 2;
-                float *beta = w.Pnrm + poff, *cj = w.Pnrm + nchb * ncols_full + poff, *Nh = w.TNh + poff * k2;
-                KGE_TRY(transd_cands(ent, ids, (int64_t)C * ncols, d_e, beta, cj, Nh, s));
-                const TransdBlock k{C, m, (int)ncols, d_e, gamma, w.A + row_off * d_e, w.asq + row_off, w.THP + row_off, w.TTP + row_off, Nh, beta, cj,
-                                    w.TPQ + 2 * row_off * ncols_full};
-                if (int rc = transd_scores(k, S, s)) return rc;
+            } else if (kge::model_row(model)->own_fwd) {
+                // the candidate scalars (TransD: [beta | c] and the first halves) per position of the lists; the stacked operand and
+                // the product block: two rows per test row
+                const int64_t poff = gidx == 0 ? 0 : (int64_t)nfull * ncols_full;
+                const OwnOperand o{w.A + row_off * w.arow, w.RV + row_off * d_e, w.asq + row_off, w.THP + row_off, w.TTP + row_off,
+                                   w.Pnrm + poff, w.TNh ? w.Pnrm + nchb * ncols_full + poff : nullptr, w.TNh ? w.TNh + poff * (d_e / 2) : nullptr};
+                KGE_TRY(kge::own_cand_rows(model, ent, ids, (int64_t)C * ncols, d_e, o, s));
+                KGE_TRY(kge::own_scores(model, OwnBlock{C, m, (int)ncols, d_e, gamma, o, ent, ids, w.TPQ ? w.TPQ + 2 * row_off * ncols_full : nullptr}, S, s));
             } else {
                 NegArgs na; fill_pair(na, model, C, m, (int)ncols, d_e, gamma, w.A + row_off * d_e, ent, ids);
                 na.S = S;
@@ -2053,8 +1677,7 @@ static size_t carve_rank_rel(Carver &cv, RelBufs &w, int model, int Eb, int64_t 
 
 size_t kge_rank_rel_workspace_bytes(int model, int Eb, int64_t n_rel, int d_e, int d_r) {
     if (Eb <= 0 || n_rel <= 0 || n_rel > 0x7fffffff || check_model(model, d_e, d_r) != KGE_OK) return 0;
-    // ids up to KGE_TRANSR only: a QuatE call takes the DistMult layout followed by the normalised relation table (include/kge_hip.h)
-    if (model == KGE_QUATE || model == KGE_PAIRRE || model == KGE_TRANSH || model == KGE_TRANSD) return 0;
+    if (!kge::model_row(model)->rel_ws_sized) return 0;
     Carver cv; RelBufs w; return carve_rank_rel(cv, w, model, Eb, n_rel, d_e, d_r);
 }
 
@@ -2063,9 +1686,7 @@ int kge_rank_rel_eval(int model, const float *ent, int64_t n_ent, const float *r
                       float gamma, float emb_init, const int64_t *filt_ptr, const int64_t *filt_ids, int Eb,
                       int32_t *ranks, float *pos_score_out, void *ws, size_t ws_bytes, unsigned flags, void *stream) {
     if (int rc = check_model(model, d_e, d_r)) return rc;
-    if (model == KGE_PAIRRE) return no_pairre("kge_rank_rel_eval");
-    if (model == KGE_TRANSH) return no_transh("kge_rank_rel_eval");
-    if (model == KGE_TRANSD) return no_transd("kge_rank_rel_eval");
+    if (int rc = closed(kge::E_RANK_REL_EVAL, model, "kge_rank_rel_eval")) return rc;
     if (model == KGE_TRANSR && !proj) return fail(KGE_ERR_ARG, "kge_rank_rel_eval: TransR needs the projection table");
     if (!ent || !rel || n_ent <= 0 || n_rel <= 0 || E < 0 || (E && (!h || !r || !t || !ranks)) || !ws)
         return fail(KGE_ERR_ARG, "kge_rank_rel_eval: bad argument (a null pointer or a count that is not positive)");
@@ -2141,10 +1762,7 @@ int kge_rank_rel_eval(int model, const float *ent, int64_t n_ent, const float *r
 int kge_step_sharded(const kge_hparams *hp, const kge_shards *sh, const kge_batch *b,
                      const kge_step_out *out, void *ws, size_t ws_bytes, void *stream) {
     if (!sh) return fail(KGE_ERR_ARG, "kge_step_sharded: null shard map");
-    if (hp && hp->model == KGE_QUATE) return no_quate("kge_step_sharded");
-    if (hp && hp->model == KGE_PAIRRE) return no_pairre("kge_step_sharded");
-    if (hp && hp->model == KGE_TRANSH) return no_transh("kge_step_sharded");
-    if (hp && hp->model == KGE_TRANSD) return no_transd("kge_step_sharded");
+    if (hp) if (int rc = closed(kge::E_STEP_SHARDED, hp->model, "kge_step_sharded")) return rc;
     // (RESCAL's relation "row" is a d_e x d_e matrix streamed by its own kernels: only the entity width is bounded)
     if (hp && (hp->d_e % 4 || hp->d_e > 1024 || (hp->model != KGE_RESCAL && (hp->d_r % 4 || hp->d_r > 1024))))
         return fail(KGE_ERR_ARG, "kge_step_sharded: row widths must be multiples of 4 and <= 1024 floats");

@@ -23,6 +23,8 @@
 #include <cstdio>
 #include <type_traits>
 #include "kge_tile_gemm.hpp"
+#include "kge_models.hpp"
+#include "kge_own_fwd.hpp"
 
 using namespace kge;
 
@@ -582,21 +584,11 @@ int merge_tree(int64_t G, int64_t L, int K, const float *is, const int64_t *io, 
 int kge_fail(int code, const char *msg);
 static int tk_fail(const char *msg) { return kge_fail(KGE_ERR_ARG, msg); }
 
-static int tk_check_model(int model, int d_e, int d_r) {
-    bool ok;
-    if (model == KGE_RESCAL) ok = d_e <= 1024 && (int64_t)d_r == (int64_t)d_e * d_e;
-    else if (model == KGE_COMPLEX || model == KGE_SIMPLE) ok = d_e % 2 == 0 && d_r == d_e;
-    else if (model == KGE_ROTATE) ok = d_e % 2 == 0 && d_r == d_e / 2;
-    else if (model == KGE_QUATE) ok = d_e % 4 == 0 && d_r == d_e;
-    else if (model == KGE_PAIRRE) ok = (int64_t)d_r == 2 * (int64_t)d_e;
-    else if (model == KGE_TRANSH) ok = d_e >= 4 && d_e % 4 == 0 && (int64_t)d_r == 2 * (int64_t)d_e;
-    else if (model == KGE_TRANSD) ok = d_e >= 8 && d_e % 8 == 0 && d_r == d_e;
-    else ok = d_r == d_e;
-    if (ok) return KGE_OK;
+static int tk_check_model(const kge::ModelRow &m, int d_e, int d_r) {
+    if (kge::widths_ok(m, d_e, d_r)) return KGE_OK;
     char msg[160];
-    if (model == KGE_TRANSD) snprintf(msg, sizeof(msg), "kge_topk_select: TransD needs d_e == d_r and d_e %% 8 == 0, rows [x | x_p] (got %d, %d)", d_e, d_r);
-    else if (model == KGE_TRANSH) snprintf(msg, sizeof(msg), "kge_topk_select: TransH needs d_e >= 4, d_e %% 4 == 0 and d_r == 2 * d_e (got %d, %d)", d_e, d_r);
-    else snprintf(msg, sizeof(msg), "kge_topk_select: dims d_e=%d d_r=%d do not fit model %d", d_e, d_r, model);
+    if (m.topk_msg) snprintf(msg, sizeof(msg), m.topk_msg, d_e, d_r);
+    else snprintf(msg, sizeof(msg), "kge_topk_select: dims d_e=%d d_r=%d do not fit model %d", d_e, d_r, m.id);
     return tk_fail(msg);
 }
 
@@ -615,7 +607,8 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
     char msg[256];
     if (filt_ptr && !filt_ids) return tk_fail("kge_topk_select_filtered: filt_ptr given without filt_ids");
     const bool sim = func >= KGE_SIM_COSINE && func <= KGE_SIM_EXT_JACCARD;
-    if (!sim && (func < KGE_TRANSE_L1 || (func > KGE_RESCAL && func != KGE_QUATE && func != KGE_PAIRRE && func != KGE_TRANSH && func != KGE_TRANSD))) {
+    const kge::ModelRow *m = sim ? nullptr : kge::model_row(func);
+    if (!sim && (!m || (m->closed & kge::E_TOPK))) {
         snprintf(msg, sizeof(msg), "kge_topk_select: unknown score function %d (TransR has no inference path)", func);
         return tk_fail(msg);
     }
@@ -635,7 +628,7 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
     // TransD: [a block | rho block | sigma | u] (2 k + 2 = d_e + 2 floats per row) and TWO scalars per candidate, [beta | c]: the bn
     // entry of a workspace sized for 2 N candidates (nothing else of the layout depends on the candidate count)
     const bool td = func == KGE_TRANSD;
-    TkWs w = carve(ws, rows, td ? 2 * N : N, func == KGE_PAIRRE ? 2 * D : func == KGE_TRANSH ? 2 * D + 1 : td ? D + 2 : D, K);
+    TkWs w = carve(ws, rows, m ? m->cand_factor * N : N, m ? m->topk_row_mul * D + m->topk_row_add : D, K);
     if (w.need > ws_bytes) {
         snprintf(msg, sizeof(msg), "kge_topk_select: workspace too small (%zu < %zu)", ws_bytes, w.need);
         return kge_fail(KGE_ERR_WORKSPACE, msg);
@@ -653,7 +646,7 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
         else { acc = mf ? ACC_MFMA : ACC_DOT; epi = func == KGE_SIM_COSINE ? EPI_COS : func == KGE_SIM_EXT_JACCARD ? EPI_JAC : EPI_RAW; }
         gamma = 0.f;
     } else {
-        if (int rc = tk_check_model(func, d_e, d_r)) return rc;
+        if (int rc = tk_check_model(*m, d_e, d_r)) return rc;
         if (func == KGE_RESCAL) {
             RescalMatvecArgs m{};
             m.B = rows; m.D = d_e; m.rel = rel; m.ridx = r;
@@ -661,27 +654,14 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
             if (side) { m.y1 = ent; m.y1idx = t; m.r1 = w.A; }
             else { m.z1 = ent; m.z1idx = h; m.c1 = w.A; }
             if (int rc = launch_rescal_matvec(m, st)) return rc;
-        } else if (func == KGE_PAIRRE) {
-            PairreEdgeArgs e{};
-            e.src = EdgeSrc{ent, h, ent, t, rel, r};
-            e.B = rows; e.d_e = d_e; e.neg_head = side; e.gamma = gamma; e.A = w.A; e.W = w.A + (size_t)rows * D;
-            e.nbase = ent; e.nidx = cand; e.n_neg = (int)N; e.nrm = w.bn;
-            if (int rc = launch_pairre_edge_fwd(e, st)) return rc;
-        } else if (func == KGE_TRANSH) {
-            TranshEdgeArgs e{};
-            e.src = EdgeSrc{ent, h, ent, t, rel, r};
-            e.B = rows; e.chunk = rows; e.d_e = d_e; e.neg_head = side; e.gamma = gamma;
-            e.AW = w.A; e.alpha = w.an; e.cw = w.A + 2 * (size_t)rows * D;
-            e.nbase = ent; e.nidx = cand; e.n_neg = (int)N; e.beta = w.bn;
-            if (int rc = launch_transh_edge_fwd(e, st)) return rc;
-        } else if (td) {
-            const size_t k = (size_t)D / 2;
-            TransdEdgeArgs e{};
-            e.src = EdgeSrc{ent, h, ent, t, rel, r};
-            e.B = rows; e.chunk = rows; e.d_e = d_e; e.neg_head = side; e.gamma = gamma;
-            e.AP = w.A; e.alpha = w.an; e.sig = w.A + 2 * (size_t)rows * k; e.u = e.sig + rows;
-            e.nbase = ent; e.nidx = cand; e.n_neg = (int)N; e.beta = w.bn; e.cj = w.bn + N;
-            if (int rc = launch_transd_edge_fwd(e, st)) return rc;
+        } else if (m->own_fwd) {
+            // the A entry: PairRE [a block | w block]; TransH [a block | w^ block | c]; TransD [a block | rho block | sigma | u] of k =
+            // d_e / 2 columns.  The bn entry: the candidates' scalars, TransD's TWO per candidate [beta | c]
+            const size_t blk = (size_t)rows * (td ? D / 2 : D);
+            const kge::OwnOperand o{w.A, w.A + blk, w.an, w.A + 2 * blk, w.A + 2 * blk + rows, w.bn, w.bn + N, nullptr};
+            const kge::OwnCands c{ent, cand, (int)N, nullptr, 0, 0, nullptr};
+            if (int rc = kge::own_prepare(func, EdgeSrc{ent, h, ent, t, rel, r}, rows, rows, d_e, side, gamma, nullptr, o, &c, st))
+                return rc;
         } else {
             EdgeFwdArgs ef{};
             ef.src = EdgeSrc{ent, h, ent, t, rel, r};

@@ -12,12 +12,13 @@ import threading
 
 import torch
 
+from . import models
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KGE_LIB") or os.path.join(_HERE, "libkge_hip.so")   # KGE_LIB: A/B builds
 
 KGE_ABI_VERSION = 8
-MODEL_IDS = {"TransE_l1": 0, "TransE_l2": 1, "TransE": 1, "DistMult": 2, "ComplEx": 3, "RotatE": 4, "SimplE": 5, "RESCAL": 6, "TransR": 7,
-             "QuatE": 8, "PairRE": 10, "TransH": 12, "TransD": 14}      # (9, 11 and 13 are not models)
+MODEL_IDS = models.MODEL_IDS      # (9, 11 and 13 are not models)
 LOSS_IDS = {"Logsigmoid": 0, "Logistic": 1, "Hinge": 2, "BCE": 3, "Softmax": 4}
 FLAG_FORCE_PAIRWISE = 1
 FLAG_NO_TRANSE_FAST = 2
@@ -356,12 +357,12 @@ def rank_rel_workspace_bytes(model, Eb, n_rel, d_e, d_r):
     """bytes of a kge_rank_rel_eval workspace.  kge_rank_rel_workspace_bytes answers for the ids up to TransR; a QuatE call takes
     the DistMult layout followed by the normalised relation table [n_rel, d_r], 256-byte aligned (include/kge_hip.h).  0: bad
     arguments."""
-    h = lib()
-    if model != MODEL_IDS["QuatE"]:
+    h, m = lib(), models.BY_ID.get(model)
+    if not (m and m.rank_rel_as):
         return h.kge_rank_rel_workspace_bytes(model, Eb, n_rel, d_e, d_r)
-    if d_e <= 0 or d_e % 4 or d_r != d_e:
+    if not models.widths_ok(m, d_e, d_r):
         return 0
-    base = h.kge_rank_rel_workspace_bytes(MODEL_IDS["DistMult"], Eb, n_rel, d_e, d_r)
+    base = h.kge_rank_rel_workspace_bytes(MODEL_IDS[m.rank_rel_as], Eb, n_rel, d_e, d_r)
     return base + (n_rel * d_r * 4 + 255) // 256 * 256 if base else 0
 
 
@@ -375,19 +376,15 @@ def topk_workspace_bytes(model, rows, n_cand, d_e, K):
 def rank_ws_cands(model, n_cand):
     """the candidate count a kge_rank_workspace_bytes / kge_topk_workspace_bytes call is made with: TransD keeps two scalars per
     candidate (|n|^2 and c = m . n) in the entry of the candidate norms, every other model one or none (include/kge_hip.h)"""
-    return 2 * n_cand if model == MODEL_IDS["TransD"] else n_cand
+    m = models.BY_ID.get(model)
+    return m.rank_cands * n_cand if m else n_cand
 
 
 def topk_row_width(model, d_e):
     """floats per query row in the A entry of a top-K workspace: PairRE the pair (a, w), TransH the pair (a, w^) and c = w^ . a,
     TransD the pair (a, rho) of half rows and the scalars |rho|^2, a . rho"""
-    if model == MODEL_IDS["TransD"]:
-        return d_e + 2
-    if model == MODEL_IDS["PairRE"]:
-        return 2 * d_e
-    if model == MODEL_IDS["TransH"]:
-        return 2 * d_e + 1
-    return d_e
+    m = models.BY_ID.get(model)
+    return m.topk_row(d_e) if m else d_e
 
 
 def model_id(name):

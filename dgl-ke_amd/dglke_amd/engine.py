@@ -8,7 +8,7 @@ import math
 
 import torch
 
-from . import _lib
+from . import _lib, models
 from ._lib import check, lib, model_id, ptr, stream_ptr
 
 
@@ -33,29 +33,11 @@ class StepEngine(object):
         self.d_r = 2 * hidden_dim if double_relation_emb else hidden_dim
         if model_name == 'RESCAL':                          # relation row = [rel_dim x ent_dim] matrix, general_models.py:232-236
             self.d_r = self.d_r * self.d_e
-        if model_name == 'QuatE':                           # rows are four quarters [a | b | c | d] (include/kge_hip.h)
-            if self.d_e % 4 or self.d_r != self.d_e:
-                raise _lib.KgeError("QuatE needs an entity width that is a multiple of 4 and relation width == entity width "
-                                    "(got %d, %d)" % (self.d_e, self.d_r))
-            if shards is not None:
-                raise _lib.KgeError("QuatE runs the strict step on local tables only (no sharded tables)")
-        if model_name == 'PairRE':                          # relation rows [rH | rT] (include/kge_hip.h)
-            if self.d_r != 2 * self.d_e:
-                raise _lib.KgeError("PairRE needs relation width == 2 * entity width (-dr without -de; got %d, %d)" % (self.d_e, self.d_r))
-            if shards is not None:
-                raise _lib.KgeError("PairRE runs the strict step on local tables only (no sharded tables)")
-        if model_name == 'TransH':                          # relation rows [d | w] (include/kge_hip.h)
-            if self.d_r != 2 * self.d_e or self.d_e % 4 or self.d_e < 4:
-                raise _lib.KgeError("TransH needs an entity width that is a multiple of 4 and relation width == 2 * entity width "
-                                    "(-dr without -de; got %d, %d)" % (self.d_e, self.d_r))
-            if shards is not None:
-                raise _lib.KgeError("TransH runs the strict step on local tables only (no sharded tables)")
-        if model_name == 'TransD':                          # rows [x | x_p] on both tables (include/kge_hip.h)
-            if self.d_r != self.d_e or self.d_e % 8 or self.d_e < 8:
-                raise _lib.KgeError("TransD needs entity and relation rows of the same width, two halves of a multiple of 4 each "
-                                    "(-de and -dr, --hidden_dim %% 4 == 0; got %d, %d)" % (self.d_e, self.d_r))
-            if shards is not None:
-                raise _lib.KgeError("TransD runs the strict step on local tables only (no sharded tables)")
+        m = models.MODELS.get(model_name)                   # (unknown names: model_id below)
+        if m and not models.widths_ok(m, self.d_e, self.d_r):
+            raise _lib.KgeError(m.engine_text % (self.d_e, self.d_r))
+        if m and m.single_gpu_only and shards is not None:
+            raise _lib.KgeError("%s runs the strict step on local tables only (no sharded tables)" % m.name)
         hp = _lib.KgeHParams()
         hp.model = model_id(model_name)
         hp.d_e, hp.d_r = self.d_e, self.d_r

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, models
 
 
 def build_filter(known_h, known_r, known_t, test_h, test_r, test_t, neg_head, n_relations=None):
@@ -195,15 +195,9 @@ class Ranker(object):
         while Eb > 1 and need_of(Eb) > self.rel_ws_budget:
             Eb = (Eb + 1) // 2
         need = need_of(Eb)
-        if need == 0 and self.model == _lib.MODEL_IDS['PairRE']:
-            raise _lib.KgeError("kge_rank_rel_eval: not available for PairRE (the score is not a product of a query row and the "
-                                "relation row: no relation ranking)")
-        if need == 0 and self.model == _lib.MODEL_IDS['TransH']:
-            raise _lib.KgeError("kge_rank_rel_eval: not available for TransH (the relation row enters through two projections: no "
-                                "relation ranking)")
-        if need == 0 and self.model == _lib.MODEL_IDS['TransD']:
-            raise _lib.KgeError("kge_rank_rel_eval: not available for TransD (the relation row enters through two projections: no "
-                                "relation ranking)")
+        m = models.BY_ID.get(self.model)
+        if need == 0 and m and m.no_relation_ranking_lib:
+            raise _lib.KgeError("kge_rank_rel_eval: not available for %s (%s)" % (m.name, m.no_relation_ranking_lib))
         if need == 0:
             raise _lib.KgeError("relation_ranks: the tables are %s / %s, which this model does not take"
                                 % (tuple(self.ent.shape), tuple(self.rel.shape)))

@@ -13,6 +13,7 @@ import torch as th
 
 from . import dist as kd
 from . import eval as kev
+from . import models
 from ._lib import KgeError
 
 
@@ -20,8 +21,7 @@ class ArgParser(argparse.ArgumentParser):
     def __init__(self):
         super(ArgParser, self).__init__()
         a = self.add_argument
-        a('--model_name', default='TransE', choices=['TransE', 'TransE_l1', 'TransE_l2', 'TransR', 'RESCAL', 'DistMult',
-                                                     'ComplEx', 'RotatE', 'SimplE', 'QuatE', 'PairRE', 'TransH', 'TransD'])
+        a('--model_name', default=models.DEFAULT, choices=models.NAMES)
         a('--data_path', type=str, default='data')
         a('--dataset', type=str, default='FB15k')
         a('--format', type=str, default='built_in')
@@ -71,7 +71,7 @@ def load_tables(args, ds, dev, rows=None):
         raise KgeError("entity embeddings are {} but the dataset / flags say {}".format(tuple(ent.shape), (ds.n_entities, d_e)))
     if rows:
         ent = np.ascontiguousarray(ent[rows[0]:rows[1]])
-    return put(ent), put(load('_relation')), put(load('projection')) if args.model_name == 'TransR' else None
+    return put(ent), put(load('_relation')), put(load('projection')) if models.MODELS[args.model_name].projection else None
 
 
 def main(argv=None):
@@ -89,32 +89,13 @@ def main(argv=None):
         raise KgeError("--eval_relation is not available on sharded tables")
     if args.eval_relation and args.eval_candidates:
         raise KgeError("--eval_relation ranks against all relations: the lists of --eval_candidates are entity lists")
-    if args.model_name == 'QuatE':               # before anything is loaded
-        from .train import check_quate_widths
-        check_quate_widths(args.model_name, args.hidden_dim, args.double_ent, args.double_rel)
-        if len(args.gpu) > 1:
-            raise KgeError("QuatE is not available on sharded tables (--gpu takes one entry)")
-    if args.model_name == 'PairRE':              # before anything is loaded
-        from .train import check_pairre_widths
-        check_pairre_widths(args.model_name, args.double_ent, args.double_rel)
-        if len(args.gpu) > 1:
-            raise KgeError("PairRE is not available on sharded tables (--gpu takes one entry)")
-        if args.eval_relation:
-            raise KgeError("PairRE has no relation ranking (--eval_relation): the score is not a product with the relation row")
-    if args.model_name == 'TransH':              # before anything is loaded
-        from .train import check_transh_widths
-        check_transh_widths(args.model_name, args.hidden_dim, args.double_ent, args.double_rel)
-        if len(args.gpu) > 1:
-            raise KgeError("TransH is not available on sharded tables (--gpu takes one entry)")
-        if args.eval_relation:
-            raise KgeError("TransH has no relation ranking (--eval_relation): the relation row enters through two projections")
-    if args.model_name == 'TransD':              # before anything is loaded
-        from .train import check_transd_widths
-        check_transd_widths(args.model_name, args.hidden_dim, args.double_ent, args.double_rel)
-        if len(args.gpu) > 1:
-            raise KgeError("TransD is not available on sharded tables (--gpu takes one entry)")
-        if args.eval_relation:
-            raise KgeError("TransD has no relation ranking (--eval_relation): the relation row enters through two projections")
+    from .train import check_model_widths     # before anything is loaded
+    check_model_widths(args.model_name, args.hidden_dim, args.double_ent, args.double_rel)
+    m = models.MODELS[args.model_name]
+    if m.single_gpu_only and len(args.gpu) > 1:
+        raise KgeError("%s is not available on sharded tables (--gpu takes one entry)" % m.name)
+    if m.no_relation_ranking and args.eval_relation:
+        raise KgeError("%s has no relation ranking (--eval_relation): %s" % (m.name, m.no_relation_ranking))
     if args.gpu[0] < 0:
         raise KgeError("dglke_eval ranks on the GPU only: pass --gpu <id> (there is no CPU fallback)")
     if not os.path.isdir(args.model_path):
@@ -128,7 +109,7 @@ def main(argv=None):
     th.cuda.set_device(dev)
     ds = kd.load_dataset(0, args)
     ent, rel, proj = load_tables(args, ds, dev)
-    model = 'TransE_l2' if args.model_name == 'TransE' else args.model_name
+    model = models.MODELS[args.model_name].alias_of or args.model_name
     emb_init = (args.gamma + 2.0) / args.hidden_dim
     cands = None
     if args.eval_candidates:
@@ -173,7 +154,7 @@ def _sharded_worker(rank, args):
     ds = kd.load_dataset(rank, args)
     spec = kd.ShardSpec(ds.n_entities, world, rank)
     shard, rel, proj = load_tables(args, ds, dev, rows=(spec.lo, spec.hi))
-    model = 'TransE_l2' if args.model_name == 'TransE' else args.model_name
+    model = models.MODELS[args.model_name].alias_of or args.model_name
     comm = kd.make_comm() if len(set(args.gpu)) == world else kd.HostStagedComm()
     try:
         test, known, Eb, _ = kev.eval_setup(ds, 'test', args)

@@ -10,11 +10,10 @@ libkge_hip.  Two ways to run a training step:
 """
 import torch as th
 
-from . import ops
+from . import models, ops, score_fun
 from .engine import StepEngine
 from .loss import LossGenerator
-from .score_fun import (ComplExScore, DistMultScore, PairREScore, QuatEScore, RESCALScore, RotatEScore, SimplEScore, TransEScore,
-                        TransDScore, TransHScore, TransRScore)
+from .score_fun import RESCALScore, TransRScore
 from .tensor_models import (ExternalEmbedding, cuda, get_dev, get_device, get_scalar, norm,
                             reshape)
 from ._lib import LOSS_IDS, KgeError
@@ -45,17 +44,9 @@ class KEModel(object):
                                       bool(getattr(args, 'neg_adversarial_sampling', False)),
                                       getattr(args, 'adversarial_temperature', None) or 1.0,
                                       bool(getattr(args, 'pairwise', False)))
-        if model_name == 'QuatE' and (entity_dim % 4 or relation_dim != entity_dim):
-            raise KgeError("QuatE needs an entity width that is a multiple of 4 and relation_dim == entity_dim (got %d, %d)"
-                           % (entity_dim, relation_dim))
-        if model_name == 'PairRE' and relation_dim != 2 * entity_dim:
-            raise KgeError("PairRE needs relation_dim == 2 * entity_dim, r = [rH | rT] (got %d, %d)" % (entity_dim, relation_dim))
-        if model_name == 'TransH' and (entity_dim % 4 or entity_dim < 4 or relation_dim != 2 * entity_dim):
-            raise KgeError("TransH needs an entity width that is a multiple of 4 and relation_dim == 2 * entity_dim, r = [d | w] "
-                           "(got %d, %d)" % (entity_dim, relation_dim))
-        if model_name == 'TransD' and (entity_dim % 8 or entity_dim < 8 or relation_dim != entity_dim):
-            raise KgeError("TransD needs entity_dim == relation_dim, rows [x | x_p] of two halves that are multiples of 4 "
-                           "(got %d, %d)" % (entity_dim, relation_dim))
+        m = models.MODELS.get(model_name)
+        if m and not models.widths_ok(m, entity_dim, relation_dim):
+            raise KgeError(m.kemodel_text % (entity_dim, relation_dim))
         self.entity_emb = ExternalEmbedding(args, n_entities, entity_dim, device)
         if model_name == 'RESCAL':        # relation_emb = relation_dim * entity_dim (general_models.py:232-236)
             if relation_dim != entity_dim:
@@ -71,33 +62,16 @@ class KEModel(object):
         self.relation_emb = ExternalEmbedding(args, n_relations, relation_dim, device)
         self.global_relation_emb = self.relation_emb
 
-        if model_name in ('TransE', 'TransE_l2'):
-            self.score_func = TransEScore(gamma, 'l2')
-        elif model_name == 'TransE_l1':
-            self.score_func = TransEScore(gamma, 'l1')
-        elif model_name == 'DistMult':
-            self.score_func = DistMultScore()
-        elif model_name == 'ComplEx':
-            self.score_func = ComplExScore()
-        elif model_name == 'RotatE':
-            self.score_func = RotatEScore(gamma, self.emb_init)
-        elif model_name == 'SimplE':
-            self.score_func = SimplEScore()
-        elif model_name == 'QuatE':
-            self.score_func = QuatEScore()
-        elif model_name == 'PairRE':
-            self.score_func = PairREScore(gamma)
-        elif model_name == 'TransH':
-            self.score_func = TransHScore(gamma)
-        elif model_name == 'TransD':
-            self.score_func = TransDScore(gamma)
-        elif model_name == 'RESCAL':
+        if m is None:
+            raise KgeError("unknown model %s" % model_name)
+        if model_name == 'RESCAL':
             self.score_func = RESCALScore(relation_dim // entity_dim, entity_dim)
         elif model_name == 'TransR':
             projection_emb = ExternalEmbedding(args, n_relations, entity_dim * relation_dim, device)
             self.score_func = TransRScore(gamma, projection_emb, relation_dim, entity_dim)
         else:
-            raise KgeError("unknown model %s" % model_name)
+            given = {'gamma': gamma, 'emb_init': self.emb_init}
+            self.score_func = getattr(score_fun, m.score)(*[given.get(x, x) for x in m.score_args])
         self.head_neg_score = self.score_func.create_neg(True)
         self.tail_neg_score = self.score_func.create_neg(False)
         self.head_neg_prepare = self.score_func.create_neg_prepare(True)

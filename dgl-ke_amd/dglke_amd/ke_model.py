@@ -24,6 +24,7 @@ import torch as th
 
 from . import _lib
 from . import infer
+from . import models
 from ._lib import KgeError
 from .infer import DEFAULT_INFER_BATCHSIZE
 from .known import KnownIndex
@@ -152,6 +153,13 @@ class BasicGEModel(object):
         return self._g
 
 
+def _check_loaded_widths(self):
+    """the loaded tables against the width rule of the model's record (models.py)"""
+    m, d_e, d_r = models.MODELS[self._model_name], self._entity_emb.shape[1], self._relation_emb.shape[1]
+    if not models.widths_ok(m, d_e, d_r):
+        raise KgeError(m.loaded_text % (d_e, d_r))
+
+
 class KGEModel(BasicGEModel):
     """ke_model.py:855-866"""
 
@@ -209,11 +217,7 @@ class QuatEModel(KGEModel):
     def __init__(self, device):
         super(QuatEModel, self).__init__(device, 'QuatE')
 
-    def _after_load(self):
-        d = self._entity_emb.shape[1]
-        if d % 4 or self._relation_emb.shape[1] != d:
-            raise KgeError("QuatE: rows of %d (entity) and %d (relation) values: the width must be a multiple of 4 and the same "
-                           "for both" % (d, self._relation_emb.shape[1]))
+    _after_load = _check_loaded_widths
 
 
 class PairREModel(KGEModel):
@@ -224,11 +228,7 @@ class PairREModel(KGEModel):
         self._gamma = gamma
         super(PairREModel, self).__init__(device, 'PairRE')
 
-    def _after_load(self):
-        d = self._entity_emb.shape[1]
-        if self._relation_emb.shape[1] != 2 * d:
-            raise KgeError("PairRE: rows of %d (entity) and %d (relation) values: the relation row must be twice as wide"
-                           % (d, self._relation_emb.shape[1]))
+    _after_load = _check_loaded_widths
 
 
 class TransHModel(KGEModel):
@@ -239,11 +239,7 @@ class TransHModel(KGEModel):
         self._gamma = gamma
         super(TransHModel, self).__init__(device, 'TransH')
 
-    def _after_load(self):
-        d = self._entity_emb.shape[1]
-        if d % 4 or self._relation_emb.shape[1] != 2 * d:
-            raise KgeError("TransH: rows of %d (entity) and %d (relation) values: the entity width must be a multiple of 4 and the "
-                           "relation row twice as wide" % (d, self._relation_emb.shape[1]))
+    _after_load = _check_loaded_widths
 
 
 class TransDModel(KGEModel):
@@ -255,11 +251,7 @@ class TransDModel(KGEModel):
         self._gamma = gamma
         super(TransDModel, self).__init__(device, 'TransD')
 
-    def _after_load(self):
-        d = self._entity_emb.shape[1]
-        if d % 8 or self._relation_emb.shape[1] != d:
-            raise KgeError("TransD: rows of %d (entity) and %d (relation) values: both must be [x | x_p], the same width and a "
-                           "multiple of 8" % (d, self._relation_emb.shape[1]))
+    _after_load = _check_loaded_widths
 
 
 class RESCALModel(KGEModel):

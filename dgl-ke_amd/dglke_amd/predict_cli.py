@@ -116,14 +116,8 @@ def check_args(args):
     config = load_model_config(os.path.join(args.model_path, 'config.json'))
     if config['model_name'] == 'TransR':
         raise KgeError("TransR has no inference path (the reference's InferModel refuses it too)")
-    from .train import check_quate_widths
-    check_quate_widths(config['model_name'], config['hidden_dim'], config['double_ent'], config['double_rel'])
-    from .train import check_pairre_widths
-    check_pairre_widths(config['model_name'], config['double_ent'], config['double_rel'])
-    from .train import check_transh_widths
-    check_transh_widths(config['model_name'], config['hidden_dim'], config['double_ent'], config['double_rel'])
-    from .train import check_transd_widths
-    check_transd_widths(config['model_name'], config['hidden_dim'], config['double_ent'], config['double_rel'])
+    from .train import check_model_widths
+    check_model_widths(config['model_name'], config['hidden_dim'], config['double_ent'], config['double_rel'])
     head, rel, tail, id2e, id2r = parse_inputs(args)
     if args.exec_mode == 'triplet_wise' and not (head is not None and rel is not None and tail is not None and
                                                  len(head) == len(rel) == len(tail)):

@@ -31,6 +31,7 @@ from . import _lib
 from . import checkpoint as ckpt
 from . import dist as kd
 from . import eval as kev
+from . import models
 from ._lib import KgeError
 from .dataloader import DeviceSampler, UniformChunkedSampler
 from .engine import StepEngine
@@ -42,8 +43,7 @@ class ArgParser(argparse.ArgumentParser):
     def __init__(self):
         super(ArgParser, self).__init__(prog="dglke_train")
         a = self.add_argument
-        a('--model_name', default='TransE', choices=['TransE', 'TransE_l1', 'TransE_l2', 'TransR', 'RESCAL',
-                                                     'DistMult', 'ComplEx', 'RotatE', 'SimplE', 'QuatE', 'PairRE', 'TransH', 'TransD'])
+        a('--model_name', default=models.DEFAULT, choices=models.NAMES)
         a('--data_path', type=str, default='data')
         a('--dataset', type=str, default='FB15k')
         a('--format', type=str, default='built_in')
@@ -501,7 +501,7 @@ class Trainer(_Trainer):
         self.n_lanes = max(1, int(args.num_proc))
         # entity-only deferral (the reference's --async_update) runs as the strict step unless the pipeline is asked for: with the
         # relation trace landing between two steps the pipeline needs one more launch than it hides
-        async_ok = args.model_name not in ('TransR', 'RESCAL')
+        async_ok = not models.own_relation_update(models.MODELS[args.model_name])
         pipeline = args.async_update_rel or args.async_update_pipeline
         self.async_update = bool(args.async_update and async_ok and pipeline)
         if args.async_update and not async_ok:
@@ -558,7 +558,7 @@ class Trainer(_Trainer):
     def evaluate(self, which, mode):
         args, m = self.args, self.model
         test, known, Eb, _ = kev.eval_setup(self.dataset, which, args)
-        proj = m.score_func.projection_emb.emb if args.model_name == 'TransR' else None
+        proj = m.score_func.projection_emb.emb if models.MODELS[args.model_name].projection else None
         # (the split and the known set do not change during a run: filter lists and test ids stay on the device between validations)
         cache = self.__dict__.setdefault('_eval_cache', {}).setdefault(which, {})
         metrics = kev.evaluate(args.model_name, m.entity_emb.emb, m.relation_emb.emb, args.gamma, m.emb_init, test, known,
@@ -588,7 +588,7 @@ class ShardedTrainer(_Trainer):
         # and TransR's projection table - is LOCAL to the trainer that holds the relation's edges, so the triples are partitioned
         # BY RELATION (whole relations): the reference's --rel_part layout, which its own multi-GPU TransR recipe passes
         # (examples/freebase/multi_gpu.sh:80-89, general_models.py:590-637).  The owners' rows are collected by sync_tables.
-        self.rel_side_local = args.model_name in ('TransR', 'RESCAL')
+        self.rel_side_local = models.own_relation_update(models.MODELS[args.model_name])
         if self.rel_side_local and args.neg_deg_sample:
             raise KgeError("--neg_deg_sample is not available for %s on more than one GPU" % args.model_name)
         self.rel_owner = None
@@ -606,9 +606,9 @@ class ShardedTrainer(_Trainer):
                       "(whole relations; edges per trainer %s)" % (args.model_name, world, np.bincount(edge_rank, minlength=world).tolist()))
         part = self.split(world, edge_rank, refusal)[rank]
         self.tabs = p2p.ShardedTables(dataset.n_entities, dataset.n_relations, self.d_e,
-                                      self.d_r * self.d_e if args.model_name == 'RESCAL' else self.d_r, self.dev, world, rank,
+                                      self.d_r * self.d_e if models.MODELS[args.model_name].relation_matrix else self.d_r, self.dev, world, rank,
                                       rel_local=self.rel_side_local,
-                                      proj_dim=self.d_e * self.d_r if args.model_name == 'TransR' else 0)
+                                      proj_dim=self.d_e * self.d_r if models.MODELS[args.model_name].projection else 0)
         if not self.tabs.probe():
             raise KgeError("peer mappings do not reach the other GPUs' memory")
         self.tabs.init_uniform(self.emb_init, args.seed)
@@ -663,7 +663,7 @@ class ShardedTrainer(_Trainer):
                              self.dataset.n_entities)
         if self.rank == 0:
             np.save(os.path.join(args.save_path, '%s_%s_relation.npy' % (args.dataset, args.model_name)), rel.cpu().numpy())
-            if args.model_name == 'TransR':      # TransRScore.save (score_fun.py:190-191): <dataset>_<model>projection.npy
+            if models.MODELS[args.model_name].projection:      # TransRScore.save (score_fun.py:190-191): <dataset>_<model>projection.npy
                 np.save(os.path.join(args.save_path, '%s_%sprojection.npy' % (args.dataset, args.model_name)),
                         self.projection().cpu().numpy())
             write_config(args, emap_file, rmap_file)
@@ -678,7 +678,7 @@ class ShardedTrainer(_Trainer):
         cache = self.__dict__.setdefault('_eval_cache', {}).setdefault(which, {})
         metrics = kev.evaluate_sharded(args.model_name, shard, lo, ds.n_entities, self.relation_table(), args.gamma, self.emb_init,
                                        test, self.entity_rows, known, batch=Eb,
-                                       proj=self.projection() if args.model_name == 'TransR' else None,
+                                       proj=self.projection() if models.MODELS[args.model_name].projection else None,
                                        n_cand=args.neg_sample_size_eval, chunk=args.batch_size_eval, seed=args.seed + 29, cache=cache)
         if self.rank == 0:
             kev.print_metrics(mode, metrics)
@@ -756,7 +756,7 @@ class A2ATrainer(ShardedTrainer):
             if self.rel_side_local:
                 print("%s on %d GPUs (a2a): entity messages exchanged, relation-side tables (relation rows%s) applied in place on the "
                       "trainer that holds the relation's edges" % (args.model_name, world,
-                                                                    ", projection matrices" if args.model_name == 'TransR' else " = matrices"))
+                                                                    ", projection matrices" if models.MODELS[args.model_name].projection else " = matrices"))
 
     def enqueue(self, n):
         """n sharded steps, eagerly (every rank issues the same collectives in the same order); inside a group of sampled
@@ -890,7 +890,7 @@ def check_optimizer(args):
     loaded: what that step does not cover"""
     if getattr(args, 'optimizer', 'Adagrad') != 'Adam':
         return
-    if args.model_name in ('RESCAL', 'TransR'):
+    if models.own_relation_update(models.MODELS[args.model_name]):
         raise KgeError("--optimizer Adam is not available for %s (RESCAL / TransR update their relation-side tables with kernels of "
                        "their own)" % args.model_name)
     if len(args.gpu) > 1:
@@ -920,101 +920,39 @@ def check_loss_flags(args):
         raise KgeError("--loss_genre Softmax cannot be combined with -pw")
 
 
-def check_quate_widths(model_name, hidden_dim, double_ent, double_rel):
-    """QuatE rows are four quarters of quaternion components and the relation row is as wide as the entity row"""
-    if model_name != 'QuatE':
-        return
-    width = hidden_dim * (2 if double_ent else 1)
-    if width % 4:
-        raise KgeError("QuatE: the entity width (--hidden_dim%s = %d) must be a multiple of 4 (four quarters [a | b | c | d])"
-                       % (" x 2 with -de" if double_ent else "", width))
-    if bool(double_rel) != bool(double_ent):
-        raise KgeError("QuatE: the relation width must equal the entity width: pass -dr together with -de (and neither alone)")
+def check_model_widths(model_name, hidden_dim, double_ent, double_rel):
+    """the -de / -dr / --hidden_dim rules of the model's record (models.py); the texts are the record's"""
+    m = models.MODELS[model_name]
+    said = dict(de=" -de" if double_ent else " no -de", dr=" -dr" if double_rel else ", no -dr", cdr=", -dr" if double_rel else ", no -dr",
+                x2=" x 2 with -de" if double_ent else "", width=hidden_dim * (2 if double_ent else 1), hidden=hidden_dim)
+
+    def flags():
+        if m.de == 'tied':
+            bad = bool(double_rel) != bool(double_ent)
+        else:
+            bad = any(want is not None and bool(got) != want for want, got in ((m.de, double_ent), (m.dr, double_rel)))
+        if bad:
+            raise KgeError(m.flags_text % said)
+
+    def multiple():
+        v = said['width'] if m.cli_of == 'width' else hidden_dim
+        if m.cli_multiple and (v % m.cli_multiple or (m.cli_of == 'hidden_dim' and v < m.cli_multiple)):
+            raise KgeError(m.multiple_text % said)
+    for check in ((multiple, flags) if m.multiple_first else (flags, multiple)):
+        check()
 
 
-def check_quate(args):
-    """QuatE trains on the strict step of one GPU's tables: refuse what has no such step, before anything is loaded"""
-    if args.model_name != 'QuatE':
-        return
-    check_quate_widths(args.model_name, args.hidden_dim, args.double_ent, args.double_rel)
-    if len(args.gpu) > 1:
-        raise KgeError("QuatE is not available on more than one GPU (--gpu takes one entry)")
-    if args.async_update_pipeline or args.async_update_rel:
-        raise KgeError("QuatE is not available in the one-step-stale pipeline (--async_update_pipeline / --async_update_rel); "
-                       "plain --async_update runs the strict step and is fine")
-
-
-def check_pairre_widths(model_name, double_ent, double_rel):
-    """PairRE's relation row is [rH | rT], twice the entity row"""
-    if model_name != 'PairRE':
-        return
-    if not double_rel or double_ent:
-        raise KgeError("PairRE: the relation row [rH | rT] is twice as wide as the entity row: pass -dr without -de (got%s%s)"
-                       % (" -de" if double_ent else " no -de", " -dr" if double_rel else ", no -dr"))
-
-
-def check_pairre(args):
-    """PairRE trains on the strict step of one GPU's tables: refuse what has no such step, before anything is loaded"""
-    if args.model_name != 'PairRE':
-        return
-    check_pairre_widths(args.model_name, args.double_ent, args.double_rel)
-    if len(args.gpu) > 1:
-        raise KgeError("PairRE is not available on more than one GPU (--gpu takes one entry)")
-    if args.async_update_pipeline or args.async_update_rel:
-        raise KgeError("PairRE is not available in the one-step-stale pipeline (--async_update_pipeline / --async_update_rel); "
-                       "plain --async_update runs the strict step and is fine")
-    if args.eval_relation:
-        raise KgeError("PairRE has no relation ranking (--eval_relation): the score is not a product with the relation row")
-
-
-def check_transh_widths(model_name, hidden_dim, double_ent, double_rel):
-    """TransH's relation row is [d | w], twice the entity row, and every path is a matrix-core product over 16-byte rows"""
-    if model_name != 'TransH':
-        return
-    if not double_rel or double_ent:
-        raise KgeError("TransH: the relation row [d | w] is twice as wide as the entity row: pass -dr without -de (got%s%s)"
-                       % (" -de" if double_ent else " no -de", " -dr" if double_rel else ", no -dr"))
-    if hidden_dim < 4 or hidden_dim % 4:
-        raise KgeError("TransH: --hidden_dim must be a multiple of 4 (got %d)" % hidden_dim)
-
-
-def check_transh(args):
-    """TransH trains on the strict step of one GPU's tables: refuse what has no such step, before anything is loaded"""
-    if args.model_name != 'TransH':
-        return
-    check_transh_widths(args.model_name, args.hidden_dim, args.double_ent, args.double_rel)
-    if len(args.gpu) > 1:
-        raise KgeError("TransH is not available on more than one GPU (--gpu takes one entry)")
-    if args.async_update_pipeline or args.async_update_rel:
-        raise KgeError("TransH is not available in the one-step-stale pipeline (--async_update_pipeline / --async_update_rel); "
-                       "plain --async_update runs the strict step and is fine")
-    if args.eval_relation:
-        raise KgeError("TransH has no relation ranking (--eval_relation): the relation row enters through two projections")
-
-
-def check_transd_widths(model_name, hidden_dim, double_ent, double_rel):
-    """TransD's entity and relation rows are [x | x_p], twice --hidden_dim, and every path is a matrix-core product over 16-byte halves"""
-    if model_name != 'TransD':
-        return
-    if not double_ent or not double_rel:
-        raise KgeError("TransD: entity rows [e | e_p] and relation rows [r | r_p] are both twice --hidden_dim: pass -de and -dr (got%s%s)"
-                       % (" -de" if double_ent else " no -de", ", -dr" if double_rel else ", no -dr"))
-    if hidden_dim < 4 or hidden_dim % 4:
-        raise KgeError("TransD: --hidden_dim must be a multiple of 4 (got %d)" % hidden_dim)
-
-
-def check_transd(args):
-    """TransD trains on the strict step of one GPU's tables: refuse what has no such step, before anything is loaded"""
-    if args.model_name != 'TransD':
-        return
-    check_transd_widths(args.model_name, args.hidden_dim, args.double_ent, args.double_rel)
-    if len(args.gpu) > 1:
-        raise KgeError("TransD is not available on more than one GPU (--gpu takes one entry)")
-    if args.async_update_pipeline or args.async_update_rel:
-        raise KgeError("TransD is not available in the one-step-stale pipeline (--async_update_pipeline / --async_update_rel); "
-                       "plain --async_update runs the strict step and is fine")
-    if args.eval_relation:
-        raise KgeError("TransD has no relation ranking (--eval_relation): the relation row enters through two projections")
+def check_model_flags(args):
+    """a model that trains on the strict step of one GPU's tables: refuse what has no such step, before anything is loaded"""
+    m = models.MODELS[args.model_name]
+    check_model_widths(args.model_name, args.hidden_dim, args.double_ent, args.double_rel)
+    if m.single_gpu_only and len(args.gpu) > 1:
+        raise KgeError("%s is not available on more than one GPU (--gpu takes one entry)" % m.name)
+    if m.no_stale_pipeline and (args.async_update_pipeline or args.async_update_rel):
+        raise KgeError("%s is not available in the one-step-stale pipeline (--async_update_pipeline / --async_update_rel); "
+                       "plain --async_update runs the strict step and is fine" % m.name)
+    if m.no_relation_ranking and args.eval_relation:
+        raise KgeError("%s has no relation ranking (--eval_relation): %s" % (m.name, m.no_relation_ranking))
 
 
 def main(argv=None, before_train=None):
@@ -1022,10 +960,7 @@ def main(argv=None, before_train=None):
     args = ArgParser().parse_args(argv)
     check_loss_flags(args)                       # before anything is loaded or created
     check_exclude_positive(args)                 # before anything is loaded or created
-    check_quate(args)                            # before anything is loaded or created
-    check_pairre(args)                           # before anything is loaded or created
-    check_transh(args)                           # before anything is loaded or created
-    check_transd(args)                           # before anything is loaded or created
+    check_model_flags(args)                      # before anything is loaded or created
     check_weighted_device_sampler(args)          # before anything is loaded or created
     check_optimizer(args)                        # before anything is loaded or created
     ckpt.check_flags(args)                       # before anything is loaded or created

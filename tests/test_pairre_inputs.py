@@ -369,10 +369,10 @@ def test_command_lines_refuse_widths_and_flag_combinations(tmp_path):
 def test_python_layers_check_the_widths_before_touching_a_device():
     lib = _lib()
     from dglke_amd import ke_model, score_fun
-    from dglke_amd.train import check_pairre_widths
+    from dglke_amd.train import check_model_widths
     assert score_fun.PairREScore.model_name == "PairRE" and score_fun.PairREScore(7.0).gamma == 7.0 and lib.model_id("PairRE") == 10
     assert issubclass(ke_model.PairREModel, ke_model.KGEModel) and ke_model.PairREModel(0, 5.0)._gamma == 5.0
-    check_pairre_widths("PairRE", False, True)
-    check_pairre_widths("DistMult", True, False)
+    check_model_widths("PairRE", 32, False, True)
+    check_model_widths("DistMult", 32, True, False)
     with pytest.raises(lib.KgeError, match="PairRE.*-dr without -de"):
-        check_pairre_widths("PairRE", True, True)
+        check_model_widths("PairRE", 32, True, True)

@@ -329,7 +329,7 @@ def test_python_layers_check_the_widths_before_touching_a_device():
     from dglke_amd import ke_model, score_fun
     assert score_fun.QuatEScore.model_name == "QuatE" and lib.model_id("QuatE") == 8
     assert issubclass(ke_model.QuatEModel, ke_model.KGEModel)
-    from dglke_amd.train import check_quate_widths
-    check_quate_widths("QuatE", 32, False, False)
-    check_quate_widths("QuatE", 18, True, True)
-    check_quate_widths("DistMult", 30, True, False)
+    from dglke_amd.train import check_model_widths
+    check_model_widths("QuatE", 32, False, False)
+    check_model_widths("QuatE", 18, True, True)
+    check_model_widths("DistMult", 30, True, False)

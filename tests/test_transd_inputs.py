@@ -444,13 +444,13 @@ def test_command_lines_refuse_widths_and_flag_combinations(tmp_path):
 def test_python_layers_check_the_widths_before_touching_a_device():
     lib = _lib()
     from dglke_amd import ke_model, score_fun
-    from dglke_amd.train import check_transd_widths
+    from dglke_amd.train import check_model_widths
     assert score_fun.TransDScore.model_name == "TransD" and score_fun.TransDScore(7.0).gamma == 7.0 and lib.model_id("TransD") == 14
     assert issubclass(ke_model.TransDModel, ke_model.KGEModel) and ke_model.TransDModel(0, 5.0)._gamma == 5.0
-    check_transd_widths("TransD", 32, True, True)
-    check_transd_widths("DistMult", 30, True, False)
+    check_model_widths("TransD", 32, True, True)
+    check_model_widths("DistMult", 30, True, False)
     with pytest.raises(lib.KgeError, match="TransD.*pass -de and -dr"):
-        check_transd_widths("TransD", 32, False, True)
+        check_model_widths("TransD", 32, False, True)
     with pytest.raises(lib.KgeError, match="TransD.*multiple of 4"):
-        check_transd_widths("TransD", 30, True, True)
+        check_model_widths("TransD", 30, True, True)
     assert lib.topk_row_width(14, 32) == 34 and lib.topk_row_width(12, 32) == 65 and lib.topk_row_width(1, 32) == 32

@@ -436,13 +436,13 @@ def test_command_lines_refuse_widths_and_flag_combinations(tmp_path):
 def test_python_layers_check_the_widths_before_touching_a_device():
     lib = _lib()
     from dglke_amd import ke_model, score_fun
-    from dglke_amd.train import check_transh_widths
+    from dglke_amd.train import check_model_widths
     assert score_fun.TransHScore.model_name == "TransH" and score_fun.TransHScore(7.0).gamma == 7.0 and lib.model_id("TransH") == 12
     assert issubclass(ke_model.TransHModel, ke_model.KGEModel) and ke_model.TransHModel(0, 5.0)._gamma == 5.0
-    check_transh_widths("TransH", 32, False, True)
-    check_transh_widths("DistMult", 30, True, False)
+    check_model_widths("TransH", 32, False, True)
+    check_model_widths("DistMult", 30, True, False)
     with pytest.raises(lib.KgeError, match="TransH.*-dr without -de"):
-        check_transh_widths("TransH", 32, True, True)
+        check_model_widths("TransH", 32, True, True)
     with pytest.raises(lib.KgeError, match="TransH.*multiple of 4"):
-        check_transh_widths("TransH", 30, False, True)
+        check_model_widths("TransH", 30, False, True)
     assert lib.topk_row_width(12, 32) == 65 and lib.topk_row_width(10, 32) == 64 and lib.topk_row_width(1, 32) == 32
