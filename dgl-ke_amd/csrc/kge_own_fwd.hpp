@@ -185,8 +185,10 @@ inline int own_bwd_products(int model, const OwnBlock &k, const OwnBufs &t, floa
     GemmArgs g; own_fill_gemm(model, g, k);
     g.W = t.PQc; g.GA = t.GA; g.GN = GN;
     if ((2 * k.chunk > k.N ? 2 * k.chunk : k.N) <= KGE_NEG_BWD_GEMM_MAXK) return launch_neg_bwd_gemm(g, s);
-    NegArgs na; fill_pair(na, KGE_DISTMULT, g.C, g.chunk, g.N, g.D, g.gamma, g.A, g.nbase, g.nidx);     // (tested here: any error of the
-    na.W = t.PQc; na.GA = t.GA; na.GN = GN;                                                             //  launcher stays an error)
+    // decided here: any error of the launcher stays an error.  Both sides are tested by the s7 shapes of tests/new_model_shape_cases.py,
+    // TransH and TransD: s7a (2 chunk = 2064) and s7b (N = 2049) come here, s7c (2 chunk = 2048) is the last shape on the tiles
+    NegArgs na; fill_pair(na, KGE_DISTMULT, g.C, g.chunk, g.N, g.D, g.gamma, g.A, g.nbase, g.nidx);
+    na.W = t.PQc; na.GA = t.GA; na.GN = GN;
     return launch_neg_bwd_pair(na, s);
 }
 

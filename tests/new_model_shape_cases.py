@@ -1,9 +1,9 @@
-"""Case tables and builders that take QuatE, PairRE and TransH across the tile, slab and list boundaries of their kernels.
+"""Case tables and builders that take QuatE, PairRE, TransH and TransD across the tile, slab and list boundaries of their kernels.
 Test infrastructure; a plain module, not a conftest.  Shared by
   tests/test_new_model_shape_inputs.py  (CPU): every condition on the inputs, from the float64 statements alone;
   tests/test_gpu_new_model_shapes.py    (GPU): the fused step at these shapes against the float64 step.
-The statements are those of tests/quate_cases.py, tests/pairre_cases.py and tests/transh_cases.py (general in B, chunk, N, the
-table sizes and the width); this module only widens the case tables.
+The statements are those of tests/quate_cases.py, tests/pairre_cases.py, tests/transh_cases.py and tests/transd_cases.py (general
+in B, chunk, N, the table sizes and the width); this module only widens the case tables.
 
 The constants the shapes are chosen against, read from the kernels:
   kge_pairre.hip      QT = 32 (score tile edge), QK = 32 (columns of a backward tile), QS = 32 (staged slab: k of the forward tile,
@@ -12,10 +12,17 @@ The constants the shapes are chosen against, read from the kernels:
   kge_neg_pair.hip    PT = 32, PK = 32 (QuatE under FORCE_PAIRWISE where d_e % 16 != 0: `pair32`; `bcast` where d_e % 16 == 0)
   kge_tile_gemm.hpp   TILE_BK = 32 (k per stage of the matrix-core products: QuatE's `gemm` route and the TransH products)
   kge_transh.hip      TH_CT = 32 (columns of a column-sum workgroup: transh_coef_kernel's grid is nb_rows + C * tct)
+  kge_transd.hip      TD_CT = 32, TD_CR = 8 (transd_cases.py: columns and row groups of a column-sum workgroup of transd_coef_kernel,
+                      grid nb_rows + C * tct; row group rg sums the rows rg, rg + TD_CR, ... of its chunk); td_stack_row: the
+                      stacked operand [A ; P] of 2 chunk rows per chunk, k = d_e / 2 columns, STACK_TILE = 32 rows to a row tile
+  kge_own_fwd.hpp     own_bwd_products (TransH, TransD): the backward GEMM tiles while max(2 chunk, N) <= GB_MAXK = 2048
+                      (kge_neg_gemm.hip; modular_op_cases.py), the pairwise kernels beyond
   kge_rowwise.hip     launch_loss: the register-resident loss rows end at N <= 512, longer rows stream (loss_kernel);
                       launch_update: the register-resident update ends at max(d_e, d_r) <= 1024 floats, 1 / 2 / 4 packs per lane
                       up to 256 / 512 / 1024; wider rows take the generic update_kernel
-Relation rows are d_e wide for QuatE and 2 d_e wide for PairRE and TransH.
+Relation rows are d_e wide for QuatE and TransD and 2 d_e wide for PairRE and TransH.  A TransD case's d_e is its ROW width 2 k
+(rows [e | e_p], [r | r_p]); the shape tables give its half-width k, a multiple of 4.  TransD tables are uniform(-1, 1) times
+transd_cases.row_scale(k), which keeps |c_j| = |m_j . n_j| of order 1; TransD leaves out no rows.
 
 Every step starts from the case's fixed tables (tail corruption, then head corruption from the same tables), so that the CPU file
 can assert every condition on the inputs of every step.
@@ -37,16 +44,21 @@ import numpy as np
 import loss_option_cases as L
 import pairre_cases as PR
 import quate_cases as QE
+import transd_cases as TD
 import transh_cases as TH
 from modular_op_cases import grad_bound, score_bound, worst
 from oracle import kge_oracle as O
 
-MODELS = ("QuatE", "PairRE", "TransH")
-MOD = {"QuatE": QE, "PairRE": PR, "TransH": TH}
+MODELS = ("QuatE", "PairRE", "TransH", "TransD")
+MOD = {"QuatE": QE, "PairRE": PR, "TransH": TH, "TransD": TD}
+STACKED = ("TransH", "TransD")      # kge_own_fwd.hpp: the products run over a stacked operand of 2 chunk rows per chunk
 QT = QK = QS = 32                   # kge_pairre.hip
 PT = PK = 32                        # kge_neg_pair.hip
 TILE_BK = 32                        # kge_tile_gemm.hpp
 TH_CT = 32                          # kge_transh.hip
+TD_CT, TD_CR = TD.TD_CT, TD.TD_CR   # kge_transd.hip
+STACK_TILE = 32                     # rows of the stacked operand to a row tile
+GB_MAXK = TD.GB_MAXK                # kge_neg_gemm.hip (KGE_NEG_BWD_GEMM_MAXK of own_bwd_products)
 LOSS_REG_N = 512                    # kge_rowwise.hip launch_loss
 UPDATE_REG_W = 1024                 # kge_rowwise.hip launch_update
 QUANTITIES = ("pos_score", "neg_score", "g_pos_ent", "g_neg", "g_rel", "ent_rows", "rel_rows", "ent_state", "rel_state")
@@ -57,7 +69,7 @@ def _seed(*key):
 
 
 def rel_width(model, d_e):
-    return d_e if model == "QuatE" else 2 * d_e
+    return d_e if model in ("QuatE", "TransD") else 2 * d_e
 
 
 def engine_gamma(model):
@@ -109,6 +121,18 @@ def make_case(model, sid, shape, oid, n_ent, n_rel, flags=0, seed=0, separated=F
 #    QuatE runs every shape under flags 0 and FORCE_PAIRWISE; the route (quate_cases.neg_route):
 #      s1 68: gemm | pair32      s2a 4: gemm | pair32      s2b 36: gemm | pair32      s3 36: gemm | pair32
 #      s4 32: gemm | bcast       s5 400: gemm | bcast      s6 1040: gemm | bcast
+#    TransD reads the last entry as its half-width k (rows 2 k wide; s5: k = 200, the recipe's rows of 400 floats).  What its kernels
+#    cross (EXPECT_TRANSD, from TD_CT, TD_CR, STACK_TILE and TILE_BK):
+#    s1   the stacked operand of 80 rows per chunk - three row tiles, the last of 16 - with C = 3; tct = 3 column-sum workgroups per
+#         chunk, the last of 8 columns; 5 rows per row group; 3 k-stages, the last of 4
+#    s2a  m = chunk = 1 in td_stack_row; one column; the narrowest width      s2b  17 rows over 8 row groups (3, 2, 2, ..); 2 k-stages
+#    s3   Np = 48: tct = 2, the last of 16; the in-batch rows' gradient joins the corrupted side (GNd of transd_edge_bwd_kernel) after
+#         the candidate-row launch of its own        s4  tct = 17        s5  rows of 400 floats       s6  rows of 1032 floats, both tables
+#    s7   TransH and TransD only - the route of own_bwd_products, whose stacked operand halves the threshold in chunk:
+#    s7a  (1, 1032, 8, 4)   2 chunk = 2064 > GB_MAXK: the pairwise backward products
+#    s7b  (1, 8, 2049, 4)   N = 2049 > GB_MAXK: the same branch from the other operand
+#    s7c  (1, 1024, 8, 4)   2 chunk = 2048: the last shape on the backward GEMM tiles
+#    (TransH: d_e = 4, its narrowest width; TransD: k = 4, rows of 8 floats)
 # --------------------------------------------------------------------------------------------------------------------------
 SHAPES = {
     #       shape               n_ent n_rel  options
@@ -121,6 +145,28 @@ SHAPES = {
     "s6": ((1, 32, 32, 516), 50, 6, ("logsigmoid-adv",)),
 }
 QUATE_S6 = (1, 16, 32, 1040)
+S7_SHAPES = {
+    "s7a": ((1, 1032, 8, 4), 400, 7, ("logsigmoid-adv",)),
+    "s7b": ((1, 8, 2049, 4), 3000, 3, ("logsigmoid-adv",)),
+    "s7c": ((1, 1024, 8, 4), 400, 7, ("logsigmoid-adv",)),
+}
+TRANSD_K = {"s5": 200}              # TransD's half-width where it is not the shape's last entry
+
+
+def case_shape(model, sid):
+    """(C, chunk, N, d_e) of shape `sid` for `model`: QuatE's own s6; TransD: the last entry is k and d_e = 2 k"""
+    shape = (SHAPES.get(sid) or S7_SHAPES[sid])[0]
+    if sid == "s6" and model == "QuatE":
+        return QUATE_S6
+    if model == "TransD":
+        return shape[:3] + (2 * TRANSD_K.get(sid, shape[3]),)
+    return shape
+
+
+def shape_ids(model):
+    return list(SHAPES) + (list(S7_SHAPES) if model in STACKED else [])
+
+
 # what each shape must produce (asserted by the CPU file from the constants above): row tiles, column tiles, k slabs of the 32-wide
 # tilings, and whether the last of each is ragged
 EXPECT_TILES = {
@@ -132,13 +178,34 @@ EXPECT_TILES = {
     "s5": dict(ti=2, tj=2, tk=13, ragged=(False, False, True)),
     "s6": dict(ti=1, tj=1, tk=17, ragged=(False, False, True)),
     ("s6", "QuatE"): dict(ti=1, tj=1, tk=33, ragged=(True, False, True)),
+    "s7a": dict(ti=33, tj=1, tk=1, ragged=(True, True, True)),
+    "s7b": dict(ti=1, tj=65, tk=1, ragged=(True, True, True)),
+    "s7c": dict(ti=32, tj=1, tk=1, ragged=(False, True, True)),
 }
+# TransD (`transd_tiles`): row tiles of the stacked operand, column-sum workgroups per chunk, (most, fewest) rows of a row group,
+# k-stages of the products; ragged: the last row tile, the last column tile, the row groups unequal, the last k-stage
+EXPECT_TRANSD = {
+    "s1": dict(stack=3, tct=3, rows=(5, 5), kst=3, ragged=(True, True, False, True)),
+    "s2a": dict(stack=1, tct=1, rows=(1, 0), kst=1, ragged=(True, True, True, True)),
+    "s2b": dict(stack=2, tct=1, rows=(3, 2), kst=2, ragged=(True, True, True, True)),
+    "s3": dict(stack=2, tct=2, rows=(3, 2), kst=2, ragged=(True, True, True, True)),          # (tct over Np = 48)
+    "s4": dict(stack=1, tct=17, rows=(1, 1), kst=1, ragged=(True, True, False, False)),
+    "s5": dict(stack=4, tct=2, rows=(8, 8), kst=7, ragged=(False, False, False, True)),
+    "s6": dict(stack=2, tct=1, rows=(4, 4), kst=17, ragged=(False, False, False, True)),
+    "s7a": dict(stack=65, tct=1, rows=(129, 129), kst=1, ragged=(True, True, False, True)),
+    "s7b": dict(stack=1, tct=65, rows=(1, 1), kst=1, ragged=(True, True, False, True)),
+    "s7c": dict(stack=64, tct=1, rows=(128, 128), kst=1, ragged=(False, True, False, True)),
+}
+# own_bwd_products (TransH, TransD): which kernels take the backward products
+EXPECT_BWD = {"s7a": "pair", "s7b": "pair", "s7c": "gemm"}          # every other shape: "gemm"
 EXPECT_ROUTES = {("s1", 0): "gemm", ("s1", 1): "pair32", ("s2a", 0): "gemm", ("s2a", 1): "pair32", ("s2b", 0): "gemm",
                  ("s2b", 1): "pair32", ("s3", 0): "gemm", ("s3", 1): "pair32", ("s4", 0): "gemm", ("s4", 1): "bcast",
                  ("s5", 0): "gemm", ("s5", 1): "bcast", ("s6", 0): "gemm", ("s6", 1): "bcast"}
 # seeds of the batches and tables, per case id: chosen so that the conditions of the CPU file hold (0 unless listed)
 BOUNDARY_SEEDS = {"PairRE-s1-hinge-pw-f0": 2, "QuatE-s2a-softmax-f1": 1, "TransH-s2a-softmax-f0": 4, "PairRE-s4-logsigmoid-adv-f0": 1,
-                  "PairRE-s4-softmax-f0": 2, "QuatE-s6-logsigmoid-adv-f0": 9, "QuatE-s6-logsigmoid-adv-f1": 4}
+                  "PairRE-s4-softmax-f0": 2, "QuatE-s6-logsigmoid-adv-f0": 9, "QuatE-s6-logsigmoid-adv-f1": 4,
+                  "TransD-s1-hinge-pw-f0": 2,           # (seed 0: a hinge pair 0.93 safety units from the kink in the second step)
+                  "TransD-s2a-softmax-f0": 5}           # (seed 0: one residual gradient row in either step)
 
 
 def tiles(c):
@@ -149,11 +216,28 @@ def tiles(c):
     return dict(ti=t(c["chunk"], QT), tj=t(Np, QT), tk=t(d, QS), ragged=(c["chunk"] % QT != 0, Np % QT != 0, d % QS != 0))
 
 
+def transd_tiles(c):
+    """what a TransD case gives transd_coef_kernel and the products over the stacked operand (EXPECT_TRANSD)"""
+    Np = c["chunk"] + c["N"] if c["neg_deg"] else c["N"]
+    m, k, chunk = 2 * c["chunk"], c["d_e"] // 2, c["chunk"]
+    t = lambda x, T: (x + T - 1) // T
+    return dict(stack=t(m, STACK_TILE), tct=t(Np, TD_CT), rows=(t(chunk, TD_CR), chunk // TD_CR), kst=t(k, TILE_BK),
+                ragged=(m % STACK_TILE != 0, Np % TD_CT != 0, chunk % TD_CR != 0, k % TILE_BK != 0))
+
+
+def bwd_route(c):
+    """own_bwd_products' condition (kge_own_fwd.hpp), for the models of STACKED: N counts the in-batch rows under --neg_deg_sample"""
+    Np = c["chunk"] + c["N"] if c["neg_deg"] else c["N"]
+    return "gemm" if max(2 * c["chunk"], Np) <= GB_MAXK else "pair"
+
+
 def _boundary_cases():
     out = []
-    for sid, (shape, n_ent, n_rel, opts) in SHAPES.items():
+    for sid, (shape, n_ent, n_rel, opts) in list(SHAPES.items()) + list(S7_SHAPES.items()):
         for model in MODELS:
-            sh = QUATE_S6 if (sid == "s6" and model == "QuatE") else shape
+            if sid not in shape_ids(model):
+                continue
+            sh = case_shape(model, sid)
             for oid in opts:
                 for flags in ((0, QE.FORCE_PAIRWISE) if model == "QuatE" else (0,)):
                     c = make_case(model, sid, sh, oid, n_ent, n_rel, flags, separated=(model == "PairRE" and sh[3] >= 400))
@@ -172,9 +256,10 @@ FUZZ_WIDTH = (4, 8, 12, 20, 32, 36, 48, 64, 100)
 # (model, seed) -> dict(seed=, n_ent=, n_rel=): the batch seed and, where no seed will do, the table sizes under which the
 # conditions of the CPU file hold; the draws of the shape and the options never change.  (TransH 22 is hinge-pw on 30 entities: a
 # sampled negative equal to the edge's own entity leaves residual rows under every seed - transh_cases.residual_rows - so it
-# takes the larger entity count.)  Seeds beyond the default 24 are checked where they run.
+# takes the larger entity count.  TransD 6 is hinge at (4, 17, 64, k = 100): under seed 0 one pair of its first step lies 0.94
+# safety units from the kink.)  Seeds beyond the default 24 are checked where they run.
 FUZZ_FIX = {("QuatE", 1): dict(seed=6), ("PairRE", 14): dict(seed=1), ("TransH", 19): dict(seed=2),
-            ("TransH", 22): dict(n_ent=200)}
+            ("TransH", 22): dict(n_ent=200), ("TransD", 6): dict(seed=1)}
 
 
 def fuzz_case(model, seed):
@@ -183,6 +268,8 @@ def fuzz_case(model, seed):
     C = int(rng.randint(1, 5))
     N = int(rng.choice(FUZZ_NEG))
     d_e = int(rng.choice(FUZZ_WIDTH))
+    if model == "TransD":           # the draw is the half-width k: rows of 2 k floats, multiples of 8
+        d_e = 2 * d_e
     ids = [c["id"] for c in MOD[model].STEP_CASES]
     oid = ids[int(rng.randint(len(ids)))]
     impts = bool(rng.randint(4) == 0)
@@ -198,15 +285,20 @@ def fuzz_case(model, seed):
 # --------------------------------------------------------------------------------------------------------------------------
 # 3. heavy update lists: tests/test_gpu_parity.py::_skewed_batch at B = 600, chunk = 100, N = 64, d_e = 100 on 3000 entities and
 #    11 relations, hub_frac 0.15, rel_frac 0.5: entity 7 and relation 1 collect lists well beyond 64 entries.  No -pw
-#    (transh_cases.residual_rows).  Nothing is excluded: PairRE takes the `separated` tables.
+#    (transh_cases.residual_rows).  Nothing is excluded: PairRE takes the `separated` tables.  TransD: k = 52, rows of 104 floats.
 # --------------------------------------------------------------------------------------------------------------------------
 HEAVY_SHAPE = (6, 100, 64, 100)
+HEAVY_K_TRANSD = 52                 # TransD: rows of 104 floats
 HEAVY_ENT, HEAVY_REL, HEAVY_HUB, HEAVY_RELF = 3000, 11, 0.15, 0.5
 HEAVY_REGS = (0.0, 1e-5)
 
 
+def heavy_shape(model):
+    return HEAVY_SHAPE[:3] + (2 * HEAVY_K_TRANSD,) if model == "TransD" else HEAVY_SHAPE
+
+
 def heavy_case(model, reg):
-    c = make_case(model, "heavy", HEAVY_SHAPE, "logsigmoid-adv", HEAVY_ENT, HEAVY_REL, separated=(model == "PairRE"))
+    c = make_case(model, "heavy", heavy_shape(model), "logsigmoid-adv", HEAVY_ENT, HEAVY_REL, separated=(model == "PairRE"))
     c.update(reg_coef=reg, reg_norm=3, heavy=True)
     c["id"] = "%s-heavy-reg%g" % (model, reg)
     return c
@@ -232,6 +324,10 @@ def tables(c):
         own = rng.randint(0, 2, (c["n_rel"], d_e)) == 1
         rel = np.concatenate([np.where(own, big, small), np.where(own, small, big)], 1)
         return ent.astype(np.float32), rel.astype(np.float32)
+    if model == "TransD":           # the condition under which transd_cases.py keeps |c_j| of order 1
+        sc = np.float32(TD.row_scale(d_e // 2))
+        return (rng.uniform(-1, 1, (c["n_ent"], d_e)).astype(np.float32) * sc,
+                rng.uniform(-1, 1, (c["n_rel"], d_e)).astype(np.float32) * sc)
     return (rng.uniform(-1, 1, (c["n_ent"], d_e)).astype(np.float32),
             rng.uniform(-1, 1, (c["n_rel"], rel_width(model, d_e))).astype(np.float32))
 
@@ -389,6 +485,12 @@ def conditions(c, skewed=None):
             f["share"] = out["share"]
             if not out["share"] >= TH.DIST_SHARE:
                 bad.append(tag + ": distance share %.3g" % out["share"])
+        if c["model"] == "TransD":
+            f["share"], f["cmax"] = out["share"], out["cmax"]
+            if not out["share"] >= TD.DIST_SHARE:
+                bad.append(tag + ": distance share %.3g" % out["share"])
+            if not out["cmax"] < TD.C_MAX:
+                bad.append(tag + ": |c_j| reaches %.3g" % out["cmax"])
         if c["genre"] == "Hinge":
             out32 = statement_step(c, bt, ent, rel, np.float32)[0]
             f["kink"] = kink_clearance(c, out, out32)
@@ -490,7 +592,9 @@ HEAVY_CASES = [heavy_case(m, reg) for m in MODELS for reg in HEAVY_REGS]
 #    triples (two 128-row tiles of rank_gemm_kernel / the pair tiles, three of rank_gemm_transh_kernel's 64-query tiles, the last
 #    ragged).  Ranker batches (Eb of rank_eval_impl): 150 - one call, every row tile of it - and 64 - three calls, two of them
 #    with e0 > 0 into the filter lists.  Chunked ranking takes chunks of 100 triples: the second chunk spans two row tiles.
-#    Exact tables: the TIE_WIDE_CASES of the three case modules.  Random tables: uniform, same sizes; ranks must lie in the band
+#    TransD ranks on rank_gemm_transd_kernel's 64-query tiles too; its widths are half-widths k (rows 64 and 72 wide) and it has no
+#    relation ranking.
+#    Exact tables: the TIE_WIDE_CASES of the four case modules.  Random tables: uniform, same sizes; ranks must lie in the band
 #    [lo, hi] of the float64 scores under the score tolerance of tests/test_gpu_eval.py.
 # --------------------------------------------------------------------------------------------------------------------------
 RANK_N, RANK_E, RANK_WIDTHS = 300, 150, (32, 36)
@@ -499,7 +603,8 @@ RANK_CHUNK = 100
 RANK_TOPK = (1, 10, 128)
 RANK_LIST = 200                 # the explicit candidate list: 200 distinct entities in random order, two column tiles
 RANK_DEGENERATE = 0.90          # share of the rank intervals that must be a single rank
-RANK_ROW_TILES = {"QuatE": 128, "PairRE": 128, "TransH": 64}      # kge_tile_gemm.hpp TILE_BM; kge_rank_gemm.hip RANK_TH_BM
+RANK_ROW_TILES = {"QuatE": 128, "PairRE": 128, "TransH": 64, "TransD": 64}      # kge_tile_gemm.hpp TILE_BM; kge_rank_gemm.hip RANK_TH_BM
+#                                                   (rank_gemm_transh_kernel and rank_gemm_transd_kernel: RANK_TH_BM queries)
 RANK_COL_TILE = 128                                               # kge_tile_gemm.hpp TILE_BN
 assert all(m.TIE_WIDE_CASES == [(RANK_N, d) for d in RANK_WIDTHS] and m.TIE_WIDE_E == RANK_E and m.TIE_WIDE_CHUNK == RANK_CHUNK
            for m in MOD.values())
@@ -515,9 +620,15 @@ def rank_random_inputs(model, d_e):
     corruptions of either side (so that the filter lists of a later Ranker batch are not empty)"""
     rng = np.random.RandomState(_seed("new-model-rank-random", model, d_e))
     c = PR.Case()
-    c.n, c.d_e = RANK_N, d_e
-    c.ent = rng.uniform(-1, 1, (RANK_N, d_e)).astype(np.float32)
-    c.rel = rng.uniform(-1, 1, (RANK_N, rel_width(model, d_e))).astype(np.float32)
+    if model == "TransD":           # `d_e` is the half-width k, as for transd_cases.tie_inputs: rows of 2 k floats times row_scale(k)
+        c.n, c.k, c.d_e = RANK_N, d_e, 2 * d_e
+        sc = np.float32(TD.row_scale(d_e))
+        c.ent = rng.uniform(-1, 1, (RANK_N, 2 * d_e)).astype(np.float32) * sc
+        c.rel = rng.uniform(-1, 1, (RANK_N, 2 * d_e)).astype(np.float32) * sc
+    else:
+        c.n, c.d_e = RANK_N, d_e
+        c.ent = rng.uniform(-1, 1, (RANK_N, d_e)).astype(np.float32)
+        c.rel = rng.uniform(-1, 1, (RANK_N, rel_width(model, d_e))).astype(np.float32)
     c.h, c.r, c.t = (rng.randint(0, RANK_N, RANK_E) for _ in range(3))
     extra = []
     for i in list(range(30)) + list(range(RANK_E - 30, RANK_E)):

@@ -1,9 +1,11 @@
-"""QuatE, PairRE and TransH on the GPU across the tile, slab and list boundaries of their kernels, against the float64 statements
-of tests/quate_cases.py, tests/pairre_cases.py and tests/transh_cases.py (cases: tests/new_model_shape_cases.py; their inputs are
-guarded on the CPU by tests/test_new_model_shape_inputs.py):
+"""QuatE, PairRE, TransH and TransD on the GPU across the tile, slab and list boundaries of their kernels, against the float64
+statements of tests/quate_cases.py, tests/pairre_cases.py, tests/transh_cases.py and tests/transd_cases.py (cases:
+tests/new_model_shape_cases.py; their inputs are guarded on the CPU by tests/test_new_model_shape_inputs.py):
   1. the fused step at boundary shapes: several row tiles, column tiles and k slabs at once, degenerate and odd edges,
      --neg_deg_sample with a chunk that is no multiple of 16, streamed loss rows, the recipe width, relation rows beyond the
-     register-resident update; QuatE on its three negative-score routes;
+     register-resident update; QuatE on its three negative-score routes; TransD's column-sum workgroups with several column tiles
+     and several rows per row group, its stacked operand across row tiles; TransH and TransD on either side of the threshold
+     between the backward GEMM tiles and the pairwise backward products (s7a, s7b beyond it, s7c the last shape on the tiles);
   2. the fused step at random shapes (KGE_NEW_MODEL_FUZZ_N cases per model, 24 by default);
   3. the fused step with hub entities and a dominant relation: update lists well beyond 64 entries, with and without the regulariser;
   4. every ranking entry and the top-K selection over several row and column tiles, with Ranker batches that reach into the filter
@@ -12,7 +14,7 @@ Each step starts from the case's fixed tables (tail, then head corruption) and i
 GPU's own float32 tables: scores, loss terms, the three trace gradients, both Adagrad states, both tables.  Bounds are the suite's
 (tests/modular_op_cases.py); where the float32 statement itself is over one (new_model_shape_cases.bound_factors, measured on the
 CPU) the bound is 3 x that statement's error.  Rows left out: PairRE's sign-ambiguous ones (at most pairre_cases.ROW_CAP) and
-hinge flips under the rule and caps of tests/test_gpu_loss_options.py.
+hinge flips under the rule and caps of tests/test_gpu_loss_options.py (TransD: nothing else, and no bound factor).
 
 new_model_shape_errors.txt, written next to the suite's other reports, records per part, case and quantity the largest error over
 its bound, the rows left out, any bound factor taken from the float32 statement, and the wall time of this file."""
@@ -48,7 +50,7 @@ def _record(part, case, note="", **q):
         out = _report_dir()
         os.makedirs(out, exist_ok=True)
         with open(os.path.join(out, "new_model_shape_errors.txt"), "w") as f:
-            f.write("QuatE, PairRE and TransH at boundary, random and heavy-list shapes against float64: largest |error| / bound per part, case "
+            f.write("QuatE, PairRE, TransH and TransD at boundary, random and heavy-list shapes against float64: largest |error| / bound per part, case "
                     "and quantity (<= 1 passes), that error, its bound\n(wall time of this file up to the last record: %.0f s)\n" % (time.time() - T0))
             top = max(((v[0], p, c, k) for (p, c), r in ERRORS.items() for k, v in r.items()), default=None)
             if top:
@@ -76,7 +78,9 @@ def _dev(a):
 def _engine(c):
     from dglke_amd.engine import StepEngine
     model = c["model"]
-    eng = StepEngine(model, c["n_ent"], c["n_rel"], c["d_e"], S.engine_gamma(model), c["lr"], DEV, False, model != "QuatE", c["adv"],
+    td = model == "TransD"           # hidden dimension k, both tables doubled: rows of d_e = 2 k floats
+    eng = StepEngine(model, c["n_ent"], c["n_rel"], c["d_e"] // 2 if td else c["d_e"], S.engine_gamma(model), c["lr"], DEV, td,
+                     model != "QuatE", c["adv"],
                      c["adv_temp"], c["reg_coef"], c["reg_norm"], loss_genre=c["genre"], pairwise=c["pairwise"], margin=c["margin"],
                      flags=int(c["flags"]) | (S.PR.NEG_DEG if c["neg_deg"] else 0))
     eng.load_tables(*S.tables(c))
@@ -119,6 +123,10 @@ def run_case(c, part):
         out = ref[0]
         if c["model"] == "TransH":
             assert out["share"] >= S.TH.DIST_SHARE and S.TH.residual_rows(out) == 0, tag + ": a step input outside the conditions of transh_cases.py"
+        if c["model"] == "TransD":
+            assert out["share"] >= S.TD.DIST_SHARE and S.TD.residual_rows(out) == 0 and out["cmax"] < S.TD.C_MAX, \
+                tag + ": a step input outside the conditions of transd_cases.py"
+            assert not S.bound_factors(c, step), tag
         gp, gn = want["pos_score"].cpu().numpy(), want["neg_score"].cpu().numpy()
         excl, note = dict(S.NO_ROWS), ""
         if c["model"] == "PairRE":
@@ -155,7 +163,7 @@ def test_step_at_boundary_shapes_matches_float64(c):
 @pytest.mark.parametrize("seed", range(S.FUZZ_N))
 @pytest.mark.parametrize("model", S.MODELS)
 def test_step_random_shapes_match_float64(model, seed):
-    """part 2: random (C, chunk, N, d_e, option set, edge importance, QuatE route) - ragged tiles of every kernel of the three models"""
+    """part 2: random (C, chunk, N, d_e, option set, edge importance, QuatE route) - ragged tiles of every kernel of the four models"""
     c = S.fuzz_case(model, seed)
     bad, _ = S.conditions(c)
     assert not bad, "\n".join(bad)
@@ -165,7 +173,7 @@ def test_step_random_shapes_match_float64(model, seed):
 @pytest.mark.parametrize("c", S.HEAVY_CASES, ids=lambda c: c["id"])
 def test_step_heavy_lists_match_float64(c):
     """part 3: hub entity 7 and dominant relation 1 - update lists of hundreds of entries on an entity row and on a 2 d_e wide relation
-    row - compared as tests/test_gpu_parity.py::test_fused_step_heavy_lists_match_oracle compares, at its tolerances, nothing left out"""
+    row (TransD: both rows 104 floats, chunk 100 no multiple of its 8 row groups) - compared as tests/test_gpu_parity.py::test_fused_step_heavy_lists_match_oracle compares, at its tolerances, nothing left out"""
     for step, bt in enumerate(S.batches(c, skewed=_skewed_batch)):
         eng, b, want, ref, _, tag = _run_step(c, bt, step)
         out, ent64, es64, rel64, rs64 = ref
@@ -241,8 +249,9 @@ def _entries(model, c, ent, rel, check, check_pos):
 @pytest.mark.parametrize("model", S.MODELS)
 def test_ranking_entries_equal_float64_over_several_tiles(model, d_e):
     """part 4, exact tables: Ranker.ranks raw, filtered and on an explicit candidate list, Ranker.chunked_ranks with chunks that span
-    two row tiles (PairRE, TransH: per-chunk lists with -1 pads and self_cand too), QuatE's relation ranking and kge_topk_select
-    (PairRE, TransH: _filtered too) for K in 1, 10, 128: ranks and order EQUAL the float64 ones, scores the float32 statement's bits"""
+    two row tiles (PairRE, TransH, TransD: per-chunk lists with -1 pads and self_cand too), QuatE's relation ranking (TransD has
+    none: that entry is closed) and kge_topk_select (PairRE, TransH, TransD: _filtered too) for K in 1, 10, 128: ranks and order
+    EQUAL the float64 ones, scores the float32 statement's bits.  TransD: the parameter is the half-width k"""
     from dglke_amd import eval as kev
     Q = S.MOD[model]
     c = Q.tie_inputs(S.RANK_N, d_e, S.RANK_E)

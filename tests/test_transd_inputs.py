@@ -244,9 +244,10 @@ def test_adam_case_keeps_the_conditions_and_the_ambiguity_cap():
 # the integer-grid ranking inputs
 # --------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n,k", Q.TIE_CASES, ids=["n%d-k%d" % c for c in Q.TIE_CASES])
-def test_grid_inputs_are_exact_in_float32_and_hold_ties(n, k):
+def test_grid_inputs_are_exact_in_float32_and_hold_ties(n, k, wide_e=None, chunk=None):
     assert {c[0] for c in Q.TIE_CASES} == {5, 129, 300} and {c[1] for c in Q.TIE_CASES} == {4, 36}
-    c = Q.tie_inputs(n, k)
+    c = Q.tie_inputs(n, k) if wide_e is None else Q.tie_inputs(n, k, wide_e)      # (the several-tile sizes)
+    chunk = Q.TIE_CHUNK if chunk is None else chunk
     assert np.array_equal(c.ent, np.rint(c.ent)) and np.abs(c.ent).max() <= 2 and np.array_equal(c.rel, np.rint(c.rel))
     assert not c.ent[0, k:].any() and not c.rel[0, k:].any() and c.ent[1:, k:].any() and c.rel[1:, k:].any()
     assert Q.TIE_GAMMA == int(Q.TIE_GAMMA)
@@ -282,9 +283,9 @@ def test_grid_inputs_are_exact_in_float32_and_hold_ties(n, k):
             assert own[i] in ids
             filt_ties += int(((S[i, ids] == p[i]) & (ids != own[i])).sum())
         assert np.all(filt <= raw - 1)
-        cand = Q.tie_candidates(n, E, Q.TIE_CHUNK)
+        cand = Q.tie_candidates(n, E, chunk)
         assert (cand == -1).sum(1).min() == 2 and cand.max() < n
-        listed, selfc = (Q.chunked_ranks_of(c, p, S, neg_head, cand, sc, Q.TIE_CHUNK) for sc in (False, True))
+        listed, selfc = (Q.chunked_ranks_of(c, p, S, neg_head, cand, sc, chunk) for sc in (False, True))
         assert listed.max() > 1 and np.any(selfc != listed)
         if n > 5:
             assert m.any(1).sum() * 10 >= E, "fewer than one row in ten has a candidate that ties its positive (neg_head=%d)" % neg_head

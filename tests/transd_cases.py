@@ -40,7 +40,7 @@ import numpy as np
 import adam_cases as A
 import softmax_loss_cases as SM
 from pairre_cases import chunked_ranks_of, filter_lists, ranks_of, tie_candidates      # noqa: F401 - model-independent, re-exported
-from modular_op_cases import GRAD_RTOL, SCORE_ATOL, SCORE_RTOL, grad_bound, score_bound, worst      # noqa: F401 - re-exported
+from modular_op_cases import GB_MAXK, GRAD_RTOL, SCORE_ATOL, SCORE_RTOL, grad_bound, score_bound, worst      # noqa: F401 - re-exported
 from transh_cases import residual_rows                                                  # noqa: F401 - model-independent, re-exported
 from oracle import kge_oracle as O
 
@@ -51,6 +51,12 @@ KNOWN_SCORE = -1.0e6        # KGE_KNOWN_SCORE
 DIST_SHARE = 0.05           # TransH's value
 C_MAX = 4.0                 # |c_j| = |m_j . n_j| of every case table stays below this
 GAMMA = 4.0
+# the tile constants the shapes of tests/new_model_shape_cases.py are chosen against, read from kge_transd.hip (transd_coef_kernel:
+# a column-sum workgroup takes TD_CT columns of one chunk, its rows split over TD_CR row groups); GB_MAXK (modular_op_cases, read
+# from kge_neg_gemm.hip): beyond it own_bwd_products (kge_own_fwd.hpp) leaves the backward GEMM tiles - max(2 chunk, N) counts here,
+# the operand being stacked
+TD_CT = 32
+TD_CR = 8
 
 
 def _seed(*key):
@@ -390,6 +396,10 @@ TIE_E = 40                      # test triples
 TIE_E_WIDE = 150                # at 300 entities: three of the ranking kernel's 64-query tiles, the last of 22
 TIE_CHUNK = 16                  # chunked_ranks: two chunks of 16 and one of 8 (wide: 9 and one of 6)
 TIE_GAMMA = 6.0
+# several tiles, as pairre_cases.TIE_WIDE_CASES (tests/new_model_shape_cases.py): (entities, k) - tie_inputs takes the half-width
+TIE_WIDE_CASES = [(300, 32), (300, 36)]
+TIE_WIDE_E = 150
+TIE_WIDE_CHUNK = 100
 
 
 def tie_E(n):
