@@ -8,6 +8,7 @@
 #include <new>
 #include <algorithm>
 #include "kge_common.hpp"
+#include "kge_constrain.hpp"
 #include "kge_models.hpp"
 #include "kge_own_fwd.hpp"
 #include "kge_sampler_common.hpp"
@@ -83,6 +84,35 @@ int check_loss(int genre, int adv, int pairwise) {
     if (pairwise && adv) return fail(KGE_ERR_ARG, "loss cannot be pairwise and adversarial sampled");
     if (pairwise && genre != KGE_LOSS_LOGISTIC && genre != KGE_LOSS_HINGE)
         return fail(KGE_ERR_ARG, "this loss cannot be applied to pairwise loss function");
+    return KGE_OK;
+}
+
+// ---- the norm constraints (KGE_FLAG_ENT_NORM_* / KGE_FLAG_REL_NORM_*, include/kge_hip.h) ----
+enum : unsigned { NORM_ENT = KGE_FLAG_ENT_NORM_CLIP | KGE_FLAG_ENT_NORM_UNIT, NORM_REL = KGE_FLAG_REL_NORM_CLIP | KGE_FLAG_REL_NORM_UNIT };
+
+const char *norm_flag_name(unsigned fl) {
+    return (fl & KGE_FLAG_ENT_NORM_CLIP) ? "KGE_FLAG_ENT_NORM_CLIP" : (fl & KGE_FLAG_ENT_NORM_UNIT) ? "KGE_FLAG_ENT_NORM_UNIT" :
+           (fl & KGE_FLAG_REL_NORM_CLIP) ? "KGE_FLAG_REL_NORM_CLIP" : "KGE_FLAG_REL_NORM_UNIT";
+}
+
+// the entries that have no launch behind their update to carry the projection (sharded tables, gradient emission, the stale pipeline)
+int norm_closed(const kge_hparams *hp, const char *who) {
+    if (!hp || !(hp->flags & (NORM_ENT | NORM_REL))) return KGE_OK;
+    return fail(KGE_ERR_ARG, "%s: %s is not available here (the norm constraints run behind the update launch of the strict step on "
+                             "local tables)", who, norm_flag_name(hp->flags));
+}
+
+// the strict step: one mode per table, and a relation row that has slices (kge_models.hpp); the model id has been checked
+int check_norm(const kge_hparams *hp, const char *who) {
+    const unsigned fl = hp->flags;
+    if (!(fl & (NORM_ENT | NORM_REL))) return KGE_OK;
+    if ((fl & NORM_ENT) == NORM_ENT)
+        return fail(KGE_ERR_ARG, "%s: KGE_FLAG_ENT_NORM_CLIP and KGE_FLAG_ENT_NORM_UNIT are two modes of one table: set one", who);
+    if ((fl & NORM_REL) == NORM_REL)
+        return fail(KGE_ERR_ARG, "%s: KGE_FLAG_REL_NORM_CLIP and KGE_FLAG_REL_NORM_UNIT are two modes of one table: set one", who);
+    const kge::ModelRow *m = kge::model_row(hp->model);
+    if ((fl & NORM_REL) && m->norm.rel == 0)
+        return fail(KGE_ERR_ARG, "%s: %s is not available for %s (%s)", who, norm_flag_name(fl & NORM_REL), m->name, m->norm.rel_why);
     return KGE_OK;
 }
 
@@ -459,9 +489,14 @@ struct StepCall {
     uint32_t *known_mask = nullptr;          // ... into this buffer of the caller's, and the stand-alone loss kernel reads it
     size_t known_mask_bytes = 0;
     const AdamArgs *adam = nullptr;          // the update launch is the Adam form (kge_step_optim, KGE_OPT_ADAM)
+    const char *who = "kge_step_fused";      // the entry, as the refusals of the norm-constraint flags name it
 };
 
-static StepCall phase_call(int phases) { StepCall c; c.phases = phases; return c; }
+static StepCall phase_call(int phases, const char *who = nullptr) {
+    StepCall c; c.phases = phases;
+    if (who) c.who = who;
+    return c;
+}
 
 // every buffer of one step's workspace.  carve_step is the only description of the layout: kge_step_workspace_bytes measures
 // with it, the step carves with it.  The layout depends on (hp, B, C, chunk, N, UE, UR, copies) alone - not on the outputs asked,
@@ -675,6 +710,7 @@ int Step::setup(void *ws, size_t ws_bytes) {
                (!sh->rel_local && (sh->rel_rows_per_shard <= 0 || !sh->rel_rows || !sh->rel_state))))
         return fail(KGE_ERR_ARG, "kge_step_sharded: bad shard map");
     if (int rc = check_model(hp->model, hp->d_e, hp->d_r)) return rc;
+    if (int rc = check_norm(hp, c.who)) return rc;
     // the relation-matrix models in the gradient-emitting step: only with the relation side applied IN PLACE (emit->gr NULL, the
     // all-to-all engine under relation partitioning).  Their kernels run against the row cache like every model's, the relation
     // matrices / projection rows of the batch belong to this rank and are updated here, only entity messages leave
@@ -1098,6 +1134,19 @@ int Step::phase_update() {
     if (c.build_update) { *c.build_update = ua; return KGE_OK; }
     if (c.adam) KGE_TRY(launch_update_adam(ua, *c.adam, s));
     else KGE_TRY(launch_update(ua, s, c.tail));
+    if (hp->flags & (NORM_ENT | NORM_REL)) {
+        // the projection of the rows this update has just written, from the same plan records (kge_constrain.hip).  A step that
+        // carries a sampler job: its tail workgroups write the job's slot, the previous job's slot and the scratch
+        // (kge_sampler_tail.hpp) - never the arrays of the batch this step runs on, which this launch reads
+        const kge::NormSlices &ns = kge::model_row(hp->model)->norm;
+        ConstrainArgs ca{};
+        ca.ent = tb->ent; ca.rel = tb->rel; ca.ue_rec = b->ue_rec; ca.ur_rec = b->ur_rec; ca.counts_dev = b->counts_dev;
+        ca.UE = (hp->flags & NORM_ENT) ? b->UE : 0; ca.UR = (hp->flags & NORM_REL) ? b->UR : 0;
+        ca.d_e = d_e; ca.d_r = d_r; ca.ent_parts = ns.ent; ca.rel_parts = ns.rel;
+        ca.ent_unit = (hp->flags & KGE_FLAG_ENT_NORM_UNIT) ? ~0u : 0u;
+        ca.rel_unit = (hp->flags & KGE_FLAG_REL_NORM_UNIT) ? ~0u : ns.rel_unit;
+        KGE_TRY(launch_constrain(ca, s));
+    }
     if (copy_g0 && hipMemcpyAsync(out->g_pos_ent, emit->g0, (size_t)b->UE * d_e * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
         return fail(KGE_ERR_LAUNCH, "hipMemcpyAsync failed");
     // deterministic reduction of this step's loss terms (only when the caller wants the per-step values; running sums are
@@ -1149,6 +1198,7 @@ static int step_sampling(const kge_hparams *hp, const kge_tables *tb, const kge_
         return fail(KGE_ERR_ARG, "kge_step_fused_sampling: 2 * batch + chunks * neg <= 4096 (larger batches: build the plan on the host)");
     if (job->scratch_bytes < kge_sampler_tail_scratch_bytes(job->B, job->C, job->N, job->n_ent))
         return fail(KGE_ERR_WORKSPACE, "kge_step_fused_sampling: scratch too small (kge_sampler_tail_scratch_bytes)");
+    c.who = "kge_step_fused_sampling";
     SmpTail t{};
     t.a.H = job->heads; t.a.R = job->rels; t.a.T = job->tails; t.a.perm = job->perm; t.a.n_train = job->n_train; t.a.n_ent = job->n_ent;
     t.a.B = job->B; t.a.C = job->C; t.a.chunk = job->chunk; t.a.N = job->N; t.a.seed = job->seed; t.a.state = job->state;
@@ -1166,7 +1216,7 @@ int kge_step_fused_sampling(const kge_hparams *hp, const kge_tables *tb, const k
 int kge_step_fused_known(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
                          size_t ws_bytes, const kge_sampler_job *job, const kge_known *known, uint32_t *mask, size_t mask_bytes,
                          void *stream) {
-    StepCall c;
+    StepCall c; c.who = "kge_step_fused_known";
     if (known) { c.known = known; c.known_mask = mask; c.known_mask_bytes = mask_bytes; }
     return step_sampling(hp, tb, b, out, ws, ws_bytes, job, c, stream);
 }
@@ -1207,6 +1257,7 @@ int kge_step_async(kge_pipe *p, const kge_hparams *hp, const kge_tables *tb, con
                    const kge_step_out *out, void *ws, size_t ws_bytes, void *stream) {
     if (!p || !hp || !tb || !b || !ws) return fail(KGE_ERR_ARG, "kge_step_async: null argument");
     if (int rc = closed(kge::E_STEP_ASYNC, hp->model, "kge_step_async")) return rc;
+    if (int rc = norm_closed(hp, "kge_step_async")) return rc;
     const size_t half = (ws_bytes / 2) & ~(size_t)255;
     void *wsp = (char *)ws + (size_t)p->parity * half;
     void *wsn = (char *)ws + (size_t)(p->parity ^ 1) * half;
@@ -1277,7 +1328,7 @@ int kge_step_phase(const kge_hparams *hp, const kge_tables *tb, const kge_batch 
     if (phases & KGE_PHASE_FORWARD) ph |= PH_FWD;
     if (phases & KGE_PHASE_BACKWARD) ph |= PH_BWD;
     if (phases & KGE_PHASE_UPDATE) ph |= PH_UPDATE;
-    return run_step(hp, tb, b, out, ws, ws_bytes, stream, phase_call(ph | PH_STRICT));
+    return run_step(hp, tb, b, out, ws, ws_bytes, stream, phase_call(ph | PH_STRICT, "kge_step_phase"));
 }
 
 int kge_step_phase_known(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
@@ -1290,7 +1341,7 @@ int kge_step_phase_known(const kge_hparams *hp, const kge_tables *tb, const kge_
     if (phases & KGE_PHASE_FORWARD) ph |= PH_FWD;
     if (phases & KGE_PHASE_BACKWARD) ph |= PH_BWD;
     if (phases & KGE_PHASE_UPDATE) ph |= PH_UPDATE;
-    StepCall c = phase_call(ph | PH_STRICT);
+    StepCall c = phase_call(ph | PH_STRICT, "kge_step_phase_known");
     c.known = known; c.known_mask = mask; c.known_mask_bytes = mask_bytes;
     return run_step(hp, tb, b, out, ws, ws_bytes, stream, c);
 }
@@ -1331,7 +1382,7 @@ int kge_step_optim(const kge_hparams *hp, const kge_optim *opt, const kge_tables
         if (phases & KGE_PHASE_BACKWARD) ph |= PH_BWD;
         if (phases & KGE_PHASE_UPDATE) ph |= PH_UPDATE;
     }
-    StepCall c = phase_call(ph);
+    StepCall c = phase_call(ph, "kge_step_optim");
     c.adam = &o;
     if (known) { c.known = known; c.known_mask = mask; c.known_mask_bytes = mask_bytes; }
     return run_step(hp, tb, b, out, ws, ws_bytes, hip_stream, c);
@@ -1340,6 +1391,7 @@ int kge_step_optim(const kge_hparams *hp, const kge_optim *opt, const kge_tables
 int kge_step_grads(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, const kge_emit *emit,
                    void *ws, size_t ws_bytes, void *stream) {
     if (hp) if (int rc = closed(kge::E_STEP_GRADS, hp->model, "kge_step_grads")) return rc;
+    if (int rc = norm_closed(hp, "kge_step_grads")) return rc;
     if (!emit || !emit->g0 || (!emit->msg_rows && (!emit->gs0 || !emit->g1 || !emit->gs1)))
         return fail(KGE_ERR_ARG, "kge_step_grads: emit buffers g0/gs0/g1/gs1 are required (packed messages: g0 + msg_rows)");
     if ((emit->gr == nullptr) != (emit->gsr == nullptr))
@@ -1763,6 +1815,7 @@ int kge_step_sharded(const kge_hparams *hp, const kge_shards *sh, const kge_batc
                      const kge_step_out *out, void *ws, size_t ws_bytes, void *stream) {
     if (!sh) return fail(KGE_ERR_ARG, "kge_step_sharded: null shard map");
     if (hp) if (int rc = closed(kge::E_STEP_SHARDED, hp->model, "kge_step_sharded")) return rc;
+    if (int rc = norm_closed(hp, "kge_step_sharded")) return rc;
     // (RESCAL's relation "row" is a d_e x d_e matrix streamed by its own kernels: only the entity width is bounded)
     if (hp && (hp->d_e % 4 || hp->d_e > 1024 || (hp->model != KGE_RESCAL && (hp->d_r % 4 || hp->d_r > 1024))))
         return fail(KGE_ERR_ARG, "kge_step_sharded: row widths must be multiples of 4 and <= 1024 floats");

@@ -30,6 +30,13 @@ FLAG_ASYNC_REL = 64
 FLAG_DENSE_BWD = 256        # merged first launch: backward GEMM reads a dense copy of the negative rows (A-B aid)
 FLAG_FWD_DIRECT = 512       # merged first launch: direct fragment loads instead of the LDS pos-side tile (A-B aid)
 FLAG_LOSS_IN_FWD = 1024     # strict step: LossGenerator inside the first launch (3 launches; opt-in: measured slower, A-B aid)
+# norm constraints of radius 1 on the rows a strict step has updated (--ent_norm / --rel_norm; include/kge_hip.h)
+FLAG_ENT_NORM_CLIP = 2048
+FLAG_ENT_NORM_UNIT = 4096
+FLAG_REL_NORM_CLIP = 8192
+FLAG_REL_NORM_UNIT = 16384
+NORM_FLAGS = {'ent': {None: 0, 'none': 0, 'clip': FLAG_ENT_NORM_CLIP, 'unit': FLAG_ENT_NORM_UNIT},
+              'rel': {None: 0, 'none': 0, 'clip': FLAG_REL_NORM_CLIP, 'unit': FLAG_REL_NORM_UNIT}}
 TICKET_INTS = 4096          # kge_step_out.tickets: int32 words, zero when first handed over
 FLAG_SPLIT_FWD = 128        # strict step: edge-forward and forward GEMM as two launches (validation / A-B aid)
 PHASE_GATHER, PHASE_FORWARD, PHASE_BACKWARD, PHASE_UPDATE = 1, 2, 4, 8

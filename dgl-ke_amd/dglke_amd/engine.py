@@ -17,10 +17,14 @@ class StepEngine(object):
                  double_entity_emb=False, double_relation_emb=False, neg_adversarial_sampling=False,
                  adversarial_temperature=1.0, regularization_coef=0.0, regularization_norm=3,
                  loss_genre='Logsigmoid', pairwise=False, margin=1.0, flags=0,
-                 tables=None, shards=None, optimizer='Adagrad', adam_betas=(0.9, 0.999), adam_eps=1e-8, moments=None):
+                 tables=None, shards=None, optimizer='Adagrad', adam_betas=(0.9, 0.999), adam_eps=1e-8, moments=None,
+                 ent_norm=None, rel_norm=None):
         """optimizer 'Adam': lazy row-sparse Adam with a per-row step count (include/kge_hip.h, kge_step_optim) - the state
         tables hold the counts, the engine owns the moment tables ent_mom [n_ent, 2, d_e] / rel_mom [n_rel, 2, d_r] (`moments`:
-        a pair the caller shares between engines, as `tables` shares the rows and the state)."""
+        a pair the caller shares between engines, as `tables` shares the rows and the state).
+        ent_norm / rel_norm None | 'clip' | 'unit': the norm constraints of radius 1 on the rows every strict step has updated
+        (include/kge_hip.h, KGE_FLAG_ENT_NORM_* / KGE_FLAG_REL_NORM_*; the slices of a row: models.py).  Tables the engine creates
+        are projected whole once (`project_tables`); tables handed in are the caller's to project."""
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise _lib.KgeError("StepEngine needs a CUDA (HIP) device; there is no CPU fallback")
@@ -38,6 +42,17 @@ class StepEngine(object):
             raise _lib.KgeError(m.engine_text % (self.d_e, self.d_r))
         if m and m.single_gpu_only and shards is not None:
             raise _lib.KgeError("%s runs the strict step on local tables only (no sharded tables)" % m.name)
+        for table, mode in (('ent', ent_norm), ('rel', rel_norm)):
+            if mode not in _lib.NORM_FLAGS[table]:
+                raise _lib.KgeError("%s_norm %r: None, 'clip' or 'unit'" % (table, mode))
+        self.ent_norm = None if ent_norm == 'none' else ent_norm
+        self.rel_norm = None if rel_norm == 'none' else rel_norm
+        if self.ent_norm or self.rel_norm:
+            if shards is not None:
+                raise _lib.KgeError("the norm constraints run on the strict step of local tables only (no sharded tables)")
+            if self.rel_norm and m and m.norm_rel == 0:
+                raise _lib.KgeError("rel_norm is not available for %s (%s)" % (m.name, m.no_rel_norm))
+        flags = int(flags) | _lib.NORM_FLAGS['ent'][self.ent_norm] | _lib.NORM_FLAGS['rel'][self.rel_norm]
         hp = _lib.KgeHParams()
         hp.model = model_id(model_name)
         hp.d_e, hp.d_r = self.d_e, self.d_r
@@ -141,7 +156,7 @@ class StepEngine(object):
                    optimizer=arg('optimizer', 'Adagrad'), moments=moments,
                    adam_betas=(getattr(args, 'adam_beta1', None) if getattr(args, 'adam_beta1', None) is not None else 0.9,
                                getattr(args, 'adam_beta2', None) if getattr(args, 'adam_beta2', None) is not None else 0.999),
-                   adam_eps=arg('adam_eps', 1e-8))
+                   adam_eps=arg('adam_eps', 1e-8), ent_norm=arg('ent_norm'), rel_norm=arg('rel_norm'))
 
     def _init_adam(self, betas, eps, moments):
         if self.model_name in ('RESCAL', 'TransR'):
@@ -233,6 +248,22 @@ class StepEngine(object):
         if self.proj is not None:                 # TransRScore.reset_parameters: projection_emb.init(1.0)
             torch.nn.init.uniform_(self.proj, -1.0, 1.0)
             self.proj_state.zero_()
+        self.project_tables()
+
+    def project_tables(self):
+        """the projection of the norm constraints on EVERY row of the constrained tables, in place (torch on the device: not a hot
+        path).  Fresh tables are projected once, so that rows no step has touched yet satisfy the constraint too; a step projects
+        the rows it updates itself.  Nothing to do without ent_norm / rel_norm."""
+        m = models.MODELS[self.model_name]
+        for table, mode, t in (('ent', getattr(self, 'ent_norm', None), self.ent), ('rel', getattr(self, 'rel_norm', None), self.rel)):
+            modes = models.norm_slices(m, table, mode)
+            if not modes:
+                continue
+            x = t.view(t.shape[0], len(modes), -1)
+            for k, md in enumerate(modes):
+                n = x[:, k].norm(dim=1, keepdim=True)
+                scale = (n > 0) & (n != 1) if md == 'unit' else n > 1
+                x[:, k] = torch.where(scale, x[:, k] / n, x[:, k])
 
     def load_tables(self, ent, rel, ent_state=None, rel_state=None, ent_mom=None, rel_mom=None):
         """rows, state (Adagrad: running mean squares; Adam: per-row counts) and, under Adam, the moment tables [n, 2, d];

@@ -20,18 +20,23 @@ Model = namedtuple('Model', [
     'no_relation_ranking_lib',     # ... in the words of eval.relation_ranks
     'rank_cands', 'topk_row',      # workspace facts: candidates a rank / top-K workspace is sized for per candidate; floats per top-K query row
     'rank_rel_as',                 # relation ranking takes this model's workspace layout followed by the normalised relation table
+    'norm_ent', 'norm_rel',        # --ent_norm / --rel_norm: equal slices of an entity / relation row, each projected on its own (norm_rel 0: refused)
+    'norm_rel_unit',               # ... bit k: relation slice k is normalised to length 1 under either relation mode (TransH's w)
+    'no_rel_norm',                 # ... None, or why --rel_norm does not apply
     'projection', 'relation_matrix', 'alias_of'])     # TransR's third table; RESCAL's relation rows are matrices; TransE is TransE_l2
 
 
 def _model(name, id, score, score_args=(), **kw):
     d = dict.fromkeys(Model._fields)
     d.update(name=name, id=id, score=score, score_args=score_args, rank_cands=1, topk_row=lambda d_e: d_e, multiple_first=False,
-             single_gpu_only=False, no_stale_pipeline=False, projection=False, relation_matrix=False)
+             single_gpu_only=False, no_stale_pipeline=False, projection=False, relation_matrix=False, norm_ent=1, norm_rel=1,
+             norm_rel_unit=0)
     d.update(kw)
     return Model(**d)
 
 
 _LOCAL = dict(single_gpu_only=True, no_stale_pipeline=True)
+_OWN_REL = dict(norm_rel=0, no_rel_norm="its relation-side tables are updated by kernels of their own")
 _TWO_PROJECTIONS = dict(no_relation_ranking="the relation row enters through two projections",
                         no_relation_ranking_lib="the relation row enters through two projections: no relation ranking")
 
@@ -39,11 +44,11 @@ MODELS = OrderedDict((m.name, m) for m in (       # in the order of the --model_
     _model('TransE', 1, 'TransEScore', ('gamma', 'l2'), alias_of='TransE_l2'),
     _model('TransE_l1', 0, 'TransEScore', ('gamma', 'l1')),
     _model('TransE_l2', 1, 'TransEScore', ('gamma', 'l2')),
-    _model('TransR', 7, 'TransRScore', projection=True),
-    _model('RESCAL', 6, 'RESCALScore', relation_matrix=True),
+    _model('TransR', 7, 'TransRScore', projection=True, **_OWN_REL),
+    _model('RESCAL', 6, 'RESCALScore', relation_matrix=True, **_OWN_REL),
     _model('DistMult', 2, 'DistMultScore'),
     _model('ComplEx', 3, 'ComplExScore'),
-    _model('RotatE', 4, 'RotatEScore', ('gamma', 'emb_init')),
+    _model('RotatE', 4, 'RotatEScore', ('gamma', 'emb_init'), norm_rel=0, no_rel_norm="the row holds phases"),
     _model('SimplE', 5, 'SimplEScore'),
     _model('QuatE', 8, 'QuatEScore', ent_multiple=4, rel_width=lambda d_e: d_e, de='tied', dr='tied',
            flags_text="QuatE: the relation width must equal the entity width: pass -dr together with -de (and neither alone)",
@@ -60,7 +65,7 @@ MODELS = OrderedDict((m.name, m) for m in (       # in the order of the --model_
            loaded_text="PairRE: rows of %d (entity) and %d (relation) values: the relation row must be twice as wide",
            no_relation_ranking="the score is not a product with the relation row",
            no_relation_ranking_lib="the score is not a product of a query row and the relation row: no relation ranking",
-           topk_row=lambda d_e: 2 * d_e, **_LOCAL),
+           topk_row=lambda d_e: 2 * d_e, norm_rel=2, **_LOCAL),                           # [rH | rT]
     _model('TransH', 12, 'TransHScore', ('gamma',), ent_multiple=4, rel_width=lambda d_e: 2 * d_e, de=False, dr=True,
            flags_text="TransH: the relation row [d | w] is twice as wide as the entity row: pass -dr without -de (got%(de)s%(dr)s)",
            cli_multiple=4, cli_of='hidden_dim', multiple_text="TransH: --hidden_dim must be a multiple of 4 (got %(hidden)d)",
@@ -69,7 +74,8 @@ MODELS = OrderedDict((m.name, m) for m in (       # in the order of the --model_
                        "(-dr without -de; got %d, %d)",
            loaded_text="TransH: rows of %d (entity) and %d (relation) values: the entity width must be a multiple of 4 and the "
                        "relation row twice as wide",
-           topk_row=lambda d_e: 2 * d_e + 1, **dict(_LOCAL, **_TWO_PROJECTIONS)),
+           topk_row=lambda d_e: 2 * d_e + 1, norm_rel=2, norm_rel_unit=2,                 # [d | w], |w| = 1
+           **dict(_LOCAL, **_TWO_PROJECTIONS)),
     _model('TransD', 14, 'TransDScore', ('gamma',), ent_multiple=8, rel_width=lambda d_e: d_e, de=True, dr=True,
            flags_text="TransD: entity rows [e | e_p] and relation rows [r | r_p] are both twice --hidden_dim: pass -de and -dr "
                       "(got%(de)s%(cdr)s)",
@@ -78,7 +84,8 @@ MODELS = OrderedDict((m.name, m) for m in (       # in the order of the --model_
            engine_text="TransD needs entity and relation rows of the same width, two halves of a multiple of 4 each "
                        "(-de and -dr, --hidden_dim %% 4 == 0; got %d, %d)",
            loaded_text="TransD: rows of %d (entity) and %d (relation) values: both must be [x | x_p], the same width and a multiple of 8",
-           rank_cands=2, topk_row=lambda d_e: d_e + 2, **dict(_LOCAL, **_TWO_PROJECTIONS)),
+           rank_cands=2, topk_row=lambda d_e: d_e + 2, norm_ent=2, norm_rel=2,            # [e | e_p], [r | r_p]
+           **dict(_LOCAL, **_TWO_PROJECTIONS)),
 ))
 NAMES = list(MODELS)                                                 # the --model_name choices
 DEFAULT = 'TransE'                                                   # ... and its default
@@ -95,3 +102,20 @@ def own_relation_update(m):
     """TransR and RESCAL update their relation-side tables (projection matrices, relation matrices) with kernels of their own: no
     update pipeline, no Adam, and on several GPUs those tables stay with the trainer that holds the relation's edges"""
     return m.projection or m.relation_matrix
+
+
+NORM_MODES = ('none', 'clip', 'unit')                                # the --ent_norm / --rel_norm choices
+
+
+def norm_slices(m, table, mode):
+    """the slices of a row of `table` ('ent' / 'rel') under --ent_norm / --rel_norm `mode` as a list of modes, one per slice
+    ('clip' / 'unit'); [] where the mode is none.  A model whose relation row has no slices (norm_rel 0) raises ValueError."""
+    if mode in (None, 'none'):
+        return []
+    if mode not in ('clip', 'unit'):
+        raise ValueError("norm mode %r: none, clip or unit" % (mode,))
+    parts = m.norm_ent if table == 'ent' else m.norm_rel
+    if parts == 0:
+        raise ValueError("%s: --rel_norm does not apply (%s)" % (m.name, m.no_rel_norm))
+    forced = 0 if table == 'ent' else m.norm_rel_unit
+    return ['unit' if (forced >> k) & 1 else mode for k in range(parts)]

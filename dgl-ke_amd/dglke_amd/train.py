@@ -127,6 +127,15 @@ class ArgParser(argparse.ArgumentParser):
         a('--adam_beta1', type=float, default=0.9, help='--optimizer Adam: decay of the first moment')
         a('--adam_beta2', type=float, default=0.999, help='--optimizer Adam: decay of the second moment')
         a('--adam_eps', type=float, default=1e-8, help='--optimizer Adam: the term added to the root of the second moment')
+        a('--ent_norm', default='none', choices=list(models.NORM_MODES),
+          help='norm constraint of radius 1 on the entity rows every step has updated, applied by one more launch behind the update: '
+               'clip scales a row onto the unit sphere only when its norm exceeds 1 (TransH / TransR / TransD: |e| <= 1), unit every '
+               'non-zero row (TransE: |e| = 1).  TransD: the halves [e | e_p] each on their own.  Fresh tables are projected once, whole.  '
+               'One GPU; not with --async_update_pipeline or --async_update_rel')
+        a('--rel_norm', default='none', choices=list(models.NORM_MODES),
+          help='the same on the relation rows.  PairRE [rH | rT] and TransD [r | r_p]: the halves each on their own; TransH [d | w]: d '
+               'by the mode, w always to length 1.  Not for RotatE (the row holds phases), RESCAL and TransR (their relation-side '
+               'tables are updated by kernels of their own)')
         a('--dist_slack', type=float, default=None,
           help='--dist_mode a2a: initial capacity of an owner bucket as a multiple of the mean share of a batch\'s unique entities '
                '(default 1.5, or KGE_DIST_SLACK); buckets grow by themselves when a group of batches needs more')
@@ -454,8 +463,10 @@ class _Trainer(object):
                     timed = None
                 t_interval = 0.0
                 if self.world == 1:
-                    print('[proc {}]sample+forward+backward+update (fused HIP step, {}{}{}{}{}): {:.3f}'.format(
+                    norms = getattr(self, 'norms', (None, None))
+                    print('[proc {}]sample+forward+backward+update (fused HIP step, {}{}{}{}{}{}): {:.3f}'.format(
                         0, args.optimizer, ', --async_update pipeline' if self.lanes[0].async_update else '',
+                        ''.join(', --%s_norm %s' % (t, v) for t, v in zip(('ent', 'rel'), norms) if v),
                         ', known training triples excluded' if self.known is not None else '',
                         {None: '', 'subsampling': ', subsampling weights', 'file': ', edge importance on the device'}[self.weighted],
                         '' if self.n_lanes == 1 else ', %d concurrent trainers' % self.n_lanes, t_train))
@@ -498,6 +509,13 @@ class Trainer(_Trainer):
         self.model = m = KEModel(args, args.model_name, dataset.n_entities, dataset.n_relations, args.hidden_dim,
                                  args.gamma, double_entity_emb=args.double_ent, double_relation_emb=args.double_rel)
         self.step_flags = int(m.engine.hp.flags)
+        self.norms = norm_constraints(args)
+        if any(self.norms):
+            # fresh tables, whole, once: rows no step has touched yet satisfy the constraint too (a --resume puts its tables back
+            # over them and they are not projected again)
+            m.engine.project_tables()
+            print('[Train] --ent_norm {}, --rel_norm {}: every step projects the rows it has updated (radius 1); the fresh tables '
+                  'were projected once'.format(self.norms[0] or 'none', self.norms[1] or 'none'))
         self.n_lanes = max(1, int(args.num_proc))
         # entity-only deferral (the reference's --async_update) runs as the strict step unless the pipeline is asked for: with the
         # relation trace landing between two steps the pipeline needs one more launch than it hides
@@ -910,6 +928,32 @@ def check_optimizer(args):
         raise KgeError("--optimizer Adam: --adam_eps must be positive (got %g)" % args.adam_eps)
 
 
+def norm_constraints(args):
+    """(--ent_norm, --rel_norm) with 'none' as None"""
+    return tuple(None if getattr(args, k, 'none') in (None, 'none') else getattr(args, k) for k in ('ent_norm', 'rel_norm'))
+
+
+def check_norm_constraints(args):
+    """--ent_norm / --rel_norm run as a launch behind the update launch of the strict single-table step: refused here, before
+    anything is loaded, what has no such launch and the relation rows that have no slices (models.py)"""
+    ent_norm, rel_norm = norm_constraints(args)
+    if not ent_norm and not rel_norm:
+        return
+    flag = "--ent_norm" if ent_norm else "--rel_norm"
+    if len(args.gpu) > 1:
+        raise KgeError("%s is not available on more than one GPU (--gpu takes one entry): sharded tables have no constraint launch"
+                       % flag)
+    if args.async_update_pipeline:
+        raise KgeError("%s is not available with --async_update_pipeline (the one-step-stale pipeline has no launch behind its "
+                       "update); plain --async_update runs the strict step and is fine" % flag)
+    if args.async_update_rel:
+        raise KgeError("%s is not available with --async_update_rel (the one-step-stale pipeline has no launch behind its "
+                       "update); plain --async_update runs the strict step and is fine" % flag)
+    m = models.MODELS[args.model_name]
+    if rel_norm and m.norm_rel == 0:
+        raise KgeError("--rel_norm is not available for %s (%s)" % (m.name, m.no_rel_norm))
+
+
 def check_loss_flags(args):
     """--loss_genre Softmax (cross-entropy of the positive against its row): the softmax is the weighting and the row is the pairing"""
     if args.loss_genre != 'Softmax':
@@ -963,6 +1007,7 @@ def main(argv=None, before_train=None):
     check_model_flags(args)                      # before anything is loaded or created
     check_weighted_device_sampler(args)          # before anything is loaded or created
     check_optimizer(args)                        # before anything is loaded or created
+    check_norm_constraints(args)                 # before anything is loaded or created
     ckpt.check_flags(args)                       # before anything is loaded or created
     if args.neg_deg_sample_eval:                # before anything is loaded or created
         if len(args.gpu) > 1:

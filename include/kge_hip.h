@@ -232,6 +232,30 @@ enum kge_status {
  * the 4-launch step, TransE_l2 equal within the rounding of |a|^2, |b|^2 (summed by the tiles instead of by edge_fwd). */
 #define KGE_FLAG_LOSS_IN_FWD 1024u
 
+/* ---- norm constraints of radius 1 on the rows a strict step has just updated (csrc/kge_constrain.hip) ----
+ * The papers of the translation family state their models under them (TransE |e| = 1; TransH |e| <= 1, |w| = 1; TransR / TransD
+ * |e|, |r|, |e_p|, |r_p| <= 1).  With one of these bits set, ONE more launch follows the update launch of kge_step_fused,
+ * kge_step_fused_known, kge_step_fused_sampling, kge_step_optim (both optimizers) and the UPDATE group of kge_step_phase /
+ * kge_step_phase_known.  It reads the plan records the update launch read (ue_rec / ur_rec, counts_dev) and projects every unique
+ * entity row of the batch's union - positive ends and negatives alike - and, with a relation bit, every unique relation row:
+ *   a row is split into equal slices (one for most models; PairRE's relation row [rH | rT], TransH's [d | w], TransD's [e | e_p] and
+ *   [r | r_p] into two; csrc/kge_models.hpp); per slice n = sqrtf(sum x^2) in fp32, s = 1.0f / n, x <- x * s
+ *     CLIP: only when n > 1 (a NaN norm leaves the slice alone);
+ *     UNIT: when n > 0 and n != 1 (a zero slice stays zero).
+ *   A slice that is not scaled keeps its bits.  Only row values change: Adagrad state, Adam moments and counts are untouched.
+ *   TransH with either relation bit: d by the bit's mode, w always UNIT (the score does not change: the kernels normalise w anyway).
+ * No workspace bytes are added; nothing depends on the host (graphs replay as before).  KGE_ERR_ARG before any launch: both bits of
+ * one table; a relation bit for RotatE (the row holds phases), RESCAL or TransR (their relation-side tables are updated by kernels
+ * of their own); any of the four bits in kge_step_sharded, kge_step_grads and kge_step_async.  The radius is 1. */
+/* entity rows: scale a slice onto the unit sphere only when its norm exceeds 1 */
+#define KGE_FLAG_ENT_NORM_CLIP 2048u
+/* entity rows: scale every non-zero slice onto the unit sphere */
+#define KGE_FLAG_ENT_NORM_UNIT 4096u
+/* relation rows: as KGE_FLAG_ENT_NORM_CLIP (TransH: w is normalised to length 1 all the same) */
+#define KGE_FLAG_REL_NORM_CLIP 8192u
+/* relation rows: as KGE_FLAG_ENT_NORM_UNIT */
+#define KGE_FLAG_REL_NORM_UNIT 16384u
+
 int         kge_abi_version(void);
 const char *kge_last_error(void);
 
