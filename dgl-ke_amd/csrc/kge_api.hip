@@ -552,7 +552,9 @@ static size_t carve_step(Carver &cv, StepBufs &w, const kge_hparams *hp, int B_,
     return cv.off;
 }
 
+static size_t ova_workspace_bytes(const kge_hparams *hp, int B, int UE, int UR);
 size_t kge_step_workspace_bytes(const kge_hparams *hp, int B, int C, int chunk, int N, int UE, int UR) {
+    if (hp && N == 0) return ova_workspace_bytes(hp, B, UE, UR);      // no sampled negatives: the 1-vs-all step of kge_step_fused
     Carver cv; StepBufs w; return carve_step(cv, w, hp, B, C, chunk, N, UE, UR, false);
 }
 
@@ -1174,8 +1176,11 @@ static int run_step(const kge_hparams *hp, const kge_tables *tb, const kge_batch
     return KGE_OK;
 }
 
+static int step_one_vs_all(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
+                           size_t ws_bytes, void *stream);
 int kge_step_fused(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b,
                    const kge_step_out *out, void *ws, size_t ws_bytes, void *stream) {
+    if (hp && tb && b && ws && b->N == 0) return step_one_vs_all(hp, tb, b, out, ws, ws_bytes, stream);      // every entity a candidate
     return run_step(hp, tb, b, out, ws, ws_bytes, stream);
 }
 
@@ -1386,6 +1391,104 @@ int kge_step_optim(const kge_hparams *hp, const kge_optim *opt, const kge_tables
     c.adam = &o;
     if (known) { c.known = known; c.known_mask = mask; c.known_mask_bytes = mask_bytes; }
     return run_step(hp, tb, b, out, ws, ws_bytes, hip_stream, c);
+}
+
+// ---- 1-vs-all softmax: every entity of the table is a candidate of every edge (kge_onevsall.hip) ----
+struct OvaBufs { float *A, *P, *dP, *part, *lse, *coef, *GAp, *GH, *GT, *GR, *row_pos, *row_neg, *reg_ent, *reg_rel; };
+// (the layout depends on (hp, B, UE, UR) alone: the split buffers take the largest split counts any table size gives)
+static size_t carve_ova(Carver &cv, OvaBufs &w, const kge_hparams *hp, int B_, int UE, int UR) {
+    w = OvaBufs{};
+    const size_t B = B_, d_e = hp->d_e, d_r = hp->d_r;
+    const OvaGeom g = ova_geom(B_, hp->d_e, 1);
+    w.A = cv.f(B * d_e); w.P = cv.f(B); w.dP = cv.f(B);
+    w.part = cv.f((size_t)ova_max_splits(g.RT) * B * 2); w.lse = cv.f(B); w.coef = cv.f(B);
+    w.GAp = cv.f((size_t)ova_max_parts(g.RT, g.nslab) * B * d_e);
+    w.GH = cv.f(B * d_e); w.GT = cv.f(B * d_e); w.GR = cv.f(B * d_r);
+    w.row_pos = cv.f(B); w.row_neg = cv.f(B); w.reg_ent = cv.f(UE); w.reg_rel = cv.f(UR);
+    return cv.off;
+}
+static bool ova_width_ok(int d_e) { return d_e >= 4 && d_e <= 512 && d_e % 4 == 0; }
+
+static size_t ova_workspace_bytes(const kge_hparams *hp, int B, int UE, int UR) {
+    if (B <= 0 || UE < 0 || UR < 0 || !ova_width_ok(hp->d_e) || hp->d_r <= 0) return 0;
+    Carver cv; OvaBufs w; return carve_ova(cv, w, hp, B, UE, UR);
+}
+
+static int step_one_vs_all(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
+                           size_t ws_bytes, void *stream) {
+    const char *who = "kge_step_fused, N == 0 (1-vs-all)";
+    if (!hp || !tb || !b || !ws) return fail(KGE_ERR_ARG, "%s: null argument", who);
+    const kge::ModelRow *mr = kge::model_row(hp->model);
+    if (!mr) return fail(KGE_ERR_ARG, "unknown model %d", hp->model);
+    if (mr->closed & kge::E_STEP_ONE_VS_ALL)
+        return fail(KGE_ERR_ARG, "%s: not available for %s (DistMult and ComplEx only: the other models' scores are no plain product a . e)", who, mr->name);
+    if (int rc = check_model(hp->model, hp->d_e, hp->d_r)) return rc;
+    if (hp->loss_genre != KGE_LOSS_SOFTMAX) return fail(KGE_ERR_ARG, "%s: loss_genre must be KGE_LOSS_SOFTMAX (got %d)", who, hp->loss_genre);
+    if (hp->adv) return fail(KGE_ERR_ARG, "%s: adv must be 0 (the softmax is the weighting)", who);
+    if (hp->pairwise) return fail(KGE_ERR_ARG, "%s: pairwise must be 0", who);
+    if (!ova_width_ok(hp->d_e))
+        return fail(KGE_ERR_ARG, "%s: needs d_e %% 4 == 0 and 4 <= d_e <= 512 (got %d)", who, hp->d_e);
+    if (hp->flags & (NORM_ENT | NORM_REL))
+        return fail(KGE_ERR_ARG, "%s: %s is not available here (the dense trace updates every entity row)", who, norm_flag_name(hp->flags));
+    if (hp->flags & KGE_FLAG_NEG_DEG_SAMPLE) return fail(KGE_ERR_ARG, "%s: KGE_FLAG_NEG_DEG_SAMPLE is not available here (there are no sampled negatives)", who);
+    if (out && (out->neg_score || out->g_neg))
+        return fail(KGE_ERR_ARG, "%s: kge_step_out.neg_score / g_neg do not exist in this step (scores and candidate gradients are never stored)", who);
+    if (b->B <= 0 || b->C <= 0 || b->chunk <= 0 || (int64_t)b->C * b->chunk != b->B)
+        return fail(KGE_ERR_ARG, "%s: need C*chunk == B (B=%d C=%d chunk=%d)", who, b->B, b->C, b->chunk);
+    if (!tb->ent || !tb->ent_state || !tb->rel || !tb->rel_state || tb->n_ent <= 0 || !b->h_gid || !b->t_gid || !b->rel_ids || !b->ue_id ||
+        !b->ue_pos_ptr || !b->ue_pos_adj || !b->ur_id || !b->ur_ptr || !b->ur_edge || !b->ue_rec || !b->ur_rec)
+        return fail(KGE_ERR_ARG, "%s: null table / batch pointer", who);
+    Carver cv(ws, ws_bytes); OvaBufs w;
+    const size_t need = carve_ova(cv, w, hp, b->B, b->UE, b->UR);
+    if (need > ws_bytes) return fail(KGE_ERR_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+    hipStream_t s = (hipStream_t)stream;
+    const int B = b->B, d_e = hp->d_e, d_r = hp->d_r;
+    const bool reg = hp->reg_coef > 0.f && hp->reg_norm > 0, want4 = out && out->loss4;
+    const float rot_div = rot_div_of(hp->emb_init);
+    float *P = (out && out->pos_score) ? out->pos_score : w.P, *GR = (out && out->g_rel) ? out->g_rel : w.GR;
+    float *acc = out ? out->loss_accum : nullptr;
+    const EdgeSrc src{tb->ent, b->h_gid, tb->ent, b->t_gid, tb->rel, b->rel_ids, kge::ShardMap{}, kge::ShardMap{}};
+    // edge_fwd: A, pos_score (the criterion reads p with its row: no positive part here)
+    EdgeFwdArgs ef;
+    fill_edge(ef, src, hp->model, B, d_e, d_r, b->neg_head, hp->gamma, rot_div);
+    ef.pos_score = P; ef.A = w.A; ef.do_pos_loss = 0; ef.lp = LossParams{KGE_LOSS_SOFTMAX, 0, 1, hp->adv_temp, hp->margin};
+    ef.w = b->edge_w; ef.w_mean = b->edge_w_mean; ef.dpos = w.dP;
+    KGE_TRY(launch_edge_fwd(ef, s));
+    OvaArgs oa{};
+    oa.B = B; oa.d = d_e; oa.n_ent = tb->n_ent; oa.g = ova_geom(B, d_e, tb->n_ent);
+    oa.A = w.A; oa.ent = tb->ent; oa.ent_state = tb->ent_state; oa.part = w.part; oa.pos = P; oa.w = b->edge_w;
+    oa.lse = w.lse; oa.coef = w.coef; oa.dpos = w.dP; oa.row_pos = want4 ? w.row_pos : nullptr; oa.row_neg = want4 ? w.row_neg : nullptr;
+    oa.acc = acc; oa.GAp = w.GAp; oa.lr = hp->lr; oa.eps = hp->eps;
+    KGE_TRY(launch_ova_fwd(oa, s));
+    KGE_TRY(launch_ova_lse(oa, s));
+    KGE_TRY(launch_ova_bwd_a(oa, s));
+    // per-edge h / t / r gradient rows from dpos and the GA parts, read from the rows as they are BEFORE the dense trace
+    EdgeBwdArgs eb;
+    fill_edge_bwd(eb, src, hp->model, B, d_e, d_r, b->neg_head, hp->gamma, rot_div, w.dP, w.GAp);
+    eb.reg_coef = reg ? hp->reg_coef : 0.f; eb.reg_norm = hp->reg_norm;
+    eb.GH = w.GH; eb.GT = w.GT; eb.GR = GR; eb.ga_parts = oa.g.Sa; eb.ga_stride = (int64_t)B * d_e;
+    KGE_TRY(launch_edge_bwd(eb, s));
+    KGE_TRY(launch_ova_bwd_e(oa, s));                 // the dense trace: every entity row and its state
+    // the update launch, on a plan without negative entries (no record has a negative list: GN is never read; a valid pointer all the same)
+    UpdateArgs ua{};
+    ua.model_d_e = d_e; ua.d_r = d_r; ua.reg_norm = hp->reg_norm; ua.UE = b->UE; ua.UR = b->UR;
+    ua.lr = hp->lr; ua.eps = hp->eps; ua.reg_coef = reg ? hp->reg_coef : 0.f;
+    ua.ent = tb->ent; ua.ent_state = tb->ent_state; ua.rel = tb->rel; ua.rel_state = tb->rel_state;
+    ua.ue_id = b->ue_id; ua.ue_pos_ptr = b->ue_pos_ptr; ua.ue_pos_adj = b->ue_pos_adj; ua.ue_neg_ptr = b->ue_neg_ptr; ua.ue_neg_slot = b->ue_neg_slot;
+    ua.ur_id = b->ur_id; ua.ur_ptr = b->ur_ptr; ua.ur_edge = b->ur_edge; ua.ue_rec = b->ue_rec; ua.ur_rec = b->ur_rec; ua.counts_dev = b->counts_dev;
+    ua.GH = w.GH; ua.GT = w.GT; ua.GN = w.GH; ua.GR = GR; ua.neg_head = b->neg_head; ua.P = w.GH; ua.GA = w.GAp; ua.acc = acc;
+    ua.reg_ent = want4 ? w.reg_ent : nullptr; ua.reg_rel = want4 ? w.reg_rel : nullptr;
+    ua.ld_e = d_e; ua.ld_r = d_r; ua.ld_gs_e = 1; ua.ld_gs_r = 1;
+    if (out && out->g_pos_ent) ua.g0 = out->g_pos_ent;
+    KGE_TRY(launch_update(ua, s));
+    if (want4) {
+        FinalizeArgs f{};
+        f.B = B; f.UE = b->UE; f.UR = b->UR; f.pos_row = 1;
+        f.row_pos = w.row_pos; f.row_neg = w.row_neg; f.reg_ent = w.reg_ent; f.reg_rel = w.reg_rel;
+        f.counts_dev = b->counts_dev; f.loss4 = out->loss4;
+        KGE_TRY(launch_finalize(f, s));
+    }
+    return KGE_OK;
 }
 
 int kge_step_grads(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, const kge_emit *emit,

@@ -931,3 +931,42 @@ int neg_bwd_lc_splits(int model, int C, int chunk, int N, int d_e);   // ga_part
 int neg_bwd_lc_nrw(int model, int C, int chunk, int d_e);      // row groups whose partials gn_reduce sums
 struct EdgeBwdArgs;
 int launch_edge_bwd_with_gn_reduce(const EdgeBwdArgs &a, const NegArgs &n, int nrw, hipStream_t s);
+// ---- 1-vs-all softmax (kge_onevsall.hip; kge_step_fused on a batch with N == 0) ----
+// Every entity of the table is a candidate of every edge: s_ij = a_i . e_j.  No score is stored: the forward keeps a running
+// (max, sum-exp) pair per row and split, the two backward kernels recompute their score tiles.
+struct OvaGeom {                     // how the launches cut the [B, n_ent] score matrix; a function of (B, d, n_ent) alone
+    int RT, NT;                      // 128-edge row tiles, 128-entity column tiles
+    int S, tps;                      // forward: splits of the column tiles, tiles per split (no split is empty)
+    int Sa, tpa;                     // GA kernel: the same for its own, smaller split count (one GA part per split)
+    int nj, nslab;                   // GA kernel: 16-column blocks per wavefront (<= 4), groups of 64 * nj columns per row
+};
+// the split counts never exceed these, whatever the table's size: the workspace is sized by them, from (B, d) alone
+inline int ova_max_splits(int RT) { return 512 / RT > 1 ? 512 / RT : 1; }
+inline int ova_max_parts(int RT, int nslab) { return 256 / (RT * nslab) > 1 ? 256 / (RT * nslab) : 1; }
+inline OvaGeom ova_geom(int B, int d, int64_t n_ent) {
+    OvaGeom g{};
+    g.RT = (B + 127) / 128; g.NT = (int)((n_ent + 127) / 128);
+    const int want = ova_max_splits(g.RT);                        // two workgroups per CU: 72 KB of LDS each
+    g.tps = (g.NT + want - 1) / want; g.S = (g.NT + g.tps - 1) / g.tps;
+    g.nj = (d + 63) / 64 < 4 ? (d + 63) / 64 : 4; g.nslab = (d + 64 * g.nj - 1) / (64 * g.nj);
+    const int wa = ova_max_parts(g.RT, g.nslab);                  // one per CU: the accumulators fill the register file
+    g.tpa = (g.NT + wa - 1) / wa; g.Sa = (g.NT + g.tpa - 1) / g.tpa;
+    return g;
+}
+struct OvaArgs {
+    int B, d; int64_t n_ent;
+    OvaGeom g;
+    const float *A;                  // [B, d] per-edge operands (edge_fwd)
+    float *ent, *ent_state;          // the table: read by every kernel, its rows and state updated by ova_bwd_e alone
+    float *part;                     // [S, B, 2] forward: (max, sum-exp) of row i over split s
+    const float *pos, *w;            // [B] positive scores; edge weights or null
+    float *lse, *coef, *dpos;        // [B] log-sum-exp, w_i / B, dL/dp_i = -w_i / B
+    float *row_pos, *row_neg;        // [B] per-row loss terms for the finalize launch (0, w_i (lse_i - p_i) / B) or null
+    float *acc;                      // [4][KGE_ACC_SLOTS] running sums or null
+    float *GAp;                      // [Sa, B, d] dL/da in parts, one per split (edge_bwd adds them in part order)
+    float lr, eps;
+};
+int launch_ova_fwd(const OvaArgs &a, hipStream_t s);
+int launch_ova_lse(const OvaArgs &a, hipStream_t s);
+int launch_ova_bwd_a(const OvaArgs &a, hipStream_t s);
+int launch_ova_bwd_e(const OvaArgs &a, hipStream_t s);

@@ -18,13 +18,15 @@ class StepEngine(object):
                  adversarial_temperature=1.0, regularization_coef=0.0, regularization_norm=3,
                  loss_genre='Logsigmoid', pairwise=False, margin=1.0, flags=0,
                  tables=None, shards=None, optimizer='Adagrad', adam_betas=(0.9, 0.999), adam_eps=1e-8, moments=None,
-                 ent_norm=None, rel_norm=None):
+                 ent_norm=None, rel_norm=None, one_vs_all=False):
         """optimizer 'Adam': lazy row-sparse Adam with a per-row step count (include/kge_hip.h, kge_step_optim) - the state
         tables hold the counts, the engine owns the moment tables ent_mom [n_ent, 2, d_e] / rel_mom [n_rel, 2, d_r] (`moments`:
         a pair the caller shares between engines, as `tables` shares the rows and the state).
         ent_norm / rel_norm None | 'clip' | 'unit': the norm constraints of radius 1 on the rows every strict step has updated
         (include/kge_hip.h, KGE_FLAG_ENT_NORM_* / KGE_FLAG_REL_NORM_*; the slices of a row: models.py).  Tables the engine creates
-        are projected whole once (`project_tables`); tables handed in are the caller's to project."""
+        are projected whole once (`project_tables`); tables handed in are the caller's to project.
+        one_vs_all: the 1-vs-all softmax step (include/kge_hip.h, kge_step_fused on a batch with N == 0): every entity of the table is a candidate
+        of every edge, batches carry N == 0.  DistMult / ComplEx, Softmax, Adagrad, local tables; `step` alone drives it."""
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise _lib.KgeError("StepEngine needs a CUDA (HIP) device; there is no CPU fallback")
@@ -111,6 +113,9 @@ class StepEngine(object):
                 if len(tables) < 6:
                     raise _lib.KgeError("TransR needs tables = (ent, ent_state, rel, rel_state, proj, proj_state)")
                 self.proj, self.proj_state = tables[4], tables[5]
+        self.one_vs_all = bool(one_vs_all)
+        if self.one_vs_all:
+            self._check_one_vs_all(m, loss_genre, neg_adversarial_sampling, pairwise, optimizer, shards, flags)
         self.optimizer = optimizer
         self.opt = None
         self.ent_mom = self.rel_mom = None
@@ -156,7 +161,29 @@ class StepEngine(object):
                    optimizer=arg('optimizer', 'Adagrad'), moments=moments,
                    adam_betas=(getattr(args, 'adam_beta1', None) if getattr(args, 'adam_beta1', None) is not None else 0.9,
                                getattr(args, 'adam_beta2', None) if getattr(args, 'adam_beta2', None) is not None else 0.999),
-                   adam_eps=arg('adam_eps', 1e-8), ent_norm=arg('ent_norm'), rel_norm=arg('rel_norm'))
+                   adam_eps=arg('adam_eps', 1e-8), ent_norm=arg('ent_norm'), rel_norm=arg('rel_norm'),
+                   one_vs_all=bool(arg('one_vs_all')))
+
+    def _check_one_vs_all(self, m, loss_genre, adv, pairwise, optimizer, shards, flags):
+        if not (m and m.one_vs_all):
+            raise _lib.KgeError("one_vs_all: DistMult and ComplEx only (got %s)" % self.model_name)
+        if loss_genre != 'Softmax':
+            raise _lib.KgeError("one_vs_all: the loss is the softmax over every entity: loss_genre must be 'Softmax' (got %r)" % (loss_genre,))
+        if adv or pairwise:
+            raise _lib.KgeError("one_vs_all: not with neg_adversarial_sampling or pairwise")
+        if optimizer == 'Adam':
+            raise _lib.KgeError("one_vs_all: optimizer='Adam' is not available (the dense trace is an Adagrad update)")
+        if shards is not None:
+            raise _lib.KgeError("one_vs_all: local tables only (no sharded tables)")
+        if self.ent_norm or self.rel_norm or (flags & _lib.FLAG_NEG_DEG_SAMPLE):
+            raise _lib.KgeError("one_vs_all: not with ent_norm / rel_norm / neg_deg_sample")
+        if not models.one_vs_all_width_ok(self.d_e):
+            raise _lib.KgeError("one_vs_all: the entity width must be a multiple of 4 in [4, %d] (got %d)"
+                                % (models.ONE_VS_ALL_MAX_DIM, self.d_e))
+
+    def _no_one_vs_all(self, what):
+        if self.one_vs_all:
+            raise _lib.KgeError("one_vs_all: %s is not available in the 1-vs-all step" % what)
 
     def _init_adam(self, betas, eps, moments):
         if self.model_name in ('RESCAL', 'TransR'):
@@ -203,6 +230,7 @@ class StepEngine(object):
         gradient and self-adversarial weight 0 (include/kge_hip.h, kge_step_fused_known).  The index is only read: engines of
         several `--num_proc` lanes share one; the pair mask of a step lives in a buffer of this engine's.  Strict single-table
         step (`step`, `step_timed`, `capture`); not with KGE_FLAG_NEG_DEG_SAMPLE / FUSED_LOSS / LOSS_IN_FWD."""
+        self._no_one_vs_all("attach_known")
         if index is None:
             self._known = None
             return
@@ -335,6 +363,13 @@ class StepEngine(object):
         """enqueue one fused step.  `want`: dict of optional output tensors (pos_score, neg_score,
         g_pos_ent, g_neg, g_rel).  `emit`: KgeEmit for the sharded path.  `sample_job` (KgeSamplerJob, DeviceSampler.tail_jobs):
         the step's launches also BUILD that batch of the next group (kge_step_fused_sampling; strict step on local tables)."""
+        if (batch.N == 0) != self.one_vs_all:
+            raise _lib.KgeError("one_vs_all: an engine with one_vs_all=True takes batches with N == 0, and only such an engine does "
+                                "(got N=%d)" % batch.N)
+        if self.one_vs_all and emit is not None:
+            self._no_one_vs_all("emit")
+        if self.one_vs_all and sample_job is not None:
+            self._no_one_vs_all("sample_job")
         ws = self.workspace_for(batch)
         out = _lib.KgeStepOut()
         if want is not None or per_step_loss:
@@ -420,6 +455,7 @@ class StepEngine(object):
         `next_batch`: the batch of the following step_async call (optional): with KGE_FLAG_ASYNC_REL its PREP shares
         this step's backward launch.  `flush_async()` must follow the last step (before the tables are read / before a
         stream capture ends)."""
+        self._no_one_vs_all("step_async")
         if self.shards is not None:
             raise _lib.KgeError("--async_update is not available on peer-to-peer sharded tables")
         if self.opt is not None:
@@ -477,6 +513,7 @@ class StepEngine(object):
         sampler (dataloader.DeviceSampler; `batches` is then the NUMBER of steps, at most its slots): the graph is [one sampler
         launch + that many steps over its slots] - every replay trains on the next batches of the sampler's sequence, whose host
         step counter the caller advances by the group size per replay (an even size keeps the corruption sides in place)."""
+        self._no_one_vs_all("capture")
         if sampler is not None:
             if async_update:
                 raise _lib.KgeError("capture: the sampler form records strict steps")

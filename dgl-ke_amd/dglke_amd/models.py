@@ -23,6 +23,7 @@ Model = namedtuple('Model', [
     'norm_ent', 'norm_rel',        # --ent_norm / --rel_norm: equal slices of an entity / relation row, each projected on its own (norm_rel 0: refused)
     'norm_rel_unit',               # ... bit k: relation slice k is normalised to length 1 under either relation mode (TransH's w)
     'no_rel_norm',                 # ... None, or why --rel_norm does not apply
+    'one_vs_all',                  # --one_vs_all / StepEngine(one_vs_all=True): the score is a plain product a . e (DistMult, ComplEx)
     'projection', 'relation_matrix', 'alias_of'])     # TransR's third table; RESCAL's relation rows are matrices; TransE is TransE_l2
 
 
@@ -30,7 +31,7 @@ def _model(name, id, score, score_args=(), **kw):
     d = dict.fromkeys(Model._fields)
     d.update(name=name, id=id, score=score, score_args=score_args, rank_cands=1, topk_row=lambda d_e: d_e, multiple_first=False,
              single_gpu_only=False, no_stale_pipeline=False, projection=False, relation_matrix=False, norm_ent=1, norm_rel=1,
-             norm_rel_unit=0)
+             norm_rel_unit=0, one_vs_all=False)
     d.update(kw)
     return Model(**d)
 
@@ -46,8 +47,8 @@ MODELS = OrderedDict((m.name, m) for m in (       # in the order of the --model_
     _model('TransE_l2', 1, 'TransEScore', ('gamma', 'l2')),
     _model('TransR', 7, 'TransRScore', projection=True, **_OWN_REL),
     _model('RESCAL', 6, 'RESCALScore', relation_matrix=True, **_OWN_REL),
-    _model('DistMult', 2, 'DistMultScore'),
-    _model('ComplEx', 3, 'ComplExScore'),
+    _model('DistMult', 2, 'DistMultScore', one_vs_all=True),
+    _model('ComplEx', 3, 'ComplExScore', one_vs_all=True),
     _model('RotatE', 4, 'RotatEScore', ('gamma', 'emb_init'), norm_rel=0, no_rel_norm="the row holds phases"),
     _model('SimplE', 5, 'SimplEScore'),
     _model('QuatE', 8, 'QuatEScore', ent_multiple=4, rel_width=lambda d_e: d_e, de='tied', dr='tied',
@@ -119,3 +120,10 @@ def norm_slices(m, table, mode):
         raise ValueError("%s: --rel_norm does not apply (%s)" % (m.name, m.no_rel_norm))
     forced = 0 if table == 'ent' else m.norm_rel_unit
     return ['unit' if (forced >> k) & 1 else mode for k in range(parts)]
+
+ONE_VS_ALL_MAX_DIM = 512                                             # the owner kernel's register-resident [64, d] gradient
+
+
+def one_vs_all_width_ok(d_e):
+    """the width rule of the 1-vs-all step: 16-byte rows for the tile loop, at most 512 floats for the owner kernel"""
+    return 4 <= d_e <= ONE_VS_ALL_MAX_DIM and d_e % 4 == 0

@@ -66,7 +66,10 @@ def build_plan(h, t, r, neg, chunk, N, neg_head, edge_w=None):
     hp = ue_pos_ptr[1:] > ue_pos_ptr[:-1]
     hn = ue_neg_ptr[1:] > ue_neg_ptr[:-1]
     ue_rec[:, 6] = np.where(hp, ue_pos_adj[np.minimum(ue_pos_ptr[:-1], 2 * B - 1)], -1)
-    ue_rec[:, 7] = np.where(hn, ue_neg_slot[np.minimum(ue_neg_ptr[:-1], Cn * N - 1)], -1)
+    if Cn * N > 0:
+        ue_rec[:, 7] = np.where(hn, ue_neg_slot[np.minimum(ue_neg_ptr[:-1], Cn * N - 1)], -1)
+    else:                                                   # N == 0 (the 1-vs-all step): no record has a negative list
+        ue_rec[:, 7] = -1
     ur_rec = np.zeros((UR, 8), np.int32)
     ur_rec[:, 0], ur_rec[:, 1] = _lohi(ur_id)
     ur_rec[:, 2], ur_rec[:, 3] = ur_ptr[:-1], ur_ptr[1:]

@@ -127,6 +127,11 @@ class ArgParser(argparse.ArgumentParser):
         a('--adam_beta1', type=float, default=0.9, help='--optimizer Adam: decay of the first moment')
         a('--adam_beta2', type=float, default=0.999, help='--optimizer Adam: decay of the second moment')
         a('--adam_eps', type=float, default=1e-8, help='--optimizer Adam: the term added to the root of the second moment')
+        a('--one_vs_all', action='store_true',
+          help='1-vs-all softmax (a flag of this build): every positive is scored against EVERY entity of the table instead of sampled '
+               'negatives (the loss LibKGE / PyKEEN / Lacroix et al. use for DistMult and ComplEx); implies --loss_genre Softmax, '
+               '--neg_sample_size is ignored.  DistMult / ComplEx, Adagrad, one GPU, one trainer, entity width a multiple of 4 up to '
+               '512; batches come from the host sampler.')
         a('--ent_norm', default='none', choices=list(models.NORM_MODES),
           help='norm constraint of radius 1 on the entity rows every step has updated, applied by one more launch behind the update: '
                'clip scales a row onto the unit sphere only when its norm exceeds 1 (TransH / TransR / TransD: |e| <= 1), unit every '
@@ -340,14 +345,17 @@ class _Trainer(object):
         th.cuda.set_device(args.gpu[rank])
         self.dev = th.device("cuda", args.gpu[rank])
         B, N = args.batch_size, args.neg_sample_size
-        self.chunk = N if N <= B else B
+        self.one_vs_all = bool(getattr(args, 'one_vs_all', False))
+        if self.one_vs_all:
+            N = 0                                     # no sampled negatives: one chunk, every entity a candidate
+        self.chunk = B if self.one_vs_all else (N if N <= B else B)
         self.C = B // self.chunk
         self.d_e = args.hidden_dim * (2 if args.double_ent else 1)
         self.d_r = args.hidden_dim * (2 if args.double_rel else 1)
         self.emb_init = (args.gamma + 2.0) / args.hidden_dim
         # the on-device sampler builds the batches of a whole group ahead; batches it cannot build - edge importance, or more ids
         # than its launch handles - come from the host sampler (plans built on the host, step by step)
-        self.device_sampler = not args.has_edge_importance and 2 * B + self.C * N <= DeviceSampler.MAX_ELEMENTS
+        self.device_sampler = not args.has_edge_importance and not self.one_vs_all and 2 * B + self.C * N <= DeviceSampler.MAX_ELEMENTS
         # weights the DEVICE sampler carries (--subsampling_weight, --has_edge_importance --edge_importance_on_device): one float per
         # triple of the training split, set by the trainer before its lanes make their samplers
         self.weighted = weighted_device_sampler(args)
@@ -393,8 +401,8 @@ class _Trainer(object):
                                  n_slots=max(2, a.graph_steps or 2), neg_chunk_size=self.chunk, seed=a.seed + 1000 * k,
                                  edge_importance=w)
         w = np.asarray(tr[3])[part] if a.has_edge_importance else None
-        return UniformChunkedSampler(h, r, t, self.dataset.n_entities, a.batch_size, a.neg_sample_size, self.dev,
-                                     neg_chunk_size=self.chunk, seed=a.seed + 1000 * k, edge_importance=w)
+        return UniformChunkedSampler(h, r, t, self.dataset.n_entities, a.batch_size, 0 if self.one_vs_all else a.neg_sample_size,
+                                     self.dev, neg_chunk_size=self.chunk, seed=a.seed + 1000 * k, edge_importance=w)
 
     def loss_engines(self):
         """(proc number, engine) of the loss sums this process prints at a log mark"""
@@ -423,7 +431,7 @@ class _Trainer(object):
         # runs as four phase groups with HIP events in between (same kernels, same result).  That one step is launched eagerly and
         # synchronised, so its absolute times are not those of the graph-replayed steps: only the SPLIT is taken from it - the
         # printed totals are the interval's measured training time divided in that step's proportions
-        phase_timers = self.world == 1 and self.n_lanes == 1 and not self.lanes[0].async_update
+        phase_timers = self.world == 1 and self.n_lanes == 1 and not self.lanes[0].async_update and not self.one_vs_all
         th.cuda.synchronize()
         self.barrier()
         train_start = start = time.time()
@@ -517,6 +525,9 @@ class Trainer(_Trainer):
             print('[Train] --ent_norm {}, --rel_norm {}: every step projects the rows it has updated (radius 1); the fresh tables '
                   'were projected once'.format(self.norms[0] or 'none', self.norms[1] or 'none'))
         self.n_lanes = max(1, int(args.num_proc))
+        if self.one_vs_all:
+            print('[Train] --one_vs_all: softmax over all {} entities per positive; --neg_sample_size {} is ignored; host-built '
+                  'plans without negatives'.format(dataset.n_entities, args.neg_sample_size))
         # entity-only deferral (the reference's --async_update) runs as the strict step unless the pipeline is asked for: with the
         # relation trace landing between two steps the pipeline needs one more launch than it hides
         async_ok = not models.own_relation_update(models.MODELS[args.model_name])
@@ -964,6 +975,43 @@ def check_loss_flags(args):
         raise KgeError("--loss_genre Softmax cannot be combined with -pw")
 
 
+def check_one_vs_all(args, argv=None):
+    """--one_vs_all runs kge_step_fused on batches without sampled negatives (N == 0) on one GPU's tables with host-built plans: implies --loss_genre Softmax and eager
+    launches, and refuses, before anything is loaded, what that step does not cover.  argv: the command line, to tell a flag that
+    was given from its default"""
+    if not getattr(args, 'one_vs_all', False):
+        return
+    argv = list(sys.argv[1:] if argv is None else argv)
+
+    def given(flag):
+        return any(a == flag or a.startswith(flag + '=') for a in argv)
+    m = models.MODELS[args.model_name]
+    if not m.one_vs_all:
+        raise KgeError("--one_vs_all is available for DistMult and ComplEx only (got %s): the other models' scores are no plain "
+                       "product with the candidate row" % args.model_name)
+    if given('--loss_genre') and args.loss_genre != 'Softmax':
+        raise KgeError("--one_vs_all is the softmax over every entity: --loss_genre %s cannot be combined with it" % args.loss_genre)
+    args.loss_genre = 'Softmax'
+    for bad, text in ((args.neg_adversarial_sampling, "-adv (the softmax is the weighting)"), (args.pairwise, "-pw"),
+                      (args.neg_deg_sample, "--neg_deg_sample (there are no sampled negatives)"),
+                      (args.exclude_positive, "--exclude_positive (there are no sampled negatives)"),
+                      (args.subsampling_weight, "--subsampling_weight (batches come from the host sampler)"),
+                      (getattr(args, 'optimizer', 'Adagrad') == 'Adam', "--optimizer Adam (the dense trace is an Adagrad update)"),
+                      (any(norm_constraints(args)), "--ent_norm / --rel_norm (the dense trace updates every entity row)"),
+                      (len(args.gpu) > 1, "more than one --gpu entry (sharded tables)"),
+                      (args.num_proc > 1, "--num_proc > 1 (the lanes would race on the dense update)"),
+                      (args.async_update or args.async_update_rel or args.async_update_pipeline, "--async_update* (no pipeline form)"),
+                      (given('--graph_steps') and args.graph_steps > 1, "--graph_steps > 1 (host-built plans, no captured graph)"),
+                      (getattr(args, 'checkpoint_interval', 0), "--checkpoint_interval (no checkpoints of such runs)"),
+                      (getattr(args, 'resume', None), "--resume (no checkpoints of such runs)")):
+        if bad:
+            raise KgeError("--one_vs_all cannot be combined with %s" % text)
+    d_e = args.hidden_dim * (2 if args.double_ent else 1)
+    if not models.one_vs_all_width_ok(d_e):
+        raise KgeError("--one_vs_all: the entity width must be a multiple of 4 in [4, %d] (got %d)" % (models.ONE_VS_ALL_MAX_DIM, d_e))
+    args.graph_steps = 0
+
+
 def check_model_widths(model_name, hidden_dim, double_ent, double_rel):
     """the -de / -dr / --hidden_dim rules of the model's record (models.py); the texts are the record's"""
     m = models.MODELS[model_name]
@@ -1002,6 +1050,7 @@ def check_model_flags(args):
 def main(argv=None, before_train=None):
     """before_train (one GPU): called with the built Trainer in front of its first step - the tests take the initial tables there"""
     args = ArgParser().parse_args(argv)
+    check_one_vs_all(args, argv)                 # before anything is loaded or created (sets --loss_genre Softmax)
     check_loss_flags(args)                       # before anything is loaded or created
     check_exclude_positive(args)                 # before anything is loaded or created
     check_model_flags(args)                      # before anything is loaded or created
@@ -1036,7 +1085,8 @@ def main(argv=None, before_train=None):
             raise KgeError("--test: the dataset has no test split")
         if args.neg_sample_size_eval < 0:
             args.neg_sample_size_eval = dataset.n_entities
-    args.batch_size = get_compatible_batch_size(args.batch_size, args.neg_sample_size)
+    if not args.one_vs_all:
+        args.batch_size = get_compatible_batch_size(args.batch_size, args.neg_sample_size)
     if not multi:
         args.batch_size_eval = get_compatible_batch_size(args.batch_size_eval, args.neg_sample_size_eval)
     args.eval_filter = not args.no_eval_filter

@@ -440,6 +440,30 @@ size_t kge_step_workspace_bytes(const kge_hparams *hp, int B, int C, int chunk, 
 /* forward + backward + update of one batch, enqueued on `stream`. */
 int kge_step_fused(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b,
                    const kge_step_out *out, void *ws, size_t ws_bytes, void *stream);
+/* ---- 1-vs-all softmax: kge_step_fused on a batch with N == 0 - no sampled negatives: EVERY entity of the table is a candidate of
+ * every edge (csrc/kge_onevsall.hip).  DistMult and ComplEx, Adagrad, local tables.  The batch has no neg_ids and every
+ * ue_neg list is empty; C / chunk as built, C * chunk == B; one corruption side per batch (neg_head).  With w_i = edge_w[i] (per edge) or 1:
+ *   a_i   = the per-edge operand edge_fwd builds for the sampled step (DistMult x . r; ComplEx the complex product, conjugated for
+ *           heads), x = the kept end;   s_ij = a_i . e_j for every j in [0, n_ent), the true end included
+ *   p_i   = the positive score in its direct form;   lse_i = m_i + log sum_j exp(s_ij - m_i), m_i = max_j s_ij
+ *   loss  = (1/B) sum_i w_i (lse_i - p_i);   dL/ds_ij = (w_i / B) exp(s_ij - lse_i);   dL/dp_i = -w_i / B
+ * Applied as two traces, one after the other, each with the Adagrad rule of the update launch (state += mean(G^2),
+ * row -= lr G / (sqrt(state) + eps)):
+ *   1. the dense trace: EVERY entity row j with G_j = sum_i dL/ds_ij a_i;
+ *   2. the update launch on the batch's plan: the kept end's gradient from GA_i = sum_j dL/ds_ij e_j and dL/dp_i, the true end's
+ *      dL/dp_i a_i, then the relation trace (state += every edge's own mean square, as in the sampled step) - all per-edge gradients
+ *      computed from the rows as they were BEFORE the dense trace;
+ *      the regulariser (reg_coef, reg_norm) as that launch applies it (entity rows: on the row as the launch finds it).
+ * No score and no candidate gradient is ever stored: the forward keeps (max, sum-exp) per row, the two backward kernels recompute
+ * their score tiles; every sum has a fixed order (bit-reproducible).  loss4 = {nan, nan, loss, regularization} and loss_accum as
+ * for KGE_LOSS_SOFTMAX; pos_score, g_pos_ent, g_rel as without the flag.  The workspace contract holds: kge_step_workspace_bytes
+ * answers for N == 0 from (hp, B, UE, UR) - C and chunk are not read, the table's size does not enter (0: bad arguments).
+ * A mode of kge_step_fused and not an entry of its own: the stream and workspace conventions of that entry are its conventions.
+ * KGE_ERR_ARG before any launch, the message naming the condition: a model other than DistMult / ComplEx; loss_genre other than
+ * KGE_LOSS_SOFTMAX; adv; pairwise; d_e outside d_e % 4 == 0, 4 <= d_e <= 512; any KGE_FLAG_*_NORM_* bit or
+ * KGE_FLAG_NEG_DEG_SAMPLE; kge_step_out.neg_score or g_neg (they do not exist).  Every other step entry refuses a batch with N == 0 as
+ * before (kge_step_phase, kge_step_fused_sampling, kge_step_fused_known, kge_step_optim, kge_step_async, kge_step_grads,
+ * kge_step_sharded).  KGE_ERR_WORKSPACE: ws_bytes below the size. */
 
 /* ---- --async_update (models/pytorch/tensor_models.py:136-175 async_update, :364-375 create/finish_async_update;
  * models/general_models.py:639-647; train_pytorch.py:120-121, 194-195; docs/source/train.rst:217-259) ----
