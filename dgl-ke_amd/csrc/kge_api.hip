@@ -1218,9 +1218,13 @@ int kge_step_fused_sampling(const kge_hparams *hp, const kge_tables *tb, const k
     return step_sampling(hp, tb, b, out, ws, ws_bytes, job, StepCall{}, stream);
 }
 
+static int step_k_vs_all(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
+                         size_t ws_bytes, const kge_sampler_job *job, const kge_known *known, void *stream);
 int kge_step_fused_known(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
                          size_t ws_bytes, const kge_sampler_job *job, const kge_known *known, uint32_t *mask, size_t mask_bytes,
                          void *stream) {
+    if (known && b && b->N == 0)      // no sampled negatives: every entity a candidate, the index gives the labels
+        return step_k_vs_all(hp, tb, b, out, ws, ws_bytes, job, known, stream);
     StepCall c; c.who = "kge_step_fused_known";
     if (known) { c.known = known; c.known_mask = mask; c.known_mask_bytes = mask_bytes; }
     return step_sampling(hp, tb, b, out, ws, ws_bytes, job, c, stream);
@@ -1409,9 +1413,21 @@ static size_t carve_ova(Carver &cv, OvaBufs &w, const kge_hparams *hp, int B_, i
 }
 static bool ova_width_ok(int d_e) { return d_e >= 4 && d_e <= 512 && d_e % 4 == 0; }
 
+// K-vs-all (kge_step_fused_known on N == 0, KGE_LOSS_BCE): behind the 1-vs-all layout the rows' list ranges, own ends and loss parts
+struct KvaBufs { int64_t *rng, *own; float *lpart; };
+static size_t carve_kva(Carver &cv, OvaBufs &w, KvaBufs &k, const kge_hparams *hp, int B_, int UE, int UR) {
+    carve_ova(cv, w, hp, B_, UE, UR);
+    const size_t B = B_;
+    const OvaGeom g = ova_geom(B_, hp->d_e, 1);
+    k.rng = cv.i64(2 * B); k.own = cv.i64(B); k.lpart = cv.f((size_t)ova_max_parts(g.RT, g.nslab) * B);
+    return cv.off;
+}
+
 static size_t ova_workspace_bytes(const kge_hparams *hp, int B, int UE, int UR) {
     if (B <= 0 || UE < 0 || UR < 0 || !ova_width_ok(hp->d_e) || hp->d_r <= 0) return 0;
-    Carver cv; OvaBufs w; return carve_ova(cv, w, hp, B, UE, UR);
+    Carver cv; OvaBufs w;
+    if (hp->loss_genre == KGE_LOSS_BCE) { KvaBufs k; return carve_kva(cv, w, k, hp, B, UE, UR); }
+    return carve_ova(cv, w, hp, B, UE, UR);
 }
 
 static int step_one_vs_all(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
@@ -1470,6 +1486,97 @@ static int step_one_vs_all(const kge_hparams *hp, const kge_tables *tb, const kg
     KGE_TRY(launch_edge_bwd(eb, s));
     KGE_TRY(launch_ova_bwd_e(oa, s));                 // the dense trace: every entity row and its state
     // the update launch, on a plan without negative entries (no record has a negative list: GN is never read; a valid pointer all the same)
+    UpdateArgs ua{};
+    ua.model_d_e = d_e; ua.d_r = d_r; ua.reg_norm = hp->reg_norm; ua.UE = b->UE; ua.UR = b->UR;
+    ua.lr = hp->lr; ua.eps = hp->eps; ua.reg_coef = reg ? hp->reg_coef : 0.f;
+    ua.ent = tb->ent; ua.ent_state = tb->ent_state; ua.rel = tb->rel; ua.rel_state = tb->rel_state;
+    ua.ue_id = b->ue_id; ua.ue_pos_ptr = b->ue_pos_ptr; ua.ue_pos_adj = b->ue_pos_adj; ua.ue_neg_ptr = b->ue_neg_ptr; ua.ue_neg_slot = b->ue_neg_slot;
+    ua.ur_id = b->ur_id; ua.ur_ptr = b->ur_ptr; ua.ur_edge = b->ur_edge; ua.ue_rec = b->ue_rec; ua.ur_rec = b->ur_rec; ua.counts_dev = b->counts_dev;
+    ua.GH = w.GH; ua.GT = w.GT; ua.GN = w.GH; ua.GR = GR; ua.neg_head = b->neg_head; ua.P = w.GH; ua.GA = w.GAp; ua.acc = acc;
+    ua.reg_ent = want4 ? w.reg_ent : nullptr; ua.reg_rel = want4 ? w.reg_rel : nullptr;
+    ua.ld_e = d_e; ua.ld_r = d_r; ua.ld_gs_e = 1; ua.ld_gs_r = 1;
+    if (out && out->g_pos_ent) ua.g0 = out->g_pos_ent;
+    KGE_TRY(launch_update(ua, s));
+    if (want4) {
+        FinalizeArgs f{};
+        f.B = B; f.UE = b->UE; f.UR = b->UR; f.pos_row = 1;
+        f.row_pos = w.row_pos; f.row_neg = w.row_neg; f.reg_ent = w.reg_ent; f.reg_rel = w.reg_rel;
+        f.counts_dev = b->counts_dev; f.loss4 = out->loss4;
+        KGE_TRY(launch_finalize(f, s));
+    }
+    return KGE_OK;
+}
+
+// ---- K-vs-all BCE with label smoothing: every entity a candidate, labels from the known index (kge_kvsall.hip) ----
+static int step_k_vs_all(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
+                         size_t ws_bytes, const kge_sampler_job *job, const kge_known *known, void *stream) {
+    const char *who = "kge_step_fused_known, N == 0 (K-vs-all)";
+    if (!hp || !tb || !ws) return fail(KGE_ERR_ARG, "%s: null argument (hp, tb and ws are required)", who);
+    const kge::ModelRow *mr = kge::model_row(hp->model);
+    if (!mr) return fail(KGE_ERR_ARG, "unknown model %d", hp->model);
+    if (job) return fail(KGE_ERR_ARG, "%s: a sampler job is not available here (there are no sampled negatives: job must be NULL)", who);
+    if (mr->closed & kge::E_STEP_ONE_VS_ALL)
+        return fail(KGE_ERR_ARG, "%s: not available for %s (DistMult and ComplEx only: the other models' scores are no plain product a . e)", who, mr->name);
+    if (int rc = check_model(hp->model, hp->d_e, hp->d_r)) return rc;
+    if (hp->loss_genre == KGE_LOSS_SOFTMAX)
+        return fail(KGE_ERR_ARG, "%s: KGE_LOSS_SOFTMAX with a known index is not built (known answers left out of the softmax row); "
+                    "loss_genre must be KGE_LOSS_BCE", who);
+    if (hp->loss_genre != KGE_LOSS_BCE) return fail(KGE_ERR_ARG, "%s: loss_genre must be KGE_LOSS_BCE (got %d)", who, hp->loss_genre);
+    if (hp->adv) return fail(KGE_ERR_ARG, "%s: adv must be 0", who);
+    if (hp->pairwise) return fail(KGE_ERR_ARG, "%s: pairwise must be 0", who);
+    if (!(hp->margin >= 0.f && hp->margin < 1.f))
+        return fail(KGE_ERR_ARG, "%s: kge_hparams.margin carries the label smoothing and must be in [0, 1) (got %g)", who, (double)hp->margin);
+    if (!ova_width_ok(hp->d_e))
+        return fail(KGE_ERR_ARG, "%s: needs d_e %% 4 == 0 and 4 <= d_e <= 512 (got %d)", who, hp->d_e);
+    if (hp->flags & (NORM_ENT | NORM_REL))
+        return fail(KGE_ERR_ARG, "%s: %s is not available here (the dense trace updates every entity row)", who, norm_flag_name(hp->flags));
+    if (hp->flags & KGE_FLAG_NEG_DEG_SAMPLE) return fail(KGE_ERR_ARG, "%s: KGE_FLAG_NEG_DEG_SAMPLE is not available here (there are no sampled negatives)", who);
+    if (out && (out->neg_score || out->g_neg))
+        return fail(KGE_ERR_ARG, "%s: kge_step_out.neg_score / g_neg do not exist in this step (scores and candidate gradients are never stored)", who);
+    if (known->n_rel <= 0 || known->m_tail < 0 || known->m_head < 0 || (known->m_tail > 0 && (!known->keys_tail || !known->vals_tail)) ||
+        (known->m_head > 0 && (!known->keys_head || !known->vals_head)))
+        return fail(KGE_ERR_ARG, "%s: kge_known: n_rel > 0 and both sorted sides (keys, vals, m >= 0) are required", who);
+    if (b->B <= 0 || b->C <= 0 || b->chunk <= 0 || (int64_t)b->C * b->chunk != b->B)
+        return fail(KGE_ERR_ARG, "%s: need C*chunk == B (B=%d C=%d chunk=%d)", who, b->B, b->C, b->chunk);
+    if (!tb->ent || !tb->ent_state || !tb->rel || !tb->rel_state || tb->n_ent <= 0 || !b->h_gid || !b->t_gid || !b->rel_ids || !b->ue_id ||
+        !b->ue_pos_ptr || !b->ue_pos_adj || !b->ur_id || !b->ur_ptr || !b->ur_edge || !b->ue_rec || !b->ur_rec)
+        return fail(KGE_ERR_ARG, "%s: null table / batch pointer", who);
+    Carver cv(ws, ws_bytes); OvaBufs w; KvaBufs kb;
+    const size_t need = carve_kva(cv, w, kb, hp, b->B, b->UE, b->UR);
+    if (need > ws_bytes) return fail(KGE_ERR_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
+    hipStream_t s = (hipStream_t)stream;
+    const int B = b->B, d_e = hp->d_e, d_r = hp->d_r;
+    const bool reg = hp->reg_coef > 0.f && hp->reg_norm > 0, want4 = out && out->loss4;
+    const float rot_div = rot_div_of(hp->emb_init);
+    float *P = (out && out->pos_score) ? out->pos_score : w.P, *GR = (out && out->g_rel) ? out->g_rel : w.GR;
+    float *acc = out ? out->loss_accum : nullptr;
+    const EdgeSrc src{tb->ent, b->h_gid, tb->ent, b->t_gid, tb->rel, b->rel_ids, kge::ShardMap{}, kge::ShardMap{}};
+    // edge_fwd: A, pos_score (the positive is a label like any other: no positive part, dL/dp = 0 from the prep launch)
+    EdgeFwdArgs ef;
+    fill_edge(ef, src, hp->model, B, d_e, d_r, b->neg_head, hp->gamma, rot_div);
+    ef.pos_score = P; ef.A = w.A; ef.do_pos_loss = 0; ef.lp = LossParams{KGE_LOSS_SOFTMAX, 0, 1, hp->adv_temp, 0.f};
+    ef.w = b->edge_w; ef.w_mean = b->edge_w_mean; ef.dpos = w.dP;
+    KGE_TRY(launch_edge_fwd(ef, s));
+    KvaArgs ka{};
+    ka.B = B; ka.d = d_e; ka.n_ent = tb->n_ent; ka.g = ova_geom(B, d_e, tb->n_ent);
+    ka.A = w.A; ka.ent = tb->ent; ka.ent_state = tb->ent_state; ka.w = b->edge_w;
+    ka.h = b->h_gid; ka.r = b->rel_ids; ka.t = b->t_gid; ka.neg_head = b->neg_head ? 1 : 0;
+    ka.keys = ka.neg_head ? known->keys_head : known->keys_tail; ka.vals = ka.neg_head ? known->vals_head : known->vals_tail;
+    ka.m = ka.neg_head ? known->m_head : known->m_tail; ka.n_rel = known->n_rel; ka.smooth = hp->margin;
+    ka.rng = kb.rng; ka.own = kb.own; ka.coef = w.coef; ka.dpos = w.dP; ka.lpart = kb.lpart;
+    ka.row_pos = want4 ? w.row_pos : nullptr; ka.row_neg = want4 ? w.row_neg : nullptr;
+    ka.acc = acc; ka.GAp = w.GAp; ka.lr = hp->lr; ka.eps = hp->eps;
+    KGE_TRY(launch_kva_prep(ka, s));
+    KGE_TRY(launch_kva_bwd_a(ka, s));                 // dL/da in parts and the loss parts: four matrix products in the step, no forward
+    KGE_TRY(launch_kva_loss(ka, s));
+    // per-edge h / t / r gradient rows from the GA parts (dL/dp = 0), read from the rows as they are BEFORE the dense trace
+    EdgeBwdArgs eb;
+    fill_edge_bwd(eb, src, hp->model, B, d_e, d_r, b->neg_head, hp->gamma, rot_div, w.dP, w.GAp);
+    eb.reg_coef = reg ? hp->reg_coef : 0.f; eb.reg_norm = hp->reg_norm;
+    eb.GH = w.GH; eb.GT = w.GT; eb.GR = GR; eb.ga_parts = ka.g.Sa; eb.ga_stride = (int64_t)B * d_e;
+    KGE_TRY(launch_edge_bwd(eb, s));
+    KGE_TRY(launch_kva_bwd_e(ka, s));                 // the dense trace: every entity row and its state
+    // the update launch, on a plan without negative entries (as in the 1-vs-all step)
     UpdateArgs ua{};
     ua.model_d_e = d_e; ua.d_r = d_r; ua.reg_norm = hp->reg_norm; ua.UE = b->UE; ua.UR = b->UR;
     ua.lr = hp->lr; ua.eps = hp->eps; ua.reg_coef = reg ? hp->reg_coef : 0.f;

@@ -970,3 +970,29 @@ int launch_ova_fwd(const OvaArgs &a, hipStream_t s);
 int launch_ova_lse(const OvaArgs &a, hipStream_t s);
 int launch_ova_bwd_a(const OvaArgs &a, hipStream_t s);
 int launch_ova_bwd_e(const OvaArgs &a, hipStream_t s);
+// ---- K-vs-all BCE with label smoothing (kge_kvsall.hip; kge_step_fused_known on a batch with N == 0) ----
+// The candidates, the cut of the score matrix (OvaGeom: RT, NT, Sa / tpa, nj / nslab) and the per-edge operand are the 1-vs-all
+// step's; the criterion is per element, so there is no forward launch: the GA kernel sums the loss, the owner kernel updates.
+struct KvaArgs {
+    int B, d; int64_t n_ent;
+    OvaGeom g;
+    const float *A;                  // [B, d] per-edge operands (edge_fwd)
+    float *ent, *ent_state;          // the table: read by both backward kernels, its rows and state updated by kva_bwd_e alone
+    const float *w;                  // [B] edge weights or null
+    const int64_t *h, *r, *t;        // [B] the positives
+    const int64_t *keys, *vals;      // the index side of the corrupted end: m sorted (key, entity) pairs (null when m == 0)
+    int64_t m, n_rel;
+    int neg_head;
+    float smooth;                    // label smoothing: y' = (1 - smooth) y + smooth / n_ent
+    int64_t *rng, *own;              // [B, 2] the row's list range [f0, f1) in vals; [B] its own true end
+    float *coef, *dpos;              // [B] w_i / B; dL/dp_i = 0
+    float *lpart;                    // [Sa, B] sum_j softplus(s_ij) - y'_ij s_ij of row i over split s
+    float *row_pos, *row_neg;        // [B] per-row loss terms for the finalize launch (0, w_i l_i / B) or null
+    float *acc;                      // [4][KGE_ACC_SLOTS] running sums or null
+    float *GAp;                      // [Sa, B, d] dL/da in parts, one per split (edge_bwd adds them in part order)
+    float lr, eps;
+};
+int launch_kva_prep(const KvaArgs &a, hipStream_t s);
+int launch_kva_bwd_a(const KvaArgs &a, hipStream_t s);
+int launch_kva_loss(const KvaArgs &a, hipStream_t s);
+int launch_kva_bwd_e(const KvaArgs &a, hipStream_t s);

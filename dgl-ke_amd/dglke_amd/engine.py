@@ -18,7 +18,7 @@ class StepEngine(object):
                  adversarial_temperature=1.0, regularization_coef=0.0, regularization_norm=3,
                  loss_genre='Logsigmoid', pairwise=False, margin=1.0, flags=0,
                  tables=None, shards=None, optimizer='Adagrad', adam_betas=(0.9, 0.999), adam_eps=1e-8, moments=None,
-                 ent_norm=None, rel_norm=None, one_vs_all=False):
+                 ent_norm=None, rel_norm=None, one_vs_all=False, k_vs_all=False, label_smoothing=0.0):
         """optimizer 'Adam': lazy row-sparse Adam with a per-row step count (include/kge_hip.h, kge_step_optim) - the state
         tables hold the counts, the engine owns the moment tables ent_mom [n_ent, 2, d_e] / rel_mom [n_rel, 2, d_r] (`moments`:
         a pair the caller shares between engines, as `tables` shares the rows and the state).
@@ -26,7 +26,11 @@ class StepEngine(object):
         (include/kge_hip.h, KGE_FLAG_ENT_NORM_* / KGE_FLAG_REL_NORM_*; the slices of a row: models.py).  Tables the engine creates
         are projected whole once (`project_tables`); tables handed in are the caller's to project.
         one_vs_all: the 1-vs-all softmax step (include/kge_hip.h, kge_step_fused on a batch with N == 0): every entity of the table is a candidate
-        of every edge, batches carry N == 0.  DistMult / ComplEx, Softmax, Adagrad, local tables; `step` alone drives it."""
+        of every edge, batches carry N == 0.  DistMult / ComplEx, Softmax, Adagrad, local tables; `step` alone drives it.
+        k_vs_all: the K-vs-all step (include/kge_hip.h, kge_step_fused_known on a batch with N == 0): binary cross-entropy over every
+        entity, label 1 for the row's own true end and for every entity the attached index (`attach_known`, required before `step`;
+        an empty index trains 1-vs-all BCE) lists for the row's query, smoothed by label_smoothing in [0, 1).  loss_genre 'BCE'; the
+        rest as one_vs_all, with which it is mutually exclusive."""
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise _lib.KgeError("StepEngine needs a CUDA (HIP) device; there is no CPU fallback")
@@ -113,9 +117,18 @@ class StepEngine(object):
                 if len(tables) < 6:
                     raise _lib.KgeError("TransR needs tables = (ent, ent_state, rel, rel_state, proj, proj_state)")
                 self.proj, self.proj_state = tables[4], tables[5]
-        self.one_vs_all = bool(one_vs_all)
-        if self.one_vs_all:
+        self.one_vs_all, self.k_vs_all = bool(one_vs_all), bool(k_vs_all)
+        if self.one_vs_all and self.k_vs_all:
+            raise _lib.KgeError("k_vs_all: mutually exclusive with one_vs_all (one criterion over every entity)")
+        if not self.k_vs_all and label_smoothing:
+            raise _lib.KgeError("label_smoothing belongs to k_vs_all=True")
+        if self.one_vs_all or self.k_vs_all:
             self._check_one_vs_all(m, loss_genre, neg_adversarial_sampling, pairwise, optimizer, shards, flags)
+        if self.k_vs_all:
+            if not 0.0 <= float(label_smoothing) < 1.0:
+                raise _lib.KgeError("k_vs_all: label_smoothing must be in [0, 1) (got %r)" % (label_smoothing,))
+            hp.margin = float(label_smoothing)      # (the N == 0 step reads no margin: the field carries the smoothing)
+        self.label_smoothing = float(label_smoothing)
         self.optimizer = optimizer
         self.opt = None
         self.ent_mom = self.rel_mom = None
@@ -162,28 +175,34 @@ class StepEngine(object):
                    adam_betas=(getattr(args, 'adam_beta1', None) if getattr(args, 'adam_beta1', None) is not None else 0.9,
                                getattr(args, 'adam_beta2', None) if getattr(args, 'adam_beta2', None) is not None else 0.999),
                    adam_eps=arg('adam_eps', 1e-8), ent_norm=arg('ent_norm'), rel_norm=arg('rel_norm'),
-                   one_vs_all=bool(arg('one_vs_all')))
+                   one_vs_all=bool(arg('one_vs_all')), k_vs_all=bool(arg('k_vs_all')), label_smoothing=arg('label_smoothing', 0.0))
 
     def _check_one_vs_all(self, m, loss_genre, adv, pairwise, optimizer, shards, flags):
+        """what the two all-entity steps (one_vs_all, k_vs_all) refuse alike; each names itself"""
+        mode = 'k_vs_all' if self.k_vs_all else 'one_vs_all'
         if not (m and m.one_vs_all):
-            raise _lib.KgeError("one_vs_all: DistMult and ComplEx only (got %s)" % self.model_name)
-        if loss_genre != 'Softmax':
+            raise _lib.KgeError("%s: DistMult and ComplEx only (got %s)" % (mode, self.model_name))
+        if self.one_vs_all and loss_genre != 'Softmax':
             raise _lib.KgeError("one_vs_all: the loss is the softmax over every entity: loss_genre must be 'Softmax' (got %r)" % (loss_genre,))
+        if self.k_vs_all and loss_genre != 'BCE':
+            raise _lib.KgeError("k_vs_all: the loss is the binary cross-entropy over every entity: loss_genre must be 'BCE' (got %r)" % (loss_genre,))
         if adv or pairwise:
-            raise _lib.KgeError("one_vs_all: not with neg_adversarial_sampling or pairwise")
+            raise _lib.KgeError("%s: not with neg_adversarial_sampling or pairwise" % mode)
         if optimizer == 'Adam':
-            raise _lib.KgeError("one_vs_all: optimizer='Adam' is not available (the dense trace is an Adagrad update)")
+            raise _lib.KgeError("%s: optimizer='Adam' is not available (the dense trace is an Adagrad update)" % mode)
         if shards is not None:
-            raise _lib.KgeError("one_vs_all: local tables only (no sharded tables)")
+            raise _lib.KgeError("%s: local tables only (no sharded tables)" % mode)
         if self.ent_norm or self.rel_norm or (flags & _lib.FLAG_NEG_DEG_SAMPLE):
-            raise _lib.KgeError("one_vs_all: not with ent_norm / rel_norm / neg_deg_sample")
+            raise _lib.KgeError("%s: not with ent_norm / rel_norm / neg_deg_sample" % mode)
         if not models.one_vs_all_width_ok(self.d_e):
-            raise _lib.KgeError("one_vs_all: the entity width must be a multiple of 4 in [4, %d] (got %d)"
-                                % (models.ONE_VS_ALL_MAX_DIM, self.d_e))
+            raise _lib.KgeError("%s: the entity width must be a multiple of 4 in [4, %d] (got %d)"
+                                % (mode, models.ONE_VS_ALL_MAX_DIM, self.d_e))
 
     def _no_one_vs_all(self, what):
         if self.one_vs_all:
             raise _lib.KgeError("one_vs_all: %s is not available in the 1-vs-all step" % what)
+        if self.k_vs_all:
+            raise _lib.KgeError("k_vs_all: %s is not available in the K-vs-all step" % what)
 
     def _init_adam(self, betas, eps, moments):
         if self.model_name in ('RESCAL', 'TransR'):
@@ -229,8 +248,10 @@ class StepEngine(object):
         a (positive, negative) pair whose corrupted triple is in the index takes the score KGE_KNOWN_SCORE in the loss - loss term,
         gradient and self-adversarial weight 0 (include/kge_hip.h, kge_step_fused_known).  The index is only read: engines of
         several `--num_proc` lanes share one; the pair mask of a step lives in a buffer of this engine's.  Strict single-table
-        step (`step`, `step_timed`, `capture`); not with KGE_FLAG_NEG_DEG_SAMPLE / FUSED_LOSS / LOSS_IN_FWD."""
-        self._no_one_vs_all("attach_known")
+        step (`step`, `step_timed`, `capture`); not with KGE_FLAG_NEG_DEG_SAMPLE / FUSED_LOSS / LOSS_IN_FWD.
+        On a k_vs_all engine the index is the source of the labels instead: its lists are the known answers of a row's query."""
+        if self.one_vs_all:
+            self._no_one_vs_all("attach_known")
         if index is None:
             self._known = None
             return
@@ -363,13 +384,16 @@ class StepEngine(object):
         """enqueue one fused step.  `want`: dict of optional output tensors (pos_score, neg_score,
         g_pos_ent, g_neg, g_rel).  `emit`: KgeEmit for the sharded path.  `sample_job` (KgeSamplerJob, DeviceSampler.tail_jobs):
         the step's launches also BUILD that batch of the next group (kge_step_fused_sampling; strict step on local tables)."""
-        if (batch.N == 0) != self.one_vs_all:
-            raise _lib.KgeError("one_vs_all: an engine with one_vs_all=True takes batches with N == 0, and only such an engine does "
-                                "(got N=%d)" % batch.N)
-        if self.one_vs_all and emit is not None:
+        dense = self.one_vs_all or self.k_vs_all
+        if (batch.N == 0) != dense:
+            raise _lib.KgeError("one_vs_all / k_vs_all: an engine with one_vs_all=True or k_vs_all=True takes batches with N == 0, and "
+                                "only such an engine does (got N=%d)" % batch.N)
+        if dense and emit is not None:
             self._no_one_vs_all("emit")
-        if self.one_vs_all and sample_job is not None:
+        if dense and sample_job is not None:
             self._no_one_vs_all("sample_job")
+        if self.k_vs_all and self._known is None:
+            raise _lib.KgeError("k_vs_all: attach_known(index) first - the index gives the labels (an empty KnownIndex: 1-vs-all BCE)")
         ws = self.workspace_for(batch)
         out = _lib.KgeStepOut()
         if want is not None or per_step_loss:

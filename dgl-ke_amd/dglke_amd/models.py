@@ -23,7 +23,7 @@ Model = namedtuple('Model', [
     'norm_ent', 'norm_rel',        # --ent_norm / --rel_norm: equal slices of an entity / relation row, each projected on its own (norm_rel 0: refused)
     'norm_rel_unit',               # ... bit k: relation slice k is normalised to length 1 under either relation mode (TransH's w)
     'no_rel_norm',                 # ... None, or why --rel_norm does not apply
-    'one_vs_all',                  # --one_vs_all / StepEngine(one_vs_all=True): the score is a plain product a . e (DistMult, ComplEx)
+    'one_vs_all',                  # --one_vs_all / --k_vs_all and the engine's modes of those names: the score is a plain product a . e (DistMult, ComplEx)
     'projection', 'relation_matrix', 'alias_of'])     # TransR's third table; RESCAL's relation rows are matrices; TransE is TransE_l2
 
 

@@ -132,6 +132,15 @@ class ArgParser(argparse.ArgumentParser):
                'negatives (the loss LibKGE / PyKEEN / Lacroix et al. use for DistMult and ComplEx); implies --loss_genre Softmax, '
                '--neg_sample_size is ignored.  DistMult / ComplEx, Adagrad, one GPU, one trainer, entity width a multiple of 4 up to '
                '512; batches come from the host sampler.')
+        a('--k_vs_all', action='store_true',
+          help='K-vs-all (a flag of this build; ConvE\'s training mode, LibKGE\'s KvsAll): binary cross-entropy of every positive\'s '
+               'query (h, r, ?) / (?, r, t) against EVERY entity, label 1 for every entity that answers the query in the training '
+               'split; implies --loss_genre BCE, --neg_sample_size is ignored.  Rows are the sampled triples, not unique queries: a '
+               'query with k answers is drawn k times as often as in LibKGE.  Restrictions as --one_vs_all; not with --one_vs_all or '
+               '--exclude_positive')
+        a('--label_smoothing', type=float, default=0.0,
+          help='--k_vs_all: labels y\' = (1 - eps) y + eps / n_entities, eps in [0, 1) (the textbook form; ConvE\'s code adds '
+               '1 / n_entities instead)')
         a('--ent_norm', default='none', choices=list(models.NORM_MODES),
           help='norm constraint of radius 1 on the entity rows every step has updated, applied by one more launch behind the update: '
                'clip scales a row onto the unit sphere only when its norm exceeds 1 (TransH / TransR / TransD: |e| <= 1), unit every '
@@ -345,7 +354,9 @@ class _Trainer(object):
         th.cuda.set_device(args.gpu[rank])
         self.dev = th.device("cuda", args.gpu[rank])
         B, N = args.batch_size, args.neg_sample_size
-        self.one_vs_all = bool(getattr(args, 'one_vs_all', False))
+        self.k_vs_all = bool(getattr(args, 'k_vs_all', False))
+        # (one_vs_all: either criterion over every entity - what the batches, the sampler and the loop need to know)
+        self.one_vs_all = bool(getattr(args, 'one_vs_all', False)) or self.k_vs_all
         if self.one_vs_all:
             N = 0                                     # no sampled negatives: one chunk, every entity a candidate
         self.chunk = B if self.one_vs_all else (N if N <= B else B)
@@ -418,7 +429,7 @@ class _Trainer(object):
         """start_step, start_since_log (a resumed run, whose state the caller has put back): the steps already trained and how many
         of them the lanes' loss sums hold - the loop goes on with step start_step + 1"""
         args = self.args
-        keys = ['loss'] if args.pairwise or args.loss_genre == 'Softmax' else ['pos_loss', 'neg_loss', 'loss']
+        keys = ['loss'] if args.pairwise or args.loss_genre == 'Softmax' or self.k_vs_all else ['pos_loss', 'neg_loss', 'loss']
         if args.regularization_coef > 0 and args.regularization_norm > 0:
             keys.append('regularization')
         idx = {'pos_loss': 0, 'neg_loss': 1, 'loss': 2, 'regularization': 3}
@@ -525,7 +536,10 @@ class Trainer(_Trainer):
             print('[Train] --ent_norm {}, --rel_norm {}: every step projects the rows it has updated (radius 1); the fresh tables '
                   'were projected once'.format(self.norms[0] or 'none', self.norms[1] or 'none'))
         self.n_lanes = max(1, int(args.num_proc))
-        if self.one_vs_all:
+        if self.k_vs_all:
+            print('[Train] --k_vs_all: binary cross-entropy over all {} entities per positive, label smoothing {}; --neg_sample_size {} '
+                  'is ignored; host-built plans without negatives'.format(dataset.n_entities, args.label_smoothing, args.neg_sample_size))
+        elif self.one_vs_all:
             print('[Train] --one_vs_all: softmax over all {} entities per positive; --neg_sample_size {} is ignored; host-built '
                   'plans without negatives'.format(dataset.n_entities, args.neg_sample_size))
         # entity-only deferral (the reference's --async_update) runs as the strict step unless the pipeline is asked for: with the
@@ -560,6 +574,15 @@ class Trainer(_Trainer):
             shared['moments'] = (m.engine.ent_mom, m.engine.rel_mom)
         self.lanes = [_Lane(self, k, m.engine if k == 0 else self.make_engine(**shared), parts[k])
                       for k in range(self.n_lanes)]
+        if self.k_vs_all:
+            # the labels: ONE index of the whole training split, sorted on the device once, as --exclude_positive builds it
+            from .known import KnownIndex
+            self.known = KnownIndex(tuple(np.asarray(x) for x in dataset.train[:3]), dataset.n_entities, dataset.n_relations,
+                                    self.dev)
+            for lane in self.lanes:
+                lane.engine.attach_known(self.known)
+            print('[Train] --k_vs_all: the {} training triples label the answers of every query (h, r, ?) / (?, r, t)'.format(
+                len(self.known)))
         if args.exclude_positive:
             # ONE index of the whole training split, sorted on the device once; the lanes' engines only read it
             from .known import KnownIndex
@@ -976,25 +999,36 @@ def check_loss_flags(args):
 
 
 def check_one_vs_all(args, argv=None):
-    """--one_vs_all runs kge_step_fused on batches without sampled negatives (N == 0) on one GPU's tables with host-built plans: implies --loss_genre Softmax and eager
-    launches, and refuses, before anything is loaded, what that step does not cover.  argv: the command line, to tell a flag that
-    was given from its default"""
-    if not getattr(args, 'one_vs_all', False):
+    """--one_vs_all / --k_vs_all run the N == 0 step (kge_step_fused / kge_step_fused_known on batches without sampled negatives) on
+    one GPU's tables with host-built plans: they imply --loss_genre Softmax / BCE and eager launches, and refuse, before anything is
+    loaded, what that step does not cover.  argv: the command line, to tell a flag that was given from its default"""
+    kva = bool(getattr(args, 'k_vs_all', False))
+    if not kva and getattr(args, 'label_smoothing', 0.0):
+        raise KgeError("--label_smoothing belongs to --k_vs_all")
+    if not kva and not getattr(args, 'one_vs_all', False):
         return
     argv = list(sys.argv[1:] if argv is None else argv)
+    flag, genre = ('--k_vs_all', 'BCE') if kva else ('--one_vs_all', 'Softmax')
 
-    def given(flag):
-        return any(a == flag or a.startswith(flag + '=') for a in argv)
+    def given(name):
+        return any(a == name or a.startswith(name + '=') for a in argv)
+    if kva and getattr(args, 'one_vs_all', False):
+        raise KgeError("--k_vs_all cannot be combined with --one_vs_all (one criterion over every entity)")
     m = models.MODELS[args.model_name]
     if not m.one_vs_all:
-        raise KgeError("--one_vs_all is available for DistMult and ComplEx only (got %s): the other models' scores are no plain "
-                       "product with the candidate row" % args.model_name)
-    if given('--loss_genre') and args.loss_genre != 'Softmax':
-        raise KgeError("--one_vs_all is the softmax over every entity: --loss_genre %s cannot be combined with it" % args.loss_genre)
-    args.loss_genre = 'Softmax'
-    for bad, text in ((args.neg_adversarial_sampling, "-adv (the softmax is the weighting)"), (args.pairwise, "-pw"),
+        raise KgeError("%s is available for DistMult and ComplEx only (got %s): the other models' scores are no plain "
+                       "product with the candidate row" % (flag, args.model_name))
+    if given('--loss_genre') and args.loss_genre != genre:
+        raise KgeError("%s is the %s over every entity: --loss_genre %s cannot be combined with it"
+                       % (flag, 'binary cross-entropy' if kva else 'softmax', args.loss_genre))
+    args.loss_genre = genre
+    if kva and not 0.0 <= args.label_smoothing < 1.0:
+        raise KgeError("--k_vs_all: --label_smoothing must be in [0, 1) (got %g)" % args.label_smoothing)
+    for bad, text in ((args.neg_adversarial_sampling, "-adv (there are no sampled negatives to weight)" if kva else "-adv (the softmax is the weighting)"),
+                      (args.pairwise, "-pw"),
                       (args.neg_deg_sample, "--neg_deg_sample (there are no sampled negatives)"),
-                      (args.exclude_positive, "--exclude_positive (there are no sampled negatives)"),
+                      (args.exclude_positive, "--exclude_positive (the known answers are the labels)" if kva else
+                       "--exclude_positive (there are no sampled negatives)"),
                       (args.subsampling_weight, "--subsampling_weight (batches come from the host sampler)"),
                       (getattr(args, 'optimizer', 'Adagrad') == 'Adam', "--optimizer Adam (the dense trace is an Adagrad update)"),
                       (any(norm_constraints(args)), "--ent_norm / --rel_norm (the dense trace updates every entity row)"),
@@ -1005,10 +1039,10 @@ def check_one_vs_all(args, argv=None):
                       (getattr(args, 'checkpoint_interval', 0), "--checkpoint_interval (no checkpoints of such runs)"),
                       (getattr(args, 'resume', None), "--resume (no checkpoints of such runs)")):
         if bad:
-            raise KgeError("--one_vs_all cannot be combined with %s" % text)
+            raise KgeError("%s cannot be combined with %s" % (flag, text))
     d_e = args.hidden_dim * (2 if args.double_ent else 1)
     if not models.one_vs_all_width_ok(d_e):
-        raise KgeError("--one_vs_all: the entity width must be a multiple of 4 in [4, %d] (got %d)" % (models.ONE_VS_ALL_MAX_DIM, d_e))
+        raise KgeError("%s: the entity width must be a multiple of 4 in [4, %d] (got %d)" % (flag, models.ONE_VS_ALL_MAX_DIM, d_e))
     args.graph_steps = 0
 
 
@@ -1050,7 +1084,7 @@ def check_model_flags(args):
 def main(argv=None, before_train=None):
     """before_train (one GPU): called with the built Trainer in front of its first step - the tests take the initial tables there"""
     args = ArgParser().parse_args(argv)
-    check_one_vs_all(args, argv)                 # before anything is loaded or created (sets --loss_genre Softmax)
+    check_one_vs_all(args, argv)                 # before anything is loaded or created (sets --loss_genre Softmax / BCE)
     check_loss_flags(args)                       # before anything is loaded or created
     check_exclude_positive(args)                 # before anything is loaded or created
     check_model_flags(args)                      # before anything is loaded or created
@@ -1085,7 +1119,7 @@ def main(argv=None, before_train=None):
             raise KgeError("--test: the dataset has no test split")
         if args.neg_sample_size_eval < 0:
             args.neg_sample_size_eval = dataset.n_entities
-    if not args.one_vs_all:
+    if not (args.one_vs_all or args.k_vs_all):
         args.batch_size = get_compatible_batch_size(args.batch_size, args.neg_sample_size)
     if not multi:
         args.batch_size_eval = get_compatible_batch_size(args.batch_size_eval, args.neg_sample_size_eval)

@@ -464,6 +464,26 @@ int kge_step_fused(const kge_hparams *hp, const kge_tables *tb, const kge_batch 
  * KGE_FLAG_NEG_DEG_SAMPLE; kge_step_out.neg_score or g_neg (they do not exist).  Every other step entry refuses a batch with N == 0 as
  * before (kge_step_phase, kge_step_fused_sampling, kge_step_fused_known, kge_step_optim, kge_step_async, kge_step_grads,
  * kge_step_sharded).  KGE_ERR_WORKSPACE: ws_bytes below the size. */
+/* ---- K-vs-all BCE with label smoothing: kge_step_fused_known(job == NULL, known != NULL) on a batch with N == 0 (csrc/kge_kvsall.hip;
+ * DESIGN.md 3.19).  Candidates, operand a_i, scores s_ij, batch layout, traces and their order, workspace and stream conventions:
+ * exactly the 1-vs-all step above.  The criterion: y_ij = 1 when j is row i's own true end (h_i when neg_head, else t_i) or in the
+ * index's list of the row's query - key h_i * n_rel + r_i on the tail side, t_i * n_rel + r_i on the head side, as
+ * kge_known_neg_mask reads it - else 0; an empty index trains 1-vs-all BCE.  With eps = kge_hparams.margin in [0, 1) (no other
+ * N == 0 mode reads that field) and w_i = edge_w[i] or 1:
+ *   y'_ij = (1 - eps) y_ij + eps / n_ent            (the textbook smoothing; ConvE's code adds 1 / n_ent instead)
+ *   l_i   = sum_j softplus(s_ij) - y'_ij s_ij;   loss = (1/B) sum_i w_i l_i
+ *   dL/ds_ij = (w_i / B) (sigma(s_ij) - y'_ij);   dL/dp_i = 0 (the positive is a label like any other; pos_score is still written)
+ * softplus and sigma are evaluated from one exp(-|s|) and stay finite for every finite score.  Rows are the batch's triples, not
+ * unique queries.  loss4 = {nan, nan, loss, regularization}; loss_accum row 2 takes w_i l_i / B.  No score, label or candidate
+ * gradient is stored; there is no forward launch (four matrix products to the softmax step's five); every sum has a fixed order.
+ * kge_step_workspace_bytes for N == 0 adds this mode's buffers (list ranges, own ends, loss parts) only when
+ * hp->loss_genre == KGE_LOSS_BCE; the table's size still does not enter.  mask / mask_bytes are ignored (kge_known_mask_bytes(B, 0)
+ * is 0).  No new entry, struct or field: the ABI number stays 8.
+ * KGE_ERR_ARG before any launch, the message naming the entry and the condition: KGE_LOSS_SOFTMAX with a known index on N == 0
+ * (known answers left out of the softmax row are not built); any other genre than KGE_LOSS_BCE; adv; pairwise; margin outside
+ * [0, 1); a sampler job; a model other than DistMult / ComplEx; d_e outside d_e % 4 == 0, 4 <= d_e <= 512; any KGE_FLAG_*_NORM_* bit
+ * or KGE_FLAG_NEG_DEG_SAMPLE; kge_step_out.neg_score or g_neg; an index with n_rel <= 0, or a side with m > 0 and no arrays.
+ * kge_step_fused on N == 0 and kge_step_fused_known with known == NULL behave exactly as before (the latter refuses N == 0). */
 
 /* ---- --async_update (models/pytorch/tensor_models.py:136-175 async_update, :364-375 create/finish_async_update;
  * models/general_models.py:639-647; train_pytorch.py:120-121, 194-195; docs/source/train.rst:217-259) ----
