@@ -12,6 +12,7 @@
 #include "kge_models.hpp"
 #include "kge_own_fwd.hpp"
 #include "kge_sampler_common.hpp"
+#include "kge_tucker.hpp"
 
 namespace {
 
@@ -59,6 +60,11 @@ int check_model(int model, int d_e, int d_r) {
     const kge::ModelRow *m = kge::model_row(model);
     if (!m) return fail(KGE_ERR_ARG, "unknown model %d", model);
     if (m->bad_dims_first && (d_e <= 0 || d_r <= 0)) return fail(KGE_ERR_ARG, "bad dims d_e=%d d_r=%d", d_e, d_r);
+    if (m->rel == kge::REL_OWN_MULT4) {               // two free widths under one rule: one text per condition (widths_msg takes the
+        if (!kge::mult4_width_ok(d_e)) return fail(KGE_ERR_ARG, m->widths_msg, m->name, "d_e", "d_e", d_e);      // name of the width),
+        if (!kge::mult4_width_ok(d_r)) return fail(KGE_ERR_ARG, m->widths_msg, m->name, "d_r", "d_r", d_r);      // the entity width first
+        return KGE_OK;
+    }
     if (!kge::widths_ok(*m, d_e, d_r)) return fail(KGE_ERR_ARG, m->widths_msg, d_e, d_r);
     return KGE_OK;
 }
@@ -67,7 +73,8 @@ int check_model(int model, int d_e, int d_r) {
 int closed(kge::Entry e, int model, const char *who) {
     const kge::ModelRow *m = kge::model_row(model);
     if (!m || !(m->closed & e)) return KGE_OK;
-    if (e == kge::E_MODULAR) return fail(KGE_ERR_ARG, "%s has no modular score ops: use kge_step_fused / kge_rank_eval_ex", m->name);
+    // (a row without a reason - TransR - keeps the per-op entries' common text; a row with one names the entry like everything else)
+    if (e == kge::E_MODULAR && !m->closed_why) return fail(KGE_ERR_ARG, "%s has no modular score ops: use kge_step_fused / kge_rank_eval_ex", m->name);
     return fail(KGE_ERR_ARG, "%s: not available for %s (%s)", who, m->name, m->closed_why);
 }
 
@@ -712,6 +719,7 @@ int Step::setup(void *ws, size_t ws_bytes) {
                (!sh->rel_local && (sh->rel_rows_per_shard <= 0 || !sh->rel_rows || !sh->rel_state))))
         return fail(KGE_ERR_ARG, "kge_step_sharded: bad shard map");
     if (int rc = check_model(hp->model, hp->d_e, hp->d_r)) return rc;
+    if (int rc = closed(kge::E_STEP_SAMPLED, hp->model, c.who)) return rc;
     if (int rc = check_norm(hp, c.who)) return rc;
     // the relation-matrix models in the gradient-emitting step: only with the relation side applied IN PLACE (emit->gr NULL, the
     // all-to-all engine under relation partitioning).  Their kernels run against the row cache like every model's, the relation
@@ -1423,11 +1431,45 @@ static size_t carve_kva(Carver &cv, OvaBufs &w, KvaBufs &k, const kge_hparams *h
     return cv.off;
 }
 
+// TuckER (kge_tucker.hip) behind either layout: the operand's parts, u, and the backward kernel's parts of GX and GR.
+// The split counts are functions of (B, d_e, d_r) alone (tk_geom)
+struct TkBufs { float *Ap, *U, *GXp, *GRp; };
+static size_t carve_tk(Carver &cv, TkBufs &t, const kge_hparams *hp, int B_) {
+    const size_t B = B_, d_e = hp->d_e, d_r = hp->d_r;
+    const TkGeom g = tk_geom(B_, hp->d_e, hp->d_r);
+    t.Ap = cv.f((size_t)g.So * B * d_e); t.U = cv.f(B * d_e);
+    t.GXp = cv.f((size_t)g.Sb * B * d_e); t.GRp = cv.f((size_t)g.nslabb * B * d_r);
+    return cv.off;
+}
+// the operand launch's arguments (step and ranking); the backward side is filled by the steps
+static void fill_tk(TkArgs &ta, int B, int d_e, int d_r, int neg_head, const float *ent, const float *rel, float *core, const int64_t *h,
+                    const int64_t *r, const int64_t *t, int max_parts = 0) {
+    ta = TkArgs{};
+    ta.B = B; ta.de = d_e; ta.dr = d_r; ta.heads = neg_head ? 1 : 0; ta.g = tk_geom(B, d_e, d_r, max_parts);
+    ta.ent = ent; ta.rel = rel; ta.core = core;
+    ta.xid = neg_head ? t : h; ta.yid = neg_head ? h : t; ta.rid = r;
+}
+// ... the three launches between the criterion's GA kernel and its owner kernel: u and GY, GX and GR, the dense core update
+static int tk_backward(TkArgs &ta, const kge_hparams *hp, const kge_tables *tb, const OvaBufs &w, const TkBufs &t, const float *GAp,
+                       int ga_parts, float *GR, bool reg, hipStream_t s) {
+    ta.core_state = tb->proj_state; ta.GAp = GAp; ta.ga_parts = ga_parts; ta.dP = w.dP; ta.U = t.U; ta.GXp = t.GXp; ta.GRp = t.GRp;
+    ta.GX = ta.heads ? w.GT : w.GH; ta.GY = ta.heads ? w.GH : w.GT; ta.GR = GR;
+    ta.reg_coef = reg ? hp->reg_coef : 0.f; ta.reg_norm = hp->reg_norm; ta.lr = hp->lr; ta.eps = hp->eps;
+    KGE_TRY(launch_tk_u(ta, s));
+    KGE_TRY(launch_tk_bwd(ta, s));                    // reads the core and the rows as they are before any update
+    KGE_TRY(launch_tk_core(ta, s));                   // the dense core update: every core row, once
+    return KGE_OK;
+}
+
 static size_t ova_workspace_bytes(const kge_hparams *hp, int B, int UE, int UR) {
     if (B <= 0 || UE < 0 || UR < 0 || !ova_width_ok(hp->d_e) || hp->d_r <= 0) return 0;
-    Carver cv; OvaBufs w;
-    if (hp->loss_genre == KGE_LOSS_BCE) { KvaBufs k; return carve_kva(cv, w, k, hp, B, UE, UR); }
-    return carve_ova(cv, w, hp, B, UE, UR);
+    const bool tk = hp->model == KGE_TUCKER;
+    if (tk && !ova_width_ok(hp->d_r)) return 0;
+    Carver cv; OvaBufs w; TkBufs t;
+    if (hp->loss_genre == KGE_LOSS_BCE) { KvaBufs k; carve_kva(cv, w, k, hp, B, UE, UR); }
+    else carve_ova(cv, w, hp, B, UE, UR);
+    if (tk) carve_tk(cv, t, hp, B);
+    return cv.off;
 }
 
 static int step_one_vs_all(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b, const kge_step_out *out, void *ws,
@@ -1454,8 +1496,12 @@ static int step_one_vs_all(const kge_hparams *hp, const kge_tables *tb, const kg
     if (!tb->ent || !tb->ent_state || !tb->rel || !tb->rel_state || tb->n_ent <= 0 || !b->h_gid || !b->t_gid || !b->rel_ids || !b->ue_id ||
         !b->ue_pos_ptr || !b->ue_pos_adj || !b->ur_id || !b->ur_ptr || !b->ur_edge || !b->ue_rec || !b->ur_rec)
         return fail(KGE_ERR_ARG, "%s: null table / batch pointer", who);
-    Carver cv(ws, ws_bytes); OvaBufs w;
-    const size_t need = carve_ova(cv, w, hp, b->B, b->UE, b->UR);
+    const bool tk = hp->model == KGE_TUCKER;
+    if (tk && (!tb->proj || !tb->proj_state))
+        return fail(KGE_ERR_ARG, "%s: TuckER needs the core tensor in kge_tables.proj / proj_state", who);
+    Carver cv(ws, ws_bytes); OvaBufs w; TkBufs tkb{};
+    size_t need = carve_ova(cv, w, hp, b->B, b->UE, b->UR);
+    if (tk) need = carve_tk(cv, tkb, hp, b->B);
     if (need > ws_bytes) return fail(KGE_ERR_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     const int B = b->B, d_e = hp->d_e, d_r = hp->d_r;
@@ -1469,7 +1515,12 @@ static int step_one_vs_all(const kge_hparams *hp, const kge_tables *tb, const kg
     fill_edge(ef, src, hp->model, B, d_e, d_r, b->neg_head, hp->gamma, rot_div);
     ef.pos_score = P; ef.A = w.A; ef.do_pos_loss = 0; ef.lp = LossParams{KGE_LOSS_SOFTMAX, 0, 1, hp->adv_temp, hp->margin};
     ef.w = b->edge_w; ef.w_mean = b->edge_w_mean; ef.dpos = w.dP;
-    KGE_TRY(launch_edge_fwd(ef, s));
+    TkArgs ta;                                        // TuckER: the operand is a product with the shared core (kge_tucker.hip)
+    if (tk) {
+        fill_tk(ta, B, d_e, d_r, b->neg_head, tb->ent, tb->rel, tb->proj, b->h_gid, b->rel_ids, b->t_gid);
+        ta.Ap = tkb.Ap; ta.A = w.A; ta.P = P;
+        KGE_TRY(launch_tk_operand(ta, s));
+    } else KGE_TRY(launch_edge_fwd(ef, s));
     OvaArgs oa{};
     oa.B = B; oa.d = d_e; oa.n_ent = tb->n_ent; oa.g = ova_geom(B, d_e, tb->n_ent);
     oa.A = w.A; oa.ent = tb->ent; oa.ent_state = tb->ent_state; oa.part = w.part; oa.pos = P; oa.w = b->edge_w;
@@ -1483,7 +1534,8 @@ static int step_one_vs_all(const kge_hparams *hp, const kge_tables *tb, const kg
     fill_edge_bwd(eb, src, hp->model, B, d_e, d_r, b->neg_head, hp->gamma, rot_div, w.dP, w.GAp);
     eb.reg_coef = reg ? hp->reg_coef : 0.f; eb.reg_norm = hp->reg_norm;
     eb.GH = w.GH; eb.GT = w.GT; eb.GR = GR; eb.ga_parts = oa.g.Sa; eb.ga_stride = (int64_t)B * d_e;
-    KGE_TRY(launch_edge_bwd(eb, s));
+    if (tk) { if (int rc = tk_backward(ta, hp, tb, w, tkb, w.GAp, oa.g.Sa, GR, reg, s)) return rc; }
+    else KGE_TRY(launch_edge_bwd(eb, s));
     KGE_TRY(launch_ova_bwd_e(oa, s));                 // the dense trace: every entity row and its state
     // the update launch, on a plan without negative entries (no record has a negative list: GN is never read; a valid pointer all the same)
     UpdateArgs ua{};
@@ -1541,8 +1593,12 @@ static int step_k_vs_all(const kge_hparams *hp, const kge_tables *tb, const kge_
     if (!tb->ent || !tb->ent_state || !tb->rel || !tb->rel_state || tb->n_ent <= 0 || !b->h_gid || !b->t_gid || !b->rel_ids || !b->ue_id ||
         !b->ue_pos_ptr || !b->ue_pos_adj || !b->ur_id || !b->ur_ptr || !b->ur_edge || !b->ue_rec || !b->ur_rec)
         return fail(KGE_ERR_ARG, "%s: null table / batch pointer", who);
-    Carver cv(ws, ws_bytes); OvaBufs w; KvaBufs kb;
-    const size_t need = carve_kva(cv, w, kb, hp, b->B, b->UE, b->UR);
+    const bool tk = hp->model == KGE_TUCKER;
+    if (tk && (!tb->proj || !tb->proj_state))
+        return fail(KGE_ERR_ARG, "%s: TuckER needs the core tensor in kge_tables.proj / proj_state", who);
+    Carver cv(ws, ws_bytes); OvaBufs w; KvaBufs kb; TkBufs tkb{};
+    size_t need = carve_kva(cv, w, kb, hp, b->B, b->UE, b->UR);
+    if (tk) need = carve_tk(cv, tkb, hp, b->B);
     if (need > ws_bytes) return fail(KGE_ERR_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     const int B = b->B, d_e = hp->d_e, d_r = hp->d_r;
@@ -1556,7 +1612,12 @@ static int step_k_vs_all(const kge_hparams *hp, const kge_tables *tb, const kge_
     fill_edge(ef, src, hp->model, B, d_e, d_r, b->neg_head, hp->gamma, rot_div);
     ef.pos_score = P; ef.A = w.A; ef.do_pos_loss = 0; ef.lp = LossParams{KGE_LOSS_SOFTMAX, 0, 1, hp->adv_temp, 0.f};
     ef.w = b->edge_w; ef.w_mean = b->edge_w_mean; ef.dpos = w.dP;
-    KGE_TRY(launch_edge_fwd(ef, s));
+    TkArgs ta;                                        // TuckER: the operand is a product with the shared core (kge_tucker.hip)
+    if (tk) {
+        fill_tk(ta, B, d_e, d_r, b->neg_head, tb->ent, tb->rel, tb->proj, b->h_gid, b->rel_ids, b->t_gid);
+        ta.Ap = tkb.Ap; ta.A = w.A; ta.P = P;
+        KGE_TRY(launch_tk_operand(ta, s));
+    } else KGE_TRY(launch_edge_fwd(ef, s));
     KvaArgs ka{};
     ka.B = B; ka.d = d_e; ka.n_ent = tb->n_ent; ka.g = ova_geom(B, d_e, tb->n_ent);
     ka.A = w.A; ka.ent = tb->ent; ka.ent_state = tb->ent_state; ka.w = b->edge_w;
@@ -1574,7 +1635,8 @@ static int step_k_vs_all(const kge_hparams *hp, const kge_tables *tb, const kge_
     fill_edge_bwd(eb, src, hp->model, B, d_e, d_r, b->neg_head, hp->gamma, rot_div, w.dP, w.GAp);
     eb.reg_coef = reg ? hp->reg_coef : 0.f; eb.reg_norm = hp->reg_norm;
     eb.GH = w.GH; eb.GT = w.GT; eb.GR = GR; eb.ga_parts = ka.g.Sa; eb.ga_stride = (int64_t)B * d_e;
-    KGE_TRY(launch_edge_bwd(eb, s));
+    if (tk) { if (int rc = tk_backward(ta, hp, tb, w, tkb, w.GAp, ka.g.Sa, GR, reg, s)) return rc; }
+    else KGE_TRY(launch_edge_bwd(eb, s));
     KGE_TRY(launch_kva_bwd_e(ka, s));                 // the dense trace: every entity row and its state
     // the update launch, on a plan without negative entries (as in the 1-vs-all step)
     UpdateArgs ua{};
@@ -1636,6 +1698,12 @@ static int rank_pos_side(int model, int neg_head, const float *ent, const float 
             if (!neg_head) { m.y2 = ent; m.y2idx = h; m.r2 = A; }
         }
         KGE_TRY(launch_rescal_matvec(m, s));
+    } else if (model == KGE_TUCKER) {
+        // a = (x (x) r) . W' (kge_tucker.hip); its parts live in the first TransR entry (1024 floats per row): at most 1024 / d_e splits
+        TkArgs ta;
+        fill_tk(ta, rows, d_e, d_r, neg_head, ent, rel, const_cast<float *>(proj), h, r, t, 1024 / d_e);
+        ta.Ap = w.THP; ta.A = A; ta.P = P;
+        KGE_TRY(launch_tk_operand(ta, s));
     } else if (kge::model_row(model)->own_fwd) {
         // th_chunk == 0 (kge_rank_eval): a in the A entry, the second vector (w, w^, rho) in the RV entry; else A is the stacked operand
         // of chunks of th_chunk rows (PairRE: the pair always lives in A and RV).  |a|^2 in asq; the rows' other scalars (TransH: w^ . a;
@@ -1685,7 +1753,8 @@ static int rank_eval_impl(int model, int neg_head, const float *qent, const floa
     const size_t need = carve_rank(cv, w, Eb, kge::model_row(model)->cand_factor * N, d_e);
     if (need > ws_bytes) return fail(KGE_ERR_WORKSPACE, "kge_rank_eval: workspace too small (%zu < %zu)", ws_bytes, need);
     float *A = w.A, *asq = w.asq, *bsq = w.bsq, *S = w.S;
-    const bool gemm = use_mfma(model, d_e, (int)N, flags);
+    const int sm = model == KGE_TUCKER ? KGE_DISTMULT : model;      // the candidate side's form: TuckER's is the plain product a . e
+    const bool gemm = use_mfma(sm, d_e, (int)N, flags);
     const bool l2g = gemm && model == KGE_TRANSE_L2;
     const float rot_div = rot_div_of(emb_init);
     if (l2g) {       // |b|^2 of every candidate row, once
@@ -1721,19 +1790,19 @@ static int rank_eval_impl(int model, int neg_head, const float *qent, const floa
             tr.HP = w.THP; tr.TP = w.TTP; tr.Q = w.TQ; tr.SG = w.TSG; tr.P = P; tr.S = S; tr.Z = nullptr;
             KGE_TRY(launch_transr_pos(tr, s));
             KGE_TRY(launch_transr_fwd(tr, s));
-        } else if (gemm && rank_gemm_supported(model, d_e)) {
+        } else if (gemm && rank_gemm_supported(sm, d_e)) {
             // one tiled GEMM per batch whose epilogue keeps the comparison bits; ranks from the mask (kge_rank_gemm.hip)
-            KGE_TRY(launch_rank_gemm(model, A, rows, cent, cand, N, d_e, gamma, clamp_of(model), asq, bsq, P, S, filt_ptr, filt_ids, e0,
+            KGE_TRY(launch_rank_gemm(sm, A, rows, cent, cand, N, d_e, gamma, clamp_of(sm), asq, bsq, P, S, filt_ptr, filt_ids, e0,
                                      ranks, s));
             continue;
         } else if (gemm) {
-            GemmArgs g; fill_gemm(g, model, 1, rows, (int)N, d_e, gamma, A, cent, cand);
+            GemmArgs g; fill_gemm(g, sm, 1, rows, (int)N, d_e, gamma, A, cent, cand);
             g.S = S; g.asq = asq; g.bsq = bsq;
             KGE_TRY(launch_neg_fwd_gemm(g, s));
         } else if (model == KGE_PAIRRE) {
             KGE_TRY(kge::own_scores(model, OwnBlock{1, rows, (int)N, d_e, gamma, OwnOperand{A, w.RV, nullptr, nullptr, nullptr, bsq}, cent, cand, nullptr}, S, s));
         } else {
-            NegArgs na; fill_pair(na, model, 1, rows, (int)N, d_e, gamma, A, cent, cand);
+            NegArgs na; fill_pair(na, sm, 1, rows, (int)N, d_e, gamma, A, cent, cand);
             na.S = S;
             KGE_TRY(launch_neg_fwd_pair(na, s));
         }
@@ -1759,6 +1828,7 @@ int kge_rank_eval_ex(int model, int neg_head, const float *ent, int64_t n_ent, c
     if (int rc = check_model(model, d_e, d_r)) return rc;
     if (model == KGE_TRANSR && (!proj || !cand))
         return fail(KGE_ERR_ARG, "kge_rank_eval_ex: TransR needs the projection table and an explicit candidate list");
+    if (model == KGE_TUCKER && !proj) return fail(KGE_ERR_ARG, "kge_rank_eval_ex: TuckER needs the core tensor (proj)");
     if (n_ent <= 0) return fail(KGE_ERR_ARG, "kge_rank_eval: bad argument");
     if (int rc = check_rank_args("kge_rank_eval", ent, rel, n_rel, h, r, t, E, filt_ptr, filt_ids, Eb, ranks, ws)) return rc;
     const int64_t N = cand ? n_cand : n_ent;
@@ -1826,6 +1896,7 @@ int kge_rank_eval_chunked(int model, int neg_head, const float *ent, int64_t n_e
                           const int64_t *filt_ptr, const int64_t *filt_ids, int32_t *ranks, float *pos_score_out,
                           void *ws, size_t ws_bytes, unsigned flags, void *stream) {
     if (int rc = check_model(model, d_e, d_r)) return rc;
+    if (int rc = closed(kge::E_RANK_CHUNKED, model, "kge_rank_eval_chunked")) return rc;
     if (chunk <= 0) return fail(KGE_ERR_ARG, "kge_rank_eval_chunked: chunk must be positive (got %d)", chunk);
     if (self_cand && filt_ptr)
         return fail(KGE_ERR_ARG, "kge_rank_eval_chunked: self_cand and a filter exclude each other "

@@ -10,9 +10,11 @@ namespace kge {
 
 // entries that refuse some model outright (ModelRow::closed: one bit each)
 enum Entry { E_STEP_ASYNC = 1, E_STEP_SHARDED = 2, E_STEP_GRADS = 4, E_STEP_FUSED_SAMPLING = 8, E_RANK_EVAL_SPLIT = 16,
-             E_RANK_REL_EVAL = 32, E_MODULAR = 64, E_TOPK = 128, E_STEP_ONE_VS_ALL = 256 };
-// d_r as the width rule wants it next to d_e: the same, twice, half, the square (RESCAL's matrix), or any width up to 1024 (TransR)
-enum RelWidth { REL_SAME, REL_DOUBLE, REL_HALF, REL_SQUARE, REL_UPTO_1024 };
+             E_RANK_REL_EVAL = 32, E_MODULAR = 64, E_TOPK = 128, E_STEP_ONE_VS_ALL = 256, E_STEP_SAMPLED = 512,
+             E_RANK_CHUNKED = 1024 };       // E_STEP_SAMPLED: every step on a batch with sampled negatives (N > 0), whatever the entry
+// d_r as the width rule wants it next to d_e: the same, twice, half, the square (RESCAL's matrix), any width up to 1024 (TransR), or
+// a width of its own under the rule of the all-entity steps' entity width, a multiple of 4 in 4 .. 512 (TuckER)
+enum RelWidth { REL_SAME, REL_DOUBLE, REL_HALF, REL_SQUARE, REL_UPTO_1024, REL_OWN_MULT4 };
 
 // the norm constraints (KGE_FLAG_ENT_NORM_* / KGE_FLAG_REL_NORM_*, kge_constrain.hip): a row is `ent` / `rel` equal slices, each projected
 // by the flag's mode; rel == 0: the relation bits are refused, for the reason rel_why; bit k of rel_unit: relation slice k is normalised
@@ -68,10 +70,21 @@ inline const ModelRow *model_row(int id) {
          "kge_topk_select: TransD needs d_e == d_r and d_e %% 8 == 0, rows [x | x_p] (got %d, %d)", OWN_FWD | OVA, ENTITY_ONLY, false,
          2, 1, 2, true, {2, 2, 0, nullptr}},          // [a block | rho block | sigma | u]; [e | e_p], [r | r_p]
     };
+    // A model of the all-entity steps alone (dglke_amd/models.py, ALL_ENTITY_ONLY), outside the table of the strict step's models:
+    // those steps refuse the norm flags, so it has no slices to list.  (Ids 16 .. 20 are the similarity functions of kge_topk_select.)
+    // The core tensor is the third table; the operand a is a product with it (kge_tucker.hip), the candidate side the plain product
+    // a . e.  widths_msg is one text for either width: it takes (model, width name, width name, value)
+    static const NormSlices WHOLE_ROWS = {1, 1, 0, nullptr};
+    static const ModelRow tucker = {KGE_TUCKER, "TuckER", 4, 512, REL_OWN_MULT4, false, "%s needs %s %% 4 == 0 and 4 <= %s <= 512 (got %d)",
+        nullptr, OWN_FWD | E_MODULAR | E_TOPK | E_STEP_SAMPLED | E_RANK_CHUNKED,
+        "the 1-vs-all and K-vs-all steps on local tables and single-table entity ranking", false, 1, 1, 0, false, WHOLE_ROWS};
+    if (id == tucker.id) return &tucker;
     for (const ModelRow &m : rows)
         if (m.id == id) return &m;
-    return nullptr;                                   // ids 9, 11, 13 and everything outside 0 .. 14: "unknown model"
+    return nullptr;                                   // ids 9, 11, 13, 15 .. 21 and everything outside 0 .. 22: "unknown model"
 }
+
+inline bool mult4_width_ok(int d) { return d >= 4 && d % 4 == 0 && d <= 512; }      // REL_OWN_MULT4: the rule of either width
 
 inline bool widths_ok(const ModelRow &m, int d_e, int d_r) {
     if (d_e < m.ent_multiple || d_e % m.ent_multiple || (m.ent_max && d_e > m.ent_max)) return false;
@@ -80,6 +93,7 @@ inline bool widths_ok(const ModelRow &m, int d_e, int d_r) {
     case REL_DOUBLE: return (int64_t)d_r == 2 * (int64_t)d_e;
     case REL_HALF: return d_r == d_e / 2;
     case REL_SQUARE: return (int64_t)d_r == (int64_t)d_e * d_e;
+    case REL_OWN_MULT4: return mult4_width_ok(d_r);
     default: return d_r > 0 && d_r <= 1024;
     }
 }

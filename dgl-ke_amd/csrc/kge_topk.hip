@@ -608,6 +608,10 @@ static int topk_select_impl(int func, int side, const float *ent, int64_t n_ent,
     if (filt_ptr && !filt_ids) return tk_fail("kge_topk_select_filtered: filt_ptr given without filt_ids");
     const bool sim = func >= KGE_SIM_COSINE && func <= KGE_SIM_EXT_JACCARD;
     const kge::ModelRow *m = sim ? nullptr : kge::model_row(func);
+    if (!sim && m && (m->closed & kge::E_TOPK) && m->closed_why) {      // (a row with a reason: by name; TransR keeps the common text)
+        snprintf(msg, sizeof(msg), "kge_topk_select: not available for %s (%s)", m->name, m->closed_why);
+        return tk_fail(msg);
+    }
     if (!sim && (!m || (m->closed & kge::E_TOPK))) {
         snprintf(msg, sizeof(msg), "kge_topk_select: unknown score function %d (TransR has no inference path)", func);
         return tk_fail(msg);

@@ -18,7 +18,7 @@ class StepEngine(object):
                  adversarial_temperature=1.0, regularization_coef=0.0, regularization_norm=3,
                  loss_genre='Logsigmoid', pairwise=False, margin=1.0, flags=0,
                  tables=None, shards=None, optimizer='Adagrad', adam_betas=(0.9, 0.999), adam_eps=1e-8, moments=None,
-                 ent_norm=None, rel_norm=None, one_vs_all=False, k_vs_all=False, label_smoothing=0.0):
+                 ent_norm=None, rel_norm=None, one_vs_all=False, k_vs_all=False, label_smoothing=0.0, relation_dim=None):
         """optimizer 'Adam': lazy row-sparse Adam with a per-row step count (include/kge_hip.h, kge_step_optim) - the state
         tables hold the counts, the engine owns the moment tables ent_mom [n_ent, 2, d_e] / rel_mom [n_rel, 2, d_r] (`moments`:
         a pair the caller shares between engines, as `tables` shares the rows and the state).
@@ -30,7 +30,10 @@ class StepEngine(object):
         k_vs_all: the K-vs-all step (include/kge_hip.h, kge_step_fused_known on a batch with N == 0): binary cross-entropy over every
         entity, label 1 for the row's own true end and for every entity the attached index (`attach_known`, required before `step`;
         an empty index trains 1-vs-all BCE) lists for the row's query, smoothed by label_smoothing in [0, 1).  loss_genre 'BCE'; the
-        rest as one_vs_all, with which it is mutually exclusive."""
+        rest as one_vs_all, with which it is mutually exclusive.
+        TuckER (include/kge_hip.h, KGE_TUCKER): one_vs_all or k_vs_all is required; the third table is the core tensor, proj
+        [d_r * d_e, d_e] with its Adagrad state proj_state [d_r * d_e] (tables = (ent, ent_state, rel, rel_state, proj,
+        proj_state)); relation_dim: the relation width d_r, a multiple of 4 in [4, 512] (default: as hidden_dim gives it)."""
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise _lib.KgeError("StepEngine needs a CUDA (HIP) device; there is no CPU fallback")
@@ -43,7 +46,17 @@ class StepEngine(object):
         self.d_r = 2 * hidden_dim if double_relation_emb else hidden_dim
         if model_name == 'RESCAL':                          # relation row = [rel_dim x ent_dim] matrix, general_models.py:232-236
             self.d_r = self.d_r * self.d_e
-        m = models.MODELS.get(model_name)                   # (unknown names: model_id below)
+        m = models.record(model_name)                       # (unknown names: model_id below)
+        core = bool(m and m.core_tensor)
+        if relation_dim is not None:
+            if not core:
+                raise _lib.KgeError("relation_dim belongs to TuckER (the other models' relation width follows from hidden_dim)")
+            self.d_r = int(relation_dim)
+        if core and models.one_vs_all_width_ok(self.d_e) and not models.one_vs_all_width_ok(self.d_r):
+            raise _lib.KgeError("TuckER needs a relation width that is a multiple of 4 in [4, 512] (got %d)" % self.d_r)
+        if core and not (one_vs_all or k_vs_all):
+            raise _lib.KgeError("TuckER trains on the all-entity steps only: one_vs_all=True or k_vs_all=True (the sampled step has "
+                                "no TuckER form)")
         if m and not models.widths_ok(m, self.d_e, self.d_r):
             raise _lib.KgeError(m.engine_text % (self.d_e, self.d_r))
         if m and m.single_gpu_only and shards is not None:
@@ -106,6 +119,9 @@ class StepEngine(object):
             if model_name == 'TransR':
                 self.proj = torch.empty(n_relations, self.d_e * self.d_r, dtype=torch.float32, device=self.device)
                 self.proj_state = torch.zeros(n_relations, dtype=torch.float32, device=self.device)
+            if core:                                        # row l * d_e + k is W[l][k][:]
+                self.proj = torch.empty(self.d_r * self.d_e, self.d_e, dtype=torch.float32, device=self.device)
+                self.proj_state = torch.zeros(self.d_r * self.d_e, dtype=torch.float32, device=self.device)
             self.ent = torch.empty(n_entities, self.d_e, dtype=torch.float32, device=self.device)
             self.ent_state = torch.zeros(n_entities, dtype=torch.float32, device=self.device)
             self.rel = torch.empty(n_relations, self.d_r, dtype=torch.float32, device=self.device)
@@ -116,6 +132,10 @@ class StepEngine(object):
             if model_name == 'TransR':
                 if len(tables) < 6:
                     raise _lib.KgeError("TransR needs tables = (ent, ent_state, rel, rel_state, proj, proj_state)")
+                self.proj, self.proj_state = tables[4], tables[5]
+            if core:
+                if len(tables) < 6 or tuple(tables[4].shape) != (self.d_r * self.d_e, self.d_e):
+                    raise _lib.KgeError("TuckER needs tables = (ent, ent_state, rel, rel_state, proj [d_r * d_e, d_e], proj_state)")
                 self.proj, self.proj_state = tables[4], tables[5]
         self.one_vs_all, self.k_vs_all = bool(one_vs_all), bool(k_vs_all)
         if self.one_vs_all and self.k_vs_all:
@@ -294,8 +314,9 @@ class StepEngine(object):
         if getattr(self, 'ent_mom', None) is not None:
             self.ent_mom.zero_()
             self.rel_mom.zero_()
-        if self.proj is not None:                 # TransRScore.reset_parameters: projection_emb.init(1.0)
-            torch.nn.init.uniform_(self.proj, -1.0, 1.0)
+        if self.proj is not None:                 # TransRScore.reset_parameters: projection_emb.init(1.0); TuckER's core: as the rows
+            lim = self.emb_init if models.record(self.model_name).core_tensor else 1.0
+            torch.nn.init.uniform_(self.proj, -lim, lim)
             self.proj_state.zero_()
         self.project_tables()
 
@@ -303,7 +324,7 @@ class StepEngine(object):
         """the projection of the norm constraints on EVERY row of the constrained tables, in place (torch on the device: not a hot
         path).  Fresh tables are projected once, so that rows no step has touched yet satisfy the constraint too; a step projects
         the rows it updates itself.  Nothing to do without ent_norm / rel_norm."""
-        m = models.MODELS[self.model_name]
+        m = models.record(self.model_name)
         for table, mode, t in (('ent', getattr(self, 'ent_norm', None), self.ent), ('rel', getattr(self, 'rel_norm', None), self.rel)):
             modes = models.norm_slices(m, table, mode)
             if not modes:
@@ -342,7 +363,7 @@ class StepEngine(object):
         tensors themselves, not copies: engines that share tables name the same ones."""
         t = {'entity': self.ent, 'relation': self.rel, 'entity_state': self.ent_state, 'relation_state': self.rel_state}
         if self.proj is not None:
-            t['projection'], t['projection_state'] = self.proj, self.proj_state
+            t['projection'], t['projection_state'] = self.proj, self.proj_state        # (TuckER: the core tensor)
         if self.opt is not None:
             t['entity_mom'], t['relation_mom'] = self.ent_mom, self.rel_mom
         return t

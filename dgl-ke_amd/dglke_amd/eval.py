@@ -157,9 +157,12 @@ class Ranker(object):
         self.gamma, self.emb_init = float(gamma), float(emb_init)
         self.batch = int(batch)
         self.flags = int(flags)
-        self.proj = proj                   # TransR: projection table [n_rel, d_e * d_r]
+        self.proj = proj                   # TransR: projection table [n_rel, d_e * d_r]; TuckER: the core tensor [d_r * d_e, d_e]
         if model_name == 'TransR' and proj is None:
             raise _lib.KgeError("TransR ranking needs the projection table (proj=...)")
+        if model_name == 'TuckER' and proj is None:
+            raise _lib.KgeError("TuckER ranking needs the core tensor (proj=...)")
+        self._list_all = model_name == 'TransR'
         self._ws = None
         self._all = None
         self._cws = None                   # workspace of chunked_ranks
@@ -283,7 +286,7 @@ class Ranker(object):
             return torch.as_tensor(np.ascontiguousarray(x)).to(dev, dt)
         h, r, t, cand = put(h), put(r), put(t), put(cand)
         E = int(h.shape[0])
-        if cand is None and self.proj is not None:         # TransR kernels walk an explicit candidate list
+        if cand is None and self._list_all:                # TransR kernels walk an explicit candidate list
             if self._all is None:
                 self._all = torch.arange(self.ent.shape[0], dtype=torch.int64, device=dev)
             cand = self._all

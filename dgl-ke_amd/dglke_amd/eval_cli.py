@@ -71,7 +71,7 @@ def load_tables(args, ds, dev, rows=None):
         raise KgeError("entity embeddings are {} but the dataset / flags say {}".format(tuple(ent.shape), (ds.n_entities, d_e)))
     if rows:
         ent = np.ascontiguousarray(ent[rows[0]:rows[1]])
-    return put(ent), put(load('_relation')), put(load('projection')) if models.MODELS[args.model_name].projection else None
+    return put(ent), put(load('_relation')), put(load('projection')) if models.third_table(models.record(args.model_name)) else None
 
 
 def main(argv=None):
@@ -91,11 +91,13 @@ def main(argv=None):
         raise KgeError("--eval_relation ranks against all relations: the lists of --eval_candidates are entity lists")
     from .train import check_model_widths     # before anything is loaded
     check_model_widths(args.model_name, args.hidden_dim, args.double_ent, args.double_rel)
-    m = models.MODELS[args.model_name]
+    m = models.record(args.model_name)
     if m.single_gpu_only and len(args.gpu) > 1:
         raise KgeError("%s is not available on sharded tables (--gpu takes one entry)" % m.name)
     if m.no_relation_ranking and args.eval_relation:
         raise KgeError("%s has no relation ranking (--eval_relation): %s" % (m.name, m.no_relation_ranking))
+    from .train import check_full_ranking_only
+    check_full_ranking_only(m, args)
     if args.gpu[0] < 0:
         raise KgeError("dglke_eval ranks on the GPU only: pass --gpu <id> (there is no CPU fallback)")
     if not os.path.isdir(args.model_path):
@@ -109,7 +111,7 @@ def main(argv=None):
     th.cuda.set_device(dev)
     ds = kd.load_dataset(0, args)
     ent, rel, proj = load_tables(args, ds, dev)
-    model = models.MODELS[args.model_name].alias_of or args.model_name
+    model = models.record(args.model_name).alias_of or args.model_name
     emb_init = (args.gamma + 2.0) / args.hidden_dim
     cands = None
     if args.eval_candidates:
@@ -154,7 +156,7 @@ def _sharded_worker(rank, args):
     ds = kd.load_dataset(rank, args)
     spec = kd.ShardSpec(ds.n_entities, world, rank)
     shard, rel, proj = load_tables(args, ds, dev, rows=(spec.lo, spec.hi))
-    model = models.MODELS[args.model_name].alias_of or args.model_name
+    model = models.record(args.model_name).alias_of or args.model_name
     comm = kd.make_comm() if len(set(args.gpu)) == world else kd.HostStagedComm()
     try:
         test, known, Eb, _ = kev.eval_setup(ds, 'test', args)

@@ -44,7 +44,7 @@ class KEModel(object):
                                       bool(getattr(args, 'neg_adversarial_sampling', False)),
                                       getattr(args, 'adversarial_temperature', None) or 1.0,
                                       bool(getattr(args, 'pairwise', False)))
-        m = models.MODELS.get(model_name)
+        m = models.record(model_name)
         if m and not models.widths_ok(m, entity_dim, relation_dim):
             raise KgeError(m.kemodel_text % (entity_dim, relation_dim))
         self.entity_emb = ExternalEmbedding(args, n_entities, entity_dim, device)
@@ -69,6 +69,8 @@ class KEModel(object):
         elif model_name == 'TransR':
             projection_emb = ExternalEmbedding(args, n_relations, entity_dim * relation_dim, device)
             self.score_func = TransRScore(gamma, projection_emb, relation_dim, entity_dim)
+        elif m.core_tensor:                 # TuckER: the core tensor W[l][k][:] in rows l * entity_dim + k
+            self.score_func = score_fun.TuckERScore(ExternalEmbedding(args, relation_dim * entity_dim, entity_dim, device), self.emb_init)
         else:
             given = {'gamma': gamma, 'emb_init': self.emb_init}
             self.score_func = getattr(score_fun, m.score)(*[given.get(x, x) for x in m.score_args])
@@ -84,7 +86,7 @@ class KEModel(object):
     def tables(self):
         """the tables and their Adagrad states as StepEngine(tables=...) takes them: engines built on them train this model"""
         t = (self.entity_emb.emb, self.entity_emb.state_sum, self.relation_emb.emb, self.relation_emb.state_sum)
-        if self.model_name == 'TransR':
+        if hasattr(self.score_func, 'projection_emb'):       # TransR's projection matrices, TuckER's core tensor
             t += (self.score_func.projection_emb.emb, self.score_func.projection_emb.state_sum)
         return t
 
@@ -108,7 +110,7 @@ class KEModel(object):
         e = self.engine
         e.ent, e.ent_state = self.entity_emb.emb, self.entity_emb.state_sum
         e.rel, e.rel_state = self.relation_emb.emb, self.relation_emb.state_sum
-        if self.model_name == 'TransR':
+        if hasattr(self.score_func, 'projection_emb'):
             e.proj, e.proj_state = self.score_func.projection_emb.emb, self.score_func.projection_emb.state_sum
         e._bind_tables()
 

@@ -24,14 +24,15 @@ Model = namedtuple('Model', [
     'norm_rel_unit',               # ... bit k: relation slice k is normalised to length 1 under either relation mode (TransH's w)
     'no_rel_norm',                 # ... None, or why --rel_norm does not apply
     'one_vs_all',                  # --one_vs_all / --k_vs_all and the engine's modes of those names: the score is a plain product a . e (DistMult, ComplEx)
-    'projection', 'relation_matrix', 'alias_of'])     # TransR's third table; RESCAL's relation rows are matrices; TransE is TransE_l2
+    'projection', 'relation_matrix', 'alias_of',      # TransR's third table; RESCAL's relation rows are matrices; TransE is TransE_l2
+    'core_tensor'])                # TuckER: the third table is ONE core tensor [d_r * d_e, d_e]; d_r is free within the all-entity width rule
 
 
 def _model(name, id, score, score_args=(), **kw):
     d = dict.fromkeys(Model._fields)
     d.update(name=name, id=id, score=score, score_args=score_args, rank_cands=1, topk_row=lambda d_e: d_e, multiple_first=False,
              single_gpu_only=False, no_stale_pipeline=False, projection=False, relation_matrix=False, norm_ent=1, norm_rel=1,
-             norm_rel_unit=0, one_vs_all=False)
+             norm_rel_unit=0, one_vs_all=False, core_tensor=False)
     d.update(kw)
     return Model(**d)
 
@@ -88,15 +89,39 @@ MODELS = OrderedDict((m.name, m) for m in (       # in the order of the --model_
            rank_cands=2, topk_row=lambda d_e: d_e + 2, norm_ent=2, norm_rel=2,            # [e | e_p], [r | r_p]
            **dict(_LOCAL, **_TWO_PROJECTIONS)),
 ))
-NAMES = list(MODELS)                                                 # the --model_name choices
+# The models of the all-entity steps alone, outside the table of the strict step's models (the command lines and the norm slices walk
+# that one).  (Ids 16 .. 20 are the similarity functions of kge_topk_select.)  s = sum r_l h_k W[l][k][m] t_m with one core tensor for
+# every edge (csrc/kge_tucker.hip).  No batch normalisation, no dropout
+ALL_ENTITY_ONLY = OrderedDict((m.name, m) for m in (
+    _model('TuckER', 22, 'TuckERScore', one_vs_all=True, core_tensor=True,
+           cli_multiple=4, cli_of='hidden_dim', multiple_text="TuckER: --hidden_dim must be a multiple of 4 (got %(hidden)d)",
+           kemodel_text="TuckER needs entity_dim and relation_dim that are multiples of 4 in [4, 512] (got %d, %d)",
+           engine_text="TuckER needs an entity width that is a multiple of 4 in [4, 512] (got %d; relation width %d)",
+           no_relation_ranking="the relation row enters through the core tensor",
+           no_relation_ranking_lib="the relation row enters through the core tensor: no relation ranking", **_LOCAL),
+))
+NAMES = list(MODELS) + list(ALL_ENTITY_ONLY)                         # the --model_name choices
 DEFAULT = 'TransE'                                                   # ... and its default
-MODEL_IDS = dict((m.name, m.id) for m in MODELS.values())            # (ids 9, 11 and 13 are not models)
-BY_ID = dict((m.id, m) for m in MODELS.values() if not m.alias_of)
+MODEL_IDS = dict((m.name, m.id) for m in list(MODELS.values()) + list(ALL_ENTITY_ONLY.values()))      # (ids 9, 11, 13, 15 .. 21 are not models)
+BY_ID = dict((m.id, m) for m in list(MODELS.values()) + list(ALL_ENTITY_ONLY.values()) if not m.alias_of)
+
+
+def record(name):
+    """the record of a model name from either table, or None"""
+    return MODELS.get(name) or ALL_ENTITY_ONLY.get(name)
 
 
 def widths_ok(m, d_e, d_r):
     """the width rule of a record (True where it has none: the older models' rules live in the library and in KEModel)"""
+    if m.core_tensor:                                                # each width under the rule of the all-entity steps
+        return one_vs_all_width_ok(d_e) and one_vs_all_width_ok(d_r)
     return m.rel_width is None or (d_e >= m.ent_multiple and d_e % m.ent_multiple == 0 and d_r == m.rel_width(d_e))
+
+
+def third_table(m):
+    """the model keeps a third table next to the entity and relation rows, saved as <dataset>_<model>projection.npy: TransR's
+    projection matrices, TuckER's core tensor"""
+    return m.projection or m.core_tensor
 
 
 def own_relation_update(m):

@@ -116,6 +116,8 @@ def check_args(args):
     config = load_model_config(os.path.join(args.model_path, 'config.json'))
     if config['model_name'] == 'TransR':
         raise KgeError("TransR has no inference path (the reference's InferModel refuses it too)")
+    if config['model_name'] == 'TuckER':
+        raise KgeError("dglke_predict: TuckER has no prediction path (top-K selection is closed to it)")
     from .train import check_model_widths
     check_model_widths(config['model_name'], config['hidden_dim'], config['double_ent'], config['double_rel'])
     head, rel, tail, id2e, id2r = parse_inputs(args)

@@ -94,6 +94,26 @@ class ComplExScore(_HipScore):
     model_name = 'ComplEx'
 
 
+class TuckERScore(_HipScore):
+    """TuckER (include/kge_hip.h, KGE_TUCKER): the score goes through one core tensor shared by every edge.  It has no per-op score
+    kernels - the library refuses them by name; the model trains through StepEngine (one_vs_all / k_vs_all) and ranks through
+    eval.Ranker, which hold the core as their third table.  Here it is projection_emb [relation_dim * entity_dim, entity_dim], row
+    l * entity_dim + k = W[l][k][:], initialised like the rows and saved and loaded the way TransR's third table is."""
+    model_name = 'TuckER'
+
+    def __init__(self, projection_emb, emb_init):
+        self.projection_emb, self.emb_init = projection_emb, emb_init
+
+    def reset_parameters(self):
+        self.projection_emb.init(self.emb_init)
+
+    def save(self, path, name):
+        self.projection_emb.save(path, name + 'projection')
+
+    def load(self, path, name):
+        self.projection_emb.load(path, name + 'projection')
+
+
 class QuatEScore(_HipScore):
     """QuatE (Zhang et al., NeurIPS 2019): rows are four quarters [a | b | c | d], one quaternion per column; the relation is
     normalised per quaternion and score = sum <h (x) r^, t> (include/kge_hip.h, enum kge_model).  No gamma, no clamp."""

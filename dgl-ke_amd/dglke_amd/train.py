@@ -536,6 +536,10 @@ class Trainer(_Trainer):
             print('[Train] --ent_norm {}, --rel_norm {}: every step projects the rows it has updated (radius 1); the fresh tables '
                   'were projected once'.format(self.norms[0] or 'none', self.norms[1] or 'none'))
         self.n_lanes = max(1, int(args.num_proc))
+        if models.record(args.model_name).core_tensor:
+            print('[Train] TuckER: one core tensor of {} x {} x {} = {} parameters ({:.1f} MB) shared by every edge, updated whole in '
+                  'every step'.format(m.rel_dim, m.entity_dim, m.entity_dim, m.rel_dim * m.entity_dim ** 2,
+                                      4e-6 * m.rel_dim * m.entity_dim ** 2))
         if self.k_vs_all:
             print('[Train] --k_vs_all: binary cross-entropy over all {} entities per positive, label smoothing {}; --neg_sample_size {} '
                   'is ignored; host-built plans without negatives'.format(dataset.n_entities, args.label_smoothing, args.neg_sample_size))
@@ -544,7 +548,7 @@ class Trainer(_Trainer):
                   'plans without negatives'.format(dataset.n_entities, args.neg_sample_size))
         # entity-only deferral (the reference's --async_update) runs as the strict step unless the pipeline is asked for: with the
         # relation trace landing between two steps the pipeline needs one more launch than it hides
-        async_ok = not models.own_relation_update(models.MODELS[args.model_name])
+        async_ok = not models.own_relation_update(models.record(args.model_name))
         pipeline = args.async_update_rel or args.async_update_pipeline
         self.async_update = bool(args.async_update and async_ok and pipeline)
         if args.async_update and not async_ok:
@@ -610,7 +614,7 @@ class Trainer(_Trainer):
     def evaluate(self, which, mode):
         args, m = self.args, self.model
         test, known, Eb, _ = kev.eval_setup(self.dataset, which, args)
-        proj = m.score_func.projection_emb.emb if models.MODELS[args.model_name].projection else None
+        proj = m.score_func.projection_emb.emb if models.third_table(models.record(args.model_name)) else None
         # (the split and the known set do not change during a run: filter lists and test ids stay on the device between validations)
         cache = self.__dict__.setdefault('_eval_cache', {}).setdefault(which, {})
         metrics = kev.evaluate(args.model_name, m.entity_emb.emb, m.relation_emb.emb, args.gamma, m.emb_init, test, known,
@@ -640,7 +644,7 @@ class ShardedTrainer(_Trainer):
         # and TransR's projection table - is LOCAL to the trainer that holds the relation's edges, so the triples are partitioned
         # BY RELATION (whole relations): the reference's --rel_part layout, which its own multi-GPU TransR recipe passes
         # (examples/freebase/multi_gpu.sh:80-89, general_models.py:590-637).  The owners' rows are collected by sync_tables.
-        self.rel_side_local = models.own_relation_update(models.MODELS[args.model_name])
+        self.rel_side_local = models.own_relation_update(models.record(args.model_name))
         if self.rel_side_local and args.neg_deg_sample:
             raise KgeError("--neg_deg_sample is not available for %s on more than one GPU" % args.model_name)
         self.rel_owner = None
@@ -658,9 +662,9 @@ class ShardedTrainer(_Trainer):
                       "(whole relations; edges per trainer %s)" % (args.model_name, world, np.bincount(edge_rank, minlength=world).tolist()))
         part = self.split(world, edge_rank, refusal)[rank]
         self.tabs = p2p.ShardedTables(dataset.n_entities, dataset.n_relations, self.d_e,
-                                      self.d_r * self.d_e if models.MODELS[args.model_name].relation_matrix else self.d_r, self.dev, world, rank,
+                                      self.d_r * self.d_e if models.record(args.model_name).relation_matrix else self.d_r, self.dev, world, rank,
                                       rel_local=self.rel_side_local,
-                                      proj_dim=self.d_e * self.d_r if models.MODELS[args.model_name].projection else 0)
+                                      proj_dim=self.d_e * self.d_r if models.record(args.model_name).projection else 0)
         if not self.tabs.probe():
             raise KgeError("peer mappings do not reach the other GPUs' memory")
         self.tabs.init_uniform(self.emb_init, args.seed)
@@ -715,7 +719,7 @@ class ShardedTrainer(_Trainer):
                              self.dataset.n_entities)
         if self.rank == 0:
             np.save(os.path.join(args.save_path, '%s_%s_relation.npy' % (args.dataset, args.model_name)), rel.cpu().numpy())
-            if models.MODELS[args.model_name].projection:      # TransRScore.save (score_fun.py:190-191): <dataset>_<model>projection.npy
+            if models.record(args.model_name).projection:      # TransRScore.save (score_fun.py:190-191): <dataset>_<model>projection.npy
                 np.save(os.path.join(args.save_path, '%s_%sprojection.npy' % (args.dataset, args.model_name)),
                         self.projection().cpu().numpy())
             write_config(args, emap_file, rmap_file)
@@ -730,7 +734,7 @@ class ShardedTrainer(_Trainer):
         cache = self.__dict__.setdefault('_eval_cache', {}).setdefault(which, {})
         metrics = kev.evaluate_sharded(args.model_name, shard, lo, ds.n_entities, self.relation_table(), args.gamma, self.emb_init,
                                        test, self.entity_rows, known, batch=Eb,
-                                       proj=self.projection() if models.MODELS[args.model_name].projection else None,
+                                       proj=self.projection() if models.record(args.model_name).projection else None,
                                        n_cand=args.neg_sample_size_eval, chunk=args.batch_size_eval, seed=args.seed + 29, cache=cache)
         if self.rank == 0:
             kev.print_metrics(mode, metrics)
@@ -808,7 +812,7 @@ class A2ATrainer(ShardedTrainer):
             if self.rel_side_local:
                 print("%s on %d GPUs (a2a): entity messages exchanged, relation-side tables (relation rows%s) applied in place on the "
                       "trainer that holds the relation's edges" % (args.model_name, world,
-                                                                    ", projection matrices" if models.MODELS[args.model_name].projection else " = matrices"))
+                                                                    ", projection matrices" if models.record(args.model_name).projection else " = matrices"))
 
     def enqueue(self, n):
         """n sharded steps, eagerly (every rank issues the same collectives in the same order); inside a group of sampled
@@ -942,7 +946,7 @@ def check_optimizer(args):
     loaded: what that step does not cover"""
     if getattr(args, 'optimizer', 'Adagrad') != 'Adam':
         return
-    if models.own_relation_update(models.MODELS[args.model_name]):
+    if models.own_relation_update(models.record(args.model_name)):
         raise KgeError("--optimizer Adam is not available for %s (RESCAL / TransR update their relation-side tables with kernels of "
                        "their own)" % args.model_name)
     if len(args.gpu) > 1:
@@ -983,7 +987,7 @@ def check_norm_constraints(args):
     if args.async_update_rel:
         raise KgeError("%s is not available with --async_update_rel (the one-step-stale pipeline has no launch behind its "
                        "update); plain --async_update runs the strict step and is fine" % flag)
-    m = models.MODELS[args.model_name]
+    m = models.record(args.model_name)
     if rel_norm and m.norm_rel == 0:
         raise KgeError("--rel_norm is not available for %s (%s)" % (m.name, m.no_rel_norm))
 
@@ -1014,7 +1018,7 @@ def check_one_vs_all(args, argv=None):
         return any(a == name or a.startswith(name + '=') for a in argv)
     if kva and getattr(args, 'one_vs_all', False):
         raise KgeError("--k_vs_all cannot be combined with --one_vs_all (one criterion over every entity)")
-    m = models.MODELS[args.model_name]
+    m = models.record(args.model_name)
     if not m.one_vs_all:
         raise KgeError("%s is available for DistMult and ComplEx only (got %s): the other models' scores are no plain "
                        "product with the candidate row" % (flag, args.model_name))
@@ -1048,7 +1052,7 @@ def check_one_vs_all(args, argv=None):
 
 def check_model_widths(model_name, hidden_dim, double_ent, double_rel):
     """the -de / -dr / --hidden_dim rules of the model's record (models.py); the texts are the record's"""
-    m = models.MODELS[model_name]
+    m = models.record(model_name)
     said = dict(de=" -de" if double_ent else " no -de", dr=" -dr" if double_rel else ", no -dr", cdr=", -dr" if double_rel else ", no -dr",
                 x2=" x 2 with -de" if double_ent else "", width=hidden_dim * (2 if double_ent else 1), hidden=hidden_dim)
 
@@ -1070,7 +1074,7 @@ def check_model_widths(model_name, hidden_dim, double_ent, double_rel):
 
 def check_model_flags(args):
     """a model that trains on the strict step of one GPU's tables: refuse what has no such step, before anything is loaded"""
-    m = models.MODELS[args.model_name]
+    m = models.record(args.model_name)
     check_model_widths(args.model_name, args.hidden_dim, args.double_ent, args.double_rel)
     if m.single_gpu_only and len(args.gpu) > 1:
         raise KgeError("%s is not available on more than one GPU (--gpu takes one entry)" % m.name)
@@ -1079,6 +1083,21 @@ def check_model_flags(args):
                        "plain --async_update runs the strict step and is fine" % m.name)
     if m.no_relation_ranking and args.eval_relation:
         raise KgeError("%s has no relation ranking (--eval_relation): %s" % (m.name, m.no_relation_ranking))
+    if m.core_tensor and not (args.one_vs_all or args.k_vs_all):
+        raise KgeError("%s trains on the all-entity steps only: pass --one_vs_all or --k_vs_all (the sampled step has no %s form)"
+                       % (m.name, m.name))
+    check_full_ranking_only(m, args)
+
+
+def check_full_ranking_only(m, args):
+    """dglke_train and dglke_eval: a model whose chunked ranking is closed (TuckER) is ranked against every entity only"""
+    if not m.core_tensor:
+        return
+    for flag, on in (('--eval_candidates', getattr(args, 'eval_candidates', None)), ('--neg_deg_sample_eval', args.neg_deg_sample_eval),
+                     ('--neg_sample_size_eval', getattr(args, 'neg_sample_size_eval', 0) > 0)):
+        if on:
+            raise KgeError("%s is ranked against every entity only: %s is not available (chunked-candidate ranking is closed to it)"
+                           % (m.name, flag))
 
 
 def main(argv=None, before_train=None):

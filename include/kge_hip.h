@@ -109,7 +109,7 @@ enum kge_model {
                           their _known forms, kge_step_optim), ranking, chunked ranking and top-K; kge_step_sharded,
                           kge_step_grads, kge_step_async, kge_step_fused_sampling (with a sampler job), kge_rank_eval_split and
                           kge_rank_rel_eval refuse it before any launch; kge_rank_rel_workspace_bytes answers 0. */
-    KGE_TRANSD    = 14 /* TransD (Ji et al., ACL 2015; not in the reference).  (Ids 9, 11 and 13 are not models: "unknown model".)
+    KGE_TRANSD    = 14,/* TransD (Ji et al., ACL 2015; not in the reference).  (Ids 9, 11 and 13 are not models: "unknown model".)
                           Entity rows [e | e_p] and relation rows [r | r_p] are both d_e == d_r == 2 k floats wide, k % 4 == 0
                           (d_e % 8 == 0: every path is a matrix-core product over the first halves).  The relation's projection of
                           an entity is the rank-one map x_perp = x + (x_p . x) r_p  (M_rx = r_p x_p^T + I, equal widths) and
@@ -146,6 +146,26 @@ enum kge_model {
                           kge_step_sharded, kge_step_grads, kge_step_async, kge_step_fused_sampling (with a sampler job),
                           kge_rank_eval_split and kge_rank_rel_eval refuse it before any launch; kge_rank_rel_workspace_bytes
                           answers 0. */
+    KGE_TUCKER    = 22 /* TuckER (Balazevic et al., EMNLP 2019; not in the reference).  (Ids 15 and 21 are not models, 16 .. 20 are the
+                          similarity functions of kge_topk_select: "unknown model".)  Entity rows [n_ent, d_e], relation rows
+                          [n_rel, d_r] and ONE core tensor W[l][k][m] of d_r x d_e x d_e shared by every edge:
+                            s(h, r, t) = sum_l sum_k sum_m r_l h_k W[l][k][m] t_m          (no gamma, no clamp).
+                          The paper's batch normalisation and dropout are not implemented.  d_e % 4 == 0, 4 <= d_e <= 512, and the
+                          same rule for d_r, each with a text of its own.  The core lives in kge_tables.proj, [d_r * d_e, d_e]: row
+                          l * d_e + k is W[l][k][:]; proj_state is [d_r * d_e], the Adagrad state of those rows (state += mean(g^2),
+                          row -= lr g / (sqrt(state) + eps)).  The regulariser acts on the gathered entity and relation rows, not
+                          on the core.  With x the kept end and y the corrupted side's true end the per-edge operand is
+                            tails corrupted: a_i[m] = sum_{l,k} r_il x_ik W[l][k][m],   heads: a_i[k] = sum_{l,m} r_il x_im W[l][k][m],
+                          p_i = a_i . y_i and s_ij = a_i . e_j: the candidate side is the plain product of DistMult.  Open entries:
+                          kge_step_fused and kge_step_fused_known on a batch with N == 0 (the 1-vs-all softmax and the K-vs-all
+                          BCE; kge_step_workspace_bytes answers for N == 0), where the step first updates every core row once
+                          (every gradient formed from the values before the step), then runs the dense entity trace, the positive
+                          entity trace and the relation trace; and kge_rank_eval_ex with proj = the core (kge_rank_workspace_bytes
+                          unchanged: a in the A entry, at most 1024 / d_e parts of it in the first TransR rows).  Every other entry
+                          that takes a model refuses it before any launch: the sampled step (N > 0) in all its entries,
+                          kge_step_optim, kge_step_phase*, kge_step_sharded, kge_step_grads, kge_step_async,
+                          kge_step_fused_sampling, kge_rank_eval_split, kge_rank_eval_chunked, kge_rank_rel_eval, kge_topk_select*
+                          and the per-op entries; kge_rank_rel_workspace_bytes answers 0. */
 };
 
 /* loss criteria (models/pytorch/loss.py:44-59) */
