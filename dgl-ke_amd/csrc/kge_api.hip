@@ -1420,6 +1420,17 @@ static size_t carve_ova(Carver &cv, OvaBufs &w, const kge_hparams *hp, int B_, i
     return cv.off;
 }
 static bool ova_width_ok(int d_e) { return d_e >= 4 && d_e <= 512 && d_e % 4 == 0; }
+// SimplE on either all-entity step: the criterion's kernels over clamped scores (kge_allent_clamp.hip).  QuatE needs
+// none: its operand is a plain product's, formed from the relation row normalised in edge_fwd's registers, and edge_bwd takes the GA
+// parts back through that normalisation (kge_rowwise.hip) - the strict step's two edge kernels as they are
+static bool clamped_scores(int model) { return clamp_of(model) > 0.f; }
+static AceArgs ace_of(const OvaArgs &o) {
+    AceArgs c{};
+    c.k.B = o.B; c.k.d = o.d; c.k.n_ent = o.n_ent; c.k.g = o.g; c.k.A = o.A; c.k.ent = o.ent; c.k.ent_state = o.ent_state; c.k.w = o.w;
+    c.k.coef = o.coef; c.k.dpos = o.dpos; c.k.row_pos = o.row_pos; c.k.row_neg = o.row_neg; c.k.acc = o.acc; c.k.GAp = o.GAp;
+    c.k.lr = o.lr; c.k.eps = o.eps; c.part = o.part; c.pos = o.pos; c.lse = o.lse;
+    return c;
+}
 
 // K-vs-all (kge_step_fused_known on N == 0, KGE_LOSS_BCE): behind the 1-vs-all layout the rows' list ranges, own ends and loss parts
 struct KvaBufs { int64_t *rng, *own; float *lpart; };
@@ -1479,7 +1490,7 @@ static int step_one_vs_all(const kge_hparams *hp, const kge_tables *tb, const kg
     const kge::ModelRow *mr = kge::model_row(hp->model);
     if (!mr) return fail(KGE_ERR_ARG, "unknown model %d", hp->model);
     if (mr->closed & kge::E_STEP_ONE_VS_ALL)
-        return fail(KGE_ERR_ARG, "%s: not available for %s (DistMult and ComplEx only: the other models' scores are no plain product a . e)", who, mr->name);
+        return fail(KGE_ERR_ARG, "%s: not available for %s (DistMult and ComplEx only, with SimplE, QuatE and TuckER: the other models' scores are no plain product a . e)", who, mr->name);
     if (int rc = check_model(hp->model, hp->d_e, hp->d_r)) return rc;
     if (hp->loss_genre != KGE_LOSS_SOFTMAX) return fail(KGE_ERR_ARG, "%s: loss_genre must be KGE_LOSS_SOFTMAX (got %d)", who, hp->loss_genre);
     if (hp->adv) return fail(KGE_ERR_ARG, "%s: adv must be 0 (the softmax is the weighting)", who);
@@ -1526,9 +1537,18 @@ static int step_one_vs_all(const kge_hparams *hp, const kge_tables *tb, const kg
     oa.A = w.A; oa.ent = tb->ent; oa.ent_state = tb->ent_state; oa.part = w.part; oa.pos = P; oa.w = b->edge_w;
     oa.lse = w.lse; oa.coef = w.coef; oa.dpos = w.dP; oa.row_pos = want4 ? w.row_pos : nullptr; oa.row_neg = want4 ? w.row_neg : nullptr;
     oa.acc = acc; oa.GAp = w.GAp; oa.lr = hp->lr; oa.eps = hp->eps;
-    KGE_TRY(launch_ova_fwd(oa, s));
-    KGE_TRY(launch_ova_lse(oa, s));
-    KGE_TRY(launch_ova_bwd_a(oa, s));
+    const bool clamped = clamped_scores(hp->model);
+    AceArgs ca{};
+    if (clamped) {
+        ca = ace_of(oa);
+        KGE_TRY(launch_ace_fwd(ca, s));
+        KGE_TRY(launch_ace_lse(ca, s));                   // (dL/dp = 0 where the positive is saturated)
+        KGE_TRY(launch_ace_bwd_a(ca, false, s));
+    } else {
+        KGE_TRY(launch_ova_fwd(oa, s));
+        KGE_TRY(launch_ova_lse(oa, s));
+        KGE_TRY(launch_ova_bwd_a(oa, s));
+    }
     // per-edge h / t / r gradient rows from dpos and the GA parts, read from the rows as they are BEFORE the dense trace
     EdgeBwdArgs eb;
     fill_edge_bwd(eb, src, hp->model, B, d_e, d_r, b->neg_head, hp->gamma, rot_div, w.dP, w.GAp);
@@ -1536,7 +1556,8 @@ static int step_one_vs_all(const kge_hparams *hp, const kge_tables *tb, const kg
     eb.GH = w.GH; eb.GT = w.GT; eb.GR = GR; eb.ga_parts = oa.g.Sa; eb.ga_stride = (int64_t)B * d_e;
     if (tk) { if (int rc = tk_backward(ta, hp, tb, w, tkb, w.GAp, oa.g.Sa, GR, reg, s)) return rc; }
     else KGE_TRY(launch_edge_bwd(eb, s));
-    KGE_TRY(launch_ova_bwd_e(oa, s));                 // the dense trace: every entity row and its state
+    if (clamped) KGE_TRY(launch_ace_bwd_e(ca, false, s));
+    else KGE_TRY(launch_ova_bwd_e(oa, s));            // the dense trace: every entity row and its state
     // the update launch, on a plan without negative entries (no record has a negative list: GN is never read; a valid pointer all the same)
     UpdateArgs ua{};
     ua.model_d_e = d_e; ua.d_r = d_r; ua.reg_norm = hp->reg_norm; ua.UE = b->UE; ua.UR = b->UR;
@@ -1568,7 +1589,7 @@ static int step_k_vs_all(const kge_hparams *hp, const kge_tables *tb, const kge_
     if (!mr) return fail(KGE_ERR_ARG, "unknown model %d", hp->model);
     if (job) return fail(KGE_ERR_ARG, "%s: a sampler job is not available here (there are no sampled negatives: job must be NULL)", who);
     if (mr->closed & kge::E_STEP_ONE_VS_ALL)
-        return fail(KGE_ERR_ARG, "%s: not available for %s (DistMult and ComplEx only: the other models' scores are no plain product a . e)", who, mr->name);
+        return fail(KGE_ERR_ARG, "%s: not available for %s (DistMult and ComplEx only, with SimplE, QuatE and TuckER: the other models' scores are no plain product a . e)", who, mr->name);
     if (int rc = check_model(hp->model, hp->d_e, hp->d_r)) return rc;
     if (hp->loss_genre == KGE_LOSS_SOFTMAX)
         return fail(KGE_ERR_ARG, "%s: KGE_LOSS_SOFTMAX with a known index is not built (known answers left out of the softmax row); "
@@ -1627,8 +1648,12 @@ static int step_k_vs_all(const kge_hparams *hp, const kge_tables *tb, const kge_
     ka.rng = kb.rng; ka.own = kb.own; ka.coef = w.coef; ka.dpos = w.dP; ka.lpart = kb.lpart;
     ka.row_pos = want4 ? w.row_pos : nullptr; ka.row_neg = want4 ? w.row_neg : nullptr;
     ka.acc = acc; ka.GAp = w.GAp; ka.lr = hp->lr; ka.eps = hp->eps;
+    const bool clamped = clamped_scores(hp->model);
+    AceArgs ca{};
+    if (clamped) ca.k = ka;
     KGE_TRY(launch_kva_prep(ka, s));
-    KGE_TRY(launch_kva_bwd_a(ka, s));                 // dL/da in parts and the loss parts: four matrix products in the step, no forward
+    if (clamped) KGE_TRY(launch_ace_bwd_a(ca, true, s));
+    else KGE_TRY(launch_kva_bwd_a(ka, s));            // dL/da in parts and the loss parts: four matrix products in the step, no forward
     KGE_TRY(launch_kva_loss(ka, s));
     // per-edge h / t / r gradient rows from the GA parts (dL/dp = 0), read from the rows as they are BEFORE the dense trace
     EdgeBwdArgs eb;
@@ -1637,7 +1662,8 @@ static int step_k_vs_all(const kge_hparams *hp, const kge_tables *tb, const kge_
     eb.GH = w.GH; eb.GT = w.GT; eb.GR = GR; eb.ga_parts = ka.g.Sa; eb.ga_stride = (int64_t)B * d_e;
     if (tk) { if (int rc = tk_backward(ta, hp, tb, w, tkb, w.GAp, ka.g.Sa, GR, reg, s)) return rc; }
     else KGE_TRY(launch_edge_bwd(eb, s));
-    KGE_TRY(launch_kva_bwd_e(ka, s));                 // the dense trace: every entity row and its state
+    if (clamped) KGE_TRY(launch_ace_bwd_e(ca, true, s));
+    else KGE_TRY(launch_kva_bwd_e(ka, s));            // the dense trace: every entity row and its state
     // the update launch, on a plan without negative entries (as in the 1-vs-all step)
     UpdateArgs ua{};
     ua.model_d_e = d_e; ua.d_r = d_r; ua.reg_norm = hp->reg_norm; ua.UE = b->UE; ua.UR = b->UR;

@@ -996,3 +996,17 @@ int launch_kva_prep(const KvaArgs &a, hipStream_t s);
 int launch_kva_bwd_a(const KvaArgs &a, hipStream_t s);
 int launch_kva_loss(const KvaArgs &a, hipStream_t s);
 int launch_kva_bwd_e(const KvaArgs &a, hipStream_t s);
+// ---- the all-entity criteria over CLAMPED scores (kge_allent_clamp.hip; SimplE on either N == 0 step) ----
+// s_ij = clamp(a_i . e_j, -KGE_SIMPLE_CLAMP, KGE_SIMPLE_CLAMP), no gradient where the raw product is saturated.  One argument block for
+// both criteria: the K-vs-all step's (the geometry, the table, the operands, the coefficient and GA buffers; its list fields are unread
+// by the softmax instances) and the softmax's three arrays.  The bound is a compile-time constant of the kernels.
+struct AceArgs {
+    KvaArgs k;
+    float *part;                     // [S, B, 2] softmax forward: (max, sum-exp) of row i over split s
+    const float *pos;                // [B] positive scores, clamped by edge_fwd
+    float *lse;                      // [B] log-sum-exp
+};
+int launch_ace_fwd(const AceArgs &a, hipStream_t s);                 // softmax: the running (max, sum-exp) pairs
+int launch_ace_lse(const AceArgs &a, hipStream_t s);                 // softmax: lse, loss, coef, dL/dp masked where p is saturated
+int launch_ace_bwd_a(const AceArgs &a, bool bce, hipStream_t s);     // GA parts (bce: and the loss parts)
+int launch_ace_bwd_e(const AceArgs &a, bool bce, hipStream_t s);     // the dense trace: every entity row and its state

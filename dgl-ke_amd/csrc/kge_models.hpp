@@ -36,7 +36,7 @@ struct ModelRow {
 };
 
 inline const ModelRow *model_row(int id) {
-    // E_STEP_ONE_VS_ALL (kge_step_fused on a batch with N == 0): open to DistMult and ComplEx alone - the entry has its own text for the others
+    // E_STEP_ONE_VS_ALL (kge_step_fused on a batch with N == 0): open to DistMult, ComplEx, SimplE (clamped scores), QuatE and TuckER - the entry has its own text for the others
     static const unsigned OVA = E_STEP_ONE_VS_ALL;
     static const unsigned LOCAL = E_STEP_ASYNC | E_STEP_SHARDED | E_STEP_GRADS | E_RANK_EVAL_SPLIT;
     static const unsigned OWN_FWD = LOCAL | E_STEP_FUSED_SAMPLING | E_RANK_REL_EVAL;
@@ -49,13 +49,13 @@ inline const ModelRow *model_row(int id) {
         {KGE_DISTMULT, "DistMult", 1, 0, REL_SAME, true, "TransE/DistMult needs d_r == d_e (got %d, %d)", nullptr, 0, nullptr, true, 1, 1, 0, false, {1, 1, 0, nullptr}},
         {KGE_COMPLEX, "ComplEx", 2, 0, REL_SAME, true, "ComplEx needs even d_e and d_r == d_e (got %d, %d)", nullptr, 0, nullptr, true, 1, 1, 0, false, {1, 1, 0, nullptr}},
         {KGE_ROTATE, "RotatE", 2, 0, REL_HALF, true, "RotatE needs d_r == d_e/2 (got d_e=%d d_r=%d)", nullptr, OVA, nullptr, true, 1, 1, 0, false, {1, 0, 0, PHASES}},
-        {KGE_SIMPLE, "SimplE", 2, 0, REL_SAME, true, "SimplE needs even d_e and d_r == d_e (got %d, %d)", nullptr, OVA, nullptr, true, 1, 1, 0, false, {1, 1, 0, nullptr}},
+        {KGE_SIMPLE, "SimplE", 2, 0, REL_SAME, true, "SimplE needs even d_e and d_r == d_e (got %d, %d)", nullptr, 0, nullptr, true, 1, 1, 0, false, {1, 1, 0, nullptr}},
         {KGE_RESCAL, "RESCAL", 1, 1024, REL_SQUARE, false, "RESCAL needs d_r == d_e*d_e and d_e <= 1024 (got d_e=%d d_r=%d)", nullptr, OVA, nullptr,
          true, 1, 1, 0, false, {1, 0, 0, OWN_REL}},
         {KGE_TRANSR, "TransR", 1, 0, REL_UPTO_1024, false, "TransR needs 0 < d_r <= 1024 (got d_e=%d d_r=%d)", nullptr, E_MODULAR | E_TOPK | OVA, nullptr,
          true, 1, 1, 0, false, {1, 0, 0, OWN_REL}},
         // ids up to KGE_TRANSR only: a QuatE call takes the DistMult layout followed by the normalised relation table (include/kge_hip.h)
-        {KGE_QUATE, "QuatE", 4, 0, REL_SAME, false, "QuatE needs d_e a positive multiple of 4 and d_r == d_e (got %d, %d)", nullptr, LOCAL | OVA,
+        {KGE_QUATE, "QuatE", 4, 0, REL_SAME, false, "QuatE needs d_e a positive multiple of 4 and d_r == d_e (got %d, %d)", nullptr, LOCAL,
          "strict step on local tables, single-table ranking", false, 1, 1, 0, false, {1, 1, 0, nullptr}},
         // no relation ranking: the score is not a product of a query row and the relation row
         {KGE_PAIRRE, "PairRE", 1, 0, REL_DOUBLE, false, "PairRE needs d_e > 0 and d_r == 2 * d_e, r = [rH | rT] (got %d, %d)", nullptr, OWN_FWD | OVA,

@@ -201,7 +201,7 @@ class StepEngine(object):
         """what the two all-entity steps (one_vs_all, k_vs_all) refuse alike; each names itself"""
         mode = 'k_vs_all' if self.k_vs_all else 'one_vs_all'
         if not (m and m.one_vs_all):
-            raise _lib.KgeError("%s: DistMult and ComplEx only (got %s)" % (mode, self.model_name))
+            raise _lib.KgeError("%s: DistMult and ComplEx only, with SimplE, QuatE and TuckER (got %s)" % (mode, self.model_name))
         if self.one_vs_all and loss_genre != 'Softmax':
             raise _lib.KgeError("one_vs_all: the loss is the softmax over every entity: loss_genre must be 'Softmax' (got %r)" % (loss_genre,))
         if self.k_vs_all and loss_genre != 'BCE':

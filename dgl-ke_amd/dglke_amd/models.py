@@ -23,7 +23,7 @@ Model = namedtuple('Model', [
     'norm_ent', 'norm_rel',        # --ent_norm / --rel_norm: equal slices of an entity / relation row, each projected on its own (norm_rel 0: refused)
     'norm_rel_unit',               # ... bit k: relation slice k is normalised to length 1 under either relation mode (TransH's w)
     'no_rel_norm',                 # ... None, or why --rel_norm does not apply
-    'one_vs_all',                  # --one_vs_all / --k_vs_all and the engine's modes of those names: the score is a plain product a . e (DistMult, ComplEx)
+    'one_vs_all',                  # --one_vs_all / --k_vs_all and the engine's modes of those names: the score is a plain product a . e, clamped or not (DistMult, ComplEx, SimplE, QuatE)
     'projection', 'relation_matrix', 'alias_of',      # TransR's third table; RESCAL's relation rows are matrices; TransE is TransE_l2
     'core_tensor'])                # TuckER: the third table is ONE core tensor [d_r * d_e, d_e]; d_r is free within the all-entity width rule
 
@@ -51,7 +51,7 @@ MODELS = OrderedDict((m.name, m) for m in (       # in the order of the --model_
     _model('DistMult', 2, 'DistMultScore', one_vs_all=True),
     _model('ComplEx', 3, 'ComplExScore', one_vs_all=True),
     _model('RotatE', 4, 'RotatEScore', ('gamma', 'emb_init'), norm_rel=0, no_rel_norm="the row holds phases"),
-    _model('SimplE', 5, 'SimplEScore'),
+    _model('SimplE', 5, 'SimplEScore', one_vs_all=True),
     _model('QuatE', 8, 'QuatEScore', ent_multiple=4, rel_width=lambda d_e: d_e, de='tied', dr='tied',
            flags_text="QuatE: the relation width must equal the entity width: pass -dr together with -de (and neither alone)",
            cli_multiple=4, cli_of='width', multiple_first=True,
@@ -59,7 +59,7 @@ MODELS = OrderedDict((m.name, m) for m in (       # in the order of the --model_
            kemodel_text="QuatE needs an entity width that is a multiple of 4 and relation_dim == entity_dim (got %d, %d)",
            engine_text="QuatE needs an entity width that is a multiple of 4 and relation width == entity width (got %d, %d)",
            loaded_text="QuatE: rows of %d (entity) and %d (relation) values: the width must be a multiple of 4 and the same for both",
-           rank_rel_as='DistMult', **_LOCAL),
+           rank_rel_as='DistMult', one_vs_all=True, **_LOCAL),
     _model('PairRE', 10, 'PairREScore', ('gamma',), ent_multiple=1, rel_width=lambda d_e: 2 * d_e, de=False, dr=True,
            flags_text="PairRE: the relation row [rH | rT] is twice as wide as the entity row: pass -dr without -de (got%(de)s%(dr)s)",
            kemodel_text="PairRE needs relation_dim == 2 * entity_dim, r = [rH | rT] (got %d, %d)",

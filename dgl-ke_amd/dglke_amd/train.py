@@ -130,7 +130,7 @@ class ArgParser(argparse.ArgumentParser):
         a('--one_vs_all', action='store_true',
           help='1-vs-all softmax (a flag of this build): every positive is scored against EVERY entity of the table instead of sampled '
                'negatives (the loss LibKGE / PyKEEN / Lacroix et al. use for DistMult and ComplEx); implies --loss_genre Softmax, '
-               '--neg_sample_size is ignored.  DistMult / ComplEx, Adagrad, one GPU, one trainer, entity width a multiple of 4 up to '
+               '--neg_sample_size is ignored.  DistMult / ComplEx / SimplE / QuatE / TuckER, Adagrad, one GPU, one trainer, entity width a multiple of 4 up to '
                '512; batches come from the host sampler.')
         a('--k_vs_all', action='store_true',
           help='K-vs-all (a flag of this build; ConvE\'s training mode, LibKGE\'s KvsAll): binary cross-entropy of every positive\'s '
@@ -1020,7 +1020,7 @@ def check_one_vs_all(args, argv=None):
         raise KgeError("--k_vs_all cannot be combined with --one_vs_all (one criterion over every entity)")
     m = models.record(args.model_name)
     if not m.one_vs_all:
-        raise KgeError("%s is available for DistMult and ComplEx only (got %s): the other models' scores are no plain "
+        raise KgeError("%s is available for DistMult and ComplEx only, with SimplE, QuatE and TuckER (got %s): the other models' scores are no plain "
                        "product with the candidate row" % (flag, args.model_name))
     if given('--loss_genre') and args.loss_genre != genre:
         raise KgeError("%s is the %s over every entity: --loss_genre %s cannot be combined with it"

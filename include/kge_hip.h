@@ -461,7 +461,13 @@ size_t kge_step_workspace_bytes(const kge_hparams *hp, int B, int C, int chunk, 
 int kge_step_fused(const kge_hparams *hp, const kge_tables *tb, const kge_batch *b,
                    const kge_step_out *out, void *ws, size_t ws_bytes, void *stream);
 /* ---- 1-vs-all softmax: kge_step_fused on a batch with N == 0 - no sampled negatives: EVERY entity of the table is a candidate of
- * every edge (csrc/kge_onevsall.hip).  DistMult and ComplEx, Adagrad, local tables.  The batch has no neg_ids and every
+ * every edge (csrc/kge_onevsall.hip).  DistMult, ComplEx, SimplE, QuatE and TuckER; Adagrad, local tables.
+ * KGE_SIMPLE (csrc/kge_allent_clamp.hip): a = 1/2 [r_inv . x_j | r . x_i] for tails, 1/2 [r . x_j | r_inv . x_i] for
+ *   heads; s_ij = clamp(a_i . e_j, -20, 20) and p_i likewise, in this mode and the K-vs-all one below; dL/d(a_i . e_j) = dL/ds_ij where
+ *   |a_i . e_j| < 20 and 0 elsewhere, the same for p_i - the sampled step's convention (a product exactly on the bound passes nothing).
+ * KGE_QUATE: a = x (x) r^ for tails, x (x) conj(r^) for heads, r^ the relation row normalised per quaternion inside the edge kernels
+ *   (no normalised table is kept); the relation gradient goes back through the normalisation, (g - r^ <r^, g>) / |r|.
+ * The batch has no neg_ids and every
  * ue_neg list is empty; C / chunk as built, C * chunk == B; one corruption side per batch (neg_head).  With w_i = edge_w[i] (per edge) or 1:
  *   a_i   = the per-edge operand edge_fwd builds for the sampled step (DistMult x . r; ComplEx the complex product, conjugated for
  *           heads), x = the kept end;   s_ij = a_i . e_j for every j in [0, n_ent), the true end included
@@ -479,7 +485,7 @@ int kge_step_fused(const kge_hparams *hp, const kge_tables *tb, const kge_batch 
  * for KGE_LOSS_SOFTMAX; pos_score, g_pos_ent, g_rel as without the flag.  The workspace contract holds: kge_step_workspace_bytes
  * answers for N == 0 from (hp, B, UE, UR) - C and chunk are not read, the table's size does not enter (0: bad arguments).
  * A mode of kge_step_fused and not an entry of its own: the stream and workspace conventions of that entry are its conventions.
- * KGE_ERR_ARG before any launch, the message naming the condition: a model other than DistMult / ComplEx; loss_genre other than
+ * KGE_ERR_ARG before any launch, the message naming the condition: a model other than those five; loss_genre other than
  * KGE_LOSS_SOFTMAX; adv; pairwise; d_e outside d_e % 4 == 0, 4 <= d_e <= 512; any KGE_FLAG_*_NORM_* bit or
  * KGE_FLAG_NEG_DEG_SAMPLE; kge_step_out.neg_score or g_neg (they do not exist).  Every other step entry refuses a batch with N == 0 as
  * before (kge_step_phase, kge_step_fused_sampling, kge_step_fused_known, kge_step_optim, kge_step_async, kge_step_grads,
